@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- the reference's headline benchmark on MI355X (BASELINE.json configs[1] at N=1).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps, writes the last timed step's outputs if --dump-outputs is given, and
+prints the result line.  --full adds everything else the benchmark measures: the CPU baseline legs (launcher, N == 1) and, after
+the timed region, the informational legs of run_extras (five phases of both tables, host-inclusive, W1, second batch, configs[2]).
 
 Launch model.  Run plainly (no WORLD_SIZE in the environment) this process is the LAUNCHER: it never touches a GPU; it
 checks that N devices are visible (exit 2 otherwise -- never a silent fall-back to fewer ranks), runs the CPU baseline
-legs (N == 1 only), then starts N fresh rank processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 /
+legs (--full, N == 1 only), then starts N fresh rank processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 /
 MASTER_PORT set, one per device), relays rank 0's JSON line and propagates the first non-zero exit code.  Run under
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (WORLD_SIZE set) the process IS a rank and
 WORLD_SIZE must equal --gpus.  The reference's own multi-rank driver is started by mpirun and partitions by comm.size()
@@ -24,7 +28,11 @@ piece i overlaps the radix partition of piece i-1); finds travel the same way an
 
 Rank 0 prints ONE JSON line: metric/value = whole-job k-mer operations (inserts + finds) per second, the two individual
 rates, `roofline` (SURVEY 8d: achieved = ops/s x algorithmic bytes/op over 8 TB/s: `frac` = the insert path, inserts/s x 50 B;
-the find path, finds/s x 41 B, and the lower of the two are reported next to it) and, at N == 1, `cpu_baseline` (the oracle port and the compiled reference LP table on a bounded sample).
+the find path, finds/s x 41 B, and the lower of the two are reported next to it) and, with --full at N == 1, `cpu_baseline` (the oracle port and the compiled reference LP table on a bounded sample).
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step returned to its caller as float64 .npy files
+(64-bit keys as two exact 32-bit halves; outputs of more than DUMP_ROWS rows cut to a fixed, seeded sample of rows, at most 40 MB
+in all).  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -51,6 +59,7 @@ QUERIES_PER_GPU = 10_000_000
 B_INSERT_NEW, B_INSERT_DUP, B_FIND_HIT, B_FIND_MISS = 50, 33, 41, 9
 B_INSERT_SECTOR, B_FIND_SECTOR = 16 + 3 * 64, 8 + 2 * 64 + 16
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8 TB/s spec (6.29 TB/s measured float4 copy)
+DUMP_ROWS, DUMP_SEED = 1 << 20, 20261016      # --dump-outputs: rows kept of a longer output, seed of the row sample
 
 
 def gen_inputs(rank, n, nq, workload="w2"):
@@ -391,6 +400,38 @@ def run_extras(args, dev, keys, vals, q, dk, dv, dq):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------------------------
+def dump_outputs(path, counts, rows):
+    """writes counts (scalars) as counts.npy and each per-row output of `rows` (equal-length device tensors: int64 = 64-bit keys,
+    int32 = 32-bit values, bool / uint8 = flags) as <name>.npy, float64 throughout; an int64 column becomes <name>_hi / <name>_lo
+    (the two 32-bit halves, exact in float64).  More than DUMP_ROWS rows: the same seeded sample of rows for every column, whose
+    row numbers are rows.npy."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    files = {"counts": np.array(counts, dtype=np.float64)}
+    n = next(iter(rows.values())).numel()
+    idx = np.arange(n, dtype=np.int64)
+    if n > DUMP_ROWS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+    files["rows"] = idx.astype(np.float64)
+    for name, t in rows.items():
+        assert t.numel() == n, (name, t.numel(), n)
+        a = t[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+        if a.dtype == np.int64:
+            u = a.view(np.uint64)
+            files[name + "_hi"] = (u >> np.uint64(32)).astype(np.float64)
+            files[name + "_lo"] = (u & np.uint64(0xFFFFFFFF)).astype(np.float64)
+        elif a.dtype == np.int32:
+            files[name] = a.view(np.uint32).astype(np.float64)
+        else:
+            files[name] = a.astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(files)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # launcher
 # ---------------------------------------------------------------------------------------------------------------------
 def _free_port():
@@ -433,7 +474,7 @@ def launch(args, argv):
               file=sys.stderr, flush=True)
         return 2
     cpu = None
-    if n == 1 and not args.no_cpu_baseline:
+    if args.full and n == 1 and not args.no_cpu_baseline:
         keys, vals, q = gen_inputs(0, args.keys, args.queries, args.workload)
         cpu = cpu_baseline(keys, vals, q)
         del keys, vals, q
@@ -534,8 +575,9 @@ def run_rank(args):
 
     prof, phases = {}, {}
     ins_ms, find_ms = [], []
+    last = {}                              # --dump-outputs: what the last timed step returned to its caller
 
-    def one_step(timed):
+    def one_step(timed, keep=False):
         if distributed:
             be = khd.GpuBackend(local_rank, "rh", 128, 0.35, 0.8, args.hash, 43)
             t = khd.ShardedTable(be, timing=timed)
@@ -553,12 +595,16 @@ def run_rank(args):
             n_ins = table.insert(dk, dv)
         e1.record()
         if distributed:
-            _, fvals, ffound = t.find(dq)
+            fkeys, fvals, ffound = t.find(dq)
             t.synchronize()                        # (find only queues its work; this also raises if any rank's local part failed)
             n_hit = int(ffound.sum().item())
+            if keep:
+                last["rows"] = {"find_keys": fkeys, "find_values": fvals, "find_found": ffound}
         else:
             fk, fv = table.find(dq)
             n_hit = fk.numel()
+            if keep:
+                last["rows"] = {"find_keys": fk, "find_values": fv}
         e2.record()
         torch.cuda.synchronize()
         if timed:
@@ -580,8 +626,8 @@ def run_rank(args):
     barrier()
     t0 = time.perf_counter()
     state = None
-    for _ in range(args.steps):
-        state = one_step(True)
+    for i in range(args.steps):
+        state = one_step(True, keep=args.dump_outputs is not None and i == args.steps - 1)
     barrier()
     elapsed = time.perf_counter() - t0
     if distributed:
@@ -607,8 +653,14 @@ def run_rank(args):
         assert g_ins == n_distinct and g_size == n_distinct, (g_ins, n_distinct)
     assert g_hit == args.queries * world, (g_hit, args.queries * world)
 
+    if args.dump_outputs is not None and rank == 0:
+        # counts: inserted, found (whole job), size (whole job), capacity of this rank's table
+        names = dump_outputs(args.dump_outputs, [g_ins, g_hit, g_size, state[3]], last.pop("rows"))
+        print("[bench] outputs of the last timed step written to %s: %s" % (args.dump_outputs, ", ".join(names)), file=sys.stderr, flush=True)
+    last.clear()
+
     extras = None
-    if not distributed and not args.no_extras and args.workload == "w2":
+    if args.full and not distributed and not args.no_extras and args.workload == "w2":
         try:            # informational legs: a failure here must not take the headline measurement (already complete) with it
             extras = run_extras(args, dev, keys, vals, q, dk, dv, dq)
         except Exception as e:
@@ -710,8 +762,13 @@ def parse(argv):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--keys", type=int, default=0, help="keys per GPU (0 = 107374184 at N=1: load exactly 0.800; 10^8 per rank at N>1)")
     ap.add_argument("--queries", type=int, default=QUERIES_PER_GPU)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="N == 1: skip the informational legs (five phases for both tables, host-inclusive, W1, second batch, configs[2])")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline legs (N == 1) and the informational legs "
+                         "after the timed region (N == 1, w2)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float64; longer outputs as a fixed, seeded row sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, N == 1: skip the informational legs (five phases for both tables, host-inclusive, W1, second batch, configs[2])")
     ap.add_argument("--workload", default="w2", choices=["w2", "w1"],
                     help="w2 = configs[1] (default, the metric's workload); w1 = benchmark_hashtables shape (x5.5 multiplicity), informational")
     ap.add_argument("--hash", default="murmur3avx64", choices=["murmur3avx64", "murmur", "farm", "identity"],
@@ -722,6 +779,8 @@ def parse(argv):
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.keys <= 0:
         args.keys = KEYS_LOAD_080 if args.gpus == 1 else KEYS_PER_GPU_DIST
     return args

@@ -9,7 +9,7 @@ TAG=${1:-r3}
 OUT=gpurun_out
 mkdir -p $OUT
 timeout -k 10 900 python3 -m pytest tests -m gpu -x -q > $OUT/gputest_$TAG.log 2>&1 && \
-timeout -k 10 400 python3 bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err && \
+timeout -k 10 400 python3 bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err && \
 { timeout -k 10 120 python3 bench.py --gpus 2 --no-cpu-baseline > $OUT/bench2_$TAG.json 2> $OUT/bench2_$TAG.err; echo "gpus2 rc=$?" > $OUT/bench2_$TAG.rc; } && \
 KH_DIST_FORCE_COLLECTIVES=1 timeout -k 10 300 python3 bench.py --no-cpu-baseline --chunks 4 --keys 100000000 > $OUT/bench_fd_$TAG.json 2> $OUT/bench_fd_$TAG.err
 rc=$?

@@ -5,7 +5,7 @@ OUT=gpurun_out; mkdir -p $OUT
 timeout -k 10 900 python3 -m pytest tests -m gpu -x -q -k "$KEXPR" > $OUT/gputest_$TAG.log 2>&1 && \
 timeout -k 10 300 python3 scripts/midsize_timing.py > $OUT/midsize_$TAG.log 2>&1 && \
 timeout -k 10 400 python3 scripts/phase_timing.py > $OUT/phases_$TAG.log 2>&1 && \
-timeout -k 10 400 python3 bench.py --no-cpu-baseline > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+timeout -k 10 400 python3 bench.py --full --no-cpu-baseline > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 rc=$?
 tail -25 $OUT/gputest_$TAG.log; cat $OUT/midsize_$TAG.log; cat $OUT/phases_$TAG.log; python3 -c "
 import json,sys

@@ -14,7 +14,7 @@ pass() {
   local WANT=""
   for c in "$@"; do if grep -q "$c" $OUT/pmc_list_$TAG.txt; then WANT="$WANT $c"; fi; done
   echo "pass $name:$WANT"
-  timeout -k 10 300 rocprofv3 --pmc $WANT --output-format csv -d $OUT/sq_${name}_$TAG -- python3 $ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline > $OUT/sq_${name}_$TAG.log 2>&1 || echo "pass $name failed"
+  timeout -k 10 300 rocprofv3 --pmc $WANT --output-format csv -d $OUT/sq_${name}_$TAG -- python3 $ROOT/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline > $OUT/sq_${name}_$TAG.log 2>&1 || echo "pass $name failed"
 }
 pass a SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS && \
 pass b SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_WAVES SQ_BUSY_CYCLES

@@ -13,6 +13,11 @@
 
   ops_ref_<name>.npz    single-key insert / update / single-key erase / a counting insert through the REAL reference LP table's members:
                     kind-independent map results, which the Robin Hood table (GPU and oracle) must reproduce as well.
+  lp_opseq_ref.npz  the REAL reference LP table through the random operation sequences of tests/test_oracle_vs_ref.py (per step:
+                    results, size, capacity, load thresholds; digests of info, occupied slots and query outputs) and its
+                    occupancy for the W1 streams of that file's Robin Hood comparison.
+  hll_ref_updates.npz   registers / estimates of the REAL reference hyperloglog64 after the random batches of
+                    tests/test_hll_io.py::test_oracle_hll_vs_reference_library.
 
 Fixtures are data only (inputs + expected outputs); no reference source is stored.
 """
@@ -162,6 +167,31 @@ def hll_and_io():
     O.ref_serialize_u64(keys[:500], os.path.join(HERE, "io_ref_keys.bin"))
 
 
+def lp_opseq():
+    """lp_opseq_ref.npz: what test_oracle_vs_ref.py holds the oracle's LP restatement to, recorded from the reference LP table
+    by that file's own drivers"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle_vs_ref as T
+    out = {}
+    for seed in T.SEEDS:
+        for hid in T.HIDS:
+            out["nums_%d_%d" % (seed, hid)], out["digests_%d_%d" % (seed, hid)] = T.lp_op_trace(
+                lambda: O.RefLPTable(128, 0.35, 0.8, hid, 43), seed, hid)
+    for n in T.SIZES:
+        ins, cap, bits, items = T.lp_occupancy(O, n)
+        out["occ_inserted_%d" % n], out["occ_capacity_%d" % n] = np.uint64(ins), np.uint64(cap)
+        out["occ_bits_%d" % n], out["occ_items_%d" % n] = bits, np.array(items)
+    np.savez_compressed(os.path.join(HERE, "lp_opseq_ref.npz"), **out)
+
+
+def hll_updates():
+    """hll_ref_updates.npz: the reference hyperloglog64 through test_hll_io.py's random batches"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_hll_io as T
+    regs, est = T.hll_update_trace(lambda ign: O.RefHLL(ign, 1, 43))
+    np.savez_compressed(os.path.join(HERE, "hll_ref_updates.npz"), regs=regs, est=est)
+
+
 if __name__ == "__main__":
     O.build(("all", "ref", "smhasher"))
     murmur_kat()
@@ -174,4 +204,6 @@ if __name__ == "__main__":
     ops_scenario("murmur_4k", 4000, 29, O.HASH_MURMUR3_X86)
     ops_scenario("farm_4k", 4000, 31, O.HASH_FARM)
     hll_and_io()
+    lp_opseq()
+    hll_updates()
     print("golden fixtures written to", HERE)

@@ -82,3 +82,57 @@ def test_bench_generators_and_host_cores_on_cpu():
     assert hc["logical"] >= 1 and hc["affinity"] >= 1 and (hc["physical"] is None or 1 <= hc["physical"] <= hc["logical"])
     s = bench._stat([1.0, 3.0, 2.0], 1_000_000, 50)
     assert s["ms_median"] == 2.0 and s["ms_min"] == 1.0 and abs(s["ops_per_s"] - 5e8) < 1 and abs(s["frac"] - 5e8 * 50 / 8e12) < 1e-12
+
+
+def test_plain_and_full_options():
+    a = bench.parse(["--steps", "3", "--warmup", "0"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (3, 0, False, None)
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full and bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        r = _run(bad)
+        assert r.returncode == 2 and r.stdout.strip() == "", (bad, r.stderr[-500:])
+
+
+def test_dump_outputs_format(tmp_path, monkeypatch):
+    """--dump-outputs on CPU tensors: float64 files only, 64-bit keys split into exact halves, 32-bit values unsigned, a longer
+    output cut to the same seeded, sorted row sample in every run"""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_ROWS", 1000)
+    keys = np.array([0, 1, 0xFFFFFFFFFFFFFFFF, 1 << 63, 0x0123456789ABCDEF] * 1000, dtype=np.uint64)
+    vals = np.arange(len(keys), dtype=np.uint32) + np.uint32(0xFFFF0000)
+    rows = {"find_keys": torch.from_numpy(keys.view(np.int64)), "find_values": torch.from_numpy(vals.view(np.int32))}
+    d1, d2 = str(tmp_path / "a"), str(tmp_path / "b")
+    names = bench.dump_outputs(d1, [5000, 5000, 7, 128], rows)
+    assert bench.dump_outputs(d2, [5000, 5000, 7, 128], rows) == names == ["counts", "find_keys_hi", "find_keys_lo", "find_values", "rows"]
+    got = {n: np.load(os.path.join(d1, n + ".npy")) for n in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert all(np.array_equal(a, np.load(os.path.join(d2, n + ".npy"))) for n, a in got.items())
+    r = got["rows"].astype(np.int64)
+    assert len(r) == 1000 and np.all(np.diff(r) > 0) and r[0] >= 0 and r[-1] < len(keys)
+    k = (got["find_keys_hi"].astype(np.uint64) << np.uint64(32)) | got["find_keys_lo"].astype(np.uint64)
+    assert np.array_equal(k, keys[r]) and np.array_equal(got["find_values"], vals[r].astype(np.float64))
+    assert np.array_equal(got["counts"], [5000, 5000, 7, 128])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """a plain run: the result line's headline keys, exactly --steps timed steps, no CPU or informational legs, and the outputs of the
+    last timed step (every query a hit, found in query order with its inserted value)"""
+    import json
+    import numpy as np
+    from kmerhash_amd import workloads as W
+    out = str(tmp_path / "dump")
+    r = _run(["--keys", "2000000", "--queries", "200000", "--steps", "3", "--warmup", "1", "--dump-outputs", out])
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["metric"] == "kmer_inserts_plus_finds_per_sec" and d["unit"] == "kmer_ops/s" and d["higher_is_better"] is True and d["dtype"] == "u64"
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 2_200_000 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert d["kernels_ms_per_step"] and "cpu_baseline" not in d and "phases" not in d
+    counts = np.load(os.path.join(out, "counts.npy"))
+    assert np.array_equal(counts[:3], [2_000_000, 200_000, 2_000_000]) and abs(counts[3] * d["config"]["final_load"] - 2_000_000) < 1
+    keys = W.distinct_u64(2_000_000, seed=1)[:200_000]
+    assert np.array_equal(np.load(os.path.join(out, "rows.npy")), np.arange(200_000))
+    k = (np.load(os.path.join(out, "find_keys_hi.npy")).astype(np.uint64) << np.uint64(32)) | np.load(os.path.join(out, "find_keys_lo.npy")).astype(np.uint64)
+    assert np.array_equal(k, keys) and np.array_equal(np.load(os.path.join(out, "find_values.npy")), np.arange(200_000))

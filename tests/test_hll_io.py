@@ -33,17 +33,32 @@ def test_oracle_hll_matches_reference_fixture(oracle):
     assert abs(float(g["est_a"]) - len(np.unique(keys))) < 3 * 1.04 / 64 * len(np.unique(keys))
 
 
-def test_oracle_hll_vs_reference_library(oracle):
-    if not oracle.ref_hll_available():
-        pytest.skip("reference HLL library not available")
+HLL_IGNORE_MSB = (0, 1, 5)
+
+
+def hll_update_trace(make):
+    """registers and estimate of make(ignore_msb) after each of 5 random batches, for every ignore_msb of HLL_IGNORE_MSB"""
     rng = np.random.default_rng(5)
-    for ign in (0, 1, 5):
-        o = oracle.OracleHLL(12, ign, 1, 43)
-        r = oracle.RefHLL(ign, 1, 43)
+    regs, ests = [], []
+    for ign in HLL_IGNORE_MSB:
+        h = make(ign)
         for _ in range(5):
-            k = rng.integers(0, 2**63, int(rng.integers(1, 30000)), dtype=np.uint64)
-            o.update(k); r.update(k)
-            assert np.array_equal(o.registers(), r.registers()) and o.estimate() == r.estimate()
+            h.update(rng.integers(0, 2**63, int(rng.integers(1, 30000)), dtype=np.uint64))
+            regs.append(h.registers())
+            ests.append(h.estimate())
+    return np.array(regs), np.array(ests, dtype=np.float64)
+
+
+def test_oracle_hll_vs_reference_library(oracle):
+    """the oracle HLL against the REAL reference hyperloglog64 over random batches: the reference's registers and estimates
+    are stored in hll_ref_updates.npz (make_golden.py); where the reference library itself is available it is replayed too"""
+    g = np.load(os.path.join(GOLD, "hll_ref_updates.npz"))
+    refs = [(g["regs"], g["est"])]
+    if oracle.ref_hll_available():
+        refs.append(hll_update_trace(lambda ign: oracle.RefHLL(ign, 1, 43)))
+    regs, ests = hll_update_trace(lambda ign: oracle.OracleHLL(12, ign, 1, 43))
+    for rregs, rests in refs:
+        assert np.array_equal(regs, rregs) and np.array_equal(ests, rests)
 
 
 def test_io_format_against_reference_files(tmp_path, oracle):
