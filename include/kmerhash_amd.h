@@ -69,7 +69,8 @@ typedef enum {
                               tree: PARITY UNPINNED for the bit layout */
 } kh_key_transform;
 
-/* ---- lifetime: ctor (capacity=128, min_lf, max_lf)  hashmap_robinhood.hpp:218-233 / hashmap_linearprobe.hpp:191-206 */
+/* ---- lifetime: ctor (capacity=128, min_lf, max_lf)  hashmap_robinhood.hpp:218-233 / hashmap_linearprobe.hpp:191-206
+ *      key_bytes must be 8 (every batch argument of a kh_table is u64[n]); 16-byte keys live in the separate kh_wtable below. */
 kh_status kh_create(kh_table** out, kh_kind kind, uint32_t key_bytes /*8*/, uint32_t val_bytes /*4*/,
                     kh_hash hash, uint64_t seed /*43*/, uint64_t capacity /*128*/,
                     float min_load_factor, float max_load_factor, int device);
@@ -245,6 +246,53 @@ kh_status kh_hll_estimate(kh_hll* h, double* out);       /* :459 */
 /* internal_estimate (:201-236) on 2^precision host registers: what estimate_global (:482-484) applies to the registers merged over all
  * ranks (merge_distributed :477-479 = an all-reduce(max) of the registers, done by the caller's communication layer).  Host only. */
 kh_status kh_hll_estimate_registers(const uint8_t* registers_host, uint32_t precision, double* out);
+
+/* ---- wide keys: a Robin Hood table of 16-byte keys with 32-bit values (k-mers up to k = 64).  A wide key is {uint64_t w0, uint64_t w1},
+ *      w0 at offset 0: the memory image of a 16-byte POD key such as kmerind's Kmer<63, DNA, uint64_t>, and the hashes read these 16
+ *      bytes in this order (KH_HASH_IDENTITY: w0; murmur3: MurmurHash3_x86_128 / _x64_128 over 16 bytes; farm: Hash64WithSeed(key, 16,
+ *      seed), parity unpinned as for 8 bytes).  A k-mer with k <= 64 is the 128-bit integer V (first base most significant, A0 C1 G2 T3,
+ *      as for 64-bit k-mers) stored as w0 = V mod 2^64, w1 = V >> 64 -- for k <= 32, w0 is the 64-bit k-mer and w1 = 0; its canonical
+ *      form is min(V, revcomp_k(V)) as 128-bit unsigned integers.  kmerind's own Kmer bit layout is not part of the reference tree:
+ *      PARITY UNPINNED for the packing.  Batches of keys are u64[2n] ([h|d] as elsewhere).  The table follows the 64-bit Robin Hood
+ *      table rule for rule (float load thresholds, one doubling per insert() call while size >= max_load, the trailing reserve(size()),
+ *      batch erase never shrinks, first value wins, std::plus wraps at 32 bits, KH_ERR_PROBE_OVERFLOW leaves the table unchanged);
+ *      its info array (kh_wide_export_info) is the canonical Robin Hood layout of the key set at the capacity.  A distinct handle type:
+ *      a kh_wtable passed to a kh_table entry point does not compile. */
+typedef struct kh_wtable kh_wtable;
+kh_status kh_wide_create(kh_wtable** out, kh_kind kind /* KH_KIND_LINEARPROBE: KH_ERR_UNSUPPORTED */, kh_hash hash, uint64_t seed,
+                         uint64_t capacity, float min_load_factor, float max_load_factor, int device);
+kh_status kh_wide_destroy(kh_wtable* t);
+kh_status kh_wide_set_stream(kh_wtable* t, void* hip_stream);
+const char* kh_wide_last_error(const kh_wtable* t);
+kh_status kh_wide_size(const kh_wtable* t, uint64_t* out);
+kh_status kh_wide_capacity(const kh_wtable* t, uint64_t* out);
+kh_status kh_wide_get_load_factors(const kh_wtable* t, float* min_lf, float* max_lf, float* current);
+kh_status kh_wide_set_min_load_factor(kh_wtable* t, float f);
+kh_status kh_wide_set_max_load_factor(kh_wtable* t, float f);
+kh_status kh_wide_clear(kh_wtable* t);
+kh_status kh_wide_reserve(kh_wtable* t, uint64_t n);
+kh_status kh_wide_rehash(kh_wtable* t, uint64_t buckets);
+kh_status kh_wide_insert(kh_wtable* t, const void* keys /*[h|d] u64[2n]*/, const void* vals /*[h|d] u32[n]*/, uint64_t n, kh_mem where,
+                         uint64_t* n_inserted);
+kh_status kh_wide_insert_reduce_plus(kh_wtable* t, const void* keys /*[h|d] u64[2n]*/, const void* vals /*[h|d] u32[n] or NULL*/, uint64_t n,
+                                     kh_mem where, uint64_t* n_inserted);
+kh_status kh_wide_count(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint8_t* out01 /*[h|d] u8[n]*/);
+kh_status kh_wide_find(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint32_t* out_vals /*[h|d] u32[n], untouched on miss*/,
+                       uint8_t* out_found /*[h|d] u8[n]*/, uint64_t* n_found);
+kh_status kh_wide_find_compact(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint64_t* out_keys /*[h|d] u64[2n]*/,
+                               uint32_t* out_vals /*[h|d] u32[n]*/, uint64_t* n_found);
+kh_status kh_wide_erase(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint64_t* n_erased);
+kh_status kh_wide_to_vector(kh_wtable* t, uint64_t* keys_host /* u64[2 size] */, uint32_t* vals_host, uint64_t* n_out);
+kh_status kh_wide_export_info(kh_wtable* t, uint8_t* out_host /* capacity bytes */);
+kh_status kh_wide_displacement_histogram(kh_wtable* t, uint64_t out[128]);
+/* out[i] = hash of the 16-byte key i */
+kh_status kh_wide_hash_batch(kh_hash hash, uint64_t seed, const void* keys /*[h|d] u64[2n]*/, uint64_t n, kh_mem where,
+                             uint64_t* out /*[h|d]*/, int device, void* hip_stream);
+/* kh_kmers_from_sequence / kh_kmers_from_fastq for k = 1..64: 16-byte k-mers {w0, w1} in order; out_kmers needs room for 2n words */
+kh_status kh_kmers128_from_sequence(const void* seq, uint64_t n, uint32_t k /*1..64*/, int canonical, kh_mem where,
+                                    uint64_t* out_kmers /*[h|d] u64[2n]*/, uint64_t* n_out, int device, void* hip_stream);
+kh_status kh_kmers128_from_fastq(const void* text, uint64_t n, uint32_t k /*1..64*/, int canonical, kh_mem where,
+                                 uint64_t* out_kmers /*[h|d] u64[2n]*/, uint64_t* n_out, int device, void* hip_stream);
 
 /* ---- measurement hooks: per-kernel HIP-event timing on the table's stream (bench.py roofline) */
 kh_status kh_profile_enable(kh_table* t, int on);

@@ -24,6 +24,11 @@ SYMBOLS = [
     "kh_hash_batch", "kh_shard_permute", "kh_shard_plan_create", "kh_shard_plan_permute", "kh_shard_plan_permute_global", "kh_shard_plan_offsets", "kh_shard_plan_destroy", "kh_profile_enable", "kh_profile_reset", "kh_profile_query", "kh_profile_dump",
     "kh_kmers_from_sequence", "kh_kmers_from_fastq", "kh_hll_create", "kh_hll_destroy", "kh_hll_set_stream", "kh_hll_update", "kh_hll_update_via_hashval",
     "kh_hll_merge", "kh_hll_clear", "kh_hll_registers", "kh_hll_estimate", "kh_hll_estimate_registers", "kh_release_cached_memory", "kh_version",
+    # wide keys (16-byte keys, k <= 64)
+    "kh_wide_create", "kh_wide_destroy", "kh_wide_set_stream", "kh_wide_last_error", "kh_wide_size", "kh_wide_capacity", "kh_wide_get_load_factors",
+    "kh_wide_set_min_load_factor", "kh_wide_set_max_load_factor", "kh_wide_clear", "kh_wide_reserve", "kh_wide_rehash", "kh_wide_insert",
+    "kh_wide_insert_reduce_plus", "kh_wide_count", "kh_wide_find", "kh_wide_find_compact", "kh_wide_erase", "kh_wide_to_vector",
+    "kh_wide_export_info", "kh_wide_displacement_histogram", "kh_wide_hash_batch", "kh_kmers128_from_sequence", "kh_kmers128_from_fastq",
 ]
 
 _lib = None
@@ -118,8 +123,33 @@ def lib():
     L.kh_profile_reset.argtypes = [vp]
     L.kh_profile_query.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), pu64]
     L.kh_profile_dump.argtypes = [vp, C.c_char_p, u64]
+    L.kh_wide_last_error.restype = C.c_char_p
+    L.kh_wide_last_error.argtypes = [vp]
+    L.kh_wide_create.argtypes = [C.POINTER(vp), i32, i32, u64, u64, f32, f32, i32]
+    L.kh_wide_destroy.argtypes = [vp]
+    L.kh_wide_set_stream.argtypes = [vp, vp]
+    L.kh_wide_size.argtypes = [vp, pu64]
+    L.kh_wide_capacity.argtypes = [vp, pu64]
+    L.kh_wide_get_load_factors.argtypes = [vp, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]
+    L.kh_wide_set_min_load_factor.argtypes = [vp, f32]
+    L.kh_wide_set_max_load_factor.argtypes = [vp, f32]
+    L.kh_wide_clear.argtypes = [vp]
+    L.kh_wide_reserve.argtypes = [vp, u64]
+    L.kh_wide_rehash.argtypes = [vp, u64]
+    L.kh_wide_insert.argtypes = [vp, vp, vp, u64, i32, pu64]
+    L.kh_wide_insert_reduce_plus.argtypes = [vp, vp, vp, u64, i32, pu64]
+    L.kh_wide_count.argtypes = [vp, vp, u64, i32, vp]
+    L.kh_wide_find.argtypes = [vp, vp, u64, i32, vp, vp, pu64]
+    L.kh_wide_find_compact.argtypes = [vp, vp, u64, i32, vp, vp, pu64]
+    L.kh_wide_erase.argtypes = [vp, vp, u64, i32, pu64]
+    L.kh_wide_to_vector.argtypes = [vp, vp, vp, pu64]
+    L.kh_wide_export_info.argtypes = [vp, vp]
+    L.kh_wide_displacement_histogram.argtypes = [vp, vp]
+    L.kh_wide_hash_batch.argtypes = [i32, u64, vp, u64, i32, vp, i32, vp]
+    L.kh_kmers128_from_sequence.argtypes = [vp, u64, u32, i32, i32, vp, pu64, i32, vp]
+    L.kh_kmers128_from_fastq.argtypes = [vp, u64, u32, i32, i32, vp, pu64, i32, vp]
     for s in SYMBOLS:
-        if s not in ("kh_version", "kh_last_error"):
+        if s not in ("kh_version", "kh_last_error", "kh_wide_last_error"):
             getattr(L, s).restype = i32
     _lib = L
     return L

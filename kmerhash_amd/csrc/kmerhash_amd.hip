@@ -11,6 +11,7 @@
 //             out without them); LP writes tombstones in place.
 //   find/count : sector probing with in-launch compaction (k_find).
 #include "kh_kernels.h"
+#include "kh_kernels_wide.h"
 #include "../../include/kmerhash_amd.h"
 
 #include <string>
@@ -2304,3 +2305,560 @@ kh_status kh_profile_dump(kh_table* t, char* buf, uint64_t cap) {
 #ifdef KH_TRACE
 extern "C" int kh_debug_trace(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(kh_trace), sizeof(unsigned long long) * 512 * 12); }
 #endif
+
+// ===================================================================================================
+// Wide keys: the 16-byte-key Robin Hood table (kh_wtable) and the 128-bit k-mer front end (kernels: kh_kernels_wide.h).
+// The table state machine is the 64-bit table's, rule for rule: the shared state (load factors, float thresholds, size, stream,
+// workspace arena, pinned scratch, last error) IS a kh_table, so capacity_after / threshold / the device pool / the arena are used
+// unchanged.  Only the general path exists: partition -> kw_dedup -> capacity decision -> kw_chunk_count / k_chunk_carry /
+// kw_chunk_place into a fresh buffer; the old buffer stays current until the new one is complete, so a failing batch leaves the
+// table unchanged.
+// ===================================================================================================
+struct kh_wtable {
+  kh_table b;          // shared state (b.cur / b.spare stay empty: the slots of a wide table are cur / spare below)
+  KwSlots cur, spare;
+};
+namespace {
+const KwSlots kNoWSlots = KwSlots{nullptr, 0};
+kh_status kw_alloc(kh_table* t, uint64_t cap, KwSlots& s) {
+  s = kNoWSlots;
+  hipError_t e = pool_alloc(t->device, std::max<uint64_t>(cap, 16) * sizeof(KwSlot), reinterpret_cast<void**>(&s.s));
+  if (e != hipSuccess) { s = kNoWSlots; return fail(t, KH_ERR_NOMEM, std::string("table allocation: ") + hipGetErrorString(e)); }
+  s.cap = cap;
+  return KH_OK;
+}
+void kw_free(kh_table* t, KwSlots& s) { pool_free(t->device, s.s); s = kNoWSlots; }
+kh_status kw_fill(kh_table* t, KwSlots s) {
+  hipLaunchKernelGGL(kw_fill_empty, dim3(grid_for(s.cap, 256)), dim3(256), 0, t->stream, s);
+  HIPCHK(hipGetLastError());
+  return KH_OK;
+}
+kh_status kw_fresh(kh_wtable* w, uint64_t cap, KwSlots& s) {      // destination of a re-layout: every slot is written once, no clearing
+  kh_table* t = &w->b;
+  if (w->spare.cap == cap && w->spare.s) { s = w->spare; w->spare = kNoWSlots; }
+  else { kh_status st = kw_alloc(t, cap, s); if (st != KH_OK) return st; }
+  if (g_poison) { hipLaunchKernelGGL(kw_poison, dim3(grid_for(cap, 256)), dim3(256), 0, t->stream, s); HIPCHK(hipGetLastError()); }
+  return KH_OK;
+}
+void kw_retire(kh_wtable* w, KwSlots& s) {
+  if (!s.s) return;
+  if (w->spare.s) { hipStreamSynchronize(w->b.stream); kw_free(&w->b, w->spare); }
+  w->spare = s;
+  s = kNoWSlots;
+}
+
+// re-layout (live elements of cur, minus the marked ones) U (new distinct elements) at capacity new_cap into a fresh buffer
+kh_status kw_rebuild(kh_wtable* w, uint64_t new_cap, const uint64_t* ck, const uint32_t* cv, const uint64_t* noff, const uint32_t* ncnt,
+                     uint32_t PB, bool drop_marked, uint64_t total_after) {
+  kh_table* t = &w->b;
+  if (total_after > new_cap) return fail(t, KH_ERR_FULL, "table would hold more elements than buckets (no slot to insert into)");
+  KwSlots nw;
+  kh_status st = kw_fresh(w, new_cap, nw);
+  if (st != KH_OK) return st;
+  const uint32_t nch = new_cap > KH_L ? (uint32_t)(new_cap >> KH_LB) : 1u;
+  uint16_t* homecnt; long long *sumA, *sumN, *xcarry; KhMP* ptmp; uint32_t* flags;
+  TAKE(homecnt, uint16_t, new_cap); TAKE(sumA, long long, nch); TAKE(sumN, long long, nch); TAKE(xcarry, long long, nch);
+  TAKE(ptmp, KhMP, nch); TAKE(flags, uint32_t, KH_NFLAGS);
+  HIPCHK(hipMemsetAsync(flags, 0, sizeof(uint32_t) * KH_NFLAGS, t->stream));
+  KwRebuildParams P;
+  memset(&P, 0, sizeof(P));
+  P.Old = w->cur; P.drop_marked = drop_marked ? 1 : 0; P.New = nw; P.ck = ck; P.cv = cv; P.noff = noff; P.ncnt = ncnt; P.PB = PB;
+  if (t->lsize == 0) P.Old.cap = 0;
+  P.seed = t->seed.s; P.homecnt = homecnt; P.sumA = sumA; P.sumN = sumN; P.xcarry = xcarry; P.flags = flags;
+  { Launch L(t, "kw_chunk_count");
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_chunk_count<HASH>), dim3(nch), dim3(KW_DD_THREADS), 0, t->stream, P)); }
+  { Launch L(t, "k_chunk_carry");
+    hipLaunchKernelGGL(k_chunk_carry, dim3(1), dim3(1024), 0, t->stream, sumA, sumN, nch, (long long)new_cap, xcarry, ptmp); }
+  { Launch L(t, "kw_chunk_place");
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_chunk_place<HASH>), dim3(nch), dim3(KW_DD_THREADS), 0, t->stream, P)); }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(t->hpin, flags, sizeof(uint32_t) * KH_NFLAGS, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  const uint32_t* f = reinterpret_cast<const uint32_t*>(t->hpin);
+  if (f[KH_FLAG_PROBE_OVERFLOW] || f[KH_FLAG_COUNT_OVERFLOW]) {
+    kw_retire(w, nw);
+    if (f[KH_FLAG_PROBE_OVERFLOW])
+      return fail(t, KH_ERR_PROBE_OVERFLOW, "Robin Hood probe distance would exceed 127 (7-bit info field, hashmap_robinhood.hpp:142-144,556)");
+    return fail(t, KH_ERR_PROBE_OVERFLOW, "more than 65535 keys share one home bucket");
+  }
+  KwSlots old = w->cur;
+  w->cur = nw;
+  kw_retire(w, old);
+  t->min_load = threshold(new_cap, t->min_lf);
+  t->max_load = threshold(new_cap, t->max_lf);
+  return KH_OK;
+}
+kh_status kw_do_rehash(kh_wtable* w, uint64_t b) {      // hashmap_robinhood.hpp:432-464, as do_rehash
+  kh_table* t = &w->b;
+  uint64_t c = next_pow2(b);
+  if (c == w->cur.cap) return KH_OK;
+  if (t->lsize > 0) {
+    if (0 >= threshold(c, t->max_lf)) c <<= 1;
+    while (t->lsize > threshold(c, t->max_lf)) c <<= 1;
+  }
+  if (c == w->cur.cap) return KH_OK;
+  { kh_status ps = arena_prepare(t, ws_rebuild(c)); if (ps != KH_OK) return ps; }
+  return kw_rebuild(w, c, nullptr, nullptr, nullptr, nullptr, 0, false, t->lsize);
+}
+kh_status kw_do_reserve(kh_wtable* w, uint64_t n) {
+  kh_table* t = &w->b;
+  if (n > t->max_load) return kw_do_rehash(w, static_cast<uint64_t>(static_cast<float>(n) / t->max_lf));
+  return KH_OK;
+}
+// workspace of one insert pass of n keys at partitioning capacity cap_u
+inline size_t kw_ws_insert(uint64_t n, uint64_t cap_u) {
+  const uint64_t np = cap_u > KH_L ? (cap_u >> KH_LB) : 1;
+  return n * (sizeof(KwRec) + 16 + 4 + 8 + 4 + 16 + 4) + np * 48 + ws_rebuild(cap_u) + (size_t(4) << 20);
+}
+
+// one insert() pass over device-resident keys (u64[2n]) / values (u32[n] or null); n < 2^32
+kh_status kw_insert_core(kh_wtable* w, const uint64_t* keys, const uint32_t* vals, uint64_t n, int mode, uint64_t forced_cap, uint64_t* n_new_out) {
+  kh_table* t = &w->b;
+  *n_new_out = 0;
+  if (n == 0) return KH_OK;
+  const uint64_t cap_u = forced_cap ? forced_cap : capacity_after(t, w->cur.cap, t->lsize, n, n, n - 1);
+  const uint32_t PB = cap_u > KH_L ? log2u(cap_u >> KH_LB) : 0u;
+  if (PB > 22) return fail(t, KH_ERR_UNSUPPORTED, "batch would need more than 2^22 partitions");
+  const uint32_t nparts = 1u << PB;
+  const bool plus = mode == INS_PLUS, plus_live = plus && t->lsize > 0;
+  uint32_t *cnt, *cnt_new, *cnt_upd = nullptr, *flags, *nv, *uv = nullptr; uint64_t *off, *noff, *nk, *us = nullptr;
+  unsigned long long *cursor, *scal; KwRec* rec;
+  TAKE(cnt, uint32_t, nparts); TAKE(off, uint64_t, nparts + 1); TAKE(cursor, unsigned long long, nparts); TAKE(rec, KwRec, n);
+  TAKE(cnt_new, uint32_t, nparts); TAKE(noff, uint64_t, nparts + 1); TAKE(nk, uint64_t, 2 * n); TAKE(nv, uint32_t, n);
+  TAKE(flags, uint32_t, KH_NFLAGS); TAKE(scal, unsigned long long, 2);
+  if (plus_live) { TAKE(cnt_upd, uint32_t, nparts); TAKE(us, uint64_t, n); TAKE(uv, uint32_t, n); }
+  HIPCHK(hipMemsetAsync(cnt, 0, sizeof(uint32_t) * nparts, t->stream));
+  HIPCHK(hipMemsetAsync(flags, 0, sizeof(uint32_t) * KH_NFLAGS, t->stream));
+  HIPCHK(hipMemsetAsync(scal, 0, 16, t->stream));
+  const uint32_t pgrid = grid_for(n, KW_PART_THREADS, 4096);
+  { Launch L(t, "kw_part_count");
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_part_count<HASH>), dim3(pgrid), dim3(KW_PART_THREADS), 0, t->stream, keys, n, t->seed.s, PB, cnt)); }
+  { Launch L(t, "k_scan");
+    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, cnt, (uint64_t)nparts, off); }
+  HIPCHK(hipMemcpyAsync(cursor, off, sizeof(uint64_t) * nparts, hipMemcpyDeviceToDevice, t->stream));
+  { Launch L(t, "kw_part_scatter");
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_part_scatter<HASH>), dim3(pgrid), dim3(KW_PART_THREADS), 0, t->stream, keys, vals,
+                                               plus ? 1u : 0u, n, t->seed.s, PB, cursor, rec)); }
+  KwDedupParams D;
+  memset(&D, 0, sizeof(D));
+  D.rec = rec; D.off = off; D.T = w->cur; D.seed = t->seed.s; D.table_empty = t->lsize == 0 ? 1 : 0;
+  D.mode = plus ? KH_DEDUP_PLUS : KH_DEDUP_FIRST;
+  D.nk = nk; D.nv = nv; D.cnt_new = cnt_new; D.us = us; D.uv = uv; D.cnt_upd = cnt_upd; D.max_idx_plus1 = scal; D.flags = flags;
+  { Launch L(t, "kw_dedup");
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_dedup<HASH>), dim3(nparts), dim3(KW_DD_THREADS), 0, t->stream, D)); }
+  { Launch L(t, "k_scan");
+    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, cnt_new, (uint64_t)nparts, noff); }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(t->hpin, noff + nparts, 8, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipMemcpyAsync(t->hpin + 1, scal, 8, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipMemcpyAsync(t->hpin + 2, flags, sizeof(uint32_t) * KH_NFLAGS, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  if (reinterpret_cast<const uint32_t*>(t->hpin + 2)[KH_FLAG_INTERNAL]) return fail(t, KH_ERR_HIP, "internal: de-duplication set overflow");
+  const uint64_t dnew = t->hpin[0];
+  const uint64_t last_first = plus ? n - 1 : (t->hpin[1] ? t->hpin[1] - 1 : 0);
+  auto apply_plus = [&](int sign) {
+    Launch L(t, "kw_apply_plus");
+    hipLaunchKernelGGL(kw_apply_plus, dim3(std::min<uint32_t>(nparts, 4096u)), dim3(256), 0, t->stream, w->cur.s, (const uint64_t*)off,
+                       (const uint32_t*)cnt_upd, (const uint64_t*)us, (const uint32_t*)uv, nparts, sign);
+  };
+  if (plus_live) apply_plus(+1);
+  const uint64_t new_cap = forced_cap ? forced_cap : capacity_after(t, w->cur.cap, t->lsize, n, dnew, last_first);
+  if (dnew > 0 || new_cap != w->cur.cap) {
+    // a chunk of the new table owns 2^(PB-k) consecutive partitions: their lists are read in place when that is a handful, gathered
+    // into one dense list when the capacity ended far below the partitioning capacity (duplicates)
+    const uint32_t k_new = new_cap > KH_L ? log2u(new_cap >> KH_LB) : 0u;
+    const uint64_t* ck = nullptr; const uint32_t* cv = nullptr; const uint64_t* lo = nullptr; const uint32_t* lc = nullptr;
+    if (dnew > 0) {
+      if (PB - k_new <= 3) { ck = nk; cv = nv; lo = off; lc = cnt_new; }
+      else {
+        uint64_t* gk; uint32_t* gv;
+        TAKE(gk, uint64_t, 2 * dnew); TAKE(gv, uint32_t, dnew);
+        Launch L(t, "kw_gather_new");
+        hipLaunchKernelGGL(kw_gather_new, dim3(nparts), dim3(256), 0, t->stream, (const uint64_t*)off, (const uint64_t*)noff, (const uint64_t*)nk,
+                           (const uint32_t*)nv, gk, gv);
+        ck = gk; cv = gv; lo = noff; lc = nullptr;
+      }
+    }
+    kh_status st = kw_rebuild(w, new_cap, ck, cv, lo, lc, PB, false, t->lsize + dnew);
+    if (st != KH_OK) {        // the table keeps its layout: it must keep its values too
+      if (plus_live) { apply_plus(-1); hipStreamSynchronize(t->stream); }
+      return st;
+    }
+    t->lsize += dnew;
+  }
+  *n_new_out = dnew;
+  return KH_OK;
+}
+
+// insert(Iter,Iter) / the reducer insert over device-resident input: passes cut only where the one-doubling-per-call rule or the
+// 32-bit stream positions demand it (insert_device), then the trailing reserve(size())
+kh_status kw_do_insert(kh_wtable* w, const void* keys, const void* vals, uint64_t n, kh_mem where, int mode, uint64_t* n_inserted) {
+  kh_table* t = &w->b;
+  if (n_inserted) *n_inserted = 0;
+  if (n && !keys) return fail(t, KH_ERR_INVALID, "null keys");
+  HIPCHK(hipSetDevice(t->device));
+  const uint64_t np_ = std::min<uint64_t>(n, g_max_pass);
+  { const uint64_t cu = capacity_after(t, w->cur.cap, t->lsize, np_ ? np_ : 1, np_, np_ ? np_ - 1 : 0);
+    kh_status ps = arena_prepare(t, (where == KH_MEM_HOST ? n * 20 : 0) + kw_ws_insert(np_, cu));
+    if (ps != KH_OK) return ps; }
+  const uint64_t* kb = static_cast<const uint64_t*>(keys);
+  const uint32_t* vb = static_cast<const uint32_t*>(vals);
+  if (where == KH_MEM_HOST && n) {
+    uint64_t* dk; TAKE(dk, uint64_t, 2 * n);
+    HIPCHK(hipMemcpyAsync(dk, keys, n * 16, hipMemcpyHostToDevice, t->stream));
+    kb = dk;
+    if (vals) { uint32_t* dv; TAKE(dv, uint32_t, n); HIPCHK(hipMemcpyAsync(dv, vals, n * 4, hipMemcpyHostToDevice, t->stream)); vb = dv; }
+  }
+  const size_t keep_blk = t->blk, keep_off = t->off;
+  uint64_t total_new = 0, done = 0;
+  kh_status st = KH_OK;
+  while (done < n && st == KH_OK) {
+    uint64_t take = n - done, forced = 0;
+    if (t->lsize >= threshold(w->cur.cap << 1, t->max_lf)) {       // more than one doubling pending: peel one call (insert_device)
+      take = 1;
+      forced = w->cur.cap << 1;
+      while (t->lsize > threshold(forced, t->max_lf)) forced <<= 1;
+    }
+    if (take > g_max_pass) take = g_max_pass;
+    t->blk = keep_blk; t->off = keep_off;
+    uint64_t nn = 0;
+    st = kw_insert_core(w, kb + 2 * done, vb ? vb + done : nullptr, take, mode, forced, &nn);
+    total_new += nn;
+    done += take;
+  }
+  if (st == KH_OK) st = kw_do_reserve(w, t->lsize);
+  if (st == KH_OK) HIPCHK(hipStreamSynchronize(t->stream));
+  if (n_inserted) *n_inserted = total_new;
+  return st;
+}
+
+// find / count / find(Iter,Iter).  Outputs live where the queries live.
+kh_status kw_do_find(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, uint32_t* out_vals, uint8_t* out_found, uint64_t* out_ckeys,
+                     uint32_t* out_cvals, bool compacted, bool count_only, uint64_t* n_found) {
+  kh_table* t = &w->b;
+  if (n_found) *n_found = 0;
+  if (n == 0) return KH_OK;
+  if (!keys) return fail(t, KH_ERR_INVALID, "null keys");
+  HIPCHK(hipSetDevice(t->device));
+  { kh_status ps = arena_prepare(t, n * 48 + (n / KH_CMP_TILE + 8) * 16 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  const uint64_t* q = static_cast<const uint64_t*>(keys);
+  const bool host = where == KH_MEM_HOST;
+  if (host) { uint64_t* d; TAKE(d, uint64_t, 2 * n); HIPCHK(hipMemcpyAsync(d, keys, n * 16, hipMemcpyHostToDevice, t->stream)); q = d; }
+  unsigned long long* hits_dev; TAKE(hits_dev, unsigned long long, 1);
+  HIPCHK(hipMemsetAsync(hits_dev, 0, 8, t->stream));
+  uint32_t* dv = out_vals; uint8_t* df = out_found;
+  if (compacted || (host && dv) || !dv) TAKE(dv, uint32_t, n);
+  if (compacted || host || !df) TAKE(df, uint8_t, n);
+  int ncu = 256;
+  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, t->device);
+  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + KW_Q_THREADS * KW_Q_ITEMS - 1) / (KW_Q_THREADS * KW_Q_ITEMS), (uint64_t)ncu * 8));
+  { Launch L(t, count_only ? "kw_count" : "kw_find");
+    if (count_only) { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_find<HASH, KW_FIND_COUNT>), dim3(grid), dim3(KW_Q_THREADS), 0, t->stream, w->cur, q, n, t->seed.s, dv, df, (unsigned long long*)nullptr)); }
+    else { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_find<HASH, KW_FIND_VALS>), dim3(grid), dim3(KW_Q_THREADS), 0, t->stream, w->cur, q, n, t->seed.s, dv, df, hits_dev)); } }
+  HIPCHK(hipGetLastError());
+  if (count_only) {
+    if (host) { HIPCHK(hipMemcpyAsync(out_found, df, n, hipMemcpyDeviceToHost, t->stream)); HIPCHK(hipStreamSynchronize(t->stream)); }
+    return KH_OK;
+  }
+  uint64_t hits = 0;
+  if (!compacted) {
+    HIPCHK(hipMemcpyAsync(t->hpin, hits_dev, 8, hipMemcpyDeviceToHost, t->stream));
+    if (host) {          // values of misses stay untouched in the caller's buffer
+      std::vector<uint32_t> hv(out_vals ? n : 0); std::vector<uint8_t> hf(n);
+      if (out_vals) HIPCHK(hipMemcpyAsync(hv.data(), dv, n * 4, hipMemcpyDeviceToHost, t->stream));
+      HIPCHK(hipMemcpyAsync(hf.data(), df, n, hipMemcpyDeviceToHost, t->stream));
+      HIPCHK(hipStreamSynchronize(t->stream));
+      for (uint64_t i = 0; i < n; ++i) { if (out_found) out_found[i] = hf[i]; if (hf[i] && out_vals) out_vals[i] = hv[i]; }
+    } else HIPCHK(hipStreamSynchronize(t->stream));
+    hits = t->hpin[0];
+  } else {
+    const uint64_t ntl = (n + KH_CMP_TILE - 1) / KH_CMP_TILE;
+    uint32_t* sums; uint64_t* offs; uint64_t* ck = out_ckeys; uint32_t* cv = out_cvals;
+    TAKE(sums, uint32_t, ntl); TAKE(offs, uint64_t, ntl + 1);
+    if (host) { TAKE(ck, uint64_t, 2 * n); TAKE(cv, uint32_t, n); }
+    hipLaunchKernelGGL(k_flag_tile_sums, dim3((uint32_t)ntl), dim3(256), 0, t->stream, (const uint8_t*)df, n, sums);
+    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, (const uint32_t*)sums, ntl, offs);
+    { Launch L(t, "kw_compact");
+      hipLaunchKernelGGL(kw_compact, dim3((uint32_t)ntl), dim3(256), 0, t->stream, (const uint8_t*)df, q, (const uint32_t*)dv, n, (const uint64_t*)offs, ck, cv); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(t->hpin, offs + ntl, 8, hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    hits = t->hpin[0];
+    if (host && hits) {
+      HIPCHK(hipMemcpyAsync(out_ckeys, ck, hits * 16, hipMemcpyDeviceToHost, t->stream));
+      HIPCHK(hipMemcpyAsync(out_cvals, cv, hits * 4, hipMemcpyDeviceToHost, t->stream));
+      HIPCHK(hipStreamSynchronize(t->stream));
+    }
+  }
+  if (n_found) *n_found = hits;
+  return KH_OK;
+}
+
+// erase(Iter,Iter): mark the hits, re-lay out without them (RH: never shrinks, hashmap_robinhood.hpp:1430-1440)
+kh_status kw_do_erase(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, uint64_t* n_erased) {
+  kh_table* t = &w->b;
+  *n_erased = 0;
+  if (n == 0) return KH_OK;
+  if (!keys) return fail(t, KH_ERR_INVALID, "null keys");
+  HIPCHK(hipSetDevice(t->device));
+  { kh_status ps = arena_prepare(t, n * 16 + ws_rebuild(w->cur.cap) + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  const uint64_t* q = static_cast<const uint64_t*>(keys);
+  if (where == KH_MEM_HOST) { uint64_t* d; TAKE(d, uint64_t, 2 * n); HIPCHK(hipMemcpyAsync(d, keys, n * 16, hipMemcpyHostToDevice, t->stream)); q = d; }
+  unsigned long long* cnt;
+  TAKE(cnt, unsigned long long, 1);
+  HIPCHK(hipMemsetAsync(cnt, 0, 8, t->stream));
+  { Launch L(t, "kw_erase_mark");
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_erase_mark<HASH>), dim3(grid_for(n, 256, 2048)), dim3(256), 0, t->stream, w->cur, q, n, t->seed.s, cnt)); }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(t->hpin, cnt, 8, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  const uint64_t ne = t->hpin[0];
+  if (ne) {
+    kh_status st = kw_rebuild(w, w->cur.cap, nullptr, nullptr, nullptr, nullptr, 0, true, t->lsize - ne);
+    if (st != KH_OK) {        // the table keeps its elements: take the marks back
+      hipLaunchKernelGGL(kw_clear_marks, dim3(grid_for(w->cur.cap, 256)), dim3(256), 0, t->stream, w->cur);
+      hipStreamSynchronize(t->stream);
+      return st;
+    }
+  }
+  t->lsize -= ne;
+  *n_erased = ne;
+  return KH_OK;
+}
+kh_status kw_unpack(kh_wtable* w, uint64_t* k, uint32_t* v, uint8_t* info, uint8_t* flags) {
+  kh_table* t = &w->b;
+  hipLaunchKernelGGL(kw_unpack_slots, dim3(grid_for(w->cur.cap, 256)), dim3(256), 0, t->stream, (const KwSlot*)w->cur.s, w->cur.cap, k, v, info, flags);
+  HIPCHK(hipGetLastError());
+  return KH_OK;
+}
+
+// 128-bit k-mers (kmers_impl with 16-byte outputs)
+kh_status kw_kmers_impl(const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq, uint64_t* out_kmers, uint64_t* n_out,
+                        int device, void* stream_) {
+  kh_table* t = nullptr;
+  if (n_out) *n_out = 0;
+  if (k < 1 || k > 64 || !n_out) return KH_ERR_INVALID;
+  if (n < k) return KH_OK;
+  if (!seq || !out_kmers) return KH_ERR_INVALID;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK(hipSetDevice(device));
+  const uint64_t ntl = (n + KH_CMP_TILE - 1) / KH_CMP_TILE;
+  const uint64_t nkt = (n + KH_KM_TILE - 1) / KH_KM_TILE;
+  const uint64_t nt = std::max(ntl, nkt);
+  const size_t sz_seq = where == KH_MEM_HOST ? ((n + 255) & ~size_t(255)) : 0;
+  const size_t sz_msk = fastq ? ((n + 255) & ~size_t(255)) : 0;
+  const size_t sz_sum = ((nt * 4 + 255) & ~size_t(255)), sz_off = ((nt + 1) * 8 + 255) & ~size_t(255);
+  const size_t sz_out = where == KH_MEM_HOST ? n * 16 : 0;
+  char* blk = nullptr;
+  HIPCHK(pool_alloc(device, sz_seq + sz_msk + sz_sum + sz_off + sz_out, reinterpret_cast<void**>(&blk)));
+  const uint8_t* dseq = static_cast<const uint8_t*>(seq);
+  char* p = blk;
+  if (where == KH_MEM_HOST) { dseq = reinterpret_cast<uint8_t*>(p); p += sz_seq; }
+  uint8_t* msk = reinterpret_cast<uint8_t*>(p); p += sz_msk;
+  uint32_t* sums = reinterpret_cast<uint32_t*>(p); p += sz_sum;
+  uint64_t* offs = reinterpret_cast<uint64_t*>(p); p += sz_off;
+  uint64_t* dout = where == KH_MEM_HOST ? reinterpret_cast<uint64_t*>(p) : out_kmers;
+  hipError_t e = hipSuccess;
+  if (where == KH_MEM_HOST) e = hipMemcpyAsync(const_cast<uint8_t*>(dseq), seq, n, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) {
+    if (fastq) {
+      hipLaunchKernelGGL(k_newline_tile_sums, dim3((uint32_t)ntl), dim3(256), 0, stream, dseq, n, sums);
+      hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, (const uint32_t*)sums, ntl, offs);
+      hipLaunchKernelGGL(k_fastq_mask, dim3((uint32_t)ntl), dim3(256), 0, stream, dseq, n, (const uint64_t*)offs, msk);
+      dseq = msk;
+    }
+    hipLaunchKernelGGL(kw_kmers_count, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
+    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, (const uint32_t*)sums, nkt, offs);
+    if (canonical) hipLaunchKernelGGL((kw_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
+    else hipLaunchKernelGGL((kw_kmers_emit<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
+    e = hipGetLastError();
+  }
+  uint64_t total = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&total, offs + nkt, 8, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e == hipSuccess && where == KH_MEM_HOST && total) {
+    e = hipMemcpyAsync(out_kmers, dout, total * 16, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  }
+  pool_free(device, blk);
+  if (e != hipSuccess) return KH_ERR_HIP;
+  *n_out = total;
+  return KH_OK;
+}
+}  // namespace
+
+extern "C" {
+kh_status kh_wide_create(kh_wtable** out, kh_kind kind, kh_hash hash, uint64_t seed, uint64_t capacity, float min_lf, float max_lf, int device) {
+  if (!out) return KH_ERR_INVALID;
+  *out = nullptr;
+  if ((int)kind == KH_KIND_LINEARPROBE) return KH_ERR_UNSUPPORTED;
+  if ((int)kind != KH_KIND_ROBINHOOD || (int)hash < 0 || (int)hash > 3) return KH_ERR_INVALID;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return KH_ERR_HIP;
+  if (device < 0 || device >= ndev) return KH_ERR_INVALID;
+  if (hipSetDevice(device) != hipSuccess) return KH_ERR_HIP;
+  kh_wtable* w = new kh_wtable();
+  kh_table* t = &w->b;
+  t->kind = KHK_RH; t->hash = (int)hash; t->device = device; t->seed = KhSeed{seed, 0u}; t->stream = nullptr;
+  t->min_lf = min_lf; t->max_lf = max_lf; t->lsize = 0;
+  t->cur = kNoSlots; t->spare = kNoSlots;
+  t->blk = 0; t->off = 0; t->hpin = nullptr; t->prof = false; t->part_overflow = nullptr; t->batch_nodup = false; t->batch_vf = 1.0;
+  memset(&t->ins, 0, sizeof(t->ins));
+  w->cur = kNoWSlots; w->spare = kNoWSlots;
+  const uint64_t cap = next_pow2(capacity);
+  if (kw_alloc(t, cap, w->cur) != KH_OK) { delete w; return KH_ERR_NOMEM; }
+  t->hpin = pinned_get();
+  if (!t->hpin) { kw_free(t, w->cur); delete w; return KH_ERR_NOMEM; }
+  if (kw_fill(t, w->cur) != KH_OK || hipStreamSynchronize(t->stream) != hipSuccess) { kw_free(t, w->cur); pinned_put(t->hpin); delete w; return KH_ERR_HIP; }
+  t->min_load = threshold(cap, min_lf);
+  t->max_load = threshold(cap, max_lf);
+  *out = w;
+  return KH_OK;
+}
+kh_status kh_wide_destroy(kh_wtable* w) {
+  if (!w) return KH_OK;
+  kh_table* t = &w->b;
+  hipSetDevice(t->device);
+  hipStreamSynchronize(t->stream);
+  for (auto& r : t->recs) { event_put(t->device, r.a); event_put(t->device, r.b); }
+  kw_free(t, w->cur); kw_free(t, w->spare);
+  for (auto& b : t->blocks) pool_free(t->device, b.p);
+  pinned_put(t->hpin);
+  delete w;
+  return KH_OK;
+}
+kh_status kh_wide_set_stream(kh_wtable* w, void* s) { return w ? kh_set_stream(&w->b, s) : KH_ERR_INVALID; }
+const char* kh_wide_last_error(const kh_wtable* w) { return w ? w->b.err.c_str() : "null table"; }
+kh_status kh_wide_size(const kh_wtable* w, uint64_t* out) { if (!w || !out) return KH_ERR_INVALID; *out = w->b.lsize; return KH_OK; }
+kh_status kh_wide_capacity(const kh_wtable* w, uint64_t* out) { if (!w || !out) return KH_ERR_INVALID; *out = w->cur.cap; return KH_OK; }
+kh_status kh_wide_get_load_factors(const kh_wtable* w, float* mn, float* mx, float* cur) {
+  if (!w) return KH_ERR_INVALID;
+  if (mn) *mn = w->b.min_lf;
+  if (mx) *mx = w->b.max_lf;
+  if (cur) *cur = static_cast<float>(w->b.lsize) / static_cast<float>(w->cur.cap);
+  return KH_OK;
+}
+kh_status kh_wide_set_min_load_factor(kh_wtable* w, float f) { if (!w) return KH_ERR_INVALID; w->b.min_lf = f; w->b.min_load = threshold(w->cur.cap, f); return KH_OK; }
+kh_status kh_wide_set_max_load_factor(kh_wtable* w, float f) { if (!w) return KH_ERR_INVALID; w->b.max_lf = f; w->b.max_load = threshold(w->cur.cap, f); return KH_OK; }
+kh_status kh_wide_clear(kh_wtable* w) {
+  if (!w) return KH_ERR_INVALID;
+  kh_table* t = &w->b;
+  HIPCHK(hipSetDevice(t->device));
+  t->lsize = 0;
+  { kh_status fs = kw_fill(t, w->cur); if (fs != KH_OK) return fs; }
+  HIPCHK(hipStreamSynchronize(t->stream));
+  return KH_OK;
+}
+kh_status kh_wide_reserve(kh_wtable* w, uint64_t n) { if (!w) return KH_ERR_INVALID; kh_table* t = &w->b; HIPCHK(hipSetDevice(t->device)); return kw_do_reserve(w, n); }
+kh_status kh_wide_rehash(kh_wtable* w, uint64_t b) { if (!w) return KH_ERR_INVALID; kh_table* t = &w->b; HIPCHK(hipSetDevice(t->device)); return kw_do_rehash(w, b); }
+kh_status kh_wide_insert(kh_wtable* w, const void* keys, const void* vals, uint64_t n, kh_mem where, uint64_t* n_inserted) {
+  if (!w) return KH_ERR_INVALID;
+  if (n && !vals) return fail(&w->b, KH_ERR_INVALID, "null values");
+  return kw_do_insert(w, keys, vals, n, where, INS_FIRST, n_inserted);
+}
+kh_status kh_wide_insert_reduce_plus(kh_wtable* w, const void* keys, const void* vals, uint64_t n, kh_mem where, uint64_t* n_inserted) {
+  if (!w) return KH_ERR_INVALID;
+  return kw_do_insert(w, keys, vals, n, where, INS_PLUS, n_inserted);
+}
+kh_status kh_wide_count(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, uint8_t* out01) {
+  if (!w) return KH_ERR_INVALID;
+  if (n && !out01) return fail(&w->b, KH_ERR_INVALID, "null argument");
+  return kw_do_find(w, keys, n, where, nullptr, out01, nullptr, nullptr, false, true, nullptr);
+}
+kh_status kh_wide_find(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, uint32_t* out_vals, uint8_t* out_found, uint64_t* n_found) {
+  if (!w) return KH_ERR_INVALID;
+  return kw_do_find(w, keys, n, where, out_vals, out_found, nullptr, nullptr, false, false, n_found);
+}
+kh_status kh_wide_find_compact(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, uint64_t* out_keys, uint32_t* out_vals, uint64_t* n_found) {
+  if (!w) return KH_ERR_INVALID;
+  if (n && (!out_keys || !out_vals)) return fail(&w->b, KH_ERR_INVALID, "null output");
+  return kw_do_find(w, keys, n, where, nullptr, nullptr, out_keys, out_vals, true, false, n_found);
+}
+kh_status kh_wide_erase(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, uint64_t* n_erased) {
+  if (!w) return KH_ERR_INVALID;
+  kh_table* t = &w->b;
+  uint64_t ne = 0;
+  kh_status st = kw_do_erase(w, keys, n, where, &ne);
+  if (n_erased) *n_erased = ne;
+  if (st == KH_OK && t->lsize < t->min_load) st = kw_do_reserve(w, t->lsize);     // hashmap_robinhood.hpp:1437: reserve() only grows
+  return st;
+}
+kh_status kh_wide_to_vector(kh_wtable* w, uint64_t* keys_host, uint32_t* vals_host, uint64_t* n_out) {
+  if (!w) return KH_ERR_INVALID;
+  kh_table* t = &w->b;
+  HIPCHK(hipSetDevice(t->device));
+  const uint64_t cap = w->cur.cap, ntl = (cap + KH_CMP_TILE - 1) / KH_CMP_TILE;
+  { kh_status ps = arena_prepare(t, cap * 45 + ntl * 12 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  uint8_t* flags; uint64_t *sk, *ck, *offs; uint32_t *sv, *cv, *sums;
+  TAKE(flags, uint8_t, cap); TAKE(sk, uint64_t, 2 * cap); TAKE(sv, uint32_t, cap); TAKE(ck, uint64_t, 2 * cap); TAKE(cv, uint32_t, cap);
+  TAKE(sums, uint32_t, ntl); TAKE(offs, uint64_t, ntl + 1);
+  kh_status st = kw_unpack(w, sk, sv, nullptr, flags);
+  if (st != KH_OK) return st;
+  hipLaunchKernelGGL(k_flag_tile_sums, dim3((uint32_t)ntl), dim3(256), 0, t->stream, (const uint8_t*)flags, cap, sums);
+  hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, (const uint32_t*)sums, ntl, offs);
+  hipLaunchKernelGGL(kw_compact, dim3((uint32_t)ntl), dim3(256), 0, t->stream, (const uint8_t*)flags, (const uint64_t*)sk, (const uint32_t*)sv, cap, (const uint64_t*)offs, ck, cv);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(t->hpin, offs + ntl, 8, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  const uint64_t m = t->hpin[0];
+  if (m && keys_host) HIPCHK(hipMemcpyAsync(keys_host, ck, m * 16, hipMemcpyDeviceToHost, t->stream));
+  if (m && vals_host) HIPCHK(hipMemcpyAsync(vals_host, cv, m * 4, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  if (n_out) *n_out = m;
+  return KH_OK;
+}
+kh_status kh_wide_export_info(kh_wtable* w, uint8_t* out_host) {
+  if (!w || !out_host) return KH_ERR_INVALID;
+  kh_table* t = &w->b;
+  HIPCHK(hipSetDevice(t->device));
+  { kh_status ps = arena_prepare(t, w->cur.cap + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  uint8_t* info;
+  TAKE(info, uint8_t, w->cur.cap);
+  kh_status st = kw_unpack(w, nullptr, nullptr, info, nullptr);
+  if (st != KH_OK) return st;
+  HIPCHK(hipMemcpyAsync(out_host, info, w->cur.cap, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  return KH_OK;
+}
+kh_status kh_wide_displacement_histogram(kh_wtable* w, uint64_t out[128]) {
+  if (!w || !out) return KH_ERR_INVALID;
+  kh_table* t = &w->b;
+  HIPCHK(hipSetDevice(t->device));
+  { kh_status ps = arena_prepare(t, size_t(1) << 20); if (ps != KH_OK) return ps; }
+  unsigned long long* d;
+  TAKE(d, unsigned long long, 128);
+  HIPCHK(hipMemsetAsync(d, 0, 128 * 8, t->stream));
+  hipLaunchKernelGGL(kw_disp_hist, dim3(grid_for(w->cur.cap, 256, 1024)), dim3(256), 0, t->stream, (const KwSlot*)w->cur.s, w->cur.cap, d);
+  HIPCHK(hipMemcpyAsync(out, d, 128 * 8, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  return KH_OK;
+}
+kh_status kh_wide_hash_batch(kh_hash hash, uint64_t seed, const void* keys, uint64_t n, kh_mem where, uint64_t* out, int device, void* stream_) {
+  kh_table* t = nullptr;
+  if (n == 0) return KH_OK;
+  if (!keys || !out || (int)hash < 0 || (int)hash > 3) return KH_ERR_INVALID;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK(hipSetDevice(device));
+  const uint64_t* dk = static_cast<const uint64_t*>(keys);
+  uint64_t* dout = out; uint64_t* tmp = nullptr;
+  if (where == KH_MEM_HOST) {
+    HIPCHK(pool_alloc(device, n * 24, reinterpret_cast<void**>(&tmp)));
+    HIPCHK(hipMemcpyAsync(tmp, keys, n * 16, hipMemcpyHostToDevice, stream));
+    dk = tmp; dout = tmp + 2 * n;
+  }
+  KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((kw_hash_batch<HASH>), dim3(grid_for(n, 256)), dim3(256), 0, stream, dk, n, seed, dout));
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && where == KH_MEM_HOST) e = hipMemcpyAsync(out, dout, n * 8, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && where == KH_MEM_HOST) e = hipStreamSynchronize(stream);
+  if (tmp) pool_free(device, tmp);
+  return e == hipSuccess ? KH_OK : KH_ERR_HIP;
+}
+kh_status kh_kmers128_from_sequence(const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, uint64_t* out_kmers, uint64_t* n_out,
+                                    int device, void* stream) {
+  return kw_kmers_impl(seq, n, k, canonical, where, false, out_kmers, n_out, device, stream);
+}
+kh_status kh_kmers128_from_fastq(const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, uint64_t* out_kmers, uint64_t* n_out,
+                                 int device, void* stream) {
+  return kw_kmers_impl(text, n, k, canonical, where, true, out_kmers, n_out, device, stream);
+}
+}  // extern "C"

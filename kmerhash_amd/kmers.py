@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _capi as K
 from .table import _Buf, hashmap_robinhood_doubling, torch
+from .wide import hashmap_robinhood_doubling_wide, kmers128_from_sequence
 
 
 def sequences_from_fastq(buf):
@@ -69,17 +70,25 @@ class KmerCounter:
 
     def __init__(self, k=31, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0):
         self.k, self.canonical, self.device = k, canonical, device
-        self.table = hashmap_robinhood_doubling(128, min_load_factor, max_load_factor, hash=hash, seed=43, device=device)
+        # 33 <= k <= 64: 16-byte k-mers in the wide table (k-mer = {w0, w1}, see kmerhash_amd.wide)
+        self.wide = 32 < k <= 64
+        cls = hashmap_robinhood_doubling_wide if self.wide else hashmap_robinhood_doubling
+        self.table = cls(128, min_load_factor, max_load_factor, hash=hash, seed=43, device=device)
+
+    def _kmers(self, seq, fastq):
+        if self.wide:
+            return kmers128_from_sequence(seq, self.k, self.canonical, self.device, _fastq=fastq)
+        return kmers_from_sequence(seq, self.k, self.canonical, self.device, _fastq=fastq)
 
     def add_sequences(self, seq):
-        km = kmers_from_sequence(seq, self.k, self.canonical, self.device)
+        km = self._kmers(seq, False)
         if len(km):
             self.table.insert_reduce_plus(km)
         return len(km)
 
     def add_fastq(self, buf):
         """raw FASTQ text (whole records), host or device: record structure, k-mer generation and counting all run on the GPU"""
-        km = kmers_from_fastq(buf, self.k, self.canonical, self.device)
+        km = self._kmers(buf, True)
         if len(km):
             self.table.insert_reduce_plus(km)
         return len(km)
@@ -91,7 +100,9 @@ class KmerCounter:
         """raw (k-mer, count) tuples, sizeof(KmerType) + sizeof(CountType) bytes each, no padding
         (BenchmarkKmerCounter.cpp:1022-1059 copyToByteArray; CountType = uint16_t there, wrapping like std::plus)"""
         k, v = self.counts()
-        rec = np.zeros(len(k), dtype=np.dtype([("kmer", "<u8"), ("count", np.dtype(count_dtype).newbyteorder("<"))]))
+        # (k > 32: the 16-byte k-mer {w0, w1}, sizeof(Kmer<63, DNA, uint64_t>) + sizeof(CountType) per tuple)
+        kt = np.dtype(("<u8", (2,))) if self.wide else np.dtype("<u8")
+        rec = np.zeros(len(k), dtype=np.dtype([("kmer", kt), ("count", np.dtype(count_dtype).newbyteorder("<"))]))
         rec["kmer"] = k
         rec["count"] = v.astype(count_dtype)
         rec.tofile(filename)
