@@ -119,17 +119,26 @@ struct Block { char* p; size_t cap; };
 // histogram-free layout shared by the pieces of a streamed insert: every piece appends to the SAME slots (cursors, overflow flag
 // and the final buffer live across the feeds), so that the build at the end sees one source
 struct SlackShared { unsigned long long* cur2; uint64_t* starts; uint32_t* ovf; uint64_t slot; };
+// a slot buffer of either key width: typed (KhSlots / KwSlots) where it is made and where a kernel is launched -- narrow() / wide()
+struct SlotBuf {
+  void* p; uint64_t cap;
+  SlotBuf() : p(nullptr), cap(0) {}
+  SlotBuf(KhSlots s) : p(s.s), cap(s.cap) {}
+  SlotBuf(KwSlots s) : p(s.s), cap(s.cap) {}
+};
+// state of a table of either key width (kh_wtable below: the same state with 32-byte slots)
 struct kh_table {
-  int kind, hash, device;
-  KhSeed seed;      // storage hash seed + key transform (kh_set_key_transform)
-  hipStream_t stream;
-  float min_lf, max_lf;
-  uint64_t min_load, max_load, lsize;
-  KhSlots cur, spare;
+  int kind = KHK_RH, hash = 0, device = 0;
+  KhSeed seed = KhSeed{0, 0u};      // storage hash seed + key transform (kh_set_key_transform)
+  hipStream_t stream = nullptr;
+  float min_lf = 0.f, max_lf = 0.f;
+  uint64_t min_load = 0, max_load = 0, lsize = 0;
+  uint32_t slot_bytes = sizeof(KhSlot);      // sizeof(KwSlot): a wide table
+  SlotBuf cur, spare;
   // workspace arena (grow-only, reset per operation)
   std::vector<Block> blocks;
-  size_t blk, off;
-  uint64_t* hpin;   // pinned host scratch (64 x u64)
+  size_t blk = 0, off = 0;
+  uint64_t* hpin = nullptr;   // pinned host scratch (64 x u64)
   std::string err;
   // streamed insert (kh_insert_begin / feed / end)
   struct {
@@ -142,14 +151,15 @@ struct kh_table {
     ulonglong2 *tmp, *fin;
     KhSrcSet S;
     uint64_t* stage_k; uint32_t* stage_v;
-  } ins;
-  uint32_t* part_overflow;      // device flag of the histogram-free partition feeding the operation in flight (or null)
-  double batch_vf;              // variance factor E[m^2]/E[m] the duplicate sample gave for the batch in flight (1: no duplicate seen)
-  bool batch_nodup;             // a sample of the batch in flight found no duplicate key (k_sample_dups)
-  bool prof;
+  } ins = {};
+  uint32_t* part_overflow = nullptr;      // device flag of the histogram-free partition feeding the operation in flight (or null)
+  double batch_vf = 1.0;                  // variance factor E[m^2]/E[m] the duplicate sample gave for the batch in flight (1: no duplicate seen)
+  bool batch_nodup = false;               // a sample of the batch in flight found no duplicate key (k_sample_dups)
+  bool prof = false;
   std::vector<ProfRec> recs;
   std::vector<std::pair<std::string, std::pair<double, uint64_t> > > prof_acc;
 };
+struct kh_wtable : kh_table {};      // a distinct handle type for the C header; its kernels differ (kh_kernels_wide.h), its host state does not
 
 namespace {
 
@@ -218,7 +228,6 @@ kh_status arena_prepare(kh_table* t, size_t bytes) {
   t->blocks.push_back(b);
   return KH_OK;
 }
-void arena_consolidate(kh_table*) {}
 #define TAKE(ptr, type, count)                                                                  \
   do {                                                                                          \
     void* p__ = nullptr;                                                                        \
@@ -228,46 +237,62 @@ void arena_consolidate(kh_table*) {}
   } while (0)
 
 // ---- slots ---------------------------------------------------------------------------------------
+// One buffer lifecycle for both key widths: the buffers are held width-erased (SlotBuf) and typed where a kernel takes them.
 const KhSlots kNoSlots = KhSlots{nullptr, 0};
+inline bool is_wide(const kh_table* t) { return t->slot_bytes == sizeof(KwSlot); }
+inline KhSlots narrow(const SlotBuf& b) { return KhSlots{static_cast<KhSlot*>(b.p), b.cap}; }
+inline KwSlots wide(const SlotBuf& b) { return KwSlots{static_cast<KwSlot*>(b.p), b.cap}; }
 const bool g_poison = getenv("KH_DEBUG_POISON") != nullptr;      // test hook: destination buffers start as garbage
-void free_slots(kh_table* t, KhSlots& s) {
-  pool_free(t->device, s.s);
-  s = kNoSlots;
+void free_slots(kh_table* t, SlotBuf& s) {
+  pool_free(t->device, s.p);
+  s = SlotBuf();
 }
-kh_status alloc_slots(kh_table* t, uint64_t cap, KhSlots& s) {
-  s = kNoSlots;
-  hipError_t e = pool_alloc(t->device, std::max<uint64_t>(cap, 16) * sizeof(KhSlot), reinterpret_cast<void**>(&s.s));
-  if (e != hipSuccess) { s = kNoSlots; return fail(t, KH_ERR_NOMEM, std::string("table allocation: ") + hipGetErrorString(e)); }
+kh_status alloc_slots(kh_table* t, uint64_t cap, SlotBuf& s) {
+  s = SlotBuf();
+  hipError_t e = pool_alloc(t->device, std::max<uint64_t>(cap, 16) * t->slot_bytes, &s.p);
+  if (e != hipSuccess) { s = SlotBuf(); return fail(t, KH_ERR_NOMEM, std::string("table allocation: ") + hipGetErrorString(e)); }
   s.cap = cap;
   return KH_OK;
 }
-kh_status fill_empty(kh_table* t, KhSlots s) {
-  const uint32_t grid = (uint32_t)std::min<uint64_t>((s.cap + 255) / 256, 256 * 16);
-  if (t->kind == KHK_RH) hipLaunchKernelGGL((k_fill_empty<KHK_RH>), dim3(grid), dim3(256), 0, t->stream, s);
-  else hipLaunchKernelGGL((k_fill_empty<KHK_LP>), dim3(grid), dim3(256), 0, t->stream, s);
+inline dim3 slots_grid(uint64_t cap) { return dim3((uint32_t)std::min<uint64_t>((cap + 255) / 256, 256 * 16)); }
+kh_status fill_empty(kh_table* t, const SlotBuf& s) {
+  if (is_wide(t)) hipLaunchKernelGGL(kw_fill_empty, slots_grid(s.cap), dim3(256), 0, t->stream, wide(s));
+  else if (t->kind == KHK_RH) hipLaunchKernelGGL((k_fill_empty<KHK_RH>), slots_grid(s.cap), dim3(256), 0, t->stream, narrow(s));
+  else hipLaunchKernelGGL((k_fill_empty<KHK_LP>), slots_grid(s.cap), dim3(256), 0, t->stream, narrow(s));
   HIPCHK(hipGetLastError());
   return KH_OK;
 }
-// a destination buffer of capacity `cap`.  It is NOT cleared: a re-layout writes every slot of its destination, occupied or
-// empty, exactly once (the slices of the chunk workgroups tile the circular table), so clearing 16 B x capacity first
-// would only add a 2 GB memset per build of a 2^27-bucket table
-kh_status fresh_slots(kh_table* t, uint64_t cap, KhSlots& s) {
-  if (t->spare.cap == cap && t->spare.s) { s = t->spare; t->spare = kNoSlots; }
+// a destination buffer of capacity `cap`, as the typed view the caller launches with.  It is NOT cleared: a re-layout writes
+// every slot of its destination, occupied or empty, exactly once (the slices of the chunk workgroups tile the circular table),
+// so clearing 16 B x capacity first would only add a 2 GB memset per build of a 2^27-bucket table
+template <typename Slots>
+kh_status fresh_slots(kh_table* t, uint64_t cap, Slots& s) {
+  SlotBuf b;
+  if (t->spare.cap == cap && t->spare.p) { b = t->spare; t->spare = SlotBuf(); }
   else {
-    kh_status st = alloc_slots(t, cap, s);
+    kh_status st = alloc_slots(t, cap, b);
     if (st != KH_OK) return st;
   }
+  s = Slots{static_cast<decltype(s.s)>(b.p), cap};
   if (g_poison) {
-    hipLaunchKernelGGL(k_poison, dim3((uint32_t)std::min<uint64_t>((cap + 255) / 256, 4096)), dim3(256), 0, t->stream, s);
+    if (is_wide(t)) hipLaunchKernelGGL(kw_poison, slots_grid(cap), dim3(256), 0, t->stream, wide(b));
+    else hipLaunchKernelGGL(k_poison, slots_grid(cap), dim3(256), 0, t->stream, narrow(b));
     HIPCHK(hipGetLastError());
   }
   return KH_OK;
 }
-void retire_slots(kh_table* t, KhSlots& s) {   // keep one spare buffer for ping-pong rebuilds
-  if (!s.s) return;
-  if (t->spare.s) { hipStreamSynchronize(t->stream); free_slots(t, t->spare); }
+void retire_slots(kh_table* t, SlotBuf s) {   // keep one spare buffer for ping-pong rebuilds
+  if (!s.p) return;
+  if (t->spare.p) { hipStreamSynchronize(t->stream); free_slots(t, t->spare); }
   t->spare = s;
-  s = kNoSlots;
+}
+// a completed re-layout becomes the table; the buffer it replaces becomes the spare
+void adopt_slots(kh_table* t, SlotBuf nw) {
+  const SlotBuf old = t->cur;
+  t->cur = nw;
+  retire_slots(t, old);
+  t->min_load = threshold(nw.cap, t->min_lf);
+  t->max_load = threshold(nw.cap, t->max_lf);
 }
 
 // ---- profiling -----------------------------------------------------------------------------------
@@ -391,14 +416,87 @@ kh_status launch_fused(kh_table* t, int src, KhFusedParams& F, const KhSlots& nw
   return KH_OK;
 }
 
+// what the flags of a re-layout or a de-duplication mean to the caller (KH_OK: none is raised)
+const char* const kProbeOverflowText = "Robin Hood probe distance would exceed 127 (7-bit info field, hashmap_robinhood.hpp:142-144,556)";
+const char* const kDedupOverflowText = "internal: de-duplication set overflow";
+kh_status flags_status(kh_table* t, const uint32_t* f) {
+  if (f[KH_FLAG_PROBE_OVERFLOW]) return fail(t, KH_ERR_PROBE_OVERFLOW, kProbeOverflowText);
+  if (f[KH_FLAG_REGION_OVERFLOW]) return fail(t, KH_ERR_PROBE_OVERFLOW, "cluster longer than one chunk (2048 slots) without an empty slot");
+  if (f[KH_FLAG_COUNT_OVERFLOW]) return fail(t, KH_ERR_PROBE_OVERFLOW, "more than 65535 keys share one home bucket");
+  if (f[KH_FLAG_INTERNAL]) return fail(t, KH_ERR_HIP, kDedupOverflowText);
+  return KH_OK;
+}
+
+// what the general re-layout driver needs to know of a key width: the kernels' argument struct and the two chunk launches
+struct Narrow {
+  typedef KhSlots Slots; typedef KhRebuildParams Params;
+  static Slots view(const SlotBuf& b) { return narrow(b); }
+  static void set_seed(Params& P, const kh_table* t) { P.seed = t->seed; }
+  static void count(kh_table* t, uint32_t nch, const Params& P) {
+    Launch L(t, "k_chunk_count");
+    KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_chunk_count<KIND, HASH>), dim3(nch), dim3(KH_CHUNK_THREADS), 0, t->stream, P));
+  }
+  static void place(kh_table* t, uint32_t nch, const Params& P) {
+    Launch L(t, "k_chunk_place");
+    KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_chunk_place<KIND, HASH>), dim3(nch), dim3(KH_CHUNK_THREADS), 0, t->stream, P));
+  }
+};
+struct Wide {
+  typedef KwSlots Slots; typedef KwRebuildParams Params;
+  static Slots view(const SlotBuf& b) { return wide(b); }
+  static void set_seed(Params& P, const kh_table* t) { P.seed = t->seed.s; }
+  static void count(kh_table* t, uint32_t nch, const Params& P) {
+    Launch L(t, "kw_chunk_count");
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_chunk_count<HASH>), dim3(nch), dim3(KW_DD_THREADS), 0, t->stream, P));
+  }
+  static void place(kh_table* t, uint32_t nch, const Params& P) {
+    Launch L(t, "kw_chunk_place");
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_chunk_place<HASH>), dim3(nch), dim3(KW_DD_THREADS), 0, t->stream, P));
+  }
+};
+// The general re-layout into the fresh buffer nw: chunk count (unless `pre` has the counts) -> k_chunk_carry -> chunk place, then
+// nw becomes the table.  A raised flag leaves the table as it was and makes nw the spare.
+template <typename W>
+kh_status relayout(kh_table* t, typename W::Slots nw, const uint64_t* ck, const uint32_t* cv, const uint64_t* noff, const uint32_t* ncnt,
+                   uint32_t PB, bool drop_marked, const PreCount* pre) {
+  const uint32_t nch = nw.cap > KH_L ? (uint32_t)(nw.cap >> KH_LB) : 1u;
+  uint16_t* homecnt; long long *sumA, *sumN, *xcarry; KhMP* ptmp; uint32_t* flags;
+  if (pre) { homecnt = pre->homecnt; sumA = pre->sumA; sumN = pre->sumN; }
+  else { TAKE(homecnt, uint16_t, nw.cap); TAKE(sumA, long long, nch); TAKE(sumN, long long, nch); }
+  TAKE(xcarry, long long, nch);
+  TAKE(ptmp, KhMP, nch);
+  TAKE(flags, uint32_t, KH_NFLAGS);
+  HIPCHK(hipMemsetAsync(flags, 0, sizeof(uint32_t) * KH_NFLAGS, t->stream));
+  typename W::Params P;
+  memset(&P, 0, sizeof(P));
+  P.Old = W::view(t->cur); P.drop_marked = drop_marked ? 1 : 0; P.New = nw; P.ck = ck; P.cv = cv; P.noff = noff; P.ncnt = ncnt; P.PB = PB;
+  if (t->lsize == 0) P.Old.cap = 0;   // nothing to carry over: the chunk kernels skip the source scan
+  W::set_seed(P, t); P.homecnt = homecnt; P.sumA = sumA; P.sumN = sumN; P.xcarry = xcarry; P.flags = flags;
+  if (!pre) W::count(t, nch, P);
+  { Launch L(t, "k_chunk_carry");
+    hipLaunchKernelGGL(k_chunk_carry, dim3(1), dim3(1024), 0, t->stream, sumA, sumN, nch, (long long)nw.cap, xcarry, ptmp); }
+  W::place(t, nch, P);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(t->hpin, flags, sizeof(uint32_t) * KH_NFLAGS, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  const kh_status st = flags_status(t, reinterpret_cast<const uint32_t*>(t->hpin));
+  if (st != KH_OK) { retire_slots(t, nw); return st; }
+  adopt_slots(t, nw);
+  return KH_OK;
+}
+
 kh_status rebuild(kh_table* t, uint64_t new_cap, const uint64_t* ck, const uint32_t* cv, const uint64_t* noff,
                   const uint32_t* ncnt, uint32_t PB, bool drop_marked, uint64_t total_after, const PreCount* pre = nullptr) {
   if (total_after > new_cap)
     return fail(t, KH_ERR_FULL, "table would hold more elements than buckets (no slot to insert into)");
+  if (is_wide(t)) {      // the general driver is all a wide table has
+    KwSlots nw;
+    kh_status st = fresh_slots(t, new_cap, nw);
+    return st != KH_OK ? st : relayout<Wide>(t, nw, ck, cv, noff, ncnt, PB, drop_marked, nullptr);
+  }
   KhSlots nw;
   kh_status st = fresh_slots(t, new_cap, nw);
   if (st != KH_OK) return st;
-  const uint32_t nch = new_cap > KH_L ? (uint32_t)(new_cap >> KH_LB) : 1u;
   // ---- one-launch rebuild (k_build_fused with the current table as its source): Robin Hood, same or doubled capacity.
   // Speculative like the bulk build: a chunk denser than the staging area, a carry chain or a poll time-out raise a flag,
   // and the three-kernel path below redoes the work into the same buffer.
@@ -413,7 +511,7 @@ kh_status rebuild(kh_table* t, uint64_t new_cap, const uint64_t* ck, const uint3
     KhFusedParams F;
     memset(&F, 0, sizeof(F));
     F.PB = PB; F.mode = KH_DEDUP_FIRST;
-    F.R.Old = t->cur; F.R.drop_marked = drop_marked ? 1 : 0; F.R.ck = ck; F.R.cv = cv; F.R.noff = noff; F.R.ncnt = ncnt; F.R.PB = PB;
+    F.R.Old = narrow(t->cur); F.R.drop_marked = drop_marked ? 1 : 0; F.R.ck = ck; F.R.cv = cv; F.R.noff = noff; F.R.ncnt = ncnt; F.R.PB = PB;
     if (from_empty) F.R.Old.cap = 0;     // nothing to carry over: the source scan is skipped
     FusedRun run;
     // (the parked list of chunk 0 is its own: one partition per chunk)
@@ -422,85 +520,44 @@ kh_status rebuild(kh_table* t, uint64_t new_cap, const uint64_t* ck, const uint3
     bool bad = false;
     for (int i = 0; i < KH_NFLAGS; ++i) bad = bad || ff[i] != 0;
     if (!bad && t->hpin[0] == total_after) {
-      KhSlots old = t->cur;
-      t->cur = nw;
-      retire_slots(t, old);
-      t->min_load = threshold(new_cap, t->min_lf);
-      t->max_load = threshold(new_cap, t->max_lf);
+      adopt_slots(t, nw);
       return KH_OK;
     }
     if (getenv("KH_DEBUG_FUSED"))
       fprintf(stderr, "[kmerhash_amd] fused rebuild rejected: placed %llu expected %llu flags=%u %u %u %u %u\n", (unsigned long long)t->hpin[0],
               (unsigned long long)total_after, ff[0], ff[1], ff[2], ff[3], ff[4]);
     if (ff[KH_FLAG_PROBE_OVERFLOW] && !ff[KH_FLAG_FUSE_INVALID]) {   // a genuine 7-bit overflow: the general path would find the same
-      KhSlots tmp = nw;
-      retire_slots(t, tmp);
-      return fail(t, KH_ERR_PROBE_OVERFLOW, "Robin Hood probe distance would exceed 127 (7-bit info field, hashmap_robinhood.hpp:142-144,556)");
+      retire_slots(t, nw);
+      return fail(t, KH_ERR_PROBE_OVERFLOW, kProbeOverflowText);
     }
     t->blk = keep_blk; t->off = keep_off;      // scratch of the failed attempt is reused by the general path
   }
-  uint16_t* homecnt; long long *sumA, *sumN, *xcarry; KhMP* ptmp; uint32_t* flags;
-  if (pre) { homecnt = pre->homecnt; sumA = pre->sumA; sumN = pre->sumN; }
-  else { TAKE(homecnt, uint16_t, new_cap); TAKE(sumA, long long, nch); TAKE(sumN, long long, nch); }
-  TAKE(xcarry, long long, nch);
-  TAKE(ptmp, KhMP, nch);
-  TAKE(flags, uint32_t, KH_NFLAGS);
-  HIPCHK(hipMemsetAsync(flags, 0, sizeof(uint32_t) * KH_NFLAGS, t->stream));
-  KhRebuildParams P;
-  P.Old = t->cur; P.drop_marked = drop_marked ? 1 : 0; P.New = nw; P.ck = ck; P.cv = cv; P.noff = noff; P.ncnt = ncnt; P.PB = PB;
-  if (t->lsize == 0) P.Old.cap = 0;   // nothing to carry over: the chunk kernels skip the source scan
-  P.seed = t->seed; P.homecnt = homecnt; P.sumA = sumA; P.sumN = sumN; P.xcarry = xcarry; P.flags = flags;
-  if (!pre) { Launch L(t, "k_chunk_count");
-    KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_chunk_count<KIND, HASH>), dim3(nch), dim3(KH_CHUNK_THREADS), 0, t->stream, P)); }
-  { Launch L(t, "k_chunk_carry");
-    hipLaunchKernelGGL(k_chunk_carry, dim3(1), dim3(1024), 0, t->stream, sumA, sumN, nch, (long long)new_cap, xcarry, ptmp); }
-  { Launch L(t, "k_chunk_place");
-    KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_chunk_place<KIND, HASH>), dim3(nch), dim3(KH_CHUNK_THREADS), 0, t->stream, P)); }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(t->hpin, flags, sizeof(uint32_t) * KH_NFLAGS, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipStreamSynchronize(t->stream));
-  const uint32_t* f = reinterpret_cast<const uint32_t*>(t->hpin);
-  if (f[KH_FLAG_PROBE_OVERFLOW] || f[KH_FLAG_REGION_OVERFLOW] || f[KH_FLAG_COUNT_OVERFLOW] || f[KH_FLAG_INTERNAL]) {
-    KhSlots tmp = nw;
-    retire_slots(t, tmp);
-    if (f[KH_FLAG_PROBE_OVERFLOW])
-      return fail(t, KH_ERR_PROBE_OVERFLOW, "Robin Hood probe distance would exceed 127 (7-bit info field, hashmap_robinhood.hpp:142-144,556)");
-    if (f[KH_FLAG_REGION_OVERFLOW])
-      return fail(t, KH_ERR_PROBE_OVERFLOW, "cluster longer than one chunk (2048 slots) without an empty slot");
-    if (f[KH_FLAG_COUNT_OVERFLOW])
-      return fail(t, KH_ERR_PROBE_OVERFLOW, "more than 65535 keys share one home bucket");
-    return fail(t, KH_ERR_HIP, "internal: de-duplication set overflow");
-  }
-  KhSlots old = t->cur;
-  t->cur = nw;
-  retire_slots(t, old);
-  t->min_load = threshold(new_cap, t->min_lf);
-  t->max_load = threshold(new_cap, t->max_lf);
-  return KH_OK;
+  return relayout<Narrow>(t, nw, ck, cv, noff, ncnt, PB, drop_marked, pre);
 }
 
 // rehash(b): hashmap_robinhood.hpp:432-464 / hashmap_linearprobe.hpp:324-349
+// Robin Hood rehash to c buckets (a power of two): copy() re-inserts through insert(), which doubles whenever size >= max_load (:530);
+// the capacity that results is the doubling rule applied to `size` distinct inserts from c.
+inline uint64_t rh_rehash_capacity(uint64_t c, uint64_t size, float max_lf) {
+  if (size > 0) {
+    if (0 >= threshold(c, max_lf)) c <<= 1;
+    while (size > threshold(c, max_lf)) c <<= 1;
+  }
+  return c;
+}
+kh_status refuse_streaming(kh_table* t) { return fail(t, KH_ERR_INVALID, "a streamed insert is in progress (kh_insert_end first)"); }
 kh_status do_rehash(kh_table* t, uint64_t b) {
-  if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is in progress (kh_insert_end first)");
+  if (t->ins.active) return refuse_streaming(t);
   uint64_t n = next_pow2(b);
   if (n == t->cur.cap) return KH_OK;
   if (t->kind == KHK_RH) {
-    // RH copy() re-inserts through insert(), which doubles whenever size >= max_load (:530):
-    // the capacity that results is the doubling rule applied to lsize distinct inserts from n.
-    uint64_t c = n;
-    if (t->lsize > 0) {
-      if (0 >= threshold(c, t->max_lf)) c <<= 1;
-      while (t->lsize > threshold(c, t->max_lf)) c <<= 1;
-    }
-    n = c;
+    n = rh_rehash_capacity(n, t->lsize, t->max_lf);
     if (n == t->cur.cap) return KH_OK;
   } else if (t->lsize > n) {
     return fail(t, KH_ERR_FULL, "ERROR: did not find any place to insert.  should not have happend (hashmap_linearprobe.hpp:408)");
   }
   { kh_status ps = arena_prepare(t, ws_rebuild(n)); if (ps != KH_OK) return ps; }
-  kh_status st = rebuild(t, n, nullptr, nullptr, nullptr, nullptr, 0, false, t->lsize);
-  arena_consolidate(t);
-  return st;
+  return rebuild(t, n, nullptr, nullptr, nullptr, nullptr, 0, false, t->lsize);
 }
 kh_status do_reserve(kh_table* t, uint64_t n) {   // :421-426 / :313-318
   if (n > t->max_load) return do_rehash(t, static_cast<uint64_t>(static_cast<float>(n) / t->max_lf));
@@ -818,17 +875,13 @@ kh_status insert_finish(kh_table* t, KhSrcSet S, uint64_t n, uint32_t PB, uint64
     bool bad = S.rec12 && fd != n;
     for (int i = 0; i < KH_NFLAGS; ++i) bad = bad || ff[i] != 0;
     if (!bad && capacity_after(t, t->cur.cap, t->lsize, n, fd, flast) == cap_u) {
-      KhSlots old = t->cur;
-      t->cur = nw;
-      retire_slots(t, old);
-      t->min_load = threshold(cap_u, t->min_lf);
-      t->max_load = threshold(cap_u, t->max_lf);
+      adopt_slots(t, nw);
       t->lsize = fd;
       *n_new_out = fd;
       if (mode == INS_UPDATE) {
         KhDedupParams A;
         memset(&A, 0, sizeof(A));
-        A.src = S; A.T = t->cur; A.seed = t->seed; A.table_empty = 0; A.mode = KH_DEDUP_LAST;
+        A.src = S; A.T = narrow(t->cur); A.seed = t->seed; A.table_empty = 0; A.mode = KH_DEDUP_LAST;
         uint32_t* cn; TAKE(cn, uint32_t, R.nparts);
         A.cnt_new = cn; A.max_idx_plus1 = totals; A.flags = F.flags; A.count_cap = 0; A.PB = PB;
         Launch L(t, "k_dedup_assign");
@@ -866,7 +919,7 @@ kh_status insert_finish(kh_table* t, KhSrcSet S, uint64_t n, uint32_t PB, uint64
     F.base_size = t->lsize;
     // giving up early only makes sense if the smaller capacity is possible at all (an insert never shrinks the table)
     F.half_max_load = (cap_u >> 1) >= t->cur.cap ? threshold(cap_u >> 1, t->max_lf) : 0;
-    F.R.Old = t->cur; F.R.PB = PB;
+    F.R.Old = narrow(t->cur); F.R.PB = PB;
     FusedRun run;
     // (Robin Hood at equal capacity, one source of 16-byte records, a chunk's records fit two per lane: the ordered-stream kernel; else the staging form)
     const bool ordered = t->kind == KHK_RH && cap_u == t->cur.cap && S.n == 1 && S.rec12 == 0 &&
@@ -880,11 +933,7 @@ kh_status insert_finish(kh_table* t, KhSrcSet S, uint64_t n, uint32_t PB, uint64
     bool bad = total < t->lsize;
     for (int i = 0; i < KH_NFLAGS; ++i) bad = bad || ff[i] != 0;
     if (!bad && capacity_after(t, t->cur.cap, t->lsize, n, fd, flast) == cap_u) {
-      KhSlots old = t->cur;
-      t->cur = nw;
-      retire_slots(t, old);
-      t->min_load = threshold(cap_u, t->min_lf);
-      t->max_load = threshold(cap_u, t->max_lf);
+      adopt_slots(t, nw);
       t->lsize = total;
       *n_new_out = fd;
       return KH_OK;
@@ -914,7 +963,7 @@ kh_status insert_finish(kh_table* t, KhSrcSet S, uint64_t n, uint32_t PB, uint64
     TAKE(pre.homecnt, uint16_t, cap_u); TAKE(pre.sumA, long long, R.nparts); TAKE(pre.sumN, long long, R.nparts);
   }
   D.count_cap = fuse ? cap_u : 0; D.PB = PB; D.homecnt = pre.homecnt; D.sumA = pre.sumA; D.sumN = pre.sumN;
-  D.T = t->cur; D.seed = t->seed; D.table_empty = t->lsize == 0 ? 1 : 0; D.mode = mode == INS_PLUS ? KH_DEDUP_PLUS : KH_DEDUP_FIRST; D.flags = flags;
+  D.T = narrow(t->cur); D.seed = t->seed; D.table_empty = t->lsize == 0 ? 1 : 0; D.mode = mode == INS_PLUS ? KH_DEDUP_PLUS : KH_DEDUP_FIRST; D.flags = flags;
   D.xcd_group = 0;
   // Reducer = std::plus into a non-empty table: k_dedup only LISTS the sums of the keys the table already holds; they are added
   // (k_apply_plus) once nothing can discard this attempt any more -- a histogram-free partition that overflowed repeats the whole
@@ -960,10 +1009,10 @@ kh_status insert_finish(kh_table* t, KhSrcSet S, uint64_t n, uint32_t PB, uint64
   const uint64_t dnew = t->hpin[0];
   const uint64_t last_first = mode == INS_PLUS ? n - 1 : (t->hpin[1] ? t->hpin[1] - 1 : 0);
   if (reinterpret_cast<const uint32_t*>(t->hpin + 2)[KH_FLAG_INTERNAL])
-    return fail(t, KH_ERR_HIP, "internal: de-duplication set overflow");
+    return fail(t, KH_ERR_HIP, kDedupOverflowText);
   auto apply_plus = [&](int sign) {
     Launch L(t, "k_apply_plus");
-    hipLaunchKernelGGL(k_apply_plus, dim3(std::min<uint32_t>(R.nparts, 4096u)), dim3(256), 0, t->stream, t->cur.s, S.merged_off, (const uint32_t*)D.cnt_upd,
+    hipLaunchKernelGGL(k_apply_plus, dim3(std::min<uint32_t>(R.nparts, 4096u)), dim3(256), 0, t->stream, narrow(t->cur).s, S.merged_off, (const uint32_t*)D.cnt_upd,
                        (const uint64_t*)D.nk, (const uint32_t*)D.nv, R.nparts, sign);
   };
   if (plus_live) apply_plus(+1);
@@ -992,7 +1041,7 @@ kh_status insert_finish(kh_table* t, KhSrcSet S, uint64_t n, uint32_t PB, uint64
     t->lsize += dnew;
   }
   if (mode == INS_UPDATE) {   // update(k,v): existing keys take the value of their LAST occurrence in the batch
-    D.T = t->cur; D.table_empty = 0; D.mode = KH_DEDUP_LAST; D.count_cap = 0;
+    D.T = narrow(t->cur); D.table_empty = 0; D.mode = KH_DEDUP_LAST; D.count_cap = 0;
     Launch L(t, "k_dedup_assign");
     KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_dedup<KIND, HASH>), dim3(R.nparts), dim3(KH_CHUNK_THREADS), 0, t->stream, D));
     HIPCHK(hipGetLastError());
@@ -1044,7 +1093,7 @@ kh_status small_batch(kh_table* t, const char* kb, uint32_t kstride, const char*
   HIPCHK(hipMemsetAsync(out, 0, 16, t->stream));
   HIPCHK(hipMemsetAsync(flags, 0, sizeof(uint32_t) * KH_NFLAGS, t->stream));
   { Launch L(t, "k_small_batch");
-    KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_small_batch<KIND, HASH>), dim3(1), dim3(64), 0, t->stream, t->cur, kb, kstride, vb, vstride,
+    KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_small_batch<KIND, HASH>), dim3(1), dim3(64), 0, t->stream, narrow(t->cur), kb, kstride, vb, vstride,
                                                              vconst, n, op, t->seed, out, flags)); }
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(t->hpin, out, 16, hipMemcpyDeviceToHost, t->stream));
@@ -1082,7 +1131,7 @@ kh_status inplace_passes(kh_table* t, const KhInplaceParams& src, uint64_t n_max
   IpResult* res = reinterpret_cast<IpResult*>(z);
   uint32_t* cnt = reinterpret_cast<uint32_t*>(z + sizeof(IpResult));
   KhInplaceParams P = src;
-  P.T = t->cur; P.seed = t->seed; P.bins = bins; P.n_done = &res->done; P.n_in = &res->n_in; P.flags = res->flags;
+  P.T = narrow(t->cur); P.seed = t->seed; P.bins = bins; P.n_done = &res->done; P.n_in = &res->n_in; P.flags = res->flags;
   const uint32_t apply_grid = (regions + KH_IP_THREADS - 1) / KH_IP_THREADS;
   // pass 1: regions [r L, (r+1) L)
   P.ofs = 0; P.cnt = cnt; P.defer = defer1; P.n_defer = &res->defer1;
@@ -1148,7 +1197,7 @@ kh_status insert_inplace(kh_table* t, const char* kb, uint32_t kstride, const ch
   D.src = S;
   D.nk = const_cast<uint64_t*>(src.in_k); D.nv = const_cast<uint32_t*>(src.in_v);
   D.cnt_new = cnt_new; D.count_cap = 0; D.PB = PB;
-  D.T = t->cur; D.seed = t->seed; D.table_empty = 0; D.mode = mode == INS_PLUS ? KH_DEDUP_PLUS : KH_DEDUP_FIRST;
+  D.T = narrow(t->cur); D.seed = t->seed; D.table_empty = 0; D.mode = mode == INS_PLUS ? KH_DEDUP_PLUS : KH_DEDUP_FIRST;
   char* zpre;                   // k_dedup's scalar and flag words
   TAKE(zpre, char, 64);
   HIPCHK(hipMemsetAsync(zpre, 0, 64, t->stream));
@@ -1158,7 +1207,7 @@ kh_status insert_inplace(kh_table* t, const char* kb, uint32_t kstride, const ch
     KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_dedup<KIND, HASH>), dim3(R.nparts), dim3(KH_CHUNK_THREADS), 0, t->stream, D)); }
   if (mode == INS_PLUS) {      // sums of the keys the table already holds (listed by k_dedup; nothing can discard an in-place batch)
     Launch L(t, "k_apply_plus");
-    hipLaunchKernelGGL(k_apply_plus, dim3(std::min<uint32_t>(R.nparts, 4096u)), dim3(256), 0, t->stream, t->cur.s, (const uint64_t*)R.part_off, (const uint32_t*)D.cnt_upd,
+    hipLaunchKernelGGL(k_apply_plus, dim3(std::min<uint32_t>(R.nparts, 4096u)), dim3(256), 0, t->stream, narrow(t->cur).s, (const uint64_t*)R.part_off, (const uint32_t*)D.cnt_upd,
                        (const uint64_t*)D.nk, (const uint32_t*)D.nv, R.nparts, 1);
   }
   IpResult* res = nullptr;
@@ -1177,7 +1226,7 @@ kh_status insert_inplace(kh_table* t, const char* kb, uint32_t kstride, const ch
   const uint64_t dnew = h->n_in, placed = h->done;
   t->lsize += placed;
   *n_new_out = placed;
-  if (reinterpret_cast<const uint32_t*>(t->hpin + 32 + 4)[KH_FLAG_INTERNAL]) return fail(t, KH_ERR_HIP, "internal: de-duplication set overflow");
+  if (reinterpret_cast<const uint32_t*>(t->hpin + 32 + 4)[KH_FLAG_INTERNAL]) return fail(t, KH_ERR_HIP, kDedupOverflowText);
   if (placed != dnew || h->flags[KH_FLAG_PROBE_OVERFLOW])
     return fail(t, KH_ERR_PROBE_OVERFLOW, "Robin Hood probe distance would exceed 127 (7-bit info field, hashmap_robinhood.hpp:142-144,556); "
                                           "the keys of the batch that fit were applied in place");
@@ -1188,7 +1237,7 @@ kh_status do_insert(kh_table* t, const void* keys, uint32_t kstride, const void*
                     kh_mem where, int mode, uint64_t* n_inserted, bool tail_reserve = true) {
   if (n_inserted) *n_inserted = 0;
   if (n && !keys) return fail(t, KH_ERR_INVALID, "null keys");
-  if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is in progress (kh_insert_end first)");
+  if (t->ins.active) return refuse_streaming(t);
   HIPCHK(hipSetDevice(t->device));
   { const uint64_t np_ = std::min<uint64_t>(n, g_max_pass);       // (pairs of one internal pass: insert_device)
     const uint64_t cu = capacity_after(t, t->cur.cap, t->lsize, np_ ? np_ : 1, np_, np_ ? np_ - 1 : 0);
@@ -1248,14 +1297,13 @@ kh_status do_insert(kh_table* t, const void* keys, uint32_t kstride, const void*
   // kh_update stands for a sequence of update(k,v) calls (:1274), which has no such tail
   if (st == KH_OK && mode != INS_UPDATE && tail_reserve) st = do_reserve(t, t->lsize);
   if (st == KH_OK) HIPCHK(hipStreamSynchronize(t->stream));
-  arena_consolidate(t);
   if (n_inserted) *n_inserted = total_new;
   return st;
 }
 
-// generic compaction: flags/q/vals (device) -> out (device); returns the number of hits
+// generic compaction: flags/q/vals (device) -> out (device), keys of the table's width; returns the number of hits
 kh_status compact(kh_table* t, const uint8_t* flags, const uint64_t* q, const uint32_t* vals, uint64_t n,
-                  uint64_t* out_keys, uint32_t* out_vals, uint8_t* out_pairs, uint64_t* n_out) {
+                  uint64_t* out_keys, uint32_t* out_vals, uint64_t* n_out) {
   *n_out = 0;
   if (n == 0) return KH_OK;
   const uint64_t ntl = (n + KH_CMP_TILE - 1) / KH_CMP_TILE;
@@ -1265,14 +1313,33 @@ kh_status compact(kh_table* t, const uint8_t* flags, const uint64_t* q, const ui
     hipLaunchKernelGGL(k_flag_tile_sums, dim3((uint32_t)ntl), dim3(256), 0, t->stream, flags, n, sums); }
   { Launch L(t, "k_scan");
     hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, sums, ntl, offs); }
-  if (out_keys || out_pairs) {
+  if (is_wide(t)) {
+    Launch L(t, "kw_compact");
+    hipLaunchKernelGGL(kw_compact, dim3((uint32_t)ntl), dim3(256), 0, t->stream, flags, q, vals, n, (const uint64_t*)offs, out_keys, out_vals);
+  } else {
     Launch L(t, "k_compact_hits");
-    hipLaunchKernelGGL(k_compact_hits, dim3((uint32_t)ntl), dim3(256), 0, t->stream, flags, q, vals, n, offs, out_keys, out_vals, out_pairs);
+    hipLaunchKernelGGL(k_compact_hits, dim3((uint32_t)ntl), dim3(256), 0, t->stream, flags, q, vals, n, offs, out_keys, out_vals, (uint8_t*)nullptr);
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(t->hpin, offs + ntl, 8, hipMemcpyDeviceToHost, t->stream));
   HIPCHK(hipStreamSynchronize(t->stream));
   *n_out = t->hpin[0];
+  return KH_OK;
+}
+// host epilogue of a per-query find: found flags and, for the hits only, values (values of misses stay untouched in the caller's buffer)
+kh_status copy_hits_selective(kh_table* t, const uint32_t* dv, const uint8_t* df, uint64_t n, uint32_t* out_vals, uint8_t* out_found) {
+  std::vector<uint32_t> hv(out_vals ? n : 0); std::vector<uint8_t> hf(n);
+  if (out_vals) HIPCHK(hipMemcpyAsync(hv.data(), dv, n * 4, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipMemcpyAsync(hf.data(), df, n, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  for (uint64_t i = 0; i < n; ++i) { if (out_found) out_found[i] = hf[i]; if (hf[i] && out_vals) out_vals[i] = hv[i]; }
+  return KH_OK;
+}
+// host epilogue of a compacted find / to_vector: the first m (key, value) pairs, keys of the table's width (null: not wanted)
+kh_status copy_compacted(kh_table* t, uint64_t m, const uint64_t* ck, const uint32_t* cv, uint64_t* keys_host, uint32_t* vals_host) {
+  if (m && keys_host) HIPCHK(hipMemcpyAsync(keys_host, ck, m * (t->slot_bytes / 2), hipMemcpyDeviceToHost, t->stream));
+  if (m && vals_host) HIPCHK(hipMemcpyAsync(vals_host, cv, m * 4, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
   return KH_OK;
 }
 
@@ -1287,7 +1354,7 @@ kh_status launch_find(kh_table* t, int out_mode, const uint64_t* q, uint64_t n, 
   HIPCHK(hipMemsetAsync(ctl, 0, nctl * 8, t->stream));
   KhFindParams F;
   memset(&F, 0, sizeof(F));
-  F.T = t->cur; F.q = q; F.n = n; F.seed = t->seed;
+  F.T = narrow(t->cur); F.q = q; F.n = n; F.seed = t->seed;
   F.out_vals = dvals; F.out_found = dfound; F.out_keys = dkeys; F.out_pairs16 = dpairs;
   F.n_found = (out_mode == KH_FIND_COUNT && !hits_dev) ? nullptr : ctl;      // count(Iter,Iter) returns no total
   F.ticket = reinterpret_cast<uint32_t*>(ctl + 1); F.tile_state = ctl + 2;
@@ -1315,7 +1382,7 @@ kh_status launch_find(kh_table* t, int out_mode, const uint64_t* q, uint64_t n, 
 kh_status do_find(kh_table* t, const void* keys, uint64_t n, kh_mem where, uint32_t* out_vals, uint8_t* out_found,
                   uint64_t* out_ckeys, uint32_t* out_cvals, void* out_pairs, bool compacted, uint64_t* n_found) {
   if (n_found) *n_found = 0;
-  if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is in progress (kh_insert_end first)");
+  if (t->ins.active) return refuse_streaming(t);
   if (n == 0) return KH_OK;
   if (!keys) return fail(t, KH_ERR_INVALID, "null keys");
   HIPCHK(hipSetDevice(t->device));
@@ -1333,14 +1400,8 @@ kh_status do_find(kh_table* t, const void* keys, uint64_t n, kh_mem where, uint3
     st = launch_find(t, KH_FIND_PERQUERY, q, n, dv, df, nullptr, nullptr, &hits_dev);
     if (st != KH_OK) return st;
     HIPCHK(hipMemcpyAsync(t->hpin, hits_dev, 8, hipMemcpyDeviceToHost, t->stream));
-    if (host) {
-      // values of misses stay untouched in the caller's buffer: copy through a flag-selective host loop
-      std::vector<uint32_t> hv(out_vals ? n : 0); std::vector<uint8_t> hf(n);
-      if (out_vals) HIPCHK(hipMemcpyAsync(hv.data(), dv, n * 4, hipMemcpyDeviceToHost, t->stream));
-      HIPCHK(hipMemcpyAsync(hf.data(), df, n, hipMemcpyDeviceToHost, t->stream));
-      HIPCHK(hipStreamSynchronize(t->stream));
-      for (uint64_t i = 0; i < n; ++i) { if (out_found) out_found[i] = hf[i]; if (hf[i] && out_vals) out_vals[i] = hv[i]; }
-    } else if (n_found) HIPCHK(hipStreamSynchronize(t->stream));
+    if (host) { st = copy_hits_selective(t, dv, df, n, out_vals, out_found); if (st != KH_OK) return st; }
+    else if (n_found) HIPCHK(hipStreamSynchronize(t->stream));
     hits = t->hpin[0];
   } else {
     uint64_t* ck = out_ckeys; uint32_t* cv = out_cvals; uint8_t* cp = static_cast<uint8_t*>(out_pairs);
@@ -1355,23 +1416,18 @@ kh_status do_find(kh_table* t, const void* keys, uint64_t n, kh_mem where, uint3
     HIPCHK(hipStreamSynchronize(t->stream));
     hits = t->hpin[0];
     if (host && hits) {
-      if (out_pairs) HIPCHK(hipMemcpyAsync(out_pairs, cp, hits * 16, hipMemcpyDeviceToHost, t->stream));
-      else {
-        HIPCHK(hipMemcpyAsync(out_ckeys, ck, hits * 8, hipMemcpyDeviceToHost, t->stream));
-        HIPCHK(hipMemcpyAsync(out_cvals, cv, hits * 4, hipMemcpyDeviceToHost, t->stream));
-      }
-      HIPCHK(hipStreamSynchronize(t->stream));
+      if (out_pairs) { HIPCHK(hipMemcpyAsync(out_pairs, cp, hits * 16, hipMemcpyDeviceToHost, t->stream)); HIPCHK(hipStreamSynchronize(t->stream)); }
+      else { st = copy_compacted(t, hits, ck, cv, out_ckeys, out_cvals); if (st != KH_OK) return st; }
     }
   }
   if (n_found) *n_found = hits;
-  arena_consolidate(t);
   return KH_OK;
 }
 
 // erase_no_resize over a batch; the caller applies the form-specific resize rule
 kh_status erase_core(kh_table* t, const void* keys, uint64_t n, kh_mem where, uint64_t* n_erased) {
   *n_erased = 0;
-  if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is in progress (kh_insert_end first)");
+  if (t->ins.active) return refuse_streaming(t);
   if (n == 0) return KH_OK;
   if (!keys) return fail(t, KH_ERR_INVALID, "null keys");
   HIPCHK(hipSetDevice(t->device));
@@ -1428,7 +1484,7 @@ kh_status erase_core(kh_table* t, const void* keys, uint64_t n, kh_mem where, ui
     memset(&F, 0, sizeof(F));
     F.src.rec[0] = R.rec; F.src.off[0] = R.part_off; F.src.n = 1; F.src.merged_off = R.part_off; F.src.slot[0] = R.slot; F.src.cur[0] = R.cursor; F.src.rec12 = 2;
     F.PB = PBe; F.mode = KH_DEDUP_ERASE;
-    F.R.Old = t->cur; F.R.PB = PBe;
+    F.R.Old = narrow(t->cur); F.R.PB = PBe;
     FusedRun run;
     // (erase keys of a chunk fit one per lane -- a histogram-free partition's slot, or the mean of an exact one leaves room: the ordered-stream
     //  kernel, four workgroups per CU; else the staging form)
@@ -1439,9 +1495,7 @@ kh_status erase_core(kh_table* t, const void* keys, uint64_t n, kh_mem where, ui
     for (int i = 0; i < KH_NFLAGS; ++i) bad = bad || ff[i] != 0;
     const uint64_t placed = t->hpin[0];
     if (!bad && placed <= t->lsize) {
-      KhSlots old = t->cur;
-      t->cur = nw;
-      retire_slots(t, old);
+      adopt_slots(t, nw);
       *n_erased = t->lsize - placed;
       t->lsize = placed;
       return KH_OK;
@@ -1455,7 +1509,7 @@ kh_status erase_core(kh_table* t, const void* keys, uint64_t n, kh_mem where, ui
   TAKE(cnt, unsigned long long, 1);
   HIPCHK(hipMemsetAsync(cnt, 0, 8, t->stream));
   { Launch L(t, "k_erase_mark");
-    KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_erase_mark<KIND, HASH>), dim3(grid_for(n, KH_Q_THREADS * KH_Q_ITEMS, 2048)), dim3(KH_Q_THREADS), 0, t->stream, t->cur, q, n, t->seed, cnt)); }
+    KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_erase_mark<KIND, HASH>), dim3(grid_for(n, KH_Q_THREADS * KH_Q_ITEMS, 2048)), dim3(KH_Q_THREADS), 0, t->stream, narrow(t->cur), q, n, t->seed, cnt)); }
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(t->hpin, cnt, 8, hipMemcpyDeviceToHost, t->stream));
   HIPCHK(hipStreamSynchronize(t->stream));
@@ -1463,7 +1517,7 @@ kh_status erase_core(kh_table* t, const void* keys, uint64_t n, kh_mem where, ui
   if (ne && t->kind == KHK_RH) {
     st = rebuild(t, t->cur.cap, nullptr, nullptr, nullptr, nullptr, 0, true, t->lsize - ne);
     if (st != KH_OK) {        // the table keeps its elements: take the marks back
-      hipLaunchKernelGGL(k_clear_marks, dim3(grid_for(t->cur.cap, 256)), dim3(256), 0, t->stream, t->cur);
+      hipLaunchKernelGGL(k_clear_marks, dim3(grid_for(t->cur.cap, 256)), dim3(256), 0, t->stream, narrow(t->cur));
       hipStreamSynchronize(t->stream);
       return st;
     }
@@ -1474,6 +1528,29 @@ kh_status erase_core(kh_table* t, const void* keys, uint64_t n, kh_mem where, ui
 }
 
 bool valid(const kh_table* t) { return t != nullptr; }
+// the one place a table's state is set up: the first slot buffer (slot_bytes is set), pinned scratch, thresholds; the caller has
+// checked its arguments and made `device` current.  On an error nothing is left allocated.
+kh_status table_init(kh_table* t, int kind, int hash, uint64_t seed, uint64_t capacity, float min_lf, float max_lf, int device) {
+  t->kind = kind; t->hash = hash; t->device = device; t->seed = KhSeed{seed, 0u};
+  t->min_lf = min_lf; t->max_lf = max_lf;
+  const uint64_t cap = next_pow2(capacity);
+  if (alloc_slots(t, cap, t->cur) != KH_OK) return KH_ERR_NOMEM;
+  t->hpin = pinned_get();
+  if (!t->hpin) { free_slots(t, t->cur); return KH_ERR_NOMEM; }
+  if (fill_empty(t, t->cur) != KH_OK || hipStreamSynchronize(t->stream) != hipSuccess) { free_slots(t, t->cur); pinned_put(t->hpin); return KH_ERR_HIP; }
+  t->min_load = threshold(cap, min_lf);
+  t->max_load = threshold(cap, max_lf);
+  return KH_OK;
+}
+void table_release(kh_table* t) {
+  if (!t) return;
+  hipSetDevice(t->device);
+  hipStreamSynchronize(t->stream);
+  for (auto& r : t->recs) { event_put(t->device, r.a); event_put(t->device, r.b); }
+  free_slots(t, t->cur); free_slots(t, t->spare);
+  for (auto& b : t->blocks) pool_free(t->device, b.p);
+  pinned_put(t->hpin);
+}
 
 }  // namespace
 
@@ -1503,33 +1580,13 @@ kh_status kh_create(kh_table** out, kh_kind kind, uint32_t key_bytes, uint32_t v
   if (device < 0 || device >= ndev) return KH_ERR_INVALID;
   if (hipSetDevice(device) != hipSuccess) return KH_ERR_HIP;
   kh_table* t = new kh_table();
-  t->kind = (int)kind; t->hash = (int)hash; t->device = device; t->seed = KhSeed{seed, 0u}; t->stream = nullptr;
-  t->min_lf = min_lf; t->max_lf = max_lf; t->lsize = 0;
-  t->cur = kNoSlots; t->spare = t->cur;
-  t->blk = 0; t->off = 0; t->hpin = nullptr; t->prof = false; t->part_overflow = nullptr; t->batch_nodup = false; t->batch_vf = 1.0;
-  memset(&t->ins, 0, sizeof(t->ins));
-  const uint64_t cap = next_pow2(capacity);
-  if (alloc_slots(t, cap, t->cur) != KH_OK) { delete t; return KH_ERR_NOMEM; }
-  t->hpin = pinned_get();
-  if (!t->hpin) { free_slots(t, t->cur); delete t; return KH_ERR_NOMEM; }
-  if (fill_empty(t, t->cur) != KH_OK || hipStreamSynchronize(t->stream) != hipSuccess) { free_slots(t, t->cur); pinned_put(t->hpin); delete t; return KH_ERR_HIP; }
-  t->min_load = threshold(cap, min_lf);
-  t->max_load = threshold(cap, max_lf);
+  const kh_status st = table_init(t, (int)kind, (int)hash, seed, capacity, min_lf, max_lf, device);
+  if (st != KH_OK) { delete t; return st; }
   *out = t;
   return KH_OK;
 }
 
-kh_status kh_destroy(kh_table* t) {
-  if (!t) return KH_OK;
-  hipSetDevice(t->device);
-  hipStreamSynchronize(t->stream);
-  for (auto& r : t->recs) { event_put(t->device, r.a); event_put(t->device, r.b); }
-  free_slots(t, t->cur); free_slots(t, t->spare);
-  for (auto& b : t->blocks) pool_free(t->device, b.p);
-  pinned_put(t->hpin);
-  delete t;
-  return KH_OK;
-}
+kh_status kh_destroy(kh_table* t) { table_release(t); delete t; return KH_OK; }
 
 kh_status kh_set_stream(kh_table* t, void* s) {
   if (!valid(t)) return KH_ERR_INVALID;
@@ -1560,7 +1617,7 @@ kh_status kh_get_load_factors(const kh_table* t, float* mn, float* mx, float* cu
 }
 kh_status kh_clear(kh_table* t) {
   if (!t) return KH_ERR_INVALID;
-  if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is in progress (kh_insert_end first)");
+  if (t->ins.active) return refuse_streaming(t);
   HIPCHK(hipSetDevice(t->device));
   t->lsize = 0;
   { kh_status fs = fill_empty(t, t->cur); if (fs != KH_OK) return fs; }
@@ -1760,7 +1817,7 @@ kh_status kh_insert_reduce_plus(kh_table* t, const void* keys, const void* vals,
 
 kh_status kh_count(kh_table* t, const void* keys, uint64_t n, kh_mem where, uint8_t* out01) {
   if (!t) return KH_ERR_INVALID;
-  if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is in progress (kh_insert_end first)");
+  if (t->ins.active) return refuse_streaming(t);
   if (n == 0) return KH_OK;
   if (!keys || !out01) return fail(t, KH_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(t->device));
@@ -1776,7 +1833,6 @@ kh_status kh_count(kh_table* t, const void* keys, uint64_t n, kh_mem where, uint
     HIPCHK(hipMemcpyAsync(out01, d, n, hipMemcpyDeviceToHost, t->stream));
     HIPCHK(hipStreamSynchronize(t->stream));
   }
-  arena_consolidate(t);
   return KH_OK;
 }
 
@@ -1800,12 +1856,11 @@ kh_status kh_erase(kh_table* t, const void* keys, uint64_t n, kh_mem where, uint
   uint64_t ne = 0;
   kh_status st = erase_core(t, keys, n, where, &ne);
   if (n_erased) *n_erased = ne;
-  if (st != KH_OK) { arena_consolidate(t); return st; }
+  if (st != KH_OK) return st;
   if (t->lsize < t->min_load) {
     if (t->kind == KHK_RH) st = do_reserve(t, t->lsize);   // hashmap_robinhood.hpp:1437: reserve() only grows
     else st = do_rehash(t, static_cast<uint64_t>(static_cast<float>(t->lsize) / t->max_lf));   // hashmap_linearprobe.hpp:1048
   }
-  arena_consolidate(t);
   return st;
 }
 kh_status kh_erase_one(kh_table* t, uint64_t key, uint64_t* n_erased) {
@@ -1814,18 +1869,18 @@ kh_status kh_erase_one(kh_table* t, uint64_t key, uint64_t* n_erased) {
   kh_status st = erase_core(t, &key, 1, KH_MEM_HOST, &ne);
   if (n_erased) *n_erased = ne;
   if (st == KH_OK && t->lsize < t->min_load) st = do_rehash(t, t->cur.cap >> 1);   // :1425 / :1036
-  arena_consolidate(t);
   return st;
 }
 
 }  // extern "C"
 namespace {
-// SoA view of the current table in the workspace (any of keys / vals / info / flags may be null)
+// SoA view of the current table in the workspace (any of keys / vals / info / flags may be null; a wide table: two words per key)
 kh_status unpack(kh_table* t, uint64_t* k, uint32_t* v, uint8_t* info, uint8_t* flags) {
   const uint64_t cap = t->cur.cap;
   Launch L(t, "k_unpack_slots");
-  if (t->kind == KHK_RH) hipLaunchKernelGGL((k_unpack_slots<KHK_RH>), dim3(grid_for(cap, 256)), dim3(256), 0, t->stream, t->cur.s, cap, k, v, info, flags);
-  else hipLaunchKernelGGL((k_unpack_slots<KHK_LP>), dim3(grid_for(cap, 256)), dim3(256), 0, t->stream, t->cur.s, cap, k, v, info, flags);
+  if (is_wide(t)) hipLaunchKernelGGL(kw_unpack_slots, dim3(grid_for(cap, 256)), dim3(256), 0, t->stream, (const KwSlot*)wide(t->cur).s, cap, k, v, info, flags);
+  else if (t->kind == KHK_RH) hipLaunchKernelGGL((k_unpack_slots<KHK_RH>), dim3(grid_for(cap, 256)), dim3(256), 0, t->stream, narrow(t->cur).s, cap, k, v, info, flags);
+  else hipLaunchKernelGGL((k_unpack_slots<KHK_LP>), dim3(grid_for(cap, 256)), dim3(256), 0, t->stream, narrow(t->cur).s, cap, k, v, info, flags);
   HIPCHK(hipGetLastError());
   return KH_OK;
 }
@@ -1833,27 +1888,25 @@ kh_status unpack(kh_table* t, uint64_t* k, uint32_t* v, uint8_t* info, uint8_t* 
 extern "C" {
 kh_status kh_to_vector(kh_table* t, uint64_t* keys_host, uint32_t* vals_host, uint64_t* n_out) {
   if (!t) return KH_ERR_INVALID;
-  if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is in progress (kh_insert_end first)");
+  if (t->ins.active) return refuse_streaming(t);
   HIPCHK(hipSetDevice(t->device));
-  { kh_status ps = arena_prepare(t, t->cur.cap * 26 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
-  const uint64_t cap = t->cur.cap;
+  const uint64_t cap = t->cur.cap, kw = t->slot_bytes / sizeof(KhSlot);      // words per key
+  { kh_status ps = arena_prepare(t, cap * (10 + 16 * kw) + cap / KH_CMP_TILE * 12 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
   uint8_t* flags; uint64_t *sk, *ck; uint32_t *sv, *cv;
-  TAKE(flags, uint8_t, cap); TAKE(sk, uint64_t, cap); TAKE(sv, uint32_t, cap); TAKE(ck, uint64_t, cap); TAKE(cv, uint32_t, cap);
+  TAKE(flags, uint8_t, cap); TAKE(sk, uint64_t, kw * cap); TAKE(sv, uint32_t, cap); TAKE(ck, uint64_t, kw * cap); TAKE(cv, uint32_t, cap);
   kh_status st = unpack(t, sk, sv, nullptr, flags);
   if (st != KH_OK) return st;
   uint64_t m = 0;
-  st = compact(t, flags, sk, sv, cap, ck, cv, nullptr, &m);
+  st = compact(t, flags, sk, sv, cap, ck, cv, &m);
   if (st != KH_OK) return st;
-  if (m && keys_host) HIPCHK(hipMemcpyAsync(keys_host, ck, m * 8, hipMemcpyDeviceToHost, t->stream));
-  if (m && vals_host) HIPCHK(hipMemcpyAsync(vals_host, cv, m * 4, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipStreamSynchronize(t->stream));
+  st = copy_compacted(t, m, ck, cv, keys_host, vals_host);
+  if (st != KH_OK) return st;
   if (n_out) *n_out = m;
-  arena_consolidate(t);
   return KH_OK;
 }
 kh_status kh_export_info(kh_table* t, uint8_t* out_host) {
   if (!t || !out_host) return KH_ERR_INVALID;
-  if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is in progress (kh_insert_end first)");
+  if (t->ins.active) return refuse_streaming(t);
   HIPCHK(hipSetDevice(t->device));
   { kh_status ps = arena_prepare(t, t->cur.cap + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
   uint8_t* info;
@@ -1866,7 +1919,7 @@ kh_status kh_export_info(kh_table* t, uint8_t* out_host) {
 }
 kh_status kh_export_slots(kh_table* t, uint64_t* keys_host, uint32_t* vals_host) {
   if (!t) return KH_ERR_INVALID;
-  if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is in progress (kh_insert_end first)");
+  if (t->ins.active) return refuse_streaming(t);
   HIPCHK(hipSetDevice(t->device));
   { kh_status ps = arena_prepare(t, t->cur.cap * 12 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
   uint64_t* sk; uint32_t* sv;
@@ -1880,9 +1933,9 @@ kh_status kh_export_slots(kh_table* t, uint64_t* keys_host, uint32_t* vals_host)
 }
 kh_status kh_export_raw_slots(kh_table* t, void* out_host) {
   if (!t || !out_host) return KH_ERR_INVALID;
-  if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is in progress (kh_insert_end first)");
+  if (t->ins.active) return refuse_streaming(t);
   HIPCHK(hipSetDevice(t->device));
-  HIPCHK(hipMemcpyAsync(out_host, t->cur.s, t->cur.cap * sizeof(KhSlot), hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipMemcpyAsync(out_host, narrow(t->cur).s, t->cur.cap * sizeof(KhSlot), hipMemcpyDeviceToHost, t->stream));
   HIPCHK(hipStreamSynchronize(t->stream));
   return KH_OK;
 }
@@ -1890,14 +1943,15 @@ kh_status kh_displacement_histogram(kh_table* t, uint64_t out[128]) {
   if (!t || !out) return KH_ERR_INVALID;
   for (int i = 0; i < 128; ++i) out[i] = 0;
   if (t->kind != KHK_RH) return KH_OK;
-  if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is in progress (kh_insert_end first)");
+  if (t->ins.active) return refuse_streaming(t);
   HIPCHK(hipSetDevice(t->device));
   { kh_status ps = arena_prepare(t, size_t(1) << 20); if (ps != KH_OK) return ps; }
   unsigned long long* d;
   TAKE(d, unsigned long long, 128);
   HIPCHK(hipMemsetAsync(d, 0, 128 * 8, t->stream));
   { Launch L(t, "k_disp_hist");
-    hipLaunchKernelGGL(k_disp_hist, dim3(grid_for(t->cur.cap, 256, 1024)), dim3(256), 0, t->stream, t->cur.s, t->cur.cap, d); }
+    if (is_wide(t)) hipLaunchKernelGGL(kw_disp_hist, dim3(grid_for(t->cur.cap, 256, 1024)), dim3(256), 0, t->stream, (const KwSlot*)wide(t->cur).s, t->cur.cap, d);
+    else hipLaunchKernelGGL(k_disp_hist, dim3(grid_for(t->cur.cap, 256, 1024)), dim3(256), 0, t->stream, narrow(t->cur).s, t->cur.cap, d); }
   HIPCHK(hipMemcpyAsync(out, d, 128 * 8, hipMemcpyDeviceToHost, t->stream));
   HIPCHK(hipStreamSynchronize(t->stream));
   return KH_OK;
@@ -1907,6 +1961,28 @@ kh_status kh_displacement_histogram(kh_table* t, uint64_t out[128]) {
 namespace {
 inline bool xform_ok(kh_key_transform xf, uint32_t k) { return xf == KH_XF_IDENTITY || (xf == KH_XF_DNA_LEX_LESS && k >= 1 && k <= 32); }
 inline KhSeed make_seed(uint64_t seed, kh_key_transform xf, uint32_t k) { return KhSeed{seed, xf == KH_XF_DNA_LEX_LESS ? k : 0u}; }
+// Hash::operator()(Key const*, count, out) for keys of kw 64-bit words: stage host keys in, hash, copy the hashes out
+kh_status hash_batch_impl(uint32_t kw, kh_hash hash, KhSeed seed, const void* keys, uint64_t n, kh_mem where, uint64_t* out, int device, void* stream_) {
+  kh_table* t = nullptr;
+  if (n == 0) return KH_OK;
+  if (!keys || !out || (int)hash < 0 || (int)hash > 3) return KH_ERR_INVALID;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK(hipSetDevice(device));
+  const uint64_t* dk = static_cast<const uint64_t*>(keys);
+  uint64_t* dout = out; uint64_t* tmp = nullptr;
+  if (where == KH_MEM_HOST) {
+    HIPCHK(pool_alloc(device, n * 8 * (kw + 1), reinterpret_cast<void**>(&tmp)));
+    HIPCHK(hipMemcpyAsync(tmp, keys, n * 8 * kw, hipMemcpyHostToDevice, stream));
+    dk = tmp; dout = tmp + kw * n;
+  }
+  if (kw == 2) { KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((kw_hash_batch<HASH>), dim3(grid_for(n, 256)), dim3(256), 0, stream, dk, n, seed.s, dout)); }
+  else { KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_hash_batch<HASH>), dim3(grid_for(n, 256)), dim3(256), 0, stream, dk, n, seed, dout)); }
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && where == KH_MEM_HOST) e = hipMemcpyAsync(out, dout, n * 8, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && where == KH_MEM_HOST) e = hipStreamSynchronize(stream);
+  if (tmp) pool_free(device, tmp);
+  return e == hipSuccess ? KH_OK : KH_ERR_HIP;
+}
 }
 extern "C" {
 kh_status kh_set_key_transform(kh_table* t, kh_key_transform xf, uint32_t k) {
@@ -1927,25 +2003,8 @@ kh_status kh_hash_batch(kh_hash hash, uint64_t seed, const void* keys, uint64_t 
 }
 kh_status kh_hash_batch_transformed(kh_hash hash, uint64_t seed_, kh_key_transform xf, uint32_t k, const void* keys, uint64_t n, kh_mem where,
                                     uint64_t* out, int device, void* stream_) {
-  kh_table* t = nullptr;
-  if (n == 0) return KH_OK;
-  if (!keys || !out || (int)hash < 0 || (int)hash > 3 || !xform_ok(xf, k)) return KH_ERR_INVALID;
-  const KhSeed seed = make_seed(seed_, xf, k);
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
-  const uint64_t* dk = static_cast<const uint64_t*>(keys);
-  uint64_t* dout = out; uint64_t* tmp = nullptr;
-  if (where == KH_MEM_HOST) {
-    HIPCHK(pool_alloc(device, n * 16, reinterpret_cast<void**>(&tmp)));
-    HIPCHK(hipMemcpyAsync(tmp, keys, n * 8, hipMemcpyHostToDevice, stream));
-    dk = tmp; dout = tmp + n;
-  }
-  KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_hash_batch<HASH>), dim3(grid_for(n, 256)), dim3(256), 0, stream, dk, n, seed, dout));
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && where == KH_MEM_HOST) e = hipMemcpyAsync(out, dout, n * 8, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess && where == KH_MEM_HOST) e = hipStreamSynchronize(stream);
-  if (tmp) pool_free(device, tmp);
-  return e == hipSuccess ? KH_OK : KH_ERR_HIP;
+  if (n && !xform_ok(xf, k)) return KH_ERR_INVALID;
+  return hash_batch_impl(1, hash, make_seed(seed_, xf, k), keys, n, where, out, device, stream_);
 }
 
 kh_status kh_shard_permute(kh_hash hash, uint64_t seed, uint32_t p, const uint64_t* keys, const uint32_t* vals, uint64_t n,
@@ -2093,12 +2152,12 @@ void kh_shard_plan_destroy(kh_shard_plan* P) {
 // ---- k-mer generation front end ----------------------------------------------------------------------
 }  // extern "C"
 namespace {
-// shared body of kh_kmers_from_sequence / kh_kmers_from_fastq
-kh_status kmers_impl(const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq,
+// shared body of kh_kmers[128]_from_sequence / kh_kmers[128]_from_fastq; kw: 64-bit words per k-mer (1: k <= 32, 2: k <= 64)
+kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq,
                      uint64_t* out_kmers, uint64_t* n_out, int device, void* stream_) {
   kh_table* t = nullptr;
   if (n_out) *n_out = 0;
-  if (k < 1 || k > 32 || !n_out) return KH_ERR_INVALID;
+  if (k < 1 || k > 32 * kw || !n_out) return KH_ERR_INVALID;
   if (n < k) return KH_OK;
   if (!seq || !out_kmers) return KH_ERR_INVALID;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -2108,8 +2167,9 @@ kh_status kmers_impl(const void* seq, uint64_t n, uint32_t k, int canonical, kh_
   // one pooled block: [text copy (host input)] [masked text (FASTQ)] [tile sums] [tile offsets] [compacted out (host output)]
   const size_t sz_seq = where == KH_MEM_HOST ? ((n + 255) & ~size_t(255)) : 0;
   const size_t sz_msk = fastq ? ((n + 255) & ~size_t(255)) : 0;
-  const size_t sz_sum = ((ntl * 4 + 255) & ~size_t(255)), sz_off = (ntl + 1) * 8;
-  const size_t sz_out = where == KH_MEM_HOST ? n * 8 : 0;
+  const uint64_t nt = std::max(ntl, nkt);
+  const size_t sz_sum = ((nt * 4 + 255) & ~size_t(255)), sz_off = (nt + 1) * 8;
+  const size_t sz_out = where == KH_MEM_HOST ? n * 8 * kw : 0;
   char* blk = nullptr;
   HIPCHK(pool_alloc(device, sz_seq + sz_msk + sz_sum + sz_off + 256 + sz_out, reinterpret_cast<void**>(&blk)));
   const uint8_t* dseq = static_cast<const uint8_t*>(seq);
@@ -2129,9 +2189,12 @@ kh_status kmers_impl(const void* seq, uint64_t n, uint32_t k, int canonical, kh_
       dseq = msk;
     }
     // two passes over the text: valid windows per tile, scan, then the windows themselves, compacted and in order
-    hipLaunchKernelGGL(k_kmers_count, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
+    if (kw == 2) hipLaunchKernelGGL(kw_kmers_count, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
+    else hipLaunchKernelGGL(k_kmers_count, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
     hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, sums, nkt, offs);
-    if (canonical) hipLaunchKernelGGL((k_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
+    if (kw == 2 && canonical) hipLaunchKernelGGL((kw_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
+    else if (kw == 2) hipLaunchKernelGGL((kw_kmers_emit<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
+    else if (canonical) hipLaunchKernelGGL((k_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
     else hipLaunchKernelGGL((k_kmers_emit<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
     e = hipGetLastError();
   }
@@ -2139,7 +2202,7 @@ kh_status kmers_impl(const void* seq, uint64_t n, uint32_t k, int canonical, kh_
   if (e == hipSuccess) e = hipMemcpyAsync(&total, offs + nkt, 8, hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
   if (e == hipSuccess && where == KH_MEM_HOST && total) {
-    e = hipMemcpyAsync(out_kmers, dout, total * 8, hipMemcpyDeviceToHost, stream);
+    e = hipMemcpyAsync(out_kmers, dout, total * 8 * kw, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
   }
   pool_free(device, blk);
@@ -2151,11 +2214,11 @@ kh_status kmers_impl(const void* seq, uint64_t n, uint32_t k, int canonical, kh_
 extern "C" {
 kh_status kh_kmers_from_sequence(const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where,
                                  uint64_t* out_kmers, uint64_t* n_out, int device, void* stream_) {
-  return kmers_impl(seq, n, k, canonical, where, false, out_kmers, n_out, device, stream_);
+  return kmers_impl(1, seq, n, k, canonical, where, false, out_kmers, n_out, device, stream_);
 }
 kh_status kh_kmers_from_fastq(const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where,
                               uint64_t* out_kmers, uint64_t* n_out, int device, void* stream_) {
-  return kmers_impl(text, n, k, canonical, where, true, out_kmers, n_out, device, stream_);
+  return kmers_impl(1, text, n, k, canonical, where, true, out_kmers, n_out, device, stream_);
 }
 
 // ---- HyperLogLog (hyperloglog64.hpp) --------------------------------------------------------------
@@ -2308,103 +2371,12 @@ extern "C" int kh_debug_trace(unsigned long long* out) { return (int)hipMemcpyFr
 
 // ===================================================================================================
 // Wide keys: the 16-byte-key Robin Hood table (kh_wtable) and the 128-bit k-mer front end (kernels: kh_kernels_wide.h).
-// The table state machine is the 64-bit table's, rule for rule: the shared state (load factors, float thresholds, size, stream,
-// workspace arena, pinned scratch, last error) IS a kh_table, so capacity_after / threshold / the device pool / the arena are used
-// unchanged.  Only the general path exists: partition -> kw_dedup -> capacity decision -> kw_chunk_count / k_chunk_carry /
-// kw_chunk_place into a fresh buffer; the old buffer stays current until the new one is complete, so a failing batch leaves the
-// table unchanged.
+// A kh_wtable IS a kh_table with 32-byte slots: buffer lifecycle, capacity rules, the general re-layout driver, the host epilogues
+// and every state accessor are the 64-bit table's own code.  What is wide-only is below: the insert pass (partition -> kw_dedup ->
+// capacity decision -> rebuild), the probing find and the mark-and-re-lay-out erase.  The old buffer stays current until the new
+// one is complete, so a failing batch leaves the table unchanged.
 // ===================================================================================================
-struct kh_wtable {
-  kh_table b;          // shared state (b.cur / b.spare stay empty: the slots of a wide table are cur / spare below)
-  KwSlots cur, spare;
-};
 namespace {
-const KwSlots kNoWSlots = KwSlots{nullptr, 0};
-kh_status kw_alloc(kh_table* t, uint64_t cap, KwSlots& s) {
-  s = kNoWSlots;
-  hipError_t e = pool_alloc(t->device, std::max<uint64_t>(cap, 16) * sizeof(KwSlot), reinterpret_cast<void**>(&s.s));
-  if (e != hipSuccess) { s = kNoWSlots; return fail(t, KH_ERR_NOMEM, std::string("table allocation: ") + hipGetErrorString(e)); }
-  s.cap = cap;
-  return KH_OK;
-}
-void kw_free(kh_table* t, KwSlots& s) { pool_free(t->device, s.s); s = kNoWSlots; }
-kh_status kw_fill(kh_table* t, KwSlots s) {
-  hipLaunchKernelGGL(kw_fill_empty, dim3(grid_for(s.cap, 256)), dim3(256), 0, t->stream, s);
-  HIPCHK(hipGetLastError());
-  return KH_OK;
-}
-kh_status kw_fresh(kh_wtable* w, uint64_t cap, KwSlots& s) {      // destination of a re-layout: every slot is written once, no clearing
-  kh_table* t = &w->b;
-  if (w->spare.cap == cap && w->spare.s) { s = w->spare; w->spare = kNoWSlots; }
-  else { kh_status st = kw_alloc(t, cap, s); if (st != KH_OK) return st; }
-  if (g_poison) { hipLaunchKernelGGL(kw_poison, dim3(grid_for(cap, 256)), dim3(256), 0, t->stream, s); HIPCHK(hipGetLastError()); }
-  return KH_OK;
-}
-void kw_retire(kh_wtable* w, KwSlots& s) {
-  if (!s.s) return;
-  if (w->spare.s) { hipStreamSynchronize(w->b.stream); kw_free(&w->b, w->spare); }
-  w->spare = s;
-  s = kNoWSlots;
-}
-
-// re-layout (live elements of cur, minus the marked ones) U (new distinct elements) at capacity new_cap into a fresh buffer
-kh_status kw_rebuild(kh_wtable* w, uint64_t new_cap, const uint64_t* ck, const uint32_t* cv, const uint64_t* noff, const uint32_t* ncnt,
-                     uint32_t PB, bool drop_marked, uint64_t total_after) {
-  kh_table* t = &w->b;
-  if (total_after > new_cap) return fail(t, KH_ERR_FULL, "table would hold more elements than buckets (no slot to insert into)");
-  KwSlots nw;
-  kh_status st = kw_fresh(w, new_cap, nw);
-  if (st != KH_OK) return st;
-  const uint32_t nch = new_cap > KH_L ? (uint32_t)(new_cap >> KH_LB) : 1u;
-  uint16_t* homecnt; long long *sumA, *sumN, *xcarry; KhMP* ptmp; uint32_t* flags;
-  TAKE(homecnt, uint16_t, new_cap); TAKE(sumA, long long, nch); TAKE(sumN, long long, nch); TAKE(xcarry, long long, nch);
-  TAKE(ptmp, KhMP, nch); TAKE(flags, uint32_t, KH_NFLAGS);
-  HIPCHK(hipMemsetAsync(flags, 0, sizeof(uint32_t) * KH_NFLAGS, t->stream));
-  KwRebuildParams P;
-  memset(&P, 0, sizeof(P));
-  P.Old = w->cur; P.drop_marked = drop_marked ? 1 : 0; P.New = nw; P.ck = ck; P.cv = cv; P.noff = noff; P.ncnt = ncnt; P.PB = PB;
-  if (t->lsize == 0) P.Old.cap = 0;
-  P.seed = t->seed.s; P.homecnt = homecnt; P.sumA = sumA; P.sumN = sumN; P.xcarry = xcarry; P.flags = flags;
-  { Launch L(t, "kw_chunk_count");
-    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_chunk_count<HASH>), dim3(nch), dim3(KW_DD_THREADS), 0, t->stream, P)); }
-  { Launch L(t, "k_chunk_carry");
-    hipLaunchKernelGGL(k_chunk_carry, dim3(1), dim3(1024), 0, t->stream, sumA, sumN, nch, (long long)new_cap, xcarry, ptmp); }
-  { Launch L(t, "kw_chunk_place");
-    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_chunk_place<HASH>), dim3(nch), dim3(KW_DD_THREADS), 0, t->stream, P)); }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(t->hpin, flags, sizeof(uint32_t) * KH_NFLAGS, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipStreamSynchronize(t->stream));
-  const uint32_t* f = reinterpret_cast<const uint32_t*>(t->hpin);
-  if (f[KH_FLAG_PROBE_OVERFLOW] || f[KH_FLAG_COUNT_OVERFLOW]) {
-    kw_retire(w, nw);
-    if (f[KH_FLAG_PROBE_OVERFLOW])
-      return fail(t, KH_ERR_PROBE_OVERFLOW, "Robin Hood probe distance would exceed 127 (7-bit info field, hashmap_robinhood.hpp:142-144,556)");
-    return fail(t, KH_ERR_PROBE_OVERFLOW, "more than 65535 keys share one home bucket");
-  }
-  KwSlots old = w->cur;
-  w->cur = nw;
-  kw_retire(w, old);
-  t->min_load = threshold(new_cap, t->min_lf);
-  t->max_load = threshold(new_cap, t->max_lf);
-  return KH_OK;
-}
-kh_status kw_do_rehash(kh_wtable* w, uint64_t b) {      // hashmap_robinhood.hpp:432-464, as do_rehash
-  kh_table* t = &w->b;
-  uint64_t c = next_pow2(b);
-  if (c == w->cur.cap) return KH_OK;
-  if (t->lsize > 0) {
-    if (0 >= threshold(c, t->max_lf)) c <<= 1;
-    while (t->lsize > threshold(c, t->max_lf)) c <<= 1;
-  }
-  if (c == w->cur.cap) return KH_OK;
-  { kh_status ps = arena_prepare(t, ws_rebuild(c)); if (ps != KH_OK) return ps; }
-  return kw_rebuild(w, c, nullptr, nullptr, nullptr, nullptr, 0, false, t->lsize);
-}
-kh_status kw_do_reserve(kh_wtable* w, uint64_t n) {
-  kh_table* t = &w->b;
-  if (n > t->max_load) return kw_do_rehash(w, static_cast<uint64_t>(static_cast<float>(n) / t->max_lf));
-  return KH_OK;
-}
 // workspace of one insert pass of n keys at partitioning capacity cap_u
 inline size_t kw_ws_insert(uint64_t n, uint64_t cap_u) {
   const uint64_t np = cap_u > KH_L ? (cap_u >> KH_LB) : 1;
@@ -2412,11 +2384,10 @@ inline size_t kw_ws_insert(uint64_t n, uint64_t cap_u) {
 }
 
 // one insert() pass over device-resident keys (u64[2n]) / values (u32[n] or null); n < 2^32
-kh_status kw_insert_core(kh_wtable* w, const uint64_t* keys, const uint32_t* vals, uint64_t n, int mode, uint64_t forced_cap, uint64_t* n_new_out) {
-  kh_table* t = &w->b;
+kh_status kw_insert_core(kh_wtable* t, const uint64_t* keys, const uint32_t* vals, uint64_t n, int mode, uint64_t forced_cap, uint64_t* n_new_out) {
   *n_new_out = 0;
   if (n == 0) return KH_OK;
-  const uint64_t cap_u = forced_cap ? forced_cap : capacity_after(t, w->cur.cap, t->lsize, n, n, n - 1);
+  const uint64_t cap_u = forced_cap ? forced_cap : capacity_after(t, t->cur.cap, t->lsize, n, n, n - 1);
   const uint32_t PB = cap_u > KH_L ? log2u(cap_u >> KH_LB) : 0u;
   if (PB > 22) return fail(t, KH_ERR_UNSUPPORTED, "batch would need more than 2^22 partitions");
   const uint32_t nparts = 1u << PB;
@@ -2441,7 +2412,7 @@ kh_status kw_insert_core(kh_wtable* w, const uint64_t* keys, const uint32_t* val
                                                plus ? 1u : 0u, n, t->seed.s, PB, cursor, rec)); }
   KwDedupParams D;
   memset(&D, 0, sizeof(D));
-  D.rec = rec; D.off = off; D.T = w->cur; D.seed = t->seed.s; D.table_empty = t->lsize == 0 ? 1 : 0;
+  D.rec = rec; D.off = off; D.T = wide(t->cur); D.seed = t->seed.s; D.table_empty = t->lsize == 0 ? 1 : 0;
   D.mode = plus ? KH_DEDUP_PLUS : KH_DEDUP_FIRST;
   D.nk = nk; D.nv = nv; D.cnt_new = cnt_new; D.us = us; D.uv = uv; D.cnt_upd = cnt_upd; D.max_idx_plus1 = scal; D.flags = flags;
   { Launch L(t, "kw_dedup");
@@ -2453,17 +2424,17 @@ kh_status kw_insert_core(kh_wtable* w, const uint64_t* keys, const uint32_t* val
   HIPCHK(hipMemcpyAsync(t->hpin + 1, scal, 8, hipMemcpyDeviceToHost, t->stream));
   HIPCHK(hipMemcpyAsync(t->hpin + 2, flags, sizeof(uint32_t) * KH_NFLAGS, hipMemcpyDeviceToHost, t->stream));
   HIPCHK(hipStreamSynchronize(t->stream));
-  if (reinterpret_cast<const uint32_t*>(t->hpin + 2)[KH_FLAG_INTERNAL]) return fail(t, KH_ERR_HIP, "internal: de-duplication set overflow");
+  if (reinterpret_cast<const uint32_t*>(t->hpin + 2)[KH_FLAG_INTERNAL]) return fail(t, KH_ERR_HIP, kDedupOverflowText);
   const uint64_t dnew = t->hpin[0];
   const uint64_t last_first = plus ? n - 1 : (t->hpin[1] ? t->hpin[1] - 1 : 0);
   auto apply_plus = [&](int sign) {
     Launch L(t, "kw_apply_plus");
-    hipLaunchKernelGGL(kw_apply_plus, dim3(std::min<uint32_t>(nparts, 4096u)), dim3(256), 0, t->stream, w->cur.s, (const uint64_t*)off,
+    hipLaunchKernelGGL(kw_apply_plus, dim3(std::min<uint32_t>(nparts, 4096u)), dim3(256), 0, t->stream, wide(t->cur).s, (const uint64_t*)off,
                        (const uint32_t*)cnt_upd, (const uint64_t*)us, (const uint32_t*)uv, nparts, sign);
   };
   if (plus_live) apply_plus(+1);
-  const uint64_t new_cap = forced_cap ? forced_cap : capacity_after(t, w->cur.cap, t->lsize, n, dnew, last_first);
-  if (dnew > 0 || new_cap != w->cur.cap) {
+  const uint64_t new_cap = forced_cap ? forced_cap : capacity_after(t, t->cur.cap, t->lsize, n, dnew, last_first);
+  if (dnew > 0 || new_cap != t->cur.cap) {
     // a chunk of the new table owns 2^(PB-k) consecutive partitions: their lists are read in place when that is a handful, gathered
     // into one dense list when the capacity ended far below the partitioning capacity (duplicates)
     const uint32_t k_new = new_cap > KH_L ? log2u(new_cap >> KH_LB) : 0u;
@@ -2479,7 +2450,7 @@ kh_status kw_insert_core(kh_wtable* w, const uint64_t* keys, const uint32_t* val
         ck = gk; cv = gv; lo = noff; lc = nullptr;
       }
     }
-    kh_status st = kw_rebuild(w, new_cap, ck, cv, lo, lc, PB, false, t->lsize + dnew);
+    kh_status st = rebuild(t, new_cap, ck, cv, lo, lc, PB, false, t->lsize + dnew);
     if (st != KH_OK) {        // the table keeps its layout: it must keep its values too
       if (plus_live) { apply_plus(-1); hipStreamSynchronize(t->stream); }
       return st;
@@ -2492,13 +2463,12 @@ kh_status kw_insert_core(kh_wtable* w, const uint64_t* keys, const uint32_t* val
 
 // insert(Iter,Iter) / the reducer insert over device-resident input: passes cut only where the one-doubling-per-call rule or the
 // 32-bit stream positions demand it (insert_device), then the trailing reserve(size())
-kh_status kw_do_insert(kh_wtable* w, const void* keys, const void* vals, uint64_t n, kh_mem where, int mode, uint64_t* n_inserted) {
-  kh_table* t = &w->b;
+kh_status kw_do_insert(kh_wtable* t, const void* keys, const void* vals, uint64_t n, kh_mem where, int mode, uint64_t* n_inserted) {
   if (n_inserted) *n_inserted = 0;
   if (n && !keys) return fail(t, KH_ERR_INVALID, "null keys");
   HIPCHK(hipSetDevice(t->device));
   const uint64_t np_ = std::min<uint64_t>(n, g_max_pass);
-  { const uint64_t cu = capacity_after(t, w->cur.cap, t->lsize, np_ ? np_ : 1, np_, np_ ? np_ - 1 : 0);
+  { const uint64_t cu = capacity_after(t, t->cur.cap, t->lsize, np_ ? np_ : 1, np_, np_ ? np_ - 1 : 0);
     kh_status ps = arena_prepare(t, (where == KH_MEM_HOST ? n * 20 : 0) + kw_ws_insert(np_, cu));
     if (ps != KH_OK) return ps; }
   const uint64_t* kb = static_cast<const uint64_t*>(keys);
@@ -2514,28 +2484,27 @@ kh_status kw_do_insert(kh_wtable* w, const void* keys, const void* vals, uint64_
   kh_status st = KH_OK;
   while (done < n && st == KH_OK) {
     uint64_t take = n - done, forced = 0;
-    if (t->lsize >= threshold(w->cur.cap << 1, t->max_lf)) {       // more than one doubling pending: peel one call (insert_device)
+    if (t->lsize >= threshold(t->cur.cap << 1, t->max_lf)) {       // more than one doubling pending: peel one call (insert_device)
       take = 1;
-      forced = w->cur.cap << 1;
+      forced = t->cur.cap << 1;
       while (t->lsize > threshold(forced, t->max_lf)) forced <<= 1;
     }
     if (take > g_max_pass) take = g_max_pass;
     t->blk = keep_blk; t->off = keep_off;
     uint64_t nn = 0;
-    st = kw_insert_core(w, kb + 2 * done, vb ? vb + done : nullptr, take, mode, forced, &nn);
+    st = kw_insert_core(t, kb + 2 * done, vb ? vb + done : nullptr, take, mode, forced, &nn);
     total_new += nn;
     done += take;
   }
-  if (st == KH_OK) st = kw_do_reserve(w, t->lsize);
+  if (st == KH_OK) st = do_reserve(t, t->lsize);
   if (st == KH_OK) HIPCHK(hipStreamSynchronize(t->stream));
   if (n_inserted) *n_inserted = total_new;
   return st;
 }
 
 // find / count / find(Iter,Iter).  Outputs live where the queries live.
-kh_status kw_do_find(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, uint32_t* out_vals, uint8_t* out_found, uint64_t* out_ckeys,
+kh_status kw_do_find(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint32_t* out_vals, uint8_t* out_found, uint64_t* out_ckeys,
                      uint32_t* out_cvals, bool compacted, bool count_only, uint64_t* n_found) {
-  kh_table* t = &w->b;
   if (n_found) *n_found = 0;
   if (n == 0) return KH_OK;
   if (!keys) return fail(t, KH_ERR_INVALID, "null keys");
@@ -2553,8 +2522,8 @@ kh_status kw_do_find(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, u
   hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, t->device);
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + KW_Q_THREADS * KW_Q_ITEMS - 1) / (KW_Q_THREADS * KW_Q_ITEMS), (uint64_t)ncu * 8));
   { Launch L(t, count_only ? "kw_count" : "kw_find");
-    if (count_only) { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_find<HASH, KW_FIND_COUNT>), dim3(grid), dim3(KW_Q_THREADS), 0, t->stream, w->cur, q, n, t->seed.s, dv, df, (unsigned long long*)nullptr)); }
-    else { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_find<HASH, KW_FIND_VALS>), dim3(grid), dim3(KW_Q_THREADS), 0, t->stream, w->cur, q, n, t->seed.s, dv, df, hits_dev)); } }
+    if (count_only) { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_find<HASH, KW_FIND_COUNT>), dim3(grid), dim3(KW_Q_THREADS), 0, t->stream, wide(t->cur), q, n, t->seed.s, dv, df, (unsigned long long*)nullptr)); }
+    else { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_find<HASH, KW_FIND_VALS>), dim3(grid), dim3(KW_Q_THREADS), 0, t->stream, wide(t->cur), q, n, t->seed.s, dv, df, hits_dev)); } }
   HIPCHK(hipGetLastError());
   if (count_only) {
     if (host) { HIPCHK(hipMemcpyAsync(out_found, df, n, hipMemcpyDeviceToHost, t->stream)); HIPCHK(hipStreamSynchronize(t->stream)); }
@@ -2563,126 +2532,48 @@ kh_status kw_do_find(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, u
   uint64_t hits = 0;
   if (!compacted) {
     HIPCHK(hipMemcpyAsync(t->hpin, hits_dev, 8, hipMemcpyDeviceToHost, t->stream));
-    if (host) {          // values of misses stay untouched in the caller's buffer
-      std::vector<uint32_t> hv(out_vals ? n : 0); std::vector<uint8_t> hf(n);
-      if (out_vals) HIPCHK(hipMemcpyAsync(hv.data(), dv, n * 4, hipMemcpyDeviceToHost, t->stream));
-      HIPCHK(hipMemcpyAsync(hf.data(), df, n, hipMemcpyDeviceToHost, t->stream));
-      HIPCHK(hipStreamSynchronize(t->stream));
-      for (uint64_t i = 0; i < n; ++i) { if (out_found) out_found[i] = hf[i]; if (hf[i] && out_vals) out_vals[i] = hv[i]; }
-    } else HIPCHK(hipStreamSynchronize(t->stream));
+    if (host) { kh_status st = copy_hits_selective(t, dv, df, n, out_vals, out_found); if (st != KH_OK) return st; }
+    else HIPCHK(hipStreamSynchronize(t->stream));
     hits = t->hpin[0];
   } else {
-    const uint64_t ntl = (n + KH_CMP_TILE - 1) / KH_CMP_TILE;
-    uint32_t* sums; uint64_t* offs; uint64_t* ck = out_ckeys; uint32_t* cv = out_cvals;
-    TAKE(sums, uint32_t, ntl); TAKE(offs, uint64_t, ntl + 1);
+    uint64_t* ck = out_ckeys; uint32_t* cv = out_cvals;
     if (host) { TAKE(ck, uint64_t, 2 * n); TAKE(cv, uint32_t, n); }
-    hipLaunchKernelGGL(k_flag_tile_sums, dim3((uint32_t)ntl), dim3(256), 0, t->stream, (const uint8_t*)df, n, sums);
-    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, (const uint32_t*)sums, ntl, offs);
-    { Launch L(t, "kw_compact");
-      hipLaunchKernelGGL(kw_compact, dim3((uint32_t)ntl), dim3(256), 0, t->stream, (const uint8_t*)df, q, (const uint32_t*)dv, n, (const uint64_t*)offs, ck, cv); }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(t->hpin, offs + ntl, 8, hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));
-    hits = t->hpin[0];
-    if (host && hits) {
-      HIPCHK(hipMemcpyAsync(out_ckeys, ck, hits * 16, hipMemcpyDeviceToHost, t->stream));
-      HIPCHK(hipMemcpyAsync(out_cvals, cv, hits * 4, hipMemcpyDeviceToHost, t->stream));
-      HIPCHK(hipStreamSynchronize(t->stream));
-    }
+    kh_status st = compact(t, df, q, dv, n, ck, cv, &hits);
+    if (st == KH_OK && host && hits) st = copy_compacted(t, hits, ck, cv, out_ckeys, out_cvals);
+    if (st != KH_OK) return st;
   }
   if (n_found) *n_found = hits;
   return KH_OK;
 }
 
 // erase(Iter,Iter): mark the hits, re-lay out without them (RH: never shrinks, hashmap_robinhood.hpp:1430-1440)
-kh_status kw_do_erase(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, uint64_t* n_erased) {
-  kh_table* t = &w->b;
+kh_status kw_do_erase(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint64_t* n_erased) {
   *n_erased = 0;
   if (n == 0) return KH_OK;
   if (!keys) return fail(t, KH_ERR_INVALID, "null keys");
   HIPCHK(hipSetDevice(t->device));
-  { kh_status ps = arena_prepare(t, n * 16 + ws_rebuild(w->cur.cap) + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  { kh_status ps = arena_prepare(t, n * 16 + ws_rebuild(t->cur.cap) + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
   const uint64_t* q = static_cast<const uint64_t*>(keys);
   if (where == KH_MEM_HOST) { uint64_t* d; TAKE(d, uint64_t, 2 * n); HIPCHK(hipMemcpyAsync(d, keys, n * 16, hipMemcpyHostToDevice, t->stream)); q = d; }
   unsigned long long* cnt;
   TAKE(cnt, unsigned long long, 1);
   HIPCHK(hipMemsetAsync(cnt, 0, 8, t->stream));
   { Launch L(t, "kw_erase_mark");
-    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_erase_mark<HASH>), dim3(grid_for(n, 256, 2048)), dim3(256), 0, t->stream, w->cur, q, n, t->seed.s, cnt)); }
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_erase_mark<HASH>), dim3(grid_for(n, 256, 2048)), dim3(256), 0, t->stream, wide(t->cur), q, n, t->seed.s, cnt)); }
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(t->hpin, cnt, 8, hipMemcpyDeviceToHost, t->stream));
   HIPCHK(hipStreamSynchronize(t->stream));
   const uint64_t ne = t->hpin[0];
   if (ne) {
-    kh_status st = kw_rebuild(w, w->cur.cap, nullptr, nullptr, nullptr, nullptr, 0, true, t->lsize - ne);
+    kh_status st = rebuild(t, t->cur.cap, nullptr, nullptr, nullptr, nullptr, 0, true, t->lsize - ne);
     if (st != KH_OK) {        // the table keeps its elements: take the marks back
-      hipLaunchKernelGGL(kw_clear_marks, dim3(grid_for(w->cur.cap, 256)), dim3(256), 0, t->stream, w->cur);
+      hipLaunchKernelGGL(kw_clear_marks, dim3(grid_for(t->cur.cap, 256)), dim3(256), 0, t->stream, wide(t->cur));
       hipStreamSynchronize(t->stream);
       return st;
     }
   }
   t->lsize -= ne;
   *n_erased = ne;
-  return KH_OK;
-}
-kh_status kw_unpack(kh_wtable* w, uint64_t* k, uint32_t* v, uint8_t* info, uint8_t* flags) {
-  kh_table* t = &w->b;
-  hipLaunchKernelGGL(kw_unpack_slots, dim3(grid_for(w->cur.cap, 256)), dim3(256), 0, t->stream, (const KwSlot*)w->cur.s, w->cur.cap, k, v, info, flags);
-  HIPCHK(hipGetLastError());
-  return KH_OK;
-}
-
-// 128-bit k-mers (kmers_impl with 16-byte outputs)
-kh_status kw_kmers_impl(const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq, uint64_t* out_kmers, uint64_t* n_out,
-                        int device, void* stream_) {
-  kh_table* t = nullptr;
-  if (n_out) *n_out = 0;
-  if (k < 1 || k > 64 || !n_out) return KH_ERR_INVALID;
-  if (n < k) return KH_OK;
-  if (!seq || !out_kmers) return KH_ERR_INVALID;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
-  const uint64_t ntl = (n + KH_CMP_TILE - 1) / KH_CMP_TILE;
-  const uint64_t nkt = (n + KH_KM_TILE - 1) / KH_KM_TILE;
-  const uint64_t nt = std::max(ntl, nkt);
-  const size_t sz_seq = where == KH_MEM_HOST ? ((n + 255) & ~size_t(255)) : 0;
-  const size_t sz_msk = fastq ? ((n + 255) & ~size_t(255)) : 0;
-  const size_t sz_sum = ((nt * 4 + 255) & ~size_t(255)), sz_off = ((nt + 1) * 8 + 255) & ~size_t(255);
-  const size_t sz_out = where == KH_MEM_HOST ? n * 16 : 0;
-  char* blk = nullptr;
-  HIPCHK(pool_alloc(device, sz_seq + sz_msk + sz_sum + sz_off + sz_out, reinterpret_cast<void**>(&blk)));
-  const uint8_t* dseq = static_cast<const uint8_t*>(seq);
-  char* p = blk;
-  if (where == KH_MEM_HOST) { dseq = reinterpret_cast<uint8_t*>(p); p += sz_seq; }
-  uint8_t* msk = reinterpret_cast<uint8_t*>(p); p += sz_msk;
-  uint32_t* sums = reinterpret_cast<uint32_t*>(p); p += sz_sum;
-  uint64_t* offs = reinterpret_cast<uint64_t*>(p); p += sz_off;
-  uint64_t* dout = where == KH_MEM_HOST ? reinterpret_cast<uint64_t*>(p) : out_kmers;
-  hipError_t e = hipSuccess;
-  if (where == KH_MEM_HOST) e = hipMemcpyAsync(const_cast<uint8_t*>(dseq), seq, n, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) {
-    if (fastq) {
-      hipLaunchKernelGGL(k_newline_tile_sums, dim3((uint32_t)ntl), dim3(256), 0, stream, dseq, n, sums);
-      hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, (const uint32_t*)sums, ntl, offs);
-      hipLaunchKernelGGL(k_fastq_mask, dim3((uint32_t)ntl), dim3(256), 0, stream, dseq, n, (const uint64_t*)offs, msk);
-      dseq = msk;
-    }
-    hipLaunchKernelGGL(kw_kmers_count, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
-    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, (const uint32_t*)sums, nkt, offs);
-    if (canonical) hipLaunchKernelGGL((kw_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
-    else hipLaunchKernelGGL((kw_kmers_emit<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
-    e = hipGetLastError();
-  }
-  uint64_t total = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&total, offs + nkt, 8, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e == hipSuccess && where == KH_MEM_HOST && total) {
-    e = hipMemcpyAsync(out_kmers, dout, total * 16, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  }
-  pool_free(device, blk);
-  if (e != hipSuccess) return KH_ERR_HIP;
-  *n_out = total;
   return KH_OK;
 }
 }  // namespace
@@ -2697,168 +2588,68 @@ kh_status kh_wide_create(kh_wtable** out, kh_kind kind, kh_hash hash, uint64_t s
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return KH_ERR_HIP;
   if (device < 0 || device >= ndev) return KH_ERR_INVALID;
   if (hipSetDevice(device) != hipSuccess) return KH_ERR_HIP;
-  kh_wtable* w = new kh_wtable();
-  kh_table* t = &w->b;
-  t->kind = KHK_RH; t->hash = (int)hash; t->device = device; t->seed = KhSeed{seed, 0u}; t->stream = nullptr;
-  t->min_lf = min_lf; t->max_lf = max_lf; t->lsize = 0;
-  t->cur = kNoSlots; t->spare = kNoSlots;
-  t->blk = 0; t->off = 0; t->hpin = nullptr; t->prof = false; t->part_overflow = nullptr; t->batch_nodup = false; t->batch_vf = 1.0;
-  memset(&t->ins, 0, sizeof(t->ins));
-  w->cur = kNoWSlots; w->spare = kNoWSlots;
-  const uint64_t cap = next_pow2(capacity);
-  if (kw_alloc(t, cap, w->cur) != KH_OK) { delete w; return KH_ERR_NOMEM; }
-  t->hpin = pinned_get();
-  if (!t->hpin) { kw_free(t, w->cur); delete w; return KH_ERR_NOMEM; }
-  if (kw_fill(t, w->cur) != KH_OK || hipStreamSynchronize(t->stream) != hipSuccess) { kw_free(t, w->cur); pinned_put(t->hpin); delete w; return KH_ERR_HIP; }
-  t->min_load = threshold(cap, min_lf);
-  t->max_load = threshold(cap, max_lf);
-  *out = w;
+  kh_wtable* t = new kh_wtable();
+  t->slot_bytes = sizeof(KwSlot);
+  const kh_status st = table_init(t, KHK_RH, (int)hash, seed, capacity, min_lf, max_lf, device);
+  if (st != KH_OK) { delete t; return st; }
+  *out = t;
   return KH_OK;
 }
-kh_status kh_wide_destroy(kh_wtable* w) {
-  if (!w) return KH_OK;
-  kh_table* t = &w->b;
-  hipSetDevice(t->device);
-  hipStreamSynchronize(t->stream);
-  for (auto& r : t->recs) { event_put(t->device, r.a); event_put(t->device, r.b); }
-  kw_free(t, w->cur); kw_free(t, w->spare);
-  for (auto& b : t->blocks) pool_free(t->device, b.p);
-  pinned_put(t->hpin);
-  delete w;
-  return KH_OK;
+kh_status kh_wide_destroy(kh_wtable* t) { table_release(t); delete t; return KH_OK; }
+// state access: the 64-bit table's entry points, which read the width from the table
+kh_status kh_wide_set_stream(kh_wtable* t, void* s) { return kh_set_stream(t, s); }
+const char* kh_wide_last_error(const kh_wtable* t) { return kh_last_error(t); }
+kh_status kh_wide_size(const kh_wtable* t, uint64_t* out) { return kh_size(t, out); }
+kh_status kh_wide_capacity(const kh_wtable* t, uint64_t* out) { return kh_capacity(t, out); }
+kh_status kh_wide_get_load_factors(const kh_wtable* t, float* mn, float* mx, float* cur) { return kh_get_load_factors(t, mn, mx, cur); }
+kh_status kh_wide_set_min_load_factor(kh_wtable* t, float f) { return kh_set_min_load_factor(t, f); }
+kh_status kh_wide_set_max_load_factor(kh_wtable* t, float f) { return kh_set_max_load_factor(t, f); }
+kh_status kh_wide_clear(kh_wtable* t) { return kh_clear(t); }
+kh_status kh_wide_reserve(kh_wtable* t, uint64_t n) { return kh_reserve(t, n); }
+kh_status kh_wide_rehash(kh_wtable* t, uint64_t b) { return kh_rehash(t, b); }
+kh_status kh_wide_to_vector(kh_wtable* t, uint64_t* keys_host, uint32_t* vals_host, uint64_t* n_out) { return kh_to_vector(t, keys_host, vals_host, n_out); }
+kh_status kh_wide_export_info(kh_wtable* t, uint8_t* out_host) { return kh_export_info(t, out_host); }
+kh_status kh_wide_displacement_histogram(kh_wtable* t, uint64_t out[128]) { return kh_displacement_histogram(t, out); }
+kh_status kh_wide_insert(kh_wtable* t, const void* keys, const void* vals, uint64_t n, kh_mem where, uint64_t* n_inserted) {
+  if (!t) return KH_ERR_INVALID;
+  if (n && !vals) return fail(t, KH_ERR_INVALID, "null values");
+  return kw_do_insert(t, keys, vals, n, where, INS_FIRST, n_inserted);
 }
-kh_status kh_wide_set_stream(kh_wtable* w, void* s) { return w ? kh_set_stream(&w->b, s) : KH_ERR_INVALID; }
-const char* kh_wide_last_error(const kh_wtable* w) { return w ? w->b.err.c_str() : "null table"; }
-kh_status kh_wide_size(const kh_wtable* w, uint64_t* out) { if (!w || !out) return KH_ERR_INVALID; *out = w->b.lsize; return KH_OK; }
-kh_status kh_wide_capacity(const kh_wtable* w, uint64_t* out) { if (!w || !out) return KH_ERR_INVALID; *out = w->cur.cap; return KH_OK; }
-kh_status kh_wide_get_load_factors(const kh_wtable* w, float* mn, float* mx, float* cur) {
-  if (!w) return KH_ERR_INVALID;
-  if (mn) *mn = w->b.min_lf;
-  if (mx) *mx = w->b.max_lf;
-  if (cur) *cur = static_cast<float>(w->b.lsize) / static_cast<float>(w->cur.cap);
-  return KH_OK;
+kh_status kh_wide_insert_reduce_plus(kh_wtable* t, const void* keys, const void* vals, uint64_t n, kh_mem where, uint64_t* n_inserted) {
+  if (!t) return KH_ERR_INVALID;
+  return kw_do_insert(t, keys, vals, n, where, INS_PLUS, n_inserted);
 }
-kh_status kh_wide_set_min_load_factor(kh_wtable* w, float f) { if (!w) return KH_ERR_INVALID; w->b.min_lf = f; w->b.min_load = threshold(w->cur.cap, f); return KH_OK; }
-kh_status kh_wide_set_max_load_factor(kh_wtable* w, float f) { if (!w) return KH_ERR_INVALID; w->b.max_lf = f; w->b.max_load = threshold(w->cur.cap, f); return KH_OK; }
-kh_status kh_wide_clear(kh_wtable* w) {
-  if (!w) return KH_ERR_INVALID;
-  kh_table* t = &w->b;
-  HIPCHK(hipSetDevice(t->device));
-  t->lsize = 0;
-  { kh_status fs = kw_fill(t, w->cur); if (fs != KH_OK) return fs; }
-  HIPCHK(hipStreamSynchronize(t->stream));
-  return KH_OK;
+kh_status kh_wide_count(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint8_t* out01) {
+  if (!t) return KH_ERR_INVALID;
+  if (n && !out01) return fail(t, KH_ERR_INVALID, "null argument");
+  return kw_do_find(t, keys, n, where, nullptr, out01, nullptr, nullptr, false, true, nullptr);
 }
-kh_status kh_wide_reserve(kh_wtable* w, uint64_t n) { if (!w) return KH_ERR_INVALID; kh_table* t = &w->b; HIPCHK(hipSetDevice(t->device)); return kw_do_reserve(w, n); }
-kh_status kh_wide_rehash(kh_wtable* w, uint64_t b) { if (!w) return KH_ERR_INVALID; kh_table* t = &w->b; HIPCHK(hipSetDevice(t->device)); return kw_do_rehash(w, b); }
-kh_status kh_wide_insert(kh_wtable* w, const void* keys, const void* vals, uint64_t n, kh_mem where, uint64_t* n_inserted) {
-  if (!w) return KH_ERR_INVALID;
-  if (n && !vals) return fail(&w->b, KH_ERR_INVALID, "null values");
-  return kw_do_insert(w, keys, vals, n, where, INS_FIRST, n_inserted);
+kh_status kh_wide_find(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint32_t* out_vals, uint8_t* out_found, uint64_t* n_found) {
+  if (!t) return KH_ERR_INVALID;
+  return kw_do_find(t, keys, n, where, out_vals, out_found, nullptr, nullptr, false, false, n_found);
 }
-kh_status kh_wide_insert_reduce_plus(kh_wtable* w, const void* keys, const void* vals, uint64_t n, kh_mem where, uint64_t* n_inserted) {
-  if (!w) return KH_ERR_INVALID;
-  return kw_do_insert(w, keys, vals, n, where, INS_PLUS, n_inserted);
+kh_status kh_wide_find_compact(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint64_t* out_keys, uint32_t* out_vals, uint64_t* n_found) {
+  if (!t) return KH_ERR_INVALID;
+  if (n && (!out_keys || !out_vals)) return fail(t, KH_ERR_INVALID, "null output");
+  return kw_do_find(t, keys, n, where, nullptr, nullptr, out_keys, out_vals, true, false, n_found);
 }
-kh_status kh_wide_count(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, uint8_t* out01) {
-  if (!w) return KH_ERR_INVALID;
-  if (n && !out01) return fail(&w->b, KH_ERR_INVALID, "null argument");
-  return kw_do_find(w, keys, n, where, nullptr, out01, nullptr, nullptr, false, true, nullptr);
-}
-kh_status kh_wide_find(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, uint32_t* out_vals, uint8_t* out_found, uint64_t* n_found) {
-  if (!w) return KH_ERR_INVALID;
-  return kw_do_find(w, keys, n, where, out_vals, out_found, nullptr, nullptr, false, false, n_found);
-}
-kh_status kh_wide_find_compact(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, uint64_t* out_keys, uint32_t* out_vals, uint64_t* n_found) {
-  if (!w) return KH_ERR_INVALID;
-  if (n && (!out_keys || !out_vals)) return fail(&w->b, KH_ERR_INVALID, "null output");
-  return kw_do_find(w, keys, n, where, nullptr, nullptr, out_keys, out_vals, true, false, n_found);
-}
-kh_status kh_wide_erase(kh_wtable* w, const void* keys, uint64_t n, kh_mem where, uint64_t* n_erased) {
-  if (!w) return KH_ERR_INVALID;
-  kh_table* t = &w->b;
+kh_status kh_wide_erase(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint64_t* n_erased) {
+  if (!t) return KH_ERR_INVALID;
   uint64_t ne = 0;
-  kh_status st = kw_do_erase(w, keys, n, where, &ne);
+  kh_status st = kw_do_erase(t, keys, n, where, &ne);
   if (n_erased) *n_erased = ne;
-  if (st == KH_OK && t->lsize < t->min_load) st = kw_do_reserve(w, t->lsize);     // hashmap_robinhood.hpp:1437: reserve() only grows
+  if (st == KH_OK && t->lsize < t->min_load) st = do_reserve(t, t->lsize);     // hashmap_robinhood.hpp:1437: reserve() only grows
   return st;
 }
-kh_status kh_wide_to_vector(kh_wtable* w, uint64_t* keys_host, uint32_t* vals_host, uint64_t* n_out) {
-  if (!w) return KH_ERR_INVALID;
-  kh_table* t = &w->b;
-  HIPCHK(hipSetDevice(t->device));
-  const uint64_t cap = w->cur.cap, ntl = (cap + KH_CMP_TILE - 1) / KH_CMP_TILE;
-  { kh_status ps = arena_prepare(t, cap * 45 + ntl * 12 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
-  uint8_t* flags; uint64_t *sk, *ck, *offs; uint32_t *sv, *cv, *sums;
-  TAKE(flags, uint8_t, cap); TAKE(sk, uint64_t, 2 * cap); TAKE(sv, uint32_t, cap); TAKE(ck, uint64_t, 2 * cap); TAKE(cv, uint32_t, cap);
-  TAKE(sums, uint32_t, ntl); TAKE(offs, uint64_t, ntl + 1);
-  kh_status st = kw_unpack(w, sk, sv, nullptr, flags);
-  if (st != KH_OK) return st;
-  hipLaunchKernelGGL(k_flag_tile_sums, dim3((uint32_t)ntl), dim3(256), 0, t->stream, (const uint8_t*)flags, cap, sums);
-  hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, (const uint32_t*)sums, ntl, offs);
-  hipLaunchKernelGGL(kw_compact, dim3((uint32_t)ntl), dim3(256), 0, t->stream, (const uint8_t*)flags, (const uint64_t*)sk, (const uint32_t*)sv, cap, (const uint64_t*)offs, ck, cv);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(t->hpin, offs + ntl, 8, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipStreamSynchronize(t->stream));
-  const uint64_t m = t->hpin[0];
-  if (m && keys_host) HIPCHK(hipMemcpyAsync(keys_host, ck, m * 16, hipMemcpyDeviceToHost, t->stream));
-  if (m && vals_host) HIPCHK(hipMemcpyAsync(vals_host, cv, m * 4, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipStreamSynchronize(t->stream));
-  if (n_out) *n_out = m;
-  return KH_OK;
-}
-kh_status kh_wide_export_info(kh_wtable* w, uint8_t* out_host) {
-  if (!w || !out_host) return KH_ERR_INVALID;
-  kh_table* t = &w->b;
-  HIPCHK(hipSetDevice(t->device));
-  { kh_status ps = arena_prepare(t, w->cur.cap + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
-  uint8_t* info;
-  TAKE(info, uint8_t, w->cur.cap);
-  kh_status st = kw_unpack(w, nullptr, nullptr, info, nullptr);
-  if (st != KH_OK) return st;
-  HIPCHK(hipMemcpyAsync(out_host, info, w->cur.cap, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipStreamSynchronize(t->stream));
-  return KH_OK;
-}
-kh_status kh_wide_displacement_histogram(kh_wtable* w, uint64_t out[128]) {
-  if (!w || !out) return KH_ERR_INVALID;
-  kh_table* t = &w->b;
-  HIPCHK(hipSetDevice(t->device));
-  { kh_status ps = arena_prepare(t, size_t(1) << 20); if (ps != KH_OK) return ps; }
-  unsigned long long* d;
-  TAKE(d, unsigned long long, 128);
-  HIPCHK(hipMemsetAsync(d, 0, 128 * 8, t->stream));
-  hipLaunchKernelGGL(kw_disp_hist, dim3(grid_for(w->cur.cap, 256, 1024)), dim3(256), 0, t->stream, (const KwSlot*)w->cur.s, w->cur.cap, d);
-  HIPCHK(hipMemcpyAsync(out, d, 128 * 8, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipStreamSynchronize(t->stream));
-  return KH_OK;
-}
-kh_status kh_wide_hash_batch(kh_hash hash, uint64_t seed, const void* keys, uint64_t n, kh_mem where, uint64_t* out, int device, void* stream_) {
-  kh_table* t = nullptr;
-  if (n == 0) return KH_OK;
-  if (!keys || !out || (int)hash < 0 || (int)hash > 3) return KH_ERR_INVALID;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
-  const uint64_t* dk = static_cast<const uint64_t*>(keys);
-  uint64_t* dout = out; uint64_t* tmp = nullptr;
-  if (where == KH_MEM_HOST) {
-    HIPCHK(pool_alloc(device, n * 24, reinterpret_cast<void**>(&tmp)));
-    HIPCHK(hipMemcpyAsync(tmp, keys, n * 16, hipMemcpyHostToDevice, stream));
-    dk = tmp; dout = tmp + 2 * n;
-  }
-  KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((kw_hash_batch<HASH>), dim3(grid_for(n, 256)), dim3(256), 0, stream, dk, n, seed, dout));
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && where == KH_MEM_HOST) e = hipMemcpyAsync(out, dout, n * 8, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess && where == KH_MEM_HOST) e = hipStreamSynchronize(stream);
-  if (tmp) pool_free(device, tmp);
-  return e == hipSuccess ? KH_OK : KH_ERR_HIP;
+kh_status kh_wide_hash_batch(kh_hash hash, uint64_t seed, const void* keys, uint64_t n, kh_mem where, uint64_t* out, int device, void* stream) {
+  return hash_batch_impl(2, hash, KhSeed{seed, 0u}, keys, n, where, out, device, stream);
 }
 kh_status kh_kmers128_from_sequence(const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, uint64_t* out_kmers, uint64_t* n_out,
                                     int device, void* stream) {
-  return kw_kmers_impl(seq, n, k, canonical, where, false, out_kmers, n_out, device, stream);
+  return kmers_impl(2, seq, n, k, canonical, where, false, out_kmers, n_out, device, stream);
 }
 kh_status kh_kmers128_from_fastq(const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, uint64_t* out_kmers, uint64_t* n_out,
                                  int device, void* stream) {
-  return kw_kmers_impl(text, n, k, canonical, where, true, out_kmers, n_out, device, stream);
+  return kmers_impl(2, text, n, k, canonical, where, true, out_kmers, n_out, device, stream);
 }
 }  // extern "C"

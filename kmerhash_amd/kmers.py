@@ -4,13 +4,10 @@ FASTQ/FASTA -> k-mers -> counting insert -> write (k-mer, count) tuples) on the 
 The reference takes its parser and k-mer type from kmerind (absent), so the k-mer definition here is this library's
 (see kh_kmers_from_sequence in include/kmerhash_amd.h): 2-bit packed, first base most significant, A=0 C=1 G=2 T=3,
 windows containing any other byte are skipped, canonical = min(k-mer, reverse complement)."""
-import ctypes as C
-
 import numpy as np
 
-from . import _capi as K
-from .table import _Buf, hashmap_robinhood_doubling, torch
-from .wide import hashmap_robinhood_doubling_wide, kmers128_from_sequence
+from .table import hashmap_robinhood_doubling, torch
+from .wide import _kmers, hashmap_robinhood_doubling_wide, kmers128_from_sequence
 
 
 def sequences_from_fastq(buf):
@@ -45,24 +42,7 @@ def kmers_from_fastq(text, k=31, canonical=True, device=0):
 
 def kmers_from_sequence(seq, k=31, canonical=True, device=0, _fastq=False):
     """-> packed k-mers (numpy uint64 for host input, torch int64 CUDA tensor for device input), sequence order"""
-    L = K.lib()
-    if isinstance(seq, (bytes, bytearray)):
-        seq = np.frombuffer(seq, dtype=np.uint8)
-    b = _Buf(seq, np.uint8, 1)
-    n_out = C.c_uint64()
-    if b.where == K.KH_MEM_DEVICE:
-        out = torch.empty(max(b.n, 1), dtype=torch.int64, device=b.device)
-        optr = out.data_ptr()
-        stream = torch.cuda.current_stream(device).cuda_stream
-    else:
-        out = np.zeros(max(b.n, 1), dtype=np.uint64)
-        optr = out.ctypes.data
-        stream = None
-    fn = L.kh_kmers_from_fastq if _fastq else L.kh_kmers_from_sequence
-    st = fn(b.ptr, b.n, k, 1 if canonical else 0, b.where, optr, C.byref(n_out), device, stream)
-    if st != K.KH_OK:
-        raise K.KhError(st, "kh_kmers_from_fastq" if _fastq else "kh_kmers_from_sequence")
-    return out[: n_out.value]
+    return _kmers("kh_kmers_from_fastq" if _fastq else "kh_kmers_from_sequence", 1, seq, k, canonical, device)
 
 
 class KmerCounter:

@@ -63,7 +63,9 @@ class _Buf:
         self.device = None
 
 
-class _HashMapBase:
+class _TableCore:
+    """handle + scalar state of a table of either key width over the C-ABI entry points PREFIX + name; no batch members"""
+    PREFIX = "kh_"
     KIND = None
     DEFAULT_MIN_LF = None
     DEFAULT_MAX_LF = None
@@ -74,16 +76,20 @@ class _HashMapBase:
         self.device = int(device)
         mn = self.DEFAULT_MIN_LF if min_load_factor is None else min_load_factor
         mx = self.DEFAULT_MAX_LF if max_load_factor is None else max_load_factor
-        st = self._L.kh_create(C.byref(self._h), self.KIND, 8, 4, _hash_id(hash), seed, capacity, mn, mx, self.device)
+        widths = (8, 4) if self.PREFIX == "kh_" else ()      # kh_create takes the key / value widths, kh_wide_create has them fixed
+        st = self._fn("create")(C.byref(self._h), self.KIND, *widths, _hash_id(hash), seed, capacity, mn, mx, self.device)
         if st != K.KH_OK:
             self._h = C.c_void_p()
-            raise KhError(st, "kh_create failed (is a GPU visible and the HIP library built?)")
+            raise KhError(st, "%screate failed (is a GPU visible and the HIP library built?)" % self.PREFIX)
 
     # -- plumbing --------------------------------------------------------------------------------
+    def _fn(self, name):
+        return getattr(self._L, self.PREFIX + name)
+
     def _chk(self, st):
         if st == K.KH_OK:
             return
-        msg = self._L.kh_last_error(self._h).decode()
+        msg = self._fn("last_error")(self._h).decode()
         if st == K.KH_ERR_FULL:
             raise KhLogicError(st, msg)
         if st == K.KH_ERR_RETRY:
@@ -94,11 +100,11 @@ class _HashMapBase:
         """issue the table's work on torch's current stream when device tensors are involved"""
         if torch is not None and any(b is not None and b.where == K.KH_MEM_DEVICE for b in bufs):
             s = torch.cuda.current_stream(self.device).cuda_stream
-            self._L.kh_set_stream(self._h, C.c_void_p(s))
+            self._fn("set_stream")(self._h, C.c_void_p(s))
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
-            self._L.kh_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -107,17 +113,18 @@ class _HashMapBase:
         except Exception:
             pass
 
-    def _out(self, like, n, np_dtype, torch_dtype):
+    def _out(self, like, shape, np_dtype, torch_dtype, zero=False):
+        """an output where the queries live; host arrays are always zeroed, device tensors when `zero`"""
         if like.where == K.KH_MEM_DEVICE:
-            t = torch.empty(n, dtype=torch_dtype, device=like.device)
+            t = (torch.zeros if zero else torch.empty)(shape, dtype=torch_dtype, device=like.device)
             return t, t.data_ptr()
-        a = np.zeros(n, dtype=np_dtype)
+        a = np.zeros(shape, dtype=np_dtype)
         return a, a.ctypes.data
 
     # -- scalar state ------------------------------------------------------------------------------
     def size(self):
         v = C.c_uint64()
-        self._chk(self._L.kh_size(self._h, C.byref(v)))
+        self._chk(self._fn("size")(self._h, C.byref(v)))
         return v.value
 
     def __len__(self):
@@ -125,49 +132,62 @@ class _HashMapBase:
 
     def capacity(self):
         v = C.c_uint64()
-        self._chk(self._L.kh_capacity(self._h, C.byref(v)))
+        self._chk(self._fn("capacity")(self._h, C.byref(v)))
         return v.value
+
+    def set_min_load_factor(self, f):
+        self._chk(self._fn("set_min_load_factor")(self._h, f))
+
+    def set_max_load_factor(self, f):
+        self._chk(self._fn("set_max_load_factor")(self._h, f))
+
+    def _lf(self, i):
+        f = [C.c_float(), C.c_float(), C.c_float()]
+        self._chk(self._fn("get_load_factors")(self._h, C.byref(f[0]), C.byref(f[1]), C.byref(f[2])))
+        return f[i].value
+
+    def get_min_load_factor(self):
+        return self._lf(0)
+
+    def get_max_load_factor(self):
+        return self._lf(1)
+
+    def get_load_factor(self):
+        return self._lf(2)
+
+    def clear(self):
+        self._chk(self._fn("clear")(self._h))
+
+    def reserve(self, n):
+        self._chk(self._fn("reserve")(self._h, int(n)))
+
+    def rehash(self, b):
+        self._chk(self._fn("rehash")(self._h, int(b)))
+
+    def displacement_histogram(self):
+        out = np.zeros(128, dtype=np.uint64)
+        self._chk(self._fn("displacement_histogram")(self._h, out.ctypes.data))
+        return out
+
+    def export_info(self):
+        out = np.zeros(self.capacity(), dtype=np.uint8)
+        self._chk(self._fn("export_info")(self._h, out.ctypes.data))
+        return out
+
+
+class _HashMapBase(_TableCore):
+    """the 64-bit-key members: every batch argument is u64[n]"""
 
     def load_thresholds(self):
         a, b = C.c_uint64(), C.c_uint64()
         self._chk(self._L.kh_get_load_thresholds(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    def set_min_load_factor(self, f):
-        self._chk(self._L.kh_set_min_load_factor(self._h, f))
-
-    def set_max_load_factor(self, f):
-        self._chk(self._L.kh_set_max_load_factor(self._h, f))
-
-    def get_load_factor(self):
-        c = C.c_float()
-        self._chk(self._L.kh_get_load_factors(self._h, None, None, C.byref(c)))
-        return c.value
-
-    def get_min_load_factor(self):
-        c = C.c_float()
-        self._chk(self._L.kh_get_load_factors(self._h, C.byref(c), None, None))
-        return c.value
-
-    def get_max_load_factor(self):
-        c = C.c_float()
-        self._chk(self._L.kh_get_load_factors(self._h, None, C.byref(c), None))
-        return c.value
-
     def set_key_transform(self, k):
         """PreTransform of fsc::TransformedHash / TransformedComparator (hash_new.hpp:387-1134): k = 0 identity, k = 1..32
         bliss::kmer::transform::lex_less on 2-bit packed DNA k-mers -- a k-mer and its reverse complement are one key
         ("bimolecule" tables); the bits stored are those of the first occurrence.  Only on an empty table."""
         self._chk(self._L.kh_set_key_transform(self._h, K.KH_XF_DNA_LEX_LESS if k else K.KH_XF_IDENTITY, int(k)))
-
-    def clear(self):
-        self._chk(self._L.kh_clear(self._h))
-
-    def reserve(self, n):
-        self._chk(self._L.kh_reserve(self._h, int(n)))
-
-    def rehash(self, b):
-        self._chk(self._L.kh_rehash(self._h, int(b)))
 
     # -- batch operations ------------------------------------------------------------------------------
     def insert(self, keys, vals=None):
@@ -321,21 +341,11 @@ class _HashMapBase:
         o = np.argsort(k, kind="stable")
         return k[o], v[o]
 
-    def export_info(self):
-        out = np.zeros(self.capacity(), dtype=np.uint8)
-        self._chk(self._L.kh_export_info(self._h, out.ctypes.data))
-        return out
-
     def export_slots(self):
         k = np.zeros(self.capacity(), dtype=np.uint64)
         v = np.zeros(self.capacity(), dtype=np.uint32)
         self._chk(self._L.kh_export_slots(self._h, k.ctypes.data, v.ctypes.data))
         return k, v
-
-    def displacement_histogram(self):
-        out = np.zeros(128, dtype=np.uint64)
-        self._chk(self._L.kh_displacement_histogram(self._h, out.ctypes.data))
-        return out
 
     # -- measurement ---------------------------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _capi as K
 from ._capi import KH_KIND_ROBINHOOD, KhError
-from .table import _Buf, _hash_id, _is_tensor, torch
+from .table import _Buf, _TableCore, _hash_id, _is_tensor, torch
 
 
 def _keys(x):
@@ -25,84 +25,14 @@ def _keys(x):
     return _Buf(a.astype(np.uint64, copy=False), np.uint64, 8)
 
 
-class hashmap_robinhood_doubling_wide:
+class hashmap_robinhood_doubling_wide(_TableCore):
     """fsc::hashmap_robinhood_doubling<Key16, uint32_t, Hash> for 16-byte keys (e.g. Kmer<63, DNA, uint64_t>): the members of
-    hashmap_robinhood_doubling for insert / insert_reduce_plus / find / count / erase / reserve / rehash / clear / to_vector."""
+    hashmap_robinhood_doubling for insert / insert_reduce_plus / find / count / erase / reserve / rehash / clear / to_vector.
+    Handle and scalar state are _TableCore's over kh_wide_*; none of the 64-bit batch members is inherited."""
+    PREFIX = "kh_wide_"
+    KIND = KH_KIND_ROBINHOOD
     DEFAULT_MIN_LF = 0.4
     DEFAULT_MAX_LF = 0.9
-
-    def __init__(self, capacity=128, min_load_factor=None, max_load_factor=None, hash="murmur3avx64", seed=43, device=0):
-        self._L = K.lib()
-        self._h = C.c_void_p()
-        self.device = int(device)
-        mn = self.DEFAULT_MIN_LF if min_load_factor is None else min_load_factor
-        mx = self.DEFAULT_MAX_LF if max_load_factor is None else max_load_factor
-        st = self._L.kh_wide_create(C.byref(self._h), KH_KIND_ROBINHOOD, _hash_id(hash), seed, capacity, mn, mx, self.device)
-        if st != K.KH_OK:
-            self._h = C.c_void_p()
-            raise KhError(st, "kh_wide_create failed (is a GPU visible and the HIP library built?)")
-
-    def _chk(self, st):
-        if st != K.KH_OK:
-            raise KhError(st, self._L.kh_wide_last_error(self._h).decode())
-
-    def _sync_stream(self, *bufs):
-        if torch is not None and any(b is not None and b.where == K.KH_MEM_DEVICE for b in bufs):
-            self._L.kh_wide_set_stream(self._h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.kh_wide_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _u64(self, fn):
-        v = C.c_uint64()
-        self._chk(fn(self._h, C.byref(v)))
-        return v.value
-
-    def size(self):
-        return self._u64(self._L.kh_wide_size)
-
-    def __len__(self):
-        return self.size()
-
-    def capacity(self):
-        return self._u64(self._L.kh_wide_capacity)
-
-    def _lf(self, i):
-        f = [C.c_float(), C.c_float(), C.c_float()]
-        self._chk(self._L.kh_wide_get_load_factors(self._h, C.byref(f[0]), C.byref(f[1]), C.byref(f[2])))
-        return f[i].value
-
-    def get_min_load_factor(self):
-        return self._lf(0)
-
-    def get_max_load_factor(self):
-        return self._lf(1)
-
-    def get_load_factor(self):
-        return self._lf(2)
-
-    def set_min_load_factor(self, f):
-        self._chk(self._L.kh_wide_set_min_load_factor(self._h, f))
-
-    def set_max_load_factor(self, f):
-        self._chk(self._L.kh_wide_set_max_load_factor(self._h, f))
-
-    def clear(self):
-        self._chk(self._L.kh_wide_clear(self._h))
-
-    def reserve(self, n):
-        self._chk(self._L.kh_wide_reserve(self._h, int(n)))
-
-    def rehash(self, b):
-        self._chk(self._L.kh_wide_rehash(self._h, int(b)))
 
     def _insert(self, fn, keys, vals):
         kb = _keys(keys)
@@ -124,19 +54,11 @@ class hashmap_robinhood_doubling_wide:
         """Reducer = std::plus (wrapping 32-bit); vals None: every occurrence counts 1"""
         return self._insert(self._L.kh_wide_insert_reduce_plus, keys, vals)
 
-    def _out(self, kb, n, np_dtype, torch_dtype, shape=None):
-        shape = (n,) if shape is None else shape
-        if kb.where == K.KH_MEM_DEVICE:
-            t = torch.zeros(shape, dtype=torch_dtype, device=kb.device)
-            return t, t.data_ptr()
-        a = np.zeros(shape, dtype=np_dtype)
-        return a, a.ctypes.data
-
     def count(self, keys):
         kb = _keys(keys)
         self._sync_stream(kb)
         n = kb.n // 2
-        out, optr = self._out(kb, n, np.uint8, torch.uint8 if torch is not None else None)
+        out, optr = self._out(kb, n, np.uint8, torch.uint8 if torch is not None else None, zero=True)
         self._chk(self._L.kh_wide_count(self._h, kb.ptr, n, kb.where, optr))
         return out
 
@@ -145,8 +67,8 @@ class hashmap_robinhood_doubling_wide:
         kb = _keys(keys)
         self._sync_stream(kb)
         n = kb.n // 2
-        vals, vptr = self._out(kb, n, np.uint32, torch.int32 if torch is not None else None)
-        found, fptr = self._out(kb, n, np.uint8, torch.uint8 if torch is not None else None)
+        vals, vptr = self._out(kb, n, np.uint32, torch.int32 if torch is not None else None, zero=True)
+        found, fptr = self._out(kb, n, np.uint8, torch.uint8 if torch is not None else None, zero=True)
         nf = C.c_uint64()
         self._chk(self._L.kh_wide_find(self._h, kb.ptr, n, kb.where, vptr, fptr, C.byref(nf)))
         return vals, found
@@ -156,8 +78,8 @@ class hashmap_robinhood_doubling_wide:
         kb = _keys(keys)
         self._sync_stream(kb)
         n = kb.n // 2
-        ok, kptr = self._out(kb, n, np.uint64, torch.int64 if torch is not None else None, (n, 2))
-        ov, vptr = self._out(kb, n, np.uint32, torch.int32 if torch is not None else None)
+        ok, kptr = self._out(kb, (n, 2), np.uint64, torch.int64 if torch is not None else None, zero=True)
+        ov, vptr = self._out(kb, n, np.uint32, torch.int32 if torch is not None else None, zero=True)
         nf = C.c_uint64()
         self._chk(self._L.kh_wide_find_compact(self._h, kb.ptr, n, kb.where, kptr, vptr, C.byref(nf)))
         return ok[: nf.value], ov[: nf.value]
@@ -188,16 +110,6 @@ class hashmap_robinhood_doubling_wide:
         o = np.lexsort((k[:, 0], k[:, 1]))
         return k[o], v[o]
 
-    def export_info(self):
-        out = np.zeros(self.capacity(), dtype=np.uint8)
-        self._chk(self._L.kh_wide_export_info(self._h, out.ctypes.data))
-        return out
-
-    def displacement_histogram(self):
-        out = np.zeros(128, dtype=np.uint64)
-        self._chk(self._L.kh_wide_displacement_histogram(self._h, out.ctypes.data))
-        return out
-
 
 def hash_batch_wide(keys, hash="murmur3avx64", seed=43, device=0):
     """Hash::operator()(Key const*, count, out) for 16-byte keys: (n, 2) keys -> n 64-bit hashes"""
@@ -216,24 +128,28 @@ def hash_batch_wide(keys, hash="murmur3avx64", seed=43, device=0):
     return out
 
 
-def kmers128_from_sequence(seq, k=63, canonical=True, device=0, _fastq=False):
-    """-> (n, 2) k-mers (numpy uint64 for host input, torch int64 CUDA tensor for device input), sequence order; k = 1..64"""
-    L = K.lib()
+def _kmers(fn_name, words, seq, k, canonical, device):
+    """shared body of kmers_from_sequence / kmers128_from_sequence (and their FASTQ forms): `words` 64-bit words per k-mer"""
     if isinstance(seq, (bytes, bytearray)):
         seq = np.frombuffer(seq, dtype=np.uint8)
     b = _Buf(seq, np.uint8, 1)
+    shape = max(b.n, 1) if words == 1 else (max(b.n, 1), words)
     n_out = C.c_uint64()
     if b.where == K.KH_MEM_DEVICE:
-        out = torch.empty((max(b.n, 1), 2), dtype=torch.int64, device=b.device)
+        out = torch.empty(shape, dtype=torch.int64, device=b.device)
         optr, stream = out.data_ptr(), torch.cuda.current_stream(device).cuda_stream
     else:
-        out = np.zeros((max(b.n, 1), 2), dtype=np.uint64)
+        out = np.zeros(shape, dtype=np.uint64)
         optr, stream = out.ctypes.data, None
-    fn = L.kh_kmers128_from_fastq if _fastq else L.kh_kmers128_from_sequence
-    st = fn(b.ptr, b.n, k, 1 if canonical else 0, b.where, optr, C.byref(n_out), device, stream)
+    st = getattr(K.lib(), fn_name)(b.ptr, b.n, k, 1 if canonical else 0, b.where, optr, C.byref(n_out), device, stream)
     if st != K.KH_OK:
-        raise KhError(st, "kh_kmers128_from_fastq" if _fastq else "kh_kmers128_from_sequence")
+        raise KhError(st, fn_name)
     return out[: n_out.value]
+
+
+def kmers128_from_sequence(seq, k=63, canonical=True, device=0, _fastq=False):
+    """-> (n, 2) k-mers (numpy uint64 for host input, torch int64 CUDA tensor for device input), sequence order; k = 1..64"""
+    return _kmers("kh_kmers128_from_fastq" if _fastq else "kh_kmers128_from_sequence", 2, seq, k, canonical, device)
 
 
 def kmers128_from_fastq(text, k=63, canonical=True, device=0):

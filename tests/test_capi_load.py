@@ -67,3 +67,18 @@ def test_product_never_touches_the_oracle():
                     if re.search(r"oracle_py|kh_oracle|libkh_oracle|libref_lp|from oracle|import oracle", txt):
                         bad.append(os.path.join(dp, fn))
     assert not bad, bad
+
+
+def test_wide_table_has_its_own_members_only():
+    """hashmap_robinhood_doubling_wide shares the handle / scalar-state core with the 64-bit tables, but no member that would pass
+    its handle to a kh_* (64-bit) entry point; every public member it had before the host code was shared is still there"""
+    from kmerhash_amd.wide import hashmap_robinhood_doubling_wide as W
+    narrow_only = ["update", "insert_one", "erase_one", "set_key_transform", "load_thresholds", "insert_begin", "insert_feed", "insert_end",
+                   "insert_abort", "export_slots", "profile", "profile_enable", "profile_reset", "insert_integrated"]
+    assert [m for m in narrow_only if hasattr(W, m)] == []
+    assert [m for m in dir(W) if m.startswith("profile")] == []
+    public = ["DEFAULT_MIN_LF", "DEFAULT_MAX_LF", "close", "size", "__len__", "capacity", "get_min_load_factor", "get_max_load_factor",
+              "get_load_factor", "set_min_load_factor", "set_max_load_factor", "clear", "reserve", "rehash", "insert", "insert_reduce_plus",
+              "count", "find_values", "find", "erase", "to_vector", "keys", "sorted_items", "export_info", "displacement_histogram"]
+    assert [m for m in public if not hasattr(W, m)] == []
+    assert (W.DEFAULT_MIN_LF, W.DEFAULT_MAX_LF) == (0.4, 0.9)
