@@ -12,6 +12,8 @@ predictable from the read positions alone, which is what --verify checks at any 
 (kh_kmers_from_fastq: record structure, 2-bit packing and canonicalisation), and feeds the k-mers to the sharded counting
 table (kmerhash_amd.dist.ShardedTable.insert_counts: hash partition, RCCL exchange, local std::plus insert; one rank: no
 exchange).  Launch model as bench.py: without WORLD_SIZE this process starts the N ranks itself and never touches a GPU.
+-k 33..64: 16-byte k-mers {w0, w1} (kh_kmers128_from_fastq) in the wide table behind kmerhash_amd.dist.WideGpuBackend; --verify then
+predicts 128-bit k-mers, --out writes 16 + 2 bytes per tuple, --hll-reserve is refused (no HyperLogLog over 16-byte keys).
 Prints ONE JSON line (rank 0).  Informational driver for SURVEY 8f-2 / configs[4]; the contract benchmark is ../bench.py."""
 import argparse
 import json
@@ -44,10 +46,37 @@ def parse(argv):
     ap.add_argument("--hll-reserve", action="store_true", help="pre-size the table from a HyperLogLog estimate per batch instead of doubling under load")
     ap.add_argument("--profile", action="store_true", help="per-kernel HIP-event times of the local table (kh_profile_*) in the JSON line")
     ap.add_argument("--verify", action="store_true", help="check size, total count and a sample of 10^5 k-mer counts against the prediction from the read positions")
-    ap.add_argument("--out", default="", help="write this rank's (k-mer, count) tuples (BenchmarkKmerCounter.cpp:1022-1211): 8 + 2 bytes each like the "
+    ap.add_argument("--out", default="", help="write this rank's (k-mer, count) tuples (BenchmarkKmerCounter.cpp:1022-1211): 8 + 2 bytes each (16 + 2 for -k > 32) like the "
                                                "reference, whose CountType is uint16_t (:184) -- the table's 32-bit counts are truncated to 16 bits in the FILE "
                                                "(= the value the reference's wrapping counter would hold); find / count / --verify use the 32-bit counts")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    # refused before any process, GPU or process group is set up
+    if not 1 <= args.k <= 64:
+        ap.error("-k must be 1..64")
+    if args.k > 32 and args.hll_reserve:
+        ap.error("--hll-reserve needs -k <= 32: the HyperLogLog has no update over 16-byte k-mers")
+    return args
+
+
+def canonical_kmers128_at(genome, positions, k):
+    """(n, 2) canonical k-mers {w0, w1} of the genome windows starting at `positions`, 32 < k <= 64 (numpy; A0 C1 G2 T3, first base
+    most significant; canonical = the smaller of the k-mer and its reverse complement as 128-bit integers)"""
+    pos = np.asarray(positions, dtype=np.int64)
+    z = lambda: np.zeros(len(pos), dtype=np.uint64)
+    f1, f0, r1, r0 = z(), z(), z(), z()
+    two, top = np.uint64(2), np.uint64(62)
+    mask_hi = np.uint64((1 << (2 * k - 64)) - 1) if k < 64 else np.uint64(0xFFFFFFFFFFFFFFFF)
+    for j in range(k):
+        c = genome[pos + j].astype(np.uint64)
+        f1 = ((f1 << two) | (f0 >> top)) & mask_hi
+        f0 = (f0 << two) | c
+        d = np.uint64(3) - c                        # base j of the window is base k-1-j of the reverse complement: bits 2j, 2j+1
+        if 2 * j < 64:
+            r0 |= d << np.uint64(2 * j)
+        else:
+            r1 |= d << np.uint64(2 * j - 64)
+    fw_less = (f1 < r1) | ((f1 == r1) & (f0 <= r0))
+    return np.ascontiguousarray(np.stack([np.where(fw_less, f0, r0), np.where(fw_less, f1, r1)], axis=1))
 
 
 def _free_port():
@@ -92,6 +121,7 @@ def run_rank(args):
         import torch.distributed as dist
         dist.init_process_group("nccl", device_id=dev)
     chunks = args.chunks if args.chunks > 0 else (4 if world > 1 else 1)
+    wide = args.k > 32          # 16-byte k-mers {w0, w1}: the wide table behind WideGpuBackend (parse() has checked -k and --hll-reserve)
 
     # ---- input: this rank's reads of the common genome (generation is not timed)
     t0 = time.perf_counter()
@@ -133,7 +163,7 @@ def run_rank(args):
         batch_note = None
     cuts = [rec * (args.reads * i // args.batches) for i in range(args.batches + 1)]
 
-    be = khd.GpuBackend(local, "rh", 128, 0.35, 0.8, args.hash, 43)
+    be = khd.WideGpuBackend(local, 128, 0.35, 0.8, args.hash, 43) if wide else khd.GpuBackend(local, "rh", 128, 0.35, 0.8, args.hash, 43)
     st = khd.ShardedTable(be, timing=True)
     hll = hyperloglog64(12, 0, args.hash, 43, local) if args.hll_reserve else None
     kc = KM.ShardedKmerCounter(st, args.k, True, chunks=chunks, reserve_from_estimate=args.hll_reserve, hll=hll)
@@ -145,6 +175,9 @@ def run_rank(args):
             torch.cuda.synchronize()
 
     caps = []
+    if args.profile and wide:
+        print("[kmer_counter] --profile: the wide table has no per-kernel profile; ignored", file=sys.stderr)
+        args.profile = False
     if args.profile:
         be.table.profile_enable(True)
     sync()
@@ -186,11 +219,12 @@ def run_rank(args):
         del d, dcov, one
         if genome is None:
             genome = dgenome.cpu().numpy()
-        qk = KM.canonical_kmers_at(genome, pos, args.k)
+        qk = canonical_kmers128_at(genome, pos, args.k) if wide else KM.canonical_kmers_at(genome, pos, args.k)
         pk, vals, found = st.find(torch.from_numpy(qk.view(np.int64)).to(dev))
-        got = dict(zip(pk.cpu().numpy().view(np.uint64).tolist(), ((vals.cpu().numpy().view(np.uint32).astype(np.int64)) * found.cpu().numpy()).tolist()))
+        as_keys = (lambda a: [tuple(r) for r in a.tolist()]) if wide else (lambda a: a.tolist())       # a wide k-mer is the row (w0, w1)
+        got = dict(zip(as_keys(pk.cpu().numpy().view(np.uint64)), ((vals.cpu().numpy().view(np.uint32).astype(np.int64)) * found.cpu().numpy()).tolist()))
         exp = {}
-        for kk, c in zip(qk.tolist(), cov_at.tolist()):
+        for kk, c in zip(as_keys(qk), cov_at.tolist()):
             exp[kk] = c                                            # (a k-mer sampled twice has the same position-independent count)
         bad = sum(1 for kk, c in exp.items() if got.get(kk, -1) != (c & 0xFFFFFFFF))
         tot = torch.tensor([total_local], dtype=torch.int64, device=dev)
@@ -202,14 +236,14 @@ def run_rank(args):
 
     if args.cycle:
         # queries: every s-th k-mer of this rank's first batch (BenchmarkKmerIndex samples the input file the same way)
-        km = KM.kmers_from_fastq(dfq[cuts[0]:cuts[1]], args.k, True, local)
+        km = (KM.kmers128_from_fastq if wide else KM.kmers_from_fastq)(dfq[cuts[0]:cuts[1]], args.k, True, local)
         qs = km[:: args.sample_ratio].contiguous()
         sync()
         t0 = time.perf_counter()
         cyc = kc.cycle(qs)
         sync()
         t_cyc = time.perf_counter() - t0
-        nq = int(qs.numel())
+        nq = int(qs.shape[0])
         ok = ok and cyc["count_hits"] == nq and cyc["find_hits"] == nq and cyc["count_hits_after"] == 0
         # (ops_per_s: the four operations over their own synchronised times; `seconds` is the wall clock of the whole call, which also
         #  holds torch's result reductions -- their first use loads torch kernels, ~0.1 s once per process)
@@ -217,7 +251,8 @@ def run_rank(args):
                             ok=bool(cyc["count_hits"] == nq and cyc["count_hits_after"] == 0))
     if args.out:
         k_, v_ = be.table.to_vector()
-        recs = np.zeros(len(k_), dtype=np.dtype([("kmer", "<u8"), ("count", "<u2")]))
+        # (k > 32: 16 + 2 bytes per tuple, the k-mer as {w0, w1} -- what KmerCounter.write gives)
+        recs = np.zeros(len(k_), dtype=np.dtype([("kmer", np.dtype(("<u8", (2,))) if wide else "<u8"), ("count", "<u2")]))
         recs["kmer"] = k_; recs["count"] = v_.astype(np.uint16)
         recs.tofile(args.out + (".%d" % rank if world > 1 else ""))
     if rank == 0:

@@ -285,6 +285,29 @@ kh_status kh_wide_erase(kh_wtable* t, const void* keys, uint64_t n, kh_mem where
 kh_status kh_wide_to_vector(kh_wtable* t, uint64_t* keys_host /* u64[2 size] */, uint32_t* vals_host, uint64_t* n_out);
 kh_status kh_wide_export_info(kh_wtable* t, uint8_t* out_host /* capacity bytes */);
 kh_status kh_wide_displacement_histogram(kh_wtable* t, uint64_t out[128]);
+/* ---- streamed insert of a wide table: the contract written above kh_insert_begin, for 16-byte keys.  The result equals ONE
+ *      kh_wide_insert (KH_INS_REDUCE_PLUS: kh_wide_insert_reduce_plus, vals may then be NULL) of the pieces concatenated in feed order:
+ *      first value wins between pieces, same capacity rule, same trailing reserve(size()).  A feed of device memory only queues the
+ *      counting half of the partition on its piece and returns without synchronising; DEVICE BUFFERS MUST STAY VALID AND UNCHANGED
+ *      UNTIL kh_wide_insert_end (or _abort) RETURNS -- they are read again there.  Host buffers are copied and may be reused as soon
+ *      as the feed returns.  At most 16 non-empty feeds (KH_ERR_UNSUPPORTED beyond, whatever the state of the table).  Between begin and end every other call that
+ *      mutates the table or uses its workspace returns KH_ERR_INVALID, and so do a feed beyond n_total, an end before n_total pairs
+ *      were fed (which also closes the streamed insert, nothing inserted) and feed / end without begin.  kh_wide_insert_abort drops the
+ *      pieces and leaves the table untouched and usable; it synchronises the table's stream.  KH_INS_REPEATABLE is accepted and changes
+ *      nothing: the wide partition is exact (count, scan, scatter), so A WIDE TABLE NEVER RETURNS KH_ERR_RETRY. */
+kh_status kh_wide_insert_begin_ex(kh_wtable* t, uint64_t n_total, unsigned flags /* KH_INS_REDUCE_PLUS | KH_INS_REPEATABLE */);
+kh_status kh_wide_insert_feed(kh_wtable* t, const void* keys /*[h|d] u64[2n]*/, const void* vals /*[h|d] u32[n] or NULL*/, uint64_t n,
+                              kh_mem where);
+kh_status kh_wide_insert_end(kh_wtable* t, uint64_t* n_inserted);
+kh_status kh_wide_insert_abort(kh_wtable* t);
+/* kh_shard_permute for 16-byte keys: rank = hash of the 16 bytes (what kh_wide_hash_batch computes) & (nranks-1), or % nranks when
+ *      nranks is not a power of two; pairs grouped by destination rank, rank 0 first, INPUT ORDER KEPT inside a rank.  Device buffers
+ *      only; nranks 1..64; out_keys_dev == NULL: count only; n == 0: counts of 0.  keys_dev and out_keys_dev MUST BE 16-BYTE ALIGNED
+ *      (every key is read and written as one 16-byte access): KH_ERR_INVALID otherwise. */
+kh_status kh_wide_shard_permute(kh_hash hash, uint64_t seed, uint32_t nranks,
+                                const uint64_t* keys_dev /* u64[2n] */, const uint32_t* vals_dev /* may be NULL */, uint64_t n,
+                                uint64_t* out_keys_dev /* u64[2n]; NULL = count only */, uint32_t* out_vals_dev,
+                                uint64_t* counts_host, int device, void* hip_stream);
 /* out[i] = hash of the 16-byte key i */
 kh_status kh_wide_hash_batch(kh_hash hash, uint64_t seed, const void* keys /*[h|d] u64[2n]*/, uint64_t n, kh_mem where,
                              uint64_t* out /*[h|d]*/, int device, void* hip_stream);

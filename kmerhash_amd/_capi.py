@@ -29,6 +29,8 @@ SYMBOLS = [
     "kh_wide_set_min_load_factor", "kh_wide_set_max_load_factor", "kh_wide_clear", "kh_wide_reserve", "kh_wide_rehash", "kh_wide_insert",
     "kh_wide_insert_reduce_plus", "kh_wide_count", "kh_wide_find", "kh_wide_find_compact", "kh_wide_erase", "kh_wide_to_vector",
     "kh_wide_export_info", "kh_wide_displacement_histogram", "kh_wide_hash_batch", "kh_kmers128_from_sequence", "kh_kmers128_from_fastq",
+    # wide keys across GPUs: the streamed insert and the stable partition by destination rank
+    "kh_wide_insert_begin_ex", "kh_wide_insert_feed", "kh_wide_insert_end", "kh_wide_insert_abort", "kh_wide_shard_permute",
 ]
 
 _lib = None
@@ -146,6 +148,11 @@ def lib():
     L.kh_wide_export_info.argtypes = [vp, vp]
     L.kh_wide_displacement_histogram.argtypes = [vp, vp]
     L.kh_wide_hash_batch.argtypes = [i32, u64, vp, u64, i32, vp, i32, vp]
+    L.kh_wide_insert_begin_ex.argtypes = [vp, u64, u32]
+    L.kh_wide_insert_feed.argtypes = [vp, vp, vp, u64, i32]
+    L.kh_wide_insert_end.argtypes = [vp, pu64]
+    L.kh_wide_insert_abort.argtypes = [vp]
+    L.kh_wide_shard_permute.argtypes = [i32, u64, u32, vp, vp, u64, vp, vp, vp, i32, vp]
     L.kh_kmers128_from_sequence.argtypes = [vp, u64, u32, i32, i32, vp, pu64, i32, vp]
     L.kh_kmers128_from_fastq.argtypes = [vp, u64, u32, i32, i32, vp, pu64, i32, vp]
     for s in SYMBOLS:

@@ -107,11 +107,11 @@ __global__ __launch_bounds__(KW_PART_THREADS) void kw_part_count(const uint64_t*
     kw_wave_reserve(q, i < n, nullptr, cnt);
   }
 }
-// (vals == nullptr: every value is vconst)
+// (vals == nullptr: every value is vconst; pos0: the stream position of keys[0] -- a piece of a streamed insert)
 template <int HASH>
 __global__ __launch_bounds__(KW_PART_THREADS) void kw_part_scatter(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t vconst,
                                                                    uint64_t n, uint64_t seed, uint32_t PB, unsigned long long* __restrict__ cursor,
-                                                                   KwRec* __restrict__ rec) {
+                                                                   KwRec* __restrict__ rec, uint32_t pos0 = 0) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x; i0 < n; i0 += stride) {
     const uint64_t i = i0 + threadIdx.x;
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(KW_PART_THREADS) void kw_part_scatter(const uint64_
       if (vals) v = vals[i];
     }
     const uint32_t pos = kw_wave_reserve(q, i < n, cursor, nullptr);
-    if (i < n) { KwRec r; r.w0 = w0; r.w1 = w1; r.iv = ((uint64_t)(uint32_t)i << 32) | v; rec[pos] = r; }
+    if (i < n) { KwRec r; r.w0 = w0; r.w1 = w1; r.iv = ((uint64_t)(pos0 + (uint32_t)i) << 32) | v; rec[pos] = r; }
   }
 }
 
@@ -539,6 +539,177 @@ __global__ void kw_disp_hist(const KwSlot* __restrict__ slots, uint64_t cap, uns
   }
   __syncthreads();
   if (threadIdx.x < 128 && h[threadIdx.x]) atomicAdd(&out128[threadIdx.x], (unsigned long long)h[threadIdx.x]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// multi-GPU sharding of 16-byte keys: stable partition of (key, value) by rank = kh_hash128(key, seed) mod p -- the wide counterparts
+// of k_shard_count / k_shard_scatter / k_shard_scatter8 (same [rank][tile] counts, same k_scan_u32_to_u64, same staging of a tile in
+// LDS in (rank, input order) -- kw_shard_scatter8 only; the generic kw_shard_scatter for p > 8 writes every pair straight to its place).
+// A tile is 2048 keys, four per lane: 2048 x (16 + 4) B + counters = 41.1 KB of LDS in kw_shard_scatter8, THREE 512-lane workgroups per
+// CU (6 waves per SIMD; four would need 164.5 KB of the 160 KB) -- the 4096-key tile of the 64-bit kernel would take 80 KB here and
+// leave one workgroup per CU.  Every key is one 16-byte load (keys and out_keys must be 16-byte aligned: the host entry point
+// checks); all of a lane's loads are issued before the first is hashed (clamped indices).
+// ---------------------------------------------------------------------------------------------
+#define KW_SHARD_THREADS 512
+#define KW_SHARD_ITEMS 4
+#define KW_SHARD_TILE (KW_SHARD_THREADS * KW_SHARD_ITEMS)
+template <int HASH>
+__device__ __forceinline__ uint32_t kw_rank_of(const uint4 k, uint64_t seed, uint32_t p, uint32_t pmask) {
+  const uint64_t h = kw_hash<HASH>((uint64_t)k.x | ((uint64_t)k.y << 32), (uint64_t)k.z | ((uint64_t)k.w << 32), seed);
+  return pmask ? (uint32_t)(h & pmask) : (uint32_t)(h % p);
+}
+template <int HASH>
+__global__ __launch_bounds__(KW_SHARD_THREADS) void kw_shard_count(const uint64_t* __restrict__ keys, uint64_t n, uint64_t seed, uint32_t p, uint32_t pmask,
+                                                                   uint32_t* __restrict__ tile_counts /* [p][ntiles] */, uint32_t ntiles) {
+  __shared__ uint32_t h[KH_SHARD_MAXR];
+  if (threadIdx.x < KH_SHARD_MAXR) h[threadIdx.x] = 0;
+  __syncthreads();
+  const uint64_t base = (uint64_t)blockIdx.x * KW_SHARD_TILE;
+  const uint4* k4 = reinterpret_cast<const uint4*>(keys);
+  uint4 key[KW_SHARD_ITEMS];
+#pragma unroll
+  for (uint32_t k = 0; k < KW_SHARD_ITEMS; ++k) {
+    const uint64_t i = base + threadIdx.x + k * KW_SHARD_THREADS;
+    key[k] = k4[i < n ? i : n - 1];
+  }
+  if (p <= 8) {
+    // per-lane counts in 16-bit fields of two 64-bit words, reduced over the wave with shuffles (k_shard_count)
+    unsigned long long c0 = 0, c1 = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < KW_SHARD_ITEMS; ++k) {
+      const uint64_t i = base + threadIdx.x + k * KW_SHARD_THREADS;
+      if (i < n) {
+        const uint32_t r = kw_rank_of<HASH>(key[k], seed, p, pmask);
+        if (r < 4) c0 += 1ull << (16 * r); else c1 += 1ull << (16 * (r - 4));
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) { c0 += __shfl_down(c0, off, 64); c1 += __shfl_down(c1, off, 64); }
+    if ((threadIdx.x & 63) == 0)
+      for (uint32_t r = 0; r < p; ++r) {
+        const uint32_t c = (uint32_t)(((r < 4 ? c0 : c1) >> (16 * (r & 3))) & 0xFFFFu);
+        if (c) atomicAdd(&h[r], c);
+      }
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < KW_SHARD_ITEMS; ++k) {
+      const uint64_t i = base + threadIdx.x + k * KW_SHARD_THREADS;
+      if (i < n) atomicAdd(&h[kw_rank_of<HASH>(key[k], seed, p, pmask)], 1u);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < p) tile_counts[(uint64_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
+}
+// any p <= KH_SHARD_MAXR: lane t owns items [4t, 4t+4) of the tile; per rank, an exclusive scan over the lanes gives the order
+template <int HASH>
+__global__ __launch_bounds__(KW_SHARD_THREADS) void kw_shard_scatter(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint64_t n,
+                                                                     uint64_t seed, uint32_t p, uint32_t pmask,
+                                                                     const uint64_t* __restrict__ tile_off /* [p][ntiles] exclusive */, uint32_t ntiles,
+                                                                     uint64_t* __restrict__ ok, uint32_t* __restrict__ ov) {
+  __shared__ uint32_t wtot[KW_SHARD_THREADS / 64][KH_SHARD_MAXR];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const uint64_t base = (uint64_t)blockIdx.x * KW_SHARD_TILE + (uint64_t)tid * KW_SHARD_ITEMS;
+  const uint4* k4 = reinterpret_cast<const uint4*>(keys);
+  uint4 key[KW_SHARD_ITEMS]; uint32_t val[KW_SHARD_ITEMS], rk[KW_SHARD_ITEMS];
+#pragma unroll
+  for (int j = 0; j < KW_SHARD_ITEMS; ++j) { const uint64_t i = base + j; key[j] = k4[i < n ? i : n - 1]; }
+#pragma unroll
+  for (int j = 0; j < KW_SHARD_ITEMS; ++j) { const uint64_t i = base + j; val[j] = vals ? vals[i < n ? i : n - 1] : 0u; }
+#pragma unroll
+  for (int j = 0; j < KW_SHARD_ITEMS; ++j) rk[j] = base + j < n ? kw_rank_of<HASH>(key[j], seed, p, pmask) : 0xFFFFFFFFu;
+  for (uint32_t r = 0; r < p; ++r) {
+    uint32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < KW_SHARD_ITEMS; ++j) c += (rk[j] == r) ? 1u : 0u;
+    uint32_t incl = c;
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t o = __shfl_up(incl, off, 64);
+      if (lane >= (uint32_t)off) incl += o;
+    }
+    if (lane == 63) wtot[wid][r] = incl;
+    __syncthreads();
+    uint32_t wpre = 0;
+    for (uint32_t w = 0; w < wid; ++w) wpre += wtot[w][r];
+    uint64_t pos = tile_off[(uint64_t)r * ntiles + blockIdx.x] + wpre + incl - c;
+#pragma unroll
+    for (int j = 0; j < KW_SHARD_ITEMS; ++j) {
+      if (rk[j] == r) {
+        reinterpret_cast<uint4*>(ok)[pos] = key[j];
+        if (vals) ov[pos] = val[j];
+        ++pos;
+      }
+    }
+  }
+}
+// p <= 8 ranks (one node): all per-rank prefix sums in one wave scan of packed 16-bit counters, the tile staged in LDS in (rank, input
+// order), the write-out coalesced (16 bytes per lane, consecutive lanes consecutive keys).  Stable, like the generic kernel.
+template <int HASH>
+__global__ __launch_bounds__(KW_SHARD_THREADS) void kw_shard_scatter8(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint64_t n,
+                                                                      uint64_t seed, uint32_t p, uint32_t pmask,
+                                                                      const uint64_t* __restrict__ tile_off /* [p][ntiles] exclusive */, uint32_t ntiles,
+                                                                      uint64_t* __restrict__ ok, uint32_t* __restrict__ ov) {
+  __shared__ uint4 lk[KW_SHARD_TILE];
+  __shared__ uint32_t lv[KW_SHARD_TILE];
+  __shared__ unsigned long long wtot[KW_SHARD_THREADS / 64][2];
+  __shared__ uint32_t rank_off[9];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const uint64_t tbase = (uint64_t)blockIdx.x * KW_SHARD_TILE;
+  const uint64_t base = tbase + (uint64_t)tid * KW_SHARD_ITEMS;
+  const uint32_t tile_len = (n - tbase) < KW_SHARD_TILE ? (uint32_t)(n - tbase) : KW_SHARD_TILE;
+  const uint4* k4 = reinterpret_cast<const uint4*>(keys);
+  uint4 key[KW_SHARD_ITEMS]; uint32_t val[KW_SHARD_ITEMS], rk[KW_SHARD_ITEMS];
+  unsigned long long c0 = 0, c1 = 0;     // counts of ranks 0-3 / 4-7, 16 bits each
+#pragma unroll
+  for (int j = 0; j < KW_SHARD_ITEMS; ++j) { const uint64_t i = base + j; key[j] = k4[i < n ? i : n - 1]; }
+#pragma unroll
+  for (int j = 0; j < KW_SHARD_ITEMS; ++j) { const uint64_t i = base + j; val[j] = vals ? vals[i < n ? i : n - 1] : 0u; }
+#pragma unroll
+  for (int j = 0; j < KW_SHARD_ITEMS; ++j) {
+    rk[j] = 0xFFu;
+    if (base + j < n) {
+      rk[j] = kw_rank_of<HASH>(key[j], seed, p, pmask);
+      if (rk[j] < 4) c0 += 1ull << (16 * rk[j]); else c1 += 1ull << (16 * (rk[j] - 4));
+    }
+  }
+  unsigned long long i0 = c0, i1 = c1;
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned long long o0 = __shfl_up(i0, off, 64), o1 = __shfl_up(i1, off, 64);
+    if (lane >= (uint32_t)off) { i0 += o0; i1 += o1; }
+  }
+  if (lane == 63) { wtot[wid][0] = i0; wtot[wid][1] = i1; }
+  __syncthreads();
+  unsigned long long e0 = i0 - c0, e1 = i1 - c1, t0 = 0, t1 = 0;
+  for (uint32_t w = 0; w < KW_SHARD_THREADS / 64; ++w) {
+    if (w < wid) { e0 += wtot[w][0]; e1 += wtot[w][1]; }
+    t0 += wtot[w][0]; t1 += wtot[w][1];
+  }
+  if (tid == 0) {
+    uint32_t run = 0;
+    for (uint32_t r = 0; r < 8; ++r) {
+      rank_off[r] = run;
+      run += (uint32_t)(((r < 4 ? t0 : t1) >> (16 * (r & 3))) & 0xFFFFu);
+    }
+    rank_off[8] = run;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < KW_SHARD_ITEMS; ++j) {
+    if (rk[j] != 0xFFu) {
+      const uint32_t r = rk[j];
+      const uint32_t within = (uint32_t)(((r < 4 ? e0 : e1) >> (16 * (r & 3))) & 0xFFFFu);
+      const uint32_t s = rank_off[r] + within;
+      lk[s] = key[j]; lv[s] = val[j];
+      if (r < 4) e0 += 1ull << (16 * r); else e1 += 1ull << (16 * (r - 4));
+    }
+  }
+  __syncthreads();
+  for (uint32_t s = tid; s < tile_len; s += KW_SHARD_THREADS) {
+    uint32_t r = 0;
+#pragma unroll
+    for (uint32_t k = 1; k < 8; ++k) r += (s >= rank_off[k]) ? 1u : 0u;
+    const uint64_t pos = tile_off[(uint64_t)r * ntiles + blockIdx.x] + (s - rank_off[r]);
+    reinterpret_cast<uint4*>(ok)[pos] = lk[s];
+    if (vals) ov[pos] = lv[s];
+  }
 }
 
 // ---------------------------------------------------------------------------------------------

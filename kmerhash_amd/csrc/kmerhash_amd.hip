@@ -151,6 +151,9 @@ struct kh_table {
     ulonglong2 *tmp, *fin;
     KhSrcSet S;
     uint64_t* stage_k; uint32_t* stage_v;
+    // wide table: the pieces fed so far (device pointers: the caller's, or workspace copies of host pieces) and the per-partition
+    // counters every feed's kw_part_count adds to
+    const uint64_t* wk[KH_MAX_SRC]; const uint32_t* wv[KH_MAX_SRC]; uint64_t wn[KH_MAX_SRC]; uint32_t wsrc; uint32_t* wcnt;
   } ins = {};
   uint32_t* part_overflow = nullptr;      // device flag of the histogram-free partition feeding the operation in flight (or null)
   double batch_vf = 1.0;                  // variance factor E[m^2]/E[m] the duplicate sample gave for the batch in flight (1: no duplicate seen)
@@ -2383,8 +2386,20 @@ inline size_t kw_ws_insert(uint64_t n, uint64_t cap_u) {
   return n * (sizeof(KwRec) + 16 + 4 + 8 + 4 + 16 + 4) + np * 48 + ws_rebuild(cap_u) + (size_t(4) << 20);
 }
 
-// one insert() pass over device-resident keys (u64[2n]) / values (u32[n] or null); n < 2^32
-kh_status kw_insert_core(kh_wtable* t, const uint64_t* keys, const uint32_t* vals, uint64_t n, int mode, uint64_t forced_cap, uint64_t* n_new_out) {
+// the per-partition counts of one source added to cnt (queued; the counting half of the partition)
+kh_status kw_count_source(kh_wtable* t, const uint64_t* keys, uint64_t n, uint32_t PB, uint32_t* cnt) {
+  if (n == 0) return KH_OK;
+  Launch L(t, "kw_part_count");
+  KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_part_count<HASH>), dim3(grid_for(n, KW_PART_THREADS, 4096)), dim3(KW_PART_THREADS), 0, t->stream, keys, n,
+                                             t->seed.s, PB, cnt));
+  return KH_OK;
+}
+// one insert() pass over device-resident keys (u64[2n]) / values (u32[n] or null); n < 2^32.  The n keys are the concatenation of
+// nsrc sources (the pieces of a streamed insert; one for a plain insert).  precnt: the per-partition counts of all sources are
+// already queued on the stream into that array (every kh_wide_insert_feed counted its piece when it arrived).
+struct KwSrc { const uint64_t* k; const uint32_t* v; uint64_t n; };
+kh_status kw_insert_core(kh_wtable* t, const KwSrc* src, uint32_t nsrc, uint64_t n, int mode, uint64_t forced_cap, uint64_t* n_new_out,
+                         uint32_t* precnt = nullptr) {
   *n_new_out = 0;
   if (n == 0) return KH_OK;
   const uint64_t cap_u = forced_cap ? forced_cap : capacity_after(t, t->cur.cap, t->lsize, n, n, n - 1);
@@ -2394,22 +2409,28 @@ kh_status kw_insert_core(kh_wtable* t, const uint64_t* keys, const uint32_t* val
   const bool plus = mode == INS_PLUS, plus_live = plus && t->lsize > 0;
   uint32_t *cnt, *cnt_new, *cnt_upd = nullptr, *flags, *nv, *uv = nullptr; uint64_t *off, *noff, *nk, *us = nullptr;
   unsigned long long *cursor, *scal; KwRec* rec;
-  TAKE(cnt, uint32_t, nparts); TAKE(off, uint64_t, nparts + 1); TAKE(cursor, unsigned long long, nparts); TAKE(rec, KwRec, n);
+  if (precnt) cnt = precnt; else TAKE(cnt, uint32_t, nparts);
+  TAKE(off, uint64_t, nparts + 1); TAKE(cursor, unsigned long long, nparts); TAKE(rec, KwRec, n);
   TAKE(cnt_new, uint32_t, nparts); TAKE(noff, uint64_t, nparts + 1); TAKE(nk, uint64_t, 2 * n); TAKE(nv, uint32_t, n);
   TAKE(flags, uint32_t, KH_NFLAGS); TAKE(scal, unsigned long long, 2);
   if (plus_live) { TAKE(cnt_upd, uint32_t, nparts); TAKE(us, uint64_t, n); TAKE(uv, uint32_t, n); }
-  HIPCHK(hipMemsetAsync(cnt, 0, sizeof(uint32_t) * nparts, t->stream));
   HIPCHK(hipMemsetAsync(flags, 0, sizeof(uint32_t) * KH_NFLAGS, t->stream));
   HIPCHK(hipMemsetAsync(scal, 0, 16, t->stream));
-  const uint32_t pgrid = grid_for(n, KW_PART_THREADS, 4096);
-  { Launch L(t, "kw_part_count");
-    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_part_count<HASH>), dim3(pgrid), dim3(KW_PART_THREADS), 0, t->stream, keys, n, t->seed.s, PB, cnt)); }
+  if (!precnt) {
+    HIPCHK(hipMemsetAsync(cnt, 0, sizeof(uint32_t) * nparts, t->stream));
+    for (uint32_t s = 0; s < nsrc; ++s) { kh_status cs = kw_count_source(t, src[s].k, src[s].n, PB, cnt); if (cs != KH_OK) return cs; }
+  }
   { Launch L(t, "k_scan");
     hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, cnt, (uint64_t)nparts, off); }
   HIPCHK(hipMemcpyAsync(cursor, off, sizeof(uint64_t) * nparts, hipMemcpyDeviceToDevice, t->stream));
-  { Launch L(t, "kw_part_scatter");
-    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_part_scatter<HASH>), dim3(pgrid), dim3(KW_PART_THREADS), 0, t->stream, keys, vals,
-                                               plus ? 1u : 0u, n, t->seed.s, PB, cursor, rec)); }
+  { uint64_t pos0 = 0;
+    for (uint32_t s = 0; s < nsrc; ++s) {        // the records of source s carry the stream positions pos0 ..
+      if (src[s].n == 0) continue;
+      Launch L(t, "kw_part_scatter");
+      KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_part_scatter<HASH>), dim3(grid_for(src[s].n, KW_PART_THREADS, 4096)), dim3(KW_PART_THREADS), 0, t->stream,
+                                                 src[s].k, src[s].v, plus ? 1u : 0u, src[s].n, t->seed.s, PB, cursor, rec, (uint32_t)pos0));
+      pos0 += src[s].n;
+    } }
   KwDedupParams D;
   memset(&D, 0, sizeof(D));
   D.rec = rec; D.off = off; D.T = wide(t->cur); D.seed = t->seed.s; D.table_empty = t->lsize == 0 ? 1 : 0;
@@ -2463,8 +2484,33 @@ kh_status kw_insert_core(kh_wtable* t, const uint64_t* keys, const uint32_t* val
 
 // insert(Iter,Iter) / the reducer insert over device-resident input: passes cut only where the one-doubling-per-call rule or the
 // 32-bit stream positions demand it (insert_device), then the trailing reserve(size())
+kh_status kw_insert_device(kh_wtable* t, const uint64_t* kb, const uint32_t* vb, uint64_t n, int mode, uint64_t* n_inserted) {
+  const size_t keep_blk = t->blk, keep_off = t->off;
+  uint64_t total_new = 0, done = 0;
+  kh_status st = KH_OK;
+  while (done < n && st == KH_OK) {
+    uint64_t take = n - done, forced = 0;
+    if (t->lsize >= threshold(t->cur.cap << 1, t->max_lf)) {       // more than one doubling pending: peel one call (insert_device)
+      take = 1;
+      forced = t->cur.cap << 1;
+      while (t->lsize > threshold(forced, t->max_lf)) forced <<= 1;
+    }
+    if (take > g_max_pass) take = g_max_pass;
+    t->blk = keep_blk; t->off = keep_off;
+    uint64_t nn = 0;
+    const KwSrc one = {kb + 2 * done, vb ? vb + done : nullptr, take};
+    st = kw_insert_core(t, &one, 1, take, mode, forced, &nn);
+    total_new += nn;
+    done += take;
+  }
+  if (st == KH_OK) st = do_reserve(t, t->lsize);
+  if (st == KH_OK) HIPCHK(hipStreamSynchronize(t->stream));
+  if (n_inserted) *n_inserted = total_new;
+  return st;
+}
 kh_status kw_do_insert(kh_wtable* t, const void* keys, const void* vals, uint64_t n, kh_mem where, int mode, uint64_t* n_inserted) {
   if (n_inserted) *n_inserted = 0;
+  if (t->ins.active) return refuse_streaming(t);
   if (n && !keys) return fail(t, KH_ERR_INVALID, "null keys");
   HIPCHK(hipSetDevice(t->device));
   const uint64_t np_ = std::min<uint64_t>(n, g_max_pass);
@@ -2479,33 +2525,14 @@ kh_status kw_do_insert(kh_wtable* t, const void* keys, const void* vals, uint64_
     kb = dk;
     if (vals) { uint32_t* dv; TAKE(dv, uint32_t, n); HIPCHK(hipMemcpyAsync(dv, vals, n * 4, hipMemcpyHostToDevice, t->stream)); vb = dv; }
   }
-  const size_t keep_blk = t->blk, keep_off = t->off;
-  uint64_t total_new = 0, done = 0;
-  kh_status st = KH_OK;
-  while (done < n && st == KH_OK) {
-    uint64_t take = n - done, forced = 0;
-    if (t->lsize >= threshold(t->cur.cap << 1, t->max_lf)) {       // more than one doubling pending: peel one call (insert_device)
-      take = 1;
-      forced = t->cur.cap << 1;
-      while (t->lsize > threshold(forced, t->max_lf)) forced <<= 1;
-    }
-    if (take > g_max_pass) take = g_max_pass;
-    t->blk = keep_blk; t->off = keep_off;
-    uint64_t nn = 0;
-    st = kw_insert_core(t, kb + 2 * done, vb ? vb + done : nullptr, take, mode, forced, &nn);
-    total_new += nn;
-    done += take;
-  }
-  if (st == KH_OK) st = do_reserve(t, t->lsize);
-  if (st == KH_OK) HIPCHK(hipStreamSynchronize(t->stream));
-  if (n_inserted) *n_inserted = total_new;
-  return st;
+  return kw_insert_device(t, kb, vb, n, mode, n_inserted);
 }
 
 // find / count / find(Iter,Iter).  Outputs live where the queries live.
 kh_status kw_do_find(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint32_t* out_vals, uint8_t* out_found, uint64_t* out_ckeys,
                      uint32_t* out_cvals, bool compacted, bool count_only, uint64_t* n_found) {
   if (n_found) *n_found = 0;
+  if (t->ins.active) return refuse_streaming(t);
   if (n == 0) return KH_OK;
   if (!keys) return fail(t, KH_ERR_INVALID, "null keys");
   HIPCHK(hipSetDevice(t->device));
@@ -2549,6 +2576,7 @@ kh_status kw_do_find(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, u
 // erase(Iter,Iter): mark the hits, re-lay out without them (RH: never shrinks, hashmap_robinhood.hpp:1430-1440)
 kh_status kw_do_erase(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint64_t* n_erased) {
   *n_erased = 0;
+  if (t->ins.active) return refuse_streaming(t);
   if (n == 0) return KH_OK;
   if (!keys) return fail(t, KH_ERR_INVALID, "null keys");
   HIPCHK(hipSetDevice(t->device));
@@ -2640,6 +2668,133 @@ kh_status kh_wide_erase(kh_wtable* t, const void* keys, uint64_t n, kh_mem where
   if (n_erased) *n_erased = ne;
   if (st == KH_OK && t->lsize < t->min_load) st = do_reserve(t, t->lsize);     // hashmap_robinhood.hpp:1437: reserve() only grows
   return st;
+}
+// ---- streamed insert of a wide table: the contract of kh_insert_begin / feed / end.  A feed queues the COUNTING half of the partition
+//      on its piece (kw_part_count into counters all pieces share) and remembers the piece; kh_wide_insert_end scans the counters
+//      and scatters every piece with its base added to the stream positions -- from there on it is kw_insert_core.  The partition is
+//      exact (count, scan, scatter), so KH_INS_REPEATABLE buys nothing here and KH_ERR_RETRY is never returned.  Batches without a
+//      one-pass form (n_total == 0, more than g_max_pass keys, more than one doubling pending, more than 2^22 partitions) are
+//      collected in workspace and inserted by the general entry point at the end.
+kh_status kh_wide_insert_begin_ex(kh_wtable* t, uint64_t n_total, unsigned flags) {
+  if (!t) return KH_ERR_INVALID;
+  if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is already in progress");
+  if (flags & ~(unsigned)(KH_INS_REDUCE_PLUS | KH_INS_REPEATABLE)) return fail(t, KH_ERR_INVALID, "unknown flag");
+  HIPCHK(hipSetDevice(t->device));
+  memset(&t->ins, 0, sizeof(t->ins));
+  t->ins.mode = (flags & KH_INS_REDUCE_PLUS) ? INS_PLUS : INS_FIRST;
+  t->ins.n_total = n_total;
+  const uint64_t np_ = std::min<uint64_t>(n_total, g_max_pass);
+  const uint64_t cu = capacity_after(t, t->cur.cap, t->lsize, np_ ? np_ : 1, np_, np_ ? np_ - 1 : 0);
+  const uint32_t PB = cu > KH_L ? log2u(cu >> KH_LB) : 0u;
+  t->ins.fallback = n_total == 0 || n_total > g_max_pass || PB > 22 || t->lsize >= threshold(t->cur.cap << 1, t->max_lf);
+  t->ins.cap_u = cu; t->ins.PB = PB;
+  // (n_total * 20: the collected batch of the fall-back, or host pieces copied in; device pieces of the one-pass form take nothing)
+  { kh_status ps = arena_prepare(t, n_total * 20 + kw_ws_insert(np_, cu) + KH_MAX_SRC * 512); if (ps != KH_OK) return ps; }
+  if (n_total) {
+    if (t->ins.fallback) { TAKE(t->ins.stage_k, uint64_t, 2 * n_total); TAKE(t->ins.stage_v, uint32_t, n_total); }
+    else {
+      const uint32_t nparts = 1u << PB;
+      TAKE(t->ins.wcnt, uint32_t, nparts);
+      HIPCHK(hipMemsetAsync(t->ins.wcnt, 0, sizeof(uint32_t) * nparts, t->stream));
+    }
+  }
+  t->ins.active = true;
+  return KH_OK;
+}
+kh_status kh_wide_insert_feed(kh_wtable* t, const void* keys, const void* vals, uint64_t n, kh_mem where) {
+  if (!t) return KH_ERR_INVALID;
+  if (!t->ins.active) return fail(t, KH_ERR_INVALID, "kh_wide_insert_feed without kh_wide_insert_begin_ex");
+  if (n == 0) return KH_OK;
+  if (!keys) return fail(t, KH_ERR_INVALID, "null keys");
+  if (!vals && t->ins.mode != INS_PLUS) return fail(t, KH_ERR_INVALID, "null values");
+  if (t->ins.fed + n > t->ins.n_total) return fail(t, KH_ERR_INVALID, "more pairs fed than announced to kh_wide_insert_begin_ex");
+  if (t->ins.wsrc == KH_MAX_SRC) return fail(t, KH_ERR_UNSUPPORTED, "more than 16 feeds in one streamed insert");     // (either form: the limit does not depend on table state)
+  HIPCHK(hipSetDevice(t->device));
+  const hipMemcpyKind kind = where == KH_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  if (t->ins.fallback) {
+    HIPCHK(hipMemcpyAsync(t->ins.stage_k + 2 * t->ins.fed, keys, n * 16, kind, t->stream));
+    if (vals) HIPCHK(hipMemcpyAsync(t->ins.stage_v + t->ins.fed, vals, n * 4, kind, t->stream));
+    else HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(t->ins.stage_v + t->ins.fed), 1, n, t->stream));
+    ++t->ins.wsrc;
+  } else {
+    const uint64_t* dk = static_cast<const uint64_t*>(keys);
+    const uint32_t* dv = static_cast<const uint32_t*>(vals);
+    if (where == KH_MEM_HOST) {
+      uint64_t* ck; TAKE(ck, uint64_t, 2 * n);
+      HIPCHK(hipMemcpyAsync(ck, keys, n * 16, hipMemcpyHostToDevice, t->stream));
+      dk = ck;
+      if (vals) { uint32_t* cv; TAKE(cv, uint32_t, n); HIPCHK(hipMemcpyAsync(cv, vals, n * 4, hipMemcpyHostToDevice, t->stream)); dv = cv; }
+    }
+    kh_status st = kw_count_source(t, dk, n, t->ins.PB, t->ins.wcnt);
+    if (st != KH_OK) return st;
+    HIPCHK(hipGetLastError());
+    const uint32_t s = t->ins.wsrc++;
+    t->ins.wk[s] = dk; t->ins.wv[s] = dv; t->ins.wn[s] = n;
+  }
+  t->ins.fed += n;
+  if (where == KH_MEM_HOST) HIPCHK(hipStreamSynchronize(t->stream));   // host buffers may be reused as soon as the feed returns
+  return KH_OK;
+}
+kh_status kh_wide_insert_end(kh_wtable* t, uint64_t* n_inserted) {
+  if (n_inserted) *n_inserted = 0;
+  if (!t) return KH_ERR_INVALID;
+  if (!t->ins.active) return fail(t, KH_ERR_INVALID, "kh_wide_insert_end without kh_wide_insert_begin_ex");
+  t->ins.active = false;
+  HIPCHK(hipSetDevice(t->device));
+  if (t->ins.fed != t->ins.n_total) {
+    hipStreamSynchronize(t->stream);      // (queued counts may still read the caller's pieces)
+    return fail(t, KH_ERR_INVALID, "fewer pairs fed than announced to kh_wide_insert_begin_ex");
+  }
+  const uint64_t n = t->ins.n_total;
+  if (t->ins.fallback) return kw_insert_device(t, t->ins.stage_k, t->ins.stage_v, n, t->ins.mode, n_inserted);
+  KwSrc src[KH_MAX_SRC];
+  for (uint32_t s = 0; s < t->ins.wsrc; ++s) { src[s].k = t->ins.wk[s]; src[s].v = t->ins.wv[s]; src[s].n = t->ins.wn[s]; }
+  uint64_t nn = 0;
+  kh_status st = kw_insert_core(t, src, t->ins.wsrc, n, t->ins.mode, 0, &nn, t->ins.wcnt);
+  if (st == KH_OK) st = do_reserve(t, t->lsize);
+  if (st == KH_OK) HIPCHK(hipStreamSynchronize(t->stream));
+  else hipStreamSynchronize(t->stream);
+  if (n_inserted) *n_inserted = nn;
+  return st;
+}
+kh_status kh_wide_insert_abort(kh_wtable* t) { return kh_insert_abort(t); }
+
+// stable partition of 16-byte keys by destination rank (kh_shard_permute for wide keys)
+kh_status kh_wide_shard_permute(kh_hash hash, uint64_t seed, uint32_t p, const uint64_t* keys, const uint32_t* vals, uint64_t n,
+                                uint64_t* out_keys, uint32_t* out_vals, uint64_t* counts_host, int device, void* stream_) {
+  kh_table* t = nullptr;
+  if (p == 0 || p > KH_SHARD_MAXR || !counts_host || (int)hash < 0 || (int)hash > 3) return KH_ERR_INVALID;
+  for (uint32_t r = 0; r < p; ++r) counts_host[r] = 0;
+  if (n == 0) return KH_OK;
+  if (!keys || (out_keys && vals && !out_vals)) return KH_ERR_INVALID;
+  if (((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(out_keys)) & 15u) != 0) return KH_ERR_INVALID;     // one 16-byte access per key
+  if ((n + KW_SHARD_TILE - 1) / KW_SHARD_TILE > 0x7FFFFFFFull) return KH_ERR_UNSUPPORTED;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK(hipSetDevice(device));
+  const uint32_t ntiles = (uint32_t)((n + KW_SHARD_TILE - 1) / KW_SHARD_TILE);
+  const uint32_t pmask = (p & (p - 1)) == 0 ? p - 1 : 0;   // power of two: & (p-1); else % p.  (p == 1: mask 0 -> % 1)
+  uint32_t* tc = nullptr; uint64_t* toff = nullptr;
+  const uint64_t m = (uint64_t)p * ntiles;
+  HIPCHK(pool_alloc(device, m * 4, reinterpret_cast<void**>(&tc)));
+  if (pool_alloc(device, (m + 1) * 8, reinterpret_cast<void**>(&toff)) != hipSuccess) { pool_free(device, tc); return KH_ERR_NOMEM; }
+  KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((kw_shard_count<HASH>), dim3(ntiles), dim3(KW_SHARD_THREADS), 0, stream, keys, n, seed, p, pmask, tc, ntiles));
+  hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, tc, m, toff);
+  if (!out_keys) {
+    // count only
+  } else if (p <= 8) {
+    KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((kw_shard_scatter8<HASH>), dim3(ntiles), dim3(KW_SHARD_THREADS), 0, stream, keys, vals, n, seed, p, pmask, (const uint64_t*)toff, ntiles, out_keys, out_vals));
+  } else {
+    KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((kw_shard_scatter<HASH>), dim3(ntiles), dim3(KW_SHARD_THREADS), 0, stream, keys, vals, n, seed, p, pmask, (const uint64_t*)toff, ntiles, out_keys, out_vals));
+  }
+  std::vector<uint64_t> ends(p + 1);
+  hipError_t e = hipGetLastError();
+  for (uint32_t r = 0; r <= p && e == hipSuccess; ++r)
+    e = hipMemcpyAsync(&ends[r], toff + (uint64_t)r * ntiles, 8, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  pool_free(device, tc); pool_free(device, toff);
+  if (e != hipSuccess) return KH_ERR_HIP;
+  for (uint32_t r = 0; r < p; ++r) counts_host[r] = ends[r + 1] - ends[r];
+  return KH_OK;
 }
 kh_status kh_wide_hash_batch(kh_hash hash, uint64_t seed, const void* keys, uint64_t n, kh_mem where, uint64_t* out, int device, void* stream) {
   return hash_batch_impl(2, hash, KhSeed{seed, 0u}, keys, n, where, out, device, stream);

@@ -23,6 +23,11 @@ A payload exchange is ONE grouped point-to-point launch (ncclGroupStart .. ncclS
 ncclGroupEnd through torch's batch_isend_irecv -- what all_to_all_single with split sizes is made of), so keys and
 values of a piece travel SoA (12 B per pair, no padding) in a single RCCL kernel; every peer pair is one xGMI link.
 
+Key width: a backend with `key_words = 2` (WideGpuBackend: the 16-byte-key table, k-mers with 32 < k <= 64) passes keys as rows of an
+(n, 2) tensor; counts, offsets and slices are in rows, receive buffers are (rows, 2), query results (permuted keys (n, 2), values,
+flags).  Such a backend has no shard_plan: an insert counts and permutes piece by piece, a query batch travels as one piece.  A
+backend without the attribute has 1-D keys, as before.
+
 `backend` objects supply the two device-specific pieces so that the exchange logic can be exercised on CPU
 (gloo, world_size 2/3) with the oracle in tests; the product backend is GpuBackend.
 """
@@ -97,6 +102,58 @@ class GpuBackend:
         if st != self.K.KH_OK:
             raise self.K.KhError(st, "kh_shard_plan_create")
         return _ShardPlan(self, plan, keys), [int(b) for b in bounds], [[int(counts[i * p + r]) for r in range(p)] for i in range(pieces)]
+
+
+class WideGpuBackend:
+    """local table = the 16-byte-key Robin Hood table on this rank's GPU (hashmap_robinhood_doubling_wide_stream); sharding =
+    kh_wide_shard_permute (stable).  Keys are (n, 2) int64 CUDA tensors.  No shard_plan: ShardedTable counts and permutes piece by
+    piece and sends a query batch as one piece."""
+    key_words = 2
+
+    def __init__(self, device, capacity=128, min_lf=0.35, max_lf=0.8, hash="murmur3avx64", seed=43, dist_hash="murmur3avx64",
+                 dist_seed=DIST_SEED):
+        import ctypes as C
+        from . import _capi as K
+        from . import table as T
+        from . import wide as W
+        self.C, self.K = C, K
+        self.device = device
+        self.table = W.hashmap_robinhood_doubling_wide_stream(capacity, min_lf, max_lf, hash=hash, seed=seed, device=device)
+        self.dist_hash = T._hash_id(dist_hash)
+        self.dist_seed = dist_seed
+        self.torch_device = torch.device("cuda", device)
+
+    @staticmethod
+    def _rows(keys):
+        if keys.dim() != 2 or keys.shape[1] != 2 or keys.element_size() != 8:
+            raise ValueError("wide keys: expected a 64-bit tensor of shape (n, 2), got %s" % (tuple(keys.shape),))
+        return keys.contiguous()
+
+    def _permute(self, keys, vals, p, ok, ov):
+        counts = (self.C.c_uint64 * p)()
+        st = self.K.lib().kh_wide_shard_permute(self.dist_hash, self.dist_seed, p, keys.data_ptr(), vals.data_ptr() if vals is not None else None,
+                                                keys.shape[0], ok.data_ptr() if ok is not None else None,
+                                                ov.data_ptr() if ov is not None else None, counts, self.device,
+                                                torch.cuda.current_stream(self.device).cuda_stream)
+        if st != self.K.KH_OK:
+            raise self.K.KhError(st, "kh_wide_shard_permute")
+        return [int(c) for c in counts]
+
+    def shard(self, keys, vals, p):
+        """-> (keys (n, 2) grouped by destination rank, vals grouped, counts[p]) ; stable inside a rank"""
+        keys = self._rows(keys)
+        vals = vals.contiguous() if vals is not None else None
+        ok = torch.empty_like(keys)
+        ov = torch.empty_like(vals) if vals is not None else None
+        return ok, ov, self._permute(keys, vals, p, ok, ov)
+
+    def shard_counts(self, keys, p):
+        """counts[p] of shard() without permuting anything"""
+        return self._permute(self._rows(keys), None, p, None, None)
+
+    def empty(self, n, dtype):
+        """n: a length or a shape ((rows, 2) for key buffers)"""
+        return torch.empty(n, dtype=dtype, device=self.torch_device)
 
 
 def plan_piece_bounds(n, pieces):
@@ -216,6 +273,7 @@ class ShardedTable:
         self.query_pieces = 0          # pieces of THIS rank's find / count batches (0 = by size; GPU backend only)
         self._late = None              # status words received with the last find / count (tensor [p]), not looked at yet
         self._fail_stage = 0           # test hook: the next collective call fails locally at this stage (1..4)
+        self.key_words = int(getattr(backend, "key_words", 1))      # 2: keys are rows of an (n, 2) tensor (16-byte keys)
 
     @property
     def local(self):
@@ -275,6 +333,10 @@ class ShardedTable:
             torch.cuda.synchronize(self.b.torch_device)
         self._late_check()
 
+    def _like(self, rows, x):
+        """a buffer of `rows` entries shaped like the entries of x (key rows of a wide backend keep their second dimension)"""
+        return self.b.empty(rows if x.dim() == 1 else (rows,) + tuple(x.shape[1:]), x.dtype)
+
     # ---- exchange helpers ---------------------------------------------------------------------------
     def _exchange_counts(self, send_counts, ex=None):
         """send_counts: [p][k] (row = destination rank) -> ([p][k] what every source sends here (row = source rank), worst status).
@@ -289,12 +351,12 @@ class ShardedTable:
 
     def _exchange(self, arrays):
         """all-to-all-v of several arrays (khmxx::distribute_permuted / mxx::all2allv :1126) as ONE grouped point-to-point launch.
-        arrays: (send tensor, send offsets[p], send counts[p], recv tensor, recv offsets[p], recv counts[p]) in elements; the
-        receive tensors are filled in place."""
+        arrays: (send tensor, send offsets[p], send counts[p], recv tensor, recv offsets[p], recv counts[p]) in elements (rows of a
+        two-dimensional tensor: a row is contiguous, so is every segment); the receive tensors are filled in place."""
         host = self._host_staged()
         work = []
         for (s, so, sn, r, ro, rn) in arrays:
-            work.append((s.cpu() if host else s, so, sn, torch.empty(r.numel(), dtype=r.dtype) if host else r, ro, rn, r))
+            work.append((s.cpu() if host else s, so, sn, torch.empty(tuple(r.shape), dtype=r.dtype) if host else r, ro, rn, r))
         ops = []
         self_ops = FORCE_COLLECTIVES and dist.get_backend(self.group) == "nccl"       # the self segment through RCCL too (rehearsal)
         for d in range(self.p):
@@ -332,7 +394,7 @@ class ShardedTable:
         """tensors grouped by destination rank -> tensors grouped by source rank (None entries pass through)"""
         tot = int(sum(recv_counts))
         so, ro = self._offs(send_counts), self._offs(recv_counts)
-        outs = [self.b.empty(tot, s.dtype) if s is not None else None for s in sends]
+        outs = [self._like(tot, s) if s is not None else None for s in sends]
         self._exchange([(s, so, send_counts, o, ro, recv_counts) for s, o in zip(sends, outs) if s is not None])
         return outs
 
@@ -352,7 +414,7 @@ class ShardedTable:
         other way round).  The received pieces are kept until the build has succeeded (a repeatable streamed insert, see below).
         Same result as ONE insert of the pieces concatenated piece-major (piece, source rank, position)."""
         self._late_check()
-        n = keys.numel()
+        n = keys.shape[0]
         if self._single():
             with self._span("local_insert"):
                 return self.local.insert_reduce_plus(keys, vals) if reduce_plus else self.local.insert(keys, vals)
@@ -430,7 +492,7 @@ class ShardedTable:
                     except Exception as e:
                         ex = e
                 if ok is None:             # failed: the peers still expect this rank's pairs -- they get a buffer of the right size
-                    ok = self.b.empty(b - a, keys.dtype)
+                    ok = self._like(b - a, keys)
                     ov = self.b.empty(b - a, vals.dtype) if vals is not None else None
                 rcounts = [rc[src][i] for src in range(self.p)]
                 ev = None
@@ -501,7 +563,7 @@ class ShardedTable:
             return 1
         if self.query_pieces > 0:
             return min(int(self.query_pieces), MAX_QUERY_PIECES)
-        n = keys.numel()
+        n = keys.shape[0]
         # measured over RCCL, one rank, self-exchange, 10^7 finds (scripts/dist_query_timing.py): 1.08 / 1.33 / 1.75 ms for 1 / 2 / 4 pieces --
         # ~0.22 ms of host work per extra piece in this layer (the C++ layer: 0.045 ms), more than the exchange of 10^7 keys can hide
         return 4 if n >= (1 << 27) else (2 if n >= (1 << 25) else 1)
@@ -512,7 +574,7 @@ class ShardedTable:
         Every rank chooses the number of pieces of ITS batch; the count exchange always carries MAX_QUERY_PIECES counts per
         destination plus that choice, and all ranks run as many rounds as the rank with the most pieces."""
         self._late_check()
-        n = keys.numel()
+        n = keys.shape[0]
         if self._single():
             with self._span("local_query"):
                 if op == "count":
@@ -537,14 +599,14 @@ class ShardedTable:
                     if planned is not None:
                         plan = planned[0]
                         off = plan.offsets(p, mine)
-                        pk = self.b.empty(n, keys.dtype)
+                        pk = self._like(n, keys)
                     else:
                         pk, _, cnt = self.b.shard(keys, None, p)
                         o = self._offs(cnt)
                         off = [[o[r], o[r] + cnt[r]] for r in range(p)]
             except Exception as e:
                 ex = e
-                pk = self.b.empty(n, keys.dtype)
+                pk = self._like(n, keys)
             sc = [[off[r][i + 1] - off[r][i] if i < mine else 0 for i in range(Q)] + [mine] for r in range(p)]
             rc, worst = self._exchange_counts(sc, ex)                   # rc[src][piece], rc[src][Q] = src's number of pieces
             self._raise_if(ex, worst, "before the count exchange; nothing was exchanged")
@@ -557,7 +619,7 @@ class ShardedTable:
             rkeys = lv = lf = out_v = out_f = None
             try:
                 self._inject(2)
-                rkeys = self.b.empty(rtot, keys.dtype)
+                rkeys = self._like(rtot, keys)
                 if op != "erase":
                     lf = self.b.empty(rtot, torch.uint8)
                     out_f = self.b.empty(n, torch.uint8)

@@ -7,7 +7,7 @@ windows containing any other byte are skipped, canonical = min(k-mer, reverse co
 import numpy as np
 
 from .table import hashmap_robinhood_doubling, torch
-from .wide import _kmers, hashmap_robinhood_doubling_wide, kmers128_from_sequence
+from .wide import _kmers, hashmap_robinhood_doubling_wide, kmers128_from_fastq, kmers128_from_sequence
 
 
 def sequences_from_fastq(buf):
@@ -166,12 +166,25 @@ class ShardedKmerCounter:
     BenchmarkKmerIndex.cpp:787-843: count, find, erase over a sample of the input, then count again.
 
     `sharded` is a kmerhash_amd.dist.ShardedTable (any backend); `kmer_fn(text) -> packed canonical k-mers` is the k-mer
-    generator (default: kh_kmers_from_fastq on this rank's GPU)."""
+    generator (default: kh_kmers_from_fastq on this rank's GPU; kh_kmers128_from_fastq when 32 < k <= 64, which needs a backend
+    of 16-byte keys such as kmerhash_amd.dist.WideGpuBackend).  Raises ValueError up front for k outside 1..64, for a sharded
+    table whose key width does not match k, and for reserve_from_estimate with k > 32 (no HyperLogLog over 16-byte keys)."""
 
     def __init__(self, sharded, k=31, canonical=True, kmer_fn=None, chunks=1, reserve_from_estimate=False, hll=None):
+        if not 1 <= k <= 64:
+            raise ValueError("k must be 1..64, got %d" % k)
+        # 33 <= k <= 64: 16-byte k-mers {w0, w1}, an (n, 2) tensor per batch, over a backend with key_words = 2
+        self.wide = k > 32
+        words = int(getattr(sharded.b, "key_words", 1))
+        if words != (2 if self.wide else 1):
+            raise ValueError("k = %d needs a sharded table of %d-byte keys, this one holds %d-byte keys (backend key_words = %d)"
+                             % (k, 16 if self.wide else 8, 8 * words, words))
+        if self.wide and reserve_from_estimate:
+            raise ValueError("reserve_from_estimate needs k <= 32: the HyperLogLog has no update over 16-byte keys")
         self.st, self.k, self.canonical, self.chunks = sharded, k, canonical, chunks
         dev = getattr(sharded.b, "device", 0)
-        self.kmer_fn = kmer_fn if kmer_fn is not None else (lambda text: kmers_from_fastq(text, k, canonical, dev))
+        default_fn = kmers128_from_fastq if self.wide else kmers_from_fastq
+        self.kmer_fn = kmer_fn if kmer_fn is not None else (lambda text: default_fn(text, k, canonical, dev))
         self.reserve_from_estimate = reserve_from_estimate
         self.hll = hll
         self.total_kmers = 0

@@ -111,6 +111,49 @@ class hashmap_robinhood_doubling_wide(_TableCore):
         return k[o], v[o]
 
 
+class hashmap_robinhood_doubling_wide_stream(hashmap_robinhood_doubling_wide):
+    """hashmap_robinhood_doubling_wide plus the streamed insert (kh_wide_insert_begin_ex / feed / end / abort): ONE insert whose
+    (n, 2) key pieces arrive one by one -- what the multi-GPU layer feeds as its exchanges land.  The result equals insert() /
+    insert_reduce_plus() of the pieces concatenated in feed order.  Device pieces must stay alive and unchanged until insert_end()
+    or insert_abort() has returned (the object keeps a reference to each)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._fed = []          # device pieces of the streamed insert in progress
+
+    def insert_begin(self, n_total, reduce_plus=False, repeatable=False):
+        """repeatable is accepted for the interface of the 64-bit table; a wide table never raises KhRetry"""
+        flags = (K.KH_INS_REDUCE_PLUS if reduce_plus else 0) | (K.KH_INS_REPEATABLE if repeatable else 0)
+        self._chk(self._L.kh_wide_insert_begin_ex(self._h, int(n_total), flags))
+        self._fed = []
+
+    def insert_feed(self, keys, vals=None):
+        """count this piece's partitions now (asynchronous for device tensors); the pieces count as one batch in feed order"""
+        kb = _keys(keys)
+        vb = _Buf(vals, np.uint32, 4) if vals is not None else None
+        if vb is not None and (vb.n != kb.n // 2 or vb.where != kb.where):
+            raise ValueError("keys/vals must have equal length and live in the same memory space")
+        self._sync_stream(kb, vb)
+        self._chk(self._L.kh_wide_insert_feed(self._h, kb.ptr, vb.ptr if vb is not None else None, kb.n // 2, kb.where))
+        if kb.where == K.KH_MEM_DEVICE:
+            self._fed.append((kb.obj, vb.obj if vb is not None else None))
+
+    def insert_end(self):
+        out = C.c_uint64()
+        try:
+            self._chk(self._L.kh_wide_insert_end(self._h, C.byref(out)))
+        finally:
+            self._fed = []
+        return out.value
+
+    def insert_abort(self):
+        """gives up a streamed insert: the pieces fed so far are dropped, the table is unchanged and usable again"""
+        try:
+            self._chk(self._L.kh_wide_insert_abort(self._h))
+        finally:
+            self._fed = []
+
+
 def hash_batch_wide(keys, hash="murmur3avx64", seed=43, device=0):
     """Hash::operator()(Key const*, count, out) for 16-byte keys: (n, 2) keys -> n 64-bit hashes"""
     L = K.lib()
