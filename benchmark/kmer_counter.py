@@ -14,6 +14,8 @@ table (kmerhash_amd.dist.ShardedTable.insert_counts: hash partition, RCCL exchan
 exchange).  Launch model as bench.py: without WORLD_SIZE this process starts the N ranks itself and never touches a GPU.
 -k 33..64: 16-byte k-mers {w0, w1} (kh_kmers128_from_fastq) in the wide table behind kmerhash_amd.dist.WideGpuBackend; --verify then
 predicts 128-bit k-mers, --out writes 16 + 2 bytes per tuple, --hll-reserve is refused (no HyperLogLog over 16-byte keys).
+--histo FILE writes the k-mer spectrum (one pass over every rank's table on its GPU, summed over the ranks), --min-count N drops the
+k-mers seen fewer than N times before --cycle / --out (the abundance filter; one marks pass + re-layout per rank, no exchange).
 Prints ONE JSON line (rank 0).  Informational driver for SURVEY 8f-2 / configs[4]; the contract benchmark is ../bench.py."""
 import argparse
 import json
@@ -49,12 +51,21 @@ def parse(argv):
     ap.add_argument("--out", default="", help="write this rank's (k-mer, count) tuples (BenchmarkKmerCounter.cpp:1022-1211): 8 + 2 bytes each (16 + 2 for -k > 32) like the "
                                                "reference, whose CountType is uint16_t (:184) -- the table's 32-bit counts are truncated to 16 bits in the FILE "
                                                "(= the value the reference's wrapping counter would hold); find / count / --verify use the 32-bit counts")
+    ap.add_argument("--histo", default="", help="rank 0 writes the k-mer spectrum here: 'count<TAB>number of distinct k-mers' per non-zero bin, the last bin "
+                                                 "('>=N') holding every larger count (ShardedKmerCounter.spectrum: kh_value_histogram per rank + one all-reduce)")
+    ap.add_argument("--histo-bins", type=int, default=256, help="bins of --histo (1..16384); the last one is the overflow bin")
+    ap.add_argument("--min-count", type=int, default=0, help="after counting, drop the k-mers that occur fewer than N times (ShardedKmerCounter.drop_below: "
+                                                             "kh_erase_values on every rank's table); applied before --cycle and --out")
     args = ap.parse_args(argv)
     # refused before any process, GPU or process group is set up
     if not 1 <= args.k <= 64:
         ap.error("-k must be 1..64")
     if args.k > 32 and args.hll_reserve:
         ap.error("--hll-reserve needs -k <= 32: the HyperLogLog has no update over 16-byte k-mers")
+    if not 1 <= args.histo_bins <= 16384:
+        ap.error("--histo-bins must be 1..16384")
+    if not 0 <= args.min_count <= 0xFFFFFFFF:
+        ap.error("--min-count must be 0..2^32-1")
     return args
 
 
@@ -117,9 +128,12 @@ def run_rank(args):
     from kmerhash_amd.hll import hyperloglog64
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    if world > 1:
+    grouped = world > 1 or khd.FORCE_COLLECTIVES      # (one rank with the collectives forced: the N > 1 code path over RCCL on one GPU)
+    if grouped:
         import torch.distributed as dist
-        dist.init_process_group("nccl", device_id=dev)
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", str(_free_port()))
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
     chunks = args.chunks if args.chunks > 0 else (4 if world > 1 else 1)
     wide = args.k > 32          # 16-byte k-mers {w0, w1}: the wide table behind WideGpuBackend (parse() has checked -k and --hll-reserve)
 
@@ -201,7 +215,19 @@ def run_rank(args):
         res["insert_kernels_ms"] = {k: round(v[1], 2) for k, v in sorted(be.table.profile().items(), key=lambda kv: -kv[1][1])}
         be.table.profile_reset()
 
+    # ---- the spectrum of the counts as they stand after counting (collective; not part of insert_s)
+    spectrum = None
+    if args.histo or args.verify:
+        t0 = time.perf_counter()
+        spectrum = kc.spectrum(args.histo_bins)
+        res["spectrum_s"] = time.perf_counter() - t0
+        if args.histo and rank == 0:
+            with open(args.histo, "w") as f:
+                for c in np.nonzero(spectrum)[0].tolist():
+                    f.write("%s%d\t%d\n" % (">=" if c == args.histo_bins - 1 else "", c, int(spectrum[c])))
+
     ok = True
+    exp_survivors = None
     if args.verify:
         # counts predicted from the read positions of ALL ranks (cov[p] = reads covering the k-mer at genome position p)
         d = torch.zeros(args.genome + 1, dtype=torch.int64, device=dev)
@@ -216,6 +242,10 @@ def run_rank(args):
         rng = np.random.default_rng(99 + rank)
         pos = rng.integers(0, args.genome - args.k, 100_000)
         cov_at = dcov[torch.from_numpy(pos).to(dev)].cpu().numpy()
+        # the spectrum predicted from the read positions: bincount of the coverage over the covered positions, clipped into the last bin
+        exp_spectrum = torch.bincount(dcov[dcov > 0].clamp(max=args.histo_bins - 1), minlength=args.histo_bins).cpu().numpy().astype(np.uint64)
+        if args.min_count > 0:
+            exp_survivors = int((dcov >= max(args.min_count, 1)).sum().item())
         del d, dcov, one
         if genome is None:
             genome = dgenome.cpu().numpy()
@@ -230,9 +260,22 @@ def run_rank(args):
         tot = torch.tensor([total_local], dtype=torch.int64, device=dev)
         if world > 1:
             dist.all_reduce(tot)
-        ok = bad == 0 and int(tot.item()) == exp_total and size_after == exp_distinct
+        spectrum_ok = bool(np.array_equal(spectrum, exp_spectrum))
+        ok = bad == 0 and int(tot.item()) == exp_total and size_after == exp_distinct and spectrum_ok
         res["verify"] = {"ok": bool(ok), "sample_mismatches": bad, "total_kmers": int(tot.item()), "expected_total": exp_total,
-                         "expected_distinct": exp_distinct}
+                         "expected_distinct": exp_distinct, "spectrum_ok": spectrum_ok}
+
+    if args.min_count > 0:
+        sync()
+        t0 = time.perf_counter()
+        dropped = kc.drop_below(args.min_count)
+        sync()
+        t_drop = time.perf_counter() - t0
+        size_kept = kc.size()
+        res["min_count"] = {"n": args.min_count, "dropped_rank0": int(dropped), "size_after": size_kept, "seconds": t_drop}
+        if exp_survivors is not None:
+            res["min_count"].update(expected_size=exp_survivors, ok=bool(size_kept == exp_survivors))
+            ok = ok and size_kept == exp_survivors
 
     if args.cycle:
         # queries: every s-th k-mer of this rank's first batch (BenchmarkKmerIndex samples the input file the same way)
@@ -244,11 +287,13 @@ def run_rank(args):
         sync()
         t_cyc = time.perf_counter() - t0
         nq = int(qs.shape[0])
-        ok = ok and cyc["count_hits"] == nq and cyc["find_hits"] == nq and cyc["count_hits_after"] == 0
+        # (after --min-count the sample also holds dropped k-mers: every query count() sees must then be found, and none afterwards)
+        hits_ok = cyc["count_hits"] == cyc["find_hits"] and (cyc["count_hits"] == nq or args.min_count > 1)
+        ok = ok and hits_ok and cyc["count_hits_after"] == 0
         # (ops_per_s: the four operations over their own synchronised times; `seconds` is the wall clock of the whole call, which also
         #  holds torch's result reductions -- their first use loads torch kernels, ~0.1 s once per process)
         res["cycle"] = dict(cyc, queries_local=nq, seconds=t_cyc, ops_per_s=4 * nq * world / (sum(cyc["phase_ms"].values()) * 1e-3), size_after=kc.size(),
-                            ok=bool(cyc["count_hits"] == nq and cyc["count_hits_after"] == 0))
+                            ok=bool(hits_ok and cyc["count_hits_after"] == 0))
     if args.out:
         k_, v_ = be.table.to_vector()
         # (k > 32: 16 + 2 bytes per tuple, the k-mer as {w0, w1} -- what KmerCounter.write gives)
@@ -262,7 +307,7 @@ def run_rank(args):
                     "kmers_per_s": total_local * world / t_ins, "ok": bool(ok)})
         print(json.dumps(res), flush=True)
     be.table.close()
-    if world > 1:
+    if grouped:
         dist.destroy_process_group()
     return 0 if ok else 1
 

@@ -174,6 +174,25 @@ kh_status kh_export_slots(kh_table* t, uint64_t* keys_host, uint32_t* vals_host 
 kh_status kh_export_raw_slots(kh_table* t, void* out_host /* capacity x 16 B */);
 kh_status kh_displacement_histogram(kh_table* t, uint64_t out[128]); /* RH only: #slots per probe distance (REPROBE_STAT) */
 
+/* ---- value-range operations: the elements whose 32-bit value v satisfies lo <= v <= hi (unsigned), found by ONE streaming pass over
+ *      the slots instead of a kh_to_vector to the host.  The reference's batched maps take an output predicate over the stored
+ *      (key, value) pair on count / find / erase (robinhood_offset_hashmap_ptr.hpp:1337-1407, 3484-3587;
+ *      distributed_batched_robinhood_map.hpp:1202-1261, 2112-2428); a C ABI cannot take a functor, the closed value range is the
+ *      predicate of k-mer counting (spectrum, abundance filter).  lo > hi is the empty range: nothing is selected or erased, KH_OK.
+ *      Between kh_insert_begin and kh_insert_end all three return KH_ERR_INVALID.  Each synchronises the table's stream. */
+/* out[b] = number of elements with value == b for b < nbins-1, out[nbins-1] = number with value >= nbins-1 (the bins sum to size());
+ *      nbins 1..16384, anything else KH_ERR_INVALID */
+kh_status kh_value_histogram(kh_table* t, uint32_t nbins, uint64_t* out_host /* u64[nbins] */);
+/* the elements in the range, in slot order (the order of kh_to_vector), into host or device buffers as `where` says.  *n_out always
+ *      receives the number of matches; out_keys == NULL: count only (out_vals == NULL: keys only).  More matches than cap_out:
+ *      KH_ERR_INVALID, *n_out set, nothing written.  lo = 0, hi = UINT32_MAX with KH_MEM_DEVICE: to_vector() into device memory. */
+kh_status kh_select_values(kh_table* t, uint32_t lo, uint32_t hi, kh_mem where, uint64_t* out_keys /*[h|d] u64[cap_out] or NULL*/,
+                           uint32_t* out_vals /*[h|d] u32[cap_out] or NULL*/, uint64_t cap_out, uint64_t* n_out);
+/* erases every element in the range: the table afterwards equals the table after kh_erase of exactly those keys (size, capacity,
+ *      info array, contents, and kh_erase's tail: RH reserve(size()) only, LP the shrinking rehash when size < min_load).  RH: if
+ *      the re-layout fails the table is unchanged. */
+kh_status kh_erase_values(kh_table* t, uint32_t lo, uint32_t hi, uint64_t* n_erased);
+
 /* ---- batched hashing: Hash::operator()(Key const*, count, out)  murmurhash3_64_avx.hpp:1584-1597, hash_new.hpp:1035-1056 */
 kh_status kh_hash_batch(kh_hash hash, uint64_t seed, const void* keys, uint64_t n, kh_mem where,
                         uint64_t* out /*[h|d]*/, int device, void* hip_stream);
@@ -285,6 +304,11 @@ kh_status kh_wide_erase(kh_wtable* t, const void* keys, uint64_t n, kh_mem where
 kh_status kh_wide_to_vector(kh_wtable* t, uint64_t* keys_host /* u64[2 size] */, uint32_t* vals_host, uint64_t* n_out);
 kh_status kh_wide_export_info(kh_wtable* t, uint8_t* out_host /* capacity bytes */);
 kh_status kh_wide_displacement_histogram(kh_wtable* t, uint64_t out[128]);
+/* kh_value_histogram / kh_select_values / kh_erase_values of a wide table; selected keys are u64[2 n] */
+kh_status kh_wide_value_histogram(kh_wtable* t, uint32_t nbins, uint64_t* out_host /* u64[nbins] */);
+kh_status kh_wide_select_values(kh_wtable* t, uint32_t lo, uint32_t hi, kh_mem where, uint64_t* out_keys /*[h|d] u64[2 cap_out] or NULL*/,
+                                uint32_t* out_vals /*[h|d] u32[cap_out] or NULL*/, uint64_t cap_out, uint64_t* n_out);
+kh_status kh_wide_erase_values(kh_wtable* t, uint32_t lo, uint32_t hi, uint64_t* n_erased);
 /* ---- streamed insert of a wide table: the contract written above kh_insert_begin, for 16-byte keys.  The result equals ONE
  *      kh_wide_insert (KH_INS_REDUCE_PLUS: kh_wide_insert_reduce_plus, vals may then be NULL) of the pieces concatenated in feed order:
  *      first value wins between pieces, same capacity rule, same trailing reserve(size()).  A feed of device memory only queues the

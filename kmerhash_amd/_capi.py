@@ -31,6 +31,8 @@ SYMBOLS = [
     "kh_wide_export_info", "kh_wide_displacement_histogram", "kh_wide_hash_batch", "kh_kmers128_from_sequence", "kh_kmers128_from_fastq",
     # wide keys across GPUs: the streamed insert and the stable partition by destination rank
     "kh_wide_insert_begin_ex", "kh_wide_insert_feed", "kh_wide_insert_end", "kh_wide_insert_abort", "kh_wide_shard_permute",
+    # value-range operations (spectrum, select and erase by value), both key widths
+    "kh_value_histogram", "kh_select_values", "kh_erase_values", "kh_wide_value_histogram", "kh_wide_select_values", "kh_wide_erase_values",
 ]
 
 _lib = None
@@ -155,6 +157,10 @@ def lib():
     L.kh_wide_shard_permute.argtypes = [i32, u64, u32, vp, vp, u64, vp, vp, vp, i32, vp]
     L.kh_kmers128_from_sequence.argtypes = [vp, u64, u32, i32, i32, vp, pu64, i32, vp]
     L.kh_kmers128_from_fastq.argtypes = [vp, u64, u32, i32, i32, vp, pu64, i32, vp]
+    for pre in ("kh_", "kh_wide_"):
+        getattr(L, pre + "value_histogram").argtypes = [vp, u32, vp]
+        getattr(L, pre + "select_values").argtypes = [vp, u32, u32, i32, vp, vp, u64, pu64]
+        getattr(L, pre + "erase_values").argtypes = [vp, u32, u32, pu64]
     for s in SYMBOLS:
         if s not in ("kh_version", "kh_last_error", "kh_wide_last_error"):
             getattr(L, s).restype = i32

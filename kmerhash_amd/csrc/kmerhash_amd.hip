@@ -10,8 +10,10 @@
 //   erase   : RH partitions the erase keys by chunk and drops them inside a one-launch re-layout (fall-back: mark hits, re-lay
 //             out without them); LP writes tombstones in place.
 //   find/count : sector probing with in-launch compaction (k_find).
+//   by value : spectrum, selection and erase over a closed value range, one streaming pass over the slots each (kh_kernels_values.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
+#include "kh_kernels_values.h"
 #include "../../include/kmerhash_amd.h"
 
 #include <string>
@@ -1961,6 +1963,124 @@ kh_status kh_displacement_histogram(kh_table* t, uint64_t out[128]) {
 }
 
 }  // extern "C"
+
+// ===================================================================================================
+// value-range operations: the predicate lo <= value <= hi over the stored elements (the output predicate the reference's batched maps
+// take on count / find / erase, robinhood_offset_hashmap_ptr.hpp:1337-1407, fixed to a closed range on the value so that it crosses a
+// C ABI).  One code path for the three tables: the kernels are instantiated per slot layout.
+// ===================================================================================================
+namespace {
+#define KV_SWITCH_LAYOUT(t, ...)                                                       \
+  if (is_wide(t)) { constexpr int LAY = KV_WIDE; __VA_ARGS__; }                        \
+  else if ((t)->kind == KHK_RH) { constexpr int LAY = KV_RH; __VA_ARGS__; }            \
+  else { constexpr int LAY = KV_LP; __VA_ARGS__; }
+
+inline int cu_count(const kh_table* t) {
+  int ncu = 256;
+  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, t->device);
+  return ncu > 0 ? ncu : 256;
+}
+}  // namespace
+extern "C" {
+kh_status kh_value_histogram(kh_table* t, uint32_t nbins, uint64_t* out_host) {
+  if (!t) return KH_ERR_INVALID;
+  if (t->ins.active) return refuse_streaming(t);
+  if (nbins < 1 || nbins > KV_MAX_BINS) return fail(t, KH_ERR_INVALID, "kh_value_histogram: nbins must be 1..16384");
+  if (!out_host) return fail(t, KH_ERR_INVALID, "null output");
+  HIPCHK(hipSetDevice(t->device));
+  memset(out_host, 0, sizeof(uint64_t) * nbins);
+  if (t->lsize == 0) { HIPCHK(hipStreamSynchronize(t->stream)); return KH_OK; }
+  { kh_status ps = arena_prepare(t, size_t(nbins) * 8 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  unsigned long long* d;
+  TAKE(d, unsigned long long, nbins);
+  HIPCHK(hipMemsetAsync(d, 0, size_t(nbins) * 8, t->stream));
+  const uint64_t cap = t->cur.cap;
+  // eight waves per SIMD while the counters leave room for four workgroups per CU; every workgroup flushes its non-zero bins once
+  const uint32_t grid = grid_for(cap, KV_HIST_THREADS * KV_HIST_ITEMS, (uint32_t)cu_count(t) * 4);
+  { Launch L(t, "k_value_hist");
+    KV_SWITCH_LAYOUT(t, hipLaunchKernelGGL((k_value_hist<LAY>), dim3(grid), dim3(KV_HIST_THREADS), size_t(nbins) * 4, t->stream, (const void*)t->cur.p, cap, nbins, d)); }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out_host, d, size_t(nbins) * 8, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  return KH_OK;
+}
+
+kh_status kh_select_values(kh_table* t, uint32_t lo, uint32_t hi, kh_mem where, uint64_t* out_keys, uint32_t* out_vals, uint64_t cap_out,
+                           uint64_t* n_out) {
+  if (n_out) *n_out = 0;
+  if (!t) return KH_ERR_INVALID;
+  if (t->ins.active) return refuse_streaming(t);
+  HIPCHK(hipSetDevice(t->device));
+  if (lo > hi || t->lsize == 0) { HIPCHK(hipStreamSynchronize(t->stream)); return KH_OK; }
+  const uint64_t cap = t->cur.cap, kw = t->slot_bytes / sizeof(KhSlot);      // words per key
+  const uint64_t ntl = (cap + KV_SEL_TILE - 1) / KV_SEL_TILE;
+  { kh_status ps = arena_prepare(t, ntl * 12 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  uint32_t* sums; uint64_t* offs;
+  TAKE(sums, uint32_t, ntl); TAKE(offs, uint64_t, ntl + 1);
+  { Launch L(t, "k_values_tile_count");
+    KV_SWITCH_LAYOUT(t, hipLaunchKernelGGL((k_values_tile_count<LAY>), dim3((uint32_t)ntl), dim3(KV_SEL_THREADS), 0, t->stream, (const void*)t->cur.p, cap, lo, hi, sums)); }
+  { Launch L(t, "k_scan");
+    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, (const uint32_t*)sums, ntl, offs); }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(t->hpin, offs + ntl, 8, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  const uint64_t m = t->hpin[0];
+  if (n_out) *n_out = m;
+  if (!out_keys || m == 0) return KH_OK;
+  if (m > cap_out) return fail(t, KH_ERR_INVALID, "kh_select_values: more matches than cap_out (n_out holds their number)");
+  const bool host = where == KH_MEM_HOST;
+  uint64_t* ck = out_keys; uint32_t* cv = out_vals;
+  if (host) { TAKE(ck, uint64_t, kw * m); if (out_vals) TAKE(cv, uint32_t, m); }
+  { Launch L(t, "k_values_tile_emit");
+    KV_SWITCH_LAYOUT(t, hipLaunchKernelGGL((k_values_tile_emit<LAY>), dim3((uint32_t)ntl), dim3(KV_SEL_THREADS), 0, t->stream, (const void*)t->cur.p, cap, lo, hi,
+                                           (const uint64_t*)offs, ck, cv)); }
+  HIPCHK(hipGetLastError());
+  if (host) return copy_compacted(t, m, ck, cv, out_keys, out_vals);
+  HIPCHK(hipStreamSynchronize(t->stream));
+  return KH_OK;
+}
+
+kh_status kh_erase_values(kh_table* t, uint32_t lo, uint32_t hi, uint64_t* n_erased) {
+  if (n_erased) *n_erased = 0;
+  if (!t) return KH_ERR_INVALID;
+  if (t->ins.active) return refuse_streaming(t);
+  HIPCHK(hipSetDevice(t->device));
+  uint64_t ne = 0;
+  if (lo <= hi && t->lsize > 0) {
+    const uint64_t cap = t->cur.cap;
+    { kh_status ps = arena_prepare(t, ws_rebuild(cap) + (cap > KH_L ? (cap >> KH_LB) : 1) * 96 + (size_t(2) << 20)); if (ps != KH_OK) return ps; }
+    unsigned long long* cnt;
+    TAKE(cnt, unsigned long long, 1);
+    HIPCHK(hipMemsetAsync(cnt, 0, 8, t->stream));
+    { Launch L(t, "k_values_mark");
+      KV_SWITCH_LAYOUT(t, hipLaunchKernelGGL((k_values_mark<LAY>), dim3(grid_for(cap, KV_MARK_THREADS * KV_MARK_ITEMS, (uint32_t)cu_count(t) * 8)), dim3(KV_MARK_THREADS), 0,
+                                             t->stream, t->cur.p, cap, lo, hi, cnt)); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(t->hpin, cnt, 8, hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    ne = t->hpin[0];
+    if (ne && t->kind == KHK_RH) {      // (LP: the tombstones are the erase)
+      const kh_status st = rebuild(t, cap, nullptr, nullptr, nullptr, nullptr, 0, true, t->lsize - ne);
+      if (st != KH_OK) {        // the table keeps its elements: take the marks back
+        if (is_wide(t)) hipLaunchKernelGGL(kw_clear_marks, dim3(grid_for(cap, 256)), dim3(256), 0, t->stream, wide(t->cur));
+        else hipLaunchKernelGGL(k_clear_marks, dim3(grid_for(cap, 256)), dim3(256), 0, t->stream, narrow(t->cur));
+        hipStreamSynchronize(t->stream);
+        return st;
+      }
+    }
+    t->lsize -= ne;
+    if (n_erased) *n_erased = ne;
+  }
+  // the tail of erase(Iter,Iter), as kh_erase / kh_wide_erase apply it (also to a batch that erased nothing)
+  kh_status st = KH_OK;
+  if (t->lsize < t->min_load) {
+    if (t->kind == KHK_RH) st = do_reserve(t, t->lsize);   // hashmap_robinhood.hpp:1437: reserve() only grows
+    else st = do_rehash(t, static_cast<uint64_t>(static_cast<float>(t->lsize) / t->max_lf));   // hashmap_linearprobe.hpp:1048
+  }
+  if (st == KH_OK) HIPCHK(hipStreamSynchronize(t->stream));
+  return st;
+}
+}  // extern "C"
 namespace {
 inline bool xform_ok(kh_key_transform xf, uint32_t k) { return xf == KH_XF_IDENTITY || (xf == KH_XF_DNA_LEX_LESS && k >= 1 && k <= 32); }
 inline KhSeed make_seed(uint64_t seed, kh_key_transform xf, uint32_t k) { return KhSeed{seed, xf == KH_XF_DNA_LEX_LESS ? k : 0u}; }
@@ -2638,6 +2758,11 @@ kh_status kh_wide_rehash(kh_wtable* t, uint64_t b) { return kh_rehash(t, b); }
 kh_status kh_wide_to_vector(kh_wtable* t, uint64_t* keys_host, uint32_t* vals_host, uint64_t* n_out) { return kh_to_vector(t, keys_host, vals_host, n_out); }
 kh_status kh_wide_export_info(kh_wtable* t, uint8_t* out_host) { return kh_export_info(t, out_host); }
 kh_status kh_wide_displacement_histogram(kh_wtable* t, uint64_t out[128]) { return kh_displacement_histogram(t, out); }
+kh_status kh_wide_value_histogram(kh_wtable* t, uint32_t nbins, uint64_t* out_host) { return kh_value_histogram(t, nbins, out_host); }
+kh_status kh_wide_select_values(kh_wtable* t, uint32_t lo, uint32_t hi, kh_mem where, uint64_t* out_keys, uint32_t* out_vals, uint64_t cap_out, uint64_t* n_out) {
+  return kh_select_values(t, lo, hi, where, out_keys, out_vals, cap_out, n_out);
+}
+kh_status kh_wide_erase_values(kh_wtable* t, uint32_t lo, uint32_t hi, uint64_t* n_erased) { return kh_erase_values(t, lo, hi, n_erased); }
 kh_status kh_wide_insert(kh_wtable* t, const void* keys, const void* vals, uint64_t n, kh_mem where, uint64_t* n_inserted) {
   if (!t) return KH_ERR_INVALID;
   if (n && !vals) return fail(t, KH_ERR_INVALID, "null values");

@@ -785,3 +785,20 @@ class ShardedTable:
 
     def local_size(self):
         return self.local.size()
+
+    def value_histogram(self, nbins=256):
+        """histogram of the values over ALL ranks (collective): every rank takes the histogram of its local table (one pass on its
+        GPU) and the ranks are summed with one all-reduce -- over RCCL under nccl, on the host under gloo.  -> numpy uint64[nbins]"""
+        self._late_check()
+        h = np.asarray(self.local.value_histogram(nbins), dtype=np.uint64)
+        if self._single():
+            return h
+        t = torch.from_numpy(h.view(np.int64).copy()).to(self._ctl_device())
+        dist.all_reduce(t, group=self.group)
+        return t.cpu().numpy().view(np.uint64).copy()
+
+    def erase_values(self, lo, hi):
+        """erases the elements with lo <= value <= hi from this rank's local table: an element lives on its owner rank alone, so
+        there is nothing to exchange.  Returns the number erased on this rank."""
+        self._late_check()
+        return self.local.erase_values(lo, hi)

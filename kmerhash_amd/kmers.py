@@ -73,8 +73,22 @@ class KmerCounter:
             self.table.insert_reduce_plus(km)
         return len(km)
 
-    def counts(self):
-        return self.table.to_vector()
+    def counts(self, min_count=0):
+        """(k-mers, counts) in slot order; min_count > 0: only the k-mers that occur at least that often (selected on the GPU)"""
+        if min_count <= 0:
+            return self.table.to_vector()
+        return self.table.select_values(min(int(min_count), 0xFFFFFFFF), 0xFFFFFFFF)
+
+    def spectrum(self, nbins=256):
+        """the k-mer spectrum: uint64[nbins], entry c = number of distinct k-mers that occur c times, the last entry those that
+        occur nbins - 1 times or more (entry 0 stays 0: a stored k-mer occurs at least once)"""
+        return self.table.value_histogram(nbins)
+
+    def drop_below(self, min_count):
+        """abundance filter: erases the k-mers that occur fewer than min_count times (sequencing errors); returns their number"""
+        if min_count <= 0:
+            return 0
+        return self.table.erase_values(0, min(int(min_count), 1 << 32) - 1)
 
     def write(self, filename, count_dtype=np.uint16):
         """raw (k-mer, count) tuples, sizeof(KmerType) + sizeof(CountType) bytes each, no padding
@@ -231,6 +245,17 @@ class ShardedKmerCounter:
 
     def size(self):
         return self.st.size()
+
+    def spectrum(self, nbins=256):
+        """the k-mer spectrum over all ranks (collective: every rank calls it and receives the same uint64[nbins])"""
+        return self.st.value_histogram(nbins)
+
+    def drop_below(self, min_count):
+        """abundance filter on this rank's local table (no exchange: a k-mer's count lives on its owner rank alone); returns the
+        number of k-mers this rank erased"""
+        if min_count <= 0:
+            return 0
+        return self.st.erase_values(0, min(int(min_count), 1 << 32) - 1)
 
 
 def read_positions(n_reads, read_len, genome_len, read_seed):

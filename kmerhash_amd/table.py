@@ -174,6 +174,62 @@ class _TableCore:
         self._chk(self._fn("export_info")(self._h, out.ctypes.data))
         return out
 
+    # -- value-range operations: the elements with lo <= value <= hi (unsigned 32-bit), one pass over the slots on the GPU ---------
+    @staticmethod
+    def _value_range(lo, hi):
+        lo, hi = int(lo), int(hi)
+        if not (0 <= lo <= 0xFFFFFFFF and 0 <= hi <= 0xFFFFFFFF):
+            raise ValueError("value range bounds must be unsigned 32-bit integers, got [%d, %d]" % (lo, hi))
+        return lo, hi
+
+    def value_histogram(self, nbins=256):
+        """uint64[nbins]: out[b] = number of elements with value b, the last bin those with value >= nbins - 1 (nbins 1..16384).
+        On a k-mer counter this is the k-mer spectrum."""
+        nbins = int(nbins)
+        out = np.zeros(min(max(nbins, 1), 16384), dtype=np.uint64)
+        self._chk(self._fn("value_histogram")(self._h, nbins if 0 <= nbins <= 0xFFFFFFFF else 0, out.ctypes.data))      # (0: refused by the library)
+        return out
+
+    def count_values(self, lo, hi):
+        """number of elements with lo <= value <= hi (lo > hi: the empty range)"""
+        lo, hi = self._value_range(lo, hi)
+        n = C.c_uint64()
+        self._chk(self._fn("select_values")(self._h, lo, hi, K.KH_MEM_HOST, None, None, 0, C.byref(n)))
+        return n.value
+
+    def select_values(self, lo, hi, device=False):
+        """(keys, vals) of the elements with lo <= value <= hi in slot order (the order of to_vector()): numpy arrays, or CUDA
+        tensors (int64 keys, int32 values: the bit patterns) written on the GPU when device=True.  A table of 16-byte keys returns
+        (m, 2) keys.  select_values(0, 0xFFFFFFFF, device=True) is to_vector() into device memory."""
+        lo, hi = self._value_range(lo, hi)
+        words = 1 if self.PREFIX == "kh_" else 2
+        m = self.size() if (lo, hi) == (0, 0xFFFFFFFF) else self.count_values(lo, hi)
+        shape = m if words == 1 else (m, 2)
+        n = C.c_uint64()
+        if device:
+            if torch is None:
+                raise RuntimeError("select_values(device=True) needs torch")
+            dev = torch.device("cuda", self.device)
+            keys = torch.empty(shape, dtype=torch.int64, device=dev)
+            vals = torch.empty(m, dtype=torch.int32, device=dev)
+            self._fn("set_stream")(self._h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+            kptr, vptr, where = keys.data_ptr() if m else None, vals.data_ptr() if m else None, K.KH_MEM_DEVICE
+        else:
+            keys = np.zeros(shape, dtype=np.uint64)
+            vals = np.zeros(m, dtype=np.uint32)
+            kptr, vptr, where = keys.ctypes.data if m else None, vals.ctypes.data if m else None, K.KH_MEM_HOST
+        self._chk(self._fn("select_values")(self._h, lo, hi, where, kptr, vptr, m, C.byref(n)))
+        assert n.value == m, (n.value, m)
+        return keys, vals
+
+    def erase_values(self, lo, hi):
+        """erases every element with lo <= value <= hi; the table afterwards is the table after erase() of exactly those keys.
+        Returns the number erased."""
+        lo, hi = self._value_range(lo, hi)
+        n = C.c_uint64()
+        self._chk(self._fn("erase_values")(self._h, lo, hi, C.byref(n)))
+        return n.value
+
 
 class _HashMapBase(_TableCore):
     """the 64-bit-key members: every batch argument is u64[n]"""
