@@ -202,6 +202,18 @@ static inline uint64_t hash_u64(int id, uint64_t key, uint64_t seed) {
   }
 }
 
+// 16-byte keys {w0, w1} (w0 first in memory), hashed as 16 bytes: the same functors over a 16-byte POD key.  farm: Hash64WithSeed
+// for len 16 is the HashLen0to16 branch above with Fetch(s) = w0, Fetch(s + len - 8) = w1, mul = k2 + 32.  identity: w0.
+static inline uint64_t hash_key16(int id, const uint64_t* key, uint64_t seed) {
+  switch (id) {
+    case HASH_IDENTITY: return key[0];
+    case HASH_MURMUR3_X86_128_LO64: return murmur3_x86_128_lo64(key, 16, uint32_t(seed));
+    case HASH_MURMUR3_X64_128_H0: return murmur3_x64_128_h0(key, 16, uint32_t(seed));
+    case HASH_FARM64: return farm64_with_seed_len8to16(key, 16, seed);
+    default: throw std::invalid_argument("unknown hash id");
+  }
+}
+
 // math_utils.hpp:64-69: 1 << (64 - lzcnt(x-1)).  x == 0 shifts by 64 (UB in C++); on x86 the shift
 // count is taken mod 64, so the reference returns 1 there; we define that value.
 static inline uint64_t next_power_of_2(uint64_t x) {

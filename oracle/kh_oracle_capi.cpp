@@ -22,6 +22,11 @@ void ora_hash_batch(int hash_id, uint64_t seed, const uint64_t* keys, uint64_t n
   for (uint64_t i = 0; i < n; ++i) out[i] = hash_u64(hash_id, keys[i], seed);
 }
 
+// 16-byte keys: keys = n x {w0, w1}; the homes of the wide-table model (oracle/wide_model.py)
+void ora_hash16_batch(int hash_id, uint64_t seed, const uint64_t* keys, uint64_t n, uint64_t* out) {
+  for (uint64_t i = 0; i < n; ++i) out[i] = hash_key16(hash_id, keys + 2 * i, seed);
+}
+
 // general-length murmur3 (pins the restatement against smhasher for every tail length)
 void ora_murmur3_x86_128(const void* key, int len, uint32_t seed, uint32_t* out4) { murmur3_x86_128(key, len, seed, out4); }
 void ora_murmur3_x64_128(const void* key, int len, uint32_t seed, uint64_t* out2) { murmur3_x64_128(key, len, seed, out2); }

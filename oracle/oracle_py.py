@@ -45,6 +45,7 @@ def lib():
         L.ora_hash_u64.restype = C.c_uint64
         L.ora_hash_u64.argtypes = [C.c_int, C.c_uint64, C.c_uint64]
         L.ora_hash_batch.argtypes = [C.c_int, C.c_uint64, _u64p, C.c_uint64, _u64p]
+        L.ora_hash16_batch.argtypes = [C.c_int, C.c_uint64, _u64p, C.c_uint64, _u64p]
         L.ora_murmur3_x86_128.argtypes = [C.c_void_p, C.c_int, C.c_uint32, _u32p]
         L.ora_murmur3_x64_128.argtypes = [C.c_void_p, C.c_int, C.c_uint32, _u64p]
         L.ora_next_power_of_2.restype = C.c_uint64
@@ -104,6 +105,14 @@ def hash_batch(hash_id, seed, keys):
     keys = _k(keys)
     out = np.empty_like(keys)
     lib().ora_hash_batch(hash_id, seed, _p(keys, _u64p), len(keys), _p(out, _u64p))
+    return out
+
+
+def hash16_batch(hash_id, seed, keys):
+    """(n, 2) 16-byte keys {w0, w1} -> n 64-bit hashes (CPU statement; never the GPU library's)"""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, 2)
+    out = np.empty(len(keys), dtype=np.uint64)
+    lib().ora_hash16_batch(hash_id, seed, _p(keys, _u64p), len(keys), _p(out, _u64p))
     return out
 
 

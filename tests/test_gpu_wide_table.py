@@ -10,6 +10,7 @@ torch = pytest.importorskip("torch")
 
 import kmerhash_amd as kh  # noqa: E402
 from kmerhash_amd import _capi as K  # noqa: E402
+from oracle.wide_model import rh_info_model  # noqa: E402      (the numpy (max,+) model over the homes: part of the wide-table CPU model)
 
 M64 = (1 << 64) - 1
 HASHES = ("murmur3avx64", "murmur", "farm")
@@ -94,23 +95,6 @@ def test_full_key_equality():
     c = w.count(keys)
     assert np.array_equal(c, np.tile(np.array([1, 0, 1, 1], dtype=np.uint8), 1000))
     w.close()
-
-
-def rh_info_model(homes, cap):
-    """canonical Robin Hood info array: elements sorted by home, slot = max(home, previous slot + 1), circular ((max,+) scan run twice
-    around the circle)"""
-    h = np.sort(np.asarray(homes, dtype=np.int64))
-    info = np.zeros(cap, dtype=np.uint8)
-    if len(h) == 0:
-        return info
-    idx = np.arange(len(h), dtype=np.int64)
-    p = idx + np.maximum.accumulate(h - idx)
-    x0 = max(0, int(p[-1]) + 1 - cap)                 # run-over of the last home into the start of the table
-    p = idx + np.maximum(np.maximum.accumulate(h - idx), x0)
-    dist = p - h
-    assert dist.max() < 128
-    info[p % cap] = 0x80 | dist
-    return info
 
 
 def expected_after(seq_ops):
