@@ -13,7 +13,10 @@ predictable from the read positions alone, which is what --verify checks at any 
 table (kmerhash_amd.dist.ShardedTable.insert_counts: hash partition, RCCL exchange, local std::plus insert; one rank: no
 exchange).  Launch model as bench.py: without WORLD_SIZE this process starts the N ranks itself and never touches a GPU.
 -k 33..64: 16-byte k-mers {w0, w1} (kh_kmers128_from_fastq) in the wide table behind kmerhash_amd.dist.WideGpuBackend; --verify then
-predicts 128-bit k-mers, --out writes 16 + 2 bytes per tuple, --hll-reserve is refused (no HyperLogLog over 16-byte keys).
+predicts 128-bit k-mers, --out writes 16 + 2 bytes per tuple, --hll-reserve (which feeds the estimator 8-byte k-mers) is refused.
+--estimate-reserve pre-sizes the table for every -k in 1..64: each batch's TEXT goes through the fused text -> HyperLogLog pass
+(kh_hll_update_from_fastq: no k-mer buffer is read back), the registers are merged over the ranks, and every rank reserves its share
+before it inserts; the JSON line then carries "estimate_reserve": {estimate, distinct, rel_err, capacity}.
 --histo FILE writes the k-mer spectrum (one pass over every rank's table on its GPU, summed over the ranks), --min-count N drops the
 k-mers seen fewer than N times before --cycle / --out (the abundance filter; one marks pass + re-layout per rank, no exchange).
 Prints ONE JSON line (rank 0).  Informational driver for SURVEY 8f-2 / configs[4]; the contract benchmark is ../bench.py."""
@@ -46,6 +49,8 @@ def parse(argv):
     ap.add_argument("--cycle", action="store_true", help="run the count / find / erase / count query cycle after the inserts")
     ap.add_argument("--sample-ratio", type=int, default=100, help="queries = every s-th k-mer of the rank's input (BenchmarkKmerIndex -q sampling)")
     ap.add_argument("--hll-reserve", action="store_true", help="pre-size the table from a HyperLogLog estimate per batch instead of doubling under load")
+    ap.add_argument("--estimate-reserve", action="store_true", help="pre-size the table per batch from a HyperLogLog estimate taken straight from the batch text "
+                                                                   "(fused pass, no k-mer buffer); every -k in 1..64")
     ap.add_argument("--profile", action="store_true", help="per-kernel HIP-event times of the local table (kh_profile_*) in the JSON line")
     ap.add_argument("--verify", action="store_true", help="check size, total count and a sample of 10^5 k-mer counts against the prediction from the read positions")
     ap.add_argument("--out", default="", help="write this rank's (k-mer, count) tuples (BenchmarkKmerCounter.cpp:1022-1211): 8 + 2 bytes each (16 + 2 for -k > 32) like the "
@@ -61,7 +66,7 @@ def parse(argv):
     if not 1 <= args.k <= 64:
         ap.error("-k must be 1..64")
     if args.k > 32 and args.hll_reserve:
-        ap.error("--hll-reserve needs -k <= 32: the HyperLogLog has no update over 16-byte k-mers")
+        ap.error("--hll-reserve needs -k <= 32 (it feeds the HyperLogLog 8-byte k-mers); --estimate-reserve pre-sizes for every -k")
     if not 1 <= args.histo_bins <= 16384:
         ap.error("--histo-bins must be 1..16384")
     if not 0 <= args.min_count <= 0xFFFFFFFF:
@@ -179,8 +184,9 @@ def run_rank(args):
 
     be = khd.WideGpuBackend(local, 128, 0.35, 0.8, args.hash, 43) if wide else khd.GpuBackend(local, "rh", 128, 0.35, 0.8, args.hash, 43)
     st = khd.ShardedTable(be, timing=True)
-    hll = hyperloglog64(12, 0, args.hash, 43, local) if args.hll_reserve else None
-    kc = KM.ShardedKmerCounter(st, args.k, True, chunks=chunks, reserve_from_estimate=args.hll_reserve, hll=hll)
+    reserve = args.hll_reserve or args.estimate_reserve
+    hll = hyperloglog64(12, 0, args.hash, 43, local) if reserve else None
+    kc = KM.ShardedKmerCounter(st, args.k, True, chunks=chunks, reserve_from_estimate=reserve, hll=hll, estimate_from_text=args.estimate_reserve)
 
     def sync():
         torch.cuda.synchronize()
@@ -210,6 +216,12 @@ def run_rank(args):
     size_after = kc.size()
     res = {"kmers_local": total_local, "capacity_per_batch_rank0": caps, "distinct_global": size_after,
            "insert_s": t_ins, "phases_ms_rank0": {k: round(v, 3) for k, v in st.timings().items()}, "batch_sizing": batch_note}
+    if args.estimate_reserve:
+        # the estimate every rank reserved its share of before the last batch (registers merged over the ranks: collective, not timed)
+        from kmerhash_amd.hll import estimate_global
+        est = estimate_global(hll, st.group)
+        res["estimate_reserve"] = {"estimate": est, "distinct": size_after, "rel_err": abs(est - size_after) / max(size_after, 1),
+                                   "capacity": int(be.table.capacity())}
     if args.profile:
         res["batch_ms"] = t_batch
         res["insert_kernels_ms"] = {k: round(v[1], 2) for k, v in sorted(be.table.profile().items(), key=lambda kv: -kv[1][1])}

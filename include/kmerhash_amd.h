@@ -341,6 +341,28 @@ kh_status kh_kmers128_from_sequence(const void* seq, uint64_t n, uint32_t k /*1.
 kh_status kh_kmers128_from_fastq(const void* text, uint64_t n, uint32_t k /*1..64*/, int canonical, kh_mem where,
                                  uint64_t* out_kmers /*[h|d] u64[2n]*/, uint64_t* n_out, int device, void* hip_stream);
 
+/* ---- HyperLogLog for every k-mer length: updates from 16-byte keys and straight from text (the reference sizes its counting table from
+ *      such an estimate before it inserts, robinhood_offset_hashmap_ptr.hpp:2484-2535; BenchmarkKmerCounter.cpp:1508-1590 estimates per
+ *      file batch, before any k-mer buffer exists).  Registers live in hash-value space: one estimator may be fed by any mix of these
+ *      calls, kh_hll_update and kh_hll_update_via_hashval.  Whether 8-byte and 16-byte keys belong in ONE estimate is the caller's
+ *      business: the same k-mer hashes differently at the two widths.
+ *      kh_hll_update_wide: the registers afterwards equal those after kh_hll_update_via_hashval of kh_wide_hash_batch(keys) with the
+ *      estimator's hash and seed.  Device keys must be 16-byte aligned (one 16-byte load per key): KH_ERR_INVALID otherwise.
+ *      kh_hll_update_from_sequence / _from_fastq: ONE pass text -> windows -> canonical form -> hash -> registers, 1 byte read per base
+ *      and no k-mer written.  The registers afterwards equal those after kh_hll_update of kh_kmers_from_sequence / _from_fastq (k <= 32:
+ *      the 8-byte k-mer is hashed) or kh_hll_update_wide of kh_kmers128_from_sequence / _from_fastq (k > 32: the 16-byte k-mer {w0, w1}),
+ *      for the same text, k and canonical flag; *n_kmers receives the number of valid windows, the n_out of those front ends.  Text at
+ *      any byte alignment; FASTQ text as for kh_kmers_from_fastq (whole 4-line records).
+ *      All three: work is issued on the estimator's stream (kh_hll_set_stream).  n_kmers == NULL and device input: the call queues its
+ *      work and returns without synchronising (the text must stay valid until that work has run); n_kmers != NULL, or host input: it
+ *      synchronises.  KH_ERR_INVALID: a NULL handle, k outside 1..64, a NULL input with n > 0.  n == 0 (and a text shorter than k):
+ *      KH_OK, registers unchanged, *n_kmers = 0. */
+kh_status kh_hll_update_wide(kh_hll* h, const void* keys /*[h|d] u64[2n]*/, uint64_t n, kh_mem where);
+kh_status kh_hll_update_from_sequence(kh_hll* h, const void* seq /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/,
+                                      int canonical, kh_mem where, uint64_t* n_kmers /* may be NULL */);
+kh_status kh_hll_update_from_fastq(kh_hll* h, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/,
+                                   int canonical, kh_mem where, uint64_t* n_kmers /* may be NULL */);
+
 /* ---- measurement hooks: per-kernel HIP-event timing on the table's stream (bench.py roofline) */
 kh_status kh_profile_enable(kh_table* t, int on);
 kh_status kh_profile_reset(kh_table* t);

@@ -33,6 +33,8 @@ SYMBOLS = [
     "kh_wide_insert_begin_ex", "kh_wide_insert_feed", "kh_wide_insert_end", "kh_wide_insert_abort", "kh_wide_shard_permute",
     # value-range operations (spectrum, select and erase by value), both key widths
     "kh_value_histogram", "kh_select_values", "kh_erase_values", "kh_wide_value_histogram", "kh_wide_select_values", "kh_wide_erase_values",
+    # HyperLogLog over 16-byte keys and straight from text (k = 1..64)
+    "kh_hll_update_wide", "kh_hll_update_from_sequence", "kh_hll_update_from_fastq",
 ]
 
 _lib = None
@@ -118,6 +120,9 @@ def lib():
     L.kh_hll_set_stream.argtypes = [vp, vp]
     L.kh_hll_update.argtypes = [vp, vp, u64, i32]
     L.kh_hll_update_via_hashval.argtypes = [vp, vp, u64, i32]
+    L.kh_hll_update_wide.argtypes = [vp, vp, u64, i32]
+    L.kh_hll_update_from_sequence.argtypes = [vp, vp, u64, u32, i32, i32, pu64]
+    L.kh_hll_update_from_fastq.argtypes = [vp, vp, u64, u32, i32, i32, pu64]
     L.kh_hll_merge.argtypes = [vp, vp]
     L.kh_hll_clear.argtypes = [vp]
     L.kh_hll_registers.argtypes = [vp, vp]

@@ -807,3 +807,104 @@ __global__ __launch_bounds__(KH_KM_THREADS) void kw_kmers_emit(const uint8_t* __
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------
+// HyperLogLog over 16-byte keys and over text (hyperloglog64.hpp:175-188 internal_update on hash values, as k_hll_update does it:
+// v = hash << ignored_msb; register = top `precision` bits of v; rank = clz((v << precision) | mask) + 1).  Registers live in hash-value
+// space, so an estimator may be fed by k_hll_update and by these kernels alike.
+//   k_hll_update_wide: keys u64[2n], one 16-byte load per key, hash = kh_hash128 (what kw_hash_batch computes).
+//   k_hll_from_text:   text -> tile (kh_km_pack_tile / kw_km_pack_tile) -> the 16 windows of the lane's word -> validity -> forward k-mer
+//                      -> canonical form -> hash -> register.  Reads 1 B per base and writes nothing but the 2^precision registers: the
+//                      k-mers (8 or 16 B per window) never reach HBM.  Workgroups are persistent: the host launches
+//                      min(tiles, KH_HLL_TEXT_WGS_PER_CU x CUs) of them, each loops grid-stride over the 4096-position tiles, keeps its
+//                      registers in LDS over ALL its tiles and merges them into the global registers once at the end (a merge per tile
+//                      would cost up to one global atomic per window).  LDS per workgroup: 4 x 2^precision B of registers (16 KB at the
+//                      default precision 12, 32 KB at 13) + 1.6 KB of tile words, so four 256-lane workgroups fit a CU (4 waves per
+//                      SIMD, <= 128 VGPRs) at every precision that uses LDS; above 13 the registers are updated in global memory.  No
+//                      workgroup waits for another: a grid that is not fully resident is merely slower.
+// ---------------------------------------------------------------------------------------------
+#define KH_HLL_TEXT_WGS_PER_CU 4
+struct KhHllRegs { uint32_t* regs; uint32_t precision, ignored; int use_lds; };
+__device__ __forceinline__ void kh_hll_put(const KhHllRegs& R, uint32_t* lds, uint64_t lzc_mask, uint64_t hv) {
+  const uint64_t v = hv << R.ignored;
+  const uint32_t r = (uint32_t)(v >> (64 - R.precision));
+  const uint32_t rank = (uint32_t)__clzll((long long)((v << R.precision) | lzc_mask)) + 1u;
+  if (R.use_lds) atomicMax(&lds[r], rank); else atomicMax(&R.regs[r], rank);
+}
+__device__ __forceinline__ void kh_hll_lds_clear(const KhHllRegs& R, uint32_t* lds) {      // (the caller's next barrier publishes the zeros)
+  if (R.use_lds) for (uint32_t i = threadIdx.x; i < (1u << R.precision); i += blockDim.x) lds[i] = 0;
+}
+__device__ __forceinline__ void kh_hll_lds_flush(const KhHllRegs& R, const uint32_t* lds) {
+  if (!R.use_lds) return;
+  __syncthreads();
+  for (uint32_t j = threadIdx.x; j < (1u << R.precision); j += blockDim.x) { const uint32_t v = lds[j]; if (v) atomicMax(&R.regs[j], v); }
+}
+template <int HASH>
+__global__ __launch_bounds__(256) void k_hll_update_wide(const uint64_t* __restrict__ keys, uint64_t n, uint64_t seed, KhHllRegs R) {
+  extern __shared__ __align__(16) uint32_t kh_dyn_smem[];
+  kh_hll_lds_clear(R, kh_dyn_smem);
+  __syncthreads();
+  const uint64_t lzc_mask = ~0ull >> (64 - R.precision - R.ignored);
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint4 k = reinterpret_cast<const uint4*>(keys)[i];
+    kh_hll_put(R, kh_dyn_smem, lzc_mask, kw_hash<HASH>((uint64_t)k.x | ((uint64_t)k.y << 32), (uint64_t)k.z | ((uint64_t)k.w << 32), seed));
+  }
+  kh_hll_lds_flush(R, kh_dyn_smem);
+}
+// KW = 1: k = 1..32, hashes the 8-byte k-mer (kh_hash64, what k_hll_update does with k_kmers_emit's output); KW = 2: k = 33..64, hashes
+// the 16-byte k-mer {w0, w1} (kh_hash128 of kw_kmers_emit's output).  n_windows (may be null): += the number of valid windows.
+template <int HASH, int KW, bool CANON>
+__global__ __launch_bounds__(KH_KM_THREADS, 4) void k_hll_from_text(const uint8_t* __restrict__ seq, uint64_t n, uint32_t k, uint64_t seed, KhHllRegs R,
+                                                                    unsigned long long* __restrict__ n_windows) {
+  extern __shared__ __align__(16) uint32_t kh_dyn_smem[];
+  __shared__ uint32_t words[KH_KM_TILE / 16 + KW_KM_HALO];
+  __shared__ uint16_t invs[KH_KM_TILE / 16 + KW_KM_HALO];
+  __shared__ uint32_t wsum[KH_KM_THREADS / 64];
+  kh_hll_lds_clear(R, kh_dyn_smem);
+  const uint64_t lzc_mask = ~0ull >> (64 - R.precision - R.ignored);
+  const uint64_t ntiles = (n + KH_KM_TILE - 1) / KH_KM_TILE;
+  uint32_t cnt = 0;
+  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    __syncthreads();      // the previous tile's words have been read (first tile: the LDS registers are zero)
+    if (KW == 2) kw_km_pack_tile(seq, n, tile * KH_KM_TILE, words, invs); else kh_km_pack_tile(seq, n, tile * KH_KM_TILE, words, invs);
+    __syncthreads();
+    if (KW == 2) {
+      const KwKmerWin W = kw_km_window(words, invs, threadIdx.x);
+      uint32_t vmask = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < 16; ++j) vmask |= kw_km_valid(W, j, k) ? (1u << j) : 0u;
+      cnt += (uint32_t)__popc(vmask);
+      for (uint32_t j = 0; j < 16; ++j) {
+        if ((vmask >> j) & 1u) {
+          uint64_t w0, w1;
+          kw_km_forward(W, j, k, &w0, &w1);
+          if (CANON) kh_xf128(&w0, &w1, k);
+          kh_hll_put(R, kh_dyn_smem, lzc_mask, kh_hash128<HASH>(w0, w1, seed));
+        }
+      }
+    } else {
+      const KhKmerWin W = kh_km_window(words, invs, threadIdx.x);
+      uint32_t vmask = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < 16; ++j) vmask |= kh_km_valid(W, j, k) ? (1u << j) : 0u;
+      cnt += (uint32_t)__popc(vmask);
+      for (uint32_t j = 0; j < 16; ++j) {
+        if ((vmask >> j) & 1u) {
+          const uint64_t fw = kh_km_forward(W, j, k);
+          kh_hll_put(R, kh_dyn_smem, lzc_mask, kh_hash64<HASH>(CANON ? kh_xf(fw, k) : fw, seed));
+        }
+      }
+    }
+  }
+  kh_hll_lds_flush(R, kh_dyn_smem);
+  if (n_windows) {      // valid windows: summed per wave, one 64-bit atomic per workgroup
+    cnt = kh_wave_sum(cnt);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long tot = 0;
+      for (uint32_t w = 0; w < KH_KM_THREADS / 64; ++w) tot += wsum[w];
+      if (tot) atomicAdd(n_windows, tot);
+    }
+  }
+}

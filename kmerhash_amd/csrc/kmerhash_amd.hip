@@ -2275,6 +2275,14 @@ void kh_shard_plan_destroy(kh_shard_plan* P) {
 // ---- k-mer generation front end ----------------------------------------------------------------------
 }  // extern "C"
 namespace {
+// FASTQ text -> the same bytes with everything that is not on a sequence line replaced by '\n' (line number = newlines before the byte;
+// sequence lines are 1 mod 4).  sums: u32[tiles of KH_CMP_TILE], offs: u64[tiles + 1], msk: u8[n]; queued on `stream`.
+void fastq_mask_text(const uint8_t* text, uint64_t n, uint32_t* sums, uint64_t* offs, uint8_t* msk, hipStream_t stream) {
+  const uint64_t ntl = (n + KH_CMP_TILE - 1) / KH_CMP_TILE;
+  hipLaunchKernelGGL(k_newline_tile_sums, dim3((uint32_t)ntl), dim3(256), 0, stream, text, n, sums);
+  hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, sums, ntl, offs);
+  hipLaunchKernelGGL(k_fastq_mask, dim3((uint32_t)ntl), dim3(256), 0, stream, text, n, (const uint64_t*)offs, msk);
+}
 // shared body of kh_kmers[128]_from_sequence / kh_kmers[128]_from_fastq; kw: 64-bit words per k-mer (1: k <= 32, 2: k <= 64)
 kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq,
                      uint64_t* out_kmers, uint64_t* n_out, int device, void* stream_) {
@@ -2305,12 +2313,7 @@ kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int c
   hipError_t e = hipSuccess;
   if (where == KH_MEM_HOST) e = hipMemcpyAsync(const_cast<uint8_t*>(dseq), seq, n, hipMemcpyHostToDevice, stream);
   if (e == hipSuccess) {
-    if (fastq) {      // keep the sequence lines only (line number = newlines before the byte; sequence lines are 1 mod 4)
-      hipLaunchKernelGGL(k_newline_tile_sums, dim3((uint32_t)ntl), dim3(256), 0, stream, dseq, n, sums);
-      hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, sums, ntl, offs);
-      hipLaunchKernelGGL(k_fastq_mask, dim3((uint32_t)ntl), dim3(256), 0, stream, dseq, n, offs, msk);
-      dseq = msk;
-    }
+    if (fastq) { fastq_mask_text(dseq, n, sums, offs, msk, stream); dseq = msk; }
     // two passes over the text: valid windows per tile, scan, then the windows themselves, compacted and in order
     if (kw == 2) hipLaunchKernelGGL(kw_kmers_count, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
     else hipLaunchKernelGGL(k_kmers_count, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
@@ -2348,6 +2351,9 @@ kh_status kh_kmers_from_fastq(const void* text, uint64_t n, uint32_t k, int cano
 }  // extern "C"
 struct kh_hll {
   int device, hash; uint64_t seed; uint32_t precision, ignored; uint32_t* regs; hipStream_t stream;
+  // workspace of the text passes (window counter, FASTQ line sums / offsets, masked text): owned by the estimator so that a call on device
+  // memory can return without synchronising; reused by the next call in stream order (ws_stream: the stream its last user was queued on)
+  char* ws; size_t ws_cap; hipStream_t ws_stream; int ncu;
 };
 extern "C" {
 kh_status kh_hll_create(kh_hll** out, uint32_t precision, uint32_t ignore_msb, kh_hash hash, uint64_t seed, int device) {
@@ -2369,29 +2375,34 @@ kh_status kh_hll_destroy(kh_hll* h) {
   if (!h) return KH_OK;
   hipSetDevice(h->device);
   hipStreamSynchronize(h->stream);
+  if (h->ws) { hipStreamSynchronize(h->ws_stream); pool_free(h->device, h->ws); }
   pool_free(h->device, h->regs);
   delete h;
   return KH_OK;
 }
 kh_status kh_hll_set_stream(kh_hll* h, void* s) { if (!h) return KH_ERR_INVALID; h->stream = static_cast<hipStream_t>(s); return KH_OK; }
-static kh_status hll_update(kh_hll* h, const void* in, uint64_t n, kh_mem where, bool from_keys) {
+// kw: 64-bit words per key (2: 16-byte keys, from_keys only)
+static kh_status hll_update(kh_hll* h, const void* in, uint64_t n, kh_mem where, bool from_keys, uint32_t kw = 1) {
   kh_table* t = nullptr;
   if (!h) return KH_ERR_INVALID;
   if (n == 0) return KH_OK;
   if (!in) return KH_ERR_INVALID;
+  if (kw == 2 && where == KH_MEM_DEVICE && (reinterpret_cast<uintptr_t>(in) & 15u) != 0) return KH_ERR_INVALID;      // one 16-byte load per key
   HIPCHK(hipSetDevice(h->device));
   const uint64_t* d = static_cast<const uint64_t*>(in);
   uint64_t* tmp = nullptr;
   if (where == KH_MEM_HOST) {
-    HIPCHK(pool_alloc(h->device, n * 8, reinterpret_cast<void**>(&tmp)));
-    hipError_t e = hipMemcpyAsync(tmp, in, n * 8, hipMemcpyHostToDevice, h->stream);
+    HIPCHK(pool_alloc(h->device, n * 8 * kw, reinterpret_cast<void**>(&tmp)));
+    hipError_t e = hipMemcpyAsync(tmp, in, n * 8 * kw, hipMemcpyHostToDevice, h->stream);
     if (e != hipSuccess) { pool_free(h->device, tmp); return KH_ERR_HIP; }
     d = tmp;
   }
   const int use_lds = h->precision <= 13 ? 1 : 0;
   const size_t smem = use_lds ? (sizeof(uint32_t) << h->precision) : 0;
   const uint32_t grid = grid_for(n, 256, 1024);
-  if (from_keys) {
+  if (kw == 2) {
+    KH_SWITCH_HASH(h->hash, hipLaunchKernelGGL((k_hll_update_wide<HASH>), dim3(grid), dim3(256), smem, h->stream, d, n, h->seed, KhHllRegs{h->regs, h->precision, h->ignored, use_lds}));
+  } else if (from_keys) {
     KH_SWITCH_HASH(h->hash, hipLaunchKernelGGL((k_hll_update<HASH, true>), dim3(grid), dim3(256), smem, h->stream, d, n, KhSeed{h->seed, 0u}, h->precision, h->ignored, h->regs, use_lds));
   } else {
     hipLaunchKernelGGL((k_hll_update<KHH_IDENTITY, false>), dim3(grid), dim3(256), smem, h->stream, d, n, KhSeed{h->seed, 0u}, h->precision, h->ignored, h->regs, use_lds);
@@ -2402,6 +2413,75 @@ static kh_status hll_update(kh_hll* h, const void* in, uint64_t n, kh_mem where,
 }
 kh_status kh_hll_update(kh_hll* h, const void* keys, uint64_t n, kh_mem where) { return hll_update(h, keys, n, where, true); }
 kh_status kh_hll_update_via_hashval(kh_hll* h, const void* hashes, uint64_t n, kh_mem where) { return hll_update(h, hashes, n, where, false); }
+kh_status kh_hll_update_wide(kh_hll* h, const void* keys, uint64_t n, kh_mem where) { return hll_update(h, keys, n, where, true, 2); }
+
+// the fused text pass: text [-> k_fastq_mask] -> k_hll_from_text.  Grid: min(tiles of KH_KM_TILE positions, KH_HLL_TEXT_WGS_PER_CU x CUs).
+static kh_status hll_from_text(kh_hll* h, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq, uint64_t* n_kmers) {
+  kh_table* t = nullptr;
+  if (n_kmers) *n_kmers = 0;
+  if (!h || k < 1 || k > 64) return KH_ERR_INVALID;
+  if (n < k) return KH_OK;      // (n == 0 included) no window: the registers stay as they are
+  if (!text) return KH_ERR_INVALID;
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->ncu) {
+    int ncu = 0;
+    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
+    h->ncu = ncu > 0 ? ncu : 1;
+  }
+  // workspace: [window counter, 256 B] [text copy (host input)] [masked text (FASTQ)] [line sums] [line offsets]
+  const uint64_t ntl = (n + KH_CMP_TILE - 1) / KH_CMP_TILE, nkt = (n + KH_KM_TILE - 1) / KH_KM_TILE;
+  const size_t sz_txt = (n + 255) & ~size_t(255);
+  const size_t sz_seq = where == KH_MEM_HOST ? sz_txt : 0, sz_msk = fastq ? sz_txt : 0;
+  const size_t sz_sum = fastq ? ((ntl * 4 + 255) & ~size_t(255)) : 0, sz_off = fastq ? (((ntl + 1) * 8 + 255) & ~size_t(255)) : 0;
+  const size_t need = 256 + sz_seq + sz_msk + sz_sum + sz_off;
+  if (h->ws && h->ws_stream != h->stream) HIPCHK(hipStreamSynchronize(h->ws_stream));      // its last user ran on another stream
+  if (h->ws_cap < need) {
+    if (h->ws) { HIPCHK(hipStreamSynchronize(h->ws_stream)); pool_free(h->device, h->ws); h->ws = nullptr; h->ws_cap = 0; }
+    HIPCHK(pool_alloc(h->device, need, reinterpret_cast<void**>(&h->ws)));
+    h->ws_cap = need;
+  }
+  h->ws_stream = h->stream;
+  char* p = h->ws;
+  unsigned long long* counter = reinterpret_cast<unsigned long long*>(p); p += 256;
+  const uint8_t* dseq = static_cast<const uint8_t*>(text);
+  if (where == KH_MEM_HOST) {
+    HIPCHK(hipMemcpyAsync(p, text, n, hipMemcpyHostToDevice, h->stream));
+    dseq = reinterpret_cast<const uint8_t*>(p); p += sz_seq;
+  }
+  if (fastq) {
+    uint8_t* msk = reinterpret_cast<uint8_t*>(p); p += sz_msk;
+    uint32_t* sums = reinterpret_cast<uint32_t*>(p); p += sz_sum;
+    uint64_t* offs = reinterpret_cast<uint64_t*>(p);
+    fastq_mask_text(dseq, n, sums, offs, msk, h->stream);
+    dseq = msk;
+  }
+  if (n_kmers) HIPCHK(hipMemsetAsync(counter, 0, 8, h->stream)); else counter = nullptr;
+  const int use_lds = h->precision <= 13 ? 1 : 0;
+  const size_t smem = use_lds ? (sizeof(uint32_t) << h->precision) : 0;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(nkt, (uint64_t)KH_HLL_TEXT_WGS_PER_CU * (uint64_t)h->ncu);
+  const KhHllRegs R{h->regs, h->precision, h->ignored, use_lds};
+#define KH_HLL_TEXT_LAUNCH(KW, CANON) \
+  KH_SWITCH_HASH(h->hash, hipLaunchKernelGGL((k_hll_from_text<HASH, KW, CANON>), dim3(grid), dim3(KH_KM_THREADS), smem, h->stream, dseq, n, k, h->seed, R, counter))
+  if (k > 32) { if (canonical) { KH_HLL_TEXT_LAUNCH(2, true); } else { KH_HLL_TEXT_LAUNCH(2, false); } }
+  else { if (canonical) { KH_HLL_TEXT_LAUNCH(1, true); } else { KH_HLL_TEXT_LAUNCH(1, false); } }
+#undef KH_HLL_TEXT_LAUNCH
+  HIPCHK(hipGetLastError());
+  if (n_kmers) {
+    unsigned long long total = 0;
+    HIPCHK(hipMemcpyAsync(&total, counter, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *n_kmers = total;
+  } else if (where == KH_MEM_HOST) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  return KH_OK;
+}
+kh_status kh_hll_update_from_sequence(kh_hll* h, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, uint64_t* n_kmers) {
+  return hll_from_text(h, seq, n, k, canonical, where, false, n_kmers);
+}
+kh_status kh_hll_update_from_fastq(kh_hll* h, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, uint64_t* n_kmers) {
+  return hll_from_text(h, text, n, k, canonical, where, true, n_kmers);
+}
 kh_status kh_hll_merge(kh_hll* h, const kh_hll* other) {
   kh_table* t = nullptr;
   if (!h || !other || h->precision != other->precision || h->device != other->device) return KH_ERR_INVALID;

@@ -76,6 +76,42 @@ class hyperloglog64:
         self._stream(b)
         self._chk(self._L.kh_hll_update_via_hashval(self._h, b.ptr, b.n, b.where), "kh_hll_update_via_hashval")
 
+    def update_wide(self, keys):
+        """16-byte keys: (n, 2) numpy uint64 array or CUDA int64 tensor ({w0, w1} per key; a device tensor must be 16-byte aligned).
+        The registers afterwards equal update_via_hashval(hash_batch_wide(keys)) with the estimator's hash and seed."""
+        from .wide import _keys
+        b = _keys(keys)
+        self._stream(b)
+        self._chk(self._L.kh_hll_update_wide(self._h, b.ptr, b.n // 2, b.where), "kh_hll_update_wide")
+
+    def _from_text(self, fn, text, k, canonical):
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(text, dtype=np.uint8)
+        b = _Buf(text, np.uint8, 1)
+        self._stream(b)
+        n = C.c_uint64()
+        self._chk(getattr(self._L, fn)(self._h, b.ptr, b.n, k, 1 if canonical else 0, b.where, C.byref(n)), fn)
+        return n.value
+
+    def update_from_sequence(self, seq, k, canonical=True):
+        """one pass text -> k-mers -> hash -> registers, no k-mer written (k = 1..64; bytes / uint8 array on the host or a uint8 CUDA
+        tensor at any byte alignment).  The registers afterwards equal update(kmers_from_sequence(seq, k, canonical)) for k <= 32 and
+        update_wide(kmers128_from_sequence(seq, k, canonical)) for k > 32.  Returns the number of valid windows."""
+        return self._from_text("kh_hll_update_from_sequence", seq, k, canonical)
+
+    def update_from_fastq(self, text, k, canonical=True):
+        """update_from_sequence over raw FASTQ text (whole 4-line records): only the sequence lines yield k-mers"""
+        return self._from_text("kh_hll_update_from_fastq", text, k, canonical)
+
+    def text_grid(self, n):
+        """the number of persistent workgroups the text passes launch for a text of n bytes: one per tile of TEXT_TILE start positions,
+        at most TEXT_WGS_PER_CU per compute unit; workgroup g handles tiles g, g + grid, g + 2 grid, ..."""
+        cus = torch.cuda.get_device_properties(self.device).multi_processor_count
+        return max(1, min((int(n) + self.TEXT_TILE - 1) // self.TEXT_TILE, self.TEXT_WGS_PER_CU * cus))
+
+    TEXT_TILE = 4096          # KH_KM_TILE
+    TEXT_WGS_PER_CU = 4       # KH_HLL_TEXT_WGS_PER_CU
+
     def merge(self, other):
         self._chk(self._L.kh_hll_merge(self._h, other._h), "kh_hll_merge")
 

@@ -48,12 +48,35 @@ def kmers_from_sequence(seq, k=31, canonical=True, device=0, _fastq=False):
 class KmerCounter:
     """counting index: k-mer -> number of occurrences (Reducer = std::plus, value 1 per occurrence)"""
 
-    def __init__(self, k=31, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0):
+    def __init__(self, k=31, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0, reserve_from_estimate=False):
+        """reserve_from_estimate: size the table before every insert from a HyperLogLog estimate of the distinct k-mers seen so far
+        (the reference's counting table does, robinhood_offset_hashmap_ptr.hpp:2484-2535): the batch text first goes through the fused
+        text -> registers pass (no k-mer buffer), the estimator accumulates over the batches.  Every k in 1..64."""
         self.k, self.canonical, self.device = k, canonical, device
         # 33 <= k <= 64: 16-byte k-mers in the wide table (k-mer = {w0, w1}, see kmerhash_amd.wide)
         self.wide = 32 < k <= 64
         cls = hashmap_robinhood_doubling_wide if self.wide else hashmap_robinhood_doubling
         self.table = cls(128, min_load_factor, max_load_factor, hash=hash, seed=43, device=device)
+        self.reserve_from_estimate = reserve_from_estimate
+        self._hash, self.hll = hash, None
+
+    def _presize(self, text, fastq):
+        if self.hll is None:      # the table's hash, seed 43, precision 12 (the reference's hyperloglog64<Key, Hash, 12>)
+            from .hll import hyperloglog64
+            self.hll = hyperloglog64(12, 0, self._hash, 43, self.device)
+        (self.hll.update_from_fastq if fastq else self.hll.update_from_sequence)(text, self.k, self.canonical)
+        est = self.hll.estimate()
+        self.table.reserve(int(est * (1.0 + self.hll.est_error_rate)))
+        return est
+
+    def presize_sequences(self, seq):
+        """the estimate and reserve steps of add_sequences alone: feeds the counter's estimator with the k-mers of `seq` (fused pass)
+        and reserves the table for the estimated number of distinct k-mers (+ the estimator's standard error); returns the estimate"""
+        return self._presize(seq, False)
+
+    def presize_fastq(self, text):
+        """presize_sequences over raw FASTQ text"""
+        return self._presize(text, True)
 
     def _kmers(self, seq, fastq):
         if self.wide:
@@ -61,6 +84,8 @@ class KmerCounter:
         return kmers_from_sequence(seq, self.k, self.canonical, self.device, _fastq=fastq)
 
     def add_sequences(self, seq):
+        if self.reserve_from_estimate:
+            self._presize(seq, False)
         km = self._kmers(seq, False)
         if len(km):
             self.table.insert_reduce_plus(km)
@@ -68,6 +93,8 @@ class KmerCounter:
 
     def add_fastq(self, buf):
         """raw FASTQ text (whole records), host or device: record structure, k-mer generation and counting all run on the GPU"""
+        if self.reserve_from_estimate:
+            self._presize(buf, True)
         km = self._kmers(buf, True)
         if len(km):
             self.table.insert_reduce_plus(km)
@@ -104,6 +131,8 @@ class KmerCounter:
 
     def close(self):
         self.table.close()
+        if self.hll is not None:
+            self.hll.close()
 
 
 def synthetic_fastq(n_reads, read_len=150, genome_len=1_000_000, seed=7, n_rate=0.001):
@@ -181,10 +210,16 @@ class ShardedKmerCounter:
 
     `sharded` is a kmerhash_amd.dist.ShardedTable (any backend); `kmer_fn(text) -> packed canonical k-mers` is the k-mer
     generator (default: kh_kmers_from_fastq on this rank's GPU; kh_kmers128_from_fastq when 32 < k <= 64, which needs a backend
-    of 16-byte keys such as kmerhash_amd.dist.WideGpuBackend).  Raises ValueError up front for k outside 1..64, for a sharded
-    table whose key width does not match k, and for reserve_from_estimate with k > 32 (no HyperLogLog over 16-byte keys)."""
+    of 16-byte keys such as kmerhash_amd.dist.WideGpuBackend).  `hll`: the estimator of reserve_from_estimate (anything with
+    update / update_wide, registers(), precision and est_error_rate; update_wide takes the (n, 2) k-mers of k > 32).
+    estimate_from_text: the estimator is fed from the batch TEXT by the fused pass (hll.update_from_fastq(text, k, canonical): no
+    k-mer is read back) instead of from the generated k-mers; the all-reduce(max) of the registers and the per-rank share are the same.
+    Raises ValueError up front for k outside 1..64, for a sharded table whose key width does not match k, for
+    reserve_from_estimate with k > 32 and no hll (the HyperLogLog must then be one with update_wide), and for estimate_from_text
+    without reserve_from_estimate and an hll that has update_from_fastq."""
 
-    def __init__(self, sharded, k=31, canonical=True, kmer_fn=None, chunks=1, reserve_from_estimate=False, hll=None):
+    def __init__(self, sharded, k=31, canonical=True, kmer_fn=None, chunks=1, reserve_from_estimate=False, hll=None,
+                 estimate_from_text=False):
         if not 1 <= k <= 64:
             raise ValueError("k must be 1..64, got %d" % k)
         # 33 <= k <= 64: 16-byte k-mers {w0, w1}, an (n, 2) tensor per batch, over a backend with key_words = 2
@@ -193,8 +228,11 @@ class ShardedKmerCounter:
         if words != (2 if self.wide else 1):
             raise ValueError("k = %d needs a sharded table of %d-byte keys, this one holds %d-byte keys (backend key_words = %d)"
                              % (k, 16 if self.wide else 8, 8 * words, words))
-        if self.wide and reserve_from_estimate:
-            raise ValueError("reserve_from_estimate needs k <= 32: the HyperLogLog has no update over 16-byte keys")
+        if self.wide and reserve_from_estimate and (hll is None or not hasattr(hll, "update_wide")):
+            raise ValueError("reserve_from_estimate with k > 32 needs hll=: a HyperLogLog with update_wide (16-byte keys)")
+        if estimate_from_text and not (reserve_from_estimate and hasattr(hll, "update_from_fastq")):
+            raise ValueError("estimate_from_text needs reserve_from_estimate and hll=: a HyperLogLog with update_from_fastq")
+        self.estimate_from_text = estimate_from_text
         self.st, self.k, self.canonical, self.chunks = sharded, k, canonical, chunks
         dev = getattr(sharded.b, "device", 0)
         default_fn = kmers128_from_fastq if self.wide else kmers_from_fastq
@@ -213,8 +251,11 @@ class ShardedKmerCounter:
             # registers are merged over all ranks (all-reduce(max): hyperloglog64.hpp:477-484 merge_distributed / estimate_global) and
             # every rank reserves its share of the global estimate (estimate_average_per_rank :487-489).  Collective: all ranks, every batch.
             from .hll import estimate_average_per_rank
-            if len(km):
-                self.hll.update(km)
+            if self.estimate_from_text:
+                if len(text):
+                    self.hll.update_from_fastq(text, self.k, self.canonical)
+            elif len(km):
+                (self.hll.update_wide if self.wide else self.hll.update)(km)
             est = estimate_average_per_rank(self.hll, self.st.group)
             self.st.local.reserve(int(est * (1.0 + self.hll.est_error_rate)))
         self.st.insert_counts(km, chunks=self.chunks)
