@@ -102,13 +102,38 @@ __device__ __forceinline__ uint64_t kh_find_pos(const KhSlot* __restrict__ slots
 }
 
 // ---------------------------------------------------------------------------------------------
+// A key of KW 64-bit words as the key-width-generic front end (batched hashing, sharding, HyperLogLog) sees it: the register type,
+// the seed its hash takes (only 8-byte keys have a key transform), one load / one store per key (16-byte keys: one dwordx4 access,
+// so their arrays must be 16-byte aligned -- the host entry points check), and the keys a lane of the shard kernels owns.
+// ---------------------------------------------------------------------------------------------
+template <int KW> struct KhKey;
+template <> struct KhKey<1> {
+  typedef uint64_t key_t;
+  typedef KhSeed seed_t;
+  static constexpr int SHARD_ITEMS = 8;
+  static __device__ __forceinline__ key_t load(const uint64_t* keys, uint64_t i) { return keys[i]; }
+  static __device__ __forceinline__ void store(uint64_t* out, uint64_t pos, key_t k) { out[pos] = k; }
+  template <int HASH> static __device__ __forceinline__ uint64_t hash(key_t k, seed_t seed) { return kh_hash64<HASH>(k, seed); }
+};
+template <> struct KhKey<2> {
+  typedef uint4 key_t;
+  typedef uint64_t seed_t;
+  static constexpr int SHARD_ITEMS = 4;
+  static __device__ __forceinline__ key_t load(const uint64_t* keys, uint64_t i) { return reinterpret_cast<const uint4*>(keys)[i]; }
+  static __device__ __forceinline__ void store(uint64_t* out, uint64_t pos, key_t k) { reinterpret_cast<uint4*>(out)[pos] = k; }
+  template <int HASH> static __device__ __forceinline__ uint64_t hash(key_t k, seed_t seed) {
+    return kh_hash128<HASH>((uint64_t)k.x | ((uint64_t)k.y << 32), (uint64_t)k.z | ((uint64_t)k.w << 32), seed);
+  }
+};
+
+// ---------------------------------------------------------------------------------------------
 // batched hashing  (Hash::operator()(Key const*, count, out))
 // ---------------------------------------------------------------------------------------------
-template <int HASH>
-__global__ void k_hash_batch(const uint64_t* __restrict__ keys, uint64_t n, KhSeed seed, uint64_t* __restrict__ out) {
+template <int HASH, int KW>
+__global__ void k_hash_batch(const uint64_t* __restrict__ keys, uint64_t n, typename KhKey<KW>::seed_t seed, uint64_t* __restrict__ out) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) out[i] = kh_hash64<HASH>(keys[i], seed);
+  for (; i < n; i += stride) out[i] = KhKey<KW>::template hash<HASH>(KhKey<KW>::load(keys, i), seed);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3305,7 +3330,11 @@ __global__ void k_unpack_slots(const KhSlot* __restrict__ slots, uint64_t cap, u
 // (distributed_batched_robinhood_map.hpp:513-534 key_to_rank, :632-741 assign_count_permute)
 // ---------------------------------------------------------------------------------------------
 #define KH_SHARD_THREADS 512
-#define KH_SHARD_TILE (KH_SHARD_THREADS * 8)     // 8 consecutive items per lane; fewer, larger tiles keep the [rank][tile] offset scan short
+// A tile is 512 x KhKey<KW>::SHARD_ITEMS keys (consecutive items per lane; fewer, larger tiles keep the [rank][tile] offset scan short).
+//   8-byte keys: 8 per lane, 4096 keys: 4096 x (8 + 4) B + counters = 48.1 KB of LDS in k_shard_scatter8.
+//   16-byte keys: 4 per lane, 2048 keys: 2048 x (16 + 4) B + counters = 41.1 KB, THREE 512-lane workgroups per CU (6 waves per SIMD; four
+//   would need 164.5 KB of the 160 KB) -- a 4096-key tile would take 80 KB here and leave one workgroup per CU.
+#define KH_SHARD_TILE(KW) (KH_SHARD_THREADS * KhKey<KW>::SHARD_ITEMS)
 #define KH_SHARD_MAXR 64
 struct KhShardAdj { long long a[8]; __host__ __device__ KhShardAdj() { for (int i = 0; i < 8; ++i) a[i] = 0; } };
 // entries (r, i) -> tile_off[r * ntiles + ntiles * i / pieces] for r <= p... (the offsets at the piece boundaries of a kh_shard_plan)
@@ -3315,35 +3344,36 @@ __global__ void k_shard_piece_bounds(const uint64_t* __restrict__ tile_off, uint
   const uint32_t r = j / (pieces + 1), i = j % (pieces + 1);
   out[j] = tile_off[(uint64_t)r * ntiles + (uint64_t)ntiles * i / pieces];
 }
-template <int HASH>
-__device__ __forceinline__ uint32_t kh_rank_of(uint64_t key, KhSeed seed, uint32_t p, uint32_t pmask) {
-  uint64_t h = kh_hash64<HASH>(key, seed);
+template <int HASH, int KW>
+__device__ __forceinline__ uint32_t kh_rank_of(typename KhKey<KW>::key_t key, typename KhKey<KW>::seed_t seed, uint32_t p, uint32_t pmask) {
+  const uint64_t h = KhKey<KW>::template hash<HASH>(key, seed);
   return pmask ? (uint32_t)(h & pmask) : (uint32_t)(h % p);
 }
-template <int HASH>
-__global__ void k_shard_count(const uint64_t* __restrict__ keys, uint64_t n, KhSeed seed, uint32_t p, uint32_t pmask,
-                              uint32_t* __restrict__ tile_counts /* [p][ntiles] */, uint32_t ntiles) {
+template <int HASH, int KW>
+__global__ __launch_bounds__(KH_SHARD_THREADS) void k_shard_count(const uint64_t* __restrict__ keys, uint64_t n, typename KhKey<KW>::seed_t seed, uint32_t p,
+                                                                  uint32_t pmask, uint32_t* __restrict__ tile_counts /* [p][ntiles] */, uint32_t ntiles) {
+  typedef KhKey<KW> K;
   __shared__ uint32_t h[KH_SHARD_MAXR];
   if (threadIdx.x < KH_SHARD_MAXR) h[threadIdx.x] = 0;
   __syncthreads();
-  uint64_t base = (uint64_t)blockIdx.x * KH_SHARD_TILE;
+  const uint64_t base = (uint64_t)blockIdx.x * KH_SHARD_TILE(KW);
+  // all keys of a lane are requested before the first one is hashed (clamped indices: a branch per key makes the compiler wait for
+  // every load in turn)
+  typename K::key_t key[K::SHARD_ITEMS];
+#pragma unroll
+  for (uint32_t k = 0; k < K::SHARD_ITEMS; ++k) {
+    const uint64_t i = base + threadIdx.x + k * KH_SHARD_THREADS;
+    key[k] = K::load(keys, i < n ? i : n - 1);
+  }
   if (p <= 8) {
     // per-lane counts in 16-bit fields of two 64-bit words, reduced over the wave with shuffles: 8 LDS atomics per wave
     // instead of one per key on 8 hot bins
     unsigned long long c0 = 0, c1 = 0;
-    // all eight keys of a lane are requested before the first one is hashed (clamped indices: a branch per key makes the
-    // compiler wait for every load in turn)
-    uint64_t key[KH_SHARD_TILE / KH_SHARD_THREADS];
 #pragma unroll
-    for (uint32_t k = 0; k < KH_SHARD_TILE / KH_SHARD_THREADS; ++k) {
-      const uint64_t i = base + threadIdx.x + k * KH_SHARD_THREADS;
-      key[k] = keys[i < n ? i : n - 1];
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < KH_SHARD_TILE / KH_SHARD_THREADS; ++k) {
+    for (uint32_t k = 0; k < K::SHARD_ITEMS; ++k) {
       const uint64_t i = base + threadIdx.x + k * KH_SHARD_THREADS;
       if (i < n) {
-        const uint32_t r = kh_rank_of<HASH>(key[k], seed, p, pmask);
+        const uint32_t r = kh_rank_of<HASH, KW>(key[k], seed, p, pmask);
         if (r < 4) c0 += 1ull << (16 * r); else c1 += 1ull << (16 * (r - 4));
       }
     }
@@ -3354,36 +3384,40 @@ __global__ void k_shard_count(const uint64_t* __restrict__ keys, uint64_t n, KhS
         if (c) atomicAdd(&h[r], c);
       }
   } else {
-    for (uint32_t j = threadIdx.x; j < KH_SHARD_TILE; j += KH_SHARD_THREADS) {
-      uint64_t i = base + j;
-      if (i < n) atomicAdd(&h[kh_rank_of<HASH>(keys[i], seed, p, pmask)], 1u);
+#pragma unroll
+    for (uint32_t k = 0; k < K::SHARD_ITEMS; ++k) {
+      const uint64_t i = base + threadIdx.x + k * KH_SHARD_THREADS;
+      if (i < n) atomicAdd(&h[kh_rank_of<HASH, KW>(key[k], seed, p, pmask)], 1u);
     }
   }
   __syncthreads();
   if (threadIdx.x < p) tile_counts[(uint64_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
 }
-template <int HASH>
-__global__ void k_shard_scatter(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint64_t n, KhSeed seed,
-                                uint32_t p, uint32_t pmask, const uint64_t* __restrict__ tile_off /* [p][ntiles] exclusive */,
-                                uint32_t ntiles, uint64_t* __restrict__ ok, uint32_t* __restrict__ ov) {
-  // stable: lane t owns items [8t, 8t+8) of the tile; per rank, an exclusive scan over lanes gives the order
+// any p <= KH_SHARD_MAXR, every pair written straight to its place.  Stable: lane t owns SHARD_ITEMS consecutive items of the tile; per
+// rank, an exclusive scan over the lanes gives the order.  (All of a lane's loads first, clamped indices: see k_shard_count.)
+template <int HASH, int KW>
+__global__ __launch_bounds__(KH_SHARD_THREADS) void k_shard_scatter(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint64_t n,
+                                                                    typename KhKey<KW>::seed_t seed, uint32_t p, uint32_t pmask,
+                                                                    const uint64_t* __restrict__ tile_off /* [p][ntiles] exclusive */, uint32_t ntiles,
+                                                                    uint64_t* __restrict__ ok, uint32_t* __restrict__ ov) {
+  typedef KhKey<KW> K;
   __shared__ uint32_t wtot[KH_SHARD_THREADS / 64][KH_SHARD_MAXR];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  uint64_t base = (uint64_t)blockIdx.x * KH_SHARD_TILE + (uint64_t)tid * 8;
-  uint64_t key[8]; uint32_t rk[8];
+  const uint64_t base = (uint64_t)blockIdx.x * KH_SHARD_TILE(KW) + (uint64_t)tid * K::SHARD_ITEMS;
+  typename K::key_t key[K::SHARD_ITEMS]; uint32_t val[K::SHARD_ITEMS], rk[K::SHARD_ITEMS];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    uint64_t i = base + j;
-    key[j] = i < n ? keys[i] : 0;
-    rk[j] = i < n ? kh_rank_of<HASH>(key[j], seed, p, pmask) : 0xFFFFFFFFu;
-  }
+  for (int j = 0; j < K::SHARD_ITEMS; ++j) { const uint64_t i = base + j; key[j] = K::load(keys, i < n ? i : n - 1); }
+#pragma unroll
+  for (int j = 0; j < K::SHARD_ITEMS; ++j) { const uint64_t i = base + j; val[j] = vals ? vals[i < n ? i : n - 1] : 0u; }
+#pragma unroll
+  for (int j = 0; j < K::SHARD_ITEMS; ++j) rk[j] = base + j < n ? kh_rank_of<HASH, KW>(key[j], seed, p, pmask) : 0xFFFFFFFFu;
   for (uint32_t r = 0; r < p; ++r) {
     uint32_t c = 0;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) c += (rk[j] == r) ? 1u : 0u;
+    for (int j = 0; j < K::SHARD_ITEMS; ++j) c += (rk[j] == r) ? 1u : 0u;
     uint32_t incl = c;
     for (int off = 1; off < 64; off <<= 1) {
-      uint32_t o = __shfl_up(incl, off, 64);
+      const uint32_t o = __shfl_up(incl, off, 64);
       if (lane >= (uint32_t)off) incl += o;
     }
     if (lane == 63) wtot[wid][r] = incl;
@@ -3392,10 +3426,10 @@ __global__ void k_shard_scatter(const uint64_t* __restrict__ keys, const uint32_
     for (uint32_t w = 0; w < wid; ++w) wpre += wtot[w][r];
     uint64_t pos = tile_off[(uint64_t)r * ntiles + blockIdx.x] + wpre + incl - c;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < K::SHARD_ITEMS; ++j) {
       if (rk[j] == r) {
-        ok[pos] = key[j];
-        if (vals) ov[pos] = vals[base + j];
+        K::store(ok, pos, key[j]);
+        if (vals) ov[pos] = val[j];
         ++pos;
       }
     }
@@ -3404,42 +3438,42 @@ __global__ void k_shard_scatter(const uint64_t* __restrict__ keys, const uint32_
 
 // p <= 8 ranks (one node): all per-rank prefix sums in one pass -- the 8 per-lane counters (<= 8 each) travel as
 // 16-bit fields of two 64-bit words through a single wave scan -- and the tile is staged in LDS in (rank, input
-// order) so that the write-out is coalesced.  Stable, like the generic kernel.
-template <int HASH>
+// order) so that the write-out is coalesced (one key per lane, consecutive lanes consecutive keys).  Stable, like the generic kernel.
+template <int HASH, int KW>
 __global__ __launch_bounds__(KH_SHARD_THREADS) void k_shard_scatter8(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint64_t n,
-                                                          KhSeed seed, uint32_t p, uint32_t pmask,
-                                                          const uint64_t* __restrict__ tile_off /* [p][ntiles] exclusive */,
-                                                          uint32_t ntiles, uint64_t* __restrict__ ok, uint32_t* __restrict__ ov,
-                                                          uint32_t tile0 = 0, KhShardAdj adj = KhShardAdj()) {
+                                                                     typename KhKey<KW>::seed_t seed, uint32_t p, uint32_t pmask,
+                                                                     const uint64_t* __restrict__ tile_off /* [p][ntiles] exclusive */,
+                                                                     uint32_t ntiles, uint64_t* __restrict__ ok, uint32_t* __restrict__ ov,
+                                                                     uint32_t tile0 = 0, KhShardAdj adj = KhShardAdj()) {
   // (tile0 / adj: the launch covers the tiles [tile0, tile0 + gridDim.x) of a larger batch whose offsets tile_off holds -- one piece
   //  of a kh_shard_plan; keys / vals / n are the piece's own, adj[r] turns the batch-wide offset of rank r into the piece's)
-  __shared__ uint64_t lk[KH_SHARD_TILE];
-  __shared__ uint32_t lv[KH_SHARD_TILE];
+  typedef KhKey<KW> K;
+  __shared__ typename K::key_t lk[KH_SHARD_TILE(KW)];
+  __shared__ uint32_t lv[KH_SHARD_TILE(KW)];
   __shared__ unsigned long long wtot[KH_SHARD_THREADS / 64][2];
   __shared__ uint32_t rank_off[9];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const uint64_t tbase = (uint64_t)blockIdx.x * KH_SHARD_TILE;
-  const uint64_t base = tbase + (uint64_t)tid * 8;
-  const uint32_t tile_len = (n - tbase) < KH_SHARD_TILE ? (uint32_t)(n - tbase) : KH_SHARD_TILE;
-  uint64_t key[8]; uint32_t val[8]; uint32_t rk[8];
+  const uint64_t tbase = (uint64_t)blockIdx.x * KH_SHARD_TILE(KW);
+  const uint64_t base = tbase + (uint64_t)tid * K::SHARD_ITEMS;
+  const uint32_t tile_len = (n - tbase) < KH_SHARD_TILE(KW) ? (uint32_t)(n - tbase) : KH_SHARD_TILE(KW);
+  typename K::key_t key[K::SHARD_ITEMS]; uint32_t val[K::SHARD_ITEMS], rk[K::SHARD_ITEMS];
   unsigned long long c0 = 0, c1 = 0;     // counts of ranks 0-3 / 4-7, 16 bits each
   // (all of a lane's loads first, clamped indices: see k_shard_count)
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { const uint64_t i = base + j; key[j] = keys[i < n ? i : n - 1]; }
+  for (int j = 0; j < K::SHARD_ITEMS; ++j) { const uint64_t i = base + j; key[j] = K::load(keys, i < n ? i : n - 1); }
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { const uint64_t i = base + j; val[j] = vals ? vals[i < n ? i : n - 1] : 0u; }
+  for (int j = 0; j < K::SHARD_ITEMS; ++j) { const uint64_t i = base + j; val[j] = vals ? vals[i < n ? i : n - 1] : 0u; }
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const uint64_t i = base + j;
+  for (int j = 0; j < K::SHARD_ITEMS; ++j) {
     rk[j] = 0xFFu;
-    if (i < n) {
-      rk[j] = kh_rank_of<HASH>(key[j], seed, p, pmask);
+    if (base + j < n) {
+      rk[j] = kh_rank_of<HASH, KW>(key[j], seed, p, pmask);
       if (rk[j] < 4) c0 += 1ull << (16 * rk[j]); else c1 += 1ull << (16 * (rk[j] - 4));
     }
   }
   unsigned long long i0 = c0, i1 = c1;
   for (int off = 1; off < 64; off <<= 1) {
-    unsigned long long o0 = __shfl_up(i0, off, 64), o1 = __shfl_up(i1, off, 64);
+    const unsigned long long o0 = __shfl_up(i0, off, 64), o1 = __shfl_up(i1, off, 64);
     if (lane >= (uint32_t)off) { i0 += o0; i1 += o1; }
   }
   if (lane == 63) { wtot[wid][0] = i0; wtot[wid][1] = i1; }
@@ -3459,7 +3493,7 @@ __global__ __launch_bounds__(KH_SHARD_THREADS) void k_shard_scatter8(const uint6
   }
   __syncthreads();
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
+  for (int j = 0; j < K::SHARD_ITEMS; ++j) {
     if (rk[j] != 0xFFu) {
       const uint32_t r = rk[j];
       const uint32_t within = (uint32_t)(((r < 4 ? e0 : e1) >> (16 * (r & 3))) & 0xFFFFu);
@@ -3474,7 +3508,7 @@ __global__ __launch_bounds__(KH_SHARD_THREADS) void k_shard_scatter8(const uint6
 #pragma unroll
     for (uint32_t k = 1; k < 8; ++k) r += (s >= rank_off[k]) ? 1u : 0u;
     const uint64_t pos = tile_off[(uint64_t)r * ntiles + tile0 + blockIdx.x] + (uint64_t)adj.a[r] + (s - rank_off[r]);
-    ok[pos] = lk[s];
+    K::store(ok, pos, lk[s]);
     if (vals) ov[pos] = lv[s];
   }
 }
@@ -3483,31 +3517,39 @@ __global__ __launch_bounds__(KH_SHARD_THREADS) void k_shard_scatter8(const uint6
 // HyperLogLog register update (reference hyperloglog64.hpp:175-188 internal_update):
 //   v = hash << ignored_msb ; register index = top `precision` bits of v ; rank = clz((v << precision) | mask) + 1
 //   with mask = low (precision + ignored_msb) bits set ; register = max(register, rank).
-// Registers are accumulated per workgroup in LDS (precision <= 13) and merged with global atomicMax.
+// Registers are accumulated per workgroup in LDS (precision <= 13: use_lds) and merged with global atomicMax.  They live in hash-value
+// space, so one estimator may be fed hash values, 8-byte keys, 16-byte keys and text (k_hll_from_text) alike.
 // ---------------------------------------------------------------------------------------------
-template <int HASH, bool FROM_KEYS>
-__global__ void k_hll_update(const uint64_t* __restrict__ in, uint64_t n, KhSeed seed, uint32_t precision, uint32_t ignored,
-                             uint32_t* __restrict__ regs, int use_lds) {
+struct KhHllRegs { uint32_t* regs; uint32_t precision, ignored; int use_lds; };
+__device__ __forceinline__ void kh_hll_put(const KhHllRegs& R, uint32_t* lds, uint64_t lzc_mask, uint64_t hv) {
+  const uint64_t v = hv << R.ignored;
+  const uint32_t r = (uint32_t)(v >> (64 - R.precision));
+  const uint32_t rank = (uint32_t)__clzll((long long)((v << R.precision) | lzc_mask)) + 1u;
+  if (R.use_lds) atomicMax(&lds[r], rank); else atomicMax(&R.regs[r], rank);
+}
+__device__ __forceinline__ void kh_hll_lds_clear(const KhHllRegs& R, uint32_t* lds) {      // (the caller's next barrier publishes the zeros)
+  if (R.use_lds) for (uint32_t i = threadIdx.x; i < (1u << R.precision); i += blockDim.x) lds[i] = 0;
+}
+__device__ __forceinline__ void kh_hll_lds_flush(const KhHllRegs& R, const uint32_t* lds) {
+  if (!R.use_lds) return;
+  __syncthreads();
+  for (uint32_t j = threadIdx.x; j < (1u << R.precision); j += blockDim.x) { const uint32_t v = lds[j]; if (v) atomicMax(&R.regs[j], v); }
+}
+// SRC: what `in` holds -- hash values, or keys of SRC 64-bit words to be hashed (16-byte keys: one 16-byte load per key)
+enum { KH_HLL_HASHVALS = 0, KH_HLL_KEYS = 1, KH_HLL_WIDE_KEYS = 2 };
+template <int HASH, int SRC>
+__global__ __launch_bounds__(256) void k_hll_update(const uint64_t* __restrict__ in, uint64_t n, typename KhKey<SRC ? SRC : 1>::seed_t seed, KhHllRegs R) {
+  typedef KhKey<SRC ? SRC : 1> K;
   extern __shared__ __align__(16) uint32_t kh_dyn_smem[];
-  const uint32_t m = 1u << precision;
-  if (use_lds) {
-    for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) kh_dyn_smem[i] = 0;
-    __syncthreads();
+  kh_hll_lds_clear(R, kh_dyn_smem);
+  __syncthreads();
+  const uint64_t lzc_mask = ~0ull >> (64 - R.precision - R.ignored);
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    uint64_t hv;
+    if constexpr (SRC == KH_HLL_HASHVALS) hv = in[i]; else hv = K::template hash<HASH>(K::load(in, i), seed);
+    kh_hll_put(R, kh_dyn_smem, lzc_mask, hv);
   }
-  const uint64_t lzc_mask = ~0ull >> (64 - precision - ignored);
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    const uint64_t hv = FROM_KEYS ? kh_hash64<HASH>(in[i], seed) : in[i];
-    const uint64_t v = hv << ignored;
-    const uint32_t r = (uint32_t)(v >> (64 - precision));
-    const uint32_t rank = (uint32_t)__clzll((long long)((v << precision) | lzc_mask)) + 1u;
-    if (use_lds) atomicMax(&kh_dyn_smem[r], rank); else atomicMax(&regs[r], rank);
-  }
-  if (use_lds) {
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < m; j += blockDim.x) { const uint32_t v = kh_dyn_smem[j]; if (v) atomicMax(&regs[j], v); }
-  }
+  kh_hll_lds_flush(R, kh_dyn_smem);
 }
 __global__ void k_hll_merge(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, uint32_t m) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3526,17 +3568,16 @@ __device__ __forceinline__ uint32_t kh_dna_code(uint32_t c) {
 }
 // Tile of 4096 start positions per 256-lane workgroup.  A lane packs ITS 16 bases (one 16-byte load, coalesced) into a 32-bit word
 // (2 bits per base, first base in the top bits) plus a 16-bit mask of the bytes that are no base; the words go to LDS.  The 16
-// windows that start in a lane's word are then cut out of three consecutive words with funnel shifts: no byte-wise rolling loop,
-// no strided global access.  (The first version read the text one byte at a time at a stride of 64 bytes between lanes and
+// windows that start in a lane's word are then cut out of three consecutive words (five for k > 32) with funnel shifts: no byte-wise
+// rolling loop, no strided global access.  (The first version read the text one byte at a time at a stride of 64 bytes between lanes and
 // wrote 8-byte k-mers at a stride of 512: 47 GB/s.)  Two passes over the text: count the valid windows per tile, scan, then
 // emit them compacted and in order (staged in LDS, written coalesced) -- the full-size k-mer / flag arrays are gone.
 #define KH_KM_TILE 4096
 #define KH_KM_THREADS 256
-struct KhKmerWin { uint64_t a; uint64_t lo; uint64_t inv; };     // bases 0..31 | bases 32..47 in the top half | 48 invalid bits (base b at bit 47 - b)
+// the tile's KH_KM_TILE / 16 words plus HALO words behind it (the windows that start in the last lanes' words run into them)
+template <uint32_t HALO>
 __device__ __forceinline__ void kh_km_pack_tile(const uint8_t* __restrict__ seq, uint64_t n, uint64_t tile0, uint32_t* words, uint16_t* invs) {
-  const uint32_t tid = threadIdx.x;
-  // lanes 0..255 pack the tile's words, lanes 0..1 also the two halo words behind it
-  for (uint32_t w = tid; w < KH_KM_TILE / 16 + 2; w += KH_KM_THREADS) {
+  for (uint32_t w = threadIdx.x; w < KH_KM_TILE / 16 + HALO; w += KH_KM_THREADS) {
     const uint64_t p0 = tile0 + (uint64_t)w * 16;
     uint8_t b[16];
     if (p0 + 16 <= n && ((reinterpret_cast<uintptr_t>(seq) + p0) & 15u) == 0) {
@@ -3558,53 +3599,100 @@ __device__ __forceinline__ void kh_km_pack_tile(const uint8_t* __restrict__ seq,
     words[w] = word; invs[w] = (uint16_t)inv;
   }
 }
-__device__ __forceinline__ KhKmerWin kh_km_window(const uint32_t* words, const uint16_t* invs, uint32_t t) {
-  KhKmerWin W;
-  W.a = ((uint64_t)words[t] << 32) | words[t + 1];
-  W.lo = (uint64_t)words[t + 2] << 32;
-  W.inv = ((uint64_t)invs[t] << 32) | ((uint64_t)invs[t + 1] << 16) | invs[t + 2];
-  return W;
-}
-// the window that starts at base j (0..15) of the lane's word: valid iff none of its k bytes is a non-base
-__device__ __forceinline__ bool kh_km_valid(const KhKmerWin& W, uint32_t j, uint32_t k) {
-  const uint64_t kmask = k >= 64 ? ~0ull : ((1ull << k) - 1ull);
-  return ((W.inv >> (48u - j - k)) & kmask) == 0;
-}
-__device__ __forceinline__ uint64_t kh_km_forward(const KhKmerWin& W, uint32_t j, uint32_t k) {
-  const uint64_t x = j ? ((W.a << (2 * j)) | (W.lo >> (64 - 2 * j))) : W.a;       // bases j.. left-aligned
-  return x >> (64 - 2 * k);
-}
+// The 16 windows that start in a lane's word, for k-mers of KW 64-bit words (KW = 1: k = 1..32, cut from three consecutive words;
+// KW = 2: k = 33..64 -- any k = 1..64 works -- cut from five): HALO, the lane's window registers Win, window(), valid(W, j, k) -- the window
+// that starts at base j (0..15) of the lane's word is valid iff none of its k bytes is a non-base (bytes behind the text's end were
+// packed as non-bases) --, forward() -- its 2-bit packed k-mer --, and hash_of_window(): forward k-mer -> canonical form -> hash, what
+// k_hash_batch<HASH, KW> makes of the k-mer the emit kernel writes.
+template <int KW> struct KhKm;
+template <> struct KhKm<1> {
+  static constexpr uint32_t HALO = 2;
+  struct Win { uint64_t a; uint64_t lo; uint64_t inv; };     // bases 0..31 | bases 32..47 in the top half | 48 invalid bits (base b at bit 47 - b)
+  static __device__ __forceinline__ Win window(const uint32_t* words, const uint16_t* invs, uint32_t t) {
+    Win W;
+    W.a = ((uint64_t)words[t] << 32) | words[t + 1];
+    W.lo = (uint64_t)words[t + 2] << 32;
+    W.inv = ((uint64_t)invs[t] << 32) | ((uint64_t)invs[t + 1] << 16) | invs[t + 2];
+    return W;
+  }
+  static __device__ __forceinline__ bool valid(const Win& W, uint32_t j, uint32_t k) {
+    const uint64_t kmask = k >= 64 ? ~0ull : ((1ull << k) - 1ull);
+    return ((W.inv >> (48u - j - k)) & kmask) == 0;
+  }
+  static __device__ __forceinline__ uint64_t forward(const Win& W, uint32_t j, uint32_t k) {
+    const uint64_t x = j ? ((W.a << (2 * j)) | (W.lo >> (64 - 2 * j))) : W.a;       // bases j.. left-aligned
+    return x >> (64 - 2 * k);
+  }
+  template <int HASH, bool CANON> static __device__ __forceinline__ uint64_t hash_of_window(const Win& W, uint32_t j, uint32_t k, uint64_t seed) {
+    const uint64_t fw = forward(W, j, k);
+    return kh_hash64<HASH>(CANON ? kh_xf(fw, k) : fw, seed);
+  }
+};
+template <> struct KhKm<2> {
+  static constexpr uint32_t HALO = 4;
+  struct Win { uint64_t a, b, c; uint64_t ia, ib; };   // bases 0..31 | 32..63 | 64..79 (top half); invalid bits of bases 0..63 | 64..79 (top)
+  static __device__ __forceinline__ Win window(const uint32_t* words, const uint16_t* invs, uint32_t t) {
+    Win W;
+    W.a = ((uint64_t)words[t] << 32) | words[t + 1];
+    W.b = ((uint64_t)words[t + 2] << 32) | words[t + 3];
+    W.c = (uint64_t)words[t + 4] << 32;
+    W.ia = ((uint64_t)invs[t] << 48) | ((uint64_t)invs[t + 1] << 32) | ((uint64_t)invs[t + 2] << 16) | invs[t + 3];
+    W.ib = (uint64_t)invs[t + 4] << 48;
+    return W;
+  }
+  static __device__ __forceinline__ bool valid(const Win& W, uint32_t j, uint32_t k) {
+    const uint64_t x = j ? ((W.ia << j) | (W.ib >> (64 - j))) : W.ia;      // invalid bits of bases j..j+63, first base in the top bit
+    return k >= 64 ? x == 0 : (x >> (64 - k)) == 0;
+  }
+  static __device__ __forceinline__ void forward(const Win& W, uint32_t j, uint32_t k, uint64_t* w0, uint64_t* w1) {
+    uint64_t A = W.a, B = W.b;
+    if (j) { A = (W.a << (2 * j)) | (W.b >> (64 - 2 * j)); B = (W.b << (2 * j)) | (W.c >> (64 - 2 * j)); }   // bases j..j+63 left-aligned
+    const uint32_t s = 128u - 2u * k;
+    if (s >= 64u) { *w0 = A >> (s - 64u); *w1 = 0; }
+    else if (s) { *w0 = (B >> s) | (A << (64u - s)); *w1 = A >> s; }
+    else { *w0 = B; *w1 = A; }
+  }
+  template <int HASH, bool CANON> static __device__ __forceinline__ uint64_t hash_of_window(const Win& W, uint32_t j, uint32_t k, uint64_t seed) {
+    uint64_t w0, w1;
+    forward(W, j, k, &w0, &w1);
+    if (CANON) kh_xf128(&w0, &w1, k);
+    return kh_hash128<HASH>(w0, w1, seed);
+  }
+};
+template <int KW>
 __global__ __launch_bounds__(KH_KM_THREADS) void k_kmers_count(const uint8_t* __restrict__ seq, uint64_t n, uint32_t k, uint32_t* __restrict__ sums) {
-  __shared__ uint32_t words[KH_KM_TILE / 16 + 2];
-  __shared__ uint16_t invs[KH_KM_TILE / 16 + 2];
+  typedef KhKm<KW> M;
+  __shared__ uint32_t words[KH_KM_TILE / 16 + M::HALO];
+  __shared__ uint16_t invs[KH_KM_TILE / 16 + M::HALO];
   __shared__ uint32_t wsum[KH_KM_THREADS / 64];
-  const uint64_t tile0 = (uint64_t)blockIdx.x * KH_KM_TILE;
-  kh_km_pack_tile(seq, n, tile0, words, invs);
+  kh_km_pack_tile<M::HALO>(seq, n, (uint64_t)blockIdx.x * KH_KM_TILE, words, invs);
   __syncthreads();
-  const KhKmerWin W = kh_km_window(words, invs, threadIdx.x);
+  const typename M::Win W = M::window(words, invs, threadIdx.x);
   uint32_t c = 0;
 #pragma unroll
-  for (uint32_t j = 0; j < 16; ++j) c += kh_km_valid(W, j, k) ? 1u : 0u;      // (bytes behind the text's end were packed as non-bases)
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+  for (uint32_t j = 0; j < 16; ++j) c += M::valid(W, j, k) ? 1u : 0u;
+  c = kh_wave_sum(c);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) sums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
+// 8-byte k-mers: the tile's windows are staged in LDS and written coalesced (kw_kmers_emit writes its 16-byte k-mers straight out)
 template <bool CANON>
 __global__ __launch_bounds__(KH_KM_THREADS) void k_kmers_emit(const uint8_t* __restrict__ seq, uint64_t n, uint32_t k, const uint64_t* __restrict__ tile_off,
                                                               uint64_t* __restrict__ out) {
-  __shared__ uint32_t words[KH_KM_TILE / 16 + 2];
-  __shared__ uint16_t invs[KH_KM_TILE / 16 + 2];
+  typedef KhKm<1> M;
+  __shared__ uint32_t words[KH_KM_TILE / 16 + M::HALO];
+  __shared__ uint16_t invs[KH_KM_TILE / 16 + M::HALO];
   __shared__ uint32_t wtot[KH_KM_THREADS / 64];
   __shared__ uint64_t stage[KH_KM_TILE];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const uint64_t tile0 = (uint64_t)blockIdx.x * KH_KM_TILE;
-  kh_km_pack_tile(seq, n, tile0, words, invs);
+  kh_km_pack_tile<M::HALO>(seq, n, tile0, words, invs);
   __syncthreads();
-  const KhKmerWin W = kh_km_window(words, invs, tid);
+  const M::Win W = M::window(words, invs, tid);
   uint32_t vmask = 0;
 #pragma unroll
-  for (uint32_t j = 0; j < 16; ++j) vmask |= kh_km_valid(W, j, k) ? (1u << j) : 0u;
+  for (uint32_t j = 0; j < 16; ++j) vmask |= M::valid(W, j, k) ? (1u << j) : 0u;
   const uint32_t mine = (uint32_t)__popc(vmask);
   uint32_t incl = mine;
   for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off, 64); if (lane >= (uint32_t)off) incl += o; }
@@ -3616,7 +3704,7 @@ __global__ __launch_bounds__(KH_KM_THREADS) void k_kmers_emit(const uint8_t* __r
 #pragma unroll
   for (uint32_t j = 0; j < 16; ++j) {
     if ((vmask >> j) & 1u) {
-      const uint64_t fw = kh_km_forward(W, j, k);
+      const uint64_t fw = M::forward(W, j, k);
       uint64_t v = fw;
       if (CANON) { const uint64_t rc = kh_revcomp(fw, k); v = fw < rc ? fw : rc; }
       stage[pos++] = v;

@@ -1,5 +1,7 @@
 // kh_kernels_wide.h -- gfx950 device code of the wide-key (16-byte key) Robin Hood table, included once by kmerhash_amd.hip after
-// kh_kernels.h.  Prefix kw_.
+// kh_kernels.h.  Prefix kw_.  The front end around the table is not here: batched hashing, the shard partition, the HyperLogLog update
+// and the k-mer window count are the key-width-generic kernels of kh_kernels.h instantiated with KW = 2 (KhKey<2>, KhKm<2>); this file
+// adds what differs for 16-byte k-mers (kw_kmers_emit) and the fused text-to-estimate pass over both widths (k_hll_from_text).
 //
 // Key: {u64 w0, u64 w1} (the memory image of a 16-byte POD key, hashed as 16 bytes: kh_hash128 in kh_hash.h).  Slot: 32 bytes
 // {u64 w0, u64 w1, u32 val, u32 info, u64 pad}, 32-byte aligned -- a 64-byte sector holds two slots, a probe reads the 24 live bytes
@@ -63,14 +65,6 @@ __global__ void kw_fill_empty(KwSlots T) {
 __global__ void kw_poison(KwSlots T) {      // test hook: destination buffers start as garbage
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < T.cap; i += (uint64_t)gridDim.x * blockDim.x)
     kw_slot_st(T.s + i, 0xDEADBEEFDEADBEEFull, 0xDEADBEEFDEADBEEFull, 0xDEADBEEFu, 0x000000A5u);
-}
-
-template <int HASH>
-__global__ void kw_hash_batch(const uint64_t* __restrict__ keys, uint64_t n, uint64_t seed, uint64_t* __restrict__ out) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint4 k = reinterpret_cast<const uint4*>(keys)[i];
-    out[i] = kw_hash<HASH>((uint64_t)k.x | ((uint64_t)k.y << 32), (uint64_t)k.z | ((uint64_t)k.w << 32), seed);
-  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -542,255 +536,23 @@ __global__ void kw_disp_hist(const KwSlot* __restrict__ slots, uint64_t cap, uns
 }
 
 // ---------------------------------------------------------------------------------------------
-// multi-GPU sharding of 16-byte keys: stable partition of (key, value) by rank = kh_hash128(key, seed) mod p -- the wide counterparts
-// of k_shard_count / k_shard_scatter / k_shard_scatter8 (same [rank][tile] counts, same k_scan_u32_to_u64, same staging of a tile in
-// LDS in (rank, input order) -- kw_shard_scatter8 only; the generic kw_shard_scatter for p > 8 writes every pair straight to its place).
-// A tile is 2048 keys, four per lane: 2048 x (16 + 4) B + counters = 41.1 KB of LDS in kw_shard_scatter8, THREE 512-lane workgroups per
-// CU (6 waves per SIMD; four would need 164.5 KB of the 160 KB) -- the 4096-key tile of the 64-bit kernel would take 80 KB here and
-// leave one workgroup per CU.  Every key is one 16-byte load (keys and out_keys must be 16-byte aligned: the host entry point
-// checks); all of a lane's loads are issued before the first is hashed (clamped indices).
+// 128-bit k-mers (k = 1..64): the second pass of the k-mer front end (kh_kernels.h: tile layout, KhKm<2> windows, k_kmers_count<2>, scan)
+// for 16-byte k-mers: every lane writes its windows straight to their place, one 16-byte store each (k_kmers_emit stages its tile in LDS).
 // ---------------------------------------------------------------------------------------------
-#define KW_SHARD_THREADS 512
-#define KW_SHARD_ITEMS 4
-#define KW_SHARD_TILE (KW_SHARD_THREADS * KW_SHARD_ITEMS)
-template <int HASH>
-__device__ __forceinline__ uint32_t kw_rank_of(const uint4 k, uint64_t seed, uint32_t p, uint32_t pmask) {
-  const uint64_t h = kw_hash<HASH>((uint64_t)k.x | ((uint64_t)k.y << 32), (uint64_t)k.z | ((uint64_t)k.w << 32), seed);
-  return pmask ? (uint32_t)(h & pmask) : (uint32_t)(h % p);
-}
-template <int HASH>
-__global__ __launch_bounds__(KW_SHARD_THREADS) void kw_shard_count(const uint64_t* __restrict__ keys, uint64_t n, uint64_t seed, uint32_t p, uint32_t pmask,
-                                                                   uint32_t* __restrict__ tile_counts /* [p][ntiles] */, uint32_t ntiles) {
-  __shared__ uint32_t h[KH_SHARD_MAXR];
-  if (threadIdx.x < KH_SHARD_MAXR) h[threadIdx.x] = 0;
-  __syncthreads();
-  const uint64_t base = (uint64_t)blockIdx.x * KW_SHARD_TILE;
-  const uint4* k4 = reinterpret_cast<const uint4*>(keys);
-  uint4 key[KW_SHARD_ITEMS];
-#pragma unroll
-  for (uint32_t k = 0; k < KW_SHARD_ITEMS; ++k) {
-    const uint64_t i = base + threadIdx.x + k * KW_SHARD_THREADS;
-    key[k] = k4[i < n ? i : n - 1];
-  }
-  if (p <= 8) {
-    // per-lane counts in 16-bit fields of two 64-bit words, reduced over the wave with shuffles (k_shard_count)
-    unsigned long long c0 = 0, c1 = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < KW_SHARD_ITEMS; ++k) {
-      const uint64_t i = base + threadIdx.x + k * KW_SHARD_THREADS;
-      if (i < n) {
-        const uint32_t r = kw_rank_of<HASH>(key[k], seed, p, pmask);
-        if (r < 4) c0 += 1ull << (16 * r); else c1 += 1ull << (16 * (r - 4));
-      }
-    }
-    for (int off = 32; off > 0; off >>= 1) { c0 += __shfl_down(c0, off, 64); c1 += __shfl_down(c1, off, 64); }
-    if ((threadIdx.x & 63) == 0)
-      for (uint32_t r = 0; r < p; ++r) {
-        const uint32_t c = (uint32_t)(((r < 4 ? c0 : c1) >> (16 * (r & 3))) & 0xFFFFu);
-        if (c) atomicAdd(&h[r], c);
-      }
-  } else {
-#pragma unroll
-    for (uint32_t k = 0; k < KW_SHARD_ITEMS; ++k) {
-      const uint64_t i = base + threadIdx.x + k * KW_SHARD_THREADS;
-      if (i < n) atomicAdd(&h[kw_rank_of<HASH>(key[k], seed, p, pmask)], 1u);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < p) tile_counts[(uint64_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
-}
-// any p <= KH_SHARD_MAXR: lane t owns items [4t, 4t+4) of the tile; per rank, an exclusive scan over the lanes gives the order
-template <int HASH>
-__global__ __launch_bounds__(KW_SHARD_THREADS) void kw_shard_scatter(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint64_t n,
-                                                                     uint64_t seed, uint32_t p, uint32_t pmask,
-                                                                     const uint64_t* __restrict__ tile_off /* [p][ntiles] exclusive */, uint32_t ntiles,
-                                                                     uint64_t* __restrict__ ok, uint32_t* __restrict__ ov) {
-  __shared__ uint32_t wtot[KW_SHARD_THREADS / 64][KH_SHARD_MAXR];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const uint64_t base = (uint64_t)blockIdx.x * KW_SHARD_TILE + (uint64_t)tid * KW_SHARD_ITEMS;
-  const uint4* k4 = reinterpret_cast<const uint4*>(keys);
-  uint4 key[KW_SHARD_ITEMS]; uint32_t val[KW_SHARD_ITEMS], rk[KW_SHARD_ITEMS];
-#pragma unroll
-  for (int j = 0; j < KW_SHARD_ITEMS; ++j) { const uint64_t i = base + j; key[j] = k4[i < n ? i : n - 1]; }
-#pragma unroll
-  for (int j = 0; j < KW_SHARD_ITEMS; ++j) { const uint64_t i = base + j; val[j] = vals ? vals[i < n ? i : n - 1] : 0u; }
-#pragma unroll
-  for (int j = 0; j < KW_SHARD_ITEMS; ++j) rk[j] = base + j < n ? kw_rank_of<HASH>(key[j], seed, p, pmask) : 0xFFFFFFFFu;
-  for (uint32_t r = 0; r < p; ++r) {
-    uint32_t c = 0;
-#pragma unroll
-    for (int j = 0; j < KW_SHARD_ITEMS; ++j) c += (rk[j] == r) ? 1u : 0u;
-    uint32_t incl = c;
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint32_t o = __shfl_up(incl, off, 64);
-      if (lane >= (uint32_t)off) incl += o;
-    }
-    if (lane == 63) wtot[wid][r] = incl;
-    __syncthreads();
-    uint32_t wpre = 0;
-    for (uint32_t w = 0; w < wid; ++w) wpre += wtot[w][r];
-    uint64_t pos = tile_off[(uint64_t)r * ntiles + blockIdx.x] + wpre + incl - c;
-#pragma unroll
-    for (int j = 0; j < KW_SHARD_ITEMS; ++j) {
-      if (rk[j] == r) {
-        reinterpret_cast<uint4*>(ok)[pos] = key[j];
-        if (vals) ov[pos] = val[j];
-        ++pos;
-      }
-    }
-  }
-}
-// p <= 8 ranks (one node): all per-rank prefix sums in one wave scan of packed 16-bit counters, the tile staged in LDS in (rank, input
-// order), the write-out coalesced (16 bytes per lane, consecutive lanes consecutive keys).  Stable, like the generic kernel.
-template <int HASH>
-__global__ __launch_bounds__(KW_SHARD_THREADS) void kw_shard_scatter8(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint64_t n,
-                                                                      uint64_t seed, uint32_t p, uint32_t pmask,
-                                                                      const uint64_t* __restrict__ tile_off /* [p][ntiles] exclusive */, uint32_t ntiles,
-                                                                      uint64_t* __restrict__ ok, uint32_t* __restrict__ ov) {
-  __shared__ uint4 lk[KW_SHARD_TILE];
-  __shared__ uint32_t lv[KW_SHARD_TILE];
-  __shared__ unsigned long long wtot[KW_SHARD_THREADS / 64][2];
-  __shared__ uint32_t rank_off[9];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const uint64_t tbase = (uint64_t)blockIdx.x * KW_SHARD_TILE;
-  const uint64_t base = tbase + (uint64_t)tid * KW_SHARD_ITEMS;
-  const uint32_t tile_len = (n - tbase) < KW_SHARD_TILE ? (uint32_t)(n - tbase) : KW_SHARD_TILE;
-  const uint4* k4 = reinterpret_cast<const uint4*>(keys);
-  uint4 key[KW_SHARD_ITEMS]; uint32_t val[KW_SHARD_ITEMS], rk[KW_SHARD_ITEMS];
-  unsigned long long c0 = 0, c1 = 0;     // counts of ranks 0-3 / 4-7, 16 bits each
-#pragma unroll
-  for (int j = 0; j < KW_SHARD_ITEMS; ++j) { const uint64_t i = base + j; key[j] = k4[i < n ? i : n - 1]; }
-#pragma unroll
-  for (int j = 0; j < KW_SHARD_ITEMS; ++j) { const uint64_t i = base + j; val[j] = vals ? vals[i < n ? i : n - 1] : 0u; }
-#pragma unroll
-  for (int j = 0; j < KW_SHARD_ITEMS; ++j) {
-    rk[j] = 0xFFu;
-    if (base + j < n) {
-      rk[j] = kw_rank_of<HASH>(key[j], seed, p, pmask);
-      if (rk[j] < 4) c0 += 1ull << (16 * rk[j]); else c1 += 1ull << (16 * (rk[j] - 4));
-    }
-  }
-  unsigned long long i0 = c0, i1 = c1;
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned long long o0 = __shfl_up(i0, off, 64), o1 = __shfl_up(i1, off, 64);
-    if (lane >= (uint32_t)off) { i0 += o0; i1 += o1; }
-  }
-  if (lane == 63) { wtot[wid][0] = i0; wtot[wid][1] = i1; }
-  __syncthreads();
-  unsigned long long e0 = i0 - c0, e1 = i1 - c1, t0 = 0, t1 = 0;
-  for (uint32_t w = 0; w < KW_SHARD_THREADS / 64; ++w) {
-    if (w < wid) { e0 += wtot[w][0]; e1 += wtot[w][1]; }
-    t0 += wtot[w][0]; t1 += wtot[w][1];
-  }
-  if (tid == 0) {
-    uint32_t run = 0;
-    for (uint32_t r = 0; r < 8; ++r) {
-      rank_off[r] = run;
-      run += (uint32_t)(((r < 4 ? t0 : t1) >> (16 * (r & 3))) & 0xFFFFu);
-    }
-    rank_off[8] = run;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < KW_SHARD_ITEMS; ++j) {
-    if (rk[j] != 0xFFu) {
-      const uint32_t r = rk[j];
-      const uint32_t within = (uint32_t)(((r < 4 ? e0 : e1) >> (16 * (r & 3))) & 0xFFFFu);
-      const uint32_t s = rank_off[r] + within;
-      lk[s] = key[j]; lv[s] = val[j];
-      if (r < 4) e0 += 1ull << (16 * r); else e1 += 1ull << (16 * (r - 4));
-    }
-  }
-  __syncthreads();
-  for (uint32_t s = tid; s < tile_len; s += KW_SHARD_THREADS) {
-    uint32_t r = 0;
-#pragma unroll
-    for (uint32_t k = 1; k < 8; ++k) r += (s >= rank_off[k]) ? 1u : 0u;
-    const uint64_t pos = tile_off[(uint64_t)r * ntiles + blockIdx.x] + (s - rank_off[r]);
-    reinterpret_cast<uint4*>(ok)[pos] = lk[s];
-    if (vals) ov[pos] = lv[s];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// 128-bit k-mers (k = 1..64): the 64-bit front end's tile layout (kh_km_pack_tile's 16 bases per lane word + invalid-byte mask) with a
-// halo of four words, so that the 16 windows starting in a lane's word are cut from five consecutive words with funnel shifts.
-// Same two passes (valid windows per tile, k_scan_u32_to_u64, windows written in order); FASTQ goes through k_fastq_mask first.
-// ---------------------------------------------------------------------------------------------
-#define KW_KM_HALO 4u
-__device__ __forceinline__ void kw_km_pack_tile(const uint8_t* __restrict__ seq, uint64_t n, uint64_t tile0, uint32_t* words, uint16_t* invs) {
-  for (uint32_t w = threadIdx.x; w < KH_KM_TILE / 16 + KW_KM_HALO; w += KH_KM_THREADS) {
-    const uint64_t p0 = tile0 + (uint64_t)w * 16;
-    uint8_t b[16];
-    if (p0 + 16 <= n && ((reinterpret_cast<uintptr_t>(seq) + p0) & 15u) == 0) {
-      const uint4 v = *reinterpret_cast<const uint4*>(seq + p0);
-      const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int j = 0; j < 16; ++j) b[j] = (uint8_t)(vv[j >> 2] >> (8 * (j & 3)));
-    } else {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) b[j] = p0 + j < n ? seq[p0 + j] : (uint8_t)'\n';
-    }
-    uint32_t word = 0, inv = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const uint32_t c = kh_dna_code(b[j]);
-      word = (word << 2) | (c & 3u);
-      inv = (inv << 1) | (c > 3u ? 1u : 0u);
-    }
-    words[w] = word; invs[w] = (uint16_t)inv;
-  }
-}
-struct KwKmerWin { uint64_t a, b, c; uint64_t ia, ib; };   // bases 0..31 | 32..63 | 64..79 (top half); invalid bits of bases 0..63 | 64..79 (top)
-__device__ __forceinline__ KwKmerWin kw_km_window(const uint32_t* words, const uint16_t* invs, uint32_t t) {
-  KwKmerWin W;
-  W.a = ((uint64_t)words[t] << 32) | words[t + 1];
-  W.b = ((uint64_t)words[t + 2] << 32) | words[t + 3];
-  W.c = (uint64_t)words[t + 4] << 32;
-  W.ia = ((uint64_t)invs[t] << 48) | ((uint64_t)invs[t + 1] << 32) | ((uint64_t)invs[t + 2] << 16) | invs[t + 3];
-  W.ib = (uint64_t)invs[t + 4] << 48;
-  return W;
-}
-__device__ __forceinline__ bool kw_km_valid(const KwKmerWin& W, uint32_t j, uint32_t k) {
-  const uint64_t x = j ? ((W.ia << j) | (W.ib >> (64 - j))) : W.ia;      // invalid bits of bases j..j+63, first base in the top bit
-  return k >= 64 ? x == 0 : (x >> (64 - k)) == 0;
-}
-__device__ __forceinline__ void kw_km_forward(const KwKmerWin& W, uint32_t j, uint32_t k, uint64_t* w0, uint64_t* w1) {
-  uint64_t A = W.a, B = W.b;
-  if (j) { A = (W.a << (2 * j)) | (W.b >> (64 - 2 * j)); B = (W.b << (2 * j)) | (W.c >> (64 - 2 * j)); }   // bases j..j+63 left-aligned
-  const uint32_t s = 128u - 2u * k;
-  if (s >= 64u) { *w0 = A >> (s - 64u); *w1 = 0; }
-  else if (s) { *w0 = (B >> s) | (A << (64u - s)); *w1 = A >> s; }
-  else { *w0 = B; *w1 = A; }
-}
-__global__ __launch_bounds__(KH_KM_THREADS) void kw_kmers_count(const uint8_t* __restrict__ seq, uint64_t n, uint32_t k, uint32_t* __restrict__ sums) {
-  __shared__ uint32_t words[KH_KM_TILE / 16 + KW_KM_HALO];
-  __shared__ uint16_t invs[KH_KM_TILE / 16 + KW_KM_HALO];
-  __shared__ uint32_t wsum[KH_KM_THREADS / 64];
-  kw_km_pack_tile(seq, n, (uint64_t)blockIdx.x * KH_KM_TILE, words, invs);
-  __syncthreads();
-  const KwKmerWin W = kw_km_window(words, invs, threadIdx.x);
-  uint32_t c = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < 16; ++j) c += kw_km_valid(W, j, k) ? 1u : 0u;
-  c = kh_wave_sum(c);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) sums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
 template <bool CANON>
 __global__ __launch_bounds__(KH_KM_THREADS) void kw_kmers_emit(const uint8_t* __restrict__ seq, uint64_t n, uint32_t k, const uint64_t* __restrict__ tile_off,
                                                                uint64_t* __restrict__ out) {
-  __shared__ uint32_t words[KH_KM_TILE / 16 + KW_KM_HALO];
-  __shared__ uint16_t invs[KH_KM_TILE / 16 + KW_KM_HALO];
+  typedef KhKm<2> M;
+  __shared__ uint32_t words[KH_KM_TILE / 16 + M::HALO];
+  __shared__ uint16_t invs[KH_KM_TILE / 16 + M::HALO];
   __shared__ uint32_t wtot[KH_KM_THREADS / 64];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  kw_km_pack_tile(seq, n, (uint64_t)blockIdx.x * KH_KM_TILE, words, invs);
+  kh_km_pack_tile<M::HALO>(seq, n, (uint64_t)blockIdx.x * KH_KM_TILE, words, invs);
   __syncthreads();
-  const KwKmerWin W = kw_km_window(words, invs, tid);
+  const M::Win W = M::window(words, invs, tid);
   uint32_t vmask = 0;
 #pragma unroll
-  for (uint32_t j = 0; j < 16; ++j) vmask |= kw_km_valid(W, j, k) ? (1u << j) : 0u;
+  for (uint32_t j = 0; j < 16; ++j) vmask |= M::valid(W, j, k) ? (1u << j) : 0u;
   const uint32_t mine = (uint32_t)__popc(vmask);
   uint32_t incl = mine;
   for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off, 64); if (lane >= (uint32_t)off) incl += o; }
@@ -801,7 +563,7 @@ __global__ __launch_bounds__(KH_KM_THREADS) void kw_kmers_emit(const uint8_t* __
   for (uint32_t j = 0; j < 16; ++j) {
     if ((vmask >> j) & 1u) {
       uint64_t w0, w1;
-      kw_km_forward(W, j, k, &w0, &w1);
+      M::forward(W, j, k, &w0, &w1);
       if (CANON) kh_xf128(&w0, &w1, k);
       reinterpret_cast<ulonglong2*>(out)[pos++] = make_ulonglong2(w0, w1);
     }
@@ -809,56 +571,25 @@ __global__ __launch_bounds__(KH_KM_THREADS) void kw_kmers_emit(const uint8_t* __
 }
 
 // ---------------------------------------------------------------------------------------------
-// HyperLogLog over 16-byte keys and over text (hyperloglog64.hpp:175-188 internal_update on hash values, as k_hll_update does it:
-// v = hash << ignored_msb; register = top `precision` bits of v; rank = clz((v << precision) | mask) + 1).  Registers live in hash-value
-// space, so an estimator may be fed by k_hll_update and by these kernels alike.
-//   k_hll_update_wide: keys u64[2n], one 16-byte load per key, hash = kh_hash128 (what kw_hash_batch computes).
-//   k_hll_from_text:   text -> tile (kh_km_pack_tile / kw_km_pack_tile) -> the 16 windows of the lane's word -> validity -> forward k-mer
-//                      -> canonical form -> hash -> register.  Reads 1 B per base and writes nothing but the 2^precision registers: the
-//                      k-mers (8 or 16 B per window) never reach HBM.  Workgroups are persistent: the host launches
-//                      min(tiles, KH_HLL_TEXT_WGS_PER_CU x CUs) of them, each loops grid-stride over the 4096-position tiles, keeps its
-//                      registers in LDS over ALL its tiles and merges them into the global registers once at the end (a merge per tile
-//                      would cost up to one global atomic per window).  LDS per workgroup: 4 x 2^precision B of registers (16 KB at the
-//                      default precision 12, 32 KB at 13) + 1.6 KB of tile words, so four 256-lane workgroups fit a CU (4 waves per
-//                      SIMD, <= 128 VGPRs) at every precision that uses LDS; above 13 the registers are updated in global memory.  No
-//                      workgroup waits for another: a grid that is not fully resident is merely slower.
+// HyperLogLog straight from text: text -> tile (kh_km_pack_tile) -> the 16 windows of the lane's word -> validity -> forward k-mer ->
+// canonical form -> hash (KhKm<KW>::hash_of_window) -> register (kh_hll_put, as k_hll_update does it).  Reads 1 B per base and writes
+// nothing but the 2^precision registers: the k-mers (8 or 16 B per window) never reach HBM.  Workgroups are persistent: the host launches
+// min(tiles, KH_HLL_TEXT_WGS_PER_CU x CUs) of them, each loops grid-stride over the 4096-position tiles, keeps its registers in LDS over
+// ALL its tiles and merges them into the global registers once at the end (a merge per tile would cost up to one global atomic per
+// window).  LDS per workgroup: 4 x 2^precision B of registers (16 KB at the default precision 12, 32 KB at 13) + 1.6 KB of tile words,
+// so four 256-lane workgroups fit a CU (4 waves per SIMD, <= 128 VGPRs) at every precision that uses LDS; above 13 the registers are
+// updated in global memory.  No workgroup waits for another: a grid that is not fully resident is merely slower.
+// KW = 1: k = 1..32, the hash of the 8-byte k-mer (what k_hll_update makes of k_kmers_emit's output); KW = 2: k = 33..64, the hash of the
+// 16-byte k-mer {w0, w1} (of kw_kmers_emit's output).  n_windows (may be null): += the number of valid windows.
 // ---------------------------------------------------------------------------------------------
 #define KH_HLL_TEXT_WGS_PER_CU 4
-struct KhHllRegs { uint32_t* regs; uint32_t precision, ignored; int use_lds; };
-__device__ __forceinline__ void kh_hll_put(const KhHllRegs& R, uint32_t* lds, uint64_t lzc_mask, uint64_t hv) {
-  const uint64_t v = hv << R.ignored;
-  const uint32_t r = (uint32_t)(v >> (64 - R.precision));
-  const uint32_t rank = (uint32_t)__clzll((long long)((v << R.precision) | lzc_mask)) + 1u;
-  if (R.use_lds) atomicMax(&lds[r], rank); else atomicMax(&R.regs[r], rank);
-}
-__device__ __forceinline__ void kh_hll_lds_clear(const KhHllRegs& R, uint32_t* lds) {      // (the caller's next barrier publishes the zeros)
-  if (R.use_lds) for (uint32_t i = threadIdx.x; i < (1u << R.precision); i += blockDim.x) lds[i] = 0;
-}
-__device__ __forceinline__ void kh_hll_lds_flush(const KhHllRegs& R, const uint32_t* lds) {
-  if (!R.use_lds) return;
-  __syncthreads();
-  for (uint32_t j = threadIdx.x; j < (1u << R.precision); j += blockDim.x) { const uint32_t v = lds[j]; if (v) atomicMax(&R.regs[j], v); }
-}
-template <int HASH>
-__global__ __launch_bounds__(256) void k_hll_update_wide(const uint64_t* __restrict__ keys, uint64_t n, uint64_t seed, KhHllRegs R) {
-  extern __shared__ __align__(16) uint32_t kh_dyn_smem[];
-  kh_hll_lds_clear(R, kh_dyn_smem);
-  __syncthreads();
-  const uint64_t lzc_mask = ~0ull >> (64 - R.precision - R.ignored);
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint4 k = reinterpret_cast<const uint4*>(keys)[i];
-    kh_hll_put(R, kh_dyn_smem, lzc_mask, kw_hash<HASH>((uint64_t)k.x | ((uint64_t)k.y << 32), (uint64_t)k.z | ((uint64_t)k.w << 32), seed));
-  }
-  kh_hll_lds_flush(R, kh_dyn_smem);
-}
-// KW = 1: k = 1..32, hashes the 8-byte k-mer (kh_hash64, what k_hll_update does with k_kmers_emit's output); KW = 2: k = 33..64, hashes
-// the 16-byte k-mer {w0, w1} (kh_hash128 of kw_kmers_emit's output).  n_windows (may be null): += the number of valid windows.
 template <int HASH, int KW, bool CANON>
 __global__ __launch_bounds__(KH_KM_THREADS, 4) void k_hll_from_text(const uint8_t* __restrict__ seq, uint64_t n, uint32_t k, uint64_t seed, KhHllRegs R,
                                                                     unsigned long long* __restrict__ n_windows) {
+  typedef KhKm<KW> M;
   extern __shared__ __align__(16) uint32_t kh_dyn_smem[];
-  __shared__ uint32_t words[KH_KM_TILE / 16 + KW_KM_HALO];
-  __shared__ uint16_t invs[KH_KM_TILE / 16 + KW_KM_HALO];
+  __shared__ uint32_t words[KH_KM_TILE / 16 + M::HALO];
+  __shared__ uint16_t invs[KH_KM_TILE / 16 + M::HALO];
   __shared__ uint32_t wsum[KH_KM_THREADS / 64];
   kh_hll_lds_clear(R, kh_dyn_smem);
   const uint64_t lzc_mask = ~0ull >> (64 - R.precision - R.ignored);
@@ -866,35 +597,15 @@ __global__ __launch_bounds__(KH_KM_THREADS, 4) void k_hll_from_text(const uint8_
   uint32_t cnt = 0;
   for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     __syncthreads();      // the previous tile's words have been read (first tile: the LDS registers are zero)
-    if (KW == 2) kw_km_pack_tile(seq, n, tile * KH_KM_TILE, words, invs); else kh_km_pack_tile(seq, n, tile * KH_KM_TILE, words, invs);
+    kh_km_pack_tile<M::HALO>(seq, n, tile * KH_KM_TILE, words, invs);
     __syncthreads();
-    if (KW == 2) {
-      const KwKmerWin W = kw_km_window(words, invs, threadIdx.x);
-      uint32_t vmask = 0;
+    const typename M::Win W = M::window(words, invs, threadIdx.x);
+    uint32_t vmask = 0;
 #pragma unroll
-      for (uint32_t j = 0; j < 16; ++j) vmask |= kw_km_valid(W, j, k) ? (1u << j) : 0u;
-      cnt += (uint32_t)__popc(vmask);
-      for (uint32_t j = 0; j < 16; ++j) {
-        if ((vmask >> j) & 1u) {
-          uint64_t w0, w1;
-          kw_km_forward(W, j, k, &w0, &w1);
-          if (CANON) kh_xf128(&w0, &w1, k);
-          kh_hll_put(R, kh_dyn_smem, lzc_mask, kh_hash128<HASH>(w0, w1, seed));
-        }
-      }
-    } else {
-      const KhKmerWin W = kh_km_window(words, invs, threadIdx.x);
-      uint32_t vmask = 0;
-#pragma unroll
-      for (uint32_t j = 0; j < 16; ++j) vmask |= kh_km_valid(W, j, k) ? (1u << j) : 0u;
-      cnt += (uint32_t)__popc(vmask);
-      for (uint32_t j = 0; j < 16; ++j) {
-        if ((vmask >> j) & 1u) {
-          const uint64_t fw = kh_km_forward(W, j, k);
-          kh_hll_put(R, kh_dyn_smem, lzc_mask, kh_hash64<HASH>(CANON ? kh_xf(fw, k) : fw, seed));
-        }
-      }
-    }
+    for (uint32_t j = 0; j < 16; ++j) vmask |= M::valid(W, j, k) ? (1u << j) : 0u;
+    cnt += (uint32_t)__popc(vmask);
+    for (uint32_t j = 0; j < 16; ++j)
+      if ((vmask >> j) & 1u) kh_hll_put(R, kh_dyn_smem, lzc_mask, M::template hash_of_window<HASH, CANON>(W, j, k, seed));
   }
   kh_hll_lds_flush(R, kh_dyn_smem);
   if (n_windows) {      // valid windows: summed per wave, one 64-bit atomic per workgroup

@@ -2098,13 +2098,55 @@ kh_status hash_batch_impl(uint32_t kw, kh_hash hash, KhSeed seed, const void* ke
     HIPCHK(hipMemcpyAsync(tmp, keys, n * 8 * kw, hipMemcpyHostToDevice, stream));
     dk = tmp; dout = tmp + kw * n;
   }
-  if (kw == 2) { KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((kw_hash_batch<HASH>), dim3(grid_for(n, 256)), dim3(256), 0, stream, dk, n, seed.s, dout)); }
-  else { KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_hash_batch<HASH>), dim3(grid_for(n, 256)), dim3(256), 0, stream, dk, n, seed, dout)); }
+  if (kw == 2) { KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_hash_batch<HASH, 2>), dim3(grid_for(n, 256)), dim3(256), 0, stream, dk, n, seed.s, dout)); }
+  else { KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_hash_batch<HASH, 1>), dim3(grid_for(n, 256)), dim3(256), 0, stream, dk, n, seed, dout)); }
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && where == KH_MEM_HOST) e = hipMemcpyAsync(out, dout, n * 8, hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess && where == KH_MEM_HOST) e = hipStreamSynchronize(stream);
   if (tmp) pool_free(device, tmp);
   return e == hipSuccess ? KH_OK : KH_ERR_HIP;
+}
+// stable partition of (key, value) by destination rank = hash(key) mod p for keys of kw 64-bit words (xf / k: 8-byte keys only);
+// out_keys == null: count only -- the caller sizes the exchange before it permutes (pipelined multi-GPU insert)
+kh_status shard_permute_impl(uint32_t kw, kh_hash hash, uint64_t seed_, kh_key_transform xf, uint32_t k, uint32_t p, const uint64_t* keys,
+                             const uint32_t* vals, uint64_t n, uint64_t* out_keys, uint32_t* out_vals, uint64_t* counts_host, int device, void* stream_) {
+  kh_table* t = nullptr;
+  if (p == 0 || p > KH_SHARD_MAXR || !counts_host || (int)hash < 0 || (int)hash > 3 || !xform_ok(xf, k)) return KH_ERR_INVALID;
+  const KhSeed seed = make_seed(seed_, xf, k);
+  for (uint32_t r = 0; r < p; ++r) counts_host[r] = 0;
+  if (n == 0) return KH_OK;
+  if (!keys || (out_keys && vals && !out_vals)) return KH_ERR_INVALID;
+  const uint64_t tile = kw == 2 ? KH_SHARD_TILE(2) : KH_SHARD_TILE(1);
+  if (kw == 2) {
+    if (((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(out_keys)) & 15u) != 0) return KH_ERR_INVALID;     // one 16-byte access per key
+    if ((n + tile - 1) / tile > 0x7FFFFFFFull) return KH_ERR_UNSUPPORTED;
+  }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK(hipSetDevice(device));
+  const uint32_t ntiles = (uint32_t)((n + tile - 1) / tile);
+  const uint32_t pmask = (p & (p - 1)) == 0 ? p - 1 : 0;   // power of two: & (p-1); else % p.  (p == 1: mask 0 -> % 1)
+  uint32_t* tc = nullptr; uint64_t* toff = nullptr;
+  const uint64_t m = (uint64_t)p * ntiles;
+  HIPCHK(pool_alloc(device, m * 4, reinterpret_cast<void**>(&tc)));
+  if (pool_alloc(device, (m + 1) * 8, reinterpret_cast<void**>(&toff)) != hipSuccess) { pool_free(device, tc); return KH_ERR_NOMEM; }
+  // (S: the seed in the form the key width's hash takes)
+#define KH_SHARD_LAUNCH(KERNEL, ...)                                                                                                                            \
+  if (kw == 2) { const uint64_t S = seed.s; KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((KERNEL<HASH, 2>), dim3(ntiles), dim3(KH_SHARD_THREADS), 0, stream, __VA_ARGS__)); } \
+  else { const KhSeed S = seed; KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((KERNEL<HASH, 1>), dim3(ntiles), dim3(KH_SHARD_THREADS), 0, stream, __VA_ARGS__)); }
+  KH_SHARD_LAUNCH(k_shard_count, keys, n, S, p, pmask, tc, ntiles);
+  hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, tc, m, toff);
+  if (out_keys && p <= 8) { KH_SHARD_LAUNCH(k_shard_scatter8, keys, vals, n, S, p, pmask, (const uint64_t*)toff, ntiles, out_keys, out_vals); }
+  else if (out_keys) { KH_SHARD_LAUNCH(k_shard_scatter, keys, vals, n, S, p, pmask, (const uint64_t*)toff, ntiles, out_keys, out_vals); }
+#undef KH_SHARD_LAUNCH
+  std::vector<uint64_t> ends(p + 1);
+  hipError_t e = hipGetLastError();
+  for (uint32_t r = 0; r <= p && e == hipSuccess; ++r)
+    e = hipMemcpyAsync(&ends[r], toff + (uint64_t)r * ntiles, 8, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  pool_free(device, tc); pool_free(device, toff);
+  if (e != hipSuccess) return KH_ERR_HIP;
+  for (uint32_t r = 0; r < p; ++r) counts_host[r] = ends[r + 1] - ends[r];
+  return KH_OK;
 }
 }
 extern "C" {
@@ -2137,38 +2179,7 @@ kh_status kh_shard_permute(kh_hash hash, uint64_t seed, uint32_t p, const uint64
 kh_status kh_shard_permute_transformed(kh_hash hash, uint64_t seed_, kh_key_transform xf, uint32_t k, uint32_t p, const uint64_t* keys,
                                        const uint32_t* vals, uint64_t n, uint64_t* out_keys, uint32_t* out_vals, uint64_t* counts_host,
                                        int device, void* stream_) {
-  kh_table* t = nullptr;
-  if (p == 0 || p > KH_SHARD_MAXR || !counts_host || (int)hash < 0 || (int)hash > 3 || !xform_ok(xf, k)) return KH_ERR_INVALID;
-  const KhSeed seed = make_seed(seed_, xf, k);
-  for (uint32_t r = 0; r < p; ++r) counts_host[r] = 0;
-  if (n == 0) return KH_OK;
-  if (!keys || (out_keys && vals && !out_vals)) return KH_ERR_INVALID;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
-  const uint32_t ntiles = (uint32_t)((n + KH_SHARD_TILE - 1) / KH_SHARD_TILE);
-  const uint32_t pmask = (p & (p - 1)) == 0 ? p - 1 : 0;   // power of two: & (p-1); else % p.  (p == 1: mask 0 -> % 1)
-  uint32_t* tc = nullptr; uint64_t* toff = nullptr;
-  const uint64_t m = (uint64_t)p * ntiles;
-  HIPCHK(pool_alloc(device, m * 4, reinterpret_cast<void**>(&tc)));
-  if (pool_alloc(device, (m + 1) * 8, reinterpret_cast<void**>(&toff)) != hipSuccess) { pool_free(device, tc); return KH_ERR_NOMEM; }
-  KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_shard_count<HASH>), dim3(ntiles), dim3(KH_SHARD_THREADS), 0, stream, keys, n, seed, p, pmask, tc, ntiles));
-  hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, tc, m, toff);
-  if (!out_keys) {
-    // count only: the caller sizes the exchange before it permutes (pipelined multi-GPU insert)
-  } else if (p <= 8) {
-    KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_shard_scatter8<HASH>), dim3(ntiles), dim3(KH_SHARD_THREADS), 0, stream, keys, vals, n, seed, p, pmask, toff, ntiles, out_keys, out_vals));
-  } else {
-    KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_shard_scatter<HASH>), dim3(ntiles), dim3(KH_SHARD_THREADS), 0, stream, keys, vals, n, seed, p, pmask, toff, ntiles, out_keys, out_vals));
-  }
-  std::vector<uint64_t> ends(p + 1);
-  hipError_t e = hipGetLastError();
-  for (uint32_t r = 0; r <= p && e == hipSuccess; ++r)
-    e = hipMemcpyAsync(&ends[r], toff + (uint64_t)r * ntiles, 8, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  pool_free(device, tc); pool_free(device, toff);
-  if (e != hipSuccess) return KH_ERR_HIP;
-  for (uint32_t r = 0; r < p; ++r) counts_host[r] = ends[r + 1] - ends[r];
-  return KH_OK;
+  return shard_permute_impl(1, hash, seed_, xf, k, p, keys, vals, n, out_keys, out_vals, counts_host, device, stream_);
 }
 
 // ---- shard plan: ONE count sweep + scan over a whole batch that is going to be exchanged in pieces; the per-piece destination
@@ -2190,8 +2201,8 @@ kh_status kh_shard_plan_create(kh_shard_plan** out, kh_hash hash, uint64_t seed_
   std::unique_ptr<kh_shard_plan> P(new kh_shard_plan());
   P->device = device; P->hash = (int)hash; P->seed = make_seed(seed_, xf, k); P->p = p; P->pmask = (p & (p - 1)) == 0 ? p - 1 : 0;
   P->pieces = pieces; P->n = n; P->tc = nullptr; P->toff = nullptr; P->bnd_dev = nullptr;
-  P->ntiles = (uint32_t)((n + KH_SHARD_TILE - 1) / KH_SHARD_TILE);
-  for (uint32_t i = 0; i <= pieces; ++i) bounds_host[i] = std::min<uint64_t>(n, ((uint64_t)P->ntiles * i / pieces) * KH_SHARD_TILE);
+  P->ntiles = (uint32_t)((n + KH_SHARD_TILE(1) - 1) / KH_SHARD_TILE(1));
+  for (uint32_t i = 0; i <= pieces; ++i) bounds_host[i] = std::min<uint64_t>(n, ((uint64_t)P->ntiles * i / pieces) * KH_SHARD_TILE(1));
   for (uint64_t j = 0; j < (uint64_t)pieces * p; ++j) counts_host[j] = 0;
   P->bnd.assign((size_t)p * (pieces + 1), 0);
   if (n) {
@@ -2203,7 +2214,7 @@ kh_status kh_shard_plan_create(kh_shard_plan** out, kh_hash hash, uint64_t seed_
       pool_free(device, P->tc);
       return KH_ERR_NOMEM;
     }
-    KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_shard_count<HASH>), dim3(P->ntiles), dim3(KH_SHARD_THREADS), 0, stream, keys, n, P->seed, p, P->pmask, P->tc, P->ntiles));
+    KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_shard_count<HASH, 1>), dim3(P->ntiles), dim3(KH_SHARD_THREADS), 0, stream, keys, n, P->seed, p, P->pmask, P->tc, P->ntiles));
     hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, P->tc, m, P->toff);
     hipLaunchKernelGGL(k_shard_piece_bounds, dim3(1 + (uint32_t)P->bnd.size() / 256), dim3(256), 0, stream, (const uint64_t*)P->toff, P->ntiles, p, pieces, P->bnd_dev);
     hipError_t e = hipGetLastError();
@@ -2226,7 +2237,7 @@ kh_status kh_shard_plan_permute(kh_shard_plan* P, uint32_t piece, const uint64_t
   HIPCHK(hipSetDevice(P->device));
   const uint32_t t0 = (uint32_t)((uint64_t)P->ntiles * piece / P->pieces), t1 = (uint32_t)((uint64_t)P->ntiles * (piece + 1) / P->pieces);
   if (t1 == t0) return KH_OK;
-  const uint64_t b0 = (uint64_t)t0 * KH_SHARD_TILE, b1 = std::min<uint64_t>(P->n, (uint64_t)t1 * KH_SHARD_TILE);
+  const uint64_t b0 = (uint64_t)t0 * KH_SHARD_TILE(1), b1 = std::min<uint64_t>(P->n, (uint64_t)t1 * KH_SHARD_TILE(1));
   KhShardAdj adj;
   uint64_t base = 0;      // where rank r's pairs of THIS piece start in the piece's output
   for (uint32_t r = 0; r < P->p; ++r) {
@@ -2234,7 +2245,7 @@ kh_status kh_shard_plan_permute(kh_shard_plan* P, uint32_t piece, const uint64_t
     adj.a[r] = (long long)base - (long long)lo;
     base += hi - lo;
   }
-  KH_SWITCH_HASH(P->hash, hipLaunchKernelGGL((k_shard_scatter8<HASH>), dim3(t1 - t0), dim3(KH_SHARD_THREADS), 0, stream, keys + b0, vals ? vals + b0 : nullptr, b1 - b0,
+  KH_SWITCH_HASH(P->hash, hipLaunchKernelGGL((k_shard_scatter8<HASH, 1>), dim3(t1 - t0), dim3(KH_SHARD_THREADS), 0, stream, keys + b0, vals ? vals + b0 : nullptr, b1 - b0,
                                              P->seed, P->p, P->pmask, (const uint64_t*)P->toff, P->ntiles, out_keys, out_vals, t0, adj));
   HIPCHK(hipGetLastError());
   return KH_OK;
@@ -2251,9 +2262,9 @@ kh_status kh_shard_plan_permute_global(kh_shard_plan* P, uint32_t piece, const u
   HIPCHK(hipSetDevice(P->device));
   const uint32_t t0 = (uint32_t)((uint64_t)P->ntiles * piece / P->pieces), t1 = (uint32_t)((uint64_t)P->ntiles * (piece + 1) / P->pieces);
   if (t1 == t0) return KH_OK;
-  const uint64_t b0 = (uint64_t)t0 * KH_SHARD_TILE, b1 = std::min<uint64_t>(P->n, (uint64_t)t1 * KH_SHARD_TILE);
+  const uint64_t b0 = (uint64_t)t0 * KH_SHARD_TILE(1), b1 = std::min<uint64_t>(P->n, (uint64_t)t1 * KH_SHARD_TILE(1));
   KhShardAdj adj;      // (all zero)
-  KH_SWITCH_HASH(P->hash, hipLaunchKernelGGL((k_shard_scatter8<HASH>), dim3(t1 - t0), dim3(KH_SHARD_THREADS), 0, stream, keys + b0, vals ? vals + b0 : nullptr, b1 - b0,
+  KH_SWITCH_HASH(P->hash, hipLaunchKernelGGL((k_shard_scatter8<HASH, 1>), dim3(t1 - t0), dim3(KH_SHARD_THREADS), 0, stream, keys + b0, vals ? vals + b0 : nullptr, b1 - b0,
                                              P->seed, P->p, P->pmask, (const uint64_t*)P->toff, P->ntiles, out_keys, out_vals, t0, adj));
   HIPCHK(hipGetLastError());
   return KH_OK;
@@ -2315,8 +2326,8 @@ kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int c
   if (e == hipSuccess) {
     if (fastq) { fastq_mask_text(dseq, n, sums, offs, msk, stream); dseq = msk; }
     // two passes over the text: valid windows per tile, scan, then the windows themselves, compacted and in order
-    if (kw == 2) hipLaunchKernelGGL(kw_kmers_count, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
-    else hipLaunchKernelGGL(k_kmers_count, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
+    if (kw == 2) hipLaunchKernelGGL(k_kmers_count<2>, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
+    else hipLaunchKernelGGL(k_kmers_count<1>, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
     hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, sums, nkt, offs);
     if (kw == 2 && canonical) hipLaunchKernelGGL((kw_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
     else if (kw == 2) hipLaunchKernelGGL((kw_kmers_emit<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
@@ -2400,13 +2411,10 @@ static kh_status hll_update(kh_hll* h, const void* in, uint64_t n, kh_mem where,
   const int use_lds = h->precision <= 13 ? 1 : 0;
   const size_t smem = use_lds ? (sizeof(uint32_t) << h->precision) : 0;
   const uint32_t grid = grid_for(n, 256, 1024);
-  if (kw == 2) {
-    KH_SWITCH_HASH(h->hash, hipLaunchKernelGGL((k_hll_update_wide<HASH>), dim3(grid), dim3(256), smem, h->stream, d, n, h->seed, KhHllRegs{h->regs, h->precision, h->ignored, use_lds}));
-  } else if (from_keys) {
-    KH_SWITCH_HASH(h->hash, hipLaunchKernelGGL((k_hll_update<HASH, true>), dim3(grid), dim3(256), smem, h->stream, d, n, KhSeed{h->seed, 0u}, h->precision, h->ignored, h->regs, use_lds));
-  } else {
-    hipLaunchKernelGGL((k_hll_update<KHH_IDENTITY, false>), dim3(grid), dim3(256), smem, h->stream, d, n, KhSeed{h->seed, 0u}, h->precision, h->ignored, h->regs, use_lds);
-  }
+  const KhHllRegs R{h->regs, h->precision, h->ignored, use_lds};
+  if (kw == 2) { KH_SWITCH_HASH(h->hash, hipLaunchKernelGGL((k_hll_update<HASH, KH_HLL_WIDE_KEYS>), dim3(grid), dim3(256), smem, h->stream, d, n, h->seed, R)); }
+  else if (from_keys) { KH_SWITCH_HASH(h->hash, hipLaunchKernelGGL((k_hll_update<HASH, KH_HLL_KEYS>), dim3(grid), dim3(256), smem, h->stream, d, n, KhSeed{h->seed, 0u}, R)); }
+  else hipLaunchKernelGGL((k_hll_update<KHH_IDENTITY, KH_HLL_HASHVALS>), dim3(grid), dim3(256), smem, h->stream, d, n, KhSeed{h->seed, 0u}, R);
   hipError_t e = hipGetLastError();
   if (tmp) { if (e == hipSuccess) e = hipStreamSynchronize(h->stream); pool_free(h->device, tmp); }
   return e == hipSuccess ? KH_OK : KH_ERR_HIP;
@@ -2967,39 +2975,7 @@ kh_status kh_wide_insert_abort(kh_wtable* t) { return kh_insert_abort(t); }
 // stable partition of 16-byte keys by destination rank (kh_shard_permute for wide keys)
 kh_status kh_wide_shard_permute(kh_hash hash, uint64_t seed, uint32_t p, const uint64_t* keys, const uint32_t* vals, uint64_t n,
                                 uint64_t* out_keys, uint32_t* out_vals, uint64_t* counts_host, int device, void* stream_) {
-  kh_table* t = nullptr;
-  if (p == 0 || p > KH_SHARD_MAXR || !counts_host || (int)hash < 0 || (int)hash > 3) return KH_ERR_INVALID;
-  for (uint32_t r = 0; r < p; ++r) counts_host[r] = 0;
-  if (n == 0) return KH_OK;
-  if (!keys || (out_keys && vals && !out_vals)) return KH_ERR_INVALID;
-  if (((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(out_keys)) & 15u) != 0) return KH_ERR_INVALID;     // one 16-byte access per key
-  if ((n + KW_SHARD_TILE - 1) / KW_SHARD_TILE > 0x7FFFFFFFull) return KH_ERR_UNSUPPORTED;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
-  const uint32_t ntiles = (uint32_t)((n + KW_SHARD_TILE - 1) / KW_SHARD_TILE);
-  const uint32_t pmask = (p & (p - 1)) == 0 ? p - 1 : 0;   // power of two: & (p-1); else % p.  (p == 1: mask 0 -> % 1)
-  uint32_t* tc = nullptr; uint64_t* toff = nullptr;
-  const uint64_t m = (uint64_t)p * ntiles;
-  HIPCHK(pool_alloc(device, m * 4, reinterpret_cast<void**>(&tc)));
-  if (pool_alloc(device, (m + 1) * 8, reinterpret_cast<void**>(&toff)) != hipSuccess) { pool_free(device, tc); return KH_ERR_NOMEM; }
-  KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((kw_shard_count<HASH>), dim3(ntiles), dim3(KW_SHARD_THREADS), 0, stream, keys, n, seed, p, pmask, tc, ntiles));
-  hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, tc, m, toff);
-  if (!out_keys) {
-    // count only
-  } else if (p <= 8) {
-    KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((kw_shard_scatter8<HASH>), dim3(ntiles), dim3(KW_SHARD_THREADS), 0, stream, keys, vals, n, seed, p, pmask, (const uint64_t*)toff, ntiles, out_keys, out_vals));
-  } else {
-    KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((kw_shard_scatter<HASH>), dim3(ntiles), dim3(KW_SHARD_THREADS), 0, stream, keys, vals, n, seed, p, pmask, (const uint64_t*)toff, ntiles, out_keys, out_vals));
-  }
-  std::vector<uint64_t> ends(p + 1);
-  hipError_t e = hipGetLastError();
-  for (uint32_t r = 0; r <= p && e == hipSuccess; ++r)
-    e = hipMemcpyAsync(&ends[r], toff + (uint64_t)r * ntiles, 8, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  pool_free(device, tc); pool_free(device, toff);
-  if (e != hipSuccess) return KH_ERR_HIP;
-  for (uint32_t r = 0; r < p; ++r) counts_host[r] = ends[r + 1] - ends[r];
-  return KH_OK;
+  return shard_permute_impl(2, hash, seed, KH_XF_IDENTITY, 0, p, keys, vals, n, out_keys, out_vals, counts_host, device, stream_);
 }
 kh_status kh_wide_hash_batch(kh_hash hash, uint64_t seed, const void* keys, uint64_t n, kh_mem where, uint64_t* out, int device, void* stream) {
   return hash_batch_impl(2, hash, KhSeed{seed, 0u}, keys, n, where, out, device, stream);

@@ -1,5 +1,6 @@
 """GPU: the two device-side pieces the sharded layer needs for 16-byte keys.
-kh_wide_shard_permute -- the stable partition by destination rank -- against numpy (hash_batch_wide reduced mod p, stable argsort);
+kh_wide_shard_permute -- the stable partition by destination rank -- against numpy (hash_batch_wide reduced mod p, stable argsort), and
+with it kh_shard_permute, the same kernels instantiated for 8-byte keys (against the CPU oracle's hash_batch reduced mod p);
 the streamed insert of the wide table (kh_wide_insert_begin_ex / feed / end / abort) against ONE plain insert of the concatenated
 pieces: same return value, size, capacity, canonical Robin Hood layout (export_info, byte-equal) and items."""
 import ctypes as C
@@ -18,7 +19,14 @@ from kmerhash_amd.dist import DIST_SEED  # noqa: E402
 from kmerhash_amd.table import _hash_id  # noqa: E402
 
 HASHES = ("murmur3avx64", "murmur", "farm", "identity")
-SIZES = (0, 1, 4095, 4096, 4097, 10**6 + 3)
+SIZES = (0, 1, 4095, 4096, 4097, 10**6 + 3)             # 16-byte keys: a tile is 2048 keys
+SIZES_P9 = SIZES[:-1] + (2047, 2048, 2049, 6147)        # ... its edges and one multi-tile size, for p = 9
+NARROW_SIZES = (0, 1, 4095, 4096, 4097, 12_291)         # 8-byte keys: the edges of a 4096-key tile and one multi-tile size
+# 8 / 9: the last p of the LDS-staged kernel / the first of the generic one (and no power of two); 64: KH_SHARD_MAXR
+RANKS = (1, 2, 3, 4, 5, 8, 9, 16, 64)
+WIDTHS = [pytest.param(2, id="wide"), pytest.param(1, id="narrow")]
+# (the 16-byte cases keep the ids they had before the 8-byte ones joined them)
+WIDTH_HASH = [pytest.param(2, h, id=h) for h in HASHES] + [pytest.param(1, h, id="narrow-" + h) for h in HASHES]
 GUARD = 64
 SENT_K, SENT_V = -0x0123456789ABCDEF, 0x5A5A5A5A
 
@@ -38,16 +46,20 @@ def random_wide(rng, n, pool=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# kh_wide_shard_permute
+# kh_wide_shard_permute / kh_shard_permute (kw: 64-bit words per key)
 # ---------------------------------------------------------------------------------------------------------------------------------
-def permute(hash, p, dk, dv, n, count_only=False):
-    """-> (status, out keys (n, 2) | None, out vals | None, counts[p]); the outputs carry GUARD sentinel rows behind them"""
-    ok = torch.full((n + GUARD, 2), SENT_K, dtype=torch.int64, device="cuda")
+def shard_fn(kw):
+    return K.lib().kh_wide_shard_permute if kw == 2 else K.lib().kh_shard_permute
+
+
+def permute(hash, p, dk, dv, n, count_only=False, kw=2):
+    """-> (status, out keys (n, 2) or (n,) | None, out vals | None, counts[p]); the outputs carry GUARD sentinel rows behind them"""
+    ok = torch.full((n + GUARD, 2) if kw == 2 else (n + GUARD,), SENT_K, dtype=torch.int64, device="cuda")
     ov = torch.full((n + GUARD,), SENT_V, dtype=torch.int32, device="cuda")
     counts = (C.c_uint64 * max(p, 1))(*([77] * max(p, 1)))
-    st = K.lib().kh_wide_shard_permute(_hash_id(hash), DIST_SEED, p, dk.data_ptr() if n else None, dv.data_ptr() if (dv is not None and n) else None, n,
-                                       None if count_only else ok.data_ptr(), None if (count_only or dv is None) else ov.data_ptr(), counts, 0,
-                                       torch.cuda.current_stream().cuda_stream)
+    st = shard_fn(kw)(_hash_id(hash), DIST_SEED, p, dk.data_ptr() if n else None, dv.data_ptr() if (dv is not None and n) else None, n,
+                      None if count_only else ok.data_ptr(), None if (count_only or dv is None) else ov.data_ptr(), counts, 0,
+                      torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     return st, ok, ov, [int(c) for c in counts]
 
@@ -64,13 +76,26 @@ def shard_input():
     return keys, vals, dev_keys(keys), dev_vals(vals)
 
 
-@pytest.mark.parametrize("hash", HASHES)
-def test_shard_permute_matches_numpy(shard_input, hash):
-    keys, vals, dk, dv = shard_input
-    h = kh.hash_batch_wide(dk, hash=hash, seed=DIST_SEED).cpu().numpy().view(np.uint64)
-    assert np.array_equal(h[:1000], kh.hash_batch_wide(keys[:1000], hash=hash, seed=DIST_SEED))     # host and device hashes agree
-    for p in (1, 2, 3, 4, 5, 8, 16, 64):
-        for n in SIZES:
+@pytest.fixture(scope="module")
+def narrow_shard_input():
+    rng = np.random.default_rng(32)
+    n = max(NARROW_SIZES)
+    keys = rng.integers(0, 1 << 63, n, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, n, dtype=np.uint64)
+    keys[5_000:5_600] = keys[7]                                 # a run of one key: a whole wave for one rank
+    vals = np.arange(n, dtype=np.uint32)
+    return keys, vals, dev_keys(keys), dev_vals(vals)
+
+
+@pytest.mark.parametrize("kw,hash", WIDTH_HASH)
+def test_shard_permute_matches_numpy(request, oracle, kw, hash):
+    keys, vals, dk, dv = request.getfixturevalue("shard_input" if kw == 2 else "narrow_shard_input")
+    if kw == 2:
+        h = kh.hash_batch_wide(dk, hash=hash, seed=DIST_SEED).cpu().numpy().view(np.uint64)
+        assert np.array_equal(h[:1000], kh.hash_batch_wide(keys[:1000], hash=hash, seed=DIST_SEED))     # host and device hashes agree
+    else:
+        h = oracle.hash_batch(_hash_id(hash), DIST_SEED, keys)
+    for p in RANKS:
+        for n in (NARROW_SIZES if kw == 1 else SIZES_P9 if p == 9 else SIZES):
             r = (h[:n] & np.uint64(p - 1)) if p & (p - 1) == 0 else (h[:n] % np.uint64(p))
             r = r.astype(np.int64)
             order = np.argsort(r, kind="stable")
@@ -78,39 +103,42 @@ def test_shard_permute_matches_numpy(shard_input, hash):
             if hash != "identity" and n >= 4095 and p <= 8:
                 assert min(exp_counts) > 0
             for with_vals in (True, False):
-                st, ok, ov, counts = permute(hash, p, dk, dv if with_vals else None, n)
-                assert st == K.KH_OK, (hash, p, n, st)
-                assert counts == exp_counts, (hash, p, n)
-                assert np.array_equal(ok[:n].cpu().numpy().view(np.uint64), keys[:n][order]), (hash, p, n, with_vals)
+                st, ok, ov, counts = permute(hash, p, dk, dv if with_vals else None, n, kw=kw)
+                assert st == K.KH_OK, (kw, hash, p, n, st)
+                assert counts == exp_counts, (kw, hash, p, n)
+                assert np.array_equal(ok[:n].cpu().numpy().view(np.uint64), keys[:n][order]), (kw, hash, p, n, with_vals)
                 assert bool((ok[n:] == SENT_K).all()), "wrote behind the key output"
                 if with_vals:
-                    assert np.array_equal(ov[:n].cpu().numpy().view(np.uint32), vals[:n][order]), (hash, p, n)
+                    assert np.array_equal(ov[:n].cpu().numpy().view(np.uint32), vals[:n][order]), (kw, hash, p, n)
                     assert bool((ov[n:] == SENT_V).all()), "wrote behind the value output"
                 else:
                     assert bool((ov == SENT_V).all())
-            st, ok, ov, counts = permute(hash, p, dk, None, n, count_only=True)
-            assert st == K.KH_OK and counts == exp_counts, (hash, p, n)
+            st, ok, ov, counts = permute(hash, p, dk, None, n, count_only=True, kw=kw)
+            assert st == K.KH_OK and counts == exp_counts, (kw, hash, p, n)
             assert bool((ok == SENT_K).all())
 
 
-def test_shard_permute_argument_checks(shard_input):
-    keys, vals, dk, dv = shard_input
+@pytest.mark.parametrize("kw", WIDTHS)
+def test_shard_permute_argument_checks(request, kw):
+    keys, vals, dk, dv = request.getfixturevalue("shard_input" if kw == 2 else "narrow_shard_input")
     for p in (0, 65):
         for n in (0, 5000):
-            assert permute("murmur3avx64", p, dk, dv, n)[0] == K.KH_ERR_INVALID
-    L = K.lib()
+            assert permute("murmur3avx64", p, dk, dv, n, kw=kw)[0] == K.KH_ERR_INVALID
+    fn = shard_fn(kw)
     counts = (C.c_uint64 * 4)()
     s = torch.cuda.current_stream().cuda_stream
     out = torch.empty((100, 2), dtype=torch.int64, device="cuda")
-    assert L.kh_wide_shard_permute(1, DIST_SEED, 4, dk.data_ptr(), None, 100, out.data_ptr(), None, None, 0, s) == K.KH_ERR_INVALID      # no counts
-    assert L.kh_wide_shard_permute(7, DIST_SEED, 4, dk.data_ptr(), None, 100, out.data_ptr(), None, counts, 0, s) == K.KH_ERR_INVALID    # no such hash
-    assert L.kh_wide_shard_permute(1, DIST_SEED, 4, None, None, 100, out.data_ptr(), None, counts, 0, s) == K.KH_ERR_INVALID             # null keys
-    assert L.kh_wide_shard_permute(1, DIST_SEED, 4, dk.data_ptr(), dv.data_ptr(), 100, out.data_ptr(), None, counts, 0, s) == K.KH_ERR_INVALID   # values without room
-    assert L.kh_wide_shard_permute(1, DIST_SEED, 4, None, None, 0, None, None, counts, 0, s) == K.KH_OK and list(counts) == [0, 0, 0, 0]
-    # keys and the key output are accessed 16 bytes at a time: a pointer 8 bytes off is refused, not dereferenced
-    assert L.kh_wide_shard_permute(1, DIST_SEED, 4, dk.data_ptr() + 8, None, 100, out.data_ptr(), None, counts, 0, s) == K.KH_ERR_INVALID
-    assert L.kh_wide_shard_permute(1, DIST_SEED, 4, dk.data_ptr(), None, 50, out.data_ptr() + 8, None, counts, 0, s) == K.KH_ERR_INVALID
-    assert L.kh_wide_shard_permute(1, DIST_SEED, 4, dk.data_ptr() + 16, None, 99, out.data_ptr() + 16, None, counts, 0, s) == K.KH_OK
+    assert fn(1, DIST_SEED, 4, dk.data_ptr(), None, 100, out.data_ptr(), None, None, 0, s) == K.KH_ERR_INVALID      # no counts
+    assert fn(7, DIST_SEED, 4, dk.data_ptr(), None, 100, out.data_ptr(), None, counts, 0, s) == K.KH_ERR_INVALID    # no such hash
+    assert fn(1, DIST_SEED, 4, None, None, 100, out.data_ptr(), None, counts, 0, s) == K.KH_ERR_INVALID             # null keys
+    assert fn(1, DIST_SEED, 4, dk.data_ptr(), dv.data_ptr(), 100, out.data_ptr(), None, counts, 0, s) == K.KH_ERR_INVALID   # values without room
+    assert fn(1, DIST_SEED, 4, None, None, 0, None, None, counts, 0, s) == K.KH_OK and list(counts) == [0, 0, 0, 0]
+    # 16-byte keys and their output are accessed 16 bytes at a time: a pointer 8 bytes off is refused, not dereferenced; 8-byte keys
+    # have no such requirement
+    off8 = K.KH_ERR_INVALID if kw == 2 else K.KH_OK
+    assert fn(1, DIST_SEED, 4, dk.data_ptr() + 8, None, 100, out.data_ptr(), None, counts, 0, s) == off8
+    assert fn(1, DIST_SEED, 4, dk.data_ptr(), None, 50, out.data_ptr() + 8, None, counts, 0, s) == off8
+    assert fn(1, DIST_SEED, 4, dk.data_ptr() + 16, None, 99, out.data_ptr() + 16, None, counts, 0, s) == K.KH_OK
 
 
 def test_backend_shard_is_the_c_call(shard_input):
