@@ -127,6 +127,16 @@ kh_status kh_insert_begin(kh_table* t, uint64_t n_total, int reduce_plus);
  *      unchanged, and the caller repeats begin (without the flag) / feed / end.  (The multi-GPU layer keeps its receive buffers.) */
 #define KH_INS_REDUCE_PLUS 1u
 #define KH_INS_REPEATABLE 2u
+/* kh_insert_reduce semantics for the streamed form: a 2-bit field (bits 2-3) that holds the kh_reduce_op next to KH_INS_REDUCE_PLUS,
+ *      which switches the reducer on.  KH_INS_REDUCE(op) builds the flags of any operation; KH_INS_REDUCE(KH_REDUCE_PLUS) is
+ *      KH_INS_REDUCE_PLUS itself.  An operation field without KH_INS_REDUCE_PLUS is an unknown combination: KH_ERR_INVALID.  Feeds of a
+ *      min / max / or insert need values (vals == NULL: KH_ERR_INVALID); KH_INS_REPEATABLE and kh_insert_abort keep their promises. */
+#define KH_INS_REDUCE_OP_SHIFT 2
+#define KH_INS_REDUCE_OP_MASK 12u
+#define KH_INS_REDUCE(op) (KH_INS_REDUCE_PLUS | ((unsigned)(op) << KH_INS_REDUCE_OP_SHIFT))
+#define KH_INS_REDUCE_MIN KH_INS_REDUCE(1)
+#define KH_INS_REDUCE_MAX KH_INS_REDUCE(2)
+#define KH_INS_REDUCE_OR KH_INS_REDUCE(3)
 kh_status kh_insert_begin_ex(kh_table* t, uint64_t n_total, unsigned flags);
 kh_status kh_insert_feed(kh_table* t, const void* keys /*[h|d] u64[n]*/, const void* vals /*[h|d] u32[n]*/, uint64_t n, kh_mem where);
 kh_status kh_insert_end(kh_table* t, uint64_t* n_inserted);
@@ -144,6 +154,17 @@ kh_status kh_insert_abort(kh_table* t);
  *      container sizes itself from a HyperLogLog estimate); capacity follows this table's doubling rule. */
 kh_status kh_insert_reduce_plus(kh_table* t, const void* keys /*[h|d] u64[n]*/, const void* vals /*[h|d] u32[n] or NULL*/,
                                 uint64_t n, kh_mem where, uint64_t* n_inserted);
+/* ---- reducer insert with another Reducer: the reference's reduction maps call reduc(stored, incoming) for whatever functor they are
+ *      instantiated with ("plus, max, etc.", robinhood_offset_hashmap_ptr.hpp:85-98, 1563-1565, 3058-3075).  Values are unsigned 32-bit;
+ *      min and max compare them unsigned.  A key the table does not hold is inserted with the reduction of the values of all its
+ *      occurrences in the batch (no identity element is involved); a key it holds gets op(stored, that reduction).  The key set, size,
+ *      capacity and info bytes afterwards are exactly those of kh_insert_reduce_plus over the same keys: only the values differ.
+ *      KH_REDUCE_PLUS is kh_insert_reduce_plus (vals == NULL: every occurrence contributes 1); for the other operations vals == NULL is
+ *      KH_ERR_INVALID, and so is an unknown op.  min, max and or are commutative, associative and idempotent: the result does not
+ *      depend on scheduling.  (ReplaceReducer, last value wins, is kh_insert followed by kh_update.) */
+typedef enum { KH_REDUCE_PLUS = 0, KH_REDUCE_MIN = 1, KH_REDUCE_MAX = 2, KH_REDUCE_OR = 3 } kh_reduce_op;
+kh_status kh_insert_reduce(kh_table* t, const void* keys /*[h|d] u64[n]*/, const void* vals /*[h|d] u32[n]; NULL with KH_REDUCE_PLUS only*/,
+                           uint64_t n, kh_mem where, kh_reduce_op op, uint64_t* n_inserted);
 
 /* ---- count(Iter,Iter): 0/1 per query in query order  hashmap_robinhood.hpp:1111-1160 / hashmap_linearprobe.hpp:639-688
  *      (the reference returns vector<size_t>; one byte per query here) */
@@ -295,6 +316,9 @@ kh_status kh_wide_insert(kh_wtable* t, const void* keys /*[h|d] u64[2n]*/, const
                          uint64_t* n_inserted);
 kh_status kh_wide_insert_reduce_plus(kh_wtable* t, const void* keys /*[h|d] u64[2n]*/, const void* vals /*[h|d] u32[n] or NULL*/, uint64_t n,
                                      kh_mem where, uint64_t* n_inserted);
+/* kh_insert_reduce for 16-byte keys */
+kh_status kh_wide_insert_reduce(kh_wtable* t, const void* keys /*[h|d] u64[2n]*/, const void* vals /*[h|d] u32[n]; NULL with KH_REDUCE_PLUS only*/,
+                                uint64_t n, kh_mem where, kh_reduce_op op, uint64_t* n_inserted);
 kh_status kh_wide_count(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint8_t* out01 /*[h|d] u8[n]*/);
 kh_status kh_wide_find(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint32_t* out_vals /*[h|d] u32[n], untouched on miss*/,
                        uint8_t* out_found /*[h|d] u8[n]*/, uint64_t* n_found);
@@ -319,7 +343,7 @@ kh_status kh_wide_erase_values(kh_wtable* t, uint32_t lo, uint32_t hi, uint64_t*
  *      were fed (which also closes the streamed insert, nothing inserted) and feed / end without begin.  kh_wide_insert_abort drops the
  *      pieces and leaves the table untouched and usable; it synchronises the table's stream.  KH_INS_REPEATABLE is accepted and changes
  *      nothing: the wide partition is exact (count, scan, scatter), so A WIDE TABLE NEVER RETURNS KH_ERR_RETRY. */
-kh_status kh_wide_insert_begin_ex(kh_wtable* t, uint64_t n_total, unsigned flags /* KH_INS_REDUCE_PLUS | KH_INS_REPEATABLE */);
+kh_status kh_wide_insert_begin_ex(kh_wtable* t, uint64_t n_total, unsigned flags /* KH_INS_REDUCE_PLUS or KH_INS_REDUCE(op) | KH_INS_REPEATABLE */);
 kh_status kh_wide_insert_feed(kh_wtable* t, const void* keys /*[h|d] u64[2n]*/, const void* vals /*[h|d] u32[n] or NULL*/, uint64_t n,
                               kh_mem where);
 kh_status kh_wide_insert_end(kh_wtable* t, uint64_t* n_inserted);

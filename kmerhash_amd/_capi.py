@@ -7,6 +7,28 @@ from .build import LIB
 
 KH_OK, KH_ERR_INVALID, KH_ERR_NOMEM, KH_ERR_FULL, KH_ERR_PROBE_OVERFLOW, KH_ERR_HIP, KH_ERR_UNSUPPORTED, KH_ERR_RETRY = range(8)
 KH_INS_REDUCE_PLUS, KH_INS_REPEATABLE = 1, 2
+KH_REDUCE_PLUS, KH_REDUCE_MIN, KH_REDUCE_MAX, KH_REDUCE_OR = range(4)
+KH_INS_REDUCE_OP_SHIFT = 2
+REDUCE_OPS = {"plus": KH_REDUCE_PLUS, "min": KH_REDUCE_MIN, "max": KH_REDUCE_MAX, "or": KH_REDUCE_OR}
+
+
+def reduce_op(op):
+    """name of a Reducer -> kh_reduce_op; anything else is refused here, before any call into the library"""
+    if not isinstance(op, str) or op not in REDUCE_OPS:
+        raise ValueError("reduce operation must be one of 'plus', 'min', 'max', 'or', got %r" % (op,))
+    return REDUCE_OPS[op]
+
+
+def ins_flags(reduce_plus=False, repeatable=False, reduce=None):
+    """flags of kh_insert_begin_ex / kh_wide_insert_begin_ex: KH_INS_REDUCE(op) | KH_INS_REPEATABLE"""
+    flags = KH_INS_REPEATABLE if repeatable else 0
+    if reduce is not None:
+        op = reduce_op(reduce)
+        if reduce_plus and op != KH_REDUCE_PLUS:
+            raise ValueError("reduce_plus=True contradicts reduce=%r" % (reduce,))
+        return flags | KH_INS_REDUCE_PLUS | (op << KH_INS_REDUCE_OP_SHIFT)
+    return flags | (KH_INS_REDUCE_PLUS if reduce_plus else 0)
+
 KH_KIND_ROBINHOOD, KH_KIND_LINEARPROBE = 0, 1
 KH_HASH_IDENTITY, KH_HASH_MURMUR3_X86_128_LO64, KH_HASH_MURMUR3_X64_128_H0, KH_HASH_FARM64 = 0, 1, 2, 3
 KH_MEM_HOST, KH_MEM_DEVICE = 0, 1
@@ -35,6 +57,8 @@ SYMBOLS = [
     "kh_value_histogram", "kh_select_values", "kh_erase_values", "kh_wide_value_histogram", "kh_wide_select_values", "kh_wide_erase_values",
     # HyperLogLog over 16-byte keys and straight from text (k = 1..64)
     "kh_hll_update_wide", "kh_hll_update_from_sequence", "kh_hll_update_from_fastq",
+    # reducer inserts beyond std::plus (min, max, bit-or), both key widths
+    "kh_insert_reduce", "kh_wide_insert_reduce",
 ]
 
 _lib = None
@@ -88,6 +112,8 @@ def lib():
     L.kh_insert_one.argtypes = [vp, u64, u32, pu64]
     L.kh_update.argtypes = [vp, vp, vp, u64, i32, pu64]
     L.kh_insert_reduce_plus.argtypes = [vp, vp, vp, u64, i32, pu64]
+    L.kh_insert_reduce.argtypes = [vp, vp, vp, u64, i32, i32, pu64]
+    L.kh_wide_insert_reduce.argtypes = [vp, vp, vp, u64, i32, i32, pu64]
     L.kh_insert_begin.argtypes = [vp, u64, i32]
     L.kh_insert_begin_ex.argtypes = [vp, u64, u32]
     L.kh_shard_plan_create.argtypes = [C.POINTER(vp), i32, u64, i32, u32, u32, vp, u64, u32, pu64, pu64, i32, vp]

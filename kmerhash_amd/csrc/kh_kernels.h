@@ -1146,11 +1146,23 @@ __device__ __forceinline__ uint32_t kh_wave_max(uint32_t v) {
 #define KH_UPD_APPLIED 0x80000000u
 enum { KH_DEDUP_FIRST = 0, KH_DEDUP_LAST = 1, KH_DEDUP_PLUS = 2, KH_DEDUP_ERASE = 3 };     // (ERASE: k_build_fused<.., 3>, no fold)
 #define KH_DD_M 2048u            // records staged per de-dup round
+// The Reducer of a KH_DEDUP_PLUS pass (kh_reduce_op: 0 plus, 1 min, 2 max, 3 or; unsigned 32-bit values).  Kernel arguments carry it as
+// `rop` next to the mode; it is uniform over a launch.  The fold takes it as one of the modes below (kh_fold_mode).
+enum { KH_ROP_PLUS = 0, KH_ROP_MIN = 1, KH_ROP_MAX = 2, KH_ROP_OR = 3 };
+enum { KH_FOLD_MIN = 4, KH_FOLD_MAX = 5, KH_FOLD_OR = 6 };
+__device__ __forceinline__ int kh_fold_mode(int mode, int rop) { return (mode == KH_DEDUP_PLUS && rop != KH_ROP_PLUS) ? KH_FOLD_MIN - 1 + rop : mode; }
+__device__ __forceinline__ uint32_t kh_reduce(uint32_t stored, uint32_t incoming, int rop) {
+  return rop == KH_ROP_PLUS ? stored + incoming : rop == KH_ROP_MIN ? (incoming < stored ? incoming : stored)
+       : rop == KH_ROP_MAX ? (incoming > stored ? incoming : stored) : (stored | incoming);
+}
 
 // Folds the duplicates among the ns records staged in LDS (lk = keys, liv = idx<<32|val) into one representative per
 // distinct key: the record that claims the key's entry of the 32-bit index set (one ds_cmpst_b32); every other
 // occurrence merges its (idx|val) word into the representative's with one 64-bit LDS atomic -- min = first value wins
-// (the index is the high word), max = last value wins, add = std::plus on the value.  Returns the bit mask of this
+// (the index is the high word), max = last value wins, add = std::plus on the value (a carry may run into the index word, which no
+// reader of a std::plus fold uses as a position).  KH_FOLD_MIN / MAX / OR: one 32-bit LDS atomic on the value word alone (the low
+// word: little endian); the index word stays the representative's own.  `mode` is uniform over the launch: the chain of
+// comparisons below is a scalar branch, no lane takes another way than its neighbour.  Returns the bit mask of this
 // lane's records (x = it * KH_CHUNK_THREADS + tid) that are representatives.  ns <= KH_DD_M < KH_HS entries: the probe
 // always finds an empty entry.  Caller: set[] zeroed and records staged before (barrier), barrier after.
 __device__ __forceinline__ uint32_t kh_dd_fold(unsigned long long* lk, unsigned long long* liv, uint32_t* set, uint32_t ns, int mode, uint32_t xk = 0) {
@@ -1173,7 +1185,13 @@ __device__ __forceinline__ uint32_t kh_dd_fold(unsigned long long* lk, unsigned 
           const unsigned long long iv = liv[x];
           if (mode == KH_DEDUP_FIRST) atomicMin(&liv[rep], iv);
           else if (mode == KH_DEDUP_LAST) atomicMax(&liv[rep], iv);
-          else atomicAdd(&liv[rep], iv & 0xFFFFFFFFull);
+          else if (mode == KH_DEDUP_PLUS) atomicAdd(&liv[rep], iv & 0xFFFFFFFFull);
+          else {
+            uint32_t* const vw = reinterpret_cast<uint32_t*>(&liv[rep]);
+            if (mode == KH_FOLD_MIN) atomicMin(vw, (uint32_t)iv);
+            else if (mode == KH_FOLD_MAX) atomicMax(vw, (uint32_t)iv);
+            else atomicOr(vw, (uint32_t)iv);
+          }
           if (it < KH_DD_M / KH_CHUNK_THREADS) rep_of[it] = rep;
           break;
         }
@@ -1295,12 +1313,15 @@ struct KhDedupParams {
   // KH_DEDUP_PLUS into a non-empty table: the keys the table already holds are NOT increased by this kernel (the host may still
   // have to discard the attempt: a histogram-free partition that overflowed, a failing re-layout).  Their (slot index, sum) pairs
   // are listed from the END of the partition's output region downwards (nk[end - 1 - j] = slot, nv[end - 1 - j] = sum; new keys
-  // + existing keys <= records of the partition, so the two lists never meet); k_apply_plus adds them once the attempt stands
+  // + existing keys <= records of the partition, so the two lists never meet); k_apply_reduce adds them once the attempt stands
   uint32_t* cnt_upd;                                             // [nparts]; bit 31 (KH_UPD_APPLIED): this partition's sums are in the table already
   // != 0: nothing can discard this attempt before the table is re-laid out (exact partition offsets, no repeatable streamed insert):
   // a partition that needs ONE class (nearly all do) adds its sums right here, as part of its membership probes, and sets
   // KH_UPD_APPLIED; the list is written all the same -- it is what takes the sums back if the re-layout fails
   int plus_immediate;
+  // the Reducer (KH_ROP_*).  min / max / or cannot be taken back from the result: a list entry whose reduction has been applied
+  // (here, or by k_apply_reduce) holds the value the slot had BEFORE instead, and the roll-back stores it back
+  int rop;
   unsigned long long* max_idx_plus1;                             // max (first-occurrence index + 1) over new keys
   KhSlots T; KhSeed seed;
   // speculative fusion of the chunk-count step (empty table, one partition == one chunk of capacity count_cap):
@@ -1356,6 +1377,7 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS) void k_dedup(KhDedupParams P) {
   const KhSrcView V = REC8 ? kh_src_setup8(P.src, q) : kh_src_setup(P.src, q, s_ptr, s_cum);
   const uint32_t m = V.m;
   const uint64_t beg = P.src.merged_off[q];            // output list of this partition
+  const int rop = REC8 ? (int)KH_ROP_PLUS : P.rop;      // (8-byte records are a counting insert: std::plus, known at compile time)
   const bool plus_live = P.mode == KH_DEDUP_PLUS && !P.table_empty;
   const uint64_t end = plus_live ? P.src.merged_off[q + 1] : 0;      // (the list of existing keys grows down from here)
   const uint64_t mask = P.T.cap - 1;
@@ -1439,7 +1461,7 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS) void k_dedup(KhDedupParams P) {
         // ---- fold duplicates into their representative; rep_mask: which of this lane's records are representatives
         for (uint32_t s = tid; s < KH_HS; s += KH_CHUNK_THREADS) set[s] = 0;
         __syncthreads();
-        rep_mask = kh_dd_fold(lk, liv, set, ns, P.mode, P.seed.xk);
+        rep_mask = kh_dd_fold(lk, liv, set, ns, kh_fold_mode(P.mode, rop), P.seed.xk);
         __syncthreads();
         if (pos >= m) break;                       // stream exhausted: the representatives are this class's distinct keys
         // ---- compact the representatives to the front (set[] is free again: scratch), then continue with the stream
@@ -1481,8 +1503,11 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS) void k_dedup(KhDedupParams P) {
           }
           if (P.mode == KH_DEDUP_LAST) { if (at != KH_NONE) P.T.s[at].val = (uint32_t)iv; }   // kh_update's assign pass: store the LAST value
           else if (P.mode == KH_DEDUP_PLUS && at != KH_NONE) {
-            upd = true;                                                    // (slot, sum) listed for k_apply_plus ...
-            if (P.plus_immediate && R == 1) P.T.s[at].val = cur_val + (uint32_t)iv;      // ... or added at once (one lane per distinct key: no race)
+            upd = true;                                                    // (slot, sum) listed for k_apply_reduce ...
+            if (P.plus_immediate && R == 1) {                              // ... or added at once (one lane per distinct key: no race)
+              P.T.s[at].val = kh_reduce(cur_val, (uint32_t)iv, rop);
+              if (rop != KH_ROP_PLUS) iv = cur_val;                      // (not invertible: the entry keeps what the slot held)
+            }
           }
           else emit = at == KH_NONE;
         }
@@ -1539,8 +1564,11 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS) void k_dedup(KhDedupParams P) {
 // it (sign = +1), or loses it again (sign = -1: the re-layout that followed failed and the table must read as before).  Every slot
 // appears in at most one list entry (a key belongs to one partition and one class): no race.
 // sign +1 skips the partitions whose sums k_dedup added itself (KH_UPD_APPLIED); sign -1 takes back every listed sum.
-__global__ void k_apply_plus(KhSlot* __restrict__ slots, const uint64_t* __restrict__ merged_off, const uint32_t* __restrict__ cnt_upd,
-                             const uint64_t* __restrict__ nk, const uint32_t* __restrict__ nv, uint32_t nparts, int sign) {
+// rop != KH_ROP_PLUS (min, max, or): sign +1 stores op(stored, listed reduction) and leaves the PREVIOUS stored value in the list
+// entry it consumed -- as k_dedup does where it applied at once -- so that after the +1 pass every entry of every partition holds a
+// previous value; sign -1 stores those back.
+__global__ void k_apply_reduce(KhSlot* __restrict__ slots, const uint64_t* __restrict__ merged_off, const uint32_t* __restrict__ cnt_upd,
+                               const uint64_t* __restrict__ nk, uint32_t* __restrict__ nv, uint32_t nparts, int sign, int rop) {
   for (uint32_t q = blockIdx.x; q < nparts; q += gridDim.x) {
     const uint64_t end = merged_off[q + 1];
     const uint32_t cw = cnt_upd[q];
@@ -1549,7 +1577,9 @@ __global__ void k_apply_plus(KhSlot* __restrict__ slots, const uint64_t* __restr
     for (uint32_t j = threadIdx.x; j < c; j += blockDim.x) {
       const uint64_t at = nk[end - 1 - j];
       const uint32_t d = nv[end - 1 - j];
-      slots[at].val += sign > 0 ? d : (0u - d);
+      if (rop == KH_ROP_PLUS) slots[at].val += sign > 0 ? d : (0u - d);
+      else if (sign > 0) { const uint32_t old = slots[at].val; slots[at].val = kh_reduce(old, d, rop); nv[end - 1 - j] = old; }
+      else slots[at].val = d;
     }
   }
 }
@@ -3773,7 +3803,7 @@ __global__ __launch_bounds__(256) void k_fastq_mask(const uint8_t* __restrict__ 
 // (hashmap_robinhood.hpp:522-624), backward-shift erase (:1294-1356), linear-probe insert into the first deleted slot of
 // the probe path or the first empty one (hashmap_linearprobe.hpp:430-513).  The host takes this path only when no call of
 // the batch can trigger a doubling (size + n <= max_load), so the serial semantics (first value wins, update overwrites,
-// std::plus adds) are exactly the reference's.  The Robin Hood info array stays canonical: it is the reference's own
+// std::plus adds, any other Reducer is applied as reduc(stored, incoming)) are exactly the reference's.  The Robin Hood info array stays canonical: it is the reference's own
 // algorithm.  A displacement chain that would push an element past distance 127 is detected by a read-only dry run of
 // the chain BEFORE the key is applied: the key and the rest of the batch are left to the general path (out[1] = keys done).
 // ---------------------------------------------------------------------------------------------
@@ -3781,7 +3811,7 @@ enum { KH_SMALL_FIRST = 0, KH_SMALL_UPDATE = 1, KH_SMALL_PLUS = 2, KH_SMALL_ERAS
 template <int KIND, int HASH>
 __global__ void k_small_batch(KhSlots T, const char* __restrict__ kbase, uint32_t kstride, const char* __restrict__ vbase, uint32_t vstride,
                               uint32_t vconst, uint32_t n, int op, KhSeed seed, unsigned long long* __restrict__ out /* [0] new/erased, [1] keys done */,
-                              uint32_t* __restrict__ flags) {
+                              uint32_t* __restrict__ flags, int rop = KH_ROP_PLUS /* the Reducer of KH_SMALL_PLUS */) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   const uint64_t mask = T.cap - 1;
   KhSlot* const S = T.s;
@@ -3818,7 +3848,7 @@ __global__ void k_small_batch(KhSlots T, const char* __restrict__ kbase, uint32_
       }
       if (found) {
         if (op == KH_SMALL_UPDATE) S[p].val = val;
-        else if (op == KH_SMALL_PLUS) S[p].val += val;
+        else if (op == KH_SMALL_PLUS) S[p].val = kh_reduce(S[p].val, val, rop);
         continue;
       }
       if (reprobe > 0xFFu) break;                         // would sit past distance 127: general path decides
@@ -3861,7 +3891,7 @@ __global__ void k_small_batch(KhSlots T, const char* __restrict__ kbase, uint32_
       }
       if (found) {
         if (op == KH_SMALL_UPDATE) S[p].val = val;
-        else if (op == KH_SMALL_PLUS) S[p].val += val;
+        else if (op == KH_SMALL_PLUS) S[p].val = kh_reduce(S[p].val, val, rop);
         continue;
       }
       if (ins == KH_NONE) { atomicOr(&flags[KH_FLAG_INTERNAL], 1u); break; }     // full table: cannot happen below max_load

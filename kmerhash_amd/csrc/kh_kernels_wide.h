@@ -130,7 +130,8 @@ __global__ __launch_bounds__(KW_PART_THREADS) void kw_part_scatter(const uint64_
 // 10^6 times stays ONE entry.  Only when a partition holds more than KW_DM - KW_DD_THREADS distinct keys are they split into R classes
 // by a second hash and the records are swept once per class.  The distinct keys are then tested against the current table (the only
 // random HBM probes) and listed: new keys at off[q] + j (nk/nv); with std::plus, the (slot, sum) pairs of keys the table already holds
-// at off[q] + j (us/uv), added by kw_apply_plus once nothing can discard the attempt.
+// at off[q] + j (us/uv), added by kw_apply_reduce once nothing can discard the attempt.  Any other Reducer (rop: min, max, or) folds with
+// one 32-bit LDS atomic on the value word of idx|val and is listed the same way.
 // LDS: 3 x 8 B x KW_DM staging + 4 B x KW_HS set = 64 KB + a few words: two 512-lane workgroups per CU (4 waves per SIMD).
 // ---------------------------------------------------------------------------------------------
 #define KW_DD_THREADS 512
@@ -139,6 +140,7 @@ __global__ __launch_bounds__(KW_PART_THREADS) void kw_part_scatter(const uint64_
 struct KwDedupParams {
   const KwRec* rec; const uint64_t* off;       // partition q = rec[off[q], off[q+1])
   KwSlots T; uint64_t seed; int table_empty; int mode;      // KH_DEDUP_FIRST / KH_DEDUP_PLUS
+  int rop;                                                   // KH_DEDUP_PLUS: the Reducer (KH_ROP_*)
   uint64_t* nk; uint32_t* nv; uint32_t* cnt_new;            // new distinct keys (2 words each) + value
   uint64_t* us; uint32_t* uv; uint32_t* cnt_upd;            // std::plus: existing keys' slot + sum
   unsigned long long* max_idx_plus1;
@@ -155,6 +157,7 @@ __global__ __launch_bounds__(KW_DD_THREADS) void kw_dedup(KwDedupParams P) {
   const uint32_t m = (uint32_t)(P.off[q + 1] - beg);
   const KwRec* R0 = P.rec + beg;
   const uint64_t mask = P.T.cap - 1;
+  const int fold = kh_fold_mode(P.mode, P.rop);      // (uniform over the launch: the fold below branches on a scalar)
   if (m == 0) { if (tid == 0) { P.cnt_new[q] = 0; if (P.cnt_upd) P.cnt_upd[q] = 0; } return; }
   for (uint32_t R = 1;; R *= 2) {
     if (tid == 0) { s_out = 0; s_upd = 0; s_max = 0; }
@@ -183,8 +186,14 @@ __global__ __launch_bounds__(KW_DD_THREADS) void kw_dedup(KwDedupParams P) {
             if (cur == 0) { rep = true; myslot = slot; break; }
             const uint32_t o = cur - 1u;
             if (l0[o] == rr.w0 && l1[o] == rr.w1) {
-              if (P.mode == KH_DEDUP_PLUS) atomicAdd((unsigned long long*)&liv[o], (unsigned long long)(rr.iv & 0xFFFFFFFFull));
-              else atomicMin((unsigned long long*)&liv[o], (unsigned long long)rr.iv);
+              if (fold == KH_DEDUP_PLUS) atomicAdd((unsigned long long*)&liv[o], (unsigned long long)(rr.iv & 0xFFFFFFFFull));
+              else if (fold == KH_DEDUP_FIRST) atomicMin((unsigned long long*)&liv[o], (unsigned long long)rr.iv);
+              else {       // value word alone (low word, little endian); the index word stays the representative's
+                uint32_t* const vw = reinterpret_cast<uint32_t*>(&liv[o]);
+                if (fold == KH_FOLD_MIN) atomicMin(vw, (uint32_t)rr.iv);
+                else if (fold == KH_FOLD_MAX) atomicMax(vw, (uint32_t)rr.iv);
+                else atomicOr(vw, (uint32_t)rr.iv);
+              }
               break;
             }
             slot = (slot + 1) & (KW_HS - 1);
@@ -240,15 +249,20 @@ __global__ __launch_bounds__(KW_DD_THREADS) void kw_dedup(KwDedupParams P) {
     if (s_out && P.mode == KH_DEDUP_FIRST) atomicMax(P.max_idx_plus1, (unsigned long long)s_max);
   }
 }
-// std::plus into keys the table already holds: sign +1 adds the listed sums, -1 takes them back (the re-layout that followed failed)
-__global__ void kw_apply_plus(KwSlot* __restrict__ slots, const uint64_t* __restrict__ off, const uint32_t* __restrict__ cnt_upd,
-                              const uint64_t* __restrict__ us, const uint32_t* __restrict__ uv, uint32_t nparts, int sign) {
+// the Reducer applied to keys the table already holds.  std::plus: sign +1 adds the listed sums, -1 takes them back (the re-layout that
+// followed failed).  min / max / or cannot be taken back from the result: sign +1 stores op(stored, listed reduction) and leaves the
+// PREVIOUS stored value in the list entry it consumed; sign -1 stores those back.  Every slot is in at most one entry: no race.
+__global__ void kw_apply_reduce(KwSlot* __restrict__ slots, const uint64_t* __restrict__ off, const uint32_t* __restrict__ cnt_upd,
+                                const uint64_t* __restrict__ us, uint32_t* __restrict__ uv, uint32_t nparts, int sign, int rop) {
   for (uint32_t q = blockIdx.x; q < nparts; q += gridDim.x) {
     const uint64_t b = off[q];
     const uint32_t c = cnt_upd[q];
     for (uint32_t j = threadIdx.x; j < c; j += blockDim.x) {
       const uint32_t d = uv[b + j];
-      slots[us[b + j]].val += sign > 0 ? d : (0u - d);
+      const uint64_t at = us[b + j];
+      if (rop == KH_ROP_PLUS) slots[at].val += sign > 0 ? d : (0u - d);
+      else if (sign > 0) { const uint32_t old = slots[at].val; slots[at].val = kh_reduce(old, d, rop); uv[b + j] = old; }
+      else slots[at].val = d;
     }
   }
 }

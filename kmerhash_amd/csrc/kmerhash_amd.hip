@@ -746,7 +746,25 @@ uint64_t capacity_after(const kh_table* t, uint64_t cap, uint64_t lsize, uint64_
   return c;
 }
 
-enum { INS_FIRST = 0, INS_UPDATE = 1, INS_PLUS = 2 };
+// INS_PLUS .. INS_OR: the reducer inserts, INS_PLUS + kh_reduce_op.  Everything structural (which keys are new, capacity rule, list
+// sizing, record kinds) asks is_reduce(); what only std::plus can do (a constant value of 1, the speculative one-launch forms) asks
+// mode == INS_PLUS.
+enum { INS_FIRST = 0, INS_UPDATE = 1, INS_PLUS = 2, INS_MIN = 3, INS_MAX = 4, INS_OR = 5 };
+inline bool is_reduce(int mode) { return mode >= INS_PLUS; }
+inline int reduce_op(int mode) { return is_reduce(mode) ? mode - INS_PLUS : 0; }      // KH_ROP_* == kh_reduce_op
+// the speculative one-launch forms (k_build_fused, k_build_lean, the fused insert into a loaded table, k_insert_stream) fold first-wins
+// or std::plus only: a min / max / or insert goes straight to the general path
+inline bool one_launch_mode(int mode) { return mode == INS_FIRST || mode == INS_UPDATE || mode == INS_PLUS; }
+inline const char* apply_label(int mode) { return mode == INS_PLUS ? "k_apply_plus" : "k_apply_reduce"; }
+static_assert(KH_REDUCE_MIN == KH_ROP_MIN && KH_REDUCE_MAX == KH_ROP_MAX && KH_REDUCE_OR == KH_ROP_OR && KH_REDUCE_PLUS == KH_ROP_PLUS, "kh_reduce_op is the kernels' rop");
+// flags of kh_insert_begin_ex / kh_wide_insert_begin_ex: the operation field (KH_INS_REDUCE(op)) counts only next to KH_INS_REDUCE_PLUS
+inline bool ins_flags_ok(unsigned flags) {
+  if (flags & ~(unsigned)(KH_INS_REDUCE_PLUS | KH_INS_REPEATABLE | KH_INS_REDUCE_OP_MASK)) return false;
+  return (flags & KH_INS_REDUCE_PLUS) || !(flags & KH_INS_REDUCE_OP_MASK);
+}
+inline int ins_flags_mode(unsigned flags) {
+  return (flags & KH_INS_REDUCE_PLUS) ? INS_PLUS + (int)((flags & KH_INS_REDUCE_OP_MASK) >> KH_INS_REDUCE_OP_SHIFT) : INS_FIRST;
+}
 // Pairs one internal pass takes.  A batch is the reference's SEQUENCE of insert() calls (one doubling decision per call), so cutting it
 // into consecutive passes changes nothing observable; what it bounds is the workspace -- ~58 B per pair of a pass: a k-mer counter's
 // file batch of 1.7e9 k-mers would otherwise ask for a 100 GB arena, whose hipMalloc alone costs 0.7 s (measured, scripts/kc_scale_probe.py).
@@ -766,7 +784,7 @@ inline bool fused_build_applies(const kh_table* t, uint64_t cap_u, uint32_t PB) 
   return t->lsize == 0 && cap_u >= 2 * (uint64_t)KH_L && t->max_lf <= 0.9f && PB == log2u(cap_u >> KH_LB) && !g_disable_fused;
 }
 inline bool nodup_build_applies(const kh_table* t, uint64_t cap_u, uint32_t PB, int mode) {
-  return fused_build_applies(t, cap_u, PB) && t->batch_nodup && mode != INS_UPDATE && !getenv("KH_DISABLE_NODUP");
+  return fused_build_applies(t, cap_u, PB) && t->batch_nodup && (mode == INS_FIRST || mode == INS_PLUS) && !getenv("KH_DISABLE_NODUP");
 }
 
 // core of insert/update for one batch of device-resident input (n < 2^32 - 16)
@@ -855,7 +873,7 @@ kh_status insert_finish(kh_table* t, KhSrcSet S, uint64_t n, uint32_t PB, uint64
   // (not for a batch whose sample says that a key comes E[m^2]/E[m] >= 2 times: the build speculates that every pair is a new key, its first 64
   //  chunks would vote it down -- 0.11 ms of launches for the reference benchmark's own input; a batch that is mostly distinct after all is
   //  merely built by the general path)
-  if (fused_build_applies(t, cap_u, PB) && S.rec12 != 2 && !(t->batch_vf >= 2.0)) {
+  if (fused_build_applies(t, cap_u, PB) && one_launch_mode(mode) && S.rec12 != 2 && !(t->batch_vf >= 2.0)) {
     const uint32_t nch = (uint32_t)(cap_u >> KH_LB);
     KhSlots nw;
     st = fresh_slots(t, cap_u, nw);
@@ -908,6 +926,7 @@ kh_status insert_finish(kh_table* t, KhSrcSet S, uint64_t n, uint32_t PB, uint64
   // next to the batch's records of the same chunk, folds them together (an element of the table beats every record), and
   // lays the chunk out -- no membership probes at random into HBM (k_dedup), no separate re-layout.  Speculates, like the
   // bulk build, that the capacity the reference's rule yields equals cap_u.
+  // (first-wins and std::plus only, like every one-launch form: one_launch_mode; spelled out here because kh_update has its own way)
   if (t->lsize > 0 && S.rec12 != 2 && (mode == INS_FIRST || mode == INS_PLUS) && !forced_cap && !g_disable_fused_rebuild &&
       t->cur.cap >= 2 * (uint64_t)KH_L && (cap_u == t->cur.cap || cap_u == 2 * t->cur.cap) && t->max_lf <= 0.9f &&
       PB == log2u(cap_u >> KH_LB) && t->lsize + n <= threshold(cap_u, 0.92f)) {
@@ -968,18 +987,21 @@ kh_status insert_finish(kh_table* t, KhSrcSet S, uint64_t n, uint32_t PB, uint64
     TAKE(pre.homecnt, uint16_t, cap_u); TAKE(pre.sumA, long long, R.nparts); TAKE(pre.sumN, long long, R.nparts);
   }
   D.count_cap = fuse ? cap_u : 0; D.PB = PB; D.homecnt = pre.homecnt; D.sumA = pre.sumA; D.sumN = pre.sumN;
-  D.T = narrow(t->cur); D.seed = t->seed; D.table_empty = t->lsize == 0 ? 1 : 0; D.mode = mode == INS_PLUS ? KH_DEDUP_PLUS : KH_DEDUP_FIRST; D.flags = flags;
+  D.T = narrow(t->cur); D.seed = t->seed; D.table_empty = t->lsize == 0 ? 1 : 0; D.mode = is_reduce(mode) ? KH_DEDUP_PLUS : KH_DEDUP_FIRST; D.flags = flags;
+  D.rop = reduce_op(mode);
   D.xcd_group = 0;
   // Reducer = std::plus into a non-empty table: k_dedup only LISTS the sums of the keys the table already holds; they are added
-  // (k_apply_plus) once nothing can discard this attempt any more -- a histogram-free partition that overflowed repeats the whole
+  // (k_apply_reduce) once nothing can discard this attempt any more -- a histogram-free partition that overflowed repeats the whole
   // batch, and a repeatable streamed insert promises "table unchanged" with KH_ERR_RETRY
-  const bool plus_live = mode == INS_PLUS && t->lsize > 0;
+  // (any Reducer; min / max / or are not taken back by a second pass with the sign turned but restored from the values the apply
+  //  step leaves in the list: k_apply_reduce)
+  const bool plus_live = is_reduce(mode) && t->lsize > 0;
   D.cnt_upd = nullptr;
   if (plus_live) TAKE(D.cnt_upd, uint32_t, R.nparts);
   // with exact partition offsets nothing can discard the attempt before the re-layout: the sums are added inside k_dedup (its
   // membership probes have the slot in hand) and the list only serves to take them back should the re-layout fail
   // ... and so they are behind a histogram-free partition once its overflow flag has been read clean: the partition is complete in stream
-  // order, so the flag is final -- one small copy + wait (tens of microseconds) instead of a k_apply_plus pass at random over the table
+  // order, so the flag is final -- one small copy + wait (tens of microseconds) instead of a k_apply_reduce pass at random over the table
   // (7 ms per 4.5e8-k-mer batch of the k-mer counter, measured)
   bool overflow_clean = t->part_overflow == nullptr;
   if (plus_live && !overflow_clean && !getenv("KH_DISABLE_PLUS_IMMEDIATE")) {
@@ -1012,13 +1034,13 @@ kh_status insert_finish(kh_table* t, KhSrcSet S, uint64_t n, uint32_t PB, uint64
   HIPCHK(hipStreamSynchronize(t->stream));
   if (t->part_overflow && (uint32_t)t->hpin[30]) return KH_RETRY_EXACT;
   const uint64_t dnew = t->hpin[0];
-  const uint64_t last_first = mode == INS_PLUS ? n - 1 : (t->hpin[1] ? t->hpin[1] - 1 : 0);
+  const uint64_t last_first = is_reduce(mode) ? n - 1 : (t->hpin[1] ? t->hpin[1] - 1 : 0);
   if (reinterpret_cast<const uint32_t*>(t->hpin + 2)[KH_FLAG_INTERNAL])
     return fail(t, KH_ERR_HIP, kDedupOverflowText);
   auto apply_plus = [&](int sign) {
-    Launch L(t, "k_apply_plus");
-    hipLaunchKernelGGL(k_apply_plus, dim3(std::min<uint32_t>(R.nparts, 4096u)), dim3(256), 0, t->stream, narrow(t->cur).s, S.merged_off, (const uint32_t*)D.cnt_upd,
-                       (const uint64_t*)D.nk, (const uint32_t*)D.nv, R.nparts, sign);
+    Launch L(t, apply_label(mode));
+    hipLaunchKernelGGL(k_apply_reduce, dim3(std::min<uint32_t>(R.nparts, 4096u)), dim3(256), 0, t->stream, narrow(t->cur).s, S.merged_off, (const uint32_t*)D.cnt_upd,
+                       (const uint64_t*)D.nk, D.nv, R.nparts, sign, D.rop);
   };
   if (plus_live) apply_plus(+1);
   const uint64_t new_cap = forced_cap ? forced_cap : capacity_after(t, t->cur.cap, t->lsize, n, dnew, last_first);
@@ -1092,14 +1114,14 @@ kh_status insert_device(kh_table* t, const char* kb, uint32_t kstride, const cha
 #define KH_SMALL_N 16
 const bool g_disable_small = getenv("KH_DISABLE_SMALL_BATCH") != nullptr;      // test hook
 kh_status small_batch(kh_table* t, const char* kb, uint32_t kstride, const char* vb, uint32_t vstride, uint32_t vconst, uint32_t n, int op,
-                      uint64_t* changed, uint32_t* done) {
+                      uint64_t* changed, uint32_t* done, int rop = KH_ROP_PLUS) {
   unsigned long long* out; uint32_t* flags;
   TAKE(out, unsigned long long, 2); TAKE(flags, uint32_t, KH_NFLAGS);
   HIPCHK(hipMemsetAsync(out, 0, 16, t->stream));
   HIPCHK(hipMemsetAsync(flags, 0, sizeof(uint32_t) * KH_NFLAGS, t->stream));
   { Launch L(t, "k_small_batch");
     KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_small_batch<KIND, HASH>), dim3(1), dim3(64), 0, t->stream, narrow(t->cur), kb, kstride, vb, vstride,
-                                                             vconst, n, op, t->seed, out, flags)); }
+                                                             vconst, n, op, t->seed, out, flags, rop)); }
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(t->hpin, out, 16, hipMemcpyDeviceToHost, t->stream));
   HIPCHK(hipMemcpyAsync(t->hpin + 2, flags, sizeof(uint32_t) * KH_NFLAGS, hipMemcpyDeviceToHost, t->stream));
@@ -1202,18 +1224,19 @@ kh_status insert_inplace(kh_table* t, const char* kb, uint32_t kstride, const ch
   D.src = S;
   D.nk = const_cast<uint64_t*>(src.in_k); D.nv = const_cast<uint32_t*>(src.in_v);
   D.cnt_new = cnt_new; D.count_cap = 0; D.PB = PB;
-  D.T = narrow(t->cur); D.seed = t->seed; D.table_empty = 0; D.mode = mode == INS_PLUS ? KH_DEDUP_PLUS : KH_DEDUP_FIRST;
+  D.T = narrow(t->cur); D.seed = t->seed; D.table_empty = 0; D.mode = is_reduce(mode) ? KH_DEDUP_PLUS : KH_DEDUP_FIRST;
+  D.rop = reduce_op(mode);
   char* zpre;                   // k_dedup's scalar and flag words
   TAKE(zpre, char, 64);
   HIPCHK(hipMemsetAsync(zpre, 0, 64, t->stream));
   D.max_idx_plus1 = reinterpret_cast<unsigned long long*>(zpre); D.flags = reinterpret_cast<uint32_t*>(zpre + 32);
-  if (mode == INS_PLUS) { TAKE(D.cnt_upd, uint32_t, R.nparts); D.plus_immediate = getenv("KH_DISABLE_PLUS_IMMEDIATE") ? 0 : 1; }      // (nothing discards an in-place batch)
+  if (is_reduce(mode)) { TAKE(D.cnt_upd, uint32_t, R.nparts); D.plus_immediate = getenv("KH_DISABLE_PLUS_IMMEDIATE") ? 0 : 1; }      // (nothing discards an in-place batch)
   { Launch L(t, "k_dedup");
     KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_dedup<KIND, HASH>), dim3(R.nparts), dim3(KH_CHUNK_THREADS), 0, t->stream, D)); }
-  if (mode == INS_PLUS) {      // sums of the keys the table already holds (listed by k_dedup; nothing can discard an in-place batch)
-    Launch L(t, "k_apply_plus");
-    hipLaunchKernelGGL(k_apply_plus, dim3(std::min<uint32_t>(R.nparts, 4096u)), dim3(256), 0, t->stream, narrow(t->cur).s, (const uint64_t*)R.part_off, (const uint32_t*)D.cnt_upd,
-                       (const uint64_t*)D.nk, (const uint32_t*)D.nv, R.nparts, 1);
+  if (is_reduce(mode)) {      // reductions of the keys the table already holds (listed by k_dedup; nothing can discard an in-place batch)
+    Launch L(t, apply_label(mode));
+    hipLaunchKernelGGL(k_apply_reduce, dim3(std::min<uint32_t>(R.nparts, 4096u)), dim3(256), 0, t->stream, narrow(t->cur).s, (const uint64_t*)R.part_off, (const uint32_t*)D.cnt_upd,
+                       (const uint64_t*)D.nk, D.nv, R.nparts, 1, D.rop);
   }
   IpResult* res = nullptr;
   st = inplace_passes<KH_IP_INSERT>(t, src, n, &res);
@@ -1242,6 +1265,7 @@ kh_status do_insert(kh_table* t, const void* keys, uint32_t kstride, const void*
                     kh_mem where, int mode, uint64_t* n_inserted, bool tail_reserve = true) {
   if (n_inserted) *n_inserted = 0;
   if (n && !keys) return fail(t, KH_ERR_INVALID, "null keys");
+  if (is_reduce(mode) && mode != INS_PLUS && !vals) return fail(t, KH_ERR_INVALID, "null values: only the std::plus reducer has a default value (1)");
   if (t->ins.active) return refuse_streaming(t);
   HIPCHK(hipSetDevice(t->device));
   { const uint64_t np_ = std::min<uint64_t>(n, g_max_pass);       // (pairs of one internal pass: insert_device)
@@ -1279,7 +1303,7 @@ kh_status do_insert(kh_table* t, const void* keys, uint32_t kstride, const void*
   if (n > 0 && n <= KH_SMALL_N && t->lsize > 0 && t->lsize + n <= t->max_load && !g_disable_small) {
     uint64_t ch = 0; uint32_t done = 0;
     st = small_batch(t, kb, kstride, vb, vstride, mode == INS_PLUS ? 1u : 0u, (uint32_t)n,
-                     mode == INS_UPDATE ? KH_SMALL_UPDATE : (mode == INS_PLUS ? KH_SMALL_PLUS : KH_SMALL_FIRST), &ch, &done);
+                     mode == INS_UPDATE ? KH_SMALL_UPDATE : (is_reduce(mode) ? KH_SMALL_PLUS : KH_SMALL_FIRST), &ch, &done, reduce_op(mode));
     if (st != KH_OK) return st;
     t->lsize += ch;
     total_new = ch;
@@ -1656,10 +1680,10 @@ kh_status kh_insert_begin(kh_table* t, uint64_t n_total, int reduce_plus) {
 kh_status kh_insert_begin_ex(kh_table* t, uint64_t n_total, unsigned flags) {
   if (!t) return KH_ERR_INVALID;
   if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is already in progress");
-  if (flags & ~(unsigned)(KH_INS_REDUCE_PLUS | KH_INS_REPEATABLE)) return fail(t, KH_ERR_INVALID, "unknown flag");
+  if (!ins_flags_ok(flags)) return fail(t, KH_ERR_INVALID, "unknown flag");
   HIPCHK(hipSetDevice(t->device));
   memset(&t->ins, 0, sizeof(t->ins));
-  t->ins.mode = (flags & KH_INS_REDUCE_PLUS) ? INS_PLUS : INS_FIRST;
+  t->ins.mode = ins_flags_mode(flags);
   t->ins.repeatable = (flags & KH_INS_REPEATABLE) != 0 && !g_disable_slack;
   t->ins.n_total = n_total;
   const uint64_t cu = capacity_after(t, t->cur.cap, t->lsize, n_total ? n_total : 1, n_total, n_total ? n_total - 1 : 0);
@@ -1685,6 +1709,7 @@ kh_status kh_insert_feed(kh_table* t, const void* keys, const void* vals, uint64
   if (!t->ins.active) return fail(t, KH_ERR_INVALID, "kh_insert_feed without kh_insert_begin");
   if (n == 0) return KH_OK;
   if (!keys) return fail(t, KH_ERR_INVALID, "null keys");
+  if (!vals && is_reduce(t->ins.mode) && t->ins.mode != INS_PLUS) return fail(t, KH_ERR_INVALID, "null values: only the std::plus reducer has a default value (1)");
   if (t->ins.fed + n > t->ins.n_total) return fail(t, KH_ERR_INVALID, "more pairs fed than announced to kh_insert_begin");
   HIPCHK(hipSetDevice(t->device));
   const uint64_t* dk; const uint32_t* dv;
@@ -1818,6 +1843,12 @@ kh_status kh_insert_abort(kh_table* t) {
 kh_status kh_insert_reduce_plus(kh_table* t, const void* keys, const void* vals, uint64_t n, kh_mem where, uint64_t* n_inserted) {
   if (!t) return KH_ERR_INVALID;
   return do_insert(t, keys, 8, vals, 4, n, where, INS_PLUS, n_inserted);
+}
+kh_status kh_insert_reduce(kh_table* t, const void* keys, const void* vals, uint64_t n, kh_mem where, kh_reduce_op op, uint64_t* n_inserted) {
+  if (!t) return KH_ERR_INVALID;
+  if (n_inserted) *n_inserted = 0;
+  if ((unsigned)op > (unsigned)KH_REDUCE_OR) return fail(t, KH_ERR_INVALID, "unknown reduce operation");
+  return do_insert(t, keys, 8, vals, 4, n, where, INS_PLUS + (int)op, n_inserted);
 }
 
 kh_status kh_count(kh_table* t, const void* keys, uint64_t n, kh_mem where, uint8_t* out01) {
@@ -2614,7 +2645,7 @@ kh_status kw_insert_core(kh_wtable* t, const KwSrc* src, uint32_t nsrc, uint64_t
   const uint32_t PB = cap_u > KH_L ? log2u(cap_u >> KH_LB) : 0u;
   if (PB > 22) return fail(t, KH_ERR_UNSUPPORTED, "batch would need more than 2^22 partitions");
   const uint32_t nparts = 1u << PB;
-  const bool plus = mode == INS_PLUS, plus_live = plus && t->lsize > 0;
+  const bool plus = is_reduce(mode), plus_live = plus && t->lsize > 0;      // (plus: any Reducer)
   uint32_t *cnt, *cnt_new, *cnt_upd = nullptr, *flags, *nv, *uv = nullptr; uint64_t *off, *noff, *nk, *us = nullptr;
   unsigned long long *cursor, *scal; KwRec* rec;
   if (precnt) cnt = precnt; else TAKE(cnt, uint32_t, nparts);
@@ -2636,13 +2667,13 @@ kh_status kw_insert_core(kh_wtable* t, const KwSrc* src, uint32_t nsrc, uint64_t
       if (src[s].n == 0) continue;
       Launch L(t, "kw_part_scatter");
       KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_part_scatter<HASH>), dim3(grid_for(src[s].n, KW_PART_THREADS, 4096)), dim3(KW_PART_THREADS), 0, t->stream,
-                                                 src[s].k, src[s].v, plus ? 1u : 0u, src[s].n, t->seed.s, PB, cursor, rec, (uint32_t)pos0));
+                                                 src[s].k, src[s].v, mode == INS_PLUS ? 1u : 0u, src[s].n, t->seed.s, PB, cursor, rec, (uint32_t)pos0));
       pos0 += src[s].n;
     } }
   KwDedupParams D;
   memset(&D, 0, sizeof(D));
   D.rec = rec; D.off = off; D.T = wide(t->cur); D.seed = t->seed.s; D.table_empty = t->lsize == 0 ? 1 : 0;
-  D.mode = plus ? KH_DEDUP_PLUS : KH_DEDUP_FIRST;
+  D.mode = plus ? KH_DEDUP_PLUS : KH_DEDUP_FIRST; D.rop = reduce_op(mode);
   D.nk = nk; D.nv = nv; D.cnt_new = cnt_new; D.us = us; D.uv = uv; D.cnt_upd = cnt_upd; D.max_idx_plus1 = scal; D.flags = flags;
   { Launch L(t, "kw_dedup");
     KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_dedup<HASH>), dim3(nparts), dim3(KW_DD_THREADS), 0, t->stream, D)); }
@@ -2657,9 +2688,9 @@ kh_status kw_insert_core(kh_wtable* t, const KwSrc* src, uint32_t nsrc, uint64_t
   const uint64_t dnew = t->hpin[0];
   const uint64_t last_first = plus ? n - 1 : (t->hpin[1] ? t->hpin[1] - 1 : 0);
   auto apply_plus = [&](int sign) {
-    Launch L(t, "kw_apply_plus");
-    hipLaunchKernelGGL(kw_apply_plus, dim3(std::min<uint32_t>(nparts, 4096u)), dim3(256), 0, t->stream, wide(t->cur).s, (const uint64_t*)off,
-                       (const uint32_t*)cnt_upd, (const uint64_t*)us, (const uint32_t*)uv, nparts, sign);
+    Launch L(t, mode == INS_PLUS ? "kw_apply_plus" : "kw_apply_reduce");
+    hipLaunchKernelGGL(kw_apply_reduce, dim3(std::min<uint32_t>(nparts, 4096u)), dim3(256), 0, t->stream, wide(t->cur).s, (const uint64_t*)off,
+                       (const uint32_t*)cnt_upd, (const uint64_t*)us, uv, nparts, sign, reduce_op(mode));
   };
   if (plus_live) apply_plus(+1);
   const uint64_t new_cap = forced_cap ? forced_cap : capacity_after(t, t->cur.cap, t->lsize, n, dnew, last_first);
@@ -2720,6 +2751,7 @@ kh_status kw_do_insert(kh_wtable* t, const void* keys, const void* vals, uint64_
   if (n_inserted) *n_inserted = 0;
   if (t->ins.active) return refuse_streaming(t);
   if (n && !keys) return fail(t, KH_ERR_INVALID, "null keys");
+  if (is_reduce(mode) && mode != INS_PLUS && !vals) return fail(t, KH_ERR_INVALID, "null values: only the std::plus reducer has a default value (1)");
   HIPCHK(hipSetDevice(t->device));
   const uint64_t np_ = std::min<uint64_t>(n, g_max_pass);
   { const uint64_t cu = capacity_after(t, t->cur.cap, t->lsize, np_ ? np_ : 1, np_, np_ ? np_ - 1 : 0);
@@ -2860,6 +2892,12 @@ kh_status kh_wide_insert_reduce_plus(kh_wtable* t, const void* keys, const void*
   if (!t) return KH_ERR_INVALID;
   return kw_do_insert(t, keys, vals, n, where, INS_PLUS, n_inserted);
 }
+kh_status kh_wide_insert_reduce(kh_wtable* t, const void* keys, const void* vals, uint64_t n, kh_mem where, kh_reduce_op op, uint64_t* n_inserted) {
+  if (!t) return KH_ERR_INVALID;
+  if (n_inserted) *n_inserted = 0;
+  if ((unsigned)op > (unsigned)KH_REDUCE_OR) return fail(t, KH_ERR_INVALID, "unknown reduce operation");
+  return kw_do_insert(t, keys, vals, n, where, INS_PLUS + (int)op, n_inserted);
+}
 kh_status kh_wide_count(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, uint8_t* out01) {
   if (!t) return KH_ERR_INVALID;
   if (n && !out01) return fail(t, KH_ERR_INVALID, "null argument");
@@ -2891,10 +2929,10 @@ kh_status kh_wide_erase(kh_wtable* t, const void* keys, uint64_t n, kh_mem where
 kh_status kh_wide_insert_begin_ex(kh_wtable* t, uint64_t n_total, unsigned flags) {
   if (!t) return KH_ERR_INVALID;
   if (t->ins.active) return fail(t, KH_ERR_INVALID, "a streamed insert is already in progress");
-  if (flags & ~(unsigned)(KH_INS_REDUCE_PLUS | KH_INS_REPEATABLE)) return fail(t, KH_ERR_INVALID, "unknown flag");
+  if (!ins_flags_ok(flags)) return fail(t, KH_ERR_INVALID, "unknown flag");
   HIPCHK(hipSetDevice(t->device));
   memset(&t->ins, 0, sizeof(t->ins));
-  t->ins.mode = (flags & KH_INS_REDUCE_PLUS) ? INS_PLUS : INS_FIRST;
+  t->ins.mode = ins_flags_mode(flags);
   t->ins.n_total = n_total;
   const uint64_t np_ = std::min<uint64_t>(n_total, g_max_pass);
   const uint64_t cu = capacity_after(t, t->cur.cap, t->lsize, np_ ? np_ : 1, np_, np_ ? np_ - 1 : 0);

@@ -222,6 +222,20 @@ class _TableCore:
         assert n.value == m, (n.value, m)
         return keys, vals
 
+    def merge(self, other, op="plus"):
+        """every (key, value) pair of `other` reduce-inserted into this table with `op` ("plus" | "min" | "max" | "or"): keys both
+        hold get op(mine, theirs), the rest are inserted.  The pairs go from table to table in device memory (select_values over the
+        whole value range, then insert_reduce); `other` is not changed.  Both tables must have the same key width.  Returns #new keys."""
+        K.reduce_op(op)
+        if not isinstance(other, _TableCore) or other.PREFIX != self.PREFIX:
+            raise ValueError("merge: the tables differ in key width")
+        keys, vals = other.select_values(0, 0xFFFFFFFF, device=True)
+        if vals.numel() == 0:
+            return 0
+        if keys.device.index != self.device:
+            keys, vals = keys.to("cuda:%d" % self.device), vals.to("cuda:%d" % self.device)
+        return self.insert_reduce(keys, vals, op)
+
     def erase_values(self, lo, hi):
         """erases every element with lo <= value <= hi; the table afterwards is the table after erase() of exactly those keys.
         Returns the number erased."""
@@ -281,10 +295,11 @@ class _HashMapBase(_TableCore):
         return out.value
 
     # -- streamed insert: one insert whose pairs arrive in pieces (multi-GPU exchange) ----------------------------
-    def insert_begin(self, n_total, reduce_plus=False, repeatable=False):
+    def insert_begin(self, n_total, reduce_plus=False, repeatable=False, reduce=None):
         """repeatable: the caller keeps every piece until insert_end has returned and feeds them again (without this flag) if
-        insert_end raises KhRetry -- allows the histogram-free partition of the pieces (kh_insert_begin_ex)"""
-        flags = (K.KH_INS_REDUCE_PLUS if reduce_plus else 0) | (K.KH_INS_REPEATABLE if repeatable else 0)
+        insert_end raises KhRetry -- allows the histogram-free partition of the pieces (kh_insert_begin_ex).
+        reduce: "plus" | "min" | "max" | "or" -- the streamed form of insert_reduce (reduce_plus=True is reduce="plus")"""
+        flags = K.ins_flags(reduce_plus, repeatable, reduce)
         self._chk(self._L.kh_insert_begin_ex(self._h, int(n_total), flags))
 
     def insert_feed(self, keys, vals=None):
@@ -315,6 +330,22 @@ class _HashMapBase(_TableCore):
         self._sync_stream(kb, vb)
         out = C.c_uint64()
         self._chk(self._L.kh_insert_reduce_plus(self._h, kb.ptr, vb.ptr if vb is not None else None, kb.n, kb.where, C.byref(out)))
+        return out.value
+
+    def insert_reduce(self, keys, vals=None, op="plus"):
+        """reducer insert with Reducer `op`: "plus" (== insert_reduce_plus), "min", "max" (unsigned) or "or" on the 32-bit values.  A new
+        key gets the reduction of the values of its occurrences, a key the table holds op(stored, that reduction).  vals may be None
+        for "plus" only.  Returns #new keys."""
+        rop = K.reduce_op(op)
+        if vals is None and rop != K.KH_REDUCE_PLUS:
+            raise ValueError("insert_reduce(op=%r) needs values: only 'plus' has a default (1 per occurrence)" % (op,))
+        kb = _Buf(keys, np.uint64, 8)
+        vb = _Buf(vals, np.uint32, 4) if vals is not None else None
+        if vb is not None and (kb.n != vb.n or kb.where != vb.where):
+            raise ValueError("keys/vals must have equal length and live in the same memory space")
+        self._sync_stream(kb, vb)
+        out = C.c_uint64()
+        self._chk(self._L.kh_insert_reduce(self._h, kb.ptr, vb.ptr if vb is not None else None, kb.n, kb.where, rop, C.byref(out)))
         return out.value
 
     def count(self, keys, out=None):

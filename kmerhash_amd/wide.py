@@ -54,6 +54,14 @@ class hashmap_robinhood_doubling_wide(_TableCore):
         """Reducer = std::plus (wrapping 32-bit); vals None: every occurrence counts 1"""
         return self._insert(self._L.kh_wide_insert_reduce_plus, keys, vals)
 
+    def insert_reduce(self, keys, vals=None, op="plus"):
+        """reducer insert with Reducer `op`: "plus" (== insert_reduce_plus), "min", "max" (unsigned) or "or"; vals may be None for
+        "plus" only"""
+        rop = K.reduce_op(op)
+        if vals is None and rop != K.KH_REDUCE_PLUS:
+            raise ValueError("insert_reduce(op=%r) needs values: only 'plus' has a default (1 per occurrence)" % (op,))
+        return self._insert(lambda h, k, v, n, where, out: self._L.kh_wide_insert_reduce(h, k, v, n, where, rop, out), keys, vals)
+
     def count(self, keys):
         kb = _keys(keys)
         self._sync_stream(kb)
@@ -121,9 +129,10 @@ class hashmap_robinhood_doubling_wide_stream(hashmap_robinhood_doubling_wide):
         super().__init__(*args, **kwargs)
         self._fed = []          # device pieces of the streamed insert in progress
 
-    def insert_begin(self, n_total, reduce_plus=False, repeatable=False):
-        """repeatable is accepted for the interface of the 64-bit table; a wide table never raises KhRetry"""
-        flags = (K.KH_INS_REDUCE_PLUS if reduce_plus else 0) | (K.KH_INS_REPEATABLE if repeatable else 0)
+    def insert_begin(self, n_total, reduce_plus=False, repeatable=False, reduce=None):
+        """repeatable is accepted for the interface of the 64-bit table; a wide table never raises KhRetry.
+        reduce: "plus" | "min" | "max" | "or" -- the streamed form of insert_reduce (reduce_plus=True is reduce="plus")"""
+        flags = K.ins_flags(reduce_plus, repeatable, reduce)
         self._chk(self._L.kh_wide_insert_begin_ex(self._h, int(n_total), flags))
         self._fed = []
 
