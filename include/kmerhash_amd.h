@@ -269,6 +269,59 @@ kh_status kh_kmers_from_sequence(const void* seq /*[h|d] u8[n]*/, uint64_t n, ui
 kh_status kh_kmers_from_fastq(const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, int canonical, kh_mem where,
                               uint64_t* out_kmers /*[h|d]*/, uint64_t* n_out, int device, void* hip_stream);
 
+/* the same k-mers, in the same order and with the same n_out, each with the byte offset of the first base of its window in the buffer
+ *      passed: out_pos[i] belongs to out_kmers[i] (for FASTQ an offset into the raw text, not into a read).  canonical != 0: the offset
+ *      is the window's; which strand the canonical form came from is not recorded (compare the window with its reverse complement).
+ *      Positions are 32-bit: n >= 2^32 is KH_ERR_INVALID before anything is allocated or read.  out_pos needs room for n entries. */
+kh_status kh_kmers_from_sequence_pos(const void* seq /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, int canonical, kh_mem where,
+                                     uint64_t* out_kmers /*[h|d]*/, uint32_t* out_pos /*[h|d]*/, uint64_t* n_out, int device, void* hip_stream);
+kh_status kh_kmers_from_fastq_pos(const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, int canonical, kh_mem where,
+                                  uint64_t* out_kmers /*[h|d]*/, uint32_t* out_pos /*[h|d]*/, uint64_t* n_out, int device, void* hip_stream);
+
+/* ---- k-mer position index: ALL occurrences per k-mer (the reference's driver offers PositionIndex<MapType> over a multimap next to
+ *      CountIndex, BenchmarkKmerIndex.cpp:342-449; the multimap is kmerind's and absent from the reference tree: the contract below is
+ *      this library's).  A STATIC index of 64-bit keys (k <= 32) on one GPU: built once from one batch of (key, position) pairs, then
+ *      queried.  State: one Robin Hood table owned by the index plus offsets u32[size + 1] and positions u32[total] in device memory.
+ *      After a build the table's value of a key is its RANK among the live slots in slot order (0..size-1) and positions[offsets[rank]
+ *      .. offsets[rank + 1]) are the positions of that key: a lookup reads one slot and two adjacent offsets words.
+ *      kh_index_build: the index must be empty (else KH_ERR_INVALID; kh_index_clear empties it); n >= 2^32: KH_ERR_INVALID before
+ *      anything is touched; n == 0: KH_OK, the index stays empty.  Afterwards key set, size, capacity, info bytes and slot order of the
+ *      table are those of a fresh Robin Hood table (capacity 128) with the same hash, seed (no key transform) and load factors after
+ *      kh_insert_reduce_plus(keys, NULL, n) -- except that the keys which share a HOME BUCKET, whose order among themselves that insert
+ *      leaves to scheduling, stand in ascending key order; offsets[0] = 0, offsets[size] = n.  THE POSITIONS OF ONE KEY ASCEND NUMERICALLY WHATEVER
+ *      THE ORDER OF THE INPUT PAIRS: the result is a function of the multiset of pairs, hash, seed and load factors only (two builds
+ *      export identical bytes).  Duplicate pairs are kept.  On any failure (KH_ERR_PROBE_OVERFLOW, a refused batch, KH_ERR_NOMEM, ...)
+ *      the index is left empty.  Device pairs must stay valid until the call returns; every call synchronises the index's stream.
+ *      kh_index_build_from_sequence / _from_fastq: kh_kmers_from_sequence_pos / _fastq_pos and the build, on device buffers (host text
+ *      is staged once; k-mers and positions never visit the host).
+ *      kh_index_export: keys in slot order (the order of kh_to_vector), offsets and positions, into host buffers (any may be NULL).
+ *      Appending to or erasing from a built index, 16-byte keys, the linear-probe layout and a strand bit are not supported. */
+typedef struct kh_index kh_index;
+kh_status kh_index_create(kh_index** out, kh_hash hash, uint64_t seed, float min_lf, float max_lf, int device);
+kh_status kh_index_destroy(kh_index* x);
+kh_status kh_index_set_stream(kh_index* x, void* hip_stream);
+const char* kh_index_last_error(const kh_index* x);
+kh_status kh_index_clear(kh_index* x);
+kh_status kh_index_build(kh_index* x, const void* keys /*[h|d] u64[n]*/, const void* pos /*[h|d] u32[n]*/, uint64_t n, kh_mem where);
+kh_status kh_index_build_from_sequence(kh_index* x, const void* seq /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, int canonical, kh_mem where);
+kh_status kh_index_build_from_fastq(kh_index* x, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, int canonical, kh_mem where);
+kh_status kh_index_size(const kh_index* x, uint64_t* distinct_keys);
+kh_status kh_index_total(const kh_index* x, uint64_t* n_positions);
+kh_status kh_index_capacity(const kh_index* x, uint64_t* buckets);
+kh_status kh_index_export(kh_index* x, uint64_t* keys_host /*[size]*/, uint32_t* offsets_host /*[size+1]*/, uint32_t* positions_host /*[total]*/);
+/* occurrences of every query key, 0 on a miss */
+kh_status kh_index_count(kh_index* x, const void* keys /*[h|d] u64[n]*/, uint64_t n, kh_mem where, uint32_t* out_counts /*[h|d] u32[n]*/);
+/* a CSR in query order: out_offsets = exclusive scan of the counts, out_offsets[n] = *n_out = the number of positions; the positions
+ *      of query i are out_pos[out_offsets[i] .. out_offsets[i + 1]), ascending; a repeated query key repeats its positions.
+ *      out_pos == NULL: out_offsets and *n_out only.  More positions than cap_out: KH_ERR_INVALID, *n_out set (out_offsets too),
+ *      nothing written to out_pos (the convention of kh_select_values). */
+kh_status kh_index_find(kh_index* x, const void* keys /*[h|d] u64[n]*/, uint64_t n, kh_mem where,
+                        uint64_t* out_offsets /*[h|d] u64[n+1]*/, uint32_t* out_pos /*[h|d] u32[cap_out] or NULL*/,
+                        uint64_t cap_out, uint64_t* n_out);
+/* per-kernel timing of the index's own table (kh_profile_enable / kh_profile_dump): the counting insert's kernels and k_index_* */
+kh_status kh_index_profile_enable(kh_index* x, int on);
+kh_status kh_index_profile_dump(kh_index* x, char* buf, uint64_t cap);
+
 /* ---- HyperLogLog cardinality estimator: fsc::hyperloglog64<T, Hash, precision> (hyperloglog64.hpp:142-475),
  *      64-bit hash values: register = top `precision` bits after dropping `ignore_msb` bits, rank = leading zeros + 1
  *      (:175-188); estimate() = harmonic mean with the linear-counting branch below 5m/2 (:201-236).  Registers are

@@ -1,0 +1,420 @@
+// kh_kernels_index.h -- gfx950 device code of the k-mer position index (kh_index_* and kh_kmers_from_*_pos), included once by
+// kmerhash_amd.hip after kh_kernels_values.h.  Prefix ki_ / k_index_ (and k_kmers_emit_pos, the sibling of k_kmers_emit).
+//
+// The index is a Robin Hood table of 64-bit keys whose VALUE is the key's rank among the live slots in slot order, plus a CSR:
+// offsets u32[size + 1] and positions u32[total]; positions[offsets[r] .. offsets[r + 1]) are the occurrences of the key of rank r,
+// ascending.  Build: counting insert (unchanged code) -> k_index_canon_runs (keys of one home bucket in key order) -> k_index_rank
+// (slot-order rank, counts, rank into the slot) -> scan ->
+// k_index_scatter (probe + cursor atomic + 4-byte write per pair) -> k_index_tile_sort (bitonic sort of fixed tiles in LDS under the
+// composite key (segment in tile, position)) -> k_index_seg_radix (the segments that cross a tile boundary, one workgroup each).
+// Lookup: k_index_lookup (begin, count per query) -> scan -> k_index_gather (balanced over output elements).  Wave64 everywhere.
+#pragma once
+#include "kh_kernels_values.h"
+
+// ---------------------------------------------------------------------------------------------
+// k-mers with the byte offset of their window: k_kmers_emit plus a second staging array.  The offset of the window that starts at base
+// j of lane tid's word is tile0 + 16 tid + j; the tile-local part (< KH_KM_TILE) is staged as 16 bits next to the k-mer and both are
+// written coalesced.
+// ---------------------------------------------------------------------------------------------
+template <bool CANON>
+__global__ __launch_bounds__(KH_KM_THREADS) void k_kmers_emit_pos(const uint8_t* __restrict__ seq, uint64_t n, uint32_t k, const uint64_t* __restrict__ tile_off,
+                                                                  uint64_t* __restrict__ out, uint32_t* __restrict__ out_pos) {
+  typedef KhKm<1> M;
+  __shared__ uint32_t words[KH_KM_TILE / 16 + M::HALO];
+  __shared__ uint16_t invs[KH_KM_TILE / 16 + M::HALO];
+  __shared__ uint32_t wtot[KH_KM_THREADS / 64];
+  __shared__ uint64_t stage[KH_KM_TILE];
+  __shared__ uint16_t spos[KH_KM_TILE];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const uint64_t tile0 = (uint64_t)blockIdx.x * KH_KM_TILE;
+  kh_km_pack_tile<M::HALO>(seq, n, tile0, words, invs);
+  __syncthreads();
+  const M::Win W = M::window(words, invs, tid);
+  uint32_t vmask = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 16; ++j) vmask |= M::valid(W, j, k) ? (1u << j) : 0u;
+  const uint32_t mine = (uint32_t)__popc(vmask);
+  uint32_t incl = mine;
+  for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off, 64); if (lane >= (uint32_t)off) incl += o; }
+  if (lane == 63) wtot[wid] = incl;
+  __syncthreads();
+  uint32_t pos = incl - mine, total = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < KH_KM_THREADS / 64; ++w) { const uint32_t c = wtot[w]; if (w < wid) pos += c; total += c; }
+#pragma unroll
+  for (uint32_t j = 0; j < 16; ++j) {
+    if ((vmask >> j) & 1u) {
+      const uint64_t fw = M::forward(W, j, k);
+      uint64_t v = fw;
+      if (CANON) { const uint64_t rc = kh_revcomp(fw, k); v = fw < rc ? fw : rc; }
+      stage[pos] = v;
+      spos[pos] = (uint16_t)(16u * tid + j);
+      ++pos;
+    }
+  }
+  __syncthreads();
+  const uint64_t o = tile_off[blockIdx.x];
+  for (uint32_t i = tid; i < total; i += KH_KM_THREADS) { out[o + i] = stage[i]; out_pos[o + i] = (uint32_t)(tile0 + spos[i]); }
+}
+
+// ---------------------------------------------------------------------------------------------
+// canonical slot order.  A Robin Hood table keeps its elements sorted by home bucket, but the order of the keys that SHARE a home bucket
+// is whatever the insert made of it (in the reference: arrival order; in the counting insert here: the order LDS atomics gave, which
+// differs from run to run).  The index promises a result that depends on the multiset of pairs only, so every run of slots with one
+// home bucket is sorted by key, in place: the lane that owns the first slot of a run walks it (a run is shorter than 128 slots, nearly
+// always 1 or 2) and selection-sorts (key, value); the info bytes are positional and stay.  Runs are disjoint: no two lanes touch a slot.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool ki_in_run(const KhSlot* __restrict__ slots, uint64_t j, uint64_t mask, uint64_t home) {
+  const uint32_t b = slots[j].info & 0xFFu;
+  return b >= 0x80u && ((j - (b & 0x7Fu)) & mask) == home;
+}
+__global__ __launch_bounds__(256) void k_index_canon_runs(KhSlot* __restrict__ slots, uint64_t cap) {
+  const uint64_t mask = cap - 1, stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += stride) {
+    const uint32_t b = slots[i].info & 0xFFu;
+    if (b < 0x80u) continue;
+    const uint64_t home = (i - (b & 0x7Fu)) & mask;
+    if (ki_in_run(slots, (i - 1) & mask, mask, home)) continue;          // not the first slot of its run
+    uint32_t len = 1;
+    while (len < 128u && len < cap && ki_in_run(slots, (i + len) & mask, mask, home)) ++len;
+    for (uint32_t a = 0; a + 1 < len; ++a) {
+      KhSlot* sa = slots + ((i + a) & mask);
+      uint64_t kmin = sa->key; uint32_t at = a;
+      for (uint32_t c = a + 1; c < len; ++c) { const uint64_t kc = slots[(i + c) & mask].key; if (kc < kmin) { kmin = kc; at = c; } }
+      if (at != a) {
+        KhSlot* sm = slots + ((i + at) & mask);
+        const uint64_t ka = sa->key; const uint32_t va = sa->val, vm = sm->val;
+        sa->key = kmin; sa->val = vm; sm->key = ka; sm->val = va;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// rank pass over a Robin Hood table after the counting insert, on the tiling of k_values_tile_count / k_values_tile_emit (the tile
+// sums come from k_values_tile_count<KV_RH> over the full value range): live slot -> rank r in slot order; counts[r] = the slot's
+// value (the occurrences of its key), and the value becomes r.  Every slot belongs to one lane: plain stores.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(KV_SEL_THREADS) void k_index_rank(KhSlot* __restrict__ slots, uint64_t cap, const uint64_t* __restrict__ tile_off,
+                                                               uint32_t* __restrict__ counts) {
+  __shared__ uint32_t wcnt[KV_SEL_ROWS * (KV_SEL_THREADS / 64)];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const uint64_t tbase = (uint64_t)blockIdx.x * KV_SEL_TILE;
+  KvItem it[KV_SEL_ROWS];
+#pragma unroll
+  for (int j = 0; j < KV_SEL_ROWS; ++j) {
+    const uint64_t i = tbase + (uint64_t)j * KV_SEL_THREADS + tid;
+    it[j] = kv_ld<KV_RH>(slots, i < cap ? i : cap - 1);
+  }
+  uint32_t hit = 0, rank[KV_SEL_ROWS];
+#pragma unroll
+  for (int j = 0; j < KV_SEL_ROWS; ++j) {
+    const uint64_t i = tbase + (uint64_t)j * KV_SEL_THREADS + tid;
+    const bool m = i < cap && kv_live<KV_RH>(it[j].info);
+    const unsigned long long b = __ballot(m);
+    rank[j] = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) wcnt[j * (KV_SEL_THREADS / 64) + wid] = (uint32_t)__popcll(b);
+    hit |= m ? (1u << j) : 0u;
+  }
+  __syncthreads();
+  const uint64_t obase = tile_off[blockIdx.x];
+  uint32_t acc = 0;
+#pragma unroll
+  for (int j = 0; j < KV_SEL_ROWS; ++j) {
+    uint32_t pre = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < KV_SEL_THREADS / 64; ++w) { if (w == wid) pre = acc; acc += wcnt[j * (KV_SEL_THREADS / 64) + w]; }
+    if ((hit >> j) & 1u) {
+      const uint64_t i = tbase + (uint64_t)j * KV_SEL_THREADS + tid;
+      const uint32_t r = (uint32_t)(obase + pre + rank[j]);
+      counts[r] = it[j].val;
+      slots[i].val = r;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// exclusive scan of n u32 counts into n + 1 offsets (u32: the CSR of the index; u64: the CSR of a query batch, whose total may pass
+// 2^32), over any number of workgroups: tile sums (u64), one workgroup scans them in place, every tile scans itself again on top.
+// ---------------------------------------------------------------------------------------------
+#define KI_SCAN_THREADS 256
+#define KI_SCAN_ITEMS 8
+#define KI_SCAN_TILE (KI_SCAN_THREADS * KI_SCAN_ITEMS)
+__device__ __forceinline__ unsigned long long ki_wave_incl(unsigned long long x, uint32_t lane) {
+  for (int off = 1; off < 64; off <<= 1) { const unsigned long long o = __shfl_up(x, off, 64); if (lane >= (uint32_t)off) x += o; }
+  return x;
+}
+__global__ __launch_bounds__(KI_SCAN_THREADS) void k_index_tile_sums(const uint32_t* __restrict__ in, uint64_t n, unsigned long long* __restrict__ sums) {
+  __shared__ unsigned long long wsum[KI_SCAN_THREADS / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint64_t i0 = (uint64_t)blockIdx.x * KI_SCAN_TILE + (uint64_t)tid * KI_SCAN_ITEMS;
+  unsigned long long c = 0;
+#pragma unroll
+  for (int j = 0; j < KI_SCAN_ITEMS; ++j) c += i0 + j < n ? in[i0 + j] : 0u;
+  c = ki_wave_incl(c, lane);
+  if (lane == 63) wsum[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) { unsigned long long t = 0; for (uint32_t w = 0; w < KI_SCAN_THREADS / 64; ++w) t += wsum[w]; sums[blockIdx.x] = t; }
+}
+#define KI_SUMS_THREADS 512
+// in place: sums[i] = sum of the entries before i, sums[nt] = the total
+__global__ __launch_bounds__(KI_SUMS_THREADS) void k_index_scan_sums(unsigned long long* __restrict__ sums, uint64_t nt) {
+  __shared__ unsigned long long wsum[KI_SUMS_THREADS / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  unsigned long long carry = 0;                                 // (workgroup-uniform)
+  for (uint64_t base = 0; base < nt; base += KI_SUMS_THREADS) {
+    const uint64_t i = base + tid;
+    const unsigned long long v = i < nt ? sums[i] : 0ull;
+    const unsigned long long incl = ki_wave_incl(v, lane);
+    if (lane == 63) wsum[wid] = incl;
+    __syncthreads();
+    unsigned long long pre = 0, tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < KI_SUMS_THREADS / 64; ++w) { const unsigned long long x = wsum[w]; if (w < wid) pre += x; tot += x; }
+    if (i < nt) sums[i] = carry + pre + incl - v;
+    carry += tot;
+    __syncthreads();
+  }
+  if (tid == 0) sums[nt] = carry;
+}
+template <typename OUT>
+__global__ __launch_bounds__(KI_SCAN_THREADS) void k_index_scan_apply(const uint32_t* __restrict__ in, uint64_t n, const unsigned long long* __restrict__ tile_off,
+                                                                      OUT* __restrict__ out /* n + 1 */) {
+  __shared__ unsigned long long wsum[KI_SCAN_THREADS / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const uint64_t i0 = (uint64_t)blockIdx.x * KI_SCAN_TILE + (uint64_t)tid * KI_SCAN_ITEMS;
+  uint32_t v[KI_SCAN_ITEMS];
+  unsigned long long c = 0;
+#pragma unroll
+  for (int j = 0; j < KI_SCAN_ITEMS; ++j) { v[j] = i0 + j < n ? in[i0 + j] : 0u; c += v[j]; }
+  const unsigned long long incl = ki_wave_incl(c, lane);
+  if (lane == 63) wsum[wid] = incl;
+  __syncthreads();
+  unsigned long long ex = tile_off[blockIdx.x] + incl - c;
+#pragma unroll
+  for (uint32_t w = 0; w < KI_SCAN_THREADS / 64; ++w) if (w < wid) ex += wsum[w];
+#pragma unroll
+  for (int j = 0; j < KI_SCAN_ITEMS; ++j) { if (i0 + j < n) out[i0 + j] = (OUT)ex; ex += v[j]; }
+  if (blockIdx.x == gridDim.x - 1 && tid == 0) out[n] = (OUT)tile_off[gridDim.x];
+}
+
+// ---------------------------------------------------------------------------------------------
+// scatter: every (key, pos) pair probes the table for its key's rank (kh_probe_items: four pairs per lane in flight, a 64-byte sector
+// per round trip), takes the next place of that key's segment from its cursor (initialised from offsets) and writes the position
+// there.  A hot k-mer makes the cursor atomic same-address; the order inside a segment is whatever the atomics gave and is restored
+// by the two sort kernels below.
+// ---------------------------------------------------------------------------------------------
+#define KI_Q_TILE (KH_Q_THREADS * KH_Q_ITEMS)
+template <int HASH>
+__global__ __launch_bounds__(KH_Q_THREADS) void k_index_scatter(KhSlots T, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ pos, uint64_t n, KhSeed seed,
+                                                                uint32_t* __restrict__ cursor, uint32_t* __restrict__ positions, uint64_t total) {
+  for (uint64_t base = (uint64_t)blockIdx.x * KI_Q_TILE; base < n; base += (uint64_t)gridDim.x * KI_Q_TILE) {
+    uint64_t key[KH_Q_ITEMS]; uint32_t r[KH_Q_ITEMS], p[KH_Q_ITEMS];
+    uint32_t valid = 0;
+#pragma unroll
+    for (int j = 0; j < KH_Q_ITEMS; ++j) {
+      const uint64_t i = base + (uint64_t)j * KH_Q_THREADS + threadIdx.x;
+      key[j] = 0; r[j] = 0; p[j] = 0;
+      if (i < n) { key[j] = keys[i]; p[j] = pos[i]; valid |= 1u << j; }
+    }
+    const uint32_t hit = kh_probe_items<KHK_RH, HASH, false>(T, key, valid, seed, r);
+#pragma unroll
+    for (int j = 0; j < KH_Q_ITEMS; ++j) {
+      if ((hit >> j) & 1u) {
+        const uint32_t dst = atomicAdd(&cursor[r[j]], 1u);
+        if (dst < total) positions[dst] = p[j];
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// tile sort: positions cut into fixed tiles of KI_SORT_TILE entries, a workgroup per tile.  The segment boundaries inside the tile come
+// from offsets (head flags in LDS, a workgroup scan turns them into the segment index within the tile); the tile is loaded coalesced as
+// (segment in tile << 32) | position, sorted with a bitonic network in LDS and written back: every segment that lies wholly inside a
+// tile is sorted afterwards, with the same work whatever the segment lengths.  The segment that runs into the tile from the one before
+// it crosses a tile boundary; the tile behind the FIRST boundary a segment crosses appends it to xlist (so each crossing segment, and
+// with it every segment longer than a tile, is listed once) for k_index_seg_radix.
+// ---------------------------------------------------------------------------------------------
+#define KI_SORT_TILE 4096
+#define KI_SORT_THREADS 512
+#define KI_SORT_PER (KI_SORT_TILE / KI_SORT_THREADS)
+__global__ __launch_bounds__(KI_SORT_THREADS) void k_index_tile_sort(uint32_t* __restrict__ positions, uint64_t total, const uint32_t* __restrict__ offsets, uint64_t nseg,
+                                                                     uint32_t* __restrict__ xlist, uint32_t* __restrict__ xcount) {
+  __shared__ uint64_t skey[KI_SORT_TILE];
+  __shared__ uint32_t sseg[KI_SORT_TILE];
+  __shared__ uint32_t wsum[KI_SORT_THREADS / 64];
+  __shared__ uint64_t s_first;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const uint64_t tile0 = (uint64_t)blockIdx.x * KI_SORT_TILE;
+  const uint32_t m = (uint32_t)(total - tile0 < KI_SORT_TILE ? total - tile0 : KI_SORT_TILE);
+  if (tid == 0) {
+    uint64_t lo = 0, hi = nseg;                      // the last segment that starts at or before the tile's first entry
+    while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (offsets[mid] <= tile0) lo = mid; else hi = mid; }
+    s_first = lo;
+    const uint64_t o = offsets[lo];
+    if (o < tile0 && o + KI_SORT_TILE >= tile0) xlist[atomicAdd(xcount, 1u)] = (uint32_t)lo;
+  }
+  for (uint32_t i = tid; i < KI_SORT_TILE; i += KI_SORT_THREADS) sseg[i] = 0;
+  __syncthreads();
+  for (uint64_t s = s_first + 1 + tid; s < nseg; s += KI_SORT_THREADS) {      // (offsets ascend strictly: every key occurs at least once)
+    const uint64_t o = offsets[s];
+    if (o >= tile0 + m) break;
+    sseg[o - tile0] = 1;
+  }
+  __syncthreads();
+  uint32_t f[KI_SORT_PER], c = 0;
+#pragma unroll
+  for (int j = 0; j < KI_SORT_PER; ++j) { c += sseg[tid * KI_SORT_PER + j]; f[j] = c; }
+  uint32_t incl = c;
+  for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off, 64); if (lane >= (uint32_t)off) incl += o; }
+  if (lane == 63) wsum[wid] = incl;
+  __syncthreads();
+  uint32_t pre = incl - c, heads = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < KI_SORT_THREADS / 64; ++w) { const uint32_t x = wsum[w]; if (w < wid) pre += x; heads += x; }
+  if (heads + 1 >= m) return;                      // (workgroup-uniform) a head at every entry but the first: no piece of a segment in this tile
+                                                   // has two entries, there is nothing to order -- every tile of a text without repeats
+#pragma unroll
+  for (int j = 0; j < KI_SORT_PER; ++j) sseg[tid * KI_SORT_PER + j] = pre + f[j];
+  __syncthreads();
+  for (uint32_t i = tid; i < KI_SORT_TILE; i += KI_SORT_THREADS)
+    skey[i] = i < m ? (((uint64_t)sseg[i] << 32) | positions[tile0 + i]) : ~0ull;
+  __syncthreads();
+  for (uint32_t k = 2; k <= KI_SORT_TILE; k <<= 1) {
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t p = tid; p < KI_SORT_TILE / 2; p += KI_SORT_THREADS) {
+        const uint32_t i = 2 * p - (p & (j - 1)), l = i + j;
+        const uint64_t a = skey[i], b = skey[l];
+        if ((a > b) == ((i & k) == 0)) { skey[i] = b; skey[l] = a; }
+      }
+      __syncthreads();
+    }
+  }
+  for (uint32_t i = tid; i < m; i += KI_SORT_THREADS) positions[tile0 + i] = (uint32_t)skey[i];
+}
+
+// ---------------------------------------------------------------------------------------------
+// the listed segments, one workgroup each: a stable LSD radix sort of the 32-bit positions, 8 bits per pass, ping-pong between the
+// segment's place in positions and the same place in scratch (u32[total]).  A pass: digit histogram in LDS, exclusive scan of the 256
+// bins, then the segment in chunks of one entry per lane, in order -- a lane's place is bin start + same-digit entries of the waves
+// before it in the chunk + same-digit lanes before it in its wave (eight ballots).  A pass whose digit is the same for the whole
+// segment (the high bytes of positions in a short text) is skipped.
+// ---------------------------------------------------------------------------------------------
+#define KI_RADIX_THREADS 512
+#define KI_RADIX_WAVES (KI_RADIX_THREADS / 64)
+__global__ __launch_bounds__(KI_RADIX_THREADS) void k_index_seg_radix(uint32_t* __restrict__ positions, uint32_t* __restrict__ scratch, const uint32_t* __restrict__ offsets,
+                                                                      const uint32_t* __restrict__ xlist, const uint32_t* __restrict__ xcount) {
+  __shared__ uint32_t bin[256];
+  __shared__ uint32_t wcnt[KI_RADIX_WAVES][256];
+  __shared__ uint32_t wtot[4];
+  __shared__ uint32_t s_same;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const uint32_t nlist = *xcount;
+  for (uint32_t e = blockIdx.x; e < nlist; e += gridDim.x) {
+    const uint32_t s = xlist[e];
+    const uint32_t b = offsets[s], len = offsets[s + 1] - b;
+    uint32_t* src = positions + b;
+    uint32_t* dst = scratch + b;
+    for (uint32_t shift = 0; shift < 32; shift += 8) {
+      if (tid < 256) bin[tid] = 0;
+      for (uint32_t w = 0; w < KI_RADIX_WAVES; ++w) if (tid < 256) wcnt[w][tid] = 0;
+      if (tid == 0) s_same = 0;
+      __syncthreads();
+      for (uint32_t i = tid; i < len; i += KI_RADIX_THREADS) atomicAdd(&bin[(src[i] >> shift) & 255u], 1u);
+      __syncthreads();
+      uint32_t v = 0, incl = 0;
+      if (tid < 256) {
+        v = bin[tid];
+        if (v == len) s_same = 1;
+        incl = v;
+        for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off, 64); if (lane >= (uint32_t)off) incl += o; }
+        if (lane == 63) wtot[wid] = incl;
+      }
+      __syncthreads();
+      const bool same = s_same != 0;
+      if (tid < 256) {
+        uint32_t ex = incl - v;
+        for (uint32_t w = 0; w < 4; ++w) if (w < wid) ex += wtot[w];
+        bin[tid] = ex;
+      }
+      __syncthreads();
+      if (same) continue;                                        // (workgroup-uniform)
+      for (uint32_t c0 = 0; c0 < len; c0 += KI_RADIX_THREADS) {
+        const uint32_t i = c0 + tid;
+        const bool valid = i < len;
+        const uint32_t x = valid ? src[i] : 0u;
+        const uint32_t d = (x >> shift) & 255u;
+        unsigned long long mask = __ballot(valid);
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+          const bool on = (d >> bit) & 1u;
+          const unsigned long long bb = __ballot(on);
+          mask &= on ? bb : ~bb;
+        }
+        const uint32_t rank = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+        if (valid && rank == 0) wcnt[wid][d] = (uint32_t)__popcll(mask);
+        __syncthreads();
+        if (valid) {
+          uint32_t pre = 0;
+#pragma unroll
+          for (uint32_t w = 0; w < KI_RADIX_WAVES; ++w) if (w < wid) pre += wcnt[w][d];
+          dst[bin[d] + pre + rank] = x;
+        }
+        __syncthreads();
+        if (tid < 256) {
+          uint32_t t = 0;
+#pragma unroll
+          for (uint32_t w = 0; w < KI_RADIX_WAVES; ++w) { t += wcnt[w][tid]; wcnt[w][tid] = 0; }
+          bin[tid] += t;
+        }
+        __syncthreads();
+      }
+      uint32_t* sw = src; src = dst; dst = sw;
+    }
+    if (src != positions + b)
+      for (uint32_t i = tid; i < len; i += KI_RADIX_THREADS) positions[b + i] = src[i];
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// lookup: (begin, count) of every query key -- one probe (the slot's value is the rank) and two adjacent offsets words; a miss is (0, 0).
+// ---------------------------------------------------------------------------------------------
+template <int HASH>
+__global__ __launch_bounds__(KH_Q_THREADS) void k_index_lookup(KhSlots T, const uint64_t* __restrict__ q, uint64_t n, KhSeed seed, const uint32_t* __restrict__ offsets,
+                                                               uint32_t* __restrict__ out_begin /* or null */, uint32_t* __restrict__ out_count) {
+  for (uint64_t base = (uint64_t)blockIdx.x * KI_Q_TILE; base < n; base += (uint64_t)gridDim.x * KI_Q_TILE) {
+    uint64_t key[KH_Q_ITEMS]; uint32_t r[KH_Q_ITEMS];
+    uint32_t valid = 0;
+#pragma unroll
+    for (int j = 0; j < KH_Q_ITEMS; ++j) {
+      const uint64_t i = base + (uint64_t)j * KH_Q_THREADS + threadIdx.x;
+      key[j] = 0; r[j] = 0;
+      if (i < n) { key[j] = q[i]; valid |= 1u << j; }
+    }
+    const uint32_t hit = kh_probe_items<KHK_RH, HASH, false>(T, key, valid, seed, r);
+#pragma unroll
+    for (int j = 0; j < KH_Q_ITEMS; ++j) {
+      const uint64_t i = base + (uint64_t)j * KH_Q_THREADS + threadIdx.x;
+      if ((valid >> j) & 1u) {
+        uint32_t b = 0, c = 0;
+        if ((hit >> j) & 1u) { b = offsets[r[j]]; c = offsets[r[j] + 1] - b; }
+        if (out_begin) out_begin[i] = b;
+        out_count[i] = c;
+      }
+    }
+  }
+}
+// gather balanced over OUTPUT elements: output j finds its query by binary search in the query CSR (the last query whose offset is
+// <= j: queries without hits share their offset with the next one and are passed over) and copies one position.  A query with 10^6
+// hits is 10^6 independent lanes.
+__global__ __launch_bounds__(256) void k_index_gather(const uint32_t* __restrict__ positions, const uint32_t* __restrict__ begin, const uint64_t* __restrict__ qoff,
+                                                      uint64_t nq, uint64_t total, uint32_t* __restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total; j += stride) {
+    uint64_t lo = 0, hi = nq;
+    while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (qoff[mid] <= j) lo = mid; else hi = mid; }
+    out[j] = positions[(uint64_t)begin[lo] + (j - qoff[lo])];
+  }
+}

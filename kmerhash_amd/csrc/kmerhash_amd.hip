@@ -11,9 +11,11 @@
 //             out without them); LP writes tombstones in place.
 //   find/count : sector probing with in-launch compaction (k_find).
 //   by value : spectrum, selection and erase over a closed value range, one streaming pass over the slots each (kh_kernels_values.h).
+//   index   : kh_index, all occurrences per k-mer: counting insert -> slot-order ranks + CSR offsets -> scatter -> segment sort (kh_kernels_index.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
 #include "kh_kernels_values.h"
+#include "kh_kernels_index.h"
 #include "../../include/kmerhash_amd.h"
 
 #include <string>
@@ -2326,8 +2328,9 @@ void fastq_mask_text(const uint8_t* text, uint64_t n, uint32_t* sums, uint64_t* 
   hipLaunchKernelGGL(k_fastq_mask, dim3((uint32_t)ntl), dim3(256), 0, stream, text, n, (const uint64_t*)offs, msk);
 }
 // shared body of kh_kmers[128]_from_sequence / kh_kmers[128]_from_fastq; kw: 64-bit words per k-mer (1: k <= 32, 2: k <= 64)
+// out_pos (kw == 1 only, n < 2^32): the byte offset of every window next to its k-mer (kh_kmers_from_sequence_pos / _fastq_pos)
 kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq,
-                     uint64_t* out_kmers, uint64_t* n_out, int device, void* stream_) {
+                     uint64_t* out_kmers, uint64_t* n_out, int device, void* stream_, uint32_t* out_pos = nullptr) {
   kh_table* t = nullptr;
   if (n_out) *n_out = 0;
   if (k < 1 || k > 32 * kw || !n_out) return KH_ERR_INVALID;
@@ -2343,8 +2346,9 @@ kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int c
   const uint64_t nt = std::max(ntl, nkt);
   const size_t sz_sum = ((nt * 4 + 255) & ~size_t(255)), sz_off = (nt + 1) * 8;
   const size_t sz_out = where == KH_MEM_HOST ? n * 8 * kw : 0;
+  const size_t sz_pos = where == KH_MEM_HOST && out_pos ? n * 4 : 0;
   char* blk = nullptr;
-  HIPCHK(pool_alloc(device, sz_seq + sz_msk + sz_sum + sz_off + 256 + sz_out, reinterpret_cast<void**>(&blk)));
+  HIPCHK(pool_alloc(device, sz_seq + sz_msk + sz_sum + sz_off + 256 + sz_out + sz_pos, reinterpret_cast<void**>(&blk)));
   const uint8_t* dseq = static_cast<const uint8_t*>(seq);
   char* p = blk;
   if (where == KH_MEM_HOST) { dseq = reinterpret_cast<uint8_t*>(p); p += sz_seq; }
@@ -2352,6 +2356,7 @@ kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int c
   uint32_t* sums = reinterpret_cast<uint32_t*>(p); p += sz_sum;
   uint64_t* offs = reinterpret_cast<uint64_t*>(p); p += (sz_off + 255) & ~size_t(255);
   uint64_t* dout = where == KH_MEM_HOST ? reinterpret_cast<uint64_t*>(p) : out_kmers;
+  uint32_t* dpos = where == KH_MEM_HOST ? reinterpret_cast<uint32_t*>(p + sz_out) : out_pos;
   hipError_t e = hipSuccess;
   if (where == KH_MEM_HOST) e = hipMemcpyAsync(const_cast<uint8_t*>(dseq), seq, n, hipMemcpyHostToDevice, stream);
   if (e == hipSuccess) {
@@ -2360,7 +2365,9 @@ kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int c
     if (kw == 2) hipLaunchKernelGGL(k_kmers_count<2>, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
     else hipLaunchKernelGGL(k_kmers_count<1>, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
     hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, sums, nkt, offs);
-    if (kw == 2 && canonical) hipLaunchKernelGGL((kw_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
+    if (out_pos && canonical) hipLaunchKernelGGL((k_kmers_emit_pos<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout, dpos);
+    else if (out_pos) hipLaunchKernelGGL((k_kmers_emit_pos<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout, dpos);
+    else if (kw == 2 && canonical) hipLaunchKernelGGL((kw_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
     else if (kw == 2) hipLaunchKernelGGL((kw_kmers_emit<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
     else if (canonical) hipLaunchKernelGGL((k_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
     else hipLaunchKernelGGL((k_kmers_emit<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
@@ -2371,6 +2378,7 @@ kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int c
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
   if (e == hipSuccess && where == KH_MEM_HOST && total) {
     e = hipMemcpyAsync(out_kmers, dout, total * 8 * kw, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && out_pos) e = hipMemcpyAsync(out_pos, dpos, total * 4, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
   }
   pool_free(device, blk);
@@ -2387,6 +2395,22 @@ kh_status kh_kmers_from_sequence(const void* seq, uint64_t n, uint32_t k, int ca
 kh_status kh_kmers_from_fastq(const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where,
                               uint64_t* out_kmers, uint64_t* n_out, int device, void* stream_) {
   return kmers_impl(1, text, n, k, canonical, where, true, out_kmers, n_out, device, stream_);
+}
+// the same k-mers in the same order, each with the byte offset of its window's first base in the buffer passed (positions are 32-bit:
+// a text of 2^32 bytes or more is refused before anything is allocated or read)
+kh_status kh_kmers_from_sequence_pos(const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where,
+                                     uint64_t* out_kmers, uint32_t* out_pos, uint64_t* n_out, int device, void* stream_) {
+  if (n_out) *n_out = 0;
+  if (n >> 32) return KH_ERR_INVALID;
+  if (n >= k && !out_pos) return KH_ERR_INVALID;
+  return kmers_impl(1, seq, n, k, canonical, where, false, out_kmers, n_out, device, stream_, out_pos);
+}
+kh_status kh_kmers_from_fastq_pos(const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where,
+                                  uint64_t* out_kmers, uint32_t* out_pos, uint64_t* n_out, int device, void* stream_) {
+  if (n_out) *n_out = 0;
+  if (n >> 32) return KH_ERR_INVALID;
+  if (n >= k && !out_pos) return KH_ERR_INVALID;
+  return kmers_impl(1, text, n, k, canonical, where, true, out_kmers, n_out, device, stream_, out_pos);
 }
 
 // ---- HyperLogLog (hyperloglog64.hpp) --------------------------------------------------------------
@@ -3025,5 +3049,274 @@ kh_status kh_kmers128_from_sequence(const void* seq, uint64_t n, uint32_t k, int
 kh_status kh_kmers128_from_fastq(const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, uint64_t* out_kmers, uint64_t* n_out,
                                  int device, void* stream) {
   return kmers_impl(2, text, n, k, canonical, where, true, out_kmers, n_out, device, stream);
+}
+}  // extern "C"
+
+// ===================================================================================================
+// k-mer position index (kh_index): all occurrences per k-mer.  The reference's driver offers PositionIndex<MapType> over a multimap next
+// to CountIndex (BenchmarkKmerIndex.cpp:342-449); the multimap itself is kmerind's and not part of the reference tree, so the contract is
+// this library's (include/kmerhash_amd.h).  A static index: one Robin Hood kh_table owned by the index, whose value per key is the key's
+// rank among the live slots in slot order, and a CSR (offsets u32[size + 1], positions u32[total]) in device memory.
+// ===================================================================================================
+struct kh_index {
+  kh_table* t = nullptr;
+  int hash = 0, device = 0;
+  uint64_t seed = 0;
+  float min_lf = 0.f, max_lf = 0.f;
+  hipStream_t stream = nullptr;
+  uint32_t* offsets = nullptr;        // u32[size + 1]
+  uint32_t* positions = nullptr;      // u32[total]
+  uint64_t total = 0;
+  bool built = false, prof = false;
+  std::string err;
+};
+namespace {
+kh_status xfail(kh_index* x, kh_status s, const std::string& msg) { if (x) x->err = msg; return s; }
+// back to the state of kh_index_create: no arrays and a FRESH table (a cleared table would keep its capacity, and the layout of the next
+// build is promised to be that of a fresh table)
+kh_status index_reset(kh_index* x) {
+  hipSetDevice(x->device);
+  if (x->t) hipStreamSynchronize(x->t->stream);
+  pool_free(x->device, x->offsets); pool_free(x->device, x->positions);
+  x->offsets = nullptr; x->positions = nullptr; x->total = 0; x->built = false;
+  if (x->t) { kh_destroy(x->t); x->t = nullptr; }
+  const kh_status st = kh_create(&x->t, KH_KIND_ROBINHOOD, 8, 4, (kh_hash)x->hash, x->seed, 128, x->min_lf, x->max_lf, x->device);
+  if (st != KH_OK) return xfail(x, st, "kh_index: the table could not be created");
+  x->t->stream = x->stream; x->t->prof = x->prof;
+  return KH_OK;
+}
+// a failed build leaves the index empty; the text of the failure survives the reset
+kh_status index_abandon(kh_index* x, kh_status s) {
+  const std::string msg = x->t ? x->t->err : std::string("kh_index: no table");
+  index_reset(x);
+  return xfail(x, s, msg);
+}
+inline uint32_t index_probe_grid(const kh_table* t, uint64_t n) {
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + KI_Q_TILE - 1) / KI_Q_TILE, (uint64_t)cu_count(t) * 8));
+}
+// exclusive scan of n (> 0) device counts into n + 1 offsets of type OUT; ssums: ull[tiles + 1] of workspace
+template <typename OUT>
+kh_status index_scan(kh_table* t, const uint32_t* counts, uint64_t n, unsigned long long* ssums, OUT* out) {
+  const uint64_t nst = (n + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
+  Launch L(t, "k_index_scan");
+  hipLaunchKernelGGL(k_index_tile_sums, dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, t->stream, counts, n, ssums);
+  hipLaunchKernelGGL(k_index_scan_sums, dim3(1), dim3(KI_SUMS_THREADS), 0, t->stream, ssums, nst);
+  hipLaunchKernelGGL((k_index_scan_apply<OUT>), dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, t->stream, counts, n, (const unsigned long long*)ssums, out);
+  HIPCHK(hipGetLastError());
+  return KH_OK;
+}
+// the build proper: n (> 0) pairs in device memory, the index empty.  On an error the caller abandons the index.
+kh_status index_build_device(kh_index* x, const uint64_t* dk, const uint32_t* dp, uint64_t n) {
+  kh_table* t = x->t;
+  // 1. the counting insert, unchanged: key set, size, capacity and slot order are those of kh_insert_reduce_plus into a fresh table
+  uint64_t nins = 0;
+  kh_status st = kh_insert_reduce_plus(t, dk, nullptr, n, KH_MEM_DEVICE, &nins);
+  if (st != KH_OK) return st;
+  const uint64_t size = t->lsize, cap = t->cur.cap;
+  if (size == 0 || size > n) return fail(t, KH_ERR_HIP, "kh_index: internal: counting insert left an impossible size");
+  void* vp = nullptr;
+  HIPCHK(pool_alloc(t->device, (size + 1) * 4, &vp)); x->offsets = static_cast<uint32_t*>(vp);
+  HIPCHK(pool_alloc(t->device, n * 4, &vp)); x->positions = static_cast<uint32_t*>(vp);
+  const uint64_t ntl = (cap + KV_SEL_TILE - 1) / KV_SEL_TILE, nst = (size + KI_SCAN_TILE - 1) / KI_SCAN_TILE, nsort = (n + KI_SORT_TILE - 1) / KI_SORT_TILE;
+  { kh_status ps = arena_prepare(t, ntl * 12 + size * 8 + nst * 8 + nsort * 4 + n * 4 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  uint32_t *sums, *counts, *cursor, *xlist, *xcount, *scratch; uint64_t* toffs; unsigned long long* ssums;
+  TAKE(sums, uint32_t, ntl); TAKE(toffs, uint64_t, ntl + 1); TAKE(counts, uint32_t, size); TAKE(cursor, uint32_t, size);
+  TAKE(ssums, unsigned long long, nst + 1); TAKE(xlist, uint32_t, nsort); TAKE(xcount, uint32_t, 1); TAKE(scratch, uint32_t, n);
+  // 2. the keys that share a home bucket in key order (the insert leaves their order to chance); rank of every live slot in slot order; counts[rank] = occurrences; the slot's value becomes the rank; offsets = scan(counts)
+  { Launch L(t, "k_index_rank");
+    hipLaunchKernelGGL(k_index_canon_runs, dim3(grid_for(cap, 256, (uint32_t)cu_count(t) * 8)), dim3(256), 0, t->stream, narrow(t->cur).s, cap);
+    hipLaunchKernelGGL((k_values_tile_count<KV_RH>), dim3((uint32_t)ntl), dim3(KV_SEL_THREADS), 0, t->stream, (const void*)t->cur.p, cap, 0u, 0xFFFFFFFFu, sums);
+    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, (const uint32_t*)sums, ntl, toffs);
+    hipLaunchKernelGGL(k_index_rank, dim3((uint32_t)ntl), dim3(KV_SEL_THREADS), 0, t->stream, narrow(t->cur).s, cap, (const uint64_t*)toffs, counts); }
+  HIPCHK(hipGetLastError());
+  st = index_scan<uint32_t>(t, counts, size, ssums, x->offsets);
+  if (st != KH_OK) return st;
+  // 3. scatter through per-key cursors
+  HIPCHK(hipMemcpyAsync(cursor, x->offsets, size * 4, hipMemcpyDeviceToDevice, t->stream));
+  HIPCHK(hipMemsetAsync(xcount, 0, 4, t->stream));
+  { Launch L(t, "k_index_scatter");
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_index_scatter<HASH>), dim3(index_probe_grid(t, n)), dim3(KH_Q_THREADS), 0, t->stream, narrow(t->cur), dk, dp, n, t->seed,
+                                               cursor, x->positions, n)); }
+  HIPCHK(hipGetLastError());
+  // 4. ascending order inside every segment: fixed tiles in LDS, then the segments that cross a tile boundary
+  { Launch L(t, "k_index_tile_sort");
+    hipLaunchKernelGGL(k_index_tile_sort, dim3((uint32_t)nsort), dim3(KI_SORT_THREADS), 0, t->stream, x->positions, n, (const uint32_t*)x->offsets, size, xlist, xcount); }
+  { Launch L(t, "k_index_seg_radix");
+    hipLaunchKernelGGL(k_index_seg_radix, dim3((uint32_t)std::min<uint64_t>(nsort, (uint64_t)cu_count(t) * 4)), dim3(KI_RADIX_THREADS), 0, t->stream, x->positions, scratch,
+                       (const uint32_t*)x->offsets, (const uint32_t*)xlist, (const uint32_t*)xcount); }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(t->stream));
+  x->total = n; x->built = true;
+  return KH_OK;
+}
+kh_status index_build_text(kh_index* x, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq) {
+  if (!x) return KH_ERR_INVALID;
+  if (n >> 32) return xfail(x, KH_ERR_INVALID, "kh_index: positions are 32-bit, a text of 2^32 bytes or more is refused");
+  if (x->built) return xfail(x, KH_ERR_INVALID, "kh_index: the index is built already (kh_index_clear first)");
+  if (k < 1 || k > 32) return xfail(x, KH_ERR_INVALID, "kh_index: k must be 1..32");
+  if (n < k) return KH_OK;
+  if (!text) return xfail(x, KH_ERR_INVALID, "null text");
+  kh_table* t = x->t;
+  HIPCHK(hipSetDevice(x->device));
+  // host text is staged once; k-mers and positions never leave the device
+  const size_t sz_text = where == KH_MEM_HOST ? ((n + 255) & ~size_t(255)) : 0;
+  char* blk = nullptr;
+  HIPCHK(pool_alloc(x->device, sz_text + n * 12, reinterpret_cast<void**>(&blk)));
+  const void* dtext = text;
+  hipError_t e = hipSuccess;
+  if (where == KH_MEM_HOST) { e = hipMemcpyAsync(blk, text, n, hipMemcpyHostToDevice, t->stream); dtext = blk; }
+  uint64_t* dk = reinterpret_cast<uint64_t*>(blk + sz_text);
+  uint32_t* dp = reinterpret_cast<uint32_t*>(blk + sz_text + n * 8);
+  uint64_t m = 0;
+  kh_status st = e == hipSuccess ? kmers_impl(1, dtext, n, k, canonical, KH_MEM_DEVICE, fastq, dk, &m, x->device, t->stream, dp) : KH_ERR_HIP;
+  if (st != KH_OK) fail(t, st, "kh_index: k-mer generation failed");
+  else if (m) st = index_build_device(x, dk, dp, m);
+  hipStreamSynchronize(t->stream);
+  pool_free(x->device, blk);
+  return st == KH_OK ? KH_OK : index_abandon(x, st);
+}
+}  // namespace
+extern "C" {
+kh_status kh_index_create(kh_index** out, kh_hash hash, uint64_t seed, float min_lf, float max_lf, int device) {
+  if (!out) return KH_ERR_INVALID;
+  *out = nullptr;
+  if ((int)hash < 0 || (int)hash > 3) return KH_ERR_INVALID;
+  kh_index* x = new kh_index();
+  x->hash = (int)hash; x->seed = seed; x->min_lf = min_lf; x->max_lf = max_lf; x->device = device;
+  const kh_status st = kh_create(&x->t, KH_KIND_ROBINHOOD, 8, 4, hash, seed, 128, min_lf, max_lf, device);      // (no GPU: KH_ERR_HIP)
+  if (st != KH_OK) { delete x; return st; }
+  *out = x;
+  return KH_OK;
+}
+kh_status kh_index_destroy(kh_index* x) {
+  if (!x) return KH_OK;
+  hipSetDevice(x->device);
+  if (x->t) { hipStreamSynchronize(x->t->stream); kh_destroy(x->t); }
+  pool_free(x->device, x->offsets); pool_free(x->device, x->positions);
+  delete x;
+  return KH_OK;
+}
+kh_status kh_index_set_stream(kh_index* x, void* s) {
+  if (!x) return KH_ERR_INVALID;
+  x->stream = static_cast<hipStream_t>(s);
+  return kh_set_stream(x->t, s);
+}
+const char* kh_index_last_error(const kh_index* x) { return x ? x->err.c_str() : "null index"; }
+kh_status kh_index_clear(kh_index* x) { if (!x) return KH_ERR_INVALID; return index_reset(x); }
+kh_status kh_index_size(const kh_index* x, uint64_t* out) { if (!x || !out) return KH_ERR_INVALID; *out = x->t->lsize; return KH_OK; }
+kh_status kh_index_total(const kh_index* x, uint64_t* out) { if (!x || !out) return KH_ERR_INVALID; *out = x->total; return KH_OK; }
+kh_status kh_index_capacity(const kh_index* x, uint64_t* out) { if (!x || !out) return KH_ERR_INVALID; *out = x->t->cur.cap; return KH_OK; }
+kh_status kh_index_profile_enable(kh_index* x, int on) { if (!x) return KH_ERR_INVALID; x->prof = on != 0; if (on) kh_profile_reset(x->t); return kh_profile_enable(x->t, on); }
+kh_status kh_index_profile_dump(kh_index* x, char* buf, uint64_t cap) { if (!x) return KH_ERR_INVALID; return kh_profile_dump(x->t, buf, cap); }
+
+kh_status kh_index_build(kh_index* x, const void* keys, const void* pos, uint64_t n, kh_mem where) {
+  if (!x) return KH_ERR_INVALID;
+  if (n >> 32) return xfail(x, KH_ERR_INVALID, "kh_index_build: positions and offsets are 32-bit, n must be below 2^32");
+  if (x->built) return xfail(x, KH_ERR_INVALID, "kh_index_build: the index is built already (kh_index_clear first)");
+  if (n == 0) return KH_OK;
+  if (!keys || !pos) return xfail(x, KH_ERR_INVALID, "null argument");
+  kh_table* t = x->t;
+  HIPCHK(hipSetDevice(x->device));
+  const uint64_t* dk = static_cast<const uint64_t*>(keys);
+  const uint32_t* dp = static_cast<const uint32_t*>(pos);
+  char* blk = nullptr;
+  hipError_t e = hipSuccess;
+  if (where == KH_MEM_HOST) {          // (not in the table's workspace: the counting insert resets it)
+    HIPCHK(pool_alloc(x->device, n * 12, reinterpret_cast<void**>(&blk)));
+    e = hipMemcpyAsync(blk, keys, n * 8, hipMemcpyHostToDevice, t->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk + n * 8, pos, n * 4, hipMemcpyHostToDevice, t->stream);
+    dk = reinterpret_cast<const uint64_t*>(blk); dp = reinterpret_cast<const uint32_t*>(blk + n * 8);
+  }
+  kh_status st = KH_ERR_HIP;
+  if (e == hipSuccess) st = index_build_device(x, dk, dp, n); else fail(t, KH_ERR_HIP, "kh_index_build: staging the pairs failed");
+  hipStreamSynchronize(t->stream);
+  pool_free(x->device, blk);
+  return st == KH_OK ? KH_OK : index_abandon(x, st);
+}
+kh_status kh_index_build_from_sequence(kh_index* x, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where) {
+  return index_build_text(x, seq, n, k, canonical, where, false);
+}
+kh_status kh_index_build_from_fastq(kh_index* x, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where) {
+  return index_build_text(x, text, n, k, canonical, where, true);
+}
+kh_status kh_index_export(kh_index* x, uint64_t* keys_host, uint32_t* offsets_host, uint32_t* positions_host) {
+  if (!x) return KH_ERR_INVALID;
+  kh_table* t = x->t;
+  HIPCHK(hipSetDevice(x->device));
+  const uint64_t size = t->lsize;
+  if (!x->built || size == 0) { if (offsets_host) offsets_host[0] = 0; return KH_OK; }
+  if (keys_host) {                    // the keys in slot order: the full value range selected in one pass over the slots
+    uint64_t m = 0;
+    const kh_status st = kh_select_values(t, 0u, 0xFFFFFFFFu, KH_MEM_HOST, keys_host, nullptr, size, &m);
+    if (st != KH_OK) { x->err = t->err; return st; }
+  }
+  if (offsets_host) HIPCHK(hipMemcpyAsync(offsets_host, x->offsets, (size + 1) * 4, hipMemcpyDeviceToHost, t->stream));
+  if (positions_host) HIPCHK(hipMemcpyAsync(positions_host, x->positions, x->total * 4, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  return KH_OK;
+}
+
+kh_status kh_index_count(kh_index* x, const void* keys, uint64_t n, kh_mem where, uint32_t* out_counts) {
+  if (!x) return KH_ERR_INVALID;
+  if (n == 0) return KH_OK;
+  if (!keys || !out_counts) return xfail(x, KH_ERR_INVALID, "null argument");
+  kh_table* t = x->t;
+  HIPCHK(hipSetDevice(x->device));
+  { kh_status ps = arena_prepare(t, n * 12 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  const uint64_t* q;
+  kh_status st = stage_in<uint64_t>(t, keys, n, where, &q);
+  if (st != KH_OK) return st;
+  uint32_t* dc = out_counts;
+  if (where == KH_MEM_HOST) TAKE(dc, uint32_t, n);
+  { Launch L(t, "k_index_lookup");
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_index_lookup<HASH>), dim3(index_probe_grid(t, n)), dim3(KH_Q_THREADS), 0, t->stream, narrow(t->cur), q, n, t->seed,
+                                               (const uint32_t*)x->offsets, (uint32_t*)nullptr, dc)); }
+  HIPCHK(hipGetLastError());
+  if (where == KH_MEM_HOST) HIPCHK(hipMemcpyAsync(out_counts, dc, n * 4, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  return KH_OK;
+}
+kh_status kh_index_find(kh_index* x, const void* keys, uint64_t n, kh_mem where, uint64_t* out_offsets, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out) {
+  if (n_out) *n_out = 0;
+  if (!x) return KH_ERR_INVALID;
+  if (!out_offsets || (n && !keys)) return xfail(x, KH_ERR_INVALID, "null argument");
+  kh_table* t = x->t;
+  HIPCHK(hipSetDevice(x->device));
+  const bool host = where == KH_MEM_HOST;
+  if (n == 0) {
+    if (host) out_offsets[0] = 0; else HIPCHK(hipMemsetAsync(out_offsets, 0, 8, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    return KH_OK;
+  }
+  const uint64_t nst = (n + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
+  { kh_status ps = arena_prepare(t, n * 24 + nst * 8 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  const uint64_t* q;
+  kh_status st = stage_in<uint64_t>(t, keys, n, where, &q);
+  if (st != KH_OK) return st;
+  uint32_t *begin, *cnt; unsigned long long* ssums; uint64_t* doff = out_offsets;
+  TAKE(begin, uint32_t, n); TAKE(cnt, uint32_t, n); TAKE(ssums, unsigned long long, nst + 1);
+  if (host) TAKE(doff, uint64_t, n + 1);
+  { Launch L(t, "k_index_lookup");
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_index_lookup<HASH>), dim3(index_probe_grid(t, n)), dim3(KH_Q_THREADS), 0, t->stream, narrow(t->cur), q, n, t->seed,
+                                               (const uint32_t*)x->offsets, begin, cnt)); }
+  HIPCHK(hipGetLastError());
+  st = index_scan<uint64_t>(t, cnt, n, ssums, doff);
+  if (st != KH_OK) return st;
+  HIPCHK(hipMemcpyAsync(t->hpin, doff + n, 8, hipMemcpyDeviceToHost, t->stream));
+  if (host) HIPCHK(hipMemcpyAsync(out_offsets, doff, (n + 1) * 8, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  const uint64_t total = t->hpin[0];
+  if (n_out) *n_out = total;
+  if (!out_pos || total == 0) return KH_OK;
+  if (total > cap_out) return xfail(x, KH_ERR_INVALID, "kh_index_find: more positions than cap_out (n_out holds their number)");
+  uint32_t* dout = out_pos;
+  if (host) TAKE(dout, uint32_t, total);
+  { Launch L(t, "k_index_gather");
+    hipLaunchKernelGGL(k_index_gather, dim3(grid_for(total, 256, (uint32_t)cu_count(t) * 8)), dim3(256), 0, t->stream, (const uint32_t*)x->positions, (const uint32_t*)begin,
+                       (const uint64_t*)doff, n, total, dout); }
+  HIPCHK(hipGetLastError());
+  if (host) HIPCHK(hipMemcpyAsync(out_pos, dout, total * 4, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  return KH_OK;
 }
 }  // extern "C"
