@@ -277,7 +277,6 @@ kh_status kh_kmers_from_sequence_pos(const void* seq /*[h|d] u8[n]*/, uint64_t n
                                      uint64_t* out_kmers /*[h|d]*/, uint32_t* out_pos /*[h|d]*/, uint64_t* n_out, int device, void* hip_stream);
 kh_status kh_kmers_from_fastq_pos(const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, int canonical, kh_mem where,
                                   uint64_t* out_kmers /*[h|d]*/, uint32_t* out_pos /*[h|d]*/, uint64_t* n_out, int device, void* hip_stream);
-
 /* ---- k-mer position index: ALL occurrences per k-mer (the reference's driver offers PositionIndex<MapType> over a multimap next to
  *      CountIndex, BenchmarkKmerIndex.cpp:342-449; the multimap is kmerind's and absent from the reference tree: the contract below is
  *      this library's).  A STATIC index of 64-bit keys (k <= 32) on one GPU: built once from one batch of (key, position) pairs, then
@@ -295,7 +294,8 @@ kh_status kh_kmers_from_fastq_pos(const void* text /*[h|d] u8[n]*/, uint64_t n, 
  *      kh_index_build_from_sequence / _from_fastq: kh_kmers_from_sequence_pos / _fastq_pos and the build, on device buffers (host text
  *      is staged once; k-mers and positions never visit the host).
  *      kh_index_export: keys in slot order (the order of kh_to_vector), offsets and positions, into host buffers (any may be NULL).
- *      Appending to or erasing from a built index, 16-byte keys, the linear-probe layout and a strand bit are not supported. */
+ *      Appending to or erasing from a built index, the linear-probe layout and a strand bit are not supported; 16-byte keys (k <= 64)
+ *      are kh_wide_index_* below. */
 typedef struct kh_index kh_index;
 kh_status kh_index_create(kh_index** out, kh_hash hash, uint64_t seed, float min_lf, float max_lf, int device);
 kh_status kh_index_destroy(kh_index* x);
@@ -447,6 +447,46 @@ kh_status kh_profile_reset(kh_table* t);
 kh_status kh_profile_query(kh_table* t, const char* prefix, double* total_ms, uint64_t* launches);
 /* writes up to `cap` bytes of "name launches total_ms\n" lines */
 kh_status kh_profile_dump(kh_table* t, char* buf, uint64_t cap);
+
+/* ---- the position index over 16-byte keys (k-mers with k <= 64): kh_index_* word for word with a key of two 64-bit words {w0, w1}
+ *      (keys u64[2n], as kh_wide_* takes them), on the wide Robin Hood table.  Static, built once from an empty index; duplicate pairs
+ *      kept; the positions of a key ascend; kh_wide_index_find returns a CSR in query order whose total is known before anything is
+ *      written (too small a cap_out: KH_ERR_INVALID, the output buffers untouched); a failed build leaves the index empty; n >= 2^32 is
+ *      refused; without a GPU kh_wide_index_create returns KH_ERR_HIP and a null handle.  After a build key set, size, capacity and info
+ *      bytes of the table are those of a fresh kh_wide_create table (capacity 128, same hash, seed and load factors) after
+ *      kh_wide_insert_reduce_plus(keys, NULL, n); the slot order is that table's up to the order of the keys that share a HOME BUCKET,
+ *      which stand in ascending order of the 128-bit value (w1 << 64) | w0 -- so the export depends on the multiset of pairs alone.
+ *      kh_wide_index_build_from_sequence / _from_fastq: kh_kmers128_from_sequence_pos / _fastq_pos and the build, k = 1..64.
+ *      kh_wide_index_export: keys_host u64[2 size] in slot order (the order of kh_wide_to_vector).
+ *      Not supported: appending to or erasing from a built index, a strand bit, read-id decoding, 64-bit positions. */
+typedef struct kh_windex kh_windex;
+kh_status kh_wide_index_create(kh_windex** out, kh_hash hash, uint64_t seed, float min_lf, float max_lf, int device);
+kh_status kh_wide_index_destroy(kh_windex* x);
+kh_status kh_wide_index_set_stream(kh_windex* x, void* hip_stream);
+const char* kh_wide_index_last_error(const kh_windex* x);
+kh_status kh_wide_index_clear(kh_windex* x);
+kh_status kh_wide_index_build(kh_windex* x, const void* keys /*[h|d] u64[2n]*/, const void* pos /*[h|d] u32[n]*/, uint64_t n, kh_mem where);
+kh_status kh_wide_index_build_from_sequence(kh_windex* x, const void* seq /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, int canonical, kh_mem where);
+kh_status kh_wide_index_build_from_fastq(kh_windex* x, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, int canonical, kh_mem where);
+kh_status kh_wide_index_size(const kh_windex* x, uint64_t* distinct_keys);
+kh_status kh_wide_index_total(const kh_windex* x, uint64_t* n_positions);
+kh_status kh_wide_index_capacity(const kh_windex* x, uint64_t* buckets);
+kh_status kh_wide_index_export(kh_windex* x, uint64_t* keys_host /*[2*size]*/, uint32_t* offsets_host /*[size+1]*/, uint32_t* positions_host /*[total]*/);
+/* the RH info byte of every bucket of the index's table (kh_wide_export_info of it; out_host u8[capacity]): equal to the counting twin's */
+kh_status kh_wide_index_export_info(kh_windex* x, uint8_t* out_host);
+kh_status kh_wide_index_count(kh_windex* x, const void* keys /*[h|d] u64[2n]*/, uint64_t n, kh_mem where, uint32_t* out_counts /*[h|d] u32[n]*/);
+kh_status kh_wide_index_find(kh_windex* x, const void* keys /*[h|d] u64[2n]*/, uint64_t n, kh_mem where,
+                             uint64_t* out_offsets /*[h|d] u64[n+1]*/, uint32_t* out_pos /*[h|d] u32[cap_out] or NULL*/,
+                             uint64_t cap_out, uint64_t* n_out);
+kh_status kh_wide_index_profile_enable(kh_windex* x, int on);
+kh_status kh_wide_index_profile_dump(kh_windex* x, char* buf, uint64_t cap);
+
+/* kh_kmers_from_sequence_pos / _fastq_pos for 16-byte k-mers, k = 1..64: out_kmers u64[2n] ({w0, w1} per k-mer, the windows and the order of
+ *      kh_kmers128_from_sequence / _fastq), out_pos[i] the byte offset of the first base of the window of k-mer i */
+kh_status kh_kmers128_from_sequence_pos(const void* seq /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, int canonical, kh_mem where,
+                                        uint64_t* out_kmers /*[h|d] u64[2n]*/, uint32_t* out_pos /*[h|d]*/, uint64_t* n_out, int device, void* hip_stream);
+kh_status kh_kmers128_from_fastq_pos(const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, int canonical, kh_mem where,
+                                     uint64_t* out_kmers /*[h|d] u64[2n]*/, uint32_t* out_pos /*[h|d]*/, uint64_t* n_out, int device, void* hip_stream);
 
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);

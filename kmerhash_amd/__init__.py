@@ -6,9 +6,9 @@ the thin host-side mirror of the reference's interface for Python callers plus w
 from .table import (hashmap_robinhood_doubling, hashmap_linearprobe_doubling, hash_batch, HASHES,  # noqa: F401
                     KhError, KhLogicError, KhRetry)
 from .wide import hashmap_robinhood_doubling_wide, hashmap_robinhood_doubling_wide_stream, hash_batch_wide, kmers128_from_sequence, kmers128_from_fastq  # noqa: F401
-from .index import KmerPositionIndex  # noqa: F401
+from .index import KmerPositionIndex, WideKmerPositionIndex  # noqa: F401
 from . import workloads  # noqa: F401
 
 __all__ = ["hashmap_robinhood_doubling", "hashmap_linearprobe_doubling", "hash_batch", "HASHES", "KhError",
            "KhLogicError", "KhRetry", "workloads", "hashmap_robinhood_doubling_wide", "hashmap_robinhood_doubling_wide_stream", "hash_batch_wide", "kmers128_from_sequence",
-           "kmers128_from_fastq", "KmerPositionIndex"]
+           "kmers128_from_fastq", "KmerPositionIndex", "WideKmerPositionIndex"]

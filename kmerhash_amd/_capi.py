@@ -64,6 +64,11 @@ SYMBOLS = [
     "kh_index_create", "kh_index_destroy", "kh_index_set_stream", "kh_index_last_error", "kh_index_clear", "kh_index_build",
     "kh_index_build_from_sequence", "kh_index_build_from_fastq", "kh_index_size", "kh_index_total", "kh_index_capacity", "kh_index_export",
     "kh_index_count", "kh_index_find", "kh_index_profile_enable", "kh_index_profile_dump",
+    # position index over 16-byte k-mers (k <= 64) and its front end
+    "kh_kmers128_from_sequence_pos", "kh_kmers128_from_fastq_pos",
+    "kh_wide_index_create", "kh_wide_index_destroy", "kh_wide_index_set_stream", "kh_wide_index_last_error", "kh_wide_index_clear", "kh_wide_index_build",
+    "kh_wide_index_build_from_sequence", "kh_wide_index_build_from_fastq", "kh_wide_index_size", "kh_wide_index_total", "kh_wide_index_capacity",
+    "kh_wide_index_export", "kh_wide_index_export_info", "kh_wide_index_count", "kh_wide_index_find", "kh_wide_index_profile_enable", "kh_wide_index_profile_dump",
 ]
 
 _lib = None
@@ -199,25 +204,29 @@ def lib():
         getattr(L, pre + "erase_values").argtypes = [vp, u32, u32, pu64]
     L.kh_kmers_from_sequence_pos.argtypes = [vp, u64, u32, i32, i32, vp, vp, pu64, i32, vp]
     L.kh_kmers_from_fastq_pos.argtypes = [vp, u64, u32, i32, i32, vp, vp, pu64, i32, vp]
-    L.kh_index_last_error.restype = C.c_char_p
-    L.kh_index_last_error.argtypes = [vp]
-    L.kh_index_create.argtypes = [C.POINTER(vp), i32, u64, f32, f32, i32]
-    L.kh_index_destroy.argtypes = [vp]
-    L.kh_index_set_stream.argtypes = [vp, vp]
-    L.kh_index_clear.argtypes = [vp]
-    L.kh_index_build.argtypes = [vp, vp, vp, u64, i32]
-    L.kh_index_build_from_sequence.argtypes = [vp, vp, u64, u32, i32, i32]
-    L.kh_index_build_from_fastq.argtypes = [vp, vp, u64, u32, i32, i32]
-    L.kh_index_size.argtypes = [vp, pu64]
-    L.kh_index_total.argtypes = [vp, pu64]
-    L.kh_index_capacity.argtypes = [vp, pu64]
-    L.kh_index_export.argtypes = [vp, vp, vp, vp]
-    L.kh_index_count.argtypes = [vp, vp, u64, i32, vp]
-    L.kh_index_find.argtypes = [vp, vp, u64, i32, vp, vp, u64, pu64]
-    L.kh_index_profile_enable.argtypes = [vp, i32]
-    L.kh_index_profile_dump.argtypes = [vp, C.c_char_p, u64]
+    L.kh_kmers128_from_sequence_pos.argtypes = [vp, u64, u32, i32, i32, vp, vp, pu64, i32, vp]
+    L.kh_kmers128_from_fastq_pos.argtypes = [vp, u64, u32, i32, i32, vp, vp, pu64, i32, vp]
+    for pre in ("kh_index_", "kh_wide_index_"):      # one contract, two key widths
+        getattr(L, pre + "last_error").restype = C.c_char_p
+        getattr(L, pre + "last_error").argtypes = [vp]
+        getattr(L, pre + "create").argtypes = [C.POINTER(vp), i32, u64, f32, f32, i32]
+        getattr(L, pre + "destroy").argtypes = [vp]
+        getattr(L, pre + "set_stream").argtypes = [vp, vp]
+        getattr(L, pre + "clear").argtypes = [vp]
+        getattr(L, pre + "build").argtypes = [vp, vp, vp, u64, i32]
+        getattr(L, pre + "build_from_sequence").argtypes = [vp, vp, u64, u32, i32, i32]
+        getattr(L, pre + "build_from_fastq").argtypes = [vp, vp, u64, u32, i32, i32]
+        getattr(L, pre + "size").argtypes = [vp, pu64]
+        getattr(L, pre + "total").argtypes = [vp, pu64]
+        getattr(L, pre + "capacity").argtypes = [vp, pu64]
+        getattr(L, pre + "export").argtypes = [vp, vp, vp, vp]
+        getattr(L, pre + "count").argtypes = [vp, vp, u64, i32, vp]
+        getattr(L, pre + "find").argtypes = [vp, vp, u64, i32, vp, vp, u64, pu64]
+        getattr(L, pre + "profile_enable").argtypes = [vp, i32]
+        getattr(L, pre + "profile_dump").argtypes = [vp, C.c_char_p, u64]
+    L.kh_wide_index_export_info.argtypes = [vp, vp]
     for s in SYMBOLS:
-        if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error"):
+        if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error", "kh_wide_index_last_error"):
             getattr(L, s).restype = i32
     _lib = L
     return L

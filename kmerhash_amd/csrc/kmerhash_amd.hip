@@ -12,10 +12,12 @@
 //   find/count : sector probing with in-launch compaction (k_find).
 //   by value : spectrum, selection and erase over a closed value range, one streaming pass over the slots each (kh_kernels_values.h).
 //   index   : kh_index, all occurrences per k-mer: counting insert -> slot-order ranks + CSR offsets -> scatter -> segment sort (kh_kernels_index.h).
+//             kh_windex: the same host code on a wide table (kh_index::kw == 2) and the kernels that touch a 32-byte slot (kh_kernels_index_wide.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
 #include "kh_kernels_values.h"
 #include "kh_kernels_index.h"
+#include "kh_kernels_index_wide.h"
 #include "../../include/kmerhash_amd.h"
 
 #include <string>
@@ -2328,7 +2330,7 @@ void fastq_mask_text(const uint8_t* text, uint64_t n, uint32_t* sums, uint64_t* 
   hipLaunchKernelGGL(k_fastq_mask, dim3((uint32_t)ntl), dim3(256), 0, stream, text, n, (const uint64_t*)offs, msk);
 }
 // shared body of kh_kmers[128]_from_sequence / kh_kmers[128]_from_fastq; kw: 64-bit words per k-mer (1: k <= 32, 2: k <= 64)
-// out_pos (kw == 1 only, n < 2^32): the byte offset of every window next to its k-mer (kh_kmers_from_sequence_pos / _fastq_pos)
+// out_pos (n < 2^32): the byte offset of every window next to its k-mer (kh_kmers[128]_from_sequence_pos / _fastq_pos)
 kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq,
                      uint64_t* out_kmers, uint64_t* n_out, int device, void* stream_, uint32_t* out_pos = nullptr) {
   kh_table* t = nullptr;
@@ -2365,7 +2367,9 @@ kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int c
     if (kw == 2) hipLaunchKernelGGL(k_kmers_count<2>, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
     else hipLaunchKernelGGL(k_kmers_count<1>, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
     hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, sums, nkt, offs);
-    if (out_pos && canonical) hipLaunchKernelGGL((k_kmers_emit_pos<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout, dpos);
+    if (out_pos && kw == 2 && canonical) hipLaunchKernelGGL((kw_kmers_emit_pos<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout, dpos);
+    else if (out_pos && kw == 2) hipLaunchKernelGGL((kw_kmers_emit_pos<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout, dpos);
+    else if (out_pos && canonical) hipLaunchKernelGGL((k_kmers_emit_pos<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout, dpos);
     else if (out_pos) hipLaunchKernelGGL((k_kmers_emit_pos<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout, dpos);
     else if (kw == 2 && canonical) hipLaunchKernelGGL((kw_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
     else if (kw == 2) hipLaunchKernelGGL((kw_kmers_emit<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
@@ -3050,6 +3054,21 @@ kh_status kh_kmers128_from_fastq(const void* text, uint64_t n, uint32_t k, int c
                                  int device, void* stream) {
   return kmers_impl(2, text, n, k, canonical, where, true, out_kmers, n_out, device, stream);
 }
+// 16-byte k-mers with the byte offset of their window (kh_kmers_from_sequence_pos / _fastq_pos for k = 1..64)
+kh_status kh_kmers128_from_sequence_pos(const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where,
+                                        uint64_t* out_kmers, uint32_t* out_pos, uint64_t* n_out, int device, void* stream) {
+  if (n_out) *n_out = 0;
+  if (n >> 32) return KH_ERR_INVALID;
+  if (n >= k && !out_pos) return KH_ERR_INVALID;
+  return kmers_impl(2, seq, n, k, canonical, where, false, out_kmers, n_out, device, stream, out_pos);
+}
+kh_status kh_kmers128_from_fastq_pos(const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where,
+                                     uint64_t* out_kmers, uint32_t* out_pos, uint64_t* n_out, int device, void* stream) {
+  if (n_out) *n_out = 0;
+  if (n >> 32) return KH_ERR_INVALID;
+  if (n >= k && !out_pos) return KH_ERR_INVALID;
+  return kmers_impl(2, text, n, k, canonical, where, true, out_kmers, n_out, device, stream, out_pos);
+}
 }  // extern "C"
 
 // ===================================================================================================
@@ -3060,6 +3079,7 @@ kh_status kh_kmers128_from_fastq(const void* text, uint64_t n, uint32_t k, int c
 // ===================================================================================================
 struct kh_index {
   kh_table* t = nullptr;
+  uint32_t kw = 1;                    // 64-bit words per key: 1 (kh_index_*), 2 (kh_wide_index_*: the table is a kh_wtable)
   int hash = 0, device = 0;
   uint64_t seed = 0;
   float min_lf = 0.f, max_lf = 0.f;
@@ -3070,7 +3090,18 @@ struct kh_index {
   bool built = false, prof = false;
   std::string err;
 };
+struct kh_windex : kh_index {};      // a distinct handle type for the C header; the host state is kh_index's, the kernels that touch a slot differ
 namespace {
+// the index's table: fresh, capacity 128, of the index's key width
+kh_status index_table_create(kh_index* x) {
+  if (x->kw == 2) {
+    kh_wtable* w = nullptr;
+    const kh_status st = kh_wide_create(&w, KH_KIND_ROBINHOOD, (kh_hash)x->hash, x->seed, 128, x->min_lf, x->max_lf, x->device);
+    x->t = w;
+    return st;
+  }
+  return kh_create(&x->t, KH_KIND_ROBINHOOD, 8, 4, (kh_hash)x->hash, x->seed, 128, x->min_lf, x->max_lf, x->device);
+}
 kh_status xfail(kh_index* x, kh_status s, const std::string& msg) { if (x) x->err = msg; return s; }
 // back to the state of kh_index_create: no arrays and a FRESH table (a cleared table would keep its capacity, and the layout of the next
 // build is promised to be that of a fresh table)
@@ -3080,7 +3111,7 @@ kh_status index_reset(kh_index* x) {
   pool_free(x->device, x->offsets); pool_free(x->device, x->positions);
   x->offsets = nullptr; x->positions = nullptr; x->total = 0; x->built = false;
   if (x->t) { kh_destroy(x->t); x->t = nullptr; }
-  const kh_status st = kh_create(&x->t, KH_KIND_ROBINHOOD, 8, 4, (kh_hash)x->hash, x->seed, 128, x->min_lf, x->max_lf, x->device);
+  const kh_status st = index_table_create(x);
   if (st != KH_OK) return xfail(x, st, "kh_index: the table could not be created");
   x->t->stream = x->stream; x->t->prof = x->prof;
   return KH_OK;
@@ -3093,6 +3124,19 @@ kh_status index_abandon(kh_index* x, kh_status s) {
 }
 inline uint32_t index_probe_grid(const kh_table* t, uint64_t n) {
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + KI_Q_TILE - 1) / KI_Q_TILE, (uint64_t)cu_count(t) * 8));
+}
+static_assert(KW_INDEX_Q_TILE == KI_Q_TILE, "one probe grid for both key widths");
+// (begin, count) per query: the lookup kernel of the index's key width
+void index_launch_lookup(kh_index* x, const uint64_t* q, uint64_t n, uint32_t* begin, uint32_t* cnt) {
+  kh_table* t = x->t;
+  Launch L(t, x->kw == 2 ? "kw_index_lookup" : "k_index_lookup");
+  if (x->kw == 2) {
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_index_lookup<HASH>), dim3(index_probe_grid(t, n)), dim3(KW_Q_THREADS), 0, t->stream, wide(t->cur), q, n, t->seed.s,
+                                               (const uint32_t*)x->offsets, (uint64_t)t->lsize, begin, cnt));
+  } else {
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_index_lookup<HASH>), dim3(index_probe_grid(t, n)), dim3(KH_Q_THREADS), 0, t->stream, narrow(t->cur), q, n, t->seed,
+                                               (const uint32_t*)x->offsets, begin, cnt));
+  }
 }
 // exclusive scan of n (> 0) device counts into n + 1 offsets of type OUT; ssums: ull[tiles + 1] of workspace
 template <typename OUT>
@@ -3110,7 +3154,8 @@ kh_status index_build_device(kh_index* x, const uint64_t* dk, const uint32_t* dp
   kh_table* t = x->t;
   // 1. the counting insert, unchanged: key set, size, capacity and slot order are those of kh_insert_reduce_plus into a fresh table
   uint64_t nins = 0;
-  kh_status st = kh_insert_reduce_plus(t, dk, nullptr, n, KH_MEM_DEVICE, &nins);
+  kh_status st = x->kw == 2 ? kh_wide_insert_reduce_plus(static_cast<kh_wtable*>(t), dk, nullptr, n, KH_MEM_DEVICE, &nins)
+                             : kh_insert_reduce_plus(t, dk, nullptr, n, KH_MEM_DEVICE, &nins);
   if (st != KH_OK) return st;
   const uint64_t size = t->lsize, cap = t->cur.cap;
   if (size == 0 || size > n) return fail(t, KH_ERR_HIP, "kh_index: internal: counting insert left an impossible size");
@@ -3123,7 +3168,14 @@ kh_status index_build_device(kh_index* x, const uint64_t* dk, const uint32_t* dp
   TAKE(sums, uint32_t, ntl); TAKE(toffs, uint64_t, ntl + 1); TAKE(counts, uint32_t, size); TAKE(cursor, uint32_t, size);
   TAKE(ssums, unsigned long long, nst + 1); TAKE(xlist, uint32_t, nsort); TAKE(xcount, uint32_t, 1); TAKE(scratch, uint32_t, n);
   // 2. the keys that share a home bucket in key order (the insert leaves their order to chance); rank of every live slot in slot order; counts[rank] = occurrences; the slot's value becomes the rank; offsets = scan(counts)
-  { Launch L(t, "k_index_rank");
+  if (x->kw == 2) {
+    Launch L(t, "kw_index_rank");
+    hipLaunchKernelGGL(kw_index_canon_runs, dim3(grid_for(cap, 256, (uint32_t)cu_count(t) * 8)), dim3(256), 0, t->stream, wide(t->cur).s, cap);
+    hipLaunchKernelGGL((k_values_tile_count<KV_WIDE>), dim3((uint32_t)ntl), dim3(KV_SEL_THREADS), 0, t->stream, (const void*)t->cur.p, cap, 0u, 0xFFFFFFFFu, sums);
+    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, (const uint32_t*)sums, ntl, toffs);
+    hipLaunchKernelGGL(kw_index_rank, dim3((uint32_t)ntl), dim3(KV_SEL_THREADS), 0, t->stream, wide(t->cur).s, cap, (const uint64_t*)toffs, counts);
+  } else {
+    Launch L(t, "k_index_rank");
     hipLaunchKernelGGL(k_index_canon_runs, dim3(grid_for(cap, 256, (uint32_t)cu_count(t) * 8)), dim3(256), 0, t->stream, narrow(t->cur).s, cap);
     hipLaunchKernelGGL((k_values_tile_count<KV_RH>), dim3((uint32_t)ntl), dim3(KV_SEL_THREADS), 0, t->stream, (const void*)t->cur.p, cap, 0u, 0xFFFFFFFFu, sums);
     hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, (const uint32_t*)sums, ntl, toffs);
@@ -3134,7 +3186,12 @@ kh_status index_build_device(kh_index* x, const uint64_t* dk, const uint32_t* dp
   // 3. scatter through per-key cursors
   HIPCHK(hipMemcpyAsync(cursor, x->offsets, size * 4, hipMemcpyDeviceToDevice, t->stream));
   HIPCHK(hipMemsetAsync(xcount, 0, 4, t->stream));
-  { Launch L(t, "k_index_scatter");
+  if (x->kw == 2) {
+    Launch L(t, "kw_index_scatter");
+    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_index_scatter<HASH>), dim3(index_probe_grid(t, n)), dim3(KW_Q_THREADS), 0, t->stream, wide(t->cur), dk, dp, n, t->seed.s,
+                                               cursor, x->positions, n, size));
+  } else {
+    Launch L(t, "k_index_scatter");
     KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_index_scatter<HASH>), dim3(index_probe_grid(t, n)), dim3(KH_Q_THREADS), 0, t->stream, narrow(t->cur), dk, dp, n, t->seed,
                                                cursor, x->positions, n)); }
   HIPCHK(hipGetLastError());
@@ -3153,7 +3210,7 @@ kh_status index_build_text(kh_index* x, const void* text, uint64_t n, uint32_t k
   if (!x) return KH_ERR_INVALID;
   if (n >> 32) return xfail(x, KH_ERR_INVALID, "kh_index: positions are 32-bit, a text of 2^32 bytes or more is refused");
   if (x->built) return xfail(x, KH_ERR_INVALID, "kh_index: the index is built already (kh_index_clear first)");
-  if (k < 1 || k > 32) return xfail(x, KH_ERR_INVALID, "kh_index: k must be 1..32");
+  if (k < 1 || k > 32 * x->kw) return xfail(x, KH_ERR_INVALID, x->kw == 2 ? "kh_wide_index: k must be 1..64" : "kh_index: k must be 1..32");
   if (n < k) return KH_OK;
   if (!text) return xfail(x, KH_ERR_INVALID, "null text");
   kh_table* t = x->t;
@@ -3161,14 +3218,14 @@ kh_status index_build_text(kh_index* x, const void* text, uint64_t n, uint32_t k
   // host text is staged once; k-mers and positions never leave the device
   const size_t sz_text = where == KH_MEM_HOST ? ((n + 255) & ~size_t(255)) : 0;
   char* blk = nullptr;
-  HIPCHK(pool_alloc(x->device, sz_text + n * 12, reinterpret_cast<void**>(&blk)));
+  HIPCHK(pool_alloc(x->device, sz_text + n * (8 * x->kw + 4), reinterpret_cast<void**>(&blk)));
   const void* dtext = text;
   hipError_t e = hipSuccess;
   if (where == KH_MEM_HOST) { e = hipMemcpyAsync(blk, text, n, hipMemcpyHostToDevice, t->stream); dtext = blk; }
   uint64_t* dk = reinterpret_cast<uint64_t*>(blk + sz_text);
-  uint32_t* dp = reinterpret_cast<uint32_t*>(blk + sz_text + n * 8);
+  uint32_t* dp = reinterpret_cast<uint32_t*>(blk + sz_text + n * 8 * x->kw);
   uint64_t m = 0;
-  kh_status st = e == hipSuccess ? kmers_impl(1, dtext, n, k, canonical, KH_MEM_DEVICE, fastq, dk, &m, x->device, t->stream, dp) : KH_ERR_HIP;
+  kh_status st = e == hipSuccess ? kmers_impl(x->kw, dtext, n, k, canonical, KH_MEM_DEVICE, fastq, dk, &m, x->device, t->stream, dp) : KH_ERR_HIP;
   if (st != KH_OK) fail(t, st, "kh_index: k-mer generation failed");
   else if (m) st = index_build_device(x, dk, dp, m);
   hipStreamSynchronize(t->stream);
@@ -3183,7 +3240,7 @@ kh_status kh_index_create(kh_index** out, kh_hash hash, uint64_t seed, float min
   if ((int)hash < 0 || (int)hash > 3) return KH_ERR_INVALID;
   kh_index* x = new kh_index();
   x->hash = (int)hash; x->seed = seed; x->min_lf = min_lf; x->max_lf = max_lf; x->device = device;
-  const kh_status st = kh_create(&x->t, KH_KIND_ROBINHOOD, 8, 4, hash, seed, 128, min_lf, max_lf, device);      // (no GPU: KH_ERR_HIP)
+  const kh_status st = index_table_create(x);      // (no GPU: KH_ERR_HIP)
   if (st != KH_OK) { delete x; return st; }
   *out = x;
   return KH_OK;
@@ -3222,10 +3279,11 @@ kh_status kh_index_build(kh_index* x, const void* keys, const void* pos, uint64_
   char* blk = nullptr;
   hipError_t e = hipSuccess;
   if (where == KH_MEM_HOST) {          // (not in the table's workspace: the counting insert resets it)
-    HIPCHK(pool_alloc(x->device, n * 12, reinterpret_cast<void**>(&blk)));
-    e = hipMemcpyAsync(blk, keys, n * 8, hipMemcpyHostToDevice, t->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(blk + n * 8, pos, n * 4, hipMemcpyHostToDevice, t->stream);
-    dk = reinterpret_cast<const uint64_t*>(blk); dp = reinterpret_cast<const uint32_t*>(blk + n * 8);
+    const uint64_t kb = n * 8 * x->kw;
+    HIPCHK(pool_alloc(x->device, kb + n * 4, reinterpret_cast<void**>(&blk)));
+    e = hipMemcpyAsync(blk, keys, kb, hipMemcpyHostToDevice, t->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk + kb, pos, n * 4, hipMemcpyHostToDevice, t->stream);
+    dk = reinterpret_cast<const uint64_t*>(blk); dp = reinterpret_cast<const uint32_t*>(blk + kb);
   }
   kh_status st = KH_ERR_HIP;
   if (e == hipSuccess) st = index_build_device(x, dk, dp, n); else fail(t, KH_ERR_HIP, "kh_index_build: staging the pairs failed");
@@ -3262,15 +3320,13 @@ kh_status kh_index_count(kh_index* x, const void* keys, uint64_t n, kh_mem where
   if (!keys || !out_counts) return xfail(x, KH_ERR_INVALID, "null argument");
   kh_table* t = x->t;
   HIPCHK(hipSetDevice(x->device));
-  { kh_status ps = arena_prepare(t, n * 12 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  { kh_status ps = arena_prepare(t, n * (8 * x->kw + 4) + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
   const uint64_t* q;
-  kh_status st = stage_in<uint64_t>(t, keys, n, where, &q);
+  kh_status st = stage_in<uint64_t>(t, keys, n * x->kw, where, &q);
   if (st != KH_OK) return st;
   uint32_t* dc = out_counts;
   if (where == KH_MEM_HOST) TAKE(dc, uint32_t, n);
-  { Launch L(t, "k_index_lookup");
-    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_index_lookup<HASH>), dim3(index_probe_grid(t, n)), dim3(KH_Q_THREADS), 0, t->stream, narrow(t->cur), q, n, t->seed,
-                                               (const uint32_t*)x->offsets, (uint32_t*)nullptr, dc)); }
+  index_launch_lookup(x, q, n, nullptr, dc);
   HIPCHK(hipGetLastError());
   if (where == KH_MEM_HOST) HIPCHK(hipMemcpyAsync(out_counts, dc, n * 4, hipMemcpyDeviceToHost, t->stream));
   HIPCHK(hipStreamSynchronize(t->stream));
@@ -3289,16 +3345,14 @@ kh_status kh_index_find(kh_index* x, const void* keys, uint64_t n, kh_mem where,
     return KH_OK;
   }
   const uint64_t nst = (n + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
-  { kh_status ps = arena_prepare(t, n * 24 + nst * 8 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  { kh_status ps = arena_prepare(t, n * (16 + 8 * x->kw) + nst * 8 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
   const uint64_t* q;
-  kh_status st = stage_in<uint64_t>(t, keys, n, where, &q);
+  kh_status st = stage_in<uint64_t>(t, keys, n * x->kw, where, &q);
   if (st != KH_OK) return st;
   uint32_t *begin, *cnt; unsigned long long* ssums; uint64_t* doff = out_offsets;
   TAKE(begin, uint32_t, n); TAKE(cnt, uint32_t, n); TAKE(ssums, unsigned long long, nst + 1);
   if (host) TAKE(doff, uint64_t, n + 1);
-  { Launch L(t, "k_index_lookup");
-    KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_index_lookup<HASH>), dim3(index_probe_grid(t, n)), dim3(KH_Q_THREADS), 0, t->stream, narrow(t->cur), q, n, t->seed,
-                                               (const uint32_t*)x->offsets, begin, cnt)); }
+  index_launch_lookup(x, q, n, begin, cnt);
   HIPCHK(hipGetLastError());
   st = index_scan<uint64_t>(t, cnt, n, ssums, doff);
   if (st != KH_OK) return st;
@@ -3318,5 +3372,49 @@ kh_status kh_index_find(kh_index* x, const void* keys, uint64_t n, kh_mem where,
   if (host) HIPCHK(hipMemcpyAsync(out_pos, dout, total * 4, hipMemcpyDeviceToHost, t->stream));
   HIPCHK(hipStreamSynchronize(t->stream));
   return KH_OK;
+}
+
+// ---- the index over 16-byte keys: the same host code (kh_index::kw == 2) on a wide table and the kw_index_* kernels
+kh_status kh_wide_index_create(kh_windex** out, kh_hash hash, uint64_t seed, float min_lf, float max_lf, int device) {
+  if (!out) return KH_ERR_INVALID;
+  *out = nullptr;
+  if ((int)hash < 0 || (int)hash > 3) return KH_ERR_INVALID;
+  kh_windex* x = new kh_windex();
+  x->kw = 2;
+  x->hash = (int)hash; x->seed = seed; x->min_lf = min_lf; x->max_lf = max_lf; x->device = device;
+  const kh_status st = index_table_create(x);      // (no GPU: KH_ERR_HIP)
+  if (st != KH_OK) { delete x; return st; }
+  *out = x;
+  return KH_OK;
+}
+kh_status kh_wide_index_destroy(kh_windex* x) { return kh_index_destroy(x); }
+kh_status kh_wide_index_set_stream(kh_windex* x, void* s) { return kh_index_set_stream(x, s); }
+const char* kh_wide_index_last_error(const kh_windex* x) { return kh_index_last_error(x); }
+kh_status kh_wide_index_clear(kh_windex* x) { return kh_index_clear(x); }
+kh_status kh_wide_index_size(const kh_windex* x, uint64_t* out) { return kh_index_size(x, out); }
+kh_status kh_wide_index_total(const kh_windex* x, uint64_t* out) { return kh_index_total(x, out); }
+kh_status kh_wide_index_capacity(const kh_windex* x, uint64_t* out) { return kh_index_capacity(x, out); }
+kh_status kh_wide_index_profile_enable(kh_windex* x, int on) { return kh_index_profile_enable(x, on); }
+kh_status kh_wide_index_profile_dump(kh_windex* x, char* buf, uint64_t cap) { return kh_index_profile_dump(x, buf, cap); }
+kh_status kh_wide_index_build(kh_windex* x, const void* keys, const void* pos, uint64_t n, kh_mem where) { return kh_index_build(x, keys, pos, n, where); }
+kh_status kh_wide_index_build_from_sequence(kh_windex* x, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where) {
+  return index_build_text(x, seq, n, k, canonical, where, false);
+}
+kh_status kh_wide_index_build_from_fastq(kh_windex* x, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where) {
+  return index_build_text(x, text, n, k, canonical, where, true);
+}
+kh_status kh_wide_index_export(kh_windex* x, uint64_t* keys_host, uint32_t* offsets_host, uint32_t* positions_host) {
+  return kh_index_export(x, keys_host, offsets_host, positions_host);
+}
+// the info bytes of the index's table (kh_wide_export_info of it): what pins the layout to the counting twin's
+kh_status kh_wide_index_export_info(kh_windex* x, uint8_t* out_host) {
+  if (!x) return KH_ERR_INVALID;
+  const kh_status st = kh_export_info(x->t, out_host);
+  if (st != KH_OK) x->err = x->t->err;
+  return st;
+}
+kh_status kh_wide_index_count(kh_windex* x, const void* keys, uint64_t n, kh_mem where, uint32_t* out_counts) { return kh_index_count(x, keys, n, where, out_counts); }
+kh_status kh_wide_index_find(kh_windex* x, const void* keys, uint64_t n, kh_mem where, uint64_t* out_offsets, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out) {
+  return kh_index_find(x, keys, n, where, out_offsets, out_pos, cap_out, n_out);
 }
 }  // extern "C"

@@ -19,35 +19,46 @@ SORT_TILE = 4096
 
 class KmerPositionIndex:
     """k-mer -> ascending positions of all its occurrences.  64-bit k-mers (k <= 32), one GPU."""
+    PREFIX = "kh_index_"          # the C entry points of this key width
+    KMAX = 32
+    WORDS = 1                     # 64-bit words per key
 
     def __init__(self, k=31, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0, seed=43):
-        if not 1 <= int(k) <= 32:
-            raise ValueError("k must be 1..32, got %r" % (k,))
+        if not 1 <= int(k) <= self.KMAX:
+            raise ValueError("k must be 1..%d, got %r" % (self.KMAX, k))
         self.k, self.canonical, self.device = int(k), bool(canonical), int(device)
         self._L = K.lib()
         self._h = C.c_void_p()
-        st = self._L.kh_index_create(C.byref(self._h), _hash_id(hash), seed, min_load_factor, max_load_factor, self.device)
+        st = self._fn("create")(C.byref(self._h), _hash_id(hash), seed, min_load_factor, max_load_factor, self.device)
         if st != K.KH_OK:
             self._h = C.c_void_p()
-            raise KhError(st, "kh_index_create failed (is a GPU visible and the HIP library built?)")
+            raise KhError(st, self.PREFIX + "create failed (is a GPU visible and the HIP library built?)")
 
     # -- plumbing --------------------------------------------------------------------------------
+    def _fn(self, name):
+        return getattr(self._L, self.PREFIX + name)
+
+    def _kbuf(self, keys):
+        """a key batch -> (_Buf over its words, number of keys)"""
+        b = _Buf(keys, np.uint64, 8)
+        return b, b.n
+
     def _chk(self, st):
         if st != K.KH_OK:
-            raise KhError(st, self._L.kh_index_last_error(self._h).decode())
+            raise KhError(st, self._fn("last_error")(self._h).decode())
 
     def _stream(self, *bufs):
         if torch is not None and any(b.where == K.KH_MEM_DEVICE for b in bufs):
-            self._L.kh_index_set_stream(self._h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+            self._fn("set_stream")(self._h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
 
     def _scalar(self, name):
         v = C.c_uint64()
-        self._chk(getattr(self._L, "kh_index_" + name)(self._h, C.byref(v)))
+        self._chk(self._fn(name)(self._h, C.byref(v)))
         return v.value
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
-            self._L.kh_index_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -60,31 +71,31 @@ class KmerPositionIndex:
     def build(self, keys, pos):
         """(k-mer, position) pairs in any order: uint64 keys and uint32 positions, both numpy or both CUDA tensors.  The index must
         be empty (clear() first); duplicate pairs are kept."""
-        kb, pb = _Buf(keys, np.uint64, 8), _Buf(pos, np.uint32, 4)
-        if kb.n != pb.n or kb.where != pb.where:
+        (kb, n), pb = self._kbuf(keys), _Buf(pos, np.uint32, 4)
+        if n != pb.n or kb.where != pb.where:
             raise ValueError("keys and positions must have the same length and live in the same memory")
         self._stream(kb, pb)
-        self._chk(self._L.kh_index_build(self._h, kb.ptr, pb.ptr, kb.n, kb.where))
-        return kb.n
+        self._chk(self._fn("build")(self._h, kb.ptr, pb.ptr, n, kb.where))
+        return n
 
     def _build_text(self, fn, text):
         if isinstance(text, (bytes, bytearray)):
             text = np.frombuffer(text, dtype=np.uint8)
         b = _Buf(text, np.uint8, 1)
         self._stream(b)
-        self._chk(getattr(self._L, fn)(self._h, b.ptr, b.n, self.k, 1 if self.canonical else 0, b.where))
+        self._chk(self._fn(fn)(self._h, b.ptr, b.n, self.k, 1 if self.canonical else 0, b.where))
         return self.total()
 
     def build_sequences(self, seq):
         """every window of k valid bases of `seq` with its byte offset in `seq`; returns the number of positions indexed"""
-        return self._build_text("kh_index_build_from_sequence", seq)
+        return self._build_text("build_from_sequence", seq)
 
     def build_fastq(self, text):
         """the same over raw FASTQ text (whole 4-line records); positions are byte offsets into the text"""
-        return self._build_text("kh_index_build_from_fastq", text)
+        return self._build_text("build_from_fastq", text)
 
     def clear(self):
-        self._chk(self._L.kh_index_clear(self._h))
+        self._chk(self._fn("clear")(self._h))
 
     # -- state -----------------------------------------------------------------------------------
     def size(self):
@@ -105,24 +116,24 @@ class KmerPositionIndex:
         """(keys uint64[size] in slot order, offsets uint32[size + 1], positions uint32[total]) as numpy arrays: the positions of
         keys[r] are positions[offsets[r]:offsets[r + 1]], ascending"""
         size, total = self.size(), self.total()
-        keys = np.zeros(size, dtype=np.uint64)
+        keys = np.zeros(size if self.WORDS == 1 else (size, self.WORDS), dtype=np.uint64)
         offsets = np.zeros(size + 1, dtype=np.uint32)
         positions = np.zeros(total, dtype=np.uint32)
-        self._chk(self._L.kh_index_export(self._h, keys.ctypes.data, offsets.ctypes.data, positions.ctypes.data))
+        self._chk(self._fn("export")(self._h, keys.ctypes.data, offsets.ctypes.data, positions.ctypes.data))
         return keys, offsets, positions
 
     # -- lookup ----------------------------------------------------------------------------------
     def count(self, keys):
         """occurrences of every query key (uint32; 0 on a miss)"""
-        q = _Buf(keys, np.uint64, 8)
+        q, n = self._kbuf(keys)
         self._stream(q)
         if q.where == K.KH_MEM_DEVICE:
-            out = torch.zeros(q.n, dtype=torch.int32, device=q.device)
+            out = torch.zeros(n, dtype=torch.int32, device=q.device)
             optr = out.data_ptr()
         else:
-            out = np.zeros(q.n, dtype=np.uint32)
+            out = np.zeros(n, dtype=np.uint32)
             optr = out.ctypes.data
-        self._chk(self._L.kh_index_count(self._h, q.ptr, q.n, q.where, optr))
+        self._chk(self._fn("count")(self._h, q.ptr, n, q.where, optr))
         return out
 
     def find(self, keys, positions=True, cap_out=None):
@@ -130,18 +141,18 @@ class KmerPositionIndex:
         are positions[offsets[i]:offsets[i + 1]], ascending; a repeated key repeats its positions.  positions=False: offsets only
         (positions is None).  cap_out: room to offer for the positions (default: exactly what is needed, found by an offsets-only pass);
         too little raises KhError(KH_ERR_INVALID)."""
-        q = _Buf(keys, np.uint64, 8)
+        q, n = self._kbuf(keys)
         self._stream(q)
         dev = q.where == K.KH_MEM_DEVICE
         n_out = C.c_uint64()
         if dev:
-            offs = torch.zeros(q.n + 1, dtype=torch.int64, device=q.device)
+            offs = torch.zeros(n + 1, dtype=torch.int64, device=q.device)
             optr = offs.data_ptr()
         else:
-            offs = np.zeros(q.n + 1, dtype=np.uint64)
+            offs = np.zeros(n + 1, dtype=np.uint64)
             optr = offs.ctypes.data
         if not positions or cap_out is None:
-            self._chk(self._L.kh_index_find(self._h, q.ptr, q.n, q.where, optr, None, 0, C.byref(n_out)))
+            self._chk(self._fn("find")(self._h, q.ptr, n, q.where, optr, None, 0, C.byref(n_out)))
             if not positions:
                 return offs, None
             cap_out = n_out.value
@@ -152,19 +163,42 @@ class KmerPositionIndex:
         else:
             out = np.zeros(max(cap_out, 1), dtype=np.uint32)
             pptr = out.ctypes.data
-        self._chk(self._L.kh_index_find(self._h, q.ptr, q.n, q.where, optr, pptr, cap_out, C.byref(n_out)))
+        self._chk(self._fn("find")(self._h, q.ptr, n, q.where, optr, pptr, cap_out, C.byref(n_out)))
         return offs, out[: n_out.value]
 
     # -- measurement -----------------------------------------------------------------------------
     def profile_enable(self, on=True):
-        self._chk(self._L.kh_index_profile_enable(self._h, 1 if on else 0))
+        self._chk(self._fn("profile_enable")(self._h, 1 if on else 0))
 
     def profile(self):
         """{kernel name: (launches, total ms)} since profile_enable(True)"""
         buf = C.create_string_buffer(1 << 16)
-        self._chk(self._L.kh_index_profile_dump(self._h, buf, len(buf)))
+        self._chk(self._fn("profile_dump")(self._h, buf, len(buf)))
         out = {}
         for line in buf.value.decode().splitlines():
             name, launches, ms = line.split()
             out[name] = (int(launches), float(ms))
         return out
+
+
+class WideKmerPositionIndex(KmerPositionIndex):
+    """KmerPositionIndex over 16-byte k-mers (k = 1..64; kh_wide_index_*): keys are (n, 2) uint64 numpy arrays or (n, 2) int64 CUDA
+    tensors, {w0, w1} per k-mer as kmerhash_amd.wide takes them; export() returns keys of shape (size, 2).  The keys that share a
+    home bucket stand in ascending order of (w1 << 64) | w0."""
+    PREFIX = "kh_wide_index_"
+    KMAX = 64
+    WORDS = 2
+
+    def __init__(self, k=63, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0, seed=43):
+        super().__init__(k, canonical, hash, min_load_factor, max_load_factor, device, seed)
+
+    def export_info(self):
+        """the Robin Hood info byte of every bucket of the index's table (uint8[capacity]): the counting twin's"""
+        out = np.zeros(self.capacity(), dtype=np.uint8)
+        self._chk(self._L.kh_wide_index_export_info(self._h, out.ctypes.data))
+        return out
+
+    def _kbuf(self, keys):
+        from .wide import _keys
+        b = _keys(keys)
+        return b, b.n // 2

@@ -199,11 +199,36 @@ def _kmers(fn_name, words, seq, k, canonical, device):
     return out[: n_out.value]
 
 
-def kmers128_from_sequence(seq, k=63, canonical=True, device=0, _fastq=False):
-    """-> (n, 2) k-mers (numpy uint64 for host input, torch int64 CUDA tensor for device input), sequence order; k = 1..64"""
+def _kmers_pos(fn_name, seq, k, canonical, device):
+    """16-byte k-mers with the byte offsets of their windows (kh_kmers128_from_sequence_pos / _fastq_pos)"""
+    if isinstance(seq, (bytes, bytearray)):
+        seq = np.frombuffer(seq, dtype=np.uint8)
+    b = _Buf(seq, np.uint8, 1)
+    n_out = C.c_uint64()
+    if b.where == K.KH_MEM_DEVICE:
+        out = torch.empty((max(b.n, 1), 2), dtype=torch.int64, device=b.device)
+        pos = torch.empty(max(b.n, 1), dtype=torch.int32, device=b.device)
+        optr, pptr, stream = out.data_ptr(), pos.data_ptr(), torch.cuda.current_stream(device).cuda_stream
+    else:
+        out = np.zeros((max(b.n, 1), 2), dtype=np.uint64)
+        pos = np.zeros(max(b.n, 1), dtype=np.uint32)
+        optr, pptr, stream = out.ctypes.data, pos.ctypes.data, None
+    st = getattr(K.lib(), fn_name)(b.ptr, b.n, k, 1 if canonical else 0, b.where, optr, pptr, C.byref(n_out), device, stream)
+    if st != K.KH_OK:
+        raise KhError(st, fn_name)
+    return out[: n_out.value], pos[: n_out.value]
+
+
+def kmers128_from_sequence(seq, k=63, canonical=True, device=0, _fastq=False, with_positions=False):
+    """-> (n, 2) k-mers (numpy uint64 for host input, torch int64 CUDA tensor for device input), sequence order; k = 1..64.
+    with_positions: -> (k-mers, positions): positions[i] (numpy uint32 / torch int32) is the byte offset in `seq` of the first base of
+    the window that gave k-mers[i] (a text of 2^32 bytes or more is refused)"""
+    if with_positions:
+        return _kmers_pos("kh_kmers128_from_fastq_pos" if _fastq else "kh_kmers128_from_sequence_pos", seq, k, canonical, device)
     return _kmers("kh_kmers128_from_fastq" if _fastq else "kh_kmers128_from_sequence", 2, seq, k, canonical, device)
 
 
-def kmers128_from_fastq(text, k=63, canonical=True, device=0):
-    """raw FASTQ text (whole 4-line records) -> (n, 2) k-mers of the sequence lines (record structure resolved on the GPU)"""
-    return kmers128_from_sequence(text, k, canonical, device, _fastq=True)
+def kmers128_from_fastq(text, k=63, canonical=True, device=0, with_positions=False):
+    """raw FASTQ text (whole 4-line records) -> (n, 2) k-mers of the sequence lines (record structure resolved on the GPU);
+    with_positions: -> (k-mers, byte offsets of their windows in the raw text)"""
+    return kmers128_from_sequence(text, k, canonical, device, _fastq=True, with_positions=with_positions)
