@@ -279,8 +279,8 @@ kh_status kh_kmers_from_fastq_pos(const void* text /*[h|d] u8[n]*/, uint64_t n, 
                                   uint64_t* out_kmers /*[h|d]*/, uint32_t* out_pos /*[h|d]*/, uint64_t* n_out, int device, void* hip_stream);
 /* ---- k-mer position index: ALL occurrences per k-mer (the reference's driver offers PositionIndex<MapType> over a multimap next to
  *      CountIndex, BenchmarkKmerIndex.cpp:342-449; the multimap is kmerind's and absent from the reference tree: the contract below is
- *      this library's).  A STATIC index of 64-bit keys (k <= 32) on one GPU: built once from one batch of (key, position) pairs, then
- *      queried.  State: one Robin Hood table owned by the index plus offsets u32[size + 1] and positions u32[total] in device memory.
+ *      this library's).  An index of 64-bit keys (k <= 32) on one GPU: built from a batch of (key, position) pairs, queried, and changed
+ *      batch by batch (kh_index_append*, kh_index_erase, kh_index_erase_counts below).  State: one Robin Hood table owned by the index plus offsets u32[size + 1] and positions u32[total] in device memory.
  *      After a build the table's value of a key is its RANK among the live slots in slot order (0..size-1) and positions[offsets[rank]
  *      .. offsets[rank + 1]) are the positions of that key: a lookup reads one slot and two adjacent offsets words.
  *      kh_index_build: the index must be empty (else KH_ERR_INVALID; kh_index_clear empties it); n >= 2^32: KH_ERR_INVALID before
@@ -294,8 +294,7 @@ kh_status kh_kmers_from_fastq_pos(const void* text /*[h|d] u8[n]*/, uint64_t n, 
  *      kh_index_build_from_sequence / _from_fastq: kh_kmers_from_sequence_pos / _fastq_pos and the build, on device buffers (host text
  *      is staged once; k-mers and positions never visit the host).
  *      kh_index_export: keys in slot order (the order of kh_to_vector), offsets and positions, into host buffers (any may be NULL).
- *      Appending to or erasing from a built index, the linear-probe layout and a strand bit are not supported; 16-byte keys (k <= 64)
- *      are kh_wide_index_* below. */
+ *      The linear-probe layout and a strand bit are not supported; 16-byte keys (k <= 64) are kh_wide_index_* below. */
 typedef struct kh_index kh_index;
 kh_status kh_index_create(kh_index** out, kh_hash hash, uint64_t seed, float min_lf, float max_lf, int device);
 kh_status kh_index_destroy(kh_index* x);
@@ -309,6 +308,33 @@ kh_status kh_index_size(const kh_index* x, uint64_t* distinct_keys);
 kh_status kh_index_total(const kh_index* x, uint64_t* n_positions);
 kh_status kh_index_capacity(const kh_index* x, uint64_t* buckets);
 kh_status kh_index_export(kh_index* x, uint64_t* keys_host /*[size]*/, uint32_t* offsets_host /*[size+1]*/, uint32_t* positions_host /*[total]*/);
+/* ---- changing a built index.  kh_index_append adds n pairs to an index in ANY state; on an empty index it is kh_index_build (the same
+ *      kernels, the same bytes).  After build(A1), append(A2), ..., append(Am): count, find and export are those of the index of the
+ *      concatenated pairs -- every key's positions ascend, duplicate pairs are kept -- and key set, size, capacity and info bytes of the
+ *      table are those of a fresh counting table after kh_insert_reduce_plus(A1), ..., kh_insert_reduce_plus(Am) in that order, the keys
+ *      of one home bucket in ascending key order.  The export is a function of the SEQUENCE OF BATCH MULTISETS: permuting the pairs
+ *      inside a batch changes no byte, and where that table's capacity equals the capacity of one insert of the concatenation the export
+ *      is byte-identical to the one-shot build.
+ *      kh_index_append_from_sequence / _from_fastq: the windows of kh_kmers_from_sequence_pos / _fastq_pos with pos_base added to every
+ *      window position on the device, so that several texts share one coordinate space.
+ *      kh_index_erase removes every occurrence of the given keys (misses and repeated keys are harmless); kh_index_erase_counts removes
+ *      every key whose number of occurrences lies in the closed range [lo, hi] (the range language of kh_erase_values; lo > hi is the
+ *      empty range: KH_OK, nothing erased).  *n_keys_erased: distinct keys removed, *n_pos_erased: positions removed (either may be
+ *      NULL).  Afterwards the index is that of the pairs whose key survives, and the table equals the counting twin after kh_erase of
+ *      the same keys (size, capacity, info bytes; home-bucket runs in key order).  Erasing every key leaves a usable empty index ON THE
+ *      TABLE AS kh_erase LEFT IT: it keeps its capacity, like a cleared table (kh_clear), unlike kh_index_clear, which goes back to a
+ *      fresh table of capacity 128 -- a later append or build lays out like the twin with the same history.
+ *      Refused with KH_ERR_INVALID before anything is touched (the index unchanged): a null argument, total + n >= 2^32,
+ *      pos_base + n > 2^32 (a window position would wrap), k out of range.  A failure after the table was touched
+ *      (KH_ERR_PROBE_OVERFLOW, KH_ERR_NOMEM, a HIP error) leaves the index EMPTY as a failed build does (fresh table); the error text
+ *      survives.  Every call synchronises the index's stream.  Peak device memory of an append or erase: the old and the new positions
+ *      (and offsets) arrays side by side, the batch (for an append with 4 B of zero values per pair during the table insert), and for an
+ *      append the sort scratch of the build (4 B per position). */
+kh_status kh_index_append(kh_index* x, const void* keys /*[h|d] u64[n]*/, const void* pos /*[h|d] u32[n]*/, uint64_t n, kh_mem where);
+kh_status kh_index_append_from_sequence(kh_index* x, const void* seq /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, int canonical, kh_mem where, uint32_t pos_base);
+kh_status kh_index_append_from_fastq(kh_index* x, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, int canonical, kh_mem where, uint32_t pos_base);
+kh_status kh_index_erase(kh_index* x, const void* keys /*[h|d] u64[n]*/, uint64_t n, kh_mem where, uint64_t* n_keys_erased, uint64_t* n_pos_erased);
+kh_status kh_index_erase_counts(kh_index* x, uint32_t lo, uint32_t hi, uint64_t* n_keys_erased, uint64_t* n_pos_erased);
 /* occurrences of every query key, 0 on a miss */
 kh_status kh_index_count(kh_index* x, const void* keys /*[h|d] u64[n]*/, uint64_t n, kh_mem where, uint32_t* out_counts /*[h|d] u32[n]*/);
 /* a CSR in query order: out_offsets = exclusive scan of the counts, out_offsets[n] = *n_out = the number of positions; the positions
@@ -449,7 +475,7 @@ kh_status kh_profile_query(kh_table* t, const char* prefix, double* total_ms, ui
 kh_status kh_profile_dump(kh_table* t, char* buf, uint64_t cap);
 
 /* ---- the position index over 16-byte keys (k-mers with k <= 64): kh_index_* word for word with a key of two 64-bit words {w0, w1}
- *      (keys u64[2n], as kh_wide_* takes them), on the wide Robin Hood table.  Static, built once from an empty index; duplicate pairs
+ *      (keys u64[2n], as kh_wide_* takes them), on the wide Robin Hood table.  Built from an empty index; duplicate pairs
  *      kept; the positions of a key ascend; kh_wide_index_find returns a CSR in query order whose total is known before anything is
  *      written (too small a cap_out: KH_ERR_INVALID, the output buffers untouched); a failed build leaves the index empty; n >= 2^32 is
  *      refused; without a GPU kh_wide_index_create returns KH_ERR_HIP and a null handle.  After a build key set, size, capacity and info
@@ -458,7 +484,9 @@ kh_status kh_profile_dump(kh_table* t, char* buf, uint64_t cap);
  *      which stand in ascending order of the 128-bit value (w1 << 64) | w0 -- so the export depends on the multiset of pairs alone.
  *      kh_wide_index_build_from_sequence / _from_fastq: kh_kmers128_from_sequence_pos / _fastq_pos and the build, k = 1..64.
  *      kh_wide_index_export: keys_host u64[2 size] in slot order (the order of kh_wide_to_vector).
- *      Not supported: appending to or erasing from a built index, a strand bit, read-id decoding, 64-bit positions. */
+ *      kh_wide_index_append* / _erase / _erase_counts: the contract of kh_index_append* / kh_index_erase / kh_index_erase_counts (twin:
+ *      kh_wide_insert_reduce_plus batch by batch, kh_wide_erase), keys u64[2n], k = 1..64.
+ *      Not supported: a strand bit, read-id decoding, 64-bit positions. */
 typedef struct kh_windex kh_windex;
 kh_status kh_wide_index_create(kh_windex** out, kh_hash hash, uint64_t seed, float min_lf, float max_lf, int device);
 kh_status kh_wide_index_destroy(kh_windex* x);
@@ -468,6 +496,11 @@ kh_status kh_wide_index_clear(kh_windex* x);
 kh_status kh_wide_index_build(kh_windex* x, const void* keys /*[h|d] u64[2n]*/, const void* pos /*[h|d] u32[n]*/, uint64_t n, kh_mem where);
 kh_status kh_wide_index_build_from_sequence(kh_windex* x, const void* seq /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, int canonical, kh_mem where);
 kh_status kh_wide_index_build_from_fastq(kh_windex* x, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, int canonical, kh_mem where);
+kh_status kh_wide_index_append(kh_windex* x, const void* keys /*[h|d] u64[2n]*/, const void* pos /*[h|d] u32[n]*/, uint64_t n, kh_mem where);
+kh_status kh_wide_index_append_from_sequence(kh_windex* x, const void* seq /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, int canonical, kh_mem where, uint32_t pos_base);
+kh_status kh_wide_index_append_from_fastq(kh_windex* x, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, int canonical, kh_mem where, uint32_t pos_base);
+kh_status kh_wide_index_erase(kh_windex* x, const void* keys /*[h|d] u64[2n]*/, uint64_t n, kh_mem where, uint64_t* n_keys_erased, uint64_t* n_pos_erased);
+kh_status kh_wide_index_erase_counts(kh_windex* x, uint32_t lo, uint32_t hi, uint64_t* n_keys_erased, uint64_t* n_pos_erased);
 kh_status kh_wide_index_size(const kh_windex* x, uint64_t* distinct_keys);
 kh_status kh_wide_index_total(const kh_windex* x, uint64_t* n_positions);
 kh_status kh_wide_index_capacity(const kh_windex* x, uint64_t* buckets);

@@ -69,6 +69,9 @@ SYMBOLS = [
     "kh_wide_index_create", "kh_wide_index_destroy", "kh_wide_index_set_stream", "kh_wide_index_last_error", "kh_wide_index_clear", "kh_wide_index_build",
     "kh_wide_index_build_from_sequence", "kh_wide_index_build_from_fastq", "kh_wide_index_size", "kh_wide_index_total", "kh_wide_index_capacity",
     "kh_wide_index_export", "kh_wide_index_export_info", "kh_wide_index_count", "kh_wide_index_find", "kh_wide_index_profile_enable", "kh_wide_index_profile_dump",
+    # changing a built index: append batches, erase keys, erase by occurrence count (both key widths)
+    "kh_index_append", "kh_index_append_from_sequence", "kh_index_append_from_fastq", "kh_index_erase", "kh_index_erase_counts",
+    "kh_wide_index_append", "kh_wide_index_append_from_sequence", "kh_wide_index_append_from_fastq", "kh_wide_index_erase", "kh_wide_index_erase_counts",
 ]
 
 _lib = None
@@ -224,6 +227,11 @@ def lib():
         getattr(L, pre + "find").argtypes = [vp, vp, u64, i32, vp, vp, u64, pu64]
         getattr(L, pre + "profile_enable").argtypes = [vp, i32]
         getattr(L, pre + "profile_dump").argtypes = [vp, C.c_char_p, u64]
+        getattr(L, pre + "append").argtypes = [vp, vp, vp, u64, i32]
+        getattr(L, pre + "append_from_sequence").argtypes = [vp, vp, u64, u32, i32, i32, u32]
+        getattr(L, pre + "append_from_fastq").argtypes = [vp, vp, u64, u32, i32, i32, u32]
+        getattr(L, pre + "erase").argtypes = [vp, vp, u64, i32, pu64, pu64]
+        getattr(L, pre + "erase_counts").argtypes = [vp, u32, u32, pu64, pu64]
     L.kh_wide_index_export_info.argtypes = [vp, vp]
     for s in SYMBOLS:
         if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error", "kh_wide_index_last_error"):

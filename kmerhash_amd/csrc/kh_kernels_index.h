@@ -418,3 +418,206 @@ __global__ __launch_bounds__(256) void k_index_gather(const uint32_t* __restrict
     out[j] = positions[(uint64_t)begin[lo] + (j - qoff[lo])];
   }
 }
+
+// ---------------------------------------------------------------------------------------------
+// mutation of a built index (kh_index_append* / kh_index_erase / kh_index_erase_counts, both key widths): the CSR is carried across a
+// change of the key set.  The slot's value is the link -- it travels with its key through every insert, erase and re-layout of the
+// table.  Append: k_index_stamp (value = old rank + 1) -> the table's own reducer insert with zero values (old keys keep the stamp, new
+// keys read 0) -> canonical runs -> k_index_rank_carry (new rank into the slot, oldrank[new rank], counts[new rank] = length of the old
+// segment) -> k_index_count_pairs (+1 per pair of the batch) -> scan -> k_index_move (old segments to the front of the new ones,
+// cursors behind them) -> the build's scatter and sorts.  Erase: the table's own erase (the survivors keep their rank: no stamp) ->
+// canonical runs -> k_index_rank_carry -> scan -> k_index_move.  The kernels that only read value and info are templates over the slot
+// layout (KV_RH / KV_WIDE) and serve both widths; the probe of the batch has a sibling in kh_kernels_index_wide.h.
+// ---------------------------------------------------------------------------------------------
+#define KI_NEW_KEY 0xFFFFFFFFu
+template <int LAY>
+__global__ __launch_bounds__(KV_MARK_THREADS) void k_index_stamp(void* __restrict__ slots, uint64_t cap) {
+  typedef typename KvSlot<LAY>::type Slot;
+  Slot* S = static_cast<Slot*>(slots);
+  const uint64_t span = (uint64_t)gridDim.x * KV_MARK_THREADS;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * KV_MARK_THREADS; i0 < cap; i0 += span * KV_MARK_ITEMS) {
+    KvItem it[KV_MARK_ITEMS];
+#pragma unroll
+    for (int j = 0; j < KV_MARK_ITEMS; ++j) {
+      const uint64_t i = i0 + (uint64_t)j * span + threadIdx.x;
+      it[j] = kv_ld<LAY>(slots, i < cap ? i : cap - 1);
+    }
+#pragma unroll
+    for (int j = 0; j < KV_MARK_ITEMS; ++j) {
+      const uint64_t i = i0 + (uint64_t)j * span + threadIdx.x;
+      if (i < cap && kv_live<LAY>(it[j].info)) S[i].val = it[j].val + 1u;          // (size < 2^32: rank + 1 fits)
+    }
+  }
+}
+// k_index_rank on either layout, for a table whose live values are old rank + bias (bias 1: stamped, 0 is a key the batch brought;
+// bias 0: every key is an old one).  Nothing is assumed about the slot order of the survivors: a run that wrapped past the last slot can
+// unwrap, keys of one home bucket change places -- the old rank is read from the slot, not counted.
+template <int LAY>
+__global__ __launch_bounds__(KV_SEL_THREADS) void k_index_rank_carry(void* __restrict__ slots, uint64_t cap, const uint64_t* __restrict__ tile_off,
+                                                                     const uint32_t* __restrict__ old_off, uint64_t old_size, uint32_t bias, uint64_t new_size,
+                                                                     uint32_t* __restrict__ counts, uint32_t* __restrict__ oldrank) {
+  __shared__ uint32_t wcnt[KV_SEL_ROWS * (KV_SEL_THREADS / 64)];
+  typedef typename KvSlot<LAY>::type Slot;
+  Slot* S = static_cast<Slot*>(slots);
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const uint64_t tbase = (uint64_t)blockIdx.x * KV_SEL_TILE;
+  KvItem it[KV_SEL_ROWS];
+#pragma unroll
+  for (int j = 0; j < KV_SEL_ROWS; ++j) {
+    const uint64_t i = tbase + (uint64_t)j * KV_SEL_THREADS + tid;
+    it[j] = kv_ld<LAY>(slots, i < cap ? i : cap - 1);
+  }
+  uint32_t hit = 0, rank[KV_SEL_ROWS];
+#pragma unroll
+  for (int j = 0; j < KV_SEL_ROWS; ++j) {
+    const uint64_t i = tbase + (uint64_t)j * KV_SEL_THREADS + tid;
+    const bool m = i < cap && kv_live<LAY>(it[j].info);
+    const unsigned long long b = __ballot(m);
+    rank[j] = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) wcnt[j * (KV_SEL_THREADS / 64) + wid] = (uint32_t)__popcll(b);
+    hit |= m ? (1u << j) : 0u;
+  }
+  __syncthreads();
+  const uint64_t obase = tile_off[blockIdx.x];
+  uint32_t acc = 0;
+#pragma unroll
+  for (int j = 0; j < KV_SEL_ROWS; ++j) {
+    uint32_t pre = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < KV_SEL_THREADS / 64; ++w) { if (w == wid) pre = acc; acc += wcnt[j * (KV_SEL_THREADS / 64) + w]; }
+    if ((hit >> j) & 1u) {
+      const uint64_t i = tbase + (uint64_t)j * KV_SEL_THREADS + tid;
+      const uint64_t r = obase + pre + rank[j];
+      const uint32_t v = it[j].val;
+      uint32_t orank = KI_NEW_KEY, len = 0;
+      if (v >= bias && (uint64_t)(v - bias) < old_size) { orank = v - bias; len = old_off[orank + 1] - old_off[orank]; }
+      if (r < new_size) { counts[r] = len; oldrank[r] = orank; }
+      S[i].val = (uint32_t)r;
+    }
+  }
+}
+// the batch counted onto the seeded counts: the probe of k_index_scatter, one atomic per pair
+template <int HASH>
+__global__ __launch_bounds__(KH_Q_THREADS) void k_index_count_pairs(KhSlots T, const uint64_t* __restrict__ keys, uint64_t n, KhSeed seed, uint32_t* __restrict__ counts,
+                                                                    uint64_t nranks) {
+  for (uint64_t base = (uint64_t)blockIdx.x * KI_Q_TILE; base < n; base += (uint64_t)gridDim.x * KI_Q_TILE) {
+    uint64_t key[KH_Q_ITEMS]; uint32_t r[KH_Q_ITEMS];
+    uint32_t valid = 0;
+#pragma unroll
+    for (int j = 0; j < KH_Q_ITEMS; ++j) {
+      const uint64_t i = base + (uint64_t)j * KH_Q_THREADS + threadIdx.x;
+      key[j] = 0; r[j] = 0;
+      if (i < n) { key[j] = keys[i]; valid |= 1u << j; }
+    }
+    const uint32_t hit = kh_probe_items<KHK_RH, HASH, false>(T, key, valid, seed, r);
+#pragma unroll
+    for (int j = 0; j < KH_Q_ITEMS; ++j)
+      if (((hit >> j) & 1u) && r[j] < nranks) atomicAdd(&counts[r[j]], 1u);
+  }
+}
+// old segments into the new positions array, balanced over OUTPUT elements as k_index_gather is: output j finds its new segment by
+// binary search in the new offsets (they ascend strictly: every key of the index occurs at least once) and, while it lies in the part
+// the old segment fills, copies one position; a segment of 10^6 entries is 10^6 independent lanes.  The lane at the head of a segment
+// sets the cursor the scatter continues from (cursor == null: an erase, nothing follows).
+__global__ __launch_bounds__(256) void k_index_move(const uint32_t* __restrict__ old_pos, const uint32_t* __restrict__ old_off, uint64_t old_size, uint64_t old_total,
+                                                    const uint32_t* __restrict__ new_off, const uint32_t* __restrict__ oldrank, uint64_t new_size, uint64_t new_total,
+                                                    uint32_t* __restrict__ new_pos, uint32_t* __restrict__ cursor /* or null */) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < new_total; j += stride) {
+    uint64_t lo = 0, hi = new_size;
+    while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (new_off[mid] <= j) lo = mid; else hi = mid; }
+    const uint64_t w = j - new_off[lo];
+    const uint32_t orank = oldrank[lo];
+    uint32_t ob = 0, olen = 0;
+    if (orank < old_size) { ob = old_off[orank]; olen = old_off[orank + 1] - ob; }
+    if (w == 0 && cursor) cursor[lo] = new_off[lo] + olen;
+    if (w < olen && (uint64_t)ob + w < old_total) new_pos[j] = old_pos[(uint64_t)ob + w];
+  }
+}
+// window positions of an appended text into the caller's coordinate space
+__global__ __launch_bounds__(256) void k_index_add_base(uint32_t* __restrict__ pos, uint64_t n, uint32_t base) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) pos[i] += base;
+}
+// erase by occurrence count: k_values_tile_count / k_values_tile_emit with the predicate on the LENGTH OF THE KEY'S SEGMENT
+// (offsets[rank + 1] - offsets[rank], the rank being the slot's value) instead of on the value, keys only.  Ranks follow the slot
+// order, so the two offsets words of a wave's slots are neighbours.
+template <int LAY>
+__device__ __forceinline__ bool ki_len_match(const KvItem& it, const uint32_t* __restrict__ offsets, uint64_t size, uint32_t lo, uint32_t hi) {
+  if (!kv_live<LAY>(it.info) || it.val >= size) return false;
+  const uint32_t len = offsets[it.val + 1] - offsets[it.val];
+  return len >= lo && len <= hi;
+}
+template <int LAY>
+__global__ __launch_bounds__(KV_SEL_THREADS) void k_index_len_count(const void* __restrict__ slots, uint64_t cap, const uint32_t* __restrict__ offsets, uint64_t size,
+                                                                    uint32_t lo, uint32_t hi, uint32_t* __restrict__ sums) {
+  __shared__ uint32_t wsum[KV_SEL_THREADS / 64];
+  const uint64_t tbase = (uint64_t)blockIdx.x * KV_SEL_TILE;
+  KvItem it[KV_SEL_ROWS];
+#pragma unroll
+  for (int j = 0; j < KV_SEL_ROWS; ++j) {
+    const uint64_t i = tbase + (uint64_t)j * KV_SEL_THREADS + threadIdx.x;
+    it[j] = kv_ld<LAY>(slots, i < cap ? i : cap - 1);
+  }
+  uint32_t c = 0;
+#pragma unroll
+  for (int j = 0; j < KV_SEL_ROWS; ++j) {
+    const uint64_t i = tbase + (uint64_t)j * KV_SEL_THREADS + threadIdx.x;
+    c += (i < cap && ki_len_match<LAY>(it[j], offsets, size, lo, hi)) ? 1u : 0u;
+  }
+  c = kh_wave_sum(c);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t tot = 0;
+    for (uint32_t w = 0; w < KV_SEL_THREADS / 64; ++w) tot += wsum[w];
+    sums[blockIdx.x] = tot;
+  }
+}
+template <int LAY>
+__global__ __launch_bounds__(KV_SEL_THREADS) void k_index_len_emit(const void* __restrict__ slots, uint64_t cap, const uint32_t* __restrict__ offsets, uint64_t size,
+                                                                   uint32_t lo, uint32_t hi, const uint64_t* __restrict__ tile_off, uint64_t* __restrict__ out_keys,
+                                                                   uint64_t cap_out) {
+  __shared__ uint32_t wcnt[KV_SEL_ROWS * (KV_SEL_THREADS / 64)];
+  typedef typename KvSlot<LAY>::type Slot;
+  const Slot* S = static_cast<const Slot*>(slots);
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const uint64_t tbase = (uint64_t)blockIdx.x * KV_SEL_TILE;
+  KvItem it[KV_SEL_ROWS];
+#pragma unroll
+  for (int j = 0; j < KV_SEL_ROWS; ++j) {
+    const uint64_t i = tbase + (uint64_t)j * KV_SEL_THREADS + tid;
+    it[j] = kv_ld<LAY>(slots, i < cap ? i : cap - 1);
+  }
+  uint32_t hit = 0, rank[KV_SEL_ROWS];
+#pragma unroll
+  for (int j = 0; j < KV_SEL_ROWS; ++j) {
+    const uint64_t i = tbase + (uint64_t)j * KV_SEL_THREADS + tid;
+    const bool m = i < cap && ki_len_match<LAY>(it[j], offsets, size, lo, hi);
+    const unsigned long long b = __ballot(m);
+    rank[j] = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) wcnt[j * (KV_SEL_THREADS / 64) + wid] = (uint32_t)__popcll(b);
+    hit |= m ? (1u << j) : 0u;
+  }
+  __syncthreads();
+  const uint64_t obase = tile_off[blockIdx.x];
+  uint32_t acc = 0;
+#pragma unroll
+  for (int j = 0; j < KV_SEL_ROWS; ++j) {
+    uint32_t pre = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < KV_SEL_THREADS / 64; ++w) { if (w == wid) pre = acc; acc += wcnt[j * (KV_SEL_THREADS / 64) + w]; }
+    if ((hit >> j) & 1u) {
+      const uint64_t i = tbase + (uint64_t)j * KV_SEL_THREADS + tid;
+      const uint64_t x = obase + pre + rank[j];
+      if (x >= cap_out) continue;
+      if (LAY == KV_WIDE) {
+        const uint4 k = *reinterpret_cast<const uint4*>(S + i);
+        out_keys[2 * x] = (uint64_t)k.x | ((uint64_t)k.y << 32);
+        out_keys[2 * x + 1] = (uint64_t)k.z | ((uint64_t)k.w << 32);
+      } else {
+        out_keys[x] = *reinterpret_cast<const uint64_t*>(S + i);
+      }
+    }
+  }
+}

@@ -222,3 +222,30 @@ __global__ __launch_bounds__(KW_Q_THREADS) void kw_index_lookup(KwSlots T, const
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------
+// append (see kh_kernels_index.h): the batch counted onto the seeded counts -- the probe of kw_index_scatter, one atomic per pair.  The
+// other kernels of append and erase read value and info only and are k_index_*<KV_WIDE>.
+// ---------------------------------------------------------------------------------------------
+template <int HASH>
+__global__ __launch_bounds__(KW_Q_THREADS) void kw_index_count_pairs(KwSlots T, const uint64_t* __restrict__ keys, uint64_t n, uint64_t seed, uint32_t* __restrict__ counts,
+                                                                     uint64_t nranks) {
+  for (uint64_t base = (uint64_t)blockIdx.x * KW_INDEX_Q_TILE; base < n; base += (uint64_t)gridDim.x * KW_INDEX_Q_TILE) {
+    uint64_t w0[KW_Q_ITEMS], w1[KW_Q_ITEMS]; uint32_t r[KW_Q_ITEMS];
+    uint32_t valid = 0;
+#pragma unroll
+    for (int j = 0; j < KW_Q_ITEMS; ++j) {
+      const uint64_t i = base + (uint64_t)j * KW_Q_THREADS + threadIdx.x;
+      w0[j] = 0; w1[j] = 0; r[j] = 0;
+      if (i < n) {
+        const uint4 k = reinterpret_cast<const uint4*>(keys)[i];
+        w0[j] = (uint64_t)k.x | ((uint64_t)k.y << 32); w1[j] = (uint64_t)k.z | ((uint64_t)k.w << 32);
+        valid |= 1u << j;
+      }
+    }
+    const uint32_t hit = kw_index_probe_items<HASH>(T, w0, w1, valid, seed, r);
+#pragma unroll
+    for (int j = 0; j < KW_Q_ITEMS; ++j)
+      if (((hit >> j) & 1u) && r[j] < nranks) atomicAdd(&counts[r[j]], 1u);
+  }
+}

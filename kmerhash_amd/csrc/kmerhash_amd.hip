@@ -3126,6 +3126,10 @@ inline uint32_t index_probe_grid(const kh_table* t, uint64_t n) {
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + KI_Q_TILE - 1) / KI_Q_TILE, (uint64_t)cu_count(t) * 8));
 }
 static_assert(KW_INDEX_Q_TILE == KI_Q_TILE, "one probe grid for both key widths");
+// the kernels that read value and info only, on the slot layout of the index's key width (the index's table is always Robin Hood)
+#define KI_SWITCH_LAYOUT(x, ...)                                                       \
+  if ((x)->kw == 2) { constexpr int LAY = KV_WIDE; __VA_ARGS__; }                      \
+  else { constexpr int LAY = KV_RH; __VA_ARGS__; }
 // (begin, count) per query: the lookup kernel of the index's key width
 void index_launch_lookup(kh_index* x, const uint64_t* q, uint64_t n, uint32_t* begin, uint32_t* cnt) {
   kh_table* t = x->t;
@@ -3206,10 +3210,145 @@ kh_status index_build_device(kh_index* x, const uint64_t* dk, const uint32_t* dp
   x->total = n; x->built = true;
   return KH_OK;
 }
-kh_status index_build_text(kh_index* x, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq) {
+// ---- mutation: the CSR carried across a change of the key set (kernels: the last section of kh_kernels_index.h) ----
+// The table has been changed by its own insert or erase; every live slot holds old rank + bias (bias 1: stamped before an insert, 0 is a
+// key the batch brought; bias 0: after an erase, which keeps the survivors' values).  New ranks, new offsets, the old segments moved to
+// the front of the new ones, then -- append only -- the nb pairs (dk, dp) scattered behind them and every segment sorted again.  The new
+// arrays come back through noff / npos; the caller swaps them in or frees them.
+kh_status index_carry_arrays(kh_index* x, uint32_t bias, uint64_t old_size, const uint64_t* dk, const uint32_t* dp, uint64_t nb, uint32_t** noff, uint32_t** npos,
+                             uint64_t* ntotal) {
+  kh_table* t = x->t;
+  const uint64_t size = t->lsize, cap = t->cur.cap, old_total = x->total, bound = old_total + nb;
+  const uint64_t ntl = (cap + KV_SEL_TILE - 1) / KV_SEL_TILE, nst = (size + KI_SCAN_TILE - 1) / KI_SCAN_TILE, nsort = (bound + KI_SORT_TILE - 1) / KI_SORT_TILE;
+  { kh_status ps = arena_prepare(t, ntl * 12 + size * 12 + nst * 8 + (nb ? nsort * 4 + bound * 4 : 0) + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  uint32_t *sums, *counts, *oldrank, *cursor = nullptr, *xlist = nullptr, *xcount = nullptr, *scratch = nullptr; uint64_t* toffs; unsigned long long* ssums;
+  TAKE(sums, uint32_t, ntl); TAKE(toffs, uint64_t, ntl + 1); TAKE(counts, uint32_t, size); TAKE(oldrank, uint32_t, size); TAKE(ssums, unsigned long long, nst + 1);
+  if (nb) { TAKE(cursor, uint32_t, size); TAKE(xlist, uint32_t, nsort); TAKE(xcount, uint32_t, 1); TAKE(scratch, uint32_t, bound); }
+  void* vp = nullptr;
+  HIPCHK(pool_alloc(t->device, (size + 1) * 4, &vp)); *noff = static_cast<uint32_t*>(vp);
+  // keys of one home bucket in key order again (an insert or a re-layout leaves their order to chance), new rank into every live slot,
+  // counts[new rank] = the length of the key's old segment
+  { Launch L(t, "k_index_rank_carry");
+    if (x->kw == 2) hipLaunchKernelGGL(kw_index_canon_runs, dim3(grid_for(cap, 256, (uint32_t)cu_count(t) * 8)), dim3(256), 0, t->stream, wide(t->cur).s, cap);
+    else hipLaunchKernelGGL(k_index_canon_runs, dim3(grid_for(cap, 256, (uint32_t)cu_count(t) * 8)), dim3(256), 0, t->stream, narrow(t->cur).s, cap);
+    KI_SWITCH_LAYOUT(x, hipLaunchKernelGGL((k_values_tile_count<LAY>), dim3((uint32_t)ntl), dim3(KV_SEL_THREADS), 0, t->stream, (const void*)t->cur.p, cap, 0u, 0xFFFFFFFFu, sums));
+    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, (const uint32_t*)sums, ntl, toffs);
+    KI_SWITCH_LAYOUT(x, hipLaunchKernelGGL((k_index_rank_carry<LAY>), dim3((uint32_t)ntl), dim3(KV_SEL_THREADS), 0, t->stream, t->cur.p, cap, (const uint64_t*)toffs,
+                                           (const uint32_t*)x->offsets, old_size, bias, size, counts, oldrank)); }
+  HIPCHK(hipGetLastError());
+  if (nb) {      // the batch on top: the random touches of the scatter, once more
+    Launch L(t, x->kw == 2 ? "kw_index_count_pairs" : "k_index_count_pairs");
+    if (x->kw == 2) { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_index_count_pairs<HASH>), dim3(index_probe_grid(t, nb)), dim3(KW_Q_THREADS), 0, t->stream, wide(t->cur), dk, nb,
+                                                                 t->seed.s, counts, size)); }
+    else { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_index_count_pairs<HASH>), dim3(index_probe_grid(t, nb)), dim3(KH_Q_THREADS), 0, t->stream, narrow(t->cur), dk, nb, t->seed,
+                                                      counts, size)); }
+  }
+  HIPCHK(hipGetLastError());
+  kh_status st = index_scan<uint32_t>(t, counts, size, ssums, *noff);
+  if (st != KH_OK) return st;
+  HIPCHK(hipMemcpyAsync(t->hpin, *noff + size, 4, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  const uint64_t total = *reinterpret_cast<const uint32_t*>(t->hpin);
+  if (total == 0 || total > bound || (nb && total != bound)) return fail(t, KH_ERR_HIP, "kh_index: internal: the carried counts do not add up");
+  HIPCHK(pool_alloc(t->device, total * 4, &vp)); *npos = static_cast<uint32_t*>(vp);
+  { Launch L(t, "k_index_move");
+    hipLaunchKernelGGL(k_index_move, dim3(grid_for(total, 256, (uint32_t)cu_count(t) * 8)), dim3(256), 0, t->stream, (const uint32_t*)x->positions, (const uint32_t*)x->offsets,
+                       old_size, old_total, (const uint32_t*)*noff, (const uint32_t*)oldrank, size, total, *npos, cursor); }
+  HIPCHK(hipGetLastError());
+  if (nb) {
+    HIPCHK(hipMemsetAsync(xcount, 0, 4, t->stream));
+    if (x->kw == 2) {
+      Launch L(t, "kw_index_scatter");
+      KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_index_scatter<HASH>), dim3(index_probe_grid(t, nb)), dim3(KW_Q_THREADS), 0, t->stream, wide(t->cur), dk, dp, nb, t->seed.s,
+                                                 cursor, *npos, total, size));
+    } else {
+      Launch L(t, "k_index_scatter");
+      KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_index_scatter<HASH>), dim3(index_probe_grid(t, nb)), dim3(KH_Q_THREADS), 0, t->stream, narrow(t->cur), dk, dp, nb, t->seed,
+                                                 cursor, *npos, total)); }
+    HIPCHK(hipGetLastError());
+    // ascending order again: the whole array (sorting only the segments that grew is an open end)
+    { Launch L(t, "k_index_tile_sort");
+      hipLaunchKernelGGL(k_index_tile_sort, dim3((uint32_t)nsort), dim3(KI_SORT_THREADS), 0, t->stream, *npos, total, (const uint32_t*)*noff, size, xlist, xcount); }
+    { Launch L(t, "k_index_seg_radix");
+      hipLaunchKernelGGL(k_index_seg_radix, dim3((uint32_t)std::min<uint64_t>(nsort, (uint64_t)cu_count(t) * 4)), dim3(KI_RADIX_THREADS), 0, t->stream, *npos, scratch,
+                         (const uint32_t*)*noff, (const uint32_t*)xlist, (const uint32_t*)xcount); }
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(t->stream));
+  *ntotal = total;
+  return KH_OK;
+}
+kh_status index_carry(kh_index* x, uint32_t bias, uint64_t old_size, const uint64_t* dk, const uint32_t* dp, uint64_t nb) {
+  kh_table* t = x->t;
+  uint32_t *noff = nullptr, *npos = nullptr; uint64_t total = 0;
+  kh_status st = KH_OK;
+  if (t->lsize) st = index_carry_arrays(x, bias, old_size, dk, dp, nb, &noff, &npos, &total);      // (nothing left: an empty index on the table as the erase left it)
+  hipStreamSynchronize(t->stream);
+  if (st != KH_OK) { pool_free(x->device, noff); pool_free(x->device, npos); return st; }
+  pool_free(x->device, x->offsets); pool_free(x->device, x->positions);
+  x->offsets = noff; x->positions = npos; x->total = total; x->built = total != 0;
+  return KH_OK;
+}
+// n (> 0) pairs in device memory onto an index in any state.  On an error the caller abandons the index.
+kh_status index_append_device(kh_index* x, const uint64_t* dk, const uint32_t* dp, uint64_t n) {
+  if (!x->built) return index_build_device(x, dk, dp, n);      // the build itself: the same kernels, the same bytes
+  kh_table* t = x->t;
+  const uint64_t old_size = t->lsize;
+  { Launch L(t, "k_index_stamp");
+    KI_SWITCH_LAYOUT(x, hipLaunchKernelGGL((k_index_stamp<LAY>), dim3(grid_for(t->cur.cap, KV_MARK_THREADS * KV_MARK_ITEMS, (uint32_t)cu_count(t) * 8)), dim3(KV_MARK_THREADS), 0,
+                                           t->stream, t->cur.p, t->cur.cap)); }
+  HIPCHK(hipGetLastError());
+  // the table's own reducer insert with zero values: key set, size, capacity and layout of kh_insert_reduce_plus; stamp | 0 = stamp
+  void* zeros = nullptr;      // (not in the table's workspace: the insert resets it)
+  HIPCHK(pool_alloc(x->device, n * 4, &zeros));
+  kh_status st = KH_ERR_HIP;
+  if (hipMemsetAsync(zeros, 0, n * 4, t->stream) != hipSuccess) fail(t, KH_ERR_HIP, "kh_index_append: clearing the values failed");
+  else {
+    uint64_t nins = 0;
+    st = x->kw == 2 ? kh_wide_insert_reduce(static_cast<kh_wtable*>(t), dk, zeros, n, KH_MEM_DEVICE, KH_REDUCE_OR, &nins)
+                    : kh_insert_reduce(t, dk, zeros, n, KH_MEM_DEVICE, KH_REDUCE_OR, &nins);
+  }
+  hipStreamSynchronize(t->stream);
+  pool_free(x->device, zeros);
+  if (st != KH_OK) return st;
+  if (t->lsize < old_size || t->lsize > old_size + n) return fail(t, KH_ERR_HIP, "kh_index: internal: the insert left an impossible size");
+  return index_carry(x, 1u, old_size, dk, dp, n);
+}
+// (key, position) pairs of a build or an append: host pairs are staged once
+kh_status index_pairs(kh_index* x, const void* keys, const void* pos, uint64_t n, kh_mem where, bool append) {
+  if (!x) return KH_ERR_INVALID;
+  if (n >> 32) return xfail(x, KH_ERR_INVALID, "kh_index_build: positions and offsets are 32-bit, n must be below 2^32");
+  if (!append && x->built) return xfail(x, KH_ERR_INVALID, "kh_index_build: the index is built already (kh_index_clear first)");
+  if (append && (x->total + n) >> 32) return xfail(x, KH_ERR_INVALID, "kh_index_append: offsets are 32-bit, the index must stay below 2^32 positions");
+  if (n == 0) return KH_OK;
+  if (!keys || !pos) return xfail(x, KH_ERR_INVALID, "null argument");
+  kh_table* t = x->t;
+  HIPCHK(hipSetDevice(x->device));
+  const uint64_t* dk = static_cast<const uint64_t*>(keys);
+  const uint32_t* dp = static_cast<const uint32_t*>(pos);
+  char* blk = nullptr;
+  hipError_t e = hipSuccess;
+  if (where == KH_MEM_HOST) {          // (not in the table's workspace: the counting insert resets it)
+    const uint64_t kb = n * 8 * x->kw;
+    HIPCHK(pool_alloc(x->device, kb + n * 4, reinterpret_cast<void**>(&blk)));
+    e = hipMemcpyAsync(blk, keys, kb, hipMemcpyHostToDevice, t->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk + kb, pos, n * 4, hipMemcpyHostToDevice, t->stream);
+    dk = reinterpret_cast<const uint64_t*>(blk); dp = reinterpret_cast<const uint32_t*>(blk + kb);
+  }
+  kh_status st = KH_ERR_HIP;
+  if (e == hipSuccess) st = append ? index_append_device(x, dk, dp, n) : index_build_device(x, dk, dp, n);
+  else fail(t, KH_ERR_HIP, "kh_index_build: staging the pairs failed");
+  hipStreamSynchronize(t->stream);
+  pool_free(x->device, blk);
+  return st == KH_OK ? KH_OK : index_abandon(x, st);
+}
+// build or append straight from text: the position-keeping k-mer front end on device buffers; an append adds pos_base to every window
+// position (several texts in one coordinate space)
+kh_status index_text(kh_index* x, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq, bool append, uint32_t pos_base) {
   if (!x) return KH_ERR_INVALID;
   if (n >> 32) return xfail(x, KH_ERR_INVALID, "kh_index: positions are 32-bit, a text of 2^32 bytes or more is refused");
-  if (x->built) return xfail(x, KH_ERR_INVALID, "kh_index: the index is built already (kh_index_clear first)");
+  if (!append && x->built) return xfail(x, KH_ERR_INVALID, "kh_index: the index is built already (kh_index_clear first)");
+  if (append && (uint64_t)pos_base + n > (uint64_t(1) << 32)) return xfail(x, KH_ERR_INVALID, "kh_index_append: pos_base + n passes 2^32, a window position would wrap");
   if (k < 1 || k > 32 * x->kw) return xfail(x, KH_ERR_INVALID, x->kw == 2 ? "kh_wide_index: k must be 1..64" : "kh_index: k must be 1..32");
   if (n < k) return KH_OK;
   if (!text) return xfail(x, KH_ERR_INVALID, "null text");
@@ -3226,11 +3365,35 @@ kh_status index_build_text(kh_index* x, const void* text, uint64_t n, uint32_t k
   uint32_t* dp = reinterpret_cast<uint32_t*>(blk + sz_text + n * 8 * x->kw);
   uint64_t m = 0;
   kh_status st = e == hipSuccess ? kmers_impl(x->kw, dtext, n, k, canonical, KH_MEM_DEVICE, fastq, dk, &m, x->device, t->stream, dp) : KH_ERR_HIP;
+  bool touched = !append;      // (a build starts from an empty index: abandoning it changes nothing)
   if (st != KH_OK) fail(t, st, "kh_index: k-mer generation failed");
-  else if (m) st = index_build_device(x, dk, dp, m);
+  else if (append && (x->total + m) >> 32) st = fail(t, KH_ERR_INVALID, "kh_index_append: offsets are 32-bit, the index must stay below 2^32 positions");
+  else if (m) {
+    touched = true;
+    if (append && pos_base) {
+      hipLaunchKernelGGL(k_index_add_base, dim3(grid_for(m, 256, (uint32_t)cu_count(t) * 8)), dim3(256), 0, t->stream, dp, m, pos_base);
+      if (hipGetLastError() != hipSuccess) st = fail(t, KH_ERR_HIP, "kh_index_append: k_index_add_base failed");
+    }
+    if (st == KH_OK) st = append ? index_append_device(x, dk, dp, m) : index_build_device(x, dk, dp, m);
+  }
   hipStreamSynchronize(t->stream);
   pool_free(x->device, blk);
-  return st == KH_OK ? KH_OK : index_abandon(x, st);
+  if (st == KH_OK) return KH_OK;
+  return touched ? index_abandon(x, st) : xfail(x, st, t->err);
+}
+// every occurrence of the given keys out of the index (keys: device or host, as the table's erase takes them)
+kh_status index_erase_keys(kh_index* x, const void* keys, uint64_t n, kh_mem where, uint64_t* n_keys_erased, uint64_t* n_pos_erased) {
+  kh_table* t = x->t;
+  const uint64_t old_size = t->lsize, old_total = x->total;
+  uint64_t ne = 0;
+  // the table's own erase: size, capacity and info bytes of the counting twin after the same call; the survivors keep their value, the old rank
+  kh_status st = x->kw == 2 ? kh_wide_erase(static_cast<kh_wtable*>(t), keys, n, where, &ne) : kh_erase(t, keys, n, where, &ne);
+  // (also after a batch of misses: a re-layout may have changed the order inside a home bucket)
+  if (st == KH_OK) st = index_carry(x, 0u, old_size, nullptr, nullptr, 0);
+  if (st != KH_OK) return index_abandon(x, st);
+  if (n_keys_erased) *n_keys_erased = ne;
+  if (n_pos_erased) *n_pos_erased = old_total - x->total;
+  return KH_OK;
 }
 }  // namespace
 extern "C" {
@@ -3266,36 +3429,62 @@ kh_status kh_index_capacity(const kh_index* x, uint64_t* out) { if (!x || !out) 
 kh_status kh_index_profile_enable(kh_index* x, int on) { if (!x) return KH_ERR_INVALID; x->prof = on != 0; if (on) kh_profile_reset(x->t); return kh_profile_enable(x->t, on); }
 kh_status kh_index_profile_dump(kh_index* x, char* buf, uint64_t cap) { if (!x) return KH_ERR_INVALID; return kh_profile_dump(x->t, buf, cap); }
 
-kh_status kh_index_build(kh_index* x, const void* keys, const void* pos, uint64_t n, kh_mem where) {
-  if (!x) return KH_ERR_INVALID;
-  if (n >> 32) return xfail(x, KH_ERR_INVALID, "kh_index_build: positions and offsets are 32-bit, n must be below 2^32");
-  if (x->built) return xfail(x, KH_ERR_INVALID, "kh_index_build: the index is built already (kh_index_clear first)");
-  if (n == 0) return KH_OK;
-  if (!keys || !pos) return xfail(x, KH_ERR_INVALID, "null argument");
-  kh_table* t = x->t;
-  HIPCHK(hipSetDevice(x->device));
-  const uint64_t* dk = static_cast<const uint64_t*>(keys);
-  const uint32_t* dp = static_cast<const uint32_t*>(pos);
-  char* blk = nullptr;
-  hipError_t e = hipSuccess;
-  if (where == KH_MEM_HOST) {          // (not in the table's workspace: the counting insert resets it)
-    const uint64_t kb = n * 8 * x->kw;
-    HIPCHK(pool_alloc(x->device, kb + n * 4, reinterpret_cast<void**>(&blk)));
-    e = hipMemcpyAsync(blk, keys, kb, hipMemcpyHostToDevice, t->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(blk + kb, pos, n * 4, hipMemcpyHostToDevice, t->stream);
-    dk = reinterpret_cast<const uint64_t*>(blk); dp = reinterpret_cast<const uint32_t*>(blk + kb);
-  }
-  kh_status st = KH_ERR_HIP;
-  if (e == hipSuccess) st = index_build_device(x, dk, dp, n); else fail(t, KH_ERR_HIP, "kh_index_build: staging the pairs failed");
-  hipStreamSynchronize(t->stream);
-  pool_free(x->device, blk);
-  return st == KH_OK ? KH_OK : index_abandon(x, st);
-}
+kh_status kh_index_build(kh_index* x, const void* keys, const void* pos, uint64_t n, kh_mem where) { return index_pairs(x, keys, pos, n, where, false); }
 kh_status kh_index_build_from_sequence(kh_index* x, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where) {
-  return index_build_text(x, seq, n, k, canonical, where, false);
+  return index_text(x, seq, n, k, canonical, where, false, false, 0u);
 }
 kh_status kh_index_build_from_fastq(kh_index* x, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where) {
-  return index_build_text(x, text, n, k, canonical, where, true);
+  return index_text(x, text, n, k, canonical, where, true, false, 0u);
+}
+kh_status kh_index_append(kh_index* x, const void* keys, const void* pos, uint64_t n, kh_mem where) { return index_pairs(x, keys, pos, n, where, true); }
+kh_status kh_index_append_from_sequence(kh_index* x, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, uint32_t pos_base) {
+  return index_text(x, seq, n, k, canonical, where, false, true, pos_base);
+}
+kh_status kh_index_append_from_fastq(kh_index* x, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, uint32_t pos_base) {
+  return index_text(x, text, n, k, canonical, where, true, true, pos_base);
+}
+kh_status kh_index_erase(kh_index* x, const void* keys, uint64_t n, kh_mem where, uint64_t* n_keys_erased, uint64_t* n_pos_erased) {
+  if (n_keys_erased) *n_keys_erased = 0;
+  if (n_pos_erased) *n_pos_erased = 0;
+  if (!x) return KH_ERR_INVALID;
+  if (n && !keys) return xfail(x, KH_ERR_INVALID, "null argument");
+  kh_table* t = x->t;
+  HIPCHK(hipSetDevice(x->device));
+  if (n == 0 || !x->built) { HIPCHK(hipStreamSynchronize(t->stream)); return KH_OK; }
+  return index_erase_keys(x, keys, n, where, n_keys_erased, n_pos_erased);
+}
+kh_status kh_index_erase_counts(kh_index* x, uint32_t lo, uint32_t hi, uint64_t* n_keys_erased, uint64_t* n_pos_erased) {
+  if (n_keys_erased) *n_keys_erased = 0;
+  if (n_pos_erased) *n_pos_erased = 0;
+  if (!x) return KH_ERR_INVALID;
+  kh_table* t = x->t;
+  HIPCHK(hipSetDevice(x->device));
+  if (lo > hi || !x->built) { HIPCHK(hipStreamSynchronize(t->stream)); return KH_OK; }      // (an empty range erases nothing, as in kh_erase_values)
+  // the keys whose segment length lies in the range, selected in slot order: count, scan, emit
+  const uint64_t cap = t->cur.cap, size = t->lsize, ntl = (cap + KV_SEL_TILE - 1) / KV_SEL_TILE;
+  { kh_status ps = arena_prepare(t, ntl * 12 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
+  uint32_t* sums; uint64_t* offs;
+  TAKE(sums, uint32_t, ntl); TAKE(offs, uint64_t, ntl + 1);
+  { Launch L(t, "k_index_len_count");
+    KI_SWITCH_LAYOUT(x, hipLaunchKernelGGL((k_index_len_count<LAY>), dim3((uint32_t)ntl), dim3(KV_SEL_THREADS), 0, t->stream, (const void*)t->cur.p, cap, (const uint32_t*)x->offsets,
+                                           size, lo, hi, sums));
+    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, t->stream, (const uint32_t*)sums, ntl, offs); }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(t->hpin, offs + ntl, 8, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipStreamSynchronize(t->stream));
+  const uint64_t m = t->hpin[0];
+  if (m == 0) return KH_OK;
+  if (m > size) return xfail(x, KH_ERR_HIP, "kh_index_erase_counts: internal: more keys selected than stored");
+  void* list = nullptr;      // (not in the table's workspace: the erase resets it)
+  HIPCHK(pool_alloc(x->device, m * 8 * x->kw, &list));
+  { Launch L(t, "k_index_len_emit");
+    KI_SWITCH_LAYOUT(x, hipLaunchKernelGGL((k_index_len_emit<LAY>), dim3((uint32_t)ntl), dim3(KV_SEL_THREADS), 0, t->stream, (const void*)t->cur.p, cap, (const uint32_t*)x->offsets,
+                                           size, lo, hi, (const uint64_t*)offs, static_cast<uint64_t*>(list), m)); }
+  kh_status st = hipGetLastError() == hipSuccess ? KH_OK : xfail(x, KH_ERR_HIP, "kh_index_erase_counts: k_index_len_emit failed");
+  if (st == KH_OK) st = index_erase_keys(x, list, m, KH_MEM_DEVICE, n_keys_erased, n_pos_erased);
+  hipStreamSynchronize(x->t->stream);
+  pool_free(x->device, list);
+  return st;
 }
 kh_status kh_index_export(kh_index* x, uint64_t* keys_host, uint32_t* offsets_host, uint32_t* positions_host) {
   if (!x) return KH_ERR_INVALID;
@@ -3398,10 +3587,23 @@ kh_status kh_wide_index_profile_enable(kh_windex* x, int on) { return kh_index_p
 kh_status kh_wide_index_profile_dump(kh_windex* x, char* buf, uint64_t cap) { return kh_index_profile_dump(x, buf, cap); }
 kh_status kh_wide_index_build(kh_windex* x, const void* keys, const void* pos, uint64_t n, kh_mem where) { return kh_index_build(x, keys, pos, n, where); }
 kh_status kh_wide_index_build_from_sequence(kh_windex* x, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where) {
-  return index_build_text(x, seq, n, k, canonical, where, false);
+  return index_text(x, seq, n, k, canonical, where, false, false, 0u);
 }
 kh_status kh_wide_index_build_from_fastq(kh_windex* x, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where) {
-  return index_build_text(x, text, n, k, canonical, where, true);
+  return index_text(x, text, n, k, canonical, where, true, false, 0u);
+}
+kh_status kh_wide_index_append(kh_windex* x, const void* keys, const void* pos, uint64_t n, kh_mem where) { return kh_index_append(x, keys, pos, n, where); }
+kh_status kh_wide_index_append_from_sequence(kh_windex* x, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, uint32_t pos_base) {
+  return index_text(x, seq, n, k, canonical, where, false, true, pos_base);
+}
+kh_status kh_wide_index_append_from_fastq(kh_windex* x, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, uint32_t pos_base) {
+  return index_text(x, text, n, k, canonical, where, true, true, pos_base);
+}
+kh_status kh_wide_index_erase(kh_windex* x, const void* keys, uint64_t n, kh_mem where, uint64_t* n_keys_erased, uint64_t* n_pos_erased) {
+  return kh_index_erase(x, keys, n, where, n_keys_erased, n_pos_erased);
+}
+kh_status kh_wide_index_erase_counts(kh_windex* x, uint32_t lo, uint32_t hi, uint64_t* n_keys_erased, uint64_t* n_pos_erased) {
+  return kh_index_erase_counts(x, lo, hi, n_keys_erased, n_pos_erased);
 }
 kh_status kh_wide_index_export(kh_windex* x, uint64_t* keys_host, uint32_t* offsets_host, uint32_t* positions_host) {
   return kh_index_export(x, keys_host, offsets_host, positions_host);

@@ -1,7 +1,8 @@
 """k-mer position index (kh_index in include/kmerhash_amd.h): k-mer -> ALL its positions, built on the GPU.
 
 The PositionIndex shape of the reference's driver (BenchmarkKmerIndex.cpp:342-449, over kmerind's multimap, which is not part of the
-reference tree): a static index, built once from (k-mer, position) pairs or straight from sequence / FASTQ text and then queried.
+reference tree): built from (k-mer, position) pairs or straight from sequence / FASTQ text, queried, and changed batch by batch
+(append*, erase, erase_counts, drop_above).
 numpy arrays are host buffers, torch CUDA tensors device buffers, as in kmerhash_amd.table; results come back in the same kind of
 container.  There is no CPU fallback."""
 import ctypes as C
@@ -78,12 +79,12 @@ class KmerPositionIndex:
         self._chk(self._fn("build")(self._h, kb.ptr, pb.ptr, n, kb.where))
         return n
 
-    def _build_text(self, fn, text):
+    def _build_text(self, fn, text, *more):
         if isinstance(text, (bytes, bytearray)):
             text = np.frombuffer(text, dtype=np.uint8)
         b = _Buf(text, np.uint8, 1)
         self._stream(b)
-        self._chk(self._fn(fn)(self._h, b.ptr, b.n, self.k, 1 if self.canonical else 0, b.where))
+        self._chk(self._fn(fn)(self._h, b.ptr, b.n, self.k, 1 if self.canonical else 0, b.where, *more))
         return self.total()
 
     def build_sequences(self, seq):
@@ -96,6 +97,55 @@ class KmerPositionIndex:
 
     def clear(self):
         self._chk(self._fn("clear")(self._h))
+
+    # -- change a built index --------------------------------------------------------------------
+    def append(self, keys, pos):
+        """more (k-mer, position) pairs onto an index in any state (on an empty one: build).  Afterwards the index is that of all pairs
+        given so far; the table is laid out like a counting table fed the same batches one by one."""
+        (kb, n), pb = self._kbuf(keys), _Buf(pos, np.uint32, 4)
+        if n != pb.n or kb.where != pb.where:
+            raise ValueError("keys and positions must have the same length and live in the same memory")
+        self._stream(kb, pb)
+        self._chk(self._fn("append")(self._h, kb.ptr, pb.ptr, n, kb.where))
+        return n
+
+    @staticmethod
+    def _base(pos_base):
+        if not 0 <= int(pos_base) < 2 ** 32:
+            raise ValueError("pos_base must be 0..2^32-1, got %r" % (pos_base,))
+        return int(pos_base)
+
+    def append_sequences(self, seq, pos_base=0):
+        """every window of `seq` onto the index, its position = pos_base + byte offset in `seq`; returns the positions indexed so far"""
+        return self._build_text("append_from_sequence", seq, self._base(pos_base))
+
+    def append_fastq(self, text, pos_base=0):
+        """the same over raw FASTQ text (whole 4-line records)"""
+        return self._build_text("append_from_fastq", text, self._base(pos_base))
+
+    def erase(self, keys):
+        """every occurrence of the given k-mers out of the index (misses and repeats are harmless) -> (distinct keys erased, positions erased)"""
+        q, n = self._kbuf(keys)
+        self._stream(q)
+        nk, npos = C.c_uint64(), C.c_uint64()
+        self._chk(self._fn("erase")(self._h, q.ptr, n, q.where, C.byref(nk), C.byref(npos)))
+        return nk.value, npos.value
+
+    def erase_counts(self, lo, hi):
+        """every k-mer whose number of occurrences lies in the closed range [lo, hi] out of the index (lo > hi: the empty range)
+        -> (distinct keys erased, positions erased)"""
+        for v in (lo, hi):
+            if not 0 <= int(v) < 2 ** 32:
+                raise ValueError("occurrence counts are 0..2^32-1, got %r" % (v,))
+        nk, npos = C.c_uint64(), C.c_uint64()
+        self._chk(self._fn("erase_counts")(self._h, int(lo), int(hi), C.byref(nk), C.byref(npos)))
+        return nk.value, npos.value
+
+    def drop_above(self, max_occ):
+        """mask repeats: every k-mer that occurs more than max_occ times out of the index -> (keys erased, positions erased)"""
+        if int(max_occ) >= 2 ** 32 - 1:
+            return 0, 0
+        return self.erase_counts(int(max_occ) + 1, 2 ** 32 - 1)
 
     # -- state -----------------------------------------------------------------------------------
     def size(self):
