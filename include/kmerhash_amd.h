@@ -521,6 +521,50 @@ kh_status kh_kmers128_from_sequence_pos(const void* seq /*[h|d] u8[n]*/, uint64_
 kh_status kh_kmers128_from_fastq_pos(const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, int canonical, kh_mem where,
                                      uint64_t* out_kmers /*[h|d] u64[2n]*/, uint32_t* out_pos /*[h|d]*/, uint64_t* n_out, int device, void* hip_stream);
 
+/* ---- (w,k)-minimizer sampling: the k-mers a seed index keeps instead of every window (the reference tree has no sampler -- its parser
+ *      and multimap are kmerind's and absent --: the definition below is this library's).
+ *      Inputs: a text, k (1..32), w (1..256), `canonical`, an ordering hash `order_hash` and `order_seed`.
+ *      - Valid windows, k-mers and positions are exactly those of kh_kmers_from_sequence_pos (packing, canonical form, byte offsets).
+ *      - Order key of the valid window at offset p: h(p) = the hash `order_hash` with seed `order_seed` of the EMITTED k-mer (of the
+ *        canonical form when `canonical` is set): the value kh_hash_batch gives for it.
+ *      - Full window: a start offset s is a full window iff all w offsets s .. s + w - 1 are valid window starts, i.e. the w + k - 1
+ *        bytes from s are all bases.  A window never spans a non-base byte, a newline or two reads.
+ *      - Selection: the pick of a full window s is the offset p in [s, s + w) with the smallest (h(p), p): ties on the hash go to the
+ *        LEFTMOST offset.
+ *      - Output: an offset is emitted ONCE if at least one full window picks it; the pairs (k-mer, offset) come out in ascending
+ *        offset order.  A run of fewer than w + k - 1 bases yields nothing.  w = 1: the output of kh_kmers_from_sequence_pos, byte for byte.
+ *      Equivalently, p is emitted iff it is valid and L + R + 1 >= w, where L counts the consecutive valid offsets directly left of p
+ *      with h > h(p) and R those directly right of p with h >= h(p), both capped at w - 1.
+ *      Two texts that share w + k - 1 bases share a sampled k-mer at the same place of that stretch; about 2 / (w + 1) of the windows
+ *      of a random text are kept.  REPEATS: in a stretch of equal k-mers (poly-A) every hash ties, the leftmost rule picks every
+ *      full-window start in it, and nothing is thinned there -- mask such k-mers in the index afterwards (kh_index_erase_counts).
+ *      The ordering hash is an argument of its own: the index's table takes its home bucket from hash & mask, and selecting the small
+ *      values of the SAME seeded hash would fill the low buckets of a small table first; choose a different hash or seed.
+ *      out_kmers == NULL: count only -- *n_out is set, nothing is written, only the count pass and the scan run.  Otherwise cap_out is
+ *      the room offered in out_kmers and out_pos (both required); more picks than cap_out: KH_ERR_INVALID with *n_out set and the
+ *      outputs untouched (the total is known before anything is written, as for kh_index_find).  KH_ERR_INVALID before anything is
+ *      allocated or read: k outside 1..32, w outside 1..256, n >= 2^32, an unknown hash, NULL text with n > 0, NULL n_out.  n == 0 or
+ *      a text shorter than w + k - 1: KH_OK and *n_out = 0.  kh_minimizers_from_fastq: the sequence lines of raw FASTQ text, as
+ *      kh_kmers_from_fastq_pos reads them (offsets into the raw text).  Two passes over the text, 1 B per base read each, 12 B per
+ *      EMITTED pair written; no hash array in device memory. */
+kh_status kh_minimizers_from_sequence(const void* seq /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, uint32_t w /*1..256*/, int canonical,
+                                      kh_hash order_hash, uint64_t order_seed, kh_mem where,
+                                      uint64_t* out_kmers /*[h|d] or NULL*/, uint32_t* out_pos /*[h|d] or NULL*/, uint64_t cap_out,
+                                      uint64_t* n_out, int device, void* hip_stream);
+kh_status kh_minimizers_from_fastq(const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, uint32_t w /*1..256*/, int canonical,
+                                   kh_hash order_hash, uint64_t order_seed, kh_mem where,
+                                   uint64_t* out_kmers /*[h|d] or NULL*/, uint32_t* out_pos /*[h|d] or NULL*/, uint64_t cap_out,
+                                   uint64_t* n_out, int device, void* hip_stream);
+/* a position index over the minimizers of a text (fastq != 0: raw FASTQ text): the pairs of kh_minimizers_from_sequence / _fastq, with
+ *      pos_base added to every offset on the device, followed by kh_index_build / kh_index_append -- the export is byte-identical to
+ *      kh_index_build over those pairs.  The pair buffers are sized from the count pass, NOT from n: peak staging is 12 B per emitted
+ *      pair (next to the text copy of a host text and the FASTQ mask).  Failure states and refusals are those of
+ *      kh_index_append_from_sequence, plus w out of range and an unknown order hash; 16-byte k-mers (kh_windex) are not supported. */
+kh_status kh_index_build_from_minimizers(kh_index* x, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, uint32_t w /*1..256*/, int canonical,
+                                         kh_hash order_hash, uint64_t order_seed, kh_mem where, int fastq);
+kh_status kh_index_append_from_minimizers(kh_index* x, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, uint32_t w /*1..256*/, int canonical,
+                                          kh_hash order_hash, uint64_t order_seed, kh_mem where, int fastq, uint32_t pos_base);
+
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);
 

@@ -72,6 +72,8 @@ SYMBOLS = [
     # changing a built index: append batches, erase keys, erase by occurrence count (both key widths)
     "kh_index_append", "kh_index_append_from_sequence", "kh_index_append_from_fastq", "kh_index_erase", "kh_index_erase_counts",
     "kh_wide_index_append", "kh_wide_index_append_from_sequence", "kh_wide_index_append_from_fastq", "kh_wide_index_erase", "kh_wide_index_erase_counts",
+    # (w,k)-minimizer sampling and the position index over the sampled k-mers
+    "kh_minimizers_from_sequence", "kh_minimizers_from_fastq", "kh_index_build_from_minimizers", "kh_index_append_from_minimizers",
 ]
 
 _lib = None
@@ -233,6 +235,10 @@ def lib():
         getattr(L, pre + "erase").argtypes = [vp, vp, u64, i32, pu64, pu64]
         getattr(L, pre + "erase_counts").argtypes = [vp, u32, u32, pu64, pu64]
     L.kh_wide_index_export_info.argtypes = [vp, vp]
+    L.kh_minimizers_from_sequence.argtypes = [vp, u64, u32, u32, i32, i32, u64, i32, vp, vp, u64, pu64, i32, vp]
+    L.kh_minimizers_from_fastq.argtypes = [vp, u64, u32, u32, i32, i32, u64, i32, vp, vp, u64, pu64, i32, vp]
+    L.kh_index_build_from_minimizers.argtypes = [vp, vp, u64, u32, u32, i32, i32, u64, i32, i32]
+    L.kh_index_append_from_minimizers.argtypes = [vp, vp, u64, u32, u32, i32, i32, u64, i32, i32, u32]
     for s in SYMBOLS:
         if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error", "kh_wide_index_last_error"):
             getattr(L, s).restype = i32

@@ -58,6 +58,163 @@ __global__ __launch_bounds__(KH_KM_THREADS) void k_kmers_emit_pos(const uint8_t*
 }
 
 // ---------------------------------------------------------------------------------------------
+// (w,k)-minimizer sampling (kh_minimizers_from_sequence / _fastq; the definition is in include/kmerhash_amd.h): the tile scheme of
+// k_kmers_count / k_kmers_emit_pos with a halo on BOTH sides.  A tile decides the picks among its KH_KM_TILE start offsets; the
+// windows that can pick one of them start up to w - 1 offsets to its left and reach up to w - 1 offsets past its right end, so the
+// tile hashes HW = ceil((w - 1) / 16) words of 16 offsets on either side as well (w = 10: 2 words on top of 256, w = 256: 32).
+//   1. pack: the HW words left of the tile (non-bases in front of the text), then kh_km_pack_tile for the tile and what lies behind it.
+//   2. hash once per offset: the order key kh_hash64<HASH>(emitted k-mer, seed) into LDS (hk, 8 B per offset, a row of 16 keys padded
+//      by one so that the 16 consecutive stores of a lane spread over the banks) and arg[i] = i for a valid window, KM_MZ_NONE otherwise.
+//   3. window minimum in O(log w) per offset: J = floor(log2 w) doubling steps turn arg[i] into the offset of the smallest (key, offset)
+//      among [i, i + 2^J) -- or KM_MZ_NONE when one of them is no valid window --, in place (a lane holds its <= 18 results in registers
+//      across the barrier).  The pick of the window that starts at s is the smaller of arg[s] and arg[s + w - 2^J] (two overlapping
+//      ranges that cover [s, s + w)); the right one wins only with a strictly smaller key, so ties go to the leftmost offset, and a
+//      window with an invalid offset (not full) picks nothing.  Work per offset: J + 1 steps of two 2-byte and two 8-byte LDS reads.
+//   4. every full window marks its pick in a 4096-bit mask (LDS atomic or; a lane skips the atomic when the window before it -- the
+//      lane before it -- picked the same offset).  Picks outside the tile belong to the neighbour tile, which finds them itself.
+// LDS: 39168 (keys) + 9216 (arg) + 1160 + 580 (packed text) + 512 (marks) + 16 = 50652 B (50656 padded): three workgroups per CU,
+// three waves per SIMD, which the launch bounds also hold the registers to.
+// The count kernel sums the marks; the emit kernel stages the marked windows' k-mers over the keys (which are dead by then) and their
+// tile-local offsets over arg, and writes both coalesced.  No hash and no flag reaches HBM: 1 B/base read per pass, 12 B per pair out.
+// ---------------------------------------------------------------------------------------------
+#define KM_MZ_WMAX 256
+#define KM_MZ_HALO_WORDS ((KM_MZ_WMAX - 1 + 15) / 16)                       // 16
+#define KM_MZ_WORDS (KH_KM_TILE / 16 + 2 * KM_MZ_HALO_WORDS)                 // 288 words of hashed offsets at most
+#define KM_MZ_OFFS (16 * KM_MZ_WORDS)                                        // 4608
+#define KM_MZ_PER ((KM_MZ_OFFS + KH_KM_THREADS - 1) / KH_KM_THREADS)         // 18
+#define KM_MZ_NONE 0xFFFFu
+#define KM_MZ_HK(i) ((i) + ((i) >> 4))
+struct KmMzLds {
+  uint64_t hk[KM_MZ_OFFS + KM_MZ_WORDS];            // order keys, 17 per word of 16 offsets; the emit stage afterwards
+  uint16_t arg[KM_MZ_OFFS];                         // offset of the range minimum / KM_MZ_NONE; the staged offsets afterwards
+  uint32_t words[KM_MZ_WORDS + KhKm<1>::HALO];
+  uint16_t invs[KM_MZ_WORDS + KhKm<1>::HALO];
+  uint32_t marks[KH_KM_TILE / 32];
+  uint32_t wtot[KH_KM_THREADS / 64];
+};
+// leaves S.marks complete (bit q: the window at tile0 + q is a minimizer) and the workgroup synchronised; returns HW
+template <int HASH, bool CANON>
+__device__ __forceinline__ uint32_t km_mz_marks(const uint8_t* __restrict__ seq, uint64_t n, uint64_t tile0, uint32_t k, uint32_t w, uint64_t seed, KmMzLds& S) {
+  typedef KhKm<1> M;
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint32_t hw = (w + 14u) >> 4, nw = KH_KM_TILE / 16 + 2 * hw, ne = 16 * nw;
+  if (tid < hw) {                                                  // (tile0 > 0: tile0 >= KH_KM_TILE > 16 hw, and the 16 bytes lie inside the text)
+    uint32_t word = 0, inv = 0xFFFFu;
+    if (tile0) {
+      const uint8_t* p = seq + (tile0 - 16ull * (hw - tid));
+      inv = 0;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const uint32_t c = kh_dna_code(p[q]);
+        word = (word << 2) | (c & 3u);
+        inv = (inv << 1) | (c > 3u ? 1u : 0u);
+      }
+    }
+    S.words[tid] = word; S.invs[tid] = (uint16_t)inv;
+  }
+  if (tid < KH_KM_TILE / 32) S.marks[tid] = 0;
+  kh_km_pack_tile<KM_MZ_HALO_WORDS + M::HALO>(seq, n, tile0, S.words + hw, S.invs + hw);
+  __syncthreads();
+  for (uint32_t e = tid; e < nw; e += KH_KM_THREADS) {
+    const M::Win W = M::window(S.words, S.invs, e);
+#pragma unroll 4                                                   // (four hashes in flight; sixteen cost 170 registers and spills)
+    for (uint32_t j = 0; j < 16; ++j) {
+      const uint32_t i = 16 * e + j;
+      S.hk[KM_MZ_HK(i)] = M::template hash_of_window<HASH, CANON>(W, j, k, seed);
+      S.arg[i] = M::valid(W, j, k) ? (uint16_t)i : (uint16_t)KM_MZ_NONE;
+    }
+  }
+  __syncthreads();
+  const uint32_t J = 31u - (uint32_t)__clz(w);
+  for (uint32_t s = 0; s < J; ++s) {
+    const uint32_t step = 1u << s;
+    uint32_t res[KM_MZ_PER];
+#pragma unroll
+    for (uint32_t r = 0; r < KM_MZ_PER; ++r) {
+      const uint32_t i = tid + r * KH_KM_THREADS;
+      uint32_t a = KM_MZ_NONE;
+      if (i + step < ne) {
+        a = S.arg[i];
+        const uint32_t b = S.arg[i + step];
+        if (b == KM_MZ_NONE) a = KM_MZ_NONE;
+        else if (a != KM_MZ_NONE && S.hk[KM_MZ_HK(b)] < S.hk[KM_MZ_HK(a)]) a = b;
+      }
+      res[r] = a;
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < KM_MZ_PER; ++r) {
+      const uint32_t i = tid + r * KH_KM_THREADS;
+      if (i < ne) S.arg[i] = (uint16_t)res[r];
+    }
+    __syncthreads();
+  }
+  const uint32_t back = w - (1u << J);
+#pragma unroll
+  for (uint32_t r = 0; r < KM_MZ_PER; ++r) {
+    const uint32_t s = tid + r * KH_KM_THREADS;
+    uint32_t p = KM_MZ_NONE;
+    if (s + w <= ne) {
+      p = S.arg[s];
+      const uint32_t b = S.arg[s + back];
+      if (b == KM_MZ_NONE) p = KM_MZ_NONE;
+      else if (p != KM_MZ_NONE && S.hk[KM_MZ_HK(b)] < S.hk[KM_MZ_HK(p)]) p = b;
+    }
+    const uint32_t before = __shfl_up(p, 1, 64);
+    const uint32_t q = p - 16u * hw;                               // (a pick left of the tile wraps past KH_KM_TILE)
+    if (p != KM_MZ_NONE && q < KH_KM_TILE && (lane == 0 || before != p)) atomicOr(&S.marks[q >> 5], 1u << (q & 31u));
+  }
+  __syncthreads();
+  return hw;
+}
+template <int HASH, bool CANON>
+__global__ __launch_bounds__(KH_KM_THREADS, 3) void k_minimizers_count(const uint8_t* __restrict__ seq, uint64_t n, uint32_t k, uint32_t w, uint64_t seed,
+                                                                    uint32_t* __restrict__ sums) {
+  __shared__ KmMzLds S;
+  km_mz_marks<HASH, CANON>(seq, n, (uint64_t)blockIdx.x * KH_KM_TILE, k, w, seed, S);
+  uint32_t c = threadIdx.x < KH_KM_TILE / 32 ? (uint32_t)__popc(S.marks[threadIdx.x]) : 0u;
+  c = kh_wave_sum(c);
+  if ((threadIdx.x & 63) == 0) S.wtot[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) sums[blockIdx.x] = S.wtot[0] + S.wtot[1] + S.wtot[2] + S.wtot[3];
+}
+// out_pos[i] = pos_base + the window's byte offset (pos_base: the coordinate space of kh_index_append_from_minimizers)
+template <int HASH, bool CANON>
+__global__ __launch_bounds__(KH_KM_THREADS, 3) void k_minimizers_emit(const uint8_t* __restrict__ seq, uint64_t n, uint32_t k, uint32_t w, uint64_t seed,
+                                                                   const uint64_t* __restrict__ tile_off, uint64_t* __restrict__ out, uint32_t* __restrict__ out_pos,
+                                                                   uint32_t pos_base) {
+  typedef KhKm<1> M;
+  __shared__ KmMzLds S;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const uint64_t tile0 = (uint64_t)blockIdx.x * KH_KM_TILE;
+  const uint32_t hw = km_mz_marks<HASH, CANON>(seq, n, tile0, k, w, seed, S);
+  const uint32_t pmask = (S.marks[tid >> 1] >> (16u * (tid & 1u))) & 0xFFFFu;      // the 16 windows of the lane's word
+  const uint32_t mine = (uint32_t)__popc(pmask);
+  uint32_t incl = mine;
+  for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off, 64); if (lane >= (uint32_t)off) incl += o; }
+  if (lane == 63) S.wtot[wid] = incl;
+  __syncthreads();
+  uint32_t pos = incl - mine, total = 0;
+#pragma unroll
+  for (uint32_t x = 0; x < KH_KM_THREADS / 64; ++x) { const uint32_t c = S.wtot[x]; if (x < wid) pos += c; total += c; }
+  const M::Win W = M::window(S.words, S.invs, tid + hw);
+  uint64_t* stage = S.hk;                                          // (every read of the keys lies before the barrier km_mz_marks ends with)
+  uint16_t* spos = S.arg;
+#pragma unroll
+  for (uint32_t j = 0; j < 16; ++j) {
+    if ((pmask >> j) & 1u) {
+      const uint64_t fw = M::forward(W, j, k);
+      stage[pos] = CANON ? kh_xf(fw, k) : fw;
+      spos[pos] = (uint16_t)(16u * tid + j);
+      ++pos;
+    }
+  }
+  __syncthreads();
+  const uint64_t o = tile_off[blockIdx.x];
+  for (uint32_t i = tid; i < total; i += KH_KM_THREADS) { out[o + i] = stage[i]; out_pos[o + i] = pos_base + (uint32_t)(tile0 + spos[i]); }
+}
+
+// ---------------------------------------------------------------------------------------------
 // canonical slot order.  A Robin Hood table keeps its elements sorted by home bucket, but the order of the keys that SHARE a home bucket
 // is whatever the insert made of it (in the reference: arrival order; in the counting insert here: the order LDS atomics gave, which
 // differs from run to run).  The index promises a result that depends on the multiset of pairs only, so every run of slots with one

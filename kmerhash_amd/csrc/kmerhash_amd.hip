@@ -2390,8 +2390,115 @@ kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int c
   *n_out = total;
   return KH_OK;
 }
+// (w,k)-minimizers in two steps, so that a caller can size its pair buffers from the count: mz_count stages a host text, masks FASTQ,
+// runs the count pass and the scan and returns the number of picks; mz_emit writes the pairs into device buffers of that many
+// entries.  prof: the table whose profile lists the launches (an index's own), or null.
+struct MzWork {
+  int device = 0;
+  char* blk = nullptr;
+  const uint8_t* dseq = nullptr;
+  uint32_t* sums = nullptr;
+  uint64_t* offs = nullptr;
+  uint64_t n = 0, nkt = 0;
+  uint32_t k = 0, w = 0;
+  int canonical = 0, hash = 0;
+  uint64_t seed = 0;
+};
+void mz_free(MzWork& M) { pool_free(M.device, M.blk); M.blk = nullptr; }
+// refusals that need no device: k, w, n, the hash and null arguments (shared by kh_minimizers_* and kh_index_*_from_minimizers)
+bool mz_args_ok(const void* seq, uint64_t n, uint32_t k, uint32_t w, int hash) {
+  return k >= 1 && k <= 32 && w >= 1 && w <= KM_MZ_WMAX && !(n >> 32) && hash >= 0 && hash <= 3 && (seq || n == 0);
+}
+kh_status mz_count(kh_table* prof, MzWork& M, const void* seq, uint64_t n, uint32_t k, uint32_t w, int canonical, int hash, uint64_t seed, kh_mem where, bool fastq,
+                   int device, hipStream_t stream, uint64_t* total) {
+  kh_table* t = prof;
+  M.device = device; M.n = n; M.k = k; M.w = w; M.canonical = canonical; M.hash = hash; M.seed = seed;
+  const uint64_t ntl = (n + KH_CMP_TILE - 1) / KH_CMP_TILE, nkt = (n + KH_KM_TILE - 1) / KH_KM_TILE;
+  M.nkt = nkt;
+  // one pooled block: [text copy (host input)] [masked text (FASTQ)] [tile sums] [tile offsets]
+  const size_t sz_seq = where == KH_MEM_HOST ? ((n + 255) & ~size_t(255)) : 0;
+  const size_t sz_msk = fastq ? ((n + 255) & ~size_t(255)) : 0;
+  const uint64_t nt = std::max(ntl, nkt);
+  const size_t sz_sum = ((nt * 4 + 255) & ~size_t(255)), sz_off = (nt + 1) * 8;
+  HIPCHK(pool_alloc(device, sz_seq + sz_msk + sz_sum + sz_off, reinterpret_cast<void**>(&M.blk)));
+  char* p = M.blk;
+  M.dseq = static_cast<const uint8_t*>(seq);
+  if (where == KH_MEM_HOST) { M.dseq = reinterpret_cast<uint8_t*>(p); p += sz_seq; }
+  uint8_t* msk = reinterpret_cast<uint8_t*>(p); p += sz_msk;
+  M.sums = reinterpret_cast<uint32_t*>(p); p += sz_sum;
+  M.offs = reinterpret_cast<uint64_t*>(p);
+  hipError_t e = hipSuccess;
+  if (where == KH_MEM_HOST) e = hipMemcpyAsync(const_cast<uint8_t*>(M.dseq), seq, n, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) {
+    if (fastq) { fastq_mask_text(M.dseq, n, M.sums, M.offs, msk, stream); M.dseq = msk; }
+    { Launch L(prof, "k_minimizers_count");
+      if (canonical) { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_minimizers_count<HASH, true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, n, k, w, seed, M.sums)); }
+      else { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_minimizers_count<HASH, false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, n, k, w, seed, M.sums)); } }
+    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, M.sums, nkt, M.offs);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(total, M.offs + nkt, 8, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) { mz_free(M); return fail(t, KH_ERR_HIP, std::string("minimizer count pass: ") + hipGetErrorString(e)); }
+  return KH_OK;
+}
+// queues the emit pass (dout u64[total], dpos u32[total], device memory); the caller synchronises
+kh_status mz_emit(kh_table* prof, const MzWork& M, hipStream_t stream, uint64_t* dout, uint32_t* dpos, uint32_t pos_base) {
+  kh_table* t = prof;
+  { Launch L(prof, "k_minimizers_emit");
+    if (M.canonical) { KH_SWITCH_HASH(M.hash, hipLaunchKernelGGL((k_minimizers_emit<HASH, true>), dim3((uint32_t)M.nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, M.n, M.k, M.w, M.seed,
+                                                                 (const uint64_t*)M.offs, dout, dpos, pos_base)); }
+    else { KH_SWITCH_HASH(M.hash, hipLaunchKernelGGL((k_minimizers_emit<HASH, false>), dim3((uint32_t)M.nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, M.n, M.k, M.w, M.seed,
+                                                     (const uint64_t*)M.offs, dout, dpos, pos_base)); } }
+  HIPCHK(hipGetLastError());
+  return KH_OK;
+}
+kh_status minimizers_impl(const void* seq, uint64_t n, uint32_t k, uint32_t w, int canonical, int hash, uint64_t seed, kh_mem where, bool fastq,
+                          uint64_t* out_kmers, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, void* stream_) {
+  kh_table* t = nullptr;
+  if (n_out) *n_out = 0;
+  if (!n_out || !mz_args_ok(seq, n, k, w, hash) || (out_kmers && !out_pos)) return KH_ERR_INVALID;
+  if (n < (uint64_t)w + k - 1) return KH_OK;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK(hipSetDevice(device));
+  MzWork M;
+  uint64_t total = 0;
+  kh_status st = mz_count(nullptr, M, seq, n, k, w, canonical, hash, seed, where, fastq, device, stream, &total);
+  if (st != KH_OK) return st;
+  *n_out = total;
+  if (!out_kmers || total == 0) { mz_free(M); return KH_OK; }
+  if (total > cap_out) { mz_free(M); return KH_ERR_INVALID; }       // (the total is known before anything is written)
+  uint64_t* dout = out_kmers; uint32_t* dpos = out_pos;
+  char* stage = nullptr;
+  hipError_t e = hipSuccess;
+  if (where == KH_MEM_HOST) {
+    e = pool_alloc(device, total * 12, reinterpret_cast<void**>(&stage));
+    dout = reinterpret_cast<uint64_t*>(stage); dpos = reinterpret_cast<uint32_t*>(stage + total * 8);
+  }
+  if (e == hipSuccess) {
+    st = mz_emit(nullptr, M, stream, dout, dpos, 0u);
+    if (st == KH_OK && where == KH_MEM_HOST) {
+      e = hipMemcpyAsync(out_kmers, dout, total * 8, hipMemcpyDeviceToHost, stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(out_pos, dpos, total * 4, hipMemcpyDeviceToHost, stream);
+    }
+  }
+  const hipError_t es = hipStreamSynchronize(stream);
+  pool_free(device, stage);
+  mz_free(M);
+  if (e == hipErrorOutOfMemory) return KH_ERR_NOMEM;
+  if (e != hipSuccess || es != hipSuccess) return KH_ERR_HIP;
+  return st;
+}
 }  // namespace
 extern "C" {
+kh_status kh_minimizers_from_sequence(const void* seq, uint64_t n, uint32_t k, uint32_t w, int canonical, kh_hash order_hash, uint64_t order_seed, kh_mem where,
+                                      uint64_t* out_kmers, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, void* stream_) {
+  return minimizers_impl(seq, n, k, w, canonical, (int)order_hash, order_seed, where, false, out_kmers, out_pos, cap_out, n_out, device, stream_);
+}
+kh_status kh_minimizers_from_fastq(const void* text, uint64_t n, uint32_t k, uint32_t w, int canonical, kh_hash order_hash, uint64_t order_seed, kh_mem where,
+                                   uint64_t* out_kmers, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, void* stream_) {
+  return minimizers_impl(text, n, k, w, canonical, (int)order_hash, order_seed, where, true, out_kmers, out_pos, cap_out, n_out, device, stream_);
+}
 kh_status kh_kmers_from_sequence(const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where,
                                  uint64_t* out_kmers, uint64_t* n_out, int device, void* stream_) {
   return kmers_impl(1, seq, n, k, canonical, where, false, out_kmers, n_out, device, stream_);
@@ -3381,6 +3488,45 @@ kh_status index_text(kh_index* x, const void* text, uint64_t n, uint32_t k, int 
   if (st == KH_OK) return KH_OK;
   return touched ? index_abandon(x, st) : xfail(x, st, t->err);
 }
+// index_text over the (w,k)-minimizers of the text instead of all its windows: count pass, pair buffers of exactly that many entries
+// (12 B per emitted pair, not per base), emit pass with pos_base added as it writes, then the build / append of the pairs
+kh_status index_minimizers(kh_index* x, const void* text, uint64_t n, uint32_t k, uint32_t w, int canonical, int hash, uint64_t seed, kh_mem where, bool fastq,
+                           bool append, uint32_t pos_base) {
+  if (!x) return KH_ERR_INVALID;
+  if (x->kw != 1) return xfail(x, KH_ERR_INVALID, "kh_index: minimizers are defined for 64-bit k-mers only");
+  if (n >> 32) return xfail(x, KH_ERR_INVALID, "kh_index: positions are 32-bit, a text of 2^32 bytes or more is refused");
+  if (!append && x->built) return xfail(x, KH_ERR_INVALID, "kh_index: the index is built already (kh_index_clear first)");
+  if (append && (uint64_t)pos_base + n > (uint64_t(1) << 32)) return xfail(x, KH_ERR_INVALID, "kh_index_append: pos_base + n passes 2^32, a window position would wrap");
+  if (k < 1 || k > 32) return xfail(x, KH_ERR_INVALID, "kh_index: k must be 1..32");
+  if (w < 1 || w > KM_MZ_WMAX) return xfail(x, KH_ERR_INVALID, "kh_index: w must be 1..256");
+  if (hash < 0 || hash > 3) return xfail(x, KH_ERR_INVALID, "kh_index: unknown order hash");
+  if (n < (uint64_t)w + k - 1) return KH_OK;
+  if (!text) return xfail(x, KH_ERR_INVALID, "null text");
+  kh_table* t = x->t;
+  HIPCHK(hipSetDevice(x->device));
+  MzWork M;
+  uint64_t m = 0;
+  kh_status st = mz_count(t, M, text, n, k, w, canonical, hash, seed, where, fastq, x->device, t->stream, &m);
+  if (st != KH_OK) return xfail(x, st, t->err);
+  if (append && (x->total + m) >> 32) { mz_free(M); return xfail(x, KH_ERR_INVALID, "kh_index_append: offsets are 32-bit, the index must stay below 2^32 positions"); }
+  if (m == 0) { mz_free(M); return KH_OK; }
+  char* pairs = nullptr;
+  const hipError_t e = pool_alloc(x->device, m * 12, reinterpret_cast<void**>(&pairs));
+  if (e != hipSuccess) { mz_free(M); return xfail(x, e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP, "kh_index: no memory for the minimizer pairs"); }
+  uint64_t* dk = reinterpret_cast<uint64_t*>(pairs);
+  uint32_t* dp = reinterpret_cast<uint32_t*>(pairs + m * 8);
+  st = mz_emit(t, M, t->stream, dk, dp, append ? pos_base : 0u);
+  bool touched = !append;      // (a build starts from an empty index: abandoning it changes nothing)
+  if (st == KH_OK) {
+    touched = true;
+    st = append ? index_append_device(x, dk, dp, m) : index_build_device(x, dk, dp, m);
+  }
+  hipStreamSynchronize(t->stream);
+  pool_free(x->device, pairs);
+  mz_free(M);
+  if (st == KH_OK) return KH_OK;
+  return touched ? index_abandon(x, st) : xfail(x, st, t->err);
+}
 // every occurrence of the given keys out of the index (keys: device or host, as the table's erase takes them)
 kh_status index_erase_keys(kh_index* x, const void* keys, uint64_t n, kh_mem where, uint64_t* n_keys_erased, uint64_t* n_pos_erased) {
   kh_table* t = x->t;
@@ -3442,6 +3588,14 @@ kh_status kh_index_append_from_sequence(kh_index* x, const void* seq, uint64_t n
 }
 kh_status kh_index_append_from_fastq(kh_index* x, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, uint32_t pos_base) {
   return index_text(x, text, n, k, canonical, where, true, true, pos_base);
+}
+kh_status kh_index_build_from_minimizers(kh_index* x, const void* text, uint64_t n, uint32_t k, uint32_t w, int canonical, kh_hash order_hash, uint64_t order_seed,
+                                         kh_mem where, int fastq) {
+  return index_minimizers(x, text, n, k, w, canonical, (int)order_hash, order_seed, where, fastq != 0, false, 0u);
+}
+kh_status kh_index_append_from_minimizers(kh_index* x, const void* text, uint64_t n, uint32_t k, uint32_t w, int canonical, kh_hash order_hash, uint64_t order_seed,
+                                          kh_mem where, int fastq, uint32_t pos_base) {
+  return index_minimizers(x, text, n, k, w, canonical, (int)order_hash, order_seed, where, fastq != 0, true, pos_base);
 }
 kh_status kh_index_erase(kh_index* x, const void* keys, uint64_t n, kh_mem where, uint64_t* n_keys_erased, uint64_t* n_pos_erased) {
   if (n_keys_erased) *n_keys_erased = 0;

@@ -24,9 +24,20 @@ class KmerPositionIndex:
     KMAX = 32
     WORDS = 1                     # 64-bit words per key
 
-    def __init__(self, k=31, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0, seed=43):
+    def __init__(self, k=31, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0, seed=43,
+                 w=None, order_hash="murmur", order_seed=42):
+        """w: index the (w,k)-minimizers of a text instead of all its windows (kmerhash_amd.minimizers_from_sequence: of every w
+        consecutive windows the one whose k-mer has the smallest order_hash(k-mer, order_seed), about 2 / (w + 1) of them);
+        build_sequences, build_fastq, append_sequences, append_fastq and find_sequences then sample with it.  None: every window."""
         if not 1 <= int(k) <= self.KMAX:
             raise ValueError("k must be 1..%d, got %r" % (self.KMAX, k))
+        if w is not None:
+            if self.WORDS != 1:
+                raise ValueError("minimizer sampling (w=) is not supported for 16-byte k-mers: use KmerPositionIndex (k <= 32)")
+            if not 1 <= int(w) <= 256:
+                raise ValueError("w must be 1..256 or None, got %r" % (w,))
+        self.w = None if w is None else int(w)
+        self.order_hash, self.order_seed = _hash_id(order_hash), int(order_seed)
         self.k, self.canonical, self.device = int(k), bool(canonical), int(device)
         self._L = K.lib()
         self._h = C.c_void_p()
@@ -84,6 +95,11 @@ class KmerPositionIndex:
             text = np.frombuffer(text, dtype=np.uint8)
         b = _Buf(text, np.uint8, 1)
         self._stream(b)
+        if self.w is not None:      # the same four calls over the minimizers of the text
+            verb, _, form = fn.partition("_from_")
+            self._chk(self._fn(verb + "_from_minimizers")(self._h, b.ptr, b.n, self.k, self.w, 1 if self.canonical else 0, self.order_hash,
+                                                          self.order_seed, b.where, 1 if form == "fastq" else 0, *more))
+            return self.total()
         self._chk(self._fn(fn)(self._h, b.ptr, b.n, self.k, 1 if self.canonical else 0, b.where, *more))
         return self.total()
 
@@ -216,6 +232,21 @@ class KmerPositionIndex:
         self._chk(self._fn("find")(self._h, q.ptr, n, q.where, optr, pptr, cap_out, C.byref(n_out)))
         return offs, out[: n_out.value]
 
+    def find_sequences(self, seq):
+        """the index's own sampling of a query text, then find: -> (qpos, offsets, positions).  The k-mers of `seq` are taken with
+        the index's k, canonical flag and -- when it was made with w -- its w, order hash and order seed (all windows otherwise);
+        qpos[i] is the byte offset in `seq` of query k-mer i and positions[offsets[i]:offsets[i + 1]] are its occurrences in the index.
+        Two device calls composed here; numpy in, numpy out, CUDA tensor in, tensors out."""
+        from .kmers import kmers_from_sequence, minimizers_from_sequence
+        if self.WORDS != 1:
+            raise ValueError("find_sequences is not supported for 16-byte k-mers")
+        if self.w is None:
+            km, qpos = kmers_from_sequence(seq, self.k, self.canonical, self.device, with_positions=True)
+        else:
+            km, qpos = minimizers_from_sequence(seq, self.k, self.w, self.canonical, self.order_hash, self.order_seed, self.device)
+        offsets, positions = self.find(km)
+        return qpos, offsets, positions
+
     # -- measurement -----------------------------------------------------------------------------
     def profile_enable(self, on=True):
         self._chk(self._fn("profile_enable")(self._h, 1 if on else 0))
@@ -239,8 +270,8 @@ class WideKmerPositionIndex(KmerPositionIndex):
     KMAX = 64
     WORDS = 2
 
-    def __init__(self, k=63, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0, seed=43):
-        super().__init__(k, canonical, hash, min_load_factor, max_load_factor, device, seed)
+    def __init__(self, k=63, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0, seed=43, w=None):
+        super().__init__(k, canonical, hash, min_load_factor, max_load_factor, device, seed, w=w)
 
     def export_info(self):
         """the Robin Hood info byte of every bucket of the index's table (uint8[capacity]): the counting twin's"""

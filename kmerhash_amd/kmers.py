@@ -72,6 +72,48 @@ def _kmers_pos(fn_name, seq, k, canonical, device):
     return out[: n_out.value], pos[: n_out.value]
 
 
+def minimizers_from_sequence(seq, k=15, w=10, canonical=True, order_hash="murmur", order_seed=42, device=0, _fastq=False):
+    """(w,k)-minimizers of `seq` -> (k-mers, positions), ascending positions: of every w consecutive valid windows the one whose
+    k-mer has the smallest order_hash(k-mer, order_seed) is kept (ties: the leftmost), each once -- about 2 / (w + 1) of the windows
+    of kmers_from_sequence(with_positions=True), and all of them for w = 1 (kh_minimizers_from_sequence in include/kmerhash_amd.h).
+    numpy uint64 / uint32 for host input, torch int64 / int32 CUDA tensors for device input.  A count pass first, then an exact
+    allocation.  In a stretch of equal k-mers (poly-A) every full-window start is kept."""
+    import ctypes as C
+    from . import _capi as K
+    from .table import _Buf, KhError, _hash_id
+    fn_name = "kh_minimizers_from_fastq" if _fastq else "kh_minimizers_from_sequence"
+    if isinstance(seq, (bytes, bytearray)):
+        seq = np.frombuffer(seq, dtype=np.uint8)
+    b = _Buf(seq, np.uint8, 1)
+    dev = b.where == K.KH_MEM_DEVICE
+    stream = torch.cuda.current_stream(device).cuda_stream if dev else None
+    fn, n_out = getattr(K.lib(), fn_name), C.c_uint64()
+    args = (b.ptr, b.n, int(k), int(w), 1 if canonical else 0, _hash_id(order_hash), int(order_seed), b.where)
+    st = fn(*args, None, None, 0, C.byref(n_out), device, stream)
+    if st != K.KH_OK:
+        raise KhError(st, fn_name)
+    m = n_out.value
+    if dev:
+        out = torch.empty(m, dtype=torch.int64, device=b.device)
+        pos = torch.empty(m, dtype=torch.int32, device=b.device)
+        optr, pptr = out.data_ptr(), pos.data_ptr()
+    else:
+        out = np.zeros(m, dtype=np.uint64)
+        pos = np.zeros(m, dtype=np.uint32)
+        optr, pptr = out.ctypes.data, pos.ctypes.data
+    if m:
+        st = fn(*args, optr, pptr, m, C.byref(n_out), device, stream)
+        if st != K.KH_OK:
+            raise KhError(st, fn_name)
+    return out, pos
+
+
+def minimizers_from_fastq(text, k=15, w=10, canonical=True, order_hash="murmur", order_seed=42, device=0):
+    """minimizers_from_sequence over the sequence lines of raw FASTQ text (whole 4-line records); positions are byte offsets into
+    the text, no pick falls on an id or quality line and no window spans two reads"""
+    return minimizers_from_sequence(text, k, w, canonical, order_hash, order_seed, device, _fastq=True)
+
+
 class KmerCounter:
     """counting index: k-mer -> number of occurrences (Reducer = std::plus, value 1 per occurrence)"""
 
