@@ -565,6 +565,18 @@ kh_status kh_index_build_from_minimizers(kh_index* x, const void* text /*[h|d] u
 kh_status kh_index_append_from_minimizers(kh_index* x, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, uint32_t w /*1..256*/, int canonical,
                                           kh_hash order_hash, uint64_t order_seed, kh_mem where, int fastq, uint32_t pos_base);
 
+/* a CSR that arrives in a permuted order, back into query order (the last step of a sharded find: the answers return grouped by owner
+ *      rank, in the permuted order of kh_shard_permute with vals = 0..n-1).
+ * counts_perm[j] and the segments of pos_perm (concatenated in order j = 0..n-1) belong to the query whose index in the caller's
+ * batch is origin[j]; origin is a permutation of 0..n-1 (precondition, not checked).  Writes the CSR in QUERY order:
+ * out_counts[i] (may be NULL), out_offsets[0..n] = exclusive scan (may be NULL), out_pos = the segments in query order (may be
+ * NULL: counts / offsets / *n_out only).  *n_out = total.  total > cap_out with out_pos != NULL: KH_ERR_INVALID, *n_out and the
+ * offsets set, out_pos untouched (the convention of kh_index_find).  Device buffers only; n == 0 and total == 0 are KH_OK.
+ * n or total >= 2^32: KH_ERR_INVALID before anything is touched.  Synchronous: the stream has drained when the call returns. */
+kh_status kh_csr_unpermute(const uint32_t* counts_perm, const uint32_t* pos_perm, const uint32_t* origin, uint64_t n,
+                           uint32_t* out_counts, uint64_t* out_offsets, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out,
+                           int device, void* hip_stream);
+
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);
 

@@ -74,6 +74,8 @@ SYMBOLS = [
     "kh_wide_index_append", "kh_wide_index_append_from_sequence", "kh_wide_index_append_from_fastq", "kh_wide_index_erase", "kh_wide_index_erase_counts",
     # (w,k)-minimizer sampling and the position index over the sampled k-mers
     "kh_minimizers_from_sequence", "kh_minimizers_from_fastq", "kh_index_build_from_minimizers", "kh_index_append_from_minimizers",
+    # a permuted CSR back into query order (the last step of a sharded index find)
+    "kh_csr_unpermute",
 ]
 
 _lib = None
@@ -239,6 +241,7 @@ def lib():
     L.kh_minimizers_from_fastq.argtypes = [vp, u64, u32, u32, i32, i32, u64, i32, vp, vp, u64, pu64, i32, vp]
     L.kh_index_build_from_minimizers.argtypes = [vp, vp, u64, u32, u32, i32, i32, u64, i32, i32]
     L.kh_index_append_from_minimizers.argtypes = [vp, vp, u64, u32, u32, i32, i32, u64, i32, i32, u32]
+    L.kh_csr_unpermute.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, pu64, i32, vp]
     for s in SYMBOLS:
         if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error", "kh_wide_index_last_error"):
             getattr(L, s).restype = i32

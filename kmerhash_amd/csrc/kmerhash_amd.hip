@@ -13,11 +13,13 @@
 //   by value : spectrum, selection and erase over a closed value range, one streaming pass over the slots each (kh_kernels_values.h).
 //   index   : kh_index, all occurrences per k-mer: counting insert -> slot-order ranks + CSR offsets -> scatter -> segment sort (kh_kernels_index.h).
 //             kh_windex: the same host code on a wide table (kh_index::kw == 2) and the kernels that touch a 32-byte slot (kh_kernels_index_wide.h).
+//   csr     : kh_csr_unpermute, a CSR that arrives in a permuted order back into query order: the index's scans and gather around one scatter (kh_kernels_csr.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
 #include "kh_kernels_values.h"
 #include "kh_kernels_index.h"
 #include "kh_kernels_index_wide.h"
+#include "kh_kernels_csr.h"
 #include "../../include/kmerhash_amd.h"
 
 #include <string>
@@ -3772,5 +3774,68 @@ kh_status kh_wide_index_export_info(kh_windex* x, uint8_t* out_host) {
 kh_status kh_wide_index_count(kh_windex* x, const void* keys, uint64_t n, kh_mem where, uint32_t* out_counts) { return kh_index_count(x, keys, n, where, out_counts); }
 kh_status kh_wide_index_find(kh_windex* x, const void* keys, uint64_t n, kh_mem where, uint64_t* out_offsets, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out) {
   return kh_index_find(x, keys, n, where, out_offsets, out_pos, cap_out, n_out);
+}
+
+// ---- a permuted CSR back into query order (kernels: kh_kernels_csr.h).  No handle: device buffers, the caller's stream.  One
+//      allocation holds every temporary; it is freed on every path after the stream has drained.
+kh_status kh_csr_unpermute(const uint32_t* counts_perm, const uint32_t* pos_perm, const uint32_t* origin, uint64_t n, uint32_t* out_counts,
+                           uint64_t* out_offsets, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, void* stream_) {
+  kh_table* t = nullptr;
+  if (n >> 32) return KH_ERR_INVALID;
+  if (n_out) *n_out = 0;
+  if (n && (!counts_perm || !origin)) return KH_ERR_INVALID;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (n == 0) {
+    if (!out_offsets) return KH_OK;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipMemsetAsync(out_offsets, 0, 8, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return KH_OK;
+  }
+  HIPCHK(hipSetDevice(device));
+  const uint64_t nst = (n + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
+  // ssums ull[nst + 1] | offsets u64[n + 1] (unless the caller's) | begin_perm u32[n + 1] | begin_q u32[n] | counts u32[n] (unless the caller's)
+  const size_t b_ssums = (nst + 1) * 8, b_off = out_offsets ? 0 : (n + 1) * 8, b_bp = (n + 2) / 2 * 8, b_bq = (n + 1) / 2 * 8, b_cq = out_counts ? 0 : n * 4;
+  char* blk = nullptr;
+  HIPCHK(pool_alloc(device, b_ssums + b_off + b_bp + b_bq + b_cq, reinterpret_cast<void**>(&blk)));
+  unsigned long long* ssums = reinterpret_cast<unsigned long long*>(blk);
+  uint64_t* doff = out_offsets ? out_offsets : reinterpret_cast<uint64_t*>(blk + b_ssums);
+  uint32_t* begin_perm = reinterpret_cast<uint32_t*>(blk + b_ssums + b_off);
+  uint32_t* begin_q = reinterpret_cast<uint32_t*>(blk + b_ssums + b_off + b_bp);
+  uint32_t* cq = out_counts ? out_counts : reinterpret_cast<uint32_t*>(blk + b_ssums + b_off + b_bp + b_bq);
+  int ncu = 256;
+  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
+  if (ncu <= 0) ncu = 256;
+  uint64_t total = 0;
+  kh_status st = KH_OK;
+  // 1. where every permuted slot's segment begins; the total is known (and checked) before any output is written
+  hipLaunchKernelGGL(k_index_tile_sums, dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, counts_perm, n, ssums);
+  hipLaunchKernelGGL(k_index_scan_sums, dim3(1), dim3(KI_SUMS_THREADS), 0, stream, ssums, nst);
+  hipLaunchKernelGGL((k_index_scan_apply<uint32_t>), dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, counts_perm, n, (const unsigned long long*)ssums, begin_perm);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(&total, ssums + nst, 8, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e == hipSuccess && (total >> 32)) st = KH_ERR_INVALID;
+  if (e == hipSuccess && st == KH_OK) {
+    if (n_out) *n_out = total;
+    // 2. counts and begins to their query; 3. the query-order offsets
+    hipLaunchKernelGGL(k_csr_scatter, dim3(grid_for(n, KC_THREADS, (uint32_t)ncu * 8)), dim3(KC_THREADS), 0, stream, counts_perm, (const uint32_t*)begin_perm, origin, n, cq, begin_q);
+    const bool move = out_pos && total && total <= cap_out;
+    if (out_offsets || move) {
+      hipLaunchKernelGGL(k_index_tile_sums, dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, (const uint32_t*)cq, n, ssums);
+      hipLaunchKernelGGL(k_index_scan_sums, dim3(1), dim3(KI_SUMS_THREADS), 0, stream, ssums, nst);
+      hipLaunchKernelGGL((k_index_scan_apply<uint64_t>), dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, (const uint32_t*)cq, n, (const unsigned long long*)ssums, doff);
+    }
+    if (out_pos && total > cap_out) st = KH_ERR_INVALID;
+    else if (move && !pos_perm) st = KH_ERR_INVALID;
+    // 4. the segments, one output element per lane
+    else if (move)
+      hipLaunchKernelGGL(k_index_gather, dim3(grid_for(total, 256, (uint32_t)ncu * 8)), dim3(256), 0, stream, pos_perm, (const uint32_t*)begin_q, (const uint64_t*)doff, n, total, out_pos);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  }
+  pool_free(device, blk);
+  if (e != hipSuccess) return e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP;
+  return st;
 }
 }  // extern "C"
