@@ -30,8 +30,13 @@ backend without the attribute has 1-D keys, as before.
 
 `backend` objects supply the two device-specific pieces so that the exchange logic can be exercised on CPU
 (gloo, world_size 2/3) with the oracle in tests; the product backend is GpuBackend.
+
+Layout: ShardExchange holds what every sharded structure uses (group, exchanges, collectives counter, failure protocol); ShardedTable
+(here) and ShardedKmerPositionIndex (dist_index.py) derive from it side by side.  GpuSharding is the one GPU implementation of
+shard / shard_counts / empty under the four GPU backends.
 """
 import os
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -47,47 +52,63 @@ DIST_SEED = 9876543   # distributed_batched_robinhood_map.hpp:513-534
 FORCE_COLLECTIVES = os.environ.get("KH_DIST_FORCE_COLLECTIVES", "0") == "1"
 
 
-class GpuBackend:
-    """local table = libkmerhash_amd table on this rank's GPU; sharding = kh_shard_permute (stable)"""
+class GpuSharding:
+    """what the GPU backends share: the device, the distribution hash and the stable partition of a batch by destination rank --
+    kh_shard_permute, or kh_wide_shard_permute for a backend with `key_words = 2` (keys are rows of an (n, 2) tensor)"""
 
-    def __init__(self, device, kind="rh", capacity=128, min_lf=0.35, max_lf=0.8, hash="murmur3avx64", seed=43,
-                 dist_hash="murmur3avx64", dist_seed=DIST_SEED):
+    def __init__(self, device, dist_hash, dist_seed):
+        """(a backend makes its table or index first, then calls this: a bad argument of the local structure is reported first)"""
         import ctypes as C
         from . import _capi as K
         from . import table as T
         self.C, self.K = C, K
         self.device = device
-        cls = T.hashmap_robinhood_doubling if kind == "rh" else T.hashmap_linearprobe_doubling
-        self.table = cls(capacity, min_lf, max_lf, hash=hash, seed=seed, device=device)
         self.dist_hash = T._hash_id(dist_hash)
         self.dist_seed = dist_seed
         self.torch_device = torch.device("cuda", device)
 
+    def _permute(self, keys, vals, p, permute):
+        """the one C call -> (keys grouped by destination rank, vals grouped, counts[p]); permute False: the counts alone"""
+        wide = getattr(self, "key_words", 1) == 2
+        name = "kh_wide_shard_permute" if wide else "kh_shard_permute"
+        if wide:
+            if keys.dim() != 2 or keys.shape[1] != 2 or keys.element_size() != 8:
+                raise ValueError("wide keys: expected a 64-bit tensor of shape (n, 2), got %s" % (tuple(keys.shape),))
+            keys = keys.contiguous()
+            vals = vals.contiguous() if vals is not None else None
+        ok = torch.empty_like(keys) if permute else None
+        ov = torch.empty_like(vals) if permute and vals is not None else None
+        counts = (self.C.c_uint64 * p)()
+        st = getattr(self.K.lib(), name)(self.dist_hash, self.dist_seed, p, keys.data_ptr(), vals.data_ptr() if vals is not None else None,
+                                         keys.shape[0] if wide else keys.numel(), ok.data_ptr() if permute else None,
+                                         ov.data_ptr() if ov is not None else None, counts, self.device,
+                                         torch.cuda.current_stream(self.device).cuda_stream)
+        if st != self.K.KH_OK:      # (only the 64-bit count-only call ever named itself so; the texts stay as they were)
+            raise self.K.KhError(st, name if wide or permute else name + " (count only)")
+        return ok, ov, [int(c) for c in counts]
+
     def shard(self, keys, vals, p):
         """-> (keys grouped by destination rank, vals grouped, counts[p]) ; stable inside a rank"""
-        n = keys.numel()
-        ok = torch.empty_like(keys)
-        ov = torch.empty_like(vals) if vals is not None else None
-        counts = (self.C.c_uint64 * p)()
-        st = self.K.lib().kh_shard_permute(self.dist_hash, self.dist_seed, p, keys.data_ptr(),
-                                           vals.data_ptr() if vals is not None else None, n, ok.data_ptr(),
-                                           ov.data_ptr() if ov is not None else None, counts, self.device,
-                                           torch.cuda.current_stream(self.device).cuda_stream)
-        if st != self.K.KH_OK:
-            raise self.K.KhError(st, "kh_shard_permute")
-        return ok, ov, [int(c) for c in counts]
+        return self._permute(keys, vals, p, True)
 
     def shard_counts(self, keys, p):
         """counts[p] of shard() without permuting anything"""
-        counts = (self.C.c_uint64 * p)()
-        st = self.K.lib().kh_shard_permute(self.dist_hash, self.dist_seed, p, keys.data_ptr(), None, keys.numel(), None, None,
-                                           counts, self.device, torch.cuda.current_stream(self.device).cuda_stream)
-        if st != self.K.KH_OK:
-            raise self.K.KhError(st, "kh_shard_permute (count only)")
-        return [int(c) for c in counts]
+        return self._permute(keys, None, p, False)[2]
 
     def empty(self, n, dtype):
+        """n: a length or a shape ((rows, 2) for the key buffers of a wide backend)"""
         return torch.empty(n, dtype=dtype, device=self.torch_device)
+
+
+class GpuBackend(GpuSharding):
+    """local table = libkmerhash_amd table on this rank's GPU; sharding = kh_shard_permute (stable)"""
+
+    def __init__(self, device, kind="rh", capacity=128, min_lf=0.35, max_lf=0.8, hash="murmur3avx64", seed=43,
+                 dist_hash="murmur3avx64", dist_seed=DIST_SEED):
+        from . import table as T
+        cls = T.hashmap_robinhood_doubling if kind == "rh" else T.hashmap_linearprobe_doubling
+        self.table = cls(capacity, min_lf, max_lf, hash=hash, seed=seed, device=device)
+        super().__init__(device, dist_hash, dist_seed)
 
     def shard_plan(self, keys, p, pieces):
         """ONE count sweep + scan + host synchronisation for a batch that travels in `pieces` pieces (kh_shard_plan_create):
@@ -104,7 +125,7 @@ class GpuBackend:
         return _ShardPlan(self, plan, keys), [int(b) for b in bounds], [[int(counts[i * p + r]) for r in range(p)] for i in range(pieces)]
 
 
-class WideGpuBackend:
+class WideGpuBackend(GpuSharding):
     """local table = the 16-byte-key Robin Hood table on this rank's GPU (hashmap_robinhood_doubling_wide_stream); sharding =
     kh_wide_shard_permute (stable).  Keys are (n, 2) int64 CUDA tensors.  No shard_plan: ShardedTable counts and permutes piece by
     piece and sends a query batch as one piece."""
@@ -112,48 +133,9 @@ class WideGpuBackend:
 
     def __init__(self, device, capacity=128, min_lf=0.35, max_lf=0.8, hash="murmur3avx64", seed=43, dist_hash="murmur3avx64",
                  dist_seed=DIST_SEED):
-        import ctypes as C
-        from . import _capi as K
-        from . import table as T
         from . import wide as W
-        self.C, self.K = C, K
-        self.device = device
         self.table = W.hashmap_robinhood_doubling_wide_stream(capacity, min_lf, max_lf, hash=hash, seed=seed, device=device)
-        self.dist_hash = T._hash_id(dist_hash)
-        self.dist_seed = dist_seed
-        self.torch_device = torch.device("cuda", device)
-
-    @staticmethod
-    def _rows(keys):
-        if keys.dim() != 2 or keys.shape[1] != 2 or keys.element_size() != 8:
-            raise ValueError("wide keys: expected a 64-bit tensor of shape (n, 2), got %s" % (tuple(keys.shape),))
-        return keys.contiguous()
-
-    def _permute(self, keys, vals, p, ok, ov):
-        counts = (self.C.c_uint64 * p)()
-        st = self.K.lib().kh_wide_shard_permute(self.dist_hash, self.dist_seed, p, keys.data_ptr(), vals.data_ptr() if vals is not None else None,
-                                                keys.shape[0], ok.data_ptr() if ok is not None else None,
-                                                ov.data_ptr() if ov is not None else None, counts, self.device,
-                                                torch.cuda.current_stream(self.device).cuda_stream)
-        if st != self.K.KH_OK:
-            raise self.K.KhError(st, "kh_wide_shard_permute")
-        return [int(c) for c in counts]
-
-    def shard(self, keys, vals, p):
-        """-> (keys (n, 2) grouped by destination rank, vals grouped, counts[p]) ; stable inside a rank"""
-        keys = self._rows(keys)
-        vals = vals.contiguous() if vals is not None else None
-        ok = torch.empty_like(keys)
-        ov = torch.empty_like(vals) if vals is not None else None
-        return ok, ov, self._permute(keys, vals, p, ok, ov)
-
-    def shard_counts(self, keys, p):
-        """counts[p] of shard() without permuting anything"""
-        return self._permute(self._rows(keys), None, p, None, None)
-
-    def empty(self, n, dtype):
-        """n: a length or a shape ((rows, 2) for key buffers)"""
-        return torch.empty(n, dtype=dtype, device=self.torch_device)
+        super().__init__(device, dist_hash, dist_seed)
 
 
 def plan_piece_bounds(n, pieces):
@@ -259,25 +241,19 @@ class _Span:
         return False
 
 
-class ShardedTable:
-    """dsc::batched_robinhood_map-style distributed map over torch.distributed (RCCL when backend='nccl')."""
+class ShardExchange:
+    """what the sharded structures share: the group, the exchanges and the failure protocol.  A subclass supplies `local` (this rank's
+    part of the structure) and its operations."""
 
     def __init__(self, backend, group=None, timing=False):
         self.b = backend
         self.group = group
         self.p = dist.get_world_size(group) if dist is not None and dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist is not None and dist.is_initialized() else 0
-        self._comm = None      # side stream of the pipelined operations, created on first use
         self.collectives = {"counts": 0, "payload": 0, "votes": 0}     # launches issued by this rank (tests assert the per-call numbers)
         self._ph = _Phases(self.b.torch_device.type == "cuda") if timing else None
-        self.query_pieces = 0          # pieces of THIS rank's find / count batches (0 = by size; GPU backend only)
-        self._late = None              # status words received with the last find / count (tensor [p]), not looked at yet
         self._fail_stage = 0           # test hook: the next collective call fails locally at this stage (1..4)
         self.key_words = int(getattr(backend, "key_words", 1))      # 2: keys are rows of an (n, 2) tensor (16-byte keys)
-
-    @property
-    def local(self):
-        return self.b.table
 
     def timings(self):
         """{phase: total ms since the last call} when constructed with timing=True"""
@@ -318,20 +294,6 @@ class ShardedTable:
             raise ex
         if worst:
             raise ShardPeerError(worst, where)
-
-    def _late_check(self):
-        if self._late is None:
-            return
-        t, self._late = self._late, None
-        worst = int(t.max().item())                      # (waits for the exchange that delivered the words)
-        if worst:
-            raise ShardPeerError(worst, "in the local part of the previous find / count: its results are invalid")
-
-    def synchronize(self):
-        """waits for the queued work of this rank and raises if any rank failed in the local part of the last find / count"""
-        if self.b.torch_device.type == "cuda":
-            torch.cuda.synchronize(self.b.torch_device)
-        self._late_check()
 
     def _like(self, rows, x):
         """a buffer of `rows` entries shaped like the entries of x (key rows of a wide backend keep their second dimension)"""
@@ -398,6 +360,103 @@ class ShardedTable:
         self._exchange([(s, so, send_counts, o, ro, recv_counts) for s, o in zip(sends, outs) if s is not None])
         return outs
 
+    def _reduce(self, vals, ex, where):
+        """all-reduce(sum) of this rank's numbers and its status word: the global numbers; raises on EVERY rank if any rank failed"""
+        t = torch.tensor([int(v) for v in vals] + [self._status_of(ex) if ex is not None else 0], dtype=torch.int64, device=self._ctl_device())
+        dist.all_reduce(t, group=self.group)
+        self.collectives["reduce"] += 1
+        out = t.cpu().tolist()
+        self._raise_if(ex, out[-1], where)
+        return out[:-1]
+
+    def _words(self, ex, device):
+        """(this rank's status word to send to every peer, room for theirs): one more array of a payload exchange"""
+        st_out = torch.full((1,), self._status_of(ex) if ex is not None else 0, dtype=torch.int64, device=device)
+        status_in = torch.zeros(self.p, dtype=torch.int64, device=device)
+        return st_out, status_in, (st_out, [0] * self.p, [1] * self.p, status_in, list(range(self.p)), [1] * self.p)
+
+    def _to_owners(self, batch, ex=None, origin=False, sent=None, more=None):
+        """this rank's batch to the owners of its keys: grouped by owner (stage 1), the counts exchanged with the status word, the
+        receive side allocated (stage 2) and voted on, ONE grouped payload exchange.
+        batch()  -> (keys, vals or None) after the caller's own checks; not called when the caller failed already (`ex`)
+        origin   : the value that goes through the permutation with a key is its index in the batch; it stays here.  Other vals travel
+        sent     : stage 3 is the exchange itself -- _inject(3) before it and a vote with this text after it
+        more(pk) -> what else the receive side needs, allocated under stage 2
+        -> pk, pv, sc, so (permuted keys and vals, send counts and offsets), rk, rv, rc, ro (the same received), more.  It returns
+        only when no rank has failed so far: a failure up to here is raised, on every rank, by the count exchange or by a vote"""
+        p = self.p
+        sc, pk, pv = [0] * p, None, None
+        if ex is None:
+            try:
+                self._inject(1)
+                keys, vals = batch()
+                with self._span("permute"):
+                    if origin:
+                        vals = torch.arange(keys.shape[0], dtype=torch.int32, device=keys.device)
+                    pk, pv, sc = self.b.shard(keys, vals, p)
+            except Exception as e:
+                ex = e
+        rc, worst = self._exchange_counts([[sc[r]] for r in range(p)], ex)
+        self._raise_if(ex, worst, "before the count exchange; nothing was exchanged")
+        rc = [rc[s][0] for s in range(p)]
+        rtot = sum(rc)
+        so, ro = self._offs(sc), self._offs(rc)
+        rk = rv = extra = None
+        try:
+            self._inject(2)
+            rk = self._like(rtot, pk)
+            if pv is not None and not origin:
+                rv = self.b.empty(rtot, pv.dtype)
+            if more is not None:
+                extra = more(pk)
+        except Exception as e:
+            ex = e
+        self._vote(ex, "while preparing to receive; nothing was exchanged")
+        if sent:
+            try:
+                self._inject(3)
+            except Exception as e:
+                ex = e
+        with self._span("exchange"):
+            self._exchange([(pk, so, sc, rk, ro, rc)] + ([(pv, so, sc, rv, ro, rc)] if rv is not None else []))
+        if sent:
+            self._vote(ex, sent)
+        return SimpleNamespace(pk=pk, pv=pv, sc=sc, so=so, rk=rk, rv=rv, rc=rc, ro=ro, more=extra)
+
+
+class ShardedTable(ShardExchange):
+    """dsc::batched_robinhood_map-style distributed map over torch.distributed (RCCL when backend='nccl')."""
+
+    def __init__(self, backend, group=None, timing=False):
+        super().__init__(backend, group, timing)
+        self._comm = None              # side stream of the pipelined operations, created on first use
+        self.query_pieces = 0          # pieces of THIS rank's find / count batches (0 = by size; GPU backend only)
+        self._late = None              # status words received with the last find / count (tensor [p]), not looked at yet
+
+    @property
+    def local(self):
+        return self.b.table
+
+    def _late_check(self):
+        if self._late is None:
+            return
+        t, self._late = self._late, None
+        worst = int(t.max().item())                      # (waits for the exchange that delivered the words)
+        if worst:
+            raise ShardPeerError(worst, "in the local part of the previous find / count: its results are invalid")
+
+    def synchronize(self):
+        """waits for the queued work of this rank and raises if any rank failed in the local part of the last find / count"""
+        if self.b.torch_device.type == "cuda":
+            torch.cuda.synchronize(self.b.torch_device)
+        self._late_check()
+
+    def _comm_streams(self):
+        """(the caller's stream, the side stream the exchanges of the pipelined operations run on)"""
+        if self._comm is None:
+            self._comm = torch.cuda.Stream(device=self.b.torch_device)
+        return torch.cuda.current_stream(self.b.torch_device), self._comm
+
     # ---- batch operations (collective: every rank calls them) -----------------------------------------
     def insert_counts(self, keys, chunks=1):
         """counting_batched_robinhood_map::insert(vector<Key>) (distributed_batched_robinhood_map.hpp:2542-2950): every key
@@ -454,12 +513,7 @@ class ShardedTable:
             self._vote(ex, "while preparing to receive; nothing was exchanged")
             # ---- stage 3: the pieces.  A local failure is kept; the rank goes on exchanging and skips its local work
             kept = []
-            cur = comm = None
-            if cuda:
-                cur = torch.cuda.current_stream(self.b.torch_device)
-                if self._comm is None:
-                    self._comm = torch.cuda.Stream(device=self.b.torch_device)
-                comm = self._comm
+            cur, comm = self._comm_streams() if cuda else (None, None)
             landed = None
 
             def feed(item):
@@ -630,12 +684,7 @@ class ShardedTable:
                 ex = e
             self._vote(ex, "while preparing to receive; nothing was exchanged")
             # ---- stage 3: everything is queued; a local failure is kept and the rank goes on exchanging
-            cur = comm = None
-            if cuda:
-                cur = torch.cuda.current_stream(self.b.torch_device)
-                if self._comm is None:
-                    self._comm = torch.cuda.Stream(device=self.b.torch_device)
-                comm = self._comm
+            cur, comm = self._comm_streams() if cuda else (None, None)
             ev_p = []
             for i in range(rounds):
                 if plan is not None and i < mine and ex is None:
@@ -719,9 +768,8 @@ class ShardedTable:
                     arrays.append((lv, so, rcn[i], out_v, sdn[i], scn[i]))
                 arrays.append((lf, so, rcn[i], out_f, sdn[i], scn[i]))
                 if last:        # the status word of this rank's local work rides with the last result exchange
-                    st_out = torch.full((1,), self._status_of(ex) if ex is not None else 0, dtype=torch.int64, device=rkeys.device)
-                    status_in = torch.zeros(p, dtype=torch.int64, device=rkeys.device)
-                    arrays.append((st_out, [0] * p, [1] * p, status_in, list(range(p)), [1] * p))
+                    _, status_in, words = self._words(ex, rkeys.device)
+                    arrays.append(words)
                 if cuda:
                     comm.wait_stream(cur)
                     with torch.cuda.stream(comm):

@@ -1,7 +1,8 @@
 """The k-mer position index sharded across the GPUs of one node (one process per GPU, torch.distributed): ShardedKmerPositionIndex.
 
-The pattern of kmerhash_amd.dist.ShardedTable -- it IS a ShardedTable as far as the exchange helpers, the collectives counter, the
-failure protocol and host staging under gloo go --, over a local KmerPositionIndex instead of a local table:
+The pattern of kmerhash_amd.dist.ShardedTable over a local KmerPositionIndex instead of a local table.  The two are siblings: both derive
+from kmerhash_amd.dist.ShardExchange (the exchange helpers, the collectives counter, the failure protocol, host staging under gloo); no
+table operation exists on the index.
     owner rank = dist_hash(key, seed 9876543) & (p-1)   (or % p); the local index hashes with its own seed (43)
     append : (key, position) pairs permuted into p segments with the position as the value (kh_shard_permute), counts exchanged, keys
              and positions SoA in ONE grouped payload launch, then the local kh_index_append of what arrived.  The result of an append
@@ -24,7 +25,7 @@ global numbers, the sum of the ranks' status words with them -- it closes the ca
     erase_counts / drop_above / size / total / clear    : 1 reduce
 With one rank and no KH_DIST_FORCE_COLLECTIVES=1 every method is the local call and nothing else.
 
-Failure protocol: ShardedTable's.  A rank that fails locally keeps taking part in the collectives the call still has to run and sends
+Failure protocol: ShardExchange's, as ShardedTable has it.  A rank that fails locally keeps taking part in the collectives the call still has to run and sends
 empty or zero payloads; every rank raises -- the failing rank its own exception, the others ShardPeerError; no rank waits without bound.
 All calls are synchronous (the local find waits for its total anyway), so there is no late status: a vote or a reduce closes each call.
 After a failed append the failing rank's local index is EMPTY (the contract of kh_index_append) while the others hold their share:
@@ -37,31 +38,21 @@ WideIndexGpuBackend.  Not built here: pipelined pieces, kh_shard
 C++ RCCL library, stitching across ranks' texts, 64-bit positions, strand bits."""
 import numpy as np
 
-from .dist import DIST_SEED, GpuBackend, ShardedTable, ShardPeerError, WideGpuBackend, dist, torch  # noqa: F401
+from .dist import DIST_SEED, GpuBackend, GpuSharding, ShardedTable, ShardExchange, ShardPeerError, WideGpuBackend, dist, torch  # noqa: F401
 
 
-class IndexGpuBackend:
+class IndexGpuBackend(GpuSharding):
     """local index = KmerPositionIndex on this rank's GPU (64-bit k-mers, k <= 32; w: minimizer sampling); sharding = kh_shard_permute"""
 
     def __init__(self, device, k=31, canonical=True, hash="farm", seed=43, w=None, order_hash="murmur", order_seed=42, min_lf=0.35,
                  max_lf=0.8, dist_hash="murmur3avx64", dist_seed=DIST_SEED):
-        import ctypes as C
-        from . import _capi as K
-        from . import table as T
-        self.C, self.K = C, K
-        self.device = device
         self.index = self._make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed)
-        self.dist_hash = T._hash_id(dist_hash)
-        self.dist_seed = dist_seed
-        self.torch_device = torch.device("cuda", device)
+        super().__init__(device, dist_hash, dist_seed)
 
     @staticmethod
     def _make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed):
         from .index import KmerPositionIndex
         return KmerPositionIndex(k, canonical, hash, min_lf, max_lf, device, seed, w=w, order_hash=order_hash, order_seed=order_seed)
-
-    shard = GpuBackend.shard          # (keys grouped by destination rank, vals grouped, counts[p]); stable inside a rank
-    empty = GpuBackend.empty
 
     def _text(self, text):
         if isinstance(text, (bytes, bytearray)):
@@ -114,18 +105,13 @@ class WideIndexGpuBackend(IndexGpuBackend):
         from .index import WideKmerPositionIndex
         return WideKmerPositionIndex(k, canonical, hash, min_lf, max_lf, device, seed)
 
-    _rows = staticmethod(WideGpuBackend._rows)
-    _permute = WideGpuBackend._permute
-    shard = WideGpuBackend.shard
-    empty = WideGpuBackend.empty
-
     def text_pairs(self, text, fastq=False):
         from .wide import kmers128_from_sequence
         x = self.index
         return kmers128_from_sequence(self._text(text), x.k, x.canonical, self.device, _fastq=fastq, with_positions=True)
 
 
-class ShardedKmerPositionIndex(ShardedTable):
+class ShardedKmerPositionIndex(ShardExchange):
     """k-mer -> ascending positions of ALL its occurrences in the texts of all ranks.  Every method is COLLECTIVE: every rank calls
     it, each with its own batch, which may be empty.  Test hook: `_fail_stage` = 1..4 makes the next append / count / find / erase
     fail locally at that stage (1: permute, 2: receive buffers, 3: exchange (append, erase) or local lookup (count, find), 4: local
@@ -139,12 +125,8 @@ class ShardedKmerPositionIndex(ShardedTable):
     def local(self):
         return self.b.index
 
-    def _not_for_an_index(self, *a, **kw):
-        raise TypeError("a table operation: the sharded index has append / build / count / find / erase / erase_counts / drop_above")
-
-    insert = insert_counts = value_histogram = erase_values = _query = _not_for_an_index
-
     def synchronize(self):
+        """waits for the queued work of this rank (every call is closed by a vote or a reduce: there is no late status)"""
         if self.b.torch_device.type == "cuda":
             torch.cuda.synchronize(self.b.torch_device)
 
@@ -162,21 +144,6 @@ class ShardedKmerPositionIndex(ShardedTable):
             pos = torch.from_numpy(np.ascontiguousarray(pos).astype(np.uint32, copy=False).view(np.int32).copy())
         return pos.to(self.b.torch_device)
 
-    def _reduce(self, vals, ex, where):
-        """all-reduce(sum) of this rank's numbers and its status word: the global numbers; raises on EVERY rank if any rank failed"""
-        t = torch.tensor([int(v) for v in vals] + [self._status_of(ex) if ex is not None else 0], dtype=torch.int64, device=self._ctl_device())
-        dist.all_reduce(t, group=self.group)
-        self.collectives["reduce"] += 1
-        out = t.cpu().tolist()
-        self._raise_if(ex, out[-1], where)
-        return out[:-1]
-
-    def _words(self, ex, device):
-        """(this rank's status word to send to every peer, room for theirs): one more array of a payload exchange"""
-        st_out = torch.full((1,), self._status_of(ex) if ex is not None else 0, dtype=torch.int64, device=device)
-        status_in = torch.zeros(self.p, dtype=torch.int64, device=device)
-        return st_out, status_in, (st_out, [0] * self.p, [1] * self.p, status_in, list(range(self.p)), [1] * self.p)
-
     # ---- append ------------------------------------------------------------------------------------------
     def append(self, keys, pos):
         """more (k-mer, position) pairs of this rank onto the global index; returns the number of pairs this rank gave"""
@@ -192,53 +159,27 @@ class ShardedKmerPositionIndex(ShardedTable):
                 raise ex
             with self._span("local_append"):
                 return (self.local.build if must_be_empty else self.local.append)(self._keys(keys), self._pos(pos))
-        p = self.p
-        n, sc, pk, pp = 0, [0] * p, None, None
-        # ---- stage 1 (local): the pairs grouped by owner rank
-        if ex is None:
-            try:
-                self._inject(1)
-                keys, pos = self._keys(keys), self._pos(pos)
-                n = keys.shape[0]
-                if pos.numel() != n:
-                    raise ValueError("keys and positions must have the same length")
-                if must_be_empty and self.local.total() != 0:
-                    raise ValueError("build: the index is not empty (clear() first, or append)")
-                with self._span("permute"):
-                    pk, pp, sc = self.b.shard(keys, pos, p)
-            except Exception as e:
-                ex = e
-        rc, worst = self._exchange_counts([[sc[r]] for r in range(p)], ex)
-        self._raise_if(ex, worst, "before the count exchange; nothing was exchanged")
-        rcounts = [rc[s][0] for s in range(p)]
-        rtot = sum(rcounts)
-        # ---- stage 2 (local): the receive side
-        rk = rp = None
-        try:
-            self._inject(2)
-            rk, rp = self._like(rtot, pk), self.b.empty(rtot, pp.dtype)
-        except Exception as e:
-            ex = e
-        self._vote(ex, "while preparing to receive; nothing was exchanged")
-        # ---- stage 3: keys and positions SoA in one grouped launch
-        try:
-            self._inject(3)
-        except Exception as e:
-            ex = e
-        so, ro = self._offs(sc), self._offs(rcounts)
-        with self._span("exchange"):
-            self._exchange([(pk, so, sc, rk, ro, rcounts), (pp, so, sc, rp, ro, rcounts)])
-        self._vote(ex, "while the pairs were exchanged; nothing was appended on any rank")
+
+        def batch():
+            k, q = self._keys(keys), self._pos(pos)
+            if q.numel() != k.shape[0]:
+                raise ValueError("keys and positions must have the same length")
+            if must_be_empty and self.local.total() != 0:
+                raise ValueError("build: the index is not empty (clear() first, or append)")
+            return k, q
+        # ---- stages 1..3: the pairs grouped by owner rank, keys and positions SoA in one grouped launch
+        x = self._to_owners(batch, ex, sent="while the pairs were exchanged; nothing was appended on any rank")
+        ex = None                                                 # (no rank has failed so far, or _to_owners had raised)
         # ---- stage 4: the local append of what arrived
         try:
             self._inject(4)
-            if rtot:
+            if x.rk.shape[0]:
                 with self._span("local_append"):
-                    self.local.append(rk, rp)
+                    self.local.append(x.rk, x.rv)
         except Exception as e:
             ex = e
         self._vote(ex, "in the local append: the failing rank's index is empty, the global index is undefined until a collective clear()")
-        return n
+        return x.pk.shape[0]
 
     def _text_pairs(self, text, pos_base, fastq):
         """(k-mers, positions + pos_base, None) of this rank's text, or (None, None, the exception)"""
@@ -295,36 +236,18 @@ class ShardedKmerPositionIndex(ShardedTable):
                 raise ex
             with self._span("local_query"):
                 return self.local.find(self._keys(keys)) if want_pos else self.local.count(self._keys(keys))
-        p = self.p
-        n, sc, pk, origin = 0, [0] * p, None, None
-        # ---- stage 1 (local): the keys grouped by owner rank; the value that travels with a key through the permutation is its
-        #      index in the caller's batch
-        if ex is None:
-            try:
-                self._inject(1)
-                keys = self._keys(keys)
-                n = keys.shape[0]
-                if n >= 2 ** 31:
-                    raise ValueError("a query batch holds fewer than 2^31 keys")
-                with self._span("permute"):
-                    pk, origin, sc = self.b.shard(keys, torch.arange(n, dtype=torch.int32, device=keys.device), p)
-            except Exception as e:
-                ex = e
-        rc, worst = self._exchange_counts([[sc[r]] for r in range(p)], ex)
-        self._raise_if(ex, worst, "before the count exchange; nothing was exchanged")
-        rcounts = [rc[s][0] for s in range(p)]
+
+        def batch():
+            k = self._keys(keys)
+            if k.shape[0] >= 2 ** 31:
+                raise ValueError("a query batch holds fewer than 2^31 keys")
+            return k, None
+        # ---- stages 1, 2 and the keys out: grouped by owner rank; the value that travels with a key through the permutation is its
+        #      index in the caller's batch (origin)
+        x = self._to_owners(batch, ex, origin=True, more=lambda pk: self.b.empty(pk.shape[0], torch.int32))
+        p, ex, origin, cperm = self.p, None, x.pv, x.more
+        sc, so, rkeys, rcounts, ro = x.sc, x.so, x.rk, x.rc, x.ro
         rtot = sum(rcounts)
-        so, ro = self._offs(sc), self._offs(rcounts)
-        # ---- stage 2 (local): the receive side
-        rkeys = cperm = None
-        try:
-            self._inject(2)
-            rkeys, cperm = self._like(rtot, pk), self.b.empty(n, torch.int32)
-        except Exception as e:
-            ex = e
-        self._vote(ex, "while preparing to receive; nothing was exchanged")
-        with self._span("exchange"):
-            self._exchange([(pk, so, sc, rkeys, ro, rcounts)])
         # ---- stage 3 (local): ONE lookup of everything received.  Receive order is grouped by source rank, so the positions of every
         #      source are one contiguous stretch of the local CSR.  A failure is kept; the rank goes on with zero counts and no positions
         lc, lpos, ptot = None, None, [0] * p
@@ -381,39 +304,14 @@ class ShardedKmerPositionIndex(ShardedTable):
         """every occurrence of the given k-mers out of the global index -> GLOBAL (distinct keys erased, positions erased)"""
         if self._single():
             return self.local.erase(self._keys(keys))
-        p = self.p
-        ex, sc, pk = None, [0] * p, None
-        try:
-            self._inject(1)
-            keys = self._keys(keys)
-            with self._span("permute"):
-                pk, _, sc = self.b.shard(keys, None, p)
-        except Exception as e:
-            ex = e
-        rc, worst = self._exchange_counts([[sc[r]] for r in range(p)], ex)
-        self._raise_if(ex, worst, "before the count exchange; nothing was exchanged")
-        rcounts = [rc[s][0] for s in range(p)]
-        rtot = sum(rcounts)
-        rkeys = None
-        try:
-            self._inject(2)
-            rkeys = self._like(rtot, pk)
-        except Exception as e:
-            ex = e
-        self._vote(ex, "while preparing to receive; nothing was exchanged")
-        try:
-            self._inject(3)
-        except Exception as e:
-            ex = e
-        with self._span("exchange"):
-            self._exchange([(pk, self._offs(sc), sc, rkeys, self._offs(rcounts), rcounts)])
-        self._vote(ex, "while the keys were exchanged; nothing was erased on any rank")
+        x = self._to_owners(lambda: (self._keys(keys), None), sent="while the keys were exchanged; nothing was erased on any rank")
+        ex = None
         nk = npos = 0
         try:
             self._inject(4)
-            if rtot:
+            if x.rk.shape[0]:
                 with self._span("local_erase"):
-                    nk, npos = self.local.erase(rkeys)
+                    nk, npos = self.local.erase(x.rk)
         except Exception as e:
             ex = e
         return tuple(self._reduce([nk, npos], ex, "in the local erase: the ranks that did not fail erased their share"))

@@ -54,7 +54,7 @@ def test_python_surface():
     assert kh.ShardedKmerPositionIndex is dist_index.ShardedKmerPositionIndex
     assert kh.IndexGpuBackend is dist_index.IndexGpuBackend and kh.WideIndexGpuBackend is dist_index.WideIndexGpuBackend
     S = kh.ShardedKmerPositionIndex
-    assert issubclass(S, dist.ShardedTable)
+    assert issubclass(S, dist.ShardExchange) and not issubclass(S, dist.ShardedTable)      # a sibling of the table, not a table
     for name in ("append", "build", "append_sequences", "append_fastq", "build_sequences", "build_fastq", "count", "find", "find_sequences",
                  "erase", "erase_counts", "drop_above", "size", "total", "clear", "synchronize", "timings"):
         assert callable(getattr(S, name)), name
