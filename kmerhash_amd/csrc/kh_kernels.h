@@ -620,6 +620,18 @@ struct KhPartParams {
   // workgroup then knows where its records lie without reading a tile list: it requests them together with the segment's cursor
   // (ONE HBM round trip before the first record arrives instead of three: tile count, tile, records) and drops what lies behind the fill.
   uint64_t slot_in; const unsigned long long* cur_in; uint32_t tps;
+  // XCD-private write fronts (histogram-free mode; speed only -- results do not depend on where a workgroup really runs).  A run ends
+  // inside a 64-byte segment (the unit of a write request from L2 to memory) that the NEXT reservation on the same cursor completes; the
+  // write-request counters are consistent with such a segment leaving two L2s as two requests when that reservation comes from another XCD
+  // (profiles/xcd_fronts_counters.json).  First pass: sub_slot != 0 cuts every slot into eight sub-slots of sub_slot records with a cursor each
+  // (cursor[digit * 8 + x], x = blockIdx.x & 7: the round-robin placement of workgroups on the eight XCDs), so every front is fed from
+  // one XCD.  Second pass: the input segments are those sub-slots (seg_shift = 3: output segment = input segment >> 3) and xcd_buckets
+  // maps workgroup w to XCD (w & 7)'s share of the level-1 buckets (x, x + 8, ...), all sub-slots and pieces of a bucket on one XCD:
+  // the output fronts of a bucket are then private to that XCD with the output layout unchanged.
+  // (Whether a SUB-slot overflows depends on the order of the input, not on the key set alone: a sub-slot holds what ONE XCD's tiles send
+  //  to a bucket.  Hashed keys in any order fill the eight alike.  hash = identity with sorted or sequential keys does not -- the tiles of
+  //  workgroups w & 7 == x then hold keys of half of the digits only -- and such a batch is repeated with exact offsets, as after any overflow.)
+  uint64_t sub_slot; uint32_t seg_shift; int xcd_buckets;
   // (k_part_scatter<HASH, true>: rec_in / orec hold KhRec12 records instead -- histogram-free mode only)
 };
 
@@ -724,7 +736,11 @@ __global__ KH_PART_LB(RK) void k_part_scatter(KhPartParams P) {
   const uint32_t ntiles = P.tiles ? *P.ntiles_dev : P.ntiles;
   if (blockIdx.x >= ntiles) return;
   uint32_t tile = blockIdx.x;
-  if (P.xcd_swizzle && (tile | 63u) < ntiles) {      // (whole groups of 64 tiles only) eight CONSECUTIVE tiles per XCD: b, b + 8, ... share one
+  const uint32_t xcd = blockIdx.x & 7u;             // (of the workgroup, not of the swizzled tile)
+  if (P.xcd_buckets) {                              // (the grid is nb1 * 8 * tps, nb1 a multiple of 8) XCD x: buckets x, x + 8, ..., each 8 * tps tiles
+    const uint32_t j = tile >> 3, per = 8u * P.tps, i = j / per;
+    tile = (i * 8u + xcd) * per + (j - i * per);    // = (bucket * 8 + sub-slot) * tps + piece
+  } else if (P.xcd_swizzle && (tile | 63u) < ntiles) {    // (whole groups of 64 tiles only) eight CONSECUTIVE tiles per XCD: b, b + 8, ... share one
     const uint32_t x = tile & 7u, j = (tile >> 3) & 7u;
     tile = (tile & ~63u) + x * 8u + j;
   }
@@ -824,10 +840,13 @@ __global__ KH_PART_LB(RK) void k_part_scatter(KhPartParams P) {
       loff[b] = run;
       run += c;
       if (c) {
-        unsigned long long g = atomicAdd(&P.cursor[(uint64_t)d.seg * nb + b], (unsigned long long)c);
-        // histogram-free mode: a reservation that runs over the partition's slot is redirected, whole, to the dump area behind
+        uint64_t ci = (uint64_t)(d.seg >> P.seg_shift) * nb + b;
+        uint64_t end = (ci + 1) * P.slot;
+        if (P.sub_slot) { end -= (uint64_t)(7u - xcd) * P.sub_slot; ci = ci * 8u + xcd; }      // (this XCD's sub-slot; slot = 8 * sub_slot)
+        unsigned long long g = atomicAdd(&P.cursor[ci], (unsigned long long)c);
+        // histogram-free mode: a reservation that runs over the partition's (sub-)slot is redirected, whole, to the dump area behind
         // the output (one tile's worth of records) and the batch is flagged for a second try with exact offsets
-        if (P.slot && g + c > ((uint64_t)d.seg * nb + b + 1) * P.slot) { *P.overflow = 1u; g = P.dump + loff[b]; }
+        if (P.slot && g + c > end) { *P.overflow = 1u; g = P.dump + loff[b]; }
         gres[k] = g;
       }
     }
@@ -974,10 +993,11 @@ __global__ void k_sample_dups(const char* __restrict__ kbase, uint32_t kstride, 
 
 // histogram-free partition: cursor[j] = j * slot (and, if asked, the same values as partition start offsets)
 // both levels of a histogram-free partition in one launch: level-1 cursors, level-2 cursors + slot starts, the overflow flag
-__global__ void k_init_cursors2(unsigned long long* __restrict__ cur1, uint64_t n1, uint64_t slot1, unsigned long long* __restrict__ cur2,
+// (sub1 = 8: eight level-1 cursors per bucket, cursor b * 8 + x at the start of bucket b's x-th sub-slot of slot1 / 8 records; else sub1 = 1)
+__global__ void k_init_cursors2(unsigned long long* __restrict__ cur1, uint64_t n1, uint64_t slot1, uint32_t sub1, unsigned long long* __restrict__ cur2,
                                 uint64_t* __restrict__ starts, uint64_t n2, uint64_t slot2, uint32_t* __restrict__ ovf) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n1) cur1[i] = i * slot1;
+  if (i < n1 * sub1) cur1[i] = (i / sub1) * slot1 + (i % sub1) * (slot1 / sub1);
   if (i < n2) cur2[i] = i * slot2;
   if (i <= n2) starts[i] = i * slot2;
   if (i == 0) *ovf = 0u;

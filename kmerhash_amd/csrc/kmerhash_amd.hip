@@ -20,6 +20,7 @@
 #include "kh_kernels_index.h"
 #include "kh_kernels_index_wide.h"
 #include "kh_kernels_csr.h"
+#include "kh_part_sizing.h"
 #include "../../include/kmerhash_amd.h"
 
 #include <string>
@@ -586,14 +587,17 @@ struct Partitioned {
   uint32_t* overflow;                           // device flag: a partition outgrew its slot (the batch must be redone with exact offsets)
   int rec12;                                    // 0: 16-byte records; 1: 12-byte (key, value) (histogram-free layout only); 2: 8-byte keys (counting insert)
 };
-// slot of a histogram-free partition with mean m records: m + 7 sigma (hashed keys: Poisson) + a little
-// (vf: variance of a partition's fill over its mean -- 1 for distinct keys (Poisson in the records); a batch with duplicates fills its partitions
-//  key by key, E[m^2] / E[m] records at a time: insert_core estimates that factor from the duplicate sample)
-inline uint64_t slack_slot(double mean, double vf = 1.0) { return (uint64_t)(mean + 7.0 * std::sqrt(mean * vf) + 16.0); }
+// (slack_slot: the slot of a histogram-free partition, mean + 7 sigma -- kh_part_sizing.h)
 const bool g_disable_slack = getenv("KH_DISABLE_SLACK_PARTITION") != nullptr;      // test hook: exact offsets always
 // eight consecutive partition tiles per XCD (blocks b, b + 8, ... share one): the adjacent output runs of consecutive tiles meet in
 // one L2 (-3 % scatter time, measured A/B); KH_DISABLE_XCD_SWIZZLE=1 turns it off
 const int g_xcd_swizzle = getenv("KH_DISABLE_XCD_SWIZZLE") ? 0 : 1;
+// XCD-private write fronts of the histogram-free partition (KhPartParams::sub_slot): KH_DISABLE_XCD_FRONTS=1 restores one cursor per
+// level-1 bucket and the tile order of the second pass
+const int g_xcd_fronts = getenv("KH_DISABLE_XCD_FRONTS") ? 0 : 1;
+// (sizing: xcd_sub_slot in kh_part_sizing.h.  KH_XCD_FRONTS_MIN_TILES: the least mean fill of a sub-slot, in tiles, for which the sub-slots are used --
+//  default 4; the benchmark shape has 6.4, a batch of 6e6 records into 2^12 partitions 1.4.  Read at every call: the tests reach the sub-slots at small shapes with it)
+inline uint32_t xcd_fronts_min_tiles() { const char* e = getenv("KH_XCD_FRONTS_MIN_TILES"); return e ? (uint32_t)std::max(0, atoi(e)) : 4u; }
 // records the two buffers of partition_batch must hold
 inline uint64_t part_buffer_records(uint64_t n, uint32_t PB, bool allow_slack, double vf = 1.0) {
   if (!allow_slack || g_disable_slack || PB <= 11 || n < (uint64_t(256) << PB)) return n;
@@ -617,8 +621,11 @@ kh_status partition_batch(kh_table* t, const char* kbase, uint32_t kstride, cons
     // (a piece of a streamed insert: its level-1 buckets are sized for the piece, the final slots -- shared -- for the whole batch)
     const uint64_t slot = shared ? shared->slot : slack_slot((double)n / (double)nparts, vf);
     const uint64_t slot1 = shared ? slack_slot((double)n / (double)nb1) : slot * nb2;
+    // (XCD-private fronts: eight sub-slots per level-1 bucket, see xcd_sub_slot; a streamed piece keeps one cursor per bucket)
+    uint32_t tps_sub = 0;
+    const uint64_t sub_slot = (g_xcd_fronts && !shared) ? xcd_sub_slot(n, nb1, nb2, slot1, vf, KH_PART_TILE, xcd_fronts_min_tiles(), &tps_sub) : 0;
     unsigned long long *cur1, *cur2; uint64_t* starts; uint32_t* ovf;
-    TAKE(cur1, unsigned long long, nb1);
+    TAKE(cur1, unsigned long long, sub_slot ? (size_t)nb1 * 8 : nb1);
     if (shared) { cur2 = shared->cur2; starts = shared->starts; ovf = shared->ovf; }
     else { TAKE(cur2, unsigned long long, nparts); TAKE(starts, uint64_t, (size_t)nparts + 1); TAKE(ovf, uint32_t, 1); }
     // the second pass cuts every level-1 slot into tiles by arithmetic (no tile list, see KhPartParams::slot_in) -- up to mean + 9 sigma of a
@@ -626,10 +633,10 @@ kh_status partition_batch(kh_table* t, const char* kbase, uint32_t kstride, cons
     // that holds more raises the overflow flag like a slot that runs over
     const double mean1 = (double)n / (double)nb1;
     const uint64_t fill_cap = std::min<uint64_t>(slot1, (uint64_t)(mean1 + 9.0 * std::sqrt(mean1 * vf) + 16.0));
-    const uint32_t tps = (uint32_t)((fill_cap + KH_PART_TILE - 1) / KH_PART_TILE);
-    const uint32_t max_tiles = nb1 * tps;
+    const uint32_t tps = sub_slot ? tps_sub : (uint32_t)((fill_cap + KH_PART_TILE - 1) / KH_PART_TILE);
+    const uint32_t max_tiles = (sub_slot ? nb1 * 8u : nb1) * tps;
     if (shared) hipLaunchKernelGGL(k_init_cursors, dim3((nb1 + 255) / 256), dim3(256), 0, t->stream, cur1, (uint64_t*)nullptr, (uint64_t)nb1, slot1);
-    else hipLaunchKernelGGL(k_init_cursors2, dim3((nparts + 256) / 256), dim3(256), 0, t->stream, cur1, (uint64_t)nb1, slot1, cur2, starts, (uint64_t)nparts, slot, ovf);
+    else hipLaunchKernelGGL(k_init_cursors2, dim3((nparts + 256) / 256), dim3(256), 0, t->stream, cur1, (uint64_t)nb1, slot1, sub_slot ? 8u : 1u, cur2, starts, (uint64_t)nparts, slot, ovf);
     KhPartParams P;
     memset(&P, 0, sizeof(P));
     P.idx_base = idx_base;
@@ -637,13 +644,15 @@ kh_status partition_batch(kh_table* t, const char* kbase, uint32_t kstride, cons
     P.kbase = kbase; P.kstride = kstride; P.vbase = vbase; P.vstride = vstride; P.vconst = vconst; P.n = n;
     P.ntiles = (uint32_t)((n + KH_PART_TILE - 1) / KH_PART_TILE);
     P.seed = t->seed; P.PB = PB; P.shift = B2; P.nb = nb1; P.cursor = cur1; P.orec = tmp; P.slot = slot1; P.overflow = ovf; P.dump = slot1 * nb1;
+    P.sub_slot = sub_slot;
     { Launch L(t, "k_part_scatter");
       if (rec12 == 1) { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_part_scatter<HASH, 1>), dim3(P.ntiles), dim3(KH_PART_THREADS), ((nb1 + 1u) & ~1u) * 8 + nb1 * 8, t->stream, P)); }
       else if (rec12 == 2) { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_part_scatter<HASH, 2>), dim3(P.ntiles), dim3(KH_PART_THREADS), ((nb1 + 1u) & ~1u) * 8 + nb1 * 8, t->stream, P)); }
       else { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_part_scatter<HASH, 0>), dim3(P.ntiles), dim3(KH_PART_THREADS), ((nb1 + 1u) & ~1u) * 8 + nb1 * 8, t->stream, P)); } }
     KhPartParams Q = P;
     Q.kbase = nullptr; Q.kstride = 0; Q.vbase = nullptr; Q.vstride = 0; Q.rec_in = tmp;
-    Q.tiles = nullptr; Q.ntiles_dev = nullptr; Q.ntiles = max_tiles; Q.slot_in = slot1; Q.cur_in = cur1; Q.tps = tps;
+    Q.tiles = nullptr; Q.ntiles_dev = nullptr; Q.ntiles = max_tiles; Q.slot_in = sub_slot ? sub_slot : slot1; Q.cur_in = cur1; Q.tps = tps;
+    Q.sub_slot = 0; Q.seg_shift = sub_slot ? 3u : 0u; Q.xcd_buckets = sub_slot ? 1 : 0;
     Q.shift = 0; Q.nb = nb2; Q.cursor = cur2; Q.orec = fin; Q.slot = slot; Q.dump = slot * nparts;
     { Launch L(t, "k_part_scatter");
       if (rec12 == 1) { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_part_scatter<HASH, 1>), dim3(max_tiles), dim3(KH_PART_THREADS), ((nb2 + 1u) & ~1u) * 8 + nb2 * 8, t->stream, Q)); }
