@@ -36,7 +36,17 @@ typedef enum {
   KH_ERR_NOMEM = 2,          /* device allocation failed */
   KH_ERR_FULL = 3,           /* LP: no slot left -- mirrors std::logic_error, hashmap_linearprobe.hpp:408,503 */
   KH_ERR_PROBE_OVERFLOW = 4, /* RH probe distance would reach 128: the reference asserts (hashmap_robinhood.hpp:556)
-                                or silently corrupts under -DNDEBUG; we refuse and leave the table unchanged */
+                                or silently corrupts under -DNDEBUG; we refuse.  A call that re-lays the table out leaves it
+                                unchanged: size, capacity, info bytes, keys and values (reducer inserts are rolled back).
+                                A batch applied IN PLACE is applied key by key and keeps what was applied; the table stays a
+                                consistent Robin Hood table and *n_inserted counts the keys inserted.
+                                - a mid-size batch into a large table: every key is inserted whole or left out, and one is left
+                                  out only if its own insertion would push an element to distance 128; the rest of the batch IS
+                                  applied (also the reductions and updates of keys the table held).
+                                - <= 16 keys: applied in batch order up to the first key that does not fit.  The keys BEFORE it
+                                  stay applied (inserts, reductions, updates); that key and every key after it are refused
+                                  together and leave no trace, even those that would fit.
+                                kh_erase_one: see there.  (tests/test_gpu_refusals.py) */
   KH_ERR_HIP = 5,            /* a HIP runtime call failed (no GPU, launch failure, ...) */
   KH_ERR_UNSUPPORTED = 6,
   KH_ERR_RETRY = 7           /* kh_insert_end of a KH_INS_REPEATABLE streamed insert: its speculative partition did not hold for this
@@ -181,7 +191,9 @@ kh_status kh_find_compact_pairs(kh_table* t, const void* keys, uint64_t n, kh_me
 
 /* ---- erase(Iter,Iter)  hashmap_robinhood.hpp:1430-1440 (never shrinks) / hashmap_linearprobe.hpp:1042-1051 (may shrink) */
 kh_status kh_erase(kh_table* t, const void* keys, uint64_t n, kh_mem where, uint64_t* n_erased);
-/* erase(key) single-key form: also halves the table when size < min_load (:1421-1428 / :1032-1039) */
+/* erase(key) single-key form: also halves the table when size < min_load (:1421-1428 / :1032-1039).  The erase comes first: if
+   the halved Robin Hood table cannot be laid out (home buckets merge past distance 127) the call returns KH_ERR_PROBE_OVERFLOW
+   with the key ERASED (*n_erased = 1) and the capacity as it was; the table is consistent and usable. */
 kh_status kh_erase_one(kh_table* t, uint64_t key, uint64_t* n_erased);
 
 /* ---- iteration / parity exports (host buffers) */

@@ -15,6 +15,7 @@ torch = pytest.importorskip("torch")
 
 import kmerhash_amd as kh  # noqa: E402
 from kmerhash_amd import workloads as W  # noqa: E402
+from refusal_checks import assert_unchanged, snapshot  # noqa: E402
 
 KINDS = [("rh", kh.hashmap_robinhood_doubling, 0), ("lp", kh.hashmap_linearprobe_doubling, 1)]
 HASHES = [("murmur3avx64", 1), ("murmur", 2), ("farm", 3), ("identity", 0)]
@@ -208,10 +209,17 @@ def test_probe_overflow_is_refused(oracle):
     good = W.distinct_u64(1000, seed=8)
     g.insert(good, np.arange(1000, dtype=np.uint32))
     bad = (np.arange(200_000, dtype=np.uint64) % np.uint64(1500)) * np.uint64(1 << 20) + np.uint64(77)
+    snap = snapshot(g)
+    g.profile_enable(True)
     with pytest.raises(kh.KhError) as ei:
         g.insert(bad, np.zeros(len(bad), dtype=np.uint32))
     assert "KH_ERR_PROBE_OVERFLOW" in str(ei.value)
     assert g.size() == 1000 and g.count(good).all()
+    # 200 000 records over 1 500 keys of one home bucket into 1 000 held keys at 2^20: too many for the in-place path, the capacity
+    # stays, so the one-launch insert raises the flag first and the same-capacity re-layout of the general path refuses
+    p = g.profile()
+    assert "k_insert_fused" in p and "k_dedup" in p and ("k_rebuild_fused" in p or "k_chunk_place" in p), p
+    assert_unchanged(g, snap, np.unique(bad))
     g.close()
 
 
