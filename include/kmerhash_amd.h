@@ -577,6 +577,66 @@ kh_status kh_index_build_from_minimizers(kh_index* x, const void* text /*[h|d] u
 kh_status kh_index_append_from_minimizers(kh_index* x, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, uint32_t w /*1..256*/, int canonical,
                                           kh_hash order_hash, uint64_t order_seed, kh_mem where, int fastq, uint32_t pos_base);
 
+/* ---- closed-syncmer sampling (Edgar 2021): a sampler whose choice is a function of the k-mer ALONE, for both key widths (k = 1..32 in
+ *      8-byte k-mers, k = 1..64 in 16-byte k-mers {w0, w1}).  The reference tree has no sampler: the definition below is this library's.
+ *      Inputs: a text, k, s with 1 <= s <= min(k, 32), `canonical`, an ordering hash `order_hash` and `order_seed`.
+ *      - Valid windows, packing, canonical form, offsets and FASTQ masking are exactly those of kh_kmers_from_sequence_pos
+ *        (kh_kmers128_from_sequence_pos for the 128 forms).
+ *      - Order key of offset i: h(i) = the hash `order_hash` with seed `order_seed` of the s-mer that starts at i, packed as a k-mer of
+ *        length s is (64 bits: s <= 32 for either key width), of its canonical form when `canonical` is set: the value kh_hash_batch
+ *        gives for it.
+ *      - Selection: let m be the smallest order key among the k - s + 1 offsets p .. p + k - s.  The k-mer of the valid window p is KEPT
+ *        iff h(p) == m or h(p + k - s) == m: its smallest s-mer is its first or its last.  A tie with an inner s-mer still keeps it.
+ *        With canonical s-mers the reverse complement of a k-mer sees the same keys in the opposite order, and the inclusive tie rule
+ *        makes the choice exactly strand-symmetric: a text and its reverse complement keep the same canonical k-mers at mirrored places.
+ *      - Output: the kept windows in ascending offset, each once; (k-mer, position) is what the all-window front end emits for it.
+ *      s == k keeps every window: the output of kh_kmers_from_sequence_pos (kh_kmers128_...), byte for byte.  About 2 / (k - s + 1) of
+ *      the k-mers of a random text are kept (not for very small s, where few distinct keys tie constantly).  Selection does not depend
+ *      on the neighbours: a run of k bases yields its k-mer if that k-mer is a syncmer, and kh_syncmer_mask answers for any k-mer, with
+ *      no text, whether a sampled index CAN hold it.  REPEATS: in a homopolymer every key ties and every window is kept, as with
+ *      minimizers -- mask such k-mers afterwards (kh_index_erase_counts).  Choose an ordering hash or seed other than the table's.
+ *      out_kmers == NULL: count only -- *n_out is set, nothing is written.  Otherwise cap_out is the room offered in out_kmers
+ *      (u64[cap_out], u64[2 cap_out] for the 128 forms) and out_pos (both required); more kept windows than cap_out: KH_ERR_INVALID with
+ *      *n_out set and the outputs untouched.  KH_ERR_INVALID before anything is allocated or read: s == 0, s > k, s > 32, k outside
+ *      1..32 (1..64), n >= 2^32, an unknown hash, NULL text with n > 0, NULL n_out.  n == 0 or a text shorter than k: KH_OK and
+ *      *n_out = 0.  Two passes over the text, 1 B per base read each, 12 B (20 B) per KEPT pair written; no hash array in device memory. */
+kh_status kh_syncmers_from_sequence(const void* seq /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, uint32_t s /*1..k*/, int canonical,
+                                    kh_hash order_hash, uint64_t order_seed, kh_mem where,
+                                    uint64_t* out_kmers /*[h|d] or NULL*/, uint32_t* out_pos /*[h|d] or NULL*/, uint64_t cap_out,
+                                    uint64_t* n_out, int device, void* hip_stream);
+kh_status kh_syncmers_from_fastq(const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, uint32_t s /*1..k*/, int canonical,
+                                 kh_hash order_hash, uint64_t order_seed, kh_mem where,
+                                 uint64_t* out_kmers /*[h|d] or NULL*/, uint32_t* out_pos /*[h|d] or NULL*/, uint64_t cap_out,
+                                 uint64_t* n_out, int device, void* hip_stream);
+kh_status kh_syncmers128_from_sequence(const void* seq /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, uint32_t s /*1..min(k,32)*/, int canonical,
+                                       kh_hash order_hash, uint64_t order_seed, kh_mem where,
+                                       uint64_t* out_kmers /*[h|d] u64[2 cap_out] or NULL*/, uint32_t* out_pos /*[h|d] or NULL*/, uint64_t cap_out,
+                                       uint64_t* n_out, int device, void* hip_stream);
+kh_status kh_syncmers128_from_fastq(const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, uint32_t s /*1..min(k,32)*/, int canonical,
+                                    kh_hash order_hash, uint64_t order_seed, kh_mem where,
+                                    uint64_t* out_kmers /*[h|d] u64[2 cap_out] or NULL*/, uint32_t* out_pos /*[h|d] or NULL*/, uint64_t cap_out,
+                                    uint64_t* n_out, int device, void* hip_stream);
+/* the selection alone, on a batch of packed k-mers (as the front ends and the tables hold them; bits above 2k are ignored):
+ *      out_mask[i] = 1 iff key i is a closed syncmer under (k, s, canonical, order_hash, order_seed), else 0; out_mask lives where the keys
+ *      live.  With `canonical` a k-mer and its reverse complement give the same answer.  Refusals as above (no n_out); n == 0: KH_OK;
+ *      NULL out_mask with n > 0: KH_ERR_INVALID.  Synchronous. */
+kh_status kh_syncmer_mask(const void* keys /*[h|d] u64[n]*/, uint64_t n, uint32_t k /*1..32*/, uint32_t s /*1..k*/, int canonical,
+                          kh_hash order_hash, uint64_t order_seed, kh_mem where, uint8_t* out_mask /*[h|d] u8[n]*/, int device, void* hip_stream);
+kh_status kh_wide_syncmer_mask(const void* keys /*[h|d] u64[2n]*/, uint64_t n, uint32_t k /*1..64*/, uint32_t s /*1..min(k,32)*/, int canonical,
+                               kh_hash order_hash, uint64_t order_seed, kh_mem where, uint8_t* out_mask /*[h|d] u8[n]*/, int device, void* hip_stream);
+/* a position index over the closed syncmers of a text (fastq != 0: raw FASTQ text), either key width: the route of
+ *      kh_index_build_from_minimizers -- count pass, pair buffers of exactly that size (12 B or 20 B per kept pair), emit pass with
+ *      pos_base added on the device, then kh_index_build / kh_index_append of the pairs, to which the export is byte-identical.
+ *      Failure states and refusals are those of kh_index_append_from_sequence, plus s out of range and an unknown order hash. */
+kh_status kh_index_build_from_syncmers(kh_index* x, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, uint32_t s /*1..k*/, int canonical,
+                                       kh_hash order_hash, uint64_t order_seed, kh_mem where, int fastq);
+kh_status kh_index_append_from_syncmers(kh_index* x, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, uint32_t s /*1..k*/, int canonical,
+                                        kh_hash order_hash, uint64_t order_seed, kh_mem where, int fastq, uint32_t pos_base);
+kh_status kh_wide_index_build_from_syncmers(kh_windex* x, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, uint32_t s /*1..min(k,32)*/,
+                                            int canonical, kh_hash order_hash, uint64_t order_seed, kh_mem where, int fastq);
+kh_status kh_wide_index_append_from_syncmers(kh_windex* x, const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, uint32_t s /*1..min(k,32)*/,
+                                             int canonical, kh_hash order_hash, uint64_t order_seed, kh_mem where, int fastq, uint32_t pos_base);
+
 /* a CSR that arrives in a permuted order, back into query order (the last step of a sharded find: the answers return grouped by owner
  *      rank, in the permuted order of kh_shard_permute with vals = 0..n-1).
  * counts_perm[j] and the segments of pos_perm (concatenated in order j = 0..n-1) belong to the query whose index in the caller's

@@ -76,6 +76,10 @@ SYMBOLS = [
     "kh_minimizers_from_sequence", "kh_minimizers_from_fastq", "kh_index_build_from_minimizers", "kh_index_append_from_minimizers",
     # a permuted CSR back into query order (the last step of a sharded index find)
     "kh_csr_unpermute",
+    # closed-syncmer sampling (both key widths), the context-free keep test and the position index over the kept k-mers
+    "kh_syncmers_from_sequence", "kh_syncmers_from_fastq", "kh_syncmers128_from_sequence", "kh_syncmers128_from_fastq",
+    "kh_syncmer_mask", "kh_wide_syncmer_mask", "kh_index_build_from_syncmers", "kh_index_append_from_syncmers",
+    "kh_wide_index_build_from_syncmers", "kh_wide_index_append_from_syncmers",
 ]
 
 _lib = None
@@ -242,6 +246,13 @@ def lib():
     L.kh_index_build_from_minimizers.argtypes = [vp, vp, u64, u32, u32, i32, i32, u64, i32, i32]
     L.kh_index_append_from_minimizers.argtypes = [vp, vp, u64, u32, u32, i32, i32, u64, i32, i32, u32]
     L.kh_csr_unpermute.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, pu64, i32, vp]
+    for s in ("kh_syncmers_from_sequence", "kh_syncmers_from_fastq", "kh_syncmers128_from_sequence", "kh_syncmers128_from_fastq"):
+        getattr(L, s).argtypes = [vp, u64, u32, u32, i32, i32, u64, i32, vp, vp, u64, pu64, i32, vp]
+    L.kh_syncmer_mask.argtypes = [vp, u64, u32, u32, i32, i32, u64, i32, vp, i32, vp]
+    L.kh_wide_syncmer_mask.argtypes = [vp, u64, u32, u32, i32, i32, u64, i32, vp, i32, vp]
+    for pre in ("kh_index_", "kh_wide_index_"):
+        getattr(L, pre + "build_from_syncmers").argtypes = [vp, vp, u64, u32, u32, i32, i32, u64, i32, i32]
+        getattr(L, pre + "append_from_syncmers").argtypes = [vp, vp, u64, u32, u32, i32, i32, u64, i32, i32, u32]
     for s in SYMBOLS:
         if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error", "kh_wide_index_last_error"):
             getattr(L, s).restype = i32

@@ -215,6 +215,183 @@ __global__ __launch_bounds__(KH_KM_THREADS, 3) void k_minimizers_emit(const uint
 }
 
 // ---------------------------------------------------------------------------------------------
+// closed-syncmer sampling (kh_syncmers[128]_from_sequence / _fastq, kh_[wide_]syncmer_mask; the definition is in include/kmerhash_amd.h):
+// the k-mer at a valid window p is kept iff the smallest order key among its k - s + 1 s-mers (offsets p .. p + k - s) is the key of
+// its first or of its last s-mer.  The tile scheme of the minimizer kernels with a halo on the RIGHT only: a tile decides its
+// KH_KM_TILE start offsets and hashes the k - s <= 63 offsets behind them as well (HW = ceil((k - s) / 16) <= 4 words of 16).
+//   1. pack: kh_km_pack_tile for the tile, the HW halo words and what the widest window cut needs behind them (KhKm<2>::HALO words for
+//      the k-mer of the tile's last lane, KhKm<1>::HALO words for the s-mer of the last hashed offset: KM_SY_HALO_WORDS + 2 in all).
+//   2. hash once per offset: the order key kh_hash64<HASH>(s-mer, seed) -- a KhKm<1> window of length s, its canonical form when CANON --
+//      into LDS (rows of 16 keys padded by one, as the minimizer keys are) and arg[i] = i, or KM_MZ_NONE when the s bytes are not all bases.
+//   3. range minimum by J = floor(log2(k - s + 1)) doubling steps on arg, keys untouched; the minimum over [p, p + k - s] is the smaller
+//      of arg[p] and arg[p + k - s + 1 - 2^J] (two overlapping ranges).  A KM_MZ_NONE anywhere in the range gives KM_MZ_NONE, and that is
+//      exactly "the k bytes from p are not all bases": no separate test of the k-mer's validity.
+//   4. keep test: key[arg] == key[p] || key[arg] == key[p + k - s] (a tie with an inner s-mer keeps the k-mer, which makes the rule
+//      exactly strand-symmetric).  A wave decides 64 consecutive offsets per round, so its ballot IS two words of the 4096-bit mask:
+//      no LDS atomic.
+// LDS: 35360 (keys: 4160 offsets, 17 per 16) + 8320 (arg) + 1048 + 524 (packed text, 262 words) + 512 (marks) + 16 = 45780 B (45784
+// padded): three workgroups per CU, three waves per SIMD, which the launch bounds also hold the registers to (a fourth workgroup would
+// need <= 40960 B; keys and arg alone are 43680).
+// The count kernel sums the marks; it never looks at a k-mer, so it has no key-width parameter and serves both widths.  The emit kernel
+// for 8-byte k-mers stages the kept k-mers over the dead keys and their tile-local offsets over arg and writes both coalesced; for
+// 16-byte k-mers a full tile (poly-A keeps all 4096 windows) would be 64 KB, so they go straight out as kw_kmers_emit_pos writes them.
+// No hash and no flag reaches HBM: 1 B per base read per pass, 12 B (8-byte k-mers) or 20 B (16-byte) per kept pair written.
+// ---------------------------------------------------------------------------------------------
+#define KM_SY_HALO_WORDS 4                                                   // ceil(63 / 16)
+#define KM_SY_WORDS (KH_KM_TILE / 16 + KM_SY_HALO_WORDS)                     // 260 words of hashed offsets at most
+#define KM_SY_OFFS (16 * KM_SY_WORDS)                                        // 4160
+#define KM_SY_PER ((KM_SY_OFFS + KH_KM_THREADS - 1) / KH_KM_THREADS)         // 17
+#define KM_SY_TEXT_HALO (KM_SY_HALO_WORDS + KhKm<1>::HALO)                   // 6 >= KhKm<2>::HALO
+struct KmSyLds {
+  uint64_t hk[KM_SY_OFFS + KM_SY_WORDS];            // order keys of the s-mers, 17 per word of 16 offsets; the emit stage afterwards (KW = 1)
+  uint16_t arg[KM_SY_OFFS];                         // offset of the range minimum / KM_MZ_NONE; the staged offsets afterwards (KW = 1)
+  uint32_t words[KH_KM_TILE / 16 + KM_SY_TEXT_HALO];
+  uint16_t invs[KH_KM_TILE / 16 + KM_SY_TEXT_HALO];
+  uint32_t marks[KH_KM_TILE / 32];
+  uint32_t wtot[KH_KM_THREADS / 64];
+};
+// leaves S.marks complete (bit q: the k-mer of the window at tile0 + q is a closed syncmer) and the workgroup synchronised
+template <int HASH, bool CANON>
+__device__ __forceinline__ void km_sy_marks(const uint8_t* __restrict__ seq, uint64_t n, uint64_t tile0, uint32_t k, uint32_t s, uint64_t seed, KmSyLds& S) {
+  typedef KhKm<1> M;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const uint32_t span = k - s;                                       // 0..63: the last s-mer of the window at p starts at p + span
+  const uint32_t nw = KH_KM_TILE / 16 + ((span + 15u) >> 4), ne = 16 * nw;
+  kh_km_pack_tile<KM_SY_TEXT_HALO>(seq, n, tile0, S.words, S.invs);
+  __syncthreads();
+  for (uint32_t e = tid; e < nw; e += KH_KM_THREADS) {
+    const M::Win W = M::window(S.words, S.invs, e);
+#pragma unroll 4
+    for (uint32_t j = 0; j < 16; ++j) {
+      const uint32_t i = 16 * e + j;
+      S.hk[KM_MZ_HK(i)] = M::template hash_of_window<HASH, CANON>(W, j, s, seed);
+      S.arg[i] = M::valid(W, j, s) ? (uint16_t)i : (uint16_t)KM_MZ_NONE;
+    }
+  }
+  __syncthreads();
+  const uint32_t J = 31u - (uint32_t)__clz(span + 1u);
+  for (uint32_t d = 0; d < J; ++d) {
+    const uint32_t step = 1u << d;
+    uint32_t res[KM_SY_PER];
+#pragma unroll
+    for (uint32_t r = 0; r < KM_SY_PER; ++r) {
+      const uint32_t i = tid + r * KH_KM_THREADS;
+      uint32_t a = KM_MZ_NONE;
+      if (i + step < ne) {
+        a = S.arg[i];
+        const uint32_t b = S.arg[i + step];
+        if (b == KM_MZ_NONE) a = KM_MZ_NONE;
+        else if (a != KM_MZ_NONE && S.hk[KM_MZ_HK(b)] < S.hk[KM_MZ_HK(a)]) a = b;
+      }
+      res[r] = a;
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < KM_SY_PER; ++r) {
+      const uint32_t i = tid + r * KH_KM_THREADS;
+      if (i < ne) S.arg[i] = (uint16_t)res[r];
+    }
+    __syncthreads();
+  }
+  const uint32_t back = span + 1u - (1u << J);
+#pragma unroll
+  for (uint32_t r = 0; r < KH_KM_TILE / KH_KM_THREADS; ++r) {
+    const uint32_t p = tid + r * KH_KM_THREADS;                      // (p + span < ne: every read below lies inside the hashed offsets)
+    const uint32_t a = S.arg[p], b = S.arg[p + back];
+    bool keep = false;
+    if (a != KM_MZ_NONE && b != KM_MZ_NONE) {
+      const uint64_t ha = S.hk[KM_MZ_HK(a)], hb = S.hk[KM_MZ_HK(b)];
+      const uint64_t m = hb < ha ? hb : ha;
+      keep = S.hk[KM_MZ_HK(p)] == m || S.hk[KM_MZ_HK(p + span)] == m;
+    }
+    const unsigned long long bal = __ballot(keep);                   // lanes 0..63 <-> offsets r * 256 + 64 wid + lane
+    if (lane == 0) { S.marks[8 * r + 2 * wid] = (uint32_t)bal; S.marks[8 * r + 2 * wid + 1] = (uint32_t)(bal >> 32); }
+  }
+  __syncthreads();
+}
+template <int HASH, bool CANON>
+__global__ __launch_bounds__(KH_KM_THREADS, 3) void k_syncmers_count(const uint8_t* __restrict__ seq, uint64_t n, uint32_t k, uint32_t s, uint64_t seed,
+                                                                  uint32_t* __restrict__ sums) {
+  __shared__ KmSyLds S;
+  km_sy_marks<HASH, CANON>(seq, n, (uint64_t)blockIdx.x * KH_KM_TILE, k, s, seed, S);
+  uint32_t c = threadIdx.x < KH_KM_TILE / 32 ? (uint32_t)__popc(S.marks[threadIdx.x]) : 0u;
+  c = kh_wave_sum(c);
+  if ((threadIdx.x & 63) == 0) S.wtot[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) sums[blockIdx.x] = S.wtot[0] + S.wtot[1] + S.wtot[2] + S.wtot[3];
+}
+// out: u64[KW] per kept window ({w0, w1} for KW = 2); out_pos[i] = pos_base + the window's byte offset
+template <int HASH, bool CANON, int KW>
+__global__ __launch_bounds__(KH_KM_THREADS, 3) void k_syncmers_emit(const uint8_t* __restrict__ seq, uint64_t n, uint32_t k, uint32_t s, uint64_t seed,
+                                                                 const uint64_t* __restrict__ tile_off, uint64_t* __restrict__ out, uint32_t* __restrict__ out_pos,
+                                                                 uint32_t pos_base) {
+  typedef KhKm<KW> M;
+  __shared__ KmSyLds S;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const uint64_t tile0 = (uint64_t)blockIdx.x * KH_KM_TILE;
+  km_sy_marks<HASH, CANON>(seq, n, tile0, k, s, seed, S);
+  const uint32_t pmask = (S.marks[tid >> 1] >> (16u * (tid & 1u))) & 0xFFFFu;      // the 16 windows of the lane's word
+  const uint32_t mine = (uint32_t)__popc(pmask);
+  uint32_t incl = mine;
+  for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off, 64); if (lane >= (uint32_t)off) incl += o; }
+  if (lane == 63) S.wtot[wid] = incl;
+  __syncthreads();
+  uint32_t pos = incl - mine, total = 0;
+#pragma unroll
+  for (uint32_t x = 0; x < KH_KM_THREADS / 64; ++x) { const uint32_t c = S.wtot[x]; if (x < wid) pos += c; total += c; }
+  const typename M::Win W = M::window(S.words, S.invs, tid);
+  const uint64_t o = tile_off[blockIdx.x];
+  if constexpr (KW == 2) {
+    for (uint32_t j = 0; j < 16; ++j) {
+      if ((pmask >> j) & 1u) {
+        uint64_t w0, w1;
+        M::forward(W, j, k, &w0, &w1);
+        if (CANON) kh_xf128(&w0, &w1, k);
+        reinterpret_cast<ulonglong2*>(out)[o + pos] = make_ulonglong2(w0, w1);
+        out_pos[o + pos] = pos_base + (uint32_t)(tile0 + 16u * tid + j);
+        ++pos;
+      }
+    }
+  } else {
+    uint64_t* stage = S.hk;                                          // (every read of the keys lies before the barrier km_sy_marks ends with)
+    uint16_t* spos = S.arg;
+#pragma unroll
+    for (uint32_t j = 0; j < 16; ++j) {
+      if ((pmask >> j) & 1u) {
+        const uint64_t fw = M::forward(W, j, k);
+        stage[pos] = CANON ? kh_xf(fw, k) : fw;
+        spos[pos] = (uint16_t)(16u * tid + j);
+        ++pos;
+      }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < total; i += KH_KM_THREADS) { out[o + i] = stage[i]; out_pos[o + i] = pos_base + (uint32_t)(tile0 + spos[i]); }
+  }
+}
+// the same test on a batch of packed k-mers (8-byte: keys u64[n]; 16-byte: keys u64[2n], {w0, w1}): out[i] = 1 iff key i is a closed
+// syncmer.  One lane per key, the k - s + 1 s-mers cut from the key's registers (s <= 32: an s-mer is one word), no LDS.  Bits above
+// the k-mer's 2k are ignored.  With CANON a key and its reverse complement see the same canonical s-mers in opposite order, and the
+// rule is symmetric in first and last: the same answer, whichever strand's bit pattern the caller holds.
+template <int HASH, bool CANON, int KW>
+__global__ __launch_bounds__(256) void k_syncmer_mask(const uint64_t* __restrict__ keys, uint64_t n, uint32_t k, uint32_t s, uint64_t seed, uint8_t* __restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  const uint64_t smask = s >= 32 ? ~0ull : ((1ull << (2 * s)) - 1ull);
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const uint64_t w0 = keys[KW * i], w1 = KW == 2 ? keys[KW * i + 1] : 0ull;
+    uint64_t first = 0, last = 0, m = ~0ull;
+    for (uint32_t sh = 2 * (k - s), j = 0; j <= k - s; ++j, sh -= 2) {            // s-mer j: bases j .. j + s - 1, sh = 2 (k - s - j)
+      uint64_t x = sh >= 64 ? (w1 >> (sh - 64)) : sh ? ((w0 >> sh) | (w1 << (64 - sh))) : w0;
+      x &= smask;
+      const uint64_t h = kh_hash64<HASH>(CANON ? kh_xf(x, s) : x, seed);
+      if (j == 0) first = h;
+      last = h;
+      m = h < m ? h : m;
+    }
+    out[i] = (first == m || last == m) ? 1 : 0;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // canonical slot order.  A Robin Hood table keeps its elements sorted by home bucket, but the order of the keys that SHARE a home bucket
 // is whatever the insert made of it (in the reference: arrival order; in the counting insert here: the order LDS atomics gave, which
 // differs from run to run).  The index promises a result that depends on the multiset of pairs only, so every run of slots with one

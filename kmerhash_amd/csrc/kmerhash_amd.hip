@@ -2412,6 +2412,7 @@ struct MzWork {
   uint64_t* offs = nullptr;
   uint64_t n = 0, nkt = 0;
   uint32_t k = 0, w = 0;
+  uint32_t s = 0, kw = 1;      // s != 0 (set by the caller before mz_count): closed syncmers of kw-word k-mers instead, w unused
   int canonical = 0, hash = 0;
   uint64_t seed = 0;
 };
@@ -2442,7 +2443,10 @@ kh_status mz_count(kh_table* prof, MzWork& M, const void* seq, uint64_t n, uint3
   if (where == KH_MEM_HOST) e = hipMemcpyAsync(const_cast<uint8_t*>(M.dseq), seq, n, hipMemcpyHostToDevice, stream);
   if (e == hipSuccess) {
     if (fastq) { fastq_mask_text(M.dseq, n, M.sums, M.offs, msk, stream); M.dseq = msk; }
-    { Launch L(prof, "k_minimizers_count");
+    if (M.s) { Launch L(prof, "k_syncmers_count");
+      if (canonical) { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_syncmers_count<HASH, true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, n, k, M.s, seed, M.sums)); }
+      else { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_syncmers_count<HASH, false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, n, k, M.s, seed, M.sums)); } }
+    else { Launch L(prof, "k_minimizers_count");
       if (canonical) { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_minimizers_count<HASH, true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, n, k, w, seed, M.sums)); }
       else { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_minimizers_count<HASH, false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, n, k, w, seed, M.sums)); } }
     hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, M.sums, nkt, M.offs);
@@ -2456,7 +2460,15 @@ kh_status mz_count(kh_table* prof, MzWork& M, const void* seq, uint64_t n, uint3
 // queues the emit pass (dout u64[total], dpos u32[total], device memory); the caller synchronises
 kh_status mz_emit(kh_table* prof, const MzWork& M, hipStream_t stream, uint64_t* dout, uint32_t* dpos, uint32_t pos_base) {
   kh_table* t = prof;
-  { Launch L(prof, "k_minimizers_emit");
+  if (M.s) { Launch L(prof, "k_syncmers_emit");
+#define KH_SY_EMIT(CANON, KW) KH_SWITCH_HASH(M.hash, hipLaunchKernelGGL((k_syncmers_emit<HASH, CANON, KW>), dim3((uint32_t)M.nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, M.n, M.k, M.s, \
+                                                                  M.seed, (const uint64_t*)M.offs, dout, dpos, pos_base))
+    if (M.kw == 2) { if (M.canonical) { KH_SY_EMIT(true, 2); } else { KH_SY_EMIT(false, 2); } }
+    else if (M.canonical) { KH_SY_EMIT(true, 1); }
+    else { KH_SY_EMIT(false, 1); }
+#undef KH_SY_EMIT
+  }
+  else { Launch L(prof, "k_minimizers_emit");
     if (M.canonical) { KH_SWITCH_HASH(M.hash, hipLaunchKernelGGL((k_minimizers_emit<HASH, true>), dim3((uint32_t)M.nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, M.n, M.k, M.w, M.seed,
                                                                  (const uint64_t*)M.offs, dout, dpos, pos_base)); }
     else { KH_SWITCH_HASH(M.hash, hipLaunchKernelGGL((k_minimizers_emit<HASH, false>), dim3((uint32_t)M.nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, M.n, M.k, M.w, M.seed,
@@ -2500,8 +2512,106 @@ kh_status minimizers_impl(const void* seq, uint64_t n, uint32_t k, uint32_t w, i
   if (e != hipSuccess || es != hipSuccess) return KH_ERR_HIP;
   return st;
 }
+// refusals of the syncmer calls that need no device: s, k for the key width, n, the hash and a null text
+bool sy_args_ok(uint32_t kw, const void* seq, uint64_t n, uint32_t k, uint32_t s, int hash) {
+  return s >= 1 && s <= k && s <= 32 && k <= 32 * kw && !(n >> 32) && hash >= 0 && hash <= 3 && (seq || n == 0);
+}
+// closed syncmers of a text: minimizers_impl with the syncmer kernels; kw: 64-bit words per emitted k-mer
+kh_status syncmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, uint32_t s, int canonical, int hash, uint64_t seed, kh_mem where, bool fastq,
+                        uint64_t* out_kmers, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, void* stream_) {
+  kh_table* t = nullptr;
+  if (n_out) *n_out = 0;
+  if (!n_out || !sy_args_ok(kw, seq, n, k, s, hash) || (out_kmers && !out_pos)) return KH_ERR_INVALID;
+  if (n < k) return KH_OK;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK(hipSetDevice(device));
+  MzWork M;
+  M.s = s; M.kw = kw;
+  uint64_t total = 0;
+  kh_status st = mz_count(nullptr, M, seq, n, k, 0u, canonical, hash, seed, where, fastq, device, stream, &total);
+  if (st != KH_OK) return st;
+  *n_out = total;
+  if (!out_kmers || total == 0) { mz_free(M); return KH_OK; }
+  if (total > cap_out) { mz_free(M); return KH_ERR_INVALID; }       // (the total is known before anything is written)
+  uint64_t* dout = out_kmers; uint32_t* dpos = out_pos;
+  char* stage = nullptr;
+  hipError_t e = hipSuccess;
+  if (where == KH_MEM_HOST) {
+    e = pool_alloc(device, total * (8 * kw + 4), reinterpret_cast<void**>(&stage));
+    dout = reinterpret_cast<uint64_t*>(stage); dpos = reinterpret_cast<uint32_t*>(stage + total * 8 * kw);
+  }
+  if (e == hipSuccess) {
+    st = mz_emit(nullptr, M, stream, dout, dpos, 0u);
+    if (st == KH_OK && where == KH_MEM_HOST) {
+      e = hipMemcpyAsync(out_kmers, dout, total * 8 * kw, hipMemcpyDeviceToHost, stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(out_pos, dpos, total * 4, hipMemcpyDeviceToHost, stream);
+    }
+  }
+  const hipError_t es = hipStreamSynchronize(stream);
+  pool_free(device, stage);
+  mz_free(M);
+  if (e == hipErrorOutOfMemory) return KH_ERR_NOMEM;
+  if (e != hipSuccess || es != hipSuccess) return KH_ERR_HIP;
+  return st;
+}
+// the keep test on a batch of packed k-mers: out_mask u8[n] in the memory the keys live in
+kh_status syncmer_mask_impl(uint32_t kw, const void* keys, uint64_t n, uint32_t k, uint32_t s, int canonical, int hash, uint64_t seed, kh_mem where, uint8_t* out_mask,
+                            int device, void* stream_) {
+  kh_table* t = nullptr;
+  if (!sy_args_ok(kw, keys, n, k, s, hash)) return KH_ERR_INVALID;
+  if (n == 0) return KH_OK;
+  if (!out_mask) return KH_ERR_INVALID;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK(hipSetDevice(device));
+  const uint64_t* dk = static_cast<const uint64_t*>(keys);
+  uint8_t* dm = out_mask;
+  char* blk = nullptr;
+  hipError_t e = hipSuccess;
+  if (where == KH_MEM_HOST) {
+    HIPCHK(pool_alloc(device, n * 8 * kw + n, reinterpret_cast<void**>(&blk)));
+    e = hipMemcpyAsync(blk, keys, n * 8 * kw, hipMemcpyHostToDevice, stream);
+    dk = reinterpret_cast<const uint64_t*>(blk); dm = reinterpret_cast<uint8_t*>(blk + n * 8 * kw);
+  }
+  if (e == hipSuccess) {
+    const uint32_t grid = grid_for(n, 256);
+#define KH_SY_MASK(CANON, KW) KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_syncmer_mask<HASH, CANON, KW>), dim3(grid), dim3(256), 0, stream, dk, n, k, s, seed, dm))
+    if (kw == 2) { if (canonical) { KH_SY_MASK(true, 2); } else { KH_SY_MASK(false, 2); } }
+    else if (canonical) { KH_SY_MASK(true, 1); }
+    else { KH_SY_MASK(false, 1); }
+#undef KH_SY_MASK
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && where == KH_MEM_HOST) e = hipMemcpyAsync(out_mask, dm, n, hipMemcpyDeviceToHost, stream);
+  const hipError_t es = hipStreamSynchronize(stream);
+  pool_free(device, blk);
+  return e == hipSuccess && es == hipSuccess ? KH_OK : KH_ERR_HIP;
+}
 }  // namespace
 extern "C" {
+kh_status kh_syncmers_from_sequence(const void* seq, uint64_t n, uint32_t k, uint32_t s, int canonical, kh_hash order_hash, uint64_t order_seed, kh_mem where,
+                                    uint64_t* out_kmers, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, void* stream_) {
+  return syncmers_impl(1, seq, n, k, s, canonical, (int)order_hash, order_seed, where, false, out_kmers, out_pos, cap_out, n_out, device, stream_);
+}
+kh_status kh_syncmers_from_fastq(const void* text, uint64_t n, uint32_t k, uint32_t s, int canonical, kh_hash order_hash, uint64_t order_seed, kh_mem where,
+                                 uint64_t* out_kmers, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, void* stream_) {
+  return syncmers_impl(1, text, n, k, s, canonical, (int)order_hash, order_seed, where, true, out_kmers, out_pos, cap_out, n_out, device, stream_);
+}
+kh_status kh_syncmers128_from_sequence(const void* seq, uint64_t n, uint32_t k, uint32_t s, int canonical, kh_hash order_hash, uint64_t order_seed, kh_mem where,
+                                       uint64_t* out_kmers, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, void* stream_) {
+  return syncmers_impl(2, seq, n, k, s, canonical, (int)order_hash, order_seed, where, false, out_kmers, out_pos, cap_out, n_out, device, stream_);
+}
+kh_status kh_syncmers128_from_fastq(const void* text, uint64_t n, uint32_t k, uint32_t s, int canonical, kh_hash order_hash, uint64_t order_seed, kh_mem where,
+                                    uint64_t* out_kmers, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, void* stream_) {
+  return syncmers_impl(2, text, n, k, s, canonical, (int)order_hash, order_seed, where, true, out_kmers, out_pos, cap_out, n_out, device, stream_);
+}
+kh_status kh_syncmer_mask(const void* keys, uint64_t n, uint32_t k, uint32_t s, int canonical, kh_hash order_hash, uint64_t order_seed, kh_mem where, uint8_t* out_mask,
+                          int device, void* stream_) {
+  return syncmer_mask_impl(1, keys, n, k, s, canonical, (int)order_hash, order_seed, where, out_mask, device, stream_);
+}
+kh_status kh_wide_syncmer_mask(const void* keys, uint64_t n, uint32_t k, uint32_t s, int canonical, kh_hash order_hash, uint64_t order_seed, kh_mem where, uint8_t* out_mask,
+                               int device, void* stream_) {
+  return syncmer_mask_impl(2, keys, n, k, s, canonical, (int)order_hash, order_seed, where, out_mask, device, stream_);
+}
 kh_status kh_minimizers_from_sequence(const void* seq, uint64_t n, uint32_t k, uint32_t w, int canonical, kh_hash order_hash, uint64_t order_seed, kh_mem where,
                                       uint64_t* out_kmers, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, void* stream_) {
   return minimizers_impl(seq, n, k, w, canonical, (int)order_hash, order_seed, where, false, out_kmers, out_pos, cap_out, n_out, device, stream_);
@@ -3500,32 +3610,35 @@ kh_status index_text(kh_index* x, const void* text, uint64_t n, uint32_t k, int 
   return touched ? index_abandon(x, st) : xfail(x, st, t->err);
 }
 // index_text over the (w,k)-minimizers of the text instead of all its windows: count pass, pair buffers of exactly that many entries
-// (12 B per emitted pair, not per base), emit pass with pos_base added as it writes, then the build / append of the pairs
+// (12 B per emitted pair, not per base), emit pass with pos_base added as it writes, then the build / append of the pairs.
+// syncmers: the same route over the closed syncmers of either key width, `w` carrying s (index_syncmers below)
 kh_status index_minimizers(kh_index* x, const void* text, uint64_t n, uint32_t k, uint32_t w, int canonical, int hash, uint64_t seed, kh_mem where, bool fastq,
-                           bool append, uint32_t pos_base) {
+                           bool append, uint32_t pos_base, bool syncmers = false) {
   if (!x) return KH_ERR_INVALID;
-  if (x->kw != 1) return xfail(x, KH_ERR_INVALID, "kh_index: minimizers are defined for 64-bit k-mers only");
+  if (!syncmers && x->kw != 1) return xfail(x, KH_ERR_INVALID, "kh_index: minimizers are defined for 64-bit k-mers only");
   if (n >> 32) return xfail(x, KH_ERR_INVALID, "kh_index: positions are 32-bit, a text of 2^32 bytes or more is refused");
   if (!append && x->built) return xfail(x, KH_ERR_INVALID, "kh_index: the index is built already (kh_index_clear first)");
   if (append && (uint64_t)pos_base + n > (uint64_t(1) << 32)) return xfail(x, KH_ERR_INVALID, "kh_index_append: pos_base + n passes 2^32, a window position would wrap");
-  if (k < 1 || k > 32) return xfail(x, KH_ERR_INVALID, "kh_index: k must be 1..32");
-  if (w < 1 || w > KM_MZ_WMAX) return xfail(x, KH_ERR_INVALID, "kh_index: w must be 1..256");
+  if (k < 1 || k > 32 * x->kw) return xfail(x, KH_ERR_INVALID, x->kw == 2 ? "kh_wide_index: k must be 1..64" : "kh_index: k must be 1..32");
+  if (syncmers && (w < 1 || w > k || w > 32)) return xfail(x, KH_ERR_INVALID, "kh_index: s must be 1..min(k, 32)");
+  if (!syncmers && (w < 1 || w > KM_MZ_WMAX)) return xfail(x, KH_ERR_INVALID, "kh_index: w must be 1..256");
   if (hash < 0 || hash > 3) return xfail(x, KH_ERR_INVALID, "kh_index: unknown order hash");
-  if (n < (uint64_t)w + k - 1) return KH_OK;
+  if (n < (syncmers ? (uint64_t)k : (uint64_t)w + k - 1)) return KH_OK;
   if (!text) return xfail(x, KH_ERR_INVALID, "null text");
   kh_table* t = x->t;
   HIPCHK(hipSetDevice(x->device));
   MzWork M;
+  if (syncmers) { M.s = w; M.kw = x->kw; }
   uint64_t m = 0;
   kh_status st = mz_count(t, M, text, n, k, w, canonical, hash, seed, where, fastq, x->device, t->stream, &m);
   if (st != KH_OK) return xfail(x, st, t->err);
   if (append && (x->total + m) >> 32) { mz_free(M); return xfail(x, KH_ERR_INVALID, "kh_index_append: offsets are 32-bit, the index must stay below 2^32 positions"); }
   if (m == 0) { mz_free(M); return KH_OK; }
   char* pairs = nullptr;
-  const hipError_t e = pool_alloc(x->device, m * 12, reinterpret_cast<void**>(&pairs));
-  if (e != hipSuccess) { mz_free(M); return xfail(x, e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP, "kh_index: no memory for the minimizer pairs"); }
+  const hipError_t e = pool_alloc(x->device, m * (8 * x->kw + 4), reinterpret_cast<void**>(&pairs));
+  if (e != hipSuccess) { mz_free(M); return xfail(x, e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP, "kh_index: no memory for the sampled pairs"); }
   uint64_t* dk = reinterpret_cast<uint64_t*>(pairs);
-  uint32_t* dp = reinterpret_cast<uint32_t*>(pairs + m * 8);
+  uint32_t* dp = reinterpret_cast<uint32_t*>(pairs + m * 8 * x->kw);
   st = mz_emit(t, M, t->stream, dk, dp, append ? pos_base : 0u);
   bool touched = !append;      // (a build starts from an empty index: abandoning it changes nothing)
   if (st == KH_OK) {
@@ -3607,6 +3720,14 @@ kh_status kh_index_build_from_minimizers(kh_index* x, const void* text, uint64_t
 kh_status kh_index_append_from_minimizers(kh_index* x, const void* text, uint64_t n, uint32_t k, uint32_t w, int canonical, kh_hash order_hash, uint64_t order_seed,
                                           kh_mem where, int fastq, uint32_t pos_base) {
   return index_minimizers(x, text, n, k, w, canonical, (int)order_hash, order_seed, where, fastq != 0, true, pos_base);
+}
+kh_status kh_index_build_from_syncmers(kh_index* x, const void* text, uint64_t n, uint32_t k, uint32_t s, int canonical, kh_hash order_hash, uint64_t order_seed,
+                                       kh_mem where, int fastq) {
+  return index_minimizers(x, text, n, k, s, canonical, (int)order_hash, order_seed, where, fastq != 0, false, 0u, true);
+}
+kh_status kh_index_append_from_syncmers(kh_index* x, const void* text, uint64_t n, uint32_t k, uint32_t s, int canonical, kh_hash order_hash, uint64_t order_seed,
+                                        kh_mem where, int fastq, uint32_t pos_base) {
+  return index_minimizers(x, text, n, k, s, canonical, (int)order_hash, order_seed, where, fastq != 0, true, pos_base, true);
 }
 kh_status kh_index_erase(kh_index* x, const void* keys, uint64_t n, kh_mem where, uint64_t* n_keys_erased, uint64_t* n_pos_erased) {
   if (n_keys_erased) *n_keys_erased = 0;
@@ -3763,6 +3884,14 @@ kh_status kh_wide_index_append_from_sequence(kh_windex* x, const void* seq, uint
 }
 kh_status kh_wide_index_append_from_fastq(kh_windex* x, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, uint32_t pos_base) {
   return index_text(x, text, n, k, canonical, where, true, true, pos_base);
+}
+kh_status kh_wide_index_build_from_syncmers(kh_windex* x, const void* text, uint64_t n, uint32_t k, uint32_t s, int canonical, kh_hash order_hash, uint64_t order_seed,
+                                            kh_mem where, int fastq) {
+  return kh_index_build_from_syncmers(x, text, n, k, s, canonical, order_hash, order_seed, where, fastq);
+}
+kh_status kh_wide_index_append_from_syncmers(kh_windex* x, const void* text, uint64_t n, uint32_t k, uint32_t s, int canonical, kh_hash order_hash, uint64_t order_seed,
+                                             kh_mem where, int fastq, uint32_t pos_base) {
+  return kh_index_append_from_syncmers(x, text, n, k, s, canonical, order_hash, order_seed, where, fastq, pos_base);
 }
 kh_status kh_wide_index_erase(kh_windex* x, const void* keys, uint64_t n, kh_mem where, uint64_t* n_keys_erased, uint64_t* n_pos_erased) {
   return kh_index_erase(x, keys, n, where, n_keys_erased, n_pos_erased);

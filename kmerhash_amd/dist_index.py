@@ -13,7 +13,8 @@ table operation exists on the index.
              exchange with the position totals per source (the status word of the local find with it), one grouped payload exchange
              that brings the per-key counts to their place in the permuted order and the segments concatenated by owner rank -- the
              CSR in permuted order --, and kh_csr_unpermute puts it into QUERY order.
-Texts: every rank samples ITS text (all windows, or the (w,k)-minimizers of an index made with w) and appends the pairs; nothing is
+Texts: every rank samples ITS text (all windows, the (w,k)-minimizers of an index made with w, or the closed syncmers of one made with
+s) and appends the pairs; nothing is
 stitched across two ranks' texts -- a window or a minimizer window never spans them, as it never spans two reads.
 
 Collectives per call (p > 1, or KH_DIST_FORCE_COLLECTIVES=1), as `collectives` counts them ("reduce": an all-reduce(sum) of the call's
@@ -42,17 +43,18 @@ from .dist import DIST_SEED, GpuBackend, GpuSharding, ShardedTable, ShardExchang
 
 
 class IndexGpuBackend(GpuSharding):
-    """local index = KmerPositionIndex on this rank's GPU (64-bit k-mers, k <= 32; w: minimizer sampling); sharding = kh_shard_permute"""
+    """local index = KmerPositionIndex on this rank's GPU (64-bit k-mers, k <= 32; w: minimizer sampling, s: closed syncmers); sharding =
+    kh_shard_permute"""
 
     def __init__(self, device, k=31, canonical=True, hash="farm", seed=43, w=None, order_hash="murmur", order_seed=42, min_lf=0.35,
-                 max_lf=0.8, dist_hash="murmur3avx64", dist_seed=DIST_SEED):
-        self.index = self._make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed)
+                 max_lf=0.8, dist_hash="murmur3avx64", dist_seed=DIST_SEED, s=None):
+        self.index = self._make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed, s)
         super().__init__(device, dist_hash, dist_seed)
 
     @staticmethod
-    def _make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed):
+    def _make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed, s):
         from .index import KmerPositionIndex
-        return KmerPositionIndex(k, canonical, hash, min_lf, max_lf, device, seed, w=w, order_hash=order_hash, order_seed=order_seed)
+        return KmerPositionIndex(k, canonical, hash, min_lf, max_lf, device, seed, w=w, order_hash=order_hash, order_seed=order_seed, s=s)
 
     def _text(self, text):
         if isinstance(text, (bytes, bytearray)):
@@ -65,6 +67,8 @@ class IndexGpuBackend(GpuSharding):
         """-> device (k-mers, positions) of this rank's text, sampled as the index samples"""
         from .kmers import kmers_from_sequence, minimizers_from_sequence
         x, t = self.index, self._text(text)
+        if x.s is not None:
+            return x._syncmers(t, fastq)
         if x.w is None:
             return kmers_from_sequence(t, x.k, x.canonical, self.device, _fastq=fastq, with_positions=True)
         return minimizers_from_sequence(t, x.k, x.w, x.canonical, x.order_hash, x.order_seed, self.device, _fastq=fastq)
@@ -93,21 +97,23 @@ class IndexGpuBackend(GpuSharding):
 
 class WideIndexGpuBackend(IndexGpuBackend):
     """local index = WideKmerPositionIndex (16-byte k-mers, k <= 64; keys are (n, 2) int64 CUDA tensors); sharding = kh_wide_shard_permute.
-    No minimizer sampling.  The unpermute step never sees a key: it is the parent's."""
+    No minimizer sampling; s: closed syncmers.  The unpermute step never sees a key: it is the parent's."""
     key_words = 2
 
     def __init__(self, device, k=63, canonical=True, hash="farm", seed=43, min_lf=0.35, max_lf=0.8, dist_hash="murmur3avx64",
-                 dist_seed=DIST_SEED):
-        super().__init__(device, k, canonical, hash, seed, None, "murmur", 42, min_lf, max_lf, dist_hash, dist_seed)
+                 dist_seed=DIST_SEED, s=None, order_hash="murmur", order_seed=42):
+        super().__init__(device, k, canonical, hash, seed, None, order_hash, order_seed, min_lf, max_lf, dist_hash, dist_seed, s)
 
     @staticmethod
-    def _make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed):
+    def _make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed, s):
         from .index import WideKmerPositionIndex
-        return WideKmerPositionIndex(k, canonical, hash, min_lf, max_lf, device, seed)
+        return WideKmerPositionIndex(k, canonical, hash, min_lf, max_lf, device, seed, order_hash=order_hash, order_seed=order_seed, s=s)
 
     def text_pairs(self, text, fastq=False):
         from .wide import kmers128_from_sequence
         x = self.index
+        if x.s is not None:
+            return x._syncmers(self._text(text), fastq)
         return kmers128_from_sequence(self._text(text), x.k, x.canonical, self.device, _fastq=fastq, with_positions=True)
 
 

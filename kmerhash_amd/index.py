@@ -25,12 +25,21 @@ class KmerPositionIndex:
     WORDS = 1                     # 64-bit words per key
 
     def __init__(self, k=31, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0, seed=43,
-                 w=None, order_hash="murmur", order_seed=42):
+                 w=None, order_hash="murmur", order_seed=42, s=None):
         """w: index the (w,k)-minimizers of a text instead of all its windows (kmerhash_amd.minimizers_from_sequence: of every w
         consecutive windows the one whose k-mer has the smallest order_hash(k-mer, order_seed), about 2 / (w + 1) of them);
-        build_sequences, build_fastq, append_sequences, append_fastq and find_sequences then sample with it.  None: every window."""
+        build_sequences, build_fastq, append_sequences, append_fastq and find_sequences then sample with it.  None: every window.
+        s: index the closed syncmers instead (kmerhash_amd.syncmers_from_sequence: the k-mers whose smallest s-mer by
+        order_hash(s-mer, order_seed) is their first or last, about 2 / (k - s + 1) of them; s = 1..min(k, 32)).  Selection is a function
+        of the k-mer alone, so it works for either key width and sampled(keys) can tell what the index can hold.  Not together with w."""
         if not 1 <= int(k) <= self.KMAX:
             raise ValueError("k must be 1..%d, got %r" % (self.KMAX, k))
+        if s is not None:
+            if w is not None:
+                raise ValueError("s (closed syncmers) and w (minimizers) are two samplers: give one of them")
+            if not 1 <= int(s) <= min(int(k), 32):
+                raise ValueError("s must be 1..min(k, 32) or None, got %r" % (s,))
+        self.s = None if s is None else int(s)
         if w is not None:
             if self.WORDS != 1:
                 raise ValueError("minimizer sampling (w=) is not supported for 16-byte k-mers: use KmerPositionIndex (k <= 32)")
@@ -95,10 +104,11 @@ class KmerPositionIndex:
             text = np.frombuffer(text, dtype=np.uint8)
         b = _Buf(text, np.uint8, 1)
         self._stream(b)
-        if self.w is not None:      # the same four calls over the minimizers of the text
+        if self.w is not None or self.s is not None:      # the same four calls over the minimizers / closed syncmers of the text
             verb, _, form = fn.partition("_from_")
-            self._chk(self._fn(verb + "_from_minimizers")(self._h, b.ptr, b.n, self.k, self.w, 1 if self.canonical else 0, self.order_hash,
-                                                          self.order_seed, b.where, 1 if form == "fastq" else 0, *more))
+            sampler, arg = ("_from_minimizers", self.w) if self.s is None else ("_from_syncmers", self.s)
+            self._chk(self._fn(verb + sampler)(self._h, b.ptr, b.n, self.k, arg, 1 if self.canonical else 0, self.order_hash,
+                                               self.order_seed, b.where, 1 if form == "fastq" else 0, *more))
             return self.total()
         self._chk(self._fn(fn)(self._h, b.ptr, b.n, self.k, 1 if self.canonical else 0, b.where, *more))
         return self.total()
@@ -234,18 +244,40 @@ class KmerPositionIndex:
 
     def find_sequences(self, seq):
         """the index's own sampling of a query text, then find: -> (qpos, offsets, positions).  The k-mers of `seq` are taken with
-        the index's k, canonical flag and -- when it was made with w -- its w, order hash and order seed (all windows otherwise);
+        the index's k, canonical flag and -- when it was made with w or s -- that sampler, order hash and order seed (all windows otherwise);
         qpos[i] is the byte offset in `seq` of query k-mer i and positions[offsets[i]:offsets[i + 1]] are its occurrences in the index.
         Two device calls composed here; numpy in, numpy out, CUDA tensor in, tensors out."""
         from .kmers import kmers_from_sequence, minimizers_from_sequence
-        if self.WORDS != 1:
-            raise ValueError("find_sequences is not supported for 16-byte k-mers")
-        if self.w is None:
+        if self.WORDS != 1 and self.s is None:
+            raise ValueError("find_sequences is not supported for 16-byte k-mers without s")
+        if self.s is not None:
+            km, qpos = self._syncmers(seq)
+        elif self.w is None:
             km, qpos = kmers_from_sequence(seq, self.k, self.canonical, self.device, with_positions=True)
         else:
             km, qpos = minimizers_from_sequence(seq, self.k, self.w, self.canonical, self.order_hash, self.order_seed, self.device)
         offsets, positions = self.find(km)
         return qpos, offsets, positions
+
+    def _syncmers(self, seq, fastq=False):
+        """the closed syncmers of a text under the index's own parameters"""
+        from .kmers import syncmers_from_sequence
+        return syncmers_from_sequence(seq, self.k, self.s, self.canonical, self.order_hash, self.order_seed, self.device, _fastq=fastq)
+
+    def sampled(self, keys):
+        """bool per key: could the index hold it?  True for every key of an index of all windows; is_syncmer(keys) under the index's
+        parameters for one made with s -- count(keys) == 0 then means "absent from the text" where sampled is True and "not sampled"
+        where it is False.  An index made with w raises: a minimizer is chosen by its neighbours, not by the k-mer."""
+        if self.w is not None:
+            raise ValueError("sampled() has no answer for a minimizer index (w=): selection there depends on the neighbouring windows")
+        q, n = self._kbuf(keys)
+        if self.s is None:
+            return torch.ones(n, dtype=torch.bool, device=q.device) if q.where == K.KH_MEM_DEVICE else np.ones(n, dtype=bool)
+        return self._is_syncmer(keys)
+
+    def _is_syncmer(self, keys):
+        from .kmers import is_syncmer
+        return is_syncmer(keys, self.k, self.s, self.canonical, self.order_hash, self.order_seed, self.device)
 
     # -- measurement -----------------------------------------------------------------------------
     def profile_enable(self, on=True):
@@ -270,8 +302,17 @@ class WideKmerPositionIndex(KmerPositionIndex):
     KMAX = 64
     WORDS = 2
 
-    def __init__(self, k=63, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0, seed=43, w=None):
-        super().__init__(k, canonical, hash, min_load_factor, max_load_factor, device, seed, w=w)
+    def __init__(self, k=63, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0, seed=43, w=None,
+                 order_hash="murmur", order_seed=42, s=None):
+        super().__init__(k, canonical, hash, min_load_factor, max_load_factor, device, seed, w=w, order_hash=order_hash, order_seed=order_seed, s=s)
+
+    def _syncmers(self, seq, fastq=False):
+        from .wide import syncmers128_from_sequence
+        return syncmers128_from_sequence(seq, self.k, self.s, self.canonical, self.order_hash, self.order_seed, self.device, _fastq=fastq)
+
+    def _is_syncmer(self, keys):
+        from .wide import is_syncmer128
+        return is_syncmer128(keys, self.k, self.s, self.canonical, self.order_hash, self.order_seed, self.device)
 
     def export_info(self):
         """the Robin Hood info byte of every bucket of the index's table (uint8[capacity]): the counting twin's"""

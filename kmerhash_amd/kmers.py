@@ -114,6 +114,78 @@ def minimizers_from_fastq(text, k=15, w=10, canonical=True, order_hash="murmur",
     return minimizers_from_sequence(text, k, w, canonical, order_hash, order_seed, device, _fastq=True)
 
 
+def _syncmers(fn_name, words, seq, k, s, canonical, order_hash, order_seed, device):
+    """shared body of syncmers_from_sequence / syncmers128_from_sequence (and their FASTQ forms): a count pass, an exact allocation,
+    the emit pass; `words` 64-bit words per k-mer"""
+    import ctypes as C
+    from . import _capi as K
+    from .table import _Buf, KhError, _hash_id
+    if isinstance(seq, (bytes, bytearray)):
+        seq = np.frombuffer(seq, dtype=np.uint8)
+    b = _Buf(seq, np.uint8, 1)
+    dev = b.where == K.KH_MEM_DEVICE
+    stream = torch.cuda.current_stream(device).cuda_stream if dev else None
+    fn, n_out = getattr(K.lib(), fn_name), C.c_uint64()
+    args = (b.ptr, b.n, int(k), int(s), 1 if canonical else 0, _hash_id(order_hash), int(order_seed), b.where)
+    st = fn(*args, None, None, 0, C.byref(n_out), device, stream)
+    if st != K.KH_OK:
+        raise KhError(st, fn_name)
+    m = n_out.value
+    shape = m if words == 1 else (m, words)
+    if dev:
+        out = torch.empty(shape, dtype=torch.int64, device=b.device)
+        pos = torch.empty(m, dtype=torch.int32, device=b.device)
+        optr, pptr = out.data_ptr(), pos.data_ptr()
+    else:
+        out = np.zeros(shape, dtype=np.uint64)
+        pos = np.zeros(m, dtype=np.uint32)
+        optr, pptr = out.ctypes.data, pos.ctypes.data
+    if m:
+        st = fn(*args, optr, pptr, m, C.byref(n_out), device, stream)
+        if st != K.KH_OK:
+            raise KhError(st, fn_name)
+    return out, pos
+
+
+def _syncmer_mask(fn_name, kb, n, k, s, canonical, order_hash, order_seed, device):
+    """shared body of is_syncmer / is_syncmer128 over a _Buf of key words: -> bool array / tensor of n entries"""
+    from . import _capi as K
+    from .table import KhError, _hash_id
+    if kb.where == K.KH_MEM_DEVICE:
+        out = torch.zeros(n, dtype=torch.uint8, device=kb.device)
+        optr, stream = out.data_ptr(), torch.cuda.current_stream(device).cuda_stream
+    else:
+        out = np.zeros(n, dtype=np.uint8)
+        optr, stream = out.ctypes.data, None
+    st = getattr(K.lib(), fn_name)(kb.ptr, n, int(k), int(s), 1 if canonical else 0, _hash_id(order_hash), int(order_seed), kb.where, optr, device,
+                                   stream)
+    if st != K.KH_OK:
+        raise KhError(st, fn_name)
+    return out.bool() if kb.where == K.KH_MEM_DEVICE else out.astype(bool)
+
+
+def syncmers_from_sequence(seq, k=15, s=11, canonical=True, order_hash="murmur", order_seed=42, device=0, _fastq=False):
+    """closed syncmers of `seq` -> (k-mers, positions), ascending positions: the windows of kmers_from_sequence(with_positions=True)
+    whose smallest s-mer by order_hash(s-mer, order_seed) -- of the canonical s-mer when `canonical` -- is the first or the last of the
+    k - s + 1 (kh_syncmers_from_sequence in include/kmerhash_amd.h).  About 2 / (k - s + 1) of the windows; all of them for s = k.
+    Whether a k-mer is kept depends on the k-mer alone (is_syncmer asks without a text).  numpy uint64 / uint32 for host input, torch
+    int64 / int32 CUDA tensors for device input.  In a homopolymer every window is kept."""
+    return _syncmers("kh_syncmers_from_fastq" if _fastq else "kh_syncmers_from_sequence", 1, seq, k, s, canonical, order_hash, order_seed, device)
+
+
+def syncmers_from_fastq(text, k=15, s=11, canonical=True, order_hash="murmur", order_seed=42, device=0):
+    """syncmers_from_sequence over the sequence lines of raw FASTQ text (whole 4-line records); positions are byte offsets into the text"""
+    return syncmers_from_sequence(text, k, s, canonical, order_hash, order_seed, device, _fastq=True)
+
+
+def is_syncmer(keys, k=15, s=11, canonical=True, order_hash="murmur", order_seed=42, device=0):
+    """for packed k-mers (uint64 numpy array or int64 CUDA tensor): a bool array / tensor, True where the k-mer is a closed syncmer
+    under these parameters -- the k-mers syncmers_from_sequence keeps, whatever text they stand in (kh_syncmer_mask)"""
+    from .table import _Buf
+    kb = _Buf(keys, np.uint64, 8)
+    return _syncmer_mask("kh_syncmer_mask", kb, kb.n, k, s, canonical, order_hash, order_seed, device)
+
+
 class KmerCounter:
     """counting index: k-mer -> number of occurrences (Reducer = std::plus, value 1 per occurrence)"""
 

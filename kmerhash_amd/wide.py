@@ -232,3 +232,23 @@ def kmers128_from_fastq(text, k=63, canonical=True, device=0, with_positions=Fal
     """raw FASTQ text (whole 4-line records) -> (n, 2) k-mers of the sequence lines (record structure resolved on the GPU);
     with_positions: -> (k-mers, byte offsets of their windows in the raw text)"""
     return kmers128_from_sequence(text, k, canonical, device, _fastq=True, with_positions=with_positions)
+
+
+def syncmers128_from_sequence(seq, k=63, s=31, canonical=True, order_hash="murmur", order_seed=42, device=0, _fastq=False):
+    """closed syncmers of `seq` as 16-byte k-mers, k = 1..64, s = 1..min(k, 32) -> ((m, 2) k-mers, positions), ascending positions: the
+    windows of kmers128_from_sequence(with_positions=True) whose smallest s-mer by order_hash (of the canonical s-mer when `canonical`)
+    is the first or the last of the k - s + 1 (kh_syncmers128_from_sequence; kmerhash_amd.syncmers_from_sequence for the definition)"""
+    from .kmers import _syncmers
+    return _syncmers("kh_syncmers128_from_fastq" if _fastq else "kh_syncmers128_from_sequence", 2, seq, k, s, canonical, order_hash, order_seed, device)
+
+
+def syncmers128_from_fastq(text, k=63, s=31, canonical=True, order_hash="murmur", order_seed=42, device=0):
+    """syncmers128_from_sequence over the sequence lines of raw FASTQ text (whole 4-line records); positions are byte offsets into the text"""
+    return syncmers128_from_sequence(text, k, s, canonical, order_hash, order_seed, device, _fastq=True)
+
+
+def is_syncmer128(keys, k=63, s=31, canonical=True, order_hash="murmur", order_seed=42, device=0):
+    """for (n, 2) 16-byte k-mers: a bool array / tensor, True where the k-mer is a closed syncmer under these parameters (kh_wide_syncmer_mask)"""
+    from .kmers import _syncmer_mask
+    kb = _keys(keys)
+    return _syncmer_mask("kh_wide_syncmer_mask", kb, kb.n // 2, k, s, canonical, order_hash, order_seed, device)
