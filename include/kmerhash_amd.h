@@ -85,6 +85,16 @@ kh_status kh_create(kh_table** out, kh_kind kind, uint32_t key_bytes /*8*/, uint
                     kh_hash hash, uint64_t seed /*43*/, uint64_t capacity /*128*/,
                     float min_load_factor, float max_load_factor, int device);
 kh_status kh_destroy(kh_table* t);
+/* Streams (DESIGN.md "Streams"): all device work of a handle is issued on the handle's stream.  A change of stream keeps earlier work
+ *      ordered before later work: kh_set_stream waits for the old stream before it switches (the same stream again: nothing happens), so
+ *      calls on one handle take effect in call order whichever streams they were issued under.  A call that reads a second handle
+ *      (kh_hll_merge) is ordered after that handle's pending work.  Most calls return a scalar and have synchronised the stream when
+ *      they return.  The calls that only queue their work, when given device memory, are: kh_count, kh_wide_count, kh_find with
+ *      n_found == NULL, kh_insert_feed / kh_wide_insert_feed, kh_hash_batch / kh_hash_batch_transformed / kh_wide_hash_batch,
+ *      kh_shard_plan_permute / _permute_global, and kh_hll_update / _update_via_hashval / _update_wide, kh_hll_update_from_sequence /
+ *      _from_fastq with n_kmers == NULL, kh_hll_merge and kh_hll_clear.  For these the caller's input buffers must stay valid and
+ *      unchanged, and the outputs are complete, only in the order of that stream: until work queued behind the call on the same
+ *      stream runs, or the stream (or a later synchronising call on the handle) has been waited for. */
 kh_status kh_set_stream(kh_table* t, void* hip_stream /* hipStream_t; NULL = default stream */);
 /* the PreTransform of the table's TransformedHash / TransformedComparator; k = k-mer length (1..32) for KH_XF_DNA_LEX_LESS.
  * Only on an empty table (the reference fixes it at compile time). */
@@ -310,6 +320,8 @@ kh_status kh_kmers_from_fastq_pos(const void* text /*[h|d] u8[n]*/, uint64_t n, 
 typedef struct kh_index kh_index;
 kh_status kh_index_create(kh_index** out, kh_hash hash, uint64_t seed, float min_lf, float max_lf, int device);
 kh_status kh_index_destroy(kh_index* x);
+/* the index's work is issued on this stream; like kh_set_stream it waits for the old stream before it switches, so earlier calls stay
+ * ordered before later ones.  Every batch call of an index synchronises the stream before it returns. */
 kh_status kh_index_set_stream(kh_index* x, void* hip_stream);
 const char* kh_index_last_error(const kh_index* x);
 kh_status kh_index_clear(kh_index* x);
@@ -367,6 +379,12 @@ kh_status kh_index_profile_dump(kh_index* x, char* buf, uint64_t cap);
 typedef struct kh_hll kh_hll;
 kh_status kh_hll_create(kh_hll** out, uint32_t precision /*12*/, uint32_t ignore_msb /*0*/, kh_hash hash, uint64_t seed, int device);
 kh_status kh_hll_destroy(kh_hll* h);
+/* the estimator's work is issued on this stream; like kh_set_stream it waits for the old stream before it switches, so an update queued
+ * under one stream is seen by kh_hll_registers / _estimate / _clear / a further update under the next, and kh_hll_destroy never frees
+ * registers a queued kernel still writes.  kh_hll_merge(h, other) runs on h's stream and first waits for other's stream when the two
+ * differ; the read of other's registers is only queued: other must not be updated, cleared or destroyed until h's stream has run the
+ * merge (kh_hll_registers(h) waits for it).  Updates from device memory, merge, clear and the text passes with n_kmers == NULL return without synchronising: their
+ * input must stay valid until the estimator's stream has run them (kh_hll_registers and kh_hll_estimate synchronise). */
 kh_status kh_hll_set_stream(kh_hll* h, void* hip_stream);
 kh_status kh_hll_update(kh_hll* h, const void* keys /*[h|d] u64[n]*/, uint64_t n, kh_mem where);               /* update(vals,count) :357 */
 kh_status kh_hll_update_via_hashval(kh_hll* h, const void* hashes /*[h|d] u64[n]*/, uint64_t n, kh_mem where); /* :449-455 */

@@ -2678,7 +2678,14 @@ kh_status kh_hll_destroy(kh_hll* h) {
   delete h;
   return KH_OK;
 }
-kh_status kh_hll_set_stream(kh_hll* h, void* s) { if (!h) return KH_ERR_INVALID; h->stream = static_cast<hipStream_t>(s); return KH_OK; }
+kh_status kh_hll_set_stream(kh_hll* h, void* s) {
+  if (!h) return KH_ERR_INVALID;
+  if (h->stream == static_cast<hipStream_t>(s)) return KH_OK;     // unchanged: nothing to order
+  hipSetDevice(h->device);
+  hipStreamSynchronize(h->stream);                                   // work already issued stays ordered before the new stream's
+  h->stream = static_cast<hipStream_t>(s);
+  return KH_OK;
+}
 // kw: 64-bit words per key (2: 16-byte keys, from_keys only)
 static kh_status hll_update(kh_hll* h, const void* in, uint64_t n, kh_mem where, bool from_keys, uint32_t kw = 1) {
   kh_table* t = nullptr;
@@ -2782,6 +2789,7 @@ kh_status kh_hll_merge(kh_hll* h, const kh_hll* other) {
   if (!h || !other || h->precision != other->precision || h->device != other->device) return KH_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
   const uint32_t m = 1u << h->precision;
+  if (other->stream != h->stream) HIPCHK(hipStreamSynchronize(other->stream));      // other's pending updates land before its registers are read
   hipLaunchKernelGGL(k_hll_merge, dim3((m + 255) / 256), dim3(256), 0, h->stream, h->regs, other->regs, m);
   HIPCHK(hipGetLastError());
   return KH_OK;

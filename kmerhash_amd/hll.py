@@ -63,6 +63,9 @@ class hyperloglog64:
             raise K.KhError(st, what)
 
     def _stream(self, b):
+        """a call with a device argument runs on torch's current stream (the argument is ready in that stream's order).  merge, clear,
+        registers and estimate have none and do not adopt it: they run on the stream of the last such call, in call order behind it --
+        kh_hll_set_stream waits for the old stream when it switches, kh_hll_merge for the other estimator's."""
         if b.where == K.KH_MEM_DEVICE and torch is not None:
             self._L.kh_hll_set_stream(self._h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
 

@@ -22,11 +22,12 @@ def dev(a, dtype):
     return torch.from_numpy(np.ascontiguousarray(a).astype(dtype).view({4: np.int32, 8: np.int64}[np.dtype(dtype).itemsize]).copy()).cuda()
 
 
-def unpermute(counts_perm, pos_perm, origin, counts=True, offsets=True, positions=True, cap=None):
-    """-> (status, n_out, counts | None, offsets | None, positions buffer | None) as numpy arrays"""
+def unpermute(counts_perm, pos_perm, origin, counts=True, offsets=True, positions=True, cap=None, inputs=None):
+    """-> (status, n_out, counts | None, offsets | None, positions buffer | None) as numpy arrays
+    inputs: the three device buffers to pass instead of copies of the arrays (which then only give the sizes)"""
     n, total = len(counts_perm), len(pos_perm)
     cap = total if cap is None else cap
-    dc, dp, do = dev(counts_perm, np.uint32), dev(pos_perm, np.uint32), dev(origin, np.uint32)
+    dc, dp, do = inputs if inputs is not None else (dev(counts_perm, np.uint32), dev(pos_perm, np.uint32), dev(origin, np.uint32))
     oc = torch.full((max(n, 1),), SENTINEL, dtype=torch.int32, device="cuda") if counts else None
     oo = torch.full((n + 1,), -1, dtype=torch.int64, device="cuda") if offsets else None
     op = torch.full((max(cap, 1),), SENTINEL, dtype=torch.int32, device="cuda") if positions else None
@@ -106,8 +107,21 @@ def test_cap_out_one_too_small():
 
 
 def test_on_a_non_default_stream():
-    s = torch.cuda.Stream()
+    """the inputs arrive late on the side stream (stream_checks.late_inputs: until a delay on that stream has run the buffers hold a
+    decoy -- the same counts rotated, so the same total, another permutation, other positions) and the stream is still busy when the
+    call is made: a call that ran on another stream would unpermute the decoy"""
+    from stream_checks import assert_busy, late_inputs, side_stream
+    s = side_stream()
     rng = np.random.default_rng(5)
+    counts, origin = rng.integers(0, 9, 5000).astype(np.uint32), rng.permutation(5000).astype(np.uint32)
+    total = int(counts.sum())
+    pos = rng.integers(0, 1 << 32, total, dtype=np.uint64).astype(np.uint32)
+    decoys = np.roll(counts, 1), (pos ^ np.uint32(0x0F0F0F0F)).astype(np.uint32), rng.permutation(5000).astype(np.uint32)
+    ec, eo, ep = np_csr_unpermute(counts, pos, origin)
     with torch.cuda.stream(s):
         assert torch.cuda.current_stream(0).cuda_stream == s.cuda_stream != torch.cuda.default_stream(0).cuda_stream
-        check(rng.integers(0, 9, 5000), rng.permutation(5000))
+        bufs = late_inputs(s, (counts, decoys[0]), (pos, decoys[1]), (origin, decoys[2]))
+        assert_busy(s)
+        st, n_out, c, o, p = unpermute(counts, pos, origin, inputs=bufs)
+    assert st == K.KH_OK and n_out == total
+    assert np.array_equal(c, ec) and np.array_equal(o, eo) and np.array_equal(p[:total], ep)
