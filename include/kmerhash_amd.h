@@ -293,7 +293,7 @@ kh_status kh_kmers_from_fastq(const void* text /*[h|d] u8[n]*/, uint64_t n, uint
 
 /* the same k-mers, in the same order and with the same n_out, each with the byte offset of the first base of its window in the buffer
  *      passed: out_pos[i] belongs to out_kmers[i] (for FASTQ an offset into the raw text, not into a read).  canonical != 0: the offset
- *      is the window's; which strand the canonical form came from is not recorded (compare the window with its reverse complement).
+ *      is the window's; which strand the canonical form came from is not recorded here: kh_stamp_strand recovers it from (text, offsets).
  *      Positions are 32-bit: n >= 2^32 is KH_ERR_INVALID before anything is allocated or read.  out_pos needs room for n entries. */
 kh_status kh_kmers_from_sequence_pos(const void* seq /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..32*/, int canonical, kh_mem where,
                                      uint64_t* out_kmers /*[h|d]*/, uint32_t* out_pos /*[h|d]*/, uint64_t* n_out, int device, void* hip_stream);
@@ -316,7 +316,7 @@ kh_status kh_kmers_from_fastq_pos(const void* text /*[h|d] u8[n]*/, uint64_t n, 
  *      kh_index_build_from_sequence / _from_fastq: kh_kmers_from_sequence_pos / _fastq_pos and the build, on device buffers (host text
  *      is staged once; k-mers and positions never visit the host).
  *      kh_index_export: keys in slot order (the order of kh_to_vector), offsets and positions, into host buffers (any may be NULL).
- *      The linear-probe layout and a strand bit are not supported; 16-byte keys (k <= 64) are kh_wide_index_* below. */
+ *      The linear-probe layout is not supported; a strand bit per occurrence: kh_index_set_stranded below; 16-byte keys (k <= 64) are kh_wide_index_* below. */
 typedef struct kh_index kh_index;
 kh_status kh_index_create(kh_index** out, kh_hash hash, uint64_t seed, float min_lf, float max_lf, int device);
 kh_status kh_index_destroy(kh_index* x);
@@ -516,7 +516,7 @@ kh_status kh_profile_dump(kh_table* t, char* buf, uint64_t cap);
  *      kh_wide_index_export: keys_host u64[2 size] in slot order (the order of kh_wide_to_vector).
  *      kh_wide_index_append* / _erase / _erase_counts: the contract of kh_index_append* / kh_index_erase / kh_index_erase_counts (twin:
  *      kh_wide_insert_reduce_plus batch by batch, kh_wide_erase), keys u64[2n], k = 1..64.
- *      Not supported: a strand bit, read-id decoding, 64-bit positions. */
+ *      Not supported: read-id decoding, 64-bit positions.  (A strand bit per occurrence: kh_wide_index_set_stranded.) */
 typedef struct kh_windex kh_windex;
 kh_status kh_wide_index_create(kh_windex** out, kh_hash hash, uint64_t seed, float min_lf, float max_lf, int device);
 kh_status kh_wide_index_destroy(kh_windex* x);
@@ -666,6 +666,47 @@ kh_status kh_wide_index_append_from_syncmers(kh_windex* x, const void* text /*[h
 kh_status kh_csr_unpermute(const uint32_t* counts_perm, const uint32_t* pos_perm, const uint32_t* origin, uint64_t n,
                            uint32_t* out_counts, uint64_t* out_offsets, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out,
                            int device, void* hip_stream);
+
+/* ---- strand of a window position, stranded indexes, anchors.  Every canonical front end emits min(k-mer, reverse complement) and the
+ *      window's offset; which of the two it emitted is a function of the text window alone and is recovered here, by one pass over
+ *      (text, positions) that serves every front end, both samplers and both key widths.
+ *      Definition.  For a text of n bytes, k in 1..64 and a position p, the window at p is VALID iff p + k <= n and its k bytes are bases
+ *      (ACGT in either case, as every front end reads them).  Its strand bit rc(p) is 1 iff the reverse complement of the window is
+ *      STRICTLY smaller than the window (A=0 C=1 G=2 T=3, first base most significant): exactly the case in which `canonical` makes the
+ *      front ends emit the reverse complement.  A palindrome has rc = 0.  The STAMPED position is v = ((pos_base + p) << 1) | rc(p);
+ *      stamped values sort like positions; position = v >> 1, strand = v & 1.  An invalid window gives KH_POS_INVALID.  The stamped
+ *      coordinate space is 2^31 (64-bit positions are not supported).  The definition is on bytes and knows nothing of FASTQ structure:
+ *      the positions the FASTQ front ends emit are raw-text offsets of windows that lie in one sequence line and qualify as they are.
+ *      kh_stamp_strand: text, pos and out live in the memory `where` names (device pointers valid on `device`); positions may come in
+ *      any order and may repeat; out may alias pos; no byte outside [text, text + n) is ever read, whatever pos holds.  *n_invalid
+ *      receives the number of KH_POS_INVALID written.  Device memory with n_invalid == NULL: the call only queues its work on
+ *      hip_stream (inputs must stay valid until it has run); a non-NULL n_invalid, or host memory, synchronises the stream.
+ *      KH_ERR_INVALID before anything is allocated or read: k outside 1..64, n >= 2^31, pos_base + n > 2^31, a null pos or out (or a
+ *      null text with n > 0) while m > 0.  m == 0: KH_OK. */
+#define KH_POS_INVALID 0xFFFFFFFFu
+kh_status kh_stamp_strand(const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t k /*1..64*/, const uint32_t* pos /*[h|d] u32[m]*/, uint64_t m,
+                          uint32_t pos_base, kh_mem where, uint32_t* out /*[h|d] u32[m], may alias pos*/, uint64_t* n_invalid /* may be NULL */,
+                          int device, void* hip_stream);
+/*      A STRANDED index stores stamped positions in every text form: kh_[wide_]index_build_from_sequence / _from_fastq,
+ *      _append_from_sequence / _from_fastq, and the _from_minimizers and _from_syncmers forms take the front end's pairs with pos_base 0
+ *      and stamp them over the device text they already hold (the stamp takes the place of the pass that adds pos_base).  Allowed only
+ *      on an empty index (size 0, total 0): otherwise KH_ERR_INVALID and the index is unchanged.  The flag survives kh_index_clear and a
+ *      failed build.  On a stranded index the text forms refuse, before the index is touched: canonical == 0, n >= 2^31,
+ *      pos_base + n > 2^31.  kh_index_build / kh_index_append over caller-supplied pairs are unchanged (the caller stamps: kh_stamp_strand),
+ *      and so are find, count, export, erase* -- they never interpret a position; find and export return the stamped values, which
+ *      ascend per key as positions do.  An index that is not stranded launches exactly the kernels it launched before. */
+kh_status kh_index_set_stranded(kh_index* x, int on);
+kh_status kh_wide_index_set_stranded(kh_windex* x, int on);
+/*      kh_anchors_from_csr: the CSR of a find over a stranded index (stamped query positions qpos[n], offsets[n + 1] with offsets[0] = 0
+ *      and offsets[n] = total, stamped hits pos[total]) into the flat anchor list a chainer consumes.  For output j in row i
+ *      (offsets[i] <= j < offsets[i + 1]): out_qpos[j] = qpos[i] >> 1, out_rpos[j] = pos[j] >> 1, out_rev[j] = (qpos[i] ^ pos[j]) & 1 --
+ *      0: the k bases at out_rpos in the reference equal those at out_qpos in the query, 1: they are its reverse complement.  Empty
+ *      rows give nothing.  Handle-free, like kh_csr_unpermute; all arrays live in the memory `where` names; device memory: the call only
+ *      queues its work on hip_stream.  total >= 2^32: KH_ERR_INVALID; n == 0 or total == 0: KH_OK, nothing written; a null array
+ *      otherwise: KH_ERR_INVALID. */
+kh_status kh_anchors_from_csr(const uint32_t* qpos /*[h|d] u32[n]*/, const uint64_t* offsets /*[h|d] u64[n+1]*/, uint64_t n,
+                              const uint32_t* pos /*[h|d] u32[total]*/, uint64_t total, kh_mem where, uint32_t* out_qpos /*[h|d] u32[total]*/,
+                              uint32_t* out_rpos /*[h|d] u32[total]*/, uint8_t* out_rev /*[h|d] u8[total]*/, int device, void* hip_stream);
 
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);

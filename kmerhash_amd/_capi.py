@@ -80,6 +80,8 @@ SYMBOLS = [
     "kh_syncmers_from_sequence", "kh_syncmers_from_fastq", "kh_syncmers128_from_sequence", "kh_syncmers128_from_fastq",
     "kh_syncmer_mask", "kh_wide_syncmer_mask", "kh_index_build_from_syncmers", "kh_index_append_from_syncmers",
     "kh_wide_index_build_from_syncmers", "kh_wide_index_append_from_syncmers",
+    # strand of a window position, stranded indexes (a strand bit per occurrence), a CSR of hits into flat anchors
+    "kh_stamp_strand", "kh_index_set_stranded", "kh_wide_index_set_stranded", "kh_anchors_from_csr",
 ]
 
 _lib = None
@@ -253,6 +255,10 @@ def lib():
     for pre in ("kh_index_", "kh_wide_index_"):
         getattr(L, pre + "build_from_syncmers").argtypes = [vp, vp, u64, u32, u32, i32, i32, u64, i32, i32]
         getattr(L, pre + "append_from_syncmers").argtypes = [vp, vp, u64, u32, u32, i32, i32, u64, i32, i32, u32]
+    L.kh_stamp_strand.argtypes = [vp, u64, u32, vp, u64, u32, i32, vp, pu64, i32, vp]
+    L.kh_index_set_stranded.argtypes = [vp, i32]
+    L.kh_wide_index_set_stranded.argtypes = [vp, i32]
+    L.kh_anchors_from_csr.argtypes = [vp, vp, u64, vp, u64, i32, vp, vp, vp, i32, vp]
     for s in SYMBOLS:
         if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error", "kh_wide_index_last_error"):
             getattr(L, s).restype = i32

@@ -873,6 +873,63 @@ __global__ __launch_bounds__(256) void k_index_add_base(uint32_t* __restrict__ p
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) pos[i] += base;
 }
+// ---------------------------------------------------------------------------------------------
+// strand of a window position (kh_stamp_strand, a stranded index): rc(p) = 1 iff the reverse complement of the k bases at p is
+// strictly smaller than the window -- the case in which the canonical front ends emit the reverse complement.  One lane per position.
+// Base i of the reverse complement is 3 - code(text[p + k - 1 - i]); the first i at which it differs from code(text[p + i]) decides,
+// and the pairs i >= ceil(k / 2) are the mirror images of the ones before: equal throughout the first half is a palindrome (rc = 0;
+// an odd k has none: its middle base differs from its own complement).  out[i] = ((pos_base + p) << 1) | rc, or KH_POS_INVALID.
+// CHECK: the public call -- p + k <= n and all k bytes are bases (the loop then runs its full length: both ends of every pair are
+// tested, which covers the window), invalid windows counted into *n_invalid (one atomic per wave).  !CHECK: positions a front end
+// emitted; the loop ends at the first difference, after 4/3 steps on average on random text.  The bound is tested in either form: no
+// byte outside [text, text + n) is read whatever pos holds.  pos and out may be the same array (one lane reads and writes entry i).
+// ---------------------------------------------------------------------------------------------
+#define KI_POS_INVALID 0xFFFFFFFFu
+template <bool CHECK>
+__global__ __launch_bounds__(256) void k_pos_strand(const uint8_t* __restrict__ text, uint64_t n, uint32_t k, const uint32_t* pos, uint64_t m, uint32_t pos_base,
+                                                    uint32_t* out, unsigned long long* __restrict__ n_invalid /* or null */) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  const uint32_t half = (k + 1) >> 1;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride) {
+    const uint64_t p = pos[i];
+    bool ok = p + k <= n;
+    uint32_t rc = 0;
+    if (ok) {
+      const uint8_t* __restrict__ w = text + p;
+      bool open = true;
+      for (uint32_t j = 0; j < half; ++j) {
+        const uint32_t a = kh_dna_code(w[j]), b = kh_dna_code(w[k - 1 - j]);
+        if (CHECK && (a | b) > 3u) { ok = false; break; }
+        if (open && a != 3u - b) {
+          rc = 3u - b < a ? 1u : 0u;
+          open = false;
+          if (!CHECK) break;
+        }
+      }
+    }
+    out[i] = ok ? ((pos_base + (uint32_t)p) << 1) | rc : KI_POS_INVALID;
+    if (CHECK && n_invalid) {
+      const unsigned long long bad = __ballot(!ok);
+      if (bad && (unsigned)__builtin_ctzll(bad) == (threadIdx.x & 63u)) atomicAdd(n_invalid, (unsigned long long)__popcll(bad));
+    }
+  }
+}
+// a CSR of hits (kh_index_find over stamped query positions) into the flat anchor list a chainer consumes, balanced over OUTPUT elements
+// as k_index_gather is: output j finds its row by binary search over offsets (the last row that begins at or before j: empty rows share
+// their offset with the row behind them and are passed over) and writes (query position, reference position, relative strand).
+__global__ __launch_bounds__(256) void k_anchors_expand(const uint32_t* __restrict__ qpos, const uint64_t* __restrict__ offsets, uint64_t n,
+                                                        const uint32_t* __restrict__ pos, uint64_t total, uint32_t* __restrict__ out_qpos,
+                                                        uint32_t* __restrict__ out_rpos, uint8_t* __restrict__ out_rev) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total; j += stride) {
+    uint64_t lo = 0, hi = n;
+    while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (offsets[mid] <= j) lo = mid; else hi = mid; }
+    const uint32_t q = qpos[lo], r = pos[j];
+    out_qpos[j] = q >> 1;
+    out_rpos[j] = r >> 1;
+    out_rev[j] = (uint8_t)((q ^ r) & 1u);
+  }
+}
 // erase by occurrence count: k_values_tile_count / k_values_tile_emit with the predicate on the LENGTH OF THE KEY'S SEGMENT
 // (offsets[rank + 1] - offsets[rank], the rank being the slot's value) instead of on the value, keys only.  Ranks follow the slot
 // order, so the two offsets words of a wave's slots are neighbours.

@@ -3324,6 +3324,7 @@ struct kh_index {
   uint32_t* positions = nullptr;      // u32[total]
   uint64_t total = 0;
   bool built = false, prof = false;
+  bool stranded = false;              // kh_index_set_stranded: the text forms store ((pos_base + p) << 1) | rc(p); survives clear and a failed build
   std::string err;
 };
 struct kh_windex : kh_index {};      // a distinct handle type for the C header; the host state is kh_index's, the kernels that touch a slot differ
@@ -3578,6 +3579,23 @@ kh_status index_pairs(kh_index* x, const void* keys, const void* pos, uint64_t n
   pool_free(x->device, blk);
   return st == KH_OK ? KH_OK : index_abandon(x, st);
 }
+// what a stranded index refuses before it is touched: the strand is that of the canonical choice, and a stamped position has 31 bits
+kh_status index_stranded_args(kh_index* x, uint64_t n, int canonical, uint32_t pos_base) {
+  if (!canonical) return xfail(x, KH_ERR_INVALID, "kh_index: a stranded index holds canonical k-mers (the strand bit says which strand the canonical form came from)");
+  if (n >> 31) return xfail(x, KH_ERR_INVALID, "kh_index: stamped positions are 31-bit, a text of 2^31 bytes or more is refused on a stranded index");
+  if ((uint64_t)pos_base + n > (uint64_t(1) << 31)) return xfail(x, KH_ERR_INVALID, "kh_index: pos_base + n passes 2^31 on a stranded index");
+  return KH_OK;
+}
+// the stamp of a stranded index: m window positions (pos_base 0, as the front end emitted them) over the device text they came from
+// become ((pos_base + p) << 1) | rc(p) in place; it takes the place of k_index_add_base and of the emit pass's base
+kh_status index_stamp(kh_index* x, const void* dtext, uint64_t n, uint32_t k, uint32_t* dp, uint64_t m, uint32_t pos_base) {
+  kh_table* t = x->t;
+  Launch L(t, "k_pos_strand");
+  hipLaunchKernelGGL((k_pos_strand<false>), dim3(grid_for(m, 256, (uint32_t)cu_count(t) * 8)), dim3(256), 0, t->stream, static_cast<const uint8_t*>(dtext), n, k,
+                     (const uint32_t*)dp, m, pos_base, dp, (unsigned long long*)nullptr);
+  if (hipGetLastError() != hipSuccess) return fail(t, KH_ERR_HIP, "kh_index: k_pos_strand failed");
+  return KH_OK;
+}
 // build or append straight from text: the position-keeping k-mer front end on device buffers; an append adds pos_base to every window
 // position (several texts in one coordinate space)
 kh_status index_text(kh_index* x, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq, bool append, uint32_t pos_base) {
@@ -3586,6 +3604,7 @@ kh_status index_text(kh_index* x, const void* text, uint64_t n, uint32_t k, int 
   if (!append && x->built) return xfail(x, KH_ERR_INVALID, "kh_index: the index is built already (kh_index_clear first)");
   if (append && (uint64_t)pos_base + n > (uint64_t(1) << 32)) return xfail(x, KH_ERR_INVALID, "kh_index_append: pos_base + n passes 2^32, a window position would wrap");
   if (k < 1 || k > 32 * x->kw) return xfail(x, KH_ERR_INVALID, x->kw == 2 ? "kh_wide_index: k must be 1..64" : "kh_index: k must be 1..32");
+  if (x->stranded) { const kh_status ss = index_stranded_args(x, n, canonical, append ? pos_base : 0u); if (ss != KH_OK) return ss; }
   if (n < k) return KH_OK;
   if (!text) return xfail(x, KH_ERR_INVALID, "null text");
   kh_table* t = x->t;
@@ -3606,7 +3625,8 @@ kh_status index_text(kh_index* x, const void* text, uint64_t n, uint32_t k, int 
   else if (append && (x->total + m) >> 32) st = fail(t, KH_ERR_INVALID, "kh_index_append: offsets are 32-bit, the index must stay below 2^32 positions");
   else if (m) {
     touched = true;
-    if (append && pos_base) {
+    if (x->stranded) st = index_stamp(x, dtext, n, k, dp, m, append ? pos_base : 0u);
+    else if (append && pos_base) {
       hipLaunchKernelGGL(k_index_add_base, dim3(grid_for(m, 256, (uint32_t)cu_count(t) * 8)), dim3(256), 0, t->stream, dp, m, pos_base);
       if (hipGetLastError() != hipSuccess) st = fail(t, KH_ERR_HIP, "kh_index_append: k_index_add_base failed");
     }
@@ -3631,6 +3651,7 @@ kh_status index_minimizers(kh_index* x, const void* text, uint64_t n, uint32_t k
   if (syncmers && (w < 1 || w > k || w > 32)) return xfail(x, KH_ERR_INVALID, "kh_index: s must be 1..min(k, 32)");
   if (!syncmers && (w < 1 || w > KM_MZ_WMAX)) return xfail(x, KH_ERR_INVALID, "kh_index: w must be 1..256");
   if (hash < 0 || hash > 3) return xfail(x, KH_ERR_INVALID, "kh_index: unknown order hash");
+  if (x->stranded) { const kh_status ss = index_stranded_args(x, n, canonical, append ? pos_base : 0u); if (ss != KH_OK) return ss; }
   if (n < (syncmers ? (uint64_t)k : (uint64_t)w + k - 1)) return KH_OK;
   if (!text) return xfail(x, KH_ERR_INVALID, "null text");
   kh_table* t = x->t;
@@ -3647,7 +3668,8 @@ kh_status index_minimizers(kh_index* x, const void* text, uint64_t n, uint32_t k
   if (e != hipSuccess) { mz_free(M); return xfail(x, e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP, "kh_index: no memory for the sampled pairs"); }
   uint64_t* dk = reinterpret_cast<uint64_t*>(pairs);
   uint32_t* dp = reinterpret_cast<uint32_t*>(pairs + m * 8 * x->kw);
-  st = mz_emit(t, M, t->stream, dk, dp, append ? pos_base : 0u);
+  st = mz_emit(t, M, t->stream, dk, dp, append && !x->stranded ? pos_base : 0u);
+  if (st == KH_OK && x->stranded) st = index_stamp(x, M.dseq, n, k, dp, m, append ? pos_base : 0u);      // (FASTQ: the masked text; sequence lines are kept in it)
   bool touched = !append;      // (a build starts from an empty index: abandoning it changes nothing)
   if (st == KH_OK) {
     touched = true;
@@ -3706,6 +3728,12 @@ kh_status kh_index_total(const kh_index* x, uint64_t* out) { if (!x || !out) ret
 kh_status kh_index_capacity(const kh_index* x, uint64_t* out) { if (!x || !out) return KH_ERR_INVALID; *out = x->t->cur.cap; return KH_OK; }
 kh_status kh_index_profile_enable(kh_index* x, int on) { if (!x) return KH_ERR_INVALID; x->prof = on != 0; if (on) kh_profile_reset(x->t); return kh_profile_enable(x->t, on); }
 kh_status kh_index_profile_dump(kh_index* x, char* buf, uint64_t cap) { if (!x) return KH_ERR_INVALID; return kh_profile_dump(x->t, buf, cap); }
+kh_status kh_index_set_stranded(kh_index* x, int on) {
+  if (!x) return KH_ERR_INVALID;
+  if (x->t->lsize != 0 || x->total != 0) return xfail(x, KH_ERR_INVALID, "kh_index_set_stranded: only on an empty index (kh_index_clear first)");
+  x->stranded = on != 0;
+  return KH_OK;
+}
 
 kh_status kh_index_build(kh_index* x, const void* keys, const void* pos, uint64_t n, kh_mem where) { return index_pairs(x, keys, pos, n, where, false); }
 kh_status kh_index_build_from_sequence(kh_index* x, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where) {
@@ -3879,6 +3907,7 @@ kh_status kh_wide_index_total(const kh_windex* x, uint64_t* out) { return kh_ind
 kh_status kh_wide_index_capacity(const kh_windex* x, uint64_t* out) { return kh_index_capacity(x, out); }
 kh_status kh_wide_index_profile_enable(kh_windex* x, int on) { return kh_index_profile_enable(x, on); }
 kh_status kh_wide_index_profile_dump(kh_windex* x, char* buf, uint64_t cap) { return kh_index_profile_dump(x, buf, cap); }
+kh_status kh_wide_index_set_stranded(kh_windex* x, int on) { return kh_index_set_stranded(x, on); }
 kh_status kh_wide_index_build(kh_windex* x, const void* keys, const void* pos, uint64_t n, kh_mem where) { return kh_index_build(x, keys, pos, n, where); }
 kh_status kh_wide_index_build_from_sequence(kh_windex* x, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where) {
   return index_text(x, seq, n, k, canonical, where, false, false, 0u);
@@ -3983,5 +4012,95 @@ kh_status kh_csr_unpermute(const uint32_t* counts_perm, const uint32_t* pos_perm
   pool_free(device, blk);
   if (e != hipSuccess) return e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP;
   return st;
+}
+
+// ---- strand of window positions (kernel: k_pos_strand in kh_kernels_index.h).  No handle.  Device memory: nothing is allocated and the
+//      call only queues its kernel unless n_invalid is asked for; host memory: text and positions are staged in one pooled block.
+kh_status kh_stamp_strand(const void* text, uint64_t n, uint32_t k, const uint32_t* pos, uint64_t m, uint32_t pos_base, kh_mem where, uint32_t* out,
+                          uint64_t* n_invalid, int device, void* stream_) {
+  kh_table* t = nullptr;
+  if (n_invalid) *n_invalid = 0;
+  if (k < 1 || k > 64 || (n >> 31) || (uint64_t)pos_base + n > (uint64_t(1) << 31)) return KH_ERR_INVALID;
+  if (m == 0) return KH_OK;
+  if (!pos || !out || (!text && n)) return KH_ERR_INVALID;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK(hipSetDevice(device));
+  const bool host = where == KH_MEM_HOST;
+  // [text copy] [positions, stamped in place] (host input) [counter]
+  const size_t sz_text = host ? ((n + 255) & ~size_t(255)) : 0, sz_pos = host ? ((m * 4 + 255) & ~size_t(255)) : 0, sz_cnt = n_invalid ? 256 : 0;
+  char* blk = nullptr;
+  if (sz_text + sz_pos + sz_cnt) HIPCHK(pool_alloc(device, sz_text + sz_pos + sz_cnt, reinterpret_cast<void**>(&blk)));
+  const uint8_t* dtext = static_cast<const uint8_t*>(text);
+  const uint32_t* dpos = pos;
+  uint32_t* dout = out;
+  unsigned long long* dcnt = n_invalid ? reinterpret_cast<unsigned long long*>(blk + sz_text + sz_pos) : nullptr;
+  hipError_t e = hipSuccess;
+  if (host) {
+    if (n) e = hipMemcpyAsync(blk, text, n, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk + sz_text, pos, m * 4, hipMemcpyHostToDevice, stream);
+    dtext = reinterpret_cast<const uint8_t*>(blk); dout = reinterpret_cast<uint32_t*>(blk + sz_text); dpos = dout;
+  }
+  if (e == hipSuccess && dcnt) e = hipMemsetAsync(dcnt, 0, 8, stream);
+  if (e == hipSuccess) {
+    int ncu = 256;
+    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
+    if (ncu <= 0) ncu = 256;
+    hipLaunchKernelGGL((k_pos_strand<true>), dim3(grid_for(m, 256, (uint32_t)ncu * 8)), dim3(256), 0, stream, dtext, n, k, dpos, m, pos_base, dout, dcnt);
+    e = hipGetLastError();
+  }
+  unsigned long long bad = 0;
+  if (e == hipSuccess && dcnt) e = hipMemcpyAsync(&bad, dcnt, 8, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess && host) e = hipMemcpyAsync(out, dout, m * 4, hipMemcpyDeviceToHost, stream);
+  if (blk) {                                   // (staged input or a counter: the block is in use until the stream has drained)
+    const hipError_t e2 = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = e2;
+    pool_free(device, blk);
+  }
+  if (e != hipSuccess) return e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP;
+  if (n_invalid) *n_invalid = bad;
+  return KH_OK;
+}
+// ---- a CSR of hits over stamped positions into flat anchors (kernel: k_anchors_expand).  No handle; device memory: queued only.
+kh_status kh_anchors_from_csr(const uint32_t* qpos, const uint64_t* offsets, uint64_t n, const uint32_t* pos, uint64_t total, kh_mem where,
+                              uint32_t* out_qpos, uint32_t* out_rpos, uint8_t* out_rev, int device, void* stream_) {
+  kh_table* t = nullptr;
+  if (total >> 32) return KH_ERR_INVALID;
+  if (n == 0 || total == 0) return KH_OK;
+  if (!qpos || !offsets || !pos || !out_qpos || !out_rpos || !out_rev) return KH_ERR_INVALID;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK(hipSetDevice(device));
+  const bool host = where == KH_MEM_HOST;
+  char* blk = nullptr;
+  const uint64_t* doff = offsets;
+  const uint32_t *dq = qpos, *dp = pos;
+  uint32_t *oq = out_qpos, *orp = out_rpos; uint8_t* orv = out_rev;
+  hipError_t e = hipSuccess;
+  const size_t b_off = (n + 1) * 8, b_q = (n * 4 + 7) & ~size_t(7), b_p = (total * 4 + 7) & ~size_t(7);
+  if (host) {      // offsets u64[n + 1] | qpos u32[n] | pos u32[total] | out_qpos u32[total] | out_rpos u32[total] | out_rev u8[total]
+    HIPCHK(pool_alloc(device, b_off + b_q + 3 * b_p + total, reinterpret_cast<void**>(&blk)));
+    e = hipMemcpyAsync(blk, offsets, b_off, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk + b_off, qpos, n * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk + b_off + b_q, pos, total * 4, hipMemcpyHostToDevice, stream);
+    doff = reinterpret_cast<const uint64_t*>(blk); dq = reinterpret_cast<const uint32_t*>(blk + b_off); dp = reinterpret_cast<const uint32_t*>(blk + b_off + b_q);
+    oq = reinterpret_cast<uint32_t*>(blk + b_off + b_q + b_p); orp = reinterpret_cast<uint32_t*>(blk + b_off + b_q + 2 * b_p);
+    orv = reinterpret_cast<uint8_t*>(blk + b_off + b_q + 3 * b_p);
+  }
+  if (e == hipSuccess) {
+    int ncu = 256;
+    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
+    if (ncu <= 0) ncu = 256;
+    hipLaunchKernelGGL(k_anchors_expand, dim3(grid_for(total, 256, (uint32_t)ncu * 8)), dim3(256), 0, stream, dq, doff, n, dp, total, oq, orp, orv);
+    e = hipGetLastError();
+  }
+  if (host) {
+    if (e == hipSuccess) e = hipMemcpyAsync(out_qpos, oq, total * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rpos, orp, total * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rev, orv, total, hipMemcpyDeviceToHost, stream);
+    const hipError_t e2 = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = e2;
+    pool_free(device, blk);
+  }
+  if (e != hipSuccess) return e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP;
+  return KH_OK;
 }
 }  // extern "C"

@@ -36,7 +36,8 @@ Batches are torch tensors on the backend's device (int64 keys -- rows of an (n, 
 positions) or numpy arrays, which are copied there; results are tensors on that device.  `backend` objects supply the device-specific
 pieces so that the exchange logic runs on the CPU over gloo in the tests; the product backends are IndexGpuBackend and
 WideIndexGpuBackend.  Not built here: pipelined pieces, kh_shard_plan_* use, a fused text -> pairs-by-rank front end, the
-C++ RCCL library, stitching across ranks' texts, 64-bit positions, strand bits."""
+C++ RCCL library, stitching across ranks' texts, 64-bit positions, a sharded anchors() (a stranded backend stores and returns stamped
+positions; orienting the hits is the caller's, kmerhash_amd.stamp_strand on its query and kmerhash_amd.anchors_from_csr)."""
 import numpy as np
 
 from .dist import DIST_SEED, GpuBackend, GpuSharding, ShardedTable, ShardExchange, ShardPeerError, WideGpuBackend, dist, torch  # noqa: F401
@@ -47,14 +48,23 @@ class IndexGpuBackend(GpuSharding):
     kh_shard_permute"""
 
     def __init__(self, device, k=31, canonical=True, hash="farm", seed=43, w=None, order_hash="murmur", order_seed=42, min_lf=0.35,
-                 max_lf=0.8, dist_hash="murmur3avx64", dist_seed=DIST_SEED, s=None):
-        self.index = self._make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed, s)
+                 max_lf=0.8, dist_hash="murmur3avx64", dist_seed=DIST_SEED, s=None, stranded=False):
+        """stranded: every rank stamps the pairs of ITS text with its pos_base (kmerhash_amd.stamp_strand) before the exchange, so the
+        sharded index stores and find returns stamped positions ((pos_base + p) << 1) | rc(p); pos_base + len(text) <= 2^31"""
+        self.index = self._make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed, s, stranded)
+        self.stranded = bool(stranded)
         super().__init__(device, dist_hash, dist_seed)
 
     @staticmethod
-    def _make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed, s):
+    def _make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed, s, stranded=False):
         from .index import KmerPositionIndex
-        return KmerPositionIndex(k, canonical, hash, min_lf, max_lf, device, seed, w=w, order_hash=order_hash, order_seed=order_seed, s=s)
+        return KmerPositionIndex(k, canonical, hash, min_lf, max_lf, device, seed, w=w, order_hash=order_hash, order_seed=order_seed, s=s,
+                                 stranded=stranded)
+
+    def stamp(self, text, pos, pos_base):
+        """the stamped positions of this rank's pairs (a stranded backend): device text, device positions, this rank's pos_base"""
+        from .kmers import stamp_strand
+        return stamp_strand(self._text(text), pos, self.index.k, pos_base, self.device)
 
     def _text(self, text):
         if isinstance(text, (bytes, bytearray)):
@@ -101,13 +111,14 @@ class WideIndexGpuBackend(IndexGpuBackend):
     key_words = 2
 
     def __init__(self, device, k=63, canonical=True, hash="farm", seed=43, min_lf=0.35, max_lf=0.8, dist_hash="murmur3avx64",
-                 dist_seed=DIST_SEED, s=None, order_hash="murmur", order_seed=42):
-        super().__init__(device, k, canonical, hash, seed, None, order_hash, order_seed, min_lf, max_lf, dist_hash, dist_seed, s)
+                 dist_seed=DIST_SEED, s=None, order_hash="murmur", order_seed=42, stranded=False):
+        super().__init__(device, k, canonical, hash, seed, None, order_hash, order_seed, min_lf, max_lf, dist_hash, dist_seed, s, stranded)
 
     @staticmethod
-    def _make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed, s):
+    def _make_index(k, canonical, hash, min_lf, max_lf, device, seed, w, order_hash, order_seed, s, stranded=False):
         from .index import WideKmerPositionIndex
-        return WideKmerPositionIndex(k, canonical, hash, min_lf, max_lf, device, seed, order_hash=order_hash, order_seed=order_seed, s=s)
+        return WideKmerPositionIndex(k, canonical, hash, min_lf, max_lf, device, seed, order_hash=order_hash, order_seed=order_seed, s=s,
+                                     stranded=stranded)
 
     def text_pairs(self, text, fastq=False):
         from .wide import kmers128_from_sequence
@@ -187,15 +198,24 @@ class ShardedKmerPositionIndex(ShardExchange):
         self._vote(ex, "in the local append: the failing rank's index is empty, the global index is undefined until a collective clear()")
         return x.pk.shape[0]
 
-    def _text_pairs(self, text, pos_base, fastq):
-        """(k-mers, positions + pos_base, None) of this rank's text, or (None, None, the exception)"""
+    def _text_pairs(self, text, pos_base, fastq, query=False):
+        """(k-mers, positions + pos_base, None) of this rank's text, or (None, None, the exception).  A stranded backend stamps the
+        positions instead ((pos_base + p) << 1 | rc(p)), except those of a query text, which stay plain offsets"""
         try:
             pos_base = int(pos_base)
-            if not 0 <= pos_base or pos_base + len(text) > 2 ** 32:
-                raise ValueError("pos_base + len(text) must stay within 2^32 (positions are 32-bit), got %d + %d" % (pos_base, len(text)))
+            stranded = bool(getattr(self.b, "stranded", False)) and not query
+            top = 31 if stranded else 32
+            if not 0 <= pos_base or pos_base + len(text) > 2 ** top:
+                raise ValueError("pos_base + len(text) must stay within 2^%d (%s), got %d + %d"
+                                 % (top, "a stamped position has 31 bits" if stranded else "positions are 32-bit", pos_base, len(text)))
+            if stranded:
+                text = self.b._text(text)                         # (on the device once: sampled and stamped from the same copy)
             with self._span("text_pairs"):
                 km, pos = self.b.text_pairs(text, fastq)
-            if pos_base:
+            if stranded:
+                with self._span("text_pairs"):
+                    pos = self.b.stamp(text, pos, pos_base)
+            elif pos_base:
                 pos = pos + (pos_base - (1 << 32) if pos_base >= (1 << 31) else pos_base)      # (32-bit positions in an int32 tensor)
             return km, pos, None
         except Exception as e:
@@ -232,7 +252,7 @@ class ShardedKmerPositionIndex(ShardExchange):
 
     def find_sequences(self, text):
         """this rank's query text sampled as the index samples, then find: -> (qpos, offsets, positions)"""
-        km, qpos, ex = self._text_pairs(text, 0, False)
+        km, qpos, ex = self._text_pairs(text, 0, False, query=True)
         offsets, positions = self._lookup(km, True, ex)
         return qpos, offsets, positions
 

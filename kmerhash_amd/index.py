@@ -25,13 +25,21 @@ class KmerPositionIndex:
     WORDS = 1                     # 64-bit words per key
 
     def __init__(self, k=31, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0, seed=43,
-                 w=None, order_hash="murmur", order_seed=42, s=None):
+                 w=None, order_hash="murmur", order_seed=42, s=None, stranded=False):
         """w: index the (w,k)-minimizers of a text instead of all its windows (kmerhash_amd.minimizers_from_sequence: of every w
         consecutive windows the one whose k-mer has the smallest order_hash(k-mer, order_seed), about 2 / (w + 1) of them);
         build_sequences, build_fastq, append_sequences, append_fastq and find_sequences then sample with it.  None: every window.
         s: index the closed syncmers instead (kmerhash_amd.syncmers_from_sequence: the k-mers whose smallest s-mer by
         order_hash(s-mer, order_seed) is their first or last, about 2 / (k - s + 1) of them; s = 1..min(k, 32)).  Selection is a function
-        of the k-mer alone, so it works for either key width and sampled(keys) can tell what the index can hold.  Not together with w."""
+        of the k-mer alone, so it works for either key width and sampled(keys) can tell what the index can hold.  Not together with w.
+        stranded: every text form (build_sequences, build_fastq, append_sequences, append_fastq, with or without a sampler) stores
+        STAMPED positions ((pos_base + p) << 1) | rc(p) instead of p -- rc(p) = 1 where the canonical k-mer is the reverse complement of
+        the window at p (kmerhash_amd.stamp_strand) --, find / export / find_sequences return them (kmerhash_amd.unstamp splits them) and
+        anchors(seq) gives oriented hits.  Needs canonical=True; the coordinate space is 2^31; build / append over caller-supplied pairs
+        store what the caller gives."""
+        if stranded and not canonical:
+            raise ValueError("stranded=True needs canonical=True: the strand bit says which strand the canonical k-mer came from")
+        self.stranded = bool(stranded)
         if not 1 <= int(k) <= self.KMAX:
             raise ValueError("k must be 1..%d, got %r" % (self.KMAX, k))
         if s is not None:
@@ -54,6 +62,8 @@ class KmerPositionIndex:
         if st != K.KH_OK:
             self._h = C.c_void_p()
             raise KhError(st, self.PREFIX + "create failed (is a GPU visible and the HIP library built?)")
+        if self.stranded:
+            self._chk(self._fn("set_stranded")(self._h, 1))
 
     # -- plumbing --------------------------------------------------------------------------------
     def _fn(self, name):
@@ -135,10 +145,10 @@ class KmerPositionIndex:
         self._chk(self._fn("append")(self._h, kb.ptr, pb.ptr, n, kb.where))
         return n
 
-    @staticmethod
-    def _base(pos_base):
-        if not 0 <= int(pos_base) < 2 ** 32:
-            raise ValueError("pos_base must be 0..2^32-1, got %r" % (pos_base,))
+    def _base(self, pos_base):
+        top = 31 if self.stranded else 32                     # (a stamped position has 31 bits)
+        if not 0 <= int(pos_base) < 2 ** top:
+            raise ValueError("pos_base must be 0..2^%d-1, got %r" % (top, pos_base))
         return int(pos_base)
 
     def append_sequences(self, seq, pos_base=0):
@@ -246,18 +256,38 @@ class KmerPositionIndex:
         """the index's own sampling of a query text, then find: -> (qpos, offsets, positions).  The k-mers of `seq` are taken with
         the index's k, canonical flag and -- when it was made with w or s -- that sampler, order hash and order seed (all windows otherwise);
         qpos[i] is the byte offset in `seq` of query k-mer i and positions[offsets[i]:offsets[i + 1]] are its occurrences in the index.
-        Two device calls composed here; numpy in, numpy out, CUDA tensor in, tensors out."""
+        Two device calls composed here; numpy in, numpy out, CUDA tensor in, tensors out.  On a stranded index the positions are the
+        stamped values (qpos stays a plain offset); anchors(seq) returns them oriented."""
+        km, qpos = self._sample(seq)
+        offsets, positions = self.find(km)
+        return qpos, offsets, positions
+
+    def _sample(self, seq):
+        """(k-mers, window offsets) of a query text, sampled as the index samples"""
         from .kmers import kmers_from_sequence, minimizers_from_sequence
         if self.WORDS != 1 and self.s is None:
             raise ValueError("find_sequences is not supported for 16-byte k-mers without s")
         if self.s is not None:
-            km, qpos = self._syncmers(seq)
-        elif self.w is None:
-            km, qpos = kmers_from_sequence(seq, self.k, self.canonical, self.device, with_positions=True)
-        else:
-            km, qpos = minimizers_from_sequence(seq, self.k, self.w, self.canonical, self.order_hash, self.order_seed, self.device)
+            return self._syncmers(seq)
+        if self.w is None:
+            return kmers_from_sequence(seq, self.k, self.canonical, self.device, with_positions=True)
+        return minimizers_from_sequence(seq, self.k, self.w, self.canonical, self.order_hash, self.order_seed, self.device)
+
+    def anchors(self, seq):
+        """oriented hits of a query text on a stranded index -> (qpos, rpos, rev), one entry per hit, in query order and then ascending
+        rpos: the query is sampled as find_sequences samples it, its positions are stamped over the query text, looked up, and the CSR
+        is expanded on the device (kh_anchors_from_csr).  rev[j] == 0: the k bases at rpos[j] in the indexed text equal those at qpos[j]
+        in `seq`; rev[j] == 1: they are their reverse complement.  numpy in, numpy out (uint32, uint32, uint8); a CUDA tensor in, tensors
+        out (int32, int32, uint8) on the current stream.  Chaining is the caller's."""
+        from .kmers import anchors_from_csr, stamp_strand
+        if not self.stranded:
+            raise ValueError("anchors() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        if isinstance(seq, (bytes, bytearray)):
+            seq = np.frombuffer(seq, dtype=np.uint8)
+        km, qpos = self._sample(seq)
+        sq = stamp_strand(seq, qpos, self.k, 0, self.device)
         offsets, positions = self.find(km)
-        return qpos, offsets, positions
+        return anchors_from_csr(sq, offsets, positions, self.device)
 
     def _syncmers(self, seq, fastq=False):
         """the closed syncmers of a text under the index's own parameters"""
@@ -303,8 +333,9 @@ class WideKmerPositionIndex(KmerPositionIndex):
     WORDS = 2
 
     def __init__(self, k=63, canonical=True, hash="farm", min_load_factor=0.35, max_load_factor=0.8, device=0, seed=43, w=None,
-                 order_hash="murmur", order_seed=42, s=None):
-        super().__init__(k, canonical, hash, min_load_factor, max_load_factor, device, seed, w=w, order_hash=order_hash, order_seed=order_seed, s=s)
+                 order_hash="murmur", order_seed=42, s=None, stranded=False):
+        super().__init__(k, canonical, hash, min_load_factor, max_load_factor, device, seed, w=w, order_hash=order_hash, order_seed=order_seed, s=s,
+                         stranded=stranded)
 
     def _syncmers(self, seq, fastq=False):
         from .wide import syncmers128_from_sequence

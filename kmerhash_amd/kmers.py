@@ -186,6 +186,72 @@ def is_syncmer(keys, k=15, s=11, canonical=True, order_hash="murmur", order_seed
     return _syncmer_mask("kh_syncmer_mask", kb, kb.n, k, s, canonical, order_hash, order_seed, device)
 
 
+POS_INVALID = 0xFFFFFFFF          # KH_POS_INVALID: the stamp of a window that is not k bases inside the text
+
+
+def stamp_strand(text, pos, k, pos_base=0, device=0, count_invalid=False):
+    """window positions -> stamped positions ((pos_base + p) << 1) | rc(p), where rc(p) = 1 iff the reverse complement of the k bases at
+    text[p:p + k] is strictly smaller than the window: the case in which a canonical front end emitted the reverse complement
+    (kh_stamp_strand in include/kmerhash_amd.h; a palindrome has rc = 0).  A window that passes the end of the text or holds a byte
+    that is no base gives POS_INVALID.  Positions in any order, repeats allowed; k = 1..64; pos_base + len(text) <= 2^31.
+    numpy uint8 / uint32 in, numpy uint32 out; CUDA tensors in (uint8 text, int32 positions), an int32 tensor out, queued on the current
+    stream.  count_invalid: -> (stamped, number of POS_INVALID written), which waits for the stream."""
+    import ctypes as C
+    from . import _capi as K
+    from .table import _Buf, KhError
+    if isinstance(text, (bytes, bytearray)):
+        text = np.frombuffer(text, dtype=np.uint8)
+    tb, pb = _Buf(text, np.uint8, 1), _Buf(pos, np.uint32, 4)
+    if tb.where != pb.where:
+        raise ValueError("text and positions must live in the same memory")
+    if not 1 <= int(k) <= 64:
+        raise ValueError("k must be 1..64, got %r" % (k,))
+    if not 0 <= int(pos_base) or int(pos_base) + tb.n > 2 ** 31:
+        raise ValueError("pos_base + len(text) must stay within 2^31 (a stamped position has 31 bits), got %r + %d" % (pos_base, tb.n))
+    if pb.where == K.KH_MEM_DEVICE:
+        out = torch.empty(pb.n, dtype=torch.int32, device=pb.device)
+        optr, stream = out.data_ptr(), torch.cuda.current_stream(device).cuda_stream
+    else:
+        out = np.zeros(pb.n, dtype=np.uint32)
+        optr, stream = out.ctypes.data, None
+    bad = C.c_uint64()
+    st = K.lib().kh_stamp_strand(tb.ptr, tb.n, int(k), pb.ptr, pb.n, int(pos_base), pb.where, optr, C.byref(bad) if count_invalid else None, device, stream)
+    if st != K.KH_OK:
+        raise KhError(st, "kh_stamp_strand")
+    return (out, bad.value) if count_invalid else out
+
+
+def unstamp(v):
+    """stamped positions -> (positions, strand bits): v >> 1 and v & 1 (numpy uint32 or int32 CUDA tensors holding uint32; POS_INVALID is
+    the caller's to filter)"""
+    if torch is not None and isinstance(v, torch.Tensor):
+        return (v >> 1) & 0x7FFFFFFF, v & 1
+    v = np.asarray(v, dtype=np.uint32)
+    return v >> np.uint32(1), v & np.uint32(1)
+
+
+def anchors_from_csr(qpos, offsets, pos, device=0):
+    """the CSR of a find over a stranded index (stamped query positions, offsets, stamped hits) -> (qpos, rpos, rev) with one entry per hit
+    (kh_anchors_from_csr): rev = 0 where the reference window equals the query window, 1 where it is its reverse complement"""
+    from . import _capi as K
+    from .table import _Buf, KhError
+    qb, ob, pb = _Buf(qpos, np.uint32, 4), _Buf(offsets, np.uint64, 8), _Buf(pos, np.uint32, 4)
+    if not qb.where == ob.where == pb.where or ob.n != qb.n + 1:
+        raise ValueError("qpos, offsets (len(qpos) + 1 entries) and pos must live in the same memory")
+    total = pb.n
+    if qb.where == K.KH_MEM_DEVICE:
+        oq, orp = (torch.empty(total, dtype=torch.int32, device=pb.device) for _ in range(2))
+        orv = torch.empty(total, dtype=torch.uint8, device=pb.device)
+        ptrs, stream = (oq.data_ptr(), orp.data_ptr(), orv.data_ptr()), torch.cuda.current_stream(device).cuda_stream
+    else:
+        oq, orp, orv = np.zeros(total, dtype=np.uint32), np.zeros(total, dtype=np.uint32), np.zeros(total, dtype=np.uint8)
+        ptrs, stream = (oq.ctypes.data, orp.ctypes.data, orv.ctypes.data), None
+    st = K.lib().kh_anchors_from_csr(qb.ptr, ob.ptr, qb.n, pb.ptr, total, qb.where, *ptrs, device, stream)
+    if st != K.KH_OK:
+        raise KhError(st, "kh_anchors_from_csr")
+    return oq, orp, orv
+
+
 class KmerCounter:
     """counting index: k-mer -> number of occurrences (Reducer = std::plus, value 1 per occurrence)"""
 
