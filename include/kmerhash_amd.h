@@ -708,6 +708,37 @@ kh_status kh_anchors_from_csr(const uint32_t* qpos /*[h|d] u32[n]*/, const uint6
                               const uint32_t* pos /*[h|d] u32[total]*/, uint64_t total, kh_mem where, uint32_t* out_qpos /*[h|d] u32[total]*/,
                               uint32_t* out_rpos /*[h|d] u32[total]*/, uint8_t* out_rev /*[h|d] u8[total]*/, int device, void* hip_stream);
 
+/* ---- collinear chains from anchors.  kh_chain_anchors takes a flat anchor list (qpos, rpos, rev: what kh_anchors_from_csr writes) and a
+ *      CSR of SEGMENTS -- segment s is the anchors [seg_offsets[s], seg_offsets[s + 1]), one read; NULL: one segment [0, m) -- and returns
+ *      the chaining DP per anchor, a partition of the anchors into disjoint chains and a compact table of the chains that pass a filter.
+ *      Chains never cross a segment boundary.  No order of the anchors inside a segment is assumed (query order makes good chains).
+ *      DP, inside a segment [a, b), i ascending.  Only bit 0 of rev is read.  An anchor with qpos >= 2^31 or rpos >= 2^31 (KH_POS_INVALID)
+ *      has f = k, pred = -1 and is nobody's candidate.  Candidates of i are the j with max(a, i - lookback) <= j < i, rev[j] == rev[i],
+ *      dq = q_i - q_j in 1..max_gap, dr in 1..max_gap (dr = r_i - r_j for rev 0, r_j - r_i for rev 1) and dd = |dq - dr| <= band.
+ *      cand = f(j) + min(dq, dr, k) - cost(dd), cost(0) = 0, cost(dd) = ((k * dd) >> 7) + (floor(log2 dd) >> 1).  f(i) = max(k, max cand);
+ *      pred(i) = the candidate of greatest cand if that cand > k (ties: the largest j), else -1.
+ *      Chains.  g(i) = max(f(i), g(c) over the c with pred(c) == i); best_child(j) = the child of greatest g (ties: the smallest index).
+ *      Anchor i STARTS a chain iff pred(i) == -1 or best_child(pred(i)) != i, else it belongs to the chain of pred(i): every anchor lies in
+ *      exactly one chain and a chain is a path of pred links.  For a chain with start s and last anchor l: count = its anchors, score =
+ *      f(l) - (pred(s) == -1 ? 0 : f(pred(s))).  It is KEPT iff score >= min_score and count >= min_count; kept chains are numbered from 0
+ *      in ascending order of their start anchor.
+ *      Outputs: out_score[i] = f(i), out_pred[i] = pred(i), out_chain[i] = the number of i's chain or -1 when it is not kept; row c of the
+ *      table: c_first, c_last (start and last anchor), c_count, c_score.  c_* all NULL: per-anchor outputs and the count only.
+ *      *n_chains = number of kept chains; the call waits for the stream to learn it (device memory: every kernel is queued on hip_stream
+ *      and that wait is the only one).  More kept chains than cap_chains (with a table): KH_ERR_INVALID, *n_chains set, per-anchor outputs
+ *      written, c_* untouched -- the cap_out convention of kh_index_find.  All arrays live in the memory `where` names.
+ *      KH_ERR_INVALID before anything is allocated, read or written: k or lookback outside 1..64, max_gap outside 1..2^31-1, band >= 2^31,
+ *      m > 2^24 (scores stay within 2^30; batch over reads), some but not all of c_* NULL, and while m > 0 a null input or per-anchor
+ *      output, n_seg > m + 2^24 or n_seg == 0 with seg_offsets given.  m == 0: KH_OK, *n_chains = 0.  seg_offsets that do not ascend from 0
+ *      to m are seen on the device only: every segment is clamped to [0, m) so nothing outside the arrays is touched, and the call
+ *      returns KH_ERR_INVALID with *n_chains = 0 and unspecified output contents. */
+kh_status kh_chain_anchors(const uint32_t* qpos /*[h|d] u32[m]*/, const uint32_t* rpos /*[h|d] u32[m]*/, const uint8_t* rev /*[h|d] u8[m]*/, uint64_t m,
+                           const uint64_t* seg_offsets /*[h|d] u64[n_seg+1] or NULL*/, uint64_t n_seg, uint32_t k /*1..64*/, uint32_t lookback /*1..64*/,
+                           uint32_t max_gap /*1..2^31-1*/, uint32_t band /*0..2^31-1*/, int32_t min_score, uint32_t min_count, kh_mem where,
+                           int32_t* out_score /*[m]*/, int32_t* out_pred /*[m], -1 = none*/, int32_t* out_chain /*[m], kept-chain number or -1*/,
+                           uint32_t* c_first, uint32_t* c_last, uint32_t* c_count, int32_t* c_score /* each [cap_chains], or all NULL */,
+                           uint64_t cap_chains, uint64_t* n_chains, int device, void* hip_stream);
+
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);
 

@@ -82,6 +82,8 @@ SYMBOLS = [
     "kh_wide_index_build_from_syncmers", "kh_wide_index_append_from_syncmers",
     # strand of a window position, stranded indexes (a strand bit per occurrence), a CSR of hits into flat anchors
     "kh_stamp_strand", "kh_index_set_stranded", "kh_wide_index_set_stranded", "kh_anchors_from_csr",
+    # collinear chains per segment (read) from flat anchors
+    "kh_chain_anchors",
 ]
 
 _lib = None
@@ -259,6 +261,7 @@ def lib():
     L.kh_index_set_stranded.argtypes = [vp, i32]
     L.kh_wide_index_set_stranded.argtypes = [vp, i32]
     L.kh_anchors_from_csr.argtypes = [vp, vp, u64, vp, u64, i32, vp, vp, vp, i32, vp]
+    L.kh_chain_anchors.argtypes = [vp, vp, vp, u64, vp, u64, u32, u32, u32, u32, i32, u32, i32, vp, vp, vp, vp, vp, vp, vp, u64, pu64, i32, vp]
     for s in SYMBOLS:
         if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error", "kh_wide_index_last_error"):
             getattr(L, s).restype = i32

@@ -14,12 +14,14 @@
 //   index   : kh_index, all occurrences per k-mer: counting insert -> slot-order ranks + CSR offsets -> scatter -> segment sort (kh_kernels_index.h).
 //             kh_windex: the same host code on a wide table (kh_index::kw == 2) and the kernels that touch a 32-byte slot (kh_kernels_index_wide.h).
 //   csr     : kh_csr_unpermute, a CSR that arrives in a permuted order back into query order: the index's scans and gather around one scatter (kh_kernels_csr.h).
+//   chain   : kh_chain_anchors, collinear chains per segment from flat anchors: a wavefront per segment, the last 64 anchors in registers (kh_kernels_chain.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
 #include "kh_kernels_values.h"
 #include "kh_kernels_index.h"
 #include "kh_kernels_index_wide.h"
 #include "kh_kernels_csr.h"
+#include "kh_kernels_chain.h"
 #include "kh_part_sizing.h"
 #include "../../include/kmerhash_amd.h"
 
@@ -4102,5 +4104,101 @@ kh_status kh_anchors_from_csr(const uint32_t* qpos, const uint64_t* offsets, uin
   }
   if (e != hipSuccess) return e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP;
   return KH_OK;
+}
+// ---- collinear chains per segment from flat anchors (kernels: kh_kernels_chain.h).  No handle; one pooled block holds the scratch (and
+//      the staged arrays of a host call); every kernel is queued on the caller's stream and the one host wait is the one for *n_chains.
+kh_status kh_chain_anchors(const uint32_t* qpos, const uint32_t* rpos, const uint8_t* rev, uint64_t m, const uint64_t* seg_offsets, uint64_t n_seg, uint32_t k,
+                           uint32_t lookback, uint32_t max_gap, uint32_t band, int32_t min_score, uint32_t min_count, kh_mem where, int32_t* out_score,
+                           int32_t* out_pred, int32_t* out_chain, uint32_t* c_first, uint32_t* c_last, uint32_t* c_count, int32_t* c_score, uint64_t cap_chains,
+                           uint64_t* n_chains, int device, void* stream_) {
+  kh_table* t = nullptr;
+  const int n_tab = (c_first != nullptr) + (c_last != nullptr) + (c_count != nullptr) + (c_score != nullptr);
+  if (k < 1 || k > 64 || lookback < 1 || lookback > 64 || max_gap < 1 || (max_gap >> 31) || (band >> 31)) return KH_ERR_INVALID;
+  if (m > (uint64_t(1) << 24) || (where != KH_MEM_HOST && where != KH_MEM_DEVICE) || (n_tab != 0 && n_tab != 4)) return KH_ERR_INVALID;
+  if (seg_offsets && (n_seg > m + (uint64_t(1) << 24) || (n_seg == 0 && m))) return KH_ERR_INVALID;
+  if (m && (!qpos || !rpos || !rev || !out_score || !out_pred || !out_chain)) return KH_ERR_INVALID;
+  if (m == 0) { if (n_chains) *n_chains = 0; return KH_OK; }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK(hipSetDevice(device));
+  const bool host = where == KH_MEM_HOST, table = n_tab == 4;
+  const uint64_t nst = (m + KI_SCAN_TILE - 1) / KI_SCAN_TILE, tab = table ? std::min<uint64_t>(cap_chains, m) : 0;
+  auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+  // scratch: best child / flags i32[m] | count u32[m] | last u32[m] | bad u32 (these three zeroed) | chain numbers u32[m + 1] | tile sums u64[nst + 1]
+  const size_t b_a = up(m * 4), b_num = up((m + 1) * 4), b_sums = up((nst + 1) * 8), b_zero = 2 * b_a + 256;
+  // host call: qpos | rpos | rev | seg | score | pred | chain | 4 table columns
+  const size_t b_rev = host ? up(m) : 0, b_seg = host && seg_offsets ? up((n_seg + 1) * 8) : 0, b_col = host ? up(tab * 4) : 0;
+  const size_t b_scratch = b_a + b_zero + b_num + b_sums, b_stage = host ? 5 * b_a + b_rev + b_seg + 4 * b_col : 0;
+  char* blk = nullptr;
+  HIPCHK(pool_alloc(device, b_scratch + b_stage, reinterpret_cast<void**>(&blk)));
+  int32_t* bc = reinterpret_cast<int32_t*>(blk);
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(blk + b_a);
+  uint32_t* last = reinterpret_cast<uint32_t*>(blk + 2 * b_a);
+  uint32_t* bad = reinterpret_cast<uint32_t*>(blk + 3 * b_a);
+  uint32_t* num = reinterpret_cast<uint32_t*>(blk + b_a + b_zero);
+  unsigned long long* ssums = reinterpret_cast<unsigned long long*>(blk + b_a + b_zero + b_num);
+  const uint32_t *dq = qpos, *dr = rpos; const uint8_t* dv = rev; const uint64_t* dseg = seg_offsets;
+  int32_t *df = out_score, *dp = out_pred, *dc = out_chain, *t_score = c_score;
+  uint32_t *t_first = c_first, *t_last = c_last, *t_count = c_count;
+  hipError_t e = hipSuccess;
+  if (host) {
+    char* s = blk + b_scratch;
+    e = hipMemcpyAsync(s, qpos, m * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s + b_a, rpos, m * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s + 2 * b_a, rev, m, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && seg_offsets) e = hipMemcpyAsync(s + 2 * b_a + b_rev, seg_offsets, (n_seg + 1) * 8, hipMemcpyHostToDevice, stream);
+    dq = reinterpret_cast<const uint32_t*>(s); dr = reinterpret_cast<const uint32_t*>(s + b_a); dv = reinterpret_cast<const uint8_t*>(s + 2 * b_a);
+    if (seg_offsets) dseg = reinterpret_cast<const uint64_t*>(s + 2 * b_a + b_rev);
+    char* o = s + 2 * b_a + b_rev + b_seg;
+    df = reinterpret_cast<int32_t*>(o); dp = reinterpret_cast<int32_t*>(o + b_a); dc = reinterpret_cast<int32_t*>(o + 2 * b_a);
+    if (table) {
+      t_first = reinterpret_cast<uint32_t*>(o + 3 * b_a); t_last = reinterpret_cast<uint32_t*>(o + 3 * b_a + b_col);
+      t_count = reinterpret_cast<uint32_t*>(o + 3 * b_a + 2 * b_col); t_score = reinterpret_cast<int32_t*>(o + 3 * b_a + 3 * b_col);
+    }
+  }
+  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, b_zero, stream);
+  unsigned long long total = 0;
+  uint32_t hbad = 0;
+  if (e == hipSuccess) {
+    int ncu = 256;
+    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
+    if (ncu <= 0) ncu = 256;
+    const uint32_t m32 = (uint32_t)m, ns32 = (uint32_t)n_seg;
+    const uint32_t gseg = grid_for(dseg ? n_seg : 1, KCH_WAVES, (uint32_t)ncu * 8), gflat = grid_for(m, 256, (uint32_t)ncu * 8);
+    const KchParams P{k, lookback, max_gap, band};
+    hipLaunchKernelGGL(k_chain_dp, dim3(gseg), dim3(KCH_THREADS), 0, stream, dq, dr, dv, m32, dseg, ns32, P, df, dp, bad);
+    hipLaunchKernelGGL(k_chain_link, dim3(gseg), dim3(KCH_THREADS), 0, stream, (const int32_t*)df, (const int32_t*)dp, m32, dseg, ns32, bc, dc, cnt, last);
+    uint32_t* flag = reinterpret_cast<uint32_t*>(bc);          // (the best children are done with)
+    hipLaunchKernelGGL((k_chain_emit<0>), dim3(gflat), dim3(256), 0, stream, (const int32_t*)df, (const int32_t*)dp, dc, m32, (const uint32_t*)cnt, (const uint32_t*)last,
+                       min_score, min_count, flag, (const uint32_t*)num, (const unsigned long long*)(ssums + nst), (const uint32_t*)bad, t_first, t_last, t_count, t_score, tab);
+    hipLaunchKernelGGL(k_index_tile_sums, dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, (const uint32_t*)flag, m, ssums);
+    hipLaunchKernelGGL(k_index_scan_sums, dim3(1), dim3(KI_SUMS_THREADS), 0, stream, ssums, nst);
+    hipLaunchKernelGGL((k_index_scan_apply<uint32_t>), dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, (const uint32_t*)flag, m, (const unsigned long long*)ssums, num);
+    hipLaunchKernelGGL((k_chain_emit<1>), dim3(gflat), dim3(256), 0, stream, (const int32_t*)df, (const int32_t*)dp, dc, m32, (const uint32_t*)cnt, (const uint32_t*)last,
+                       min_score, min_count, flag, (const uint32_t*)num, (const unsigned long long*)(ssums + nst), (const uint32_t*)bad, t_first, t_last, t_count, t_score, tab);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, ssums + nst, 8, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, stream);
+  }
+  { const hipError_t e2 = hipStreamSynchronize(stream); if (e == hipSuccess) e = e2; }
+  kh_status st = KH_OK;
+  if (e == hipSuccess && hbad) { st = KH_ERR_INVALID; total = 0; }
+  if (e == hipSuccess && !hbad && table && total > cap_chains) st = KH_ERR_INVALID;
+  if (e == hipSuccess && host && !hbad) {
+    e = hipMemcpyAsync(out_score, df, m * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_pred, dp, m * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_chain, dc, m * 4, hipMemcpyDeviceToHost, stream);
+    if (table && st == KH_OK && total) {
+      if (e == hipSuccess) e = hipMemcpyAsync(c_first, t_first, total * 4, hipMemcpyDeviceToHost, stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(c_last, t_last, total * 4, hipMemcpyDeviceToHost, stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(c_count, t_count, total * 4, hipMemcpyDeviceToHost, stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(c_score, t_score, total * 4, hipMemcpyDeviceToHost, stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = e2;
+  }
+  pool_free(device, blk);
+  if (e != hipSuccess) return e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP;
+  if (n_chains) *n_chains = total;
+  return st;
 }
 }  // extern "C"

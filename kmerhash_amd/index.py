@@ -5,6 +5,7 @@ reference tree): built from (k-mer, position) pairs or straight from sequence / 
 (append*, erase, erase_counts, drop_above).
 numpy arrays are host buffers, torch CUDA tensors device buffers, as in kmerhash_amd.table; results come back in the same kind of
 container.  There is no CPU fallback."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -16,6 +17,8 @@ from .table import _Buf, _hash_id, torch
 # entries of positions a workgroup of the build sorts in LDS at a time (KI_SORT_TILE in csrc/kh_kernels_index.h): a segment that crosses
 # a multiple of it takes the radix path
 SORT_TILE = 4096
+
+ChainTable = collections.namedtuple("ChainTable", "seg rev q_start q_end r_start r_end count score anchors chain")
 
 
 class KmerPositionIndex:
@@ -278,7 +281,7 @@ class KmerPositionIndex:
         rpos: the query is sampled as find_sequences samples it, its positions are stamped over the query text, looked up, and the CSR
         is expanded on the device (kh_anchors_from_csr).  rev[j] == 0: the k bases at rpos[j] in the indexed text equal those at qpos[j]
         in `seq`; rev[j] == 1: they are their reverse complement.  numpy in, numpy out (uint32, uint32, uint8); a CUDA tensor in, tensors
-        out (int32, int32, uint8) on the current stream.  Chaining is the caller's."""
+        out (int32, int32, uint8) on the current stream.  chains(seq) chains them per read."""
         from .kmers import anchors_from_csr, stamp_strand
         if not self.stranded:
             raise ValueError("anchors() needs an index made with stranded=True: without the strand bit a hit has no orientation")
@@ -288,6 +291,43 @@ class KmerPositionIndex:
         sq = stamp_strand(seq, qpos, self.k, 0, self.device)
         offsets, positions = self.find(km)
         return anchors_from_csr(sq, offsets, positions, self.device)
+
+    def chains(self, seq, read_starts=None, **params):
+        """candidate loci of the reads in a query text on a stranded index: anchors(seq), then collinear chains per read on the device
+        (kmers.chain_anchors with the index's k; params: lookback, max_gap, band, min_score, min_count).  read_starts: ascending byte
+        offsets of the reads in `seq`, the first one 0 (None: one read); a chain never holds anchors of two reads.
+        -> ChainTable(seg, rev, q_start, q_end, r_start, r_end, count, score, anchors, chain): one row per kept chain -- its read, its
+        strand, the query interval [q_start, q_end) and the reference interval [r_start, r_end) its first and last anchor span, its
+        number of anchors and its score -- then anchors = (qpos, rpos, rev) as anchors() returns them and chain[j] = the row of anchor
+        j or -1.  numpy in, numpy out; a CUDA tensor in, tensors out on the current stream."""
+        from .kmers import chain_anchors
+        if not self.stranded:
+            raise ValueError("chains() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        q, r, v = self.anchors(seq)
+        dev = torch is not None and isinstance(q, torch.Tensor)
+        if read_starts is None:
+            seg, rs = None, None
+        else:
+            rs = np.asarray(read_starts.cpu() if torch is not None and isinstance(read_starts, torch.Tensor) else read_starts, dtype=np.int64).ravel()
+            if rs.size == 0 or rs[0] != 0 or (np.diff(rs) < 0).any():
+                raise ValueError("read_starts must be ascending byte offsets of the reads in seq, the first one 0")
+            # read s owns the anchors with read_starts[s] <= qpos < read_starts[s + 1]; qpos ascends
+            if dev:
+                seg = torch.cat([torch.searchsorted(q.long(), torch.from_numpy(rs).to(q.device)), torch.tensor([q.numel()], dtype=torch.int64, device=q.device)])
+            else:
+                seg = np.concatenate([np.searchsorted(q, rs, side="left"), [len(q)]]).astype(np.uint64)
+        c = chain_anchors(q, r, v, self.k, seg, device=self.device, **params)
+        if dev:
+            first, last = c.first.long(), c.last.long()
+            qf, ql, rf, rl = q[first], q[last], r[first], r[last]
+            sg = torch.zeros_like(c.first) if seg is None else (torch.searchsorted(seg, first, right=True) - 1).int()
+            rows = (sg, v[first], qf, ql + self.k, torch.minimum(rf, rl), torch.maximum(rf, rl) + self.k, c.count, c.cscore)
+        else:
+            first, last = c.first.astype(np.int64), c.last.astype(np.int64)
+            qf, ql, rf, rl = q[first], q[last], r[first], r[last]
+            sg = np.zeros(len(first), dtype=np.uint32) if seg is None else (np.searchsorted(seg, first.astype(np.uint64), side="right") - 1).astype(np.uint32)
+            rows = (sg, v[first], qf, ql + np.uint32(self.k), np.minimum(rf, rl), np.maximum(rf, rl) + np.uint32(self.k), c.count, c.cscore)
+        return ChainTable(*rows, (q, r, v), c.chain)
 
     def _syncmers(self, seq, fastq=False):
         """the closed syncmers of a text under the index's own parameters"""

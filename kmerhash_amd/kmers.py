@@ -4,6 +4,8 @@ FASTQ/FASTA -> k-mers -> counting insert -> write (k-mer, count) tuples) on the 
 The reference takes its parser and k-mer type from kmerind (absent), so the k-mer definition here is this library's
 (see kh_kmers_from_sequence in include/kmerhash_amd.h): 2-bit packed, first base most significant, A=0 C=1 G=2 T=3,
 windows containing any other byte are skipped, canonical = min(k-mer, reverse complement)."""
+import collections
+
 import numpy as np
 
 from .table import hashmap_robinhood_doubling, torch
@@ -250,6 +252,67 @@ def anchors_from_csr(qpos, offsets, pos, device=0):
     if st != K.KH_OK:
         raise KhError(st, "kh_anchors_from_csr")
     return oq, orp, orv
+
+
+Chains = collections.namedtuple("Chains", "score pred chain first last count cscore")
+
+
+def _check_chain_params(k, lookback, max_gap, band, min_score, min_count):
+    """the refusals of kh_chain_anchors that depend on the parameters alone, as ValueError"""
+    if not 1 <= int(k) <= 64:
+        raise ValueError("k must be 1..64, got %r" % (k,))
+    if not 1 <= int(lookback) <= 64:
+        raise ValueError("lookback must be 1..64 (the candidates of an anchor are scored by one wavefront), got %r" % (lookback,))
+    if not 1 <= int(max_gap) <= 2 ** 31 - 1:
+        raise ValueError("max_gap must be 1..2^31-1, got %r" % (max_gap,))
+    if not 0 <= int(band) <= 2 ** 31 - 1:
+        raise ValueError("band must be 0..2^31-1, got %r" % (band,))
+    if not -2 ** 31 <= int(min_score) < 2 ** 31:
+        raise ValueError("min_score must fit a signed 32-bit integer, got %r" % (min_score,))
+    if not 0 <= int(min_count) < 2 ** 32:
+        raise ValueError("min_count must be 0..2^32-1, got %r" % (min_count,))
+
+
+def chain_anchors(qpos, rpos, rev, k, seg_offsets=None, lookback=64, max_gap=5000, band=500, min_score=40, min_count=3, device=0):
+    """collinear chains of oriented anchors (kh_chain_anchors in include/kmerhash_amd.h, which holds the definition): per segment -- the
+    anchors [seg_offsets[s], seg_offsets[s + 1]), one read; None: all of them -- a banded DP over the `lookback` anchors before each one,
+    a partition of the anchors into disjoint chains and the chains with score >= min_score and count >= min_count, numbered by their
+    first anchor.  -> Chains(score, pred, chain, first, last, count, cscore): f(i), pred(i) (-1: none) and the chain number (-1: not
+    kept) per anchor, then first / last anchor, anchor count and score per kept chain.  numpy in (uint32, uint32, uint8, uint64), numpy
+    out; CUDA tensors in (int32, int32, uint8, int64), tensors out on the current stream.  At most 2^24 anchors per call."""
+    import ctypes as C
+    from . import _capi as K
+    from .table import _Buf, KhError
+    _check_chain_params(k, lookback, max_gap, band, min_score, min_count)
+    qb, rb, vb = _Buf(qpos, np.uint32, 4), _Buf(rpos, np.uint32, 4), _Buf(rev, np.uint8, 1)
+    sb = None if seg_offsets is None else _Buf(seg_offsets, np.uint64, 8)
+    if not qb.where == rb.where == vb.where or (sb is not None and sb.where != qb.where):
+        raise ValueError("qpos, rpos, rev and seg_offsets must live in the same memory")
+    m = qb.n
+    if rb.n != m or vb.n != m:
+        raise ValueError("qpos, rpos and rev must have one entry per anchor, got %d, %d and %d" % (m, rb.n, vb.n))
+    if m > 2 ** 24:
+        raise ValueError("at most 2^24 anchors per call (batch over reads), got %d" % m)
+    if sb is not None and (sb.n < 1 or sb.n - 1 > m + 2 ** 24 or (sb.n == 1 and m)):
+        raise ValueError("seg_offsets must hold n_seg + 1 entries ascending from 0 to the number of anchors, got %d entries for %d anchors" % (sb.n, m))
+    cap = m // max(1, int(min_count))          # kept chains are disjoint and hold min_count anchors each
+    if qb.where == K.KH_MEM_DEVICE:
+        per = [torch.empty(m, dtype=torch.int32, device=qb.device) for _ in range(3)]
+        tab = [torch.empty(cap, dtype=torch.int32, device=qb.device) for _ in range(4)]
+        ptrs, stream = [t.data_ptr() if t.numel() else None for t in per + tab], torch.cuda.current_stream(device).cuda_stream
+    else:
+        per = [np.zeros(m, dtype=np.int32) for _ in range(3)]
+        tab = [np.zeros(cap, dtype=np.uint32) for _ in range(3)] + [np.zeros(cap, dtype=np.int32)]
+        ptrs, stream = [a.ctypes.data if a.size else None for a in per + tab], None
+    if cap == 0:
+        ptrs[3:] = [None] * 4
+    n = C.c_uint64()
+    st = K.lib().kh_chain_anchors(qb.ptr if m else None, rb.ptr if m else None, vb.ptr if m else None, m, None if sb is None else sb.ptr,
+                                  0 if sb is None else sb.n - 1, int(k), int(lookback), int(max_gap), int(band), int(min_score), int(min_count), qb.where,
+                                  *ptrs, cap, C.byref(n), device, stream)
+    if st != K.KH_OK:
+        raise KhError(st, "kh_chain_anchors" + (": seg_offsets do not ascend from 0 to the number of anchors" if st == K.KH_ERR_INVALID else ""))
+    return Chains(*per, *(t[:n.value] for t in tab))
 
 
 class KmerCounter:

@@ -1,0 +1,68 @@
+"""Compiler report of the kernels kh_chain_anchors adds (CPU test over kmerhash_amd/kernel_resources.json): k_chain_dp and k_chain_link
+are in the library once and k_chain_emit in its two phases, all keep their registers in registers, use no LDS -- the ring of the last
+64 anchors lives in one register per lane and field -- and run at the full eight waves per SIMD, as DESIGN.md §3 states; the index
+kernels they sit beside are still there in their old numbers."""
+import json
+import os
+
+import pytest
+
+from kmerhash_amd import build as B
+
+NEW = {"k_chain_dp": 1, "k_chain_link": 1, "k_chain_emit": 2}
+LDS_BYTES = 0
+WAVES_PER_SIMD = 8
+# the index kernels as the parent commit builds them: kernel -> instantiations
+OLD = {"k_index_tile_sums": 1, "k_index_scan_sums": 1, "k_index_scan_apply": 2, "k_index_gather": 1, "k_index_move": 1, "k_index_lookup": 4,
+       "kw_index_lookup": 4, "k_index_rank": 1, "kw_index_rank": 1, "k_index_scatter": 4, "kw_index_scatter": 4, "k_index_tile_sort": 1,
+       "k_index_seg_radix": 1, "k_index_canon_runs": 1, "k_index_stamp": 2, "k_index_rank_carry": 2, "k_index_count_pairs": 4,
+       "kw_index_count_pairs": 4, "k_index_len_count": 2, "k_index_len_emit": 2, "k_index_add_base": 1, "k_pos_strand": 2, "k_anchors_expand": 1,
+       "k_csr_scatter": 1}
+
+
+@pytest.fixture(scope="module")
+def resources():
+    B.build_library()
+    if not os.path.exists(B.RES):
+        B.build_library(force=True)
+    return json.load(open(B.RES))
+
+
+def of(resources, kernel):
+    return {n: r for n, r in resources.items() if "%d%s" % (len(kernel), kernel) in n}      # (mangled: <length><name>)
+
+
+def test_every_chain_kernel_is_a_listed_one(resources):
+    names = [n for n in resources if "k_chain_" in n]
+    assert len(names) == sum(NEW.values()), names
+    for n in names:
+        assert any("%d%s" % (len(k), k) in n for k in NEW), n
+
+
+@pytest.mark.parametrize("kernel", sorted(NEW))
+def test_built_in_the_stated_number_without_scratch_or_spills(resources, kernel):
+    hits = of(resources, kernel)
+    assert len(hits) == NEW[kernel], (kernel, sorted(hits))
+    for name, r in hits.items():
+        assert r["Scratch"] == 0 and r["VGPRSpill"] == 0 and r["SGPRSpill"] == 0, (name, r)
+
+
+@pytest.mark.parametrize("kernel", sorted(NEW))
+def test_lds_and_occupancy_are_the_documented_ones(resources, kernel):
+    for name, r in of(resources, kernel).items():
+        assert r["LDS"] == LDS_BYTES, (name, r)
+        assert r["Occupancy"] == WAVES_PER_SIMD, (name, r)
+        assert r["VGPRs"] <= 512 // WAVES_PER_SIMD, (name, r)
+
+
+@pytest.mark.parametrize("kernel", sorted(NEW))
+def test_design_states_these_numbers(kernel):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rows = [l for l in open(os.path.join(root, "DESIGN.md")) if kernel in l and l.lstrip().startswith("|")]
+    assert rows, "DESIGN.md §3 has no row for %s" % kernel
+    assert any("no LDS" in l and "8 waves/SIMD" in l for l in rows), rows
+
+
+@pytest.mark.parametrize("kernel", sorted(OLD))
+def test_the_index_kernels_are_still_there_in_their_old_numbers(resources, kernel):
+    assert len(of(resources, kernel)) == OLD[kernel], kernel
