@@ -23,6 +23,7 @@
 #include "kh_kernels_csr.h"
 #include "kh_kernels_chain.h"
 #include "kh_part_sizing.h"
+#include "kh_scratch.h"
 #include "../../include/kmerhash_amd.h"
 
 #include <string>
@@ -190,13 +191,124 @@ kh_status fail(kh_table* t, kh_status s, const std::string& msg) {
   if (t) t->err = msg;
   return s;
 }
-#define HIPCHK(call)                                                                                   \
+// the one mapping of a HIP error to a status
+inline kh_status hip_status(hipError_t e) { return e == hipSuccess ? KH_OK : e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP; }
+kh_status hip_fail(kh_table* t, const char* call, hipError_t e) {
+  if (t) t->err = std::string(call) + ": " + hipGetErrorString(e);
+  return hip_status(e);
+}
+// HIPCHK: in a function with a table `t` in scope, whose error text it sets; HIPCHK0: where there is no table
+#define HIPCHK_T(table, call)                                                                          \
   do {                                                                                                 \
     hipError_t e__ = (call);                                                                           \
-    if (e__ != hipSuccess)                                                                             \
-      return fail(t, e__ == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP,                          \
-                  std::string(#call) + ": " + hipGetErrorString(e__));                                \
+    if (e__ != hipSuccess) return hip_fail(table, #call, e__);                                         \
   } while (0)
+#define HIPCHK(call) HIPCHK_T(t, call)
+#define HIPCHK0(call) HIPCHK_T(nullptr, call)
+
+inline int cu_count(int device) {
+  int ncu = 256;
+  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
+  return ncu > 0 ? ncu : 256;
+}
+inline int cu_count(const kh_table* t) { return cu_count(t->device); }
+
+// ---- scratch of one handle-free call ---------------------------------------------------------------
+// Bound to (device, stream), which the caller has made current.  The call describes its block once, as a function of the scratch
+// (layout(): kh_scratch.h's two passes), with take() for temporaries and in() / out() for arrays that live where `where` says: device
+// memory is used as it is, host memory gets a carved copy -- in() queues the copy in, copy_back() the copy out.  The first HIP error
+// sticks and turns the later copies into no-ops.  finish(), also run by the destructor on every early return, waits for the stream
+// if a block or a host copy of this call may still be in use, returns the blocks to the pool and maps the error.
+class Scratch {
+ public:
+  Scratch(int device, hipStream_t stream) : device_(device), stream_(stream) {}
+  Scratch(const Scratch&) = delete;
+  Scratch& operator=(const Scratch&) = delete;
+  ~Scratch() { finish(); }
+
+  hipError_t error() const { return err_; }
+  bool ok() const { return err_ == hipSuccess; }
+  void check(hipError_t e) { if (err_ == hipSuccess) err_ = e; }
+  // after kernel launches: their launch error, and the blocks are in use again
+  bool launched() { check(hipGetLastError()); busy_ = true; return ok(); }
+
+  // a pooled block of its own (null: the error is set)
+  void* alloc(size_t bytes) {
+    void* p = nullptr;
+    if (ok() && nblk_ == kMaxBlocks) err_ = hipErrorInvalidValue;
+    if (ok()) err_ = pool_alloc(device_, bytes, &p);
+    if (!ok()) return nullptr;
+    blk_[nblk_++] = p;
+    busy_ = true;
+    return p;
+  }
+  // the bytes `layout` takes; the same layout over a block the caller owns (a persistent workspace); both over a pooled block
+  template <typename F> size_t measure(F&& layout) { car_ = KhCarver(); layout(*this); return car_.size(); }
+  template <typename F> void carve(void* base, F&& layout) { car_ = KhCarver(base); layout(*this); }
+  template <typename F> bool layout(F&& layout) {
+    const size_t bytes = measure(layout);
+    void* p = bytes ? alloc(bytes) : nullptr;
+    if (bytes && !p) return false;
+    carve(p, layout);      // (no bytes: nothing is staged, the caller's pointers pass through)
+    return ok();
+  }
+  // inside a layout function
+  template <typename T> T* take(uint64_t count) { return car_.take<T>(count); }
+  template <typename T> const T* in(const T* p, uint64_t count, kh_mem where) {
+    if (where != KH_MEM_HOST) return p;
+    T* d = car_.take<T>(count);
+    if (d) copy(d, p, count * sizeof(T), hipMemcpyHostToDevice);
+    return d;
+  }
+  template <typename T> T* out(T* p, uint64_t count, kh_mem where) {
+    if (where != KH_MEM_HOST) return p;
+    T* d = car_.take<T>(count);
+    if (d && nout_ == kMaxOut) check(hipErrorInvalidValue);
+    else if (d) outs_[nout_++] = Out{p, d};
+    return d;
+  }
+  // the first `count` elements of what out() returned as `d`, back to the host array it stands for (device memory: nothing to do)
+  template <typename T> void copy_back(const T* d, uint64_t count) {
+    for (int i = 0; i < nout_ && count; ++i)
+      if (outs_[i].dev == d) { copy(outs_[i].host, d, count * sizeof(T), hipMemcpyDeviceToHost); return; }
+  }
+  // device values into host variables of the call
+  template <typename T> void read(T* host, const T* dev, uint64_t count = 1) { copy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost); }
+  void zero(void* p, size_t bytes) { if (ok()) { err_ = hipMemsetAsync(p, 0, bytes, stream_); busy_ = true; } }
+  // waits for everything queued so far (a total the host needs before it goes on)
+  bool sync() {
+    check(hipStreamSynchronize(stream_));
+    busy_ = pending_ = false;
+    return ok();
+  }
+  // the first block leaves the scratch: the caller owns it now and returns it with pool_free
+  void* keep() {
+    void* p = nblk_ ? blk_[0] : nullptr;
+    for (int i = 1; i < nblk_; ++i) blk_[i - 1] = blk_[i];
+    if (nblk_) --nblk_;
+    return p;
+  }
+  kh_status finish() {
+    if (pending_ || (nblk_ && busy_)) sync();
+    for (int i = 0; i < nblk_; ++i) pool_free(device_, blk_[i]);
+    nblk_ = 0; nout_ = 0; busy_ = pending_ = false;
+    return hip_status(err_);
+  }
+
+ private:
+  void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    if (ok()) { err_ = hipMemcpyAsync(dst, src, bytes, kind, stream_); pending_ = true; }
+  }
+  static const int kMaxBlocks = 4, kMaxOut = 8;
+  struct Out { void* host; const void* dev; };
+  int device_; hipStream_t stream_;
+  hipError_t err_ = hipSuccess;
+  KhCarver car_;
+  void* blk_[kMaxBlocks]; int nblk_ = 0;
+  Out outs_[kMaxOut]; int nout_ = 0;
+  bool busy_ = false;         // work that may use a block has been queued since the last wait
+  bool pending_ = false;      // a copy from or to host memory has been queued since the last wait
+};
 
 // ---- workspace arena ---------------------------------------------------------------------------
 void arena_reset(kh_table* t) { t->blk = 0; t->off = 0; }
@@ -690,8 +802,7 @@ kh_status partition_batch(kh_table* t, const char* kbase, uint32_t kstride, cons
   const bool full_hist = B2 > 0 && PB <= 18;     // 2^16 16-bit bins = 128 KB of LDS per sweep; up to four sweeps (slices of the id space)
   if (full_hist) {
     // one sweep over the keys gives the histogram of the full partition id; both levels' offsets follow from one scan
-    int ncu = 256;
-    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, t->device);
+    const int ncu = cu_count(t);
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)ncu, (n + 4095) / 4096));
     const uint32_t slice_bits = PB > 16 ? PB - 16 : 0;
     { Launch L(t, "k_part_hist");
@@ -1404,8 +1515,7 @@ kh_status launch_find(kh_table* t, int out_mode, const uint64_t* q, uint64_t n, 
   F.out_vals = dvals; F.out_found = dfound; F.out_keys = dkeys; F.out_pairs16 = dpairs;
   F.n_found = (out_mode == KH_FIND_COUNT && !hits_dev) ? nullptr : ctl;      // count(Iter,Iter) returns no total
   F.ticket = reinterpret_cast<uint32_t*>(ctl + 1); F.tile_state = ctl + 2;
-  int ncu = 256;
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, t->device);
+  const int ncu = cu_count(t);
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(ntiles, (uint64_t)ncu * 8));
   const char* name = out_mode == KH_FIND_COUNT ? "k_count" : "k_find";
   { Launch L(t, name);
@@ -2023,11 +2133,6 @@ namespace {
   else if ((t)->kind == KHK_RH) { constexpr int LAY = KV_RH; __VA_ARGS__; }            \
   else { constexpr int LAY = KV_LP; __VA_ARGS__; }
 
-inline int cu_count(const kh_table* t) {
-  int ncu = 256;
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, t->device);
-  return ncu > 0 ? ncu : 256;
-}
 }  // namespace
 extern "C" {
 kh_status kh_value_histogram(kh_table* t, uint32_t nbins, uint64_t* out_host) {
@@ -2134,31 +2239,22 @@ inline bool xform_ok(kh_key_transform xf, uint32_t k) { return xf == KH_XF_IDENT
 inline KhSeed make_seed(uint64_t seed, kh_key_transform xf, uint32_t k) { return KhSeed{seed, xf == KH_XF_DNA_LEX_LESS ? k : 0u}; }
 // Hash::operator()(Key const*, count, out) for keys of kw 64-bit words: stage host keys in, hash, copy the hashes out
 kh_status hash_batch_impl(uint32_t kw, kh_hash hash, KhSeed seed, const void* keys, uint64_t n, kh_mem where, uint64_t* out, int device, void* stream_) {
-  kh_table* t = nullptr;
   if (n == 0) return KH_OK;
   if (!keys || !out || (int)hash < 0 || (int)hash > 3) return KH_ERR_INVALID;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
-  const uint64_t* dk = static_cast<const uint64_t*>(keys);
-  uint64_t* dout = out; uint64_t* tmp = nullptr;
-  if (where == KH_MEM_HOST) {
-    HIPCHK(pool_alloc(device, n * 8 * (kw + 1), reinterpret_cast<void**>(&tmp)));
-    HIPCHK(hipMemcpyAsync(tmp, keys, n * 8 * kw, hipMemcpyHostToDevice, stream));
-    dk = tmp; dout = tmp + kw * n;
-  }
+  HIPCHK0(hipSetDevice(device));
+  Scratch s(device, stream);
+  const uint64_t* dk = nullptr; uint64_t* dout = nullptr;
+  if (!s.layout([&](Scratch& c) { dk = c.in(static_cast<const uint64_t*>(keys), n * kw, where); dout = c.out(out, n, where); })) return s.finish();
   if (kw == 2) { KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_hash_batch<HASH, 2>), dim3(grid_for(n, 256)), dim3(256), 0, stream, dk, n, seed.s, dout)); }
   else { KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_hash_batch<HASH, 1>), dim3(grid_for(n, 256)), dim3(256), 0, stream, dk, n, seed, dout)); }
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && where == KH_MEM_HOST) e = hipMemcpyAsync(out, dout, n * 8, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess && where == KH_MEM_HOST) e = hipStreamSynchronize(stream);
-  if (tmp) pool_free(device, tmp);
-  return e == hipSuccess ? KH_OK : KH_ERR_HIP;
+  if (s.launched()) s.copy_back(dout, n);
+  return s.finish();
 }
 // stable partition of (key, value) by destination rank = hash(key) mod p for keys of kw 64-bit words (xf / k: 8-byte keys only);
 // out_keys == null: count only -- the caller sizes the exchange before it permutes (pipelined multi-GPU insert)
 kh_status shard_permute_impl(uint32_t kw, kh_hash hash, uint64_t seed_, kh_key_transform xf, uint32_t k, uint32_t p, const uint64_t* keys,
                              const uint32_t* vals, uint64_t n, uint64_t* out_keys, uint32_t* out_vals, uint64_t* counts_host, int device, void* stream_) {
-  kh_table* t = nullptr;
   if (p == 0 || p > KH_SHARD_MAXR || !counts_host || (int)hash < 0 || (int)hash > 3 || !xform_ok(xf, k)) return KH_ERR_INVALID;
   const KhSeed seed = make_seed(seed_, xf, k);
   for (uint32_t r = 0; r < p; ++r) counts_host[r] = 0;
@@ -2170,13 +2266,13 @@ kh_status shard_permute_impl(uint32_t kw, kh_hash hash, uint64_t seed_, kh_key_t
     if ((n + tile - 1) / tile > 0x7FFFFFFFull) return KH_ERR_UNSUPPORTED;
   }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
+  HIPCHK0(hipSetDevice(device));
   const uint32_t ntiles = (uint32_t)((n + tile - 1) / tile);
   const uint32_t pmask = (p & (p - 1)) == 0 ? p - 1 : 0;   // power of two: & (p-1); else % p.  (p == 1: mask 0 -> % 1)
   uint32_t* tc = nullptr; uint64_t* toff = nullptr;
   const uint64_t m = (uint64_t)p * ntiles;
-  HIPCHK(pool_alloc(device, m * 4, reinterpret_cast<void**>(&tc)));
-  if (pool_alloc(device, (m + 1) * 8, reinterpret_cast<void**>(&toff)) != hipSuccess) { pool_free(device, tc); return KH_ERR_NOMEM; }
+  Scratch s(device, stream);
+  if (!s.layout([&](Scratch& c) { tc = c.take<uint32_t>(m); toff = c.take<uint64_t>(m + 1); })) return s.finish();
   // (S: the seed in the form the key width's hash takes)
 #define KH_SHARD_LAUNCH(KERNEL, ...)                                                                                                                            \
   if (kw == 2) { const uint64_t S = seed.s; KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((KERNEL<HASH, 2>), dim3(ntiles), dim3(KH_SHARD_THREADS), 0, stream, __VA_ARGS__)); } \
@@ -2187,12 +2283,10 @@ kh_status shard_permute_impl(uint32_t kw, kh_hash hash, uint64_t seed_, kh_key_t
   else if (out_keys) { KH_SHARD_LAUNCH(k_shard_scatter, keys, vals, n, S, p, pmask, (const uint64_t*)toff, ntiles, out_keys, out_vals); }
 #undef KH_SHARD_LAUNCH
   std::vector<uint64_t> ends(p + 1);
-  hipError_t e = hipGetLastError();
-  for (uint32_t r = 0; r <= p && e == hipSuccess; ++r)
-    e = hipMemcpyAsync(&ends[r], toff + (uint64_t)r * ntiles, 8, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  pool_free(device, tc); pool_free(device, toff);
-  if (e != hipSuccess) return KH_ERR_HIP;
+  s.launched();
+  for (uint32_t r = 0; r <= p; ++r) s.read(&ends[r], toff + (uint64_t)r * ntiles);
+  const kh_status st = s.finish();
+  if (st != KH_OK) return st;
   for (uint32_t r = 0; r < p; ++r) counts_host[r] = ends[r + 1] - ends[r];
   return KH_OK;
 }
@@ -2235,87 +2329,72 @@ kh_status kh_shard_permute_transformed(kh_hash hash, uint64_t seed_, kh_key_tran
 //      scatter kernel alone (no second count, no second scan, one host synchronisation instead of one per piece)
 struct kh_shard_plan {
   int device, hash; KhSeed seed; uint32_t p, pmask, pieces, ntiles; uint64_t n;
-  uint32_t* tc; uint64_t* toff; uint64_t* bnd_dev;
+  void* blk; const uint64_t* toff;      // the pooled block of the scan, and the scanned [rank][tile] offsets inside it
   std::vector<uint64_t> bnd;      // [p][pieces+1] scanned offsets at the piece boundaries
 };
 kh_status kh_shard_plan_create(kh_shard_plan** out, kh_hash hash, uint64_t seed_, kh_key_transform xf, uint32_t k, uint32_t p, const uint64_t* keys,
                                uint64_t n, uint32_t pieces, uint64_t* counts_host, uint64_t* bounds_host, int device, void* stream_) {
-  kh_table* t = nullptr;
   if (!out) return KH_ERR_INVALID;
   *out = nullptr;
   if (p == 0 || p > 8 || pieces == 0 || pieces > 64 || !counts_host || !bounds_host || (int)hash < 0 || (int)hash > 3 || !xform_ok(xf, k) || (n && !keys)) return KH_ERR_INVALID;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
+  HIPCHK0(hipSetDevice(device));
   std::unique_ptr<kh_shard_plan> P(new kh_shard_plan());
   P->device = device; P->hash = (int)hash; P->seed = make_seed(seed_, xf, k); P->p = p; P->pmask = (p & (p - 1)) == 0 ? p - 1 : 0;
-  P->pieces = pieces; P->n = n; P->tc = nullptr; P->toff = nullptr; P->bnd_dev = nullptr;
+  P->pieces = pieces; P->n = n; P->blk = nullptr; P->toff = nullptr;
   P->ntiles = (uint32_t)((n + KH_SHARD_TILE(1) - 1) / KH_SHARD_TILE(1));
   for (uint32_t i = 0; i <= pieces; ++i) bounds_host[i] = std::min<uint64_t>(n, ((uint64_t)P->ntiles * i / pieces) * KH_SHARD_TILE(1));
   for (uint64_t j = 0; j < (uint64_t)pieces * p; ++j) counts_host[j] = 0;
   P->bnd.assign((size_t)p * (pieces + 1), 0);
   if (n) {
     const uint64_t m = (uint64_t)p * P->ntiles;
-    HIPCHK(pool_alloc(device, m * 4, reinterpret_cast<void**>(&P->tc)));
-    if (pool_alloc(device, (m + 1) * 8, reinterpret_cast<void**>(&P->toff)) != hipSuccess ||
-        pool_alloc(device, P->bnd.size() * 8, reinterpret_cast<void**>(&P->bnd_dev)) != hipSuccess) {
-      if (P->toff) pool_free(device, P->toff);
-      pool_free(device, P->tc);
-      return KH_ERR_NOMEM;
-    }
-    KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_shard_count<HASH, 1>), dim3(P->ntiles), dim3(KH_SHARD_THREADS), 0, stream, keys, n, P->seed, p, P->pmask, P->tc, P->ntiles));
-    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, P->tc, m, P->toff);
-    hipLaunchKernelGGL(k_shard_piece_bounds, dim3(1 + (uint32_t)P->bnd.size() / 256), dim3(256), 0, stream, (const uint64_t*)P->toff, P->ntiles, p, pieces, P->bnd_dev);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(P->bnd.data(), P->bnd_dev, P->bnd.size() * 8, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { pool_free(device, P->tc); pool_free(device, P->toff); pool_free(device, P->bnd_dev); return KH_ERR_HIP; }
+    uint32_t* tc = nullptr; uint64_t *toff = nullptr, *bnd_dev = nullptr;
+    Scratch s(device, stream);      // (an error on the way out returns the block)
+    if (!s.layout([&](Scratch& c) { tc = c.take<uint32_t>(m); toff = c.take<uint64_t>(m + 1); bnd_dev = c.take<uint64_t>(P->bnd.size()); })) return s.finish();
+    KH_SWITCH_HASH((int)hash, hipLaunchKernelGGL((k_shard_count<HASH, 1>), dim3(P->ntiles), dim3(KH_SHARD_THREADS), 0, stream, keys, n, P->seed, p, P->pmask, tc, P->ntiles));
+    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, tc, m, toff);
+    hipLaunchKernelGGL(k_shard_piece_bounds, dim3(1 + (uint32_t)P->bnd.size() / 256), dim3(256), 0, stream, (const uint64_t*)toff, P->ntiles, p, pieces, bnd_dev);
+    s.launched();
+    s.read(P->bnd.data(), bnd_dev, P->bnd.size());
+    if (!s.sync()) return s.finish();
+    P->blk = s.keep(); P->toff = toff;      // the plan's from here on
     for (uint32_t i = 0; i < pieces; ++i)
       for (uint32_t r = 0; r < p; ++r) counts_host[(size_t)i * p + r] = P->bnd[(size_t)r * (pieces + 1) + i + 1] - P->bnd[(size_t)r * (pieces + 1) + i];
   }
   *out = P.release();
   return KH_OK;
 }
-kh_status kh_shard_plan_permute(kh_shard_plan* P, uint32_t piece, const uint64_t* keys, const uint32_t* vals, uint64_t* out_keys, uint32_t* out_vals,
-                                void* stream_) {
-  kh_table* t = nullptr;
+// one piece through the scatter kernel.  global: to its place in the layout of the WHOLE batch grouped by rank (what kh_shard_permute of
+// all n pairs gives) -- the scanned [rank][tile] offsets already are positions in that layout; else to the piece's own output, rank by rank
+static kh_status shard_plan_permute(kh_shard_plan* P, uint32_t piece, const uint64_t* keys, const uint32_t* vals, uint64_t* out_keys, uint32_t* out_vals,
+                                    void* stream_, bool global) {
   if (!P || piece >= P->pieces || (vals && !out_vals)) return KH_ERR_INVALID;
   if (P->n == 0) return KH_OK;
   if (!keys || !out_keys) return KH_ERR_INVALID;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(P->device));
+  HIPCHK0(hipSetDevice(P->device));
   const uint32_t t0 = (uint32_t)((uint64_t)P->ntiles * piece / P->pieces), t1 = (uint32_t)((uint64_t)P->ntiles * (piece + 1) / P->pieces);
   if (t1 == t0) return KH_OK;
   const uint64_t b0 = (uint64_t)t0 * KH_SHARD_TILE(1), b1 = std::min<uint64_t>(P->n, (uint64_t)t1 * KH_SHARD_TILE(1));
-  KhShardAdj adj;
+  KhShardAdj adj;      // (all zero)
   uint64_t base = 0;      // where rank r's pairs of THIS piece start in the piece's output
-  for (uint32_t r = 0; r < P->p; ++r) {
+  for (uint32_t r = 0; r < P->p && !global; ++r) {
     const uint64_t lo = P->bnd[(size_t)r * (P->pieces + 1) + piece], hi = P->bnd[(size_t)r * (P->pieces + 1) + piece + 1];
     adj.a[r] = (long long)base - (long long)lo;
     base += hi - lo;
   }
   KH_SWITCH_HASH(P->hash, hipLaunchKernelGGL((k_shard_scatter8<HASH, 1>), dim3(t1 - t0), dim3(KH_SHARD_THREADS), 0, stream, keys + b0, vals ? vals + b0 : nullptr, b1 - b0,
-                                             P->seed, P->p, P->pmask, (const uint64_t*)P->toff, P->ntiles, out_keys, out_vals, t0, adj));
-  HIPCHK(hipGetLastError());
+                                             P->seed, P->p, P->pmask, P->toff, P->ntiles, out_keys, out_vals, t0, adj));
+  HIPCHK0(hipGetLastError());
   return KH_OK;
 }
-// piece `piece` written to its place in the layout of the WHOLE batch grouped by rank (what kh_shard_permute of all n pairs gives):
-// the scanned [rank][tile] offsets already are positions in that layout
+kh_status kh_shard_plan_permute(kh_shard_plan* P, uint32_t piece, const uint64_t* keys, const uint32_t* vals, uint64_t* out_keys, uint32_t* out_vals,
+                                void* stream_) {
+  return shard_plan_permute(P, piece, keys, vals, out_keys, out_vals, stream_, false);
+}
 kh_status kh_shard_plan_permute_global(kh_shard_plan* P, uint32_t piece, const uint64_t* keys, const uint32_t* vals, uint64_t* out_keys, uint32_t* out_vals,
                                        void* stream_) {
-  kh_table* t = nullptr;
-  if (!P || piece >= P->pieces || (vals && !out_vals)) return KH_ERR_INVALID;
-  if (P->n == 0) return KH_OK;
-  if (!keys || !out_keys) return KH_ERR_INVALID;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(P->device));
-  const uint32_t t0 = (uint32_t)((uint64_t)P->ntiles * piece / P->pieces), t1 = (uint32_t)((uint64_t)P->ntiles * (piece + 1) / P->pieces);
-  if (t1 == t0) return KH_OK;
-  const uint64_t b0 = (uint64_t)t0 * KH_SHARD_TILE(1), b1 = std::min<uint64_t>(P->n, (uint64_t)t1 * KH_SHARD_TILE(1));
-  KhShardAdj adj;      // (all zero)
-  KH_SWITCH_HASH(P->hash, hipLaunchKernelGGL((k_shard_scatter8<HASH, 1>), dim3(t1 - t0), dim3(KH_SHARD_THREADS), 0, stream, keys + b0, vals ? vals + b0 : nullptr, b1 - b0,
-                                             P->seed, P->p, P->pmask, (const uint64_t*)P->toff, P->ntiles, out_keys, out_vals, t0, adj));
-  HIPCHK(hipGetLastError());
-  return KH_OK;
+  return shard_plan_permute(P, piece, keys, vals, out_keys, out_vals, stream_, true);
 }
 kh_status kh_shard_plan_offsets(const kh_shard_plan* P, uint64_t* out) {
   if (!P || !out) return KH_ERR_INVALID;
@@ -2325,9 +2404,7 @@ kh_status kh_shard_plan_offsets(const kh_shard_plan* P, uint64_t* out) {
 }
 void kh_shard_plan_destroy(kh_shard_plan* P) {
   if (!P) return;
-  if (P->tc) pool_free(P->device, P->tc);
-  if (P->toff) pool_free(P->device, P->toff);
-  if (P->bnd_dev) pool_free(P->device, P->bnd_dev);
+  pool_free(P->device, P->blk);
   delete P;
 }
 
@@ -2342,251 +2419,189 @@ void fastq_mask_text(const uint8_t* text, uint64_t n, uint32_t* sums, uint64_t* 
   hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, sums, ntl, offs);
   hipLaunchKernelGGL(k_fastq_mask, dim3((uint32_t)ntl), dim3(256), 0, stream, text, n, (const uint64_t*)offs, msk);
 }
+// The text front end of the k-mer, sampling, HyperLogLog and index text calls: a host text is staged, a FASTQ text is masked, and the
+// tile sums / tile offsets of the passes that follow live next to it.  carve() inside the call's layout function, mask() once it ran.
+struct TextFront {
+  const uint8_t* text = nullptr;      // the text the window kernels read: the caller's, its staged copy, or the masked text after mask()
+  uint8_t* msk = nullptr;             // u8[n] (FASTQ)
+  uint32_t* sums = nullptr;           // u32[nt]
+  uint64_t* offs = nullptr;           // u64[nt + 1]
+  // nt: tiles of the largest pass that uses sums / offs (FASTQ: at least those of KH_CMP_TILE; 0: none)
+  void carve(Scratch& c, const void* src, uint64_t n, kh_mem where, bool fastq, uint64_t nt) {
+    text = c.in(static_cast<const uint8_t*>(src), n, where);
+    msk = c.take<uint8_t>(fastq ? n : 0);
+    sums = c.take<uint32_t>(nt);
+    offs = c.take<uint64_t>(nt ? nt + 1 : 0);
+  }
+  void mask(uint64_t n, hipStream_t stream) {
+    if (msk) { fastq_mask_text(text, n, sums, offs, msk, stream); text = msk; }
+  }
+};
+inline uint64_t cmp_tiles(uint64_t n) { return (n + KH_CMP_TILE - 1) / KH_CMP_TILE; }      // tiles of the FASTQ line kernels
+inline uint64_t km_tiles(uint64_t n) { return (n + KH_KM_TILE - 1) / KH_KM_TILE; }         // tiles of the k-mer kernels
 // shared body of kh_kmers[128]_from_sequence / kh_kmers[128]_from_fastq; kw: 64-bit words per k-mer (1: k <= 32, 2: k <= 64)
 // out_pos (n < 2^32): the byte offset of every window next to its k-mer (kh_kmers[128]_from_sequence_pos / _fastq_pos)
 kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq,
                      uint64_t* out_kmers, uint64_t* n_out, int device, void* stream_, uint32_t* out_pos = nullptr) {
-  kh_table* t = nullptr;
   if (n_out) *n_out = 0;
   if (k < 1 || k > 32 * kw || !n_out) return KH_ERR_INVALID;
   if (n < k) return KH_OK;
   if (!seq || !out_kmers) return KH_ERR_INVALID;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
-  const uint64_t ntl = (n + KH_CMP_TILE - 1) / KH_CMP_TILE;            // tiles of the FASTQ line kernels
-  const uint64_t nkt = (n + KH_KM_TILE - 1) / KH_KM_TILE;              // tiles of the k-mer kernels
-  // one pooled block: [text copy (host input)] [masked text (FASTQ)] [tile sums] [tile offsets] [compacted out (host output)]
-  const size_t sz_seq = where == KH_MEM_HOST ? ((n + 255) & ~size_t(255)) : 0;
-  const size_t sz_msk = fastq ? ((n + 255) & ~size_t(255)) : 0;
-  const uint64_t nt = std::max(ntl, nkt);
-  const size_t sz_sum = ((nt * 4 + 255) & ~size_t(255)), sz_off = (nt + 1) * 8;
-  const size_t sz_out = where == KH_MEM_HOST ? n * 8 * kw : 0;
-  const size_t sz_pos = where == KH_MEM_HOST && out_pos ? n * 4 : 0;
-  char* blk = nullptr;
-  HIPCHK(pool_alloc(device, sz_seq + sz_msk + sz_sum + sz_off + 256 + sz_out + sz_pos, reinterpret_cast<void**>(&blk)));
-  const uint8_t* dseq = static_cast<const uint8_t*>(seq);
-  char* p = blk;
-  if (where == KH_MEM_HOST) { dseq = reinterpret_cast<uint8_t*>(p); p += sz_seq; }
-  uint8_t* msk = reinterpret_cast<uint8_t*>(p); p += sz_msk;
-  uint32_t* sums = reinterpret_cast<uint32_t*>(p); p += sz_sum;
-  uint64_t* offs = reinterpret_cast<uint64_t*>(p); p += (sz_off + 255) & ~size_t(255);
-  uint64_t* dout = where == KH_MEM_HOST ? reinterpret_cast<uint64_t*>(p) : out_kmers;
-  uint32_t* dpos = where == KH_MEM_HOST ? reinterpret_cast<uint32_t*>(p + sz_out) : out_pos;
-  hipError_t e = hipSuccess;
-  if (where == KH_MEM_HOST) e = hipMemcpyAsync(const_cast<uint8_t*>(dseq), seq, n, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) {
-    if (fastq) { fastq_mask_text(dseq, n, sums, offs, msk, stream); dseq = msk; }
-    // two passes over the text: valid windows per tile, scan, then the windows themselves, compacted and in order
-    if (kw == 2) hipLaunchKernelGGL(k_kmers_count<2>, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
-    else hipLaunchKernelGGL(k_kmers_count<1>, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
-    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, sums, nkt, offs);
-    if (out_pos && kw == 2 && canonical) hipLaunchKernelGGL((kw_kmers_emit_pos<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout, dpos);
-    else if (out_pos && kw == 2) hipLaunchKernelGGL((kw_kmers_emit_pos<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout, dpos);
-    else if (out_pos && canonical) hipLaunchKernelGGL((k_kmers_emit_pos<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout, dpos);
-    else if (out_pos) hipLaunchKernelGGL((k_kmers_emit_pos<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout, dpos);
-    else if (kw == 2 && canonical) hipLaunchKernelGGL((kw_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
-    else if (kw == 2) hipLaunchKernelGGL((kw_kmers_emit<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
-    else if (canonical) hipLaunchKernelGGL((k_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
-    else hipLaunchKernelGGL((k_kmers_emit<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, (const uint64_t*)offs, dout);
-    e = hipGetLastError();
-  }
+  HIPCHK0(hipSetDevice(device));
+  const uint64_t nkt = km_tiles(n);
+  Scratch s(device, stream);
+  TextFront F;
+  uint64_t* dout = nullptr; uint32_t* dpos = nullptr;      // compacted, where the caller's memory is
+  if (!s.layout([&](Scratch& c) {
+        F.carve(c, seq, n, where, fastq, std::max(cmp_tiles(n), nkt));
+        dout = c.out(out_kmers, n * kw, where);
+        dpos = c.out(out_pos, out_pos ? n : 0, where);
+      })) return s.finish();
+  F.mask(n, stream);
+  const uint8_t* dseq = F.text; uint32_t* sums = F.sums; const uint64_t* offs = F.offs;
+  // two passes over the text: valid windows per tile, scan, then the windows themselves, compacted and in order
+  if (kw == 2) hipLaunchKernelGGL(k_kmers_count<2>, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
+  else hipLaunchKernelGGL(k_kmers_count<1>, dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, sums);
+  hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, sums, nkt, F.offs);
+  if (out_pos && kw == 2 && canonical) hipLaunchKernelGGL((kw_kmers_emit_pos<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, offs, dout, dpos);
+  else if (out_pos && kw == 2) hipLaunchKernelGGL((kw_kmers_emit_pos<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, offs, dout, dpos);
+  else if (out_pos && canonical) hipLaunchKernelGGL((k_kmers_emit_pos<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, offs, dout, dpos);
+  else if (out_pos) hipLaunchKernelGGL((k_kmers_emit_pos<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, offs, dout, dpos);
+  else if (kw == 2 && canonical) hipLaunchKernelGGL((kw_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, offs, dout);
+  else if (kw == 2) hipLaunchKernelGGL((kw_kmers_emit<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, offs, dout);
+  else if (canonical) hipLaunchKernelGGL((k_kmers_emit<true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, offs, dout);
+  else hipLaunchKernelGGL((k_kmers_emit<false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, offs, dout);
+  s.launched();
   uint64_t total = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&total, offs + nkt, 8, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e == hipSuccess && where == KH_MEM_HOST && total) {
-    e = hipMemcpyAsync(out_kmers, dout, total * 8 * kw, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess && out_pos) e = hipMemcpyAsync(out_pos, dpos, total * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  }
-  pool_free(device, blk);
-  if (e != hipSuccess) return KH_ERR_HIP;
+  s.read(&total, offs + nkt);
+  if (s.sync()) { s.copy_back(dout, total * kw); s.copy_back(dpos, total); }
+  const kh_status st = s.finish();
+  if (st != KH_OK) return st;
   *n_out = total;
   return KH_OK;
 }
 // (w,k)-minimizers in two steps, so that a caller can size its pair buffers from the count: mz_count stages a host text, masks FASTQ,
 // runs the count pass and the scan and returns the number of picks; mz_emit writes the pairs into device buffers of that many
-// entries.  prof: the table whose profile lists the launches (an index's own), or null.
+// entries.  The work's scratch holds the front end's block (and whatever the caller carves for the pairs) until the work goes away.
+// prof: the table whose profile lists the launches (an index's own), or null.
 struct MzWork {
-  int device = 0;
-  char* blk = nullptr;
-  const uint8_t* dseq = nullptr;
-  uint32_t* sums = nullptr;
-  uint64_t* offs = nullptr;
+  MzWork(int device, hipStream_t stream) : scr(device, stream) {}
+  Scratch scr;
+  TextFront F;
   uint64_t n = 0, nkt = 0;
   uint32_t k = 0, w = 0;
   uint32_t s = 0, kw = 1;      // s != 0 (set by the caller before mz_count): closed syncmers of kw-word k-mers instead, w unused
   int canonical = 0, hash = 0;
   uint64_t seed = 0;
 };
-void mz_free(MzWork& M) { pool_free(M.device, M.blk); M.blk = nullptr; }
 // refusals that need no device: k, w, n, the hash and null arguments (shared by kh_minimizers_* and kh_index_*_from_minimizers)
 bool mz_args_ok(const void* seq, uint64_t n, uint32_t k, uint32_t w, int hash) {
   return k >= 1 && k <= 32 && w >= 1 && w <= KM_MZ_WMAX && !(n >> 32) && hash >= 0 && hash <= 3 && (seq || n == 0);
 }
 kh_status mz_count(kh_table* prof, MzWork& M, const void* seq, uint64_t n, uint32_t k, uint32_t w, int canonical, int hash, uint64_t seed, kh_mem where, bool fastq,
-                   int device, hipStream_t stream, uint64_t* total) {
-  kh_table* t = prof;
-  M.device = device; M.n = n; M.k = k; M.w = w; M.canonical = canonical; M.hash = hash; M.seed = seed;
-  const uint64_t ntl = (n + KH_CMP_TILE - 1) / KH_CMP_TILE, nkt = (n + KH_KM_TILE - 1) / KH_KM_TILE;
+                   hipStream_t stream, uint64_t* total) {
+  M.n = n; M.k = k; M.w = w; M.canonical = canonical; M.hash = hash; M.seed = seed;
+  const uint64_t nkt = km_tiles(n);
   M.nkt = nkt;
-  // one pooled block: [text copy (host input)] [masked text (FASTQ)] [tile sums] [tile offsets]
-  const size_t sz_seq = where == KH_MEM_HOST ? ((n + 255) & ~size_t(255)) : 0;
-  const size_t sz_msk = fastq ? ((n + 255) & ~size_t(255)) : 0;
-  const uint64_t nt = std::max(ntl, nkt);
-  const size_t sz_sum = ((nt * 4 + 255) & ~size_t(255)), sz_off = (nt + 1) * 8;
-  HIPCHK(pool_alloc(device, sz_seq + sz_msk + sz_sum + sz_off, reinterpret_cast<void**>(&M.blk)));
-  char* p = M.blk;
-  M.dseq = static_cast<const uint8_t*>(seq);
-  if (where == KH_MEM_HOST) { M.dseq = reinterpret_cast<uint8_t*>(p); p += sz_seq; }
-  uint8_t* msk = reinterpret_cast<uint8_t*>(p); p += sz_msk;
-  M.sums = reinterpret_cast<uint32_t*>(p); p += sz_sum;
-  M.offs = reinterpret_cast<uint64_t*>(p);
-  hipError_t e = hipSuccess;
-  if (where == KH_MEM_HOST) e = hipMemcpyAsync(const_cast<uint8_t*>(M.dseq), seq, n, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) {
-    if (fastq) { fastq_mask_text(M.dseq, n, M.sums, M.offs, msk, stream); M.dseq = msk; }
+  Scratch& S = M.scr;
+  if (S.layout([&](Scratch& c) { M.F.carve(c, seq, n, where, fastq, std::max(cmp_tiles(n), nkt)); })) {
+    M.F.mask(n, stream);
+    const uint8_t* dseq = M.F.text; uint32_t* sums = M.F.sums;
     if (M.s) { Launch L(prof, "k_syncmers_count");
-      if (canonical) { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_syncmers_count<HASH, true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, n, k, M.s, seed, M.sums)); }
-      else { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_syncmers_count<HASH, false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, n, k, M.s, seed, M.sums)); } }
+      if (canonical) { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_syncmers_count<HASH, true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, M.s, seed, sums)); }
+      else { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_syncmers_count<HASH, false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, M.s, seed, sums)); } }
     else { Launch L(prof, "k_minimizers_count");
-      if (canonical) { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_minimizers_count<HASH, true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, n, k, w, seed, M.sums)); }
-      else { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_minimizers_count<HASH, false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, n, k, w, seed, M.sums)); } }
-    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, M.sums, nkt, M.offs);
-    e = hipGetLastError();
+      if (canonical) { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_minimizers_count<HASH, true>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, w, seed, sums)); }
+      else { KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_minimizers_count<HASH, false>), dim3((uint32_t)nkt), dim3(KH_KM_THREADS), 0, stream, dseq, n, k, w, seed, sums)); } }
+    hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, sums, nkt, M.F.offs);
+    S.launched();
+    S.read(total, M.F.offs + nkt);
+    S.sync();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(total, M.offs + nkt, 8, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e != hipSuccess) { mz_free(M); return fail(t, KH_ERR_HIP, std::string("minimizer count pass: ") + hipGetErrorString(e)); }
+  if (!S.ok()) { const std::string msg = std::string("minimizer count pass: ") + hipGetErrorString(S.error()); return fail(prof, S.finish(), msg); }
   return KH_OK;
 }
 // queues the emit pass (dout u64[total], dpos u32[total], device memory); the caller synchronises
-kh_status mz_emit(kh_table* prof, const MzWork& M, hipStream_t stream, uint64_t* dout, uint32_t* dpos, uint32_t pos_base) {
-  kh_table* t = prof;
+kh_status mz_emit(kh_table* prof, MzWork& M, hipStream_t stream, uint64_t* dout, uint32_t* dpos, uint32_t pos_base) {
+  const uint8_t* dseq = M.F.text; const uint64_t* offs = M.F.offs;
   if (M.s) { Launch L(prof, "k_syncmers_emit");
-#define KH_SY_EMIT(CANON, KW) KH_SWITCH_HASH(M.hash, hipLaunchKernelGGL((k_syncmers_emit<HASH, CANON, KW>), dim3((uint32_t)M.nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, M.n, M.k, M.s, \
-                                                                  M.seed, (const uint64_t*)M.offs, dout, dpos, pos_base))
+#define KH_SY_EMIT(CANON, KW) KH_SWITCH_HASH(M.hash, hipLaunchKernelGGL((k_syncmers_emit<HASH, CANON, KW>), dim3((uint32_t)M.nkt), dim3(KH_KM_THREADS), 0, stream, dseq, M.n, M.k, M.s, \
+                                                                  M.seed, offs, dout, dpos, pos_base))
     if (M.kw == 2) { if (M.canonical) { KH_SY_EMIT(true, 2); } else { KH_SY_EMIT(false, 2); } }
     else if (M.canonical) { KH_SY_EMIT(true, 1); }
     else { KH_SY_EMIT(false, 1); }
 #undef KH_SY_EMIT
   }
   else { Launch L(prof, "k_minimizers_emit");
-    if (M.canonical) { KH_SWITCH_HASH(M.hash, hipLaunchKernelGGL((k_minimizers_emit<HASH, true>), dim3((uint32_t)M.nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, M.n, M.k, M.w, M.seed,
-                                                                 (const uint64_t*)M.offs, dout, dpos, pos_base)); }
-    else { KH_SWITCH_HASH(M.hash, hipLaunchKernelGGL((k_minimizers_emit<HASH, false>), dim3((uint32_t)M.nkt), dim3(KH_KM_THREADS), 0, stream, M.dseq, M.n, M.k, M.w, M.seed,
-                                                     (const uint64_t*)M.offs, dout, dpos, pos_base)); } }
-  HIPCHK(hipGetLastError());
+    if (M.canonical) { KH_SWITCH_HASH(M.hash, hipLaunchKernelGGL((k_minimizers_emit<HASH, true>), dim3((uint32_t)M.nkt), dim3(KH_KM_THREADS), 0, stream, dseq, M.n, M.k, M.w, M.seed,
+                                                                 offs, dout, dpos, pos_base)); }
+    else { KH_SWITCH_HASH(M.hash, hipLaunchKernelGGL((k_minimizers_emit<HASH, false>), dim3((uint32_t)M.nkt), dim3(KH_KM_THREADS), 0, stream, dseq, M.n, M.k, M.w, M.seed,
+                                                     offs, dout, dpos, pos_base)); } }
+  if (!M.scr.launched()) return hip_fail(prof, "minimizer emit pass", M.scr.error());
   return KH_OK;
+}
+// shared body of kh_minimizers_* and kh_syncmers[128]_*: the entry family has preset the work (M.s, M.kw) and judged its own arguments;
+// min_n: the shortest text that holds a window.  The pairs of a host call are staged in a second block, sized by the count
+kh_status sampled_impl(MzWork& M, bool args_ok, uint64_t min_n, const void* seq, uint64_t n, uint32_t k, uint32_t w, int canonical, int hash, uint64_t seed, kh_mem where,
+                       bool fastq, uint64_t* out_kmers, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, hipStream_t stream) {
+  if (n_out) *n_out = 0;
+  if (!n_out || !args_ok || (out_kmers && !out_pos)) return KH_ERR_INVALID;
+  if (n < min_n) return KH_OK;
+  HIPCHK0(hipSetDevice(device));
+  uint64_t total = 0;
+  kh_status st = mz_count(nullptr, M, seq, n, k, w, canonical, hash, seed, where, fastq, stream, &total);
+  if (st != KH_OK) return st;
+  *n_out = total;
+  if (!out_kmers || total == 0) return KH_OK;
+  if (total > cap_out) return KH_ERR_INVALID;       // (the total is known before anything is written)
+  uint64_t* dout = nullptr; uint32_t* dpos = nullptr;
+  if (!M.scr.layout([&](Scratch& c) { dout = c.out(out_kmers, total * M.kw, where); dpos = c.out(out_pos, total, where); })) return M.scr.finish();
+  st = mz_emit(nullptr, M, stream, dout, dpos, 0u);
+  M.scr.copy_back(dout, total * M.kw);
+  M.scr.copy_back(dpos, total);
+  const kh_status fs = M.scr.finish();
+  return fs != KH_OK ? fs : st;
 }
 kh_status minimizers_impl(const void* seq, uint64_t n, uint32_t k, uint32_t w, int canonical, int hash, uint64_t seed, kh_mem where, bool fastq,
                           uint64_t* out_kmers, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, void* stream_) {
-  kh_table* t = nullptr;
-  if (n_out) *n_out = 0;
-  if (!n_out || !mz_args_ok(seq, n, k, w, hash) || (out_kmers && !out_pos)) return KH_ERR_INVALID;
-  if (n < (uint64_t)w + k - 1) return KH_OK;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
-  MzWork M;
-  uint64_t total = 0;
-  kh_status st = mz_count(nullptr, M, seq, n, k, w, canonical, hash, seed, where, fastq, device, stream, &total);
-  if (st != KH_OK) return st;
-  *n_out = total;
-  if (!out_kmers || total == 0) { mz_free(M); return KH_OK; }
-  if (total > cap_out) { mz_free(M); return KH_ERR_INVALID; }       // (the total is known before anything is written)
-  uint64_t* dout = out_kmers; uint32_t* dpos = out_pos;
-  char* stage = nullptr;
-  hipError_t e = hipSuccess;
-  if (where == KH_MEM_HOST) {
-    e = pool_alloc(device, total * 12, reinterpret_cast<void**>(&stage));
-    dout = reinterpret_cast<uint64_t*>(stage); dpos = reinterpret_cast<uint32_t*>(stage + total * 8);
-  }
-  if (e == hipSuccess) {
-    st = mz_emit(nullptr, M, stream, dout, dpos, 0u);
-    if (st == KH_OK && where == KH_MEM_HOST) {
-      e = hipMemcpyAsync(out_kmers, dout, total * 8, hipMemcpyDeviceToHost, stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(out_pos, dpos, total * 4, hipMemcpyDeviceToHost, stream);
-    }
-  }
-  const hipError_t es = hipStreamSynchronize(stream);
-  pool_free(device, stage);
-  mz_free(M);
-  if (e == hipErrorOutOfMemory) return KH_ERR_NOMEM;
-  if (e != hipSuccess || es != hipSuccess) return KH_ERR_HIP;
-  return st;
+  MzWork M(device, stream);
+  return sampled_impl(M, mz_args_ok(seq, n, k, w, hash), (uint64_t)w + k - 1, seq, n, k, w, canonical, hash, seed, where, fastq, out_kmers, out_pos, cap_out, n_out, device, stream);
 }
 // refusals of the syncmer calls that need no device: s, k for the key width, n, the hash and a null text
 bool sy_args_ok(uint32_t kw, const void* seq, uint64_t n, uint32_t k, uint32_t s, int hash) {
   return s >= 1 && s <= k && s <= 32 && k <= 32 * kw && !(n >> 32) && hash >= 0 && hash <= 3 && (seq || n == 0);
 }
-// closed syncmers of a text: minimizers_impl with the syncmer kernels; kw: 64-bit words per emitted k-mer
+// closed syncmers of a text: the minimizer route with the syncmer kernels; kw: 64-bit words per emitted k-mer
 kh_status syncmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, uint32_t s, int canonical, int hash, uint64_t seed, kh_mem where, bool fastq,
                         uint64_t* out_kmers, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, void* stream_) {
-  kh_table* t = nullptr;
-  if (n_out) *n_out = 0;
-  if (!n_out || !sy_args_ok(kw, seq, n, k, s, hash) || (out_kmers && !out_pos)) return KH_ERR_INVALID;
-  if (n < k) return KH_OK;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
-  MzWork M;
+  MzWork M(device, stream);
   M.s = s; M.kw = kw;
-  uint64_t total = 0;
-  kh_status st = mz_count(nullptr, M, seq, n, k, 0u, canonical, hash, seed, where, fastq, device, stream, &total);
-  if (st != KH_OK) return st;
-  *n_out = total;
-  if (!out_kmers || total == 0) { mz_free(M); return KH_OK; }
-  if (total > cap_out) { mz_free(M); return KH_ERR_INVALID; }       // (the total is known before anything is written)
-  uint64_t* dout = out_kmers; uint32_t* dpos = out_pos;
-  char* stage = nullptr;
-  hipError_t e = hipSuccess;
-  if (where == KH_MEM_HOST) {
-    e = pool_alloc(device, total * (8 * kw + 4), reinterpret_cast<void**>(&stage));
-    dout = reinterpret_cast<uint64_t*>(stage); dpos = reinterpret_cast<uint32_t*>(stage + total * 8 * kw);
-  }
-  if (e == hipSuccess) {
-    st = mz_emit(nullptr, M, stream, dout, dpos, 0u);
-    if (st == KH_OK && where == KH_MEM_HOST) {
-      e = hipMemcpyAsync(out_kmers, dout, total * 8 * kw, hipMemcpyDeviceToHost, stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(out_pos, dpos, total * 4, hipMemcpyDeviceToHost, stream);
-    }
-  }
-  const hipError_t es = hipStreamSynchronize(stream);
-  pool_free(device, stage);
-  mz_free(M);
-  if (e == hipErrorOutOfMemory) return KH_ERR_NOMEM;
-  if (e != hipSuccess || es != hipSuccess) return KH_ERR_HIP;
-  return st;
+  return sampled_impl(M, sy_args_ok(kw, seq, n, k, s, hash), k, seq, n, k, 0u, canonical, hash, seed, where, fastq, out_kmers, out_pos, cap_out, n_out, device, stream);
 }
 // the keep test on a batch of packed k-mers: out_mask u8[n] in the memory the keys live in
 kh_status syncmer_mask_impl(uint32_t kw, const void* keys, uint64_t n, uint32_t k, uint32_t s, int canonical, int hash, uint64_t seed, kh_mem where, uint8_t* out_mask,
                             int device, void* stream_) {
-  kh_table* t = nullptr;
   if (!sy_args_ok(kw, keys, n, k, s, hash)) return KH_ERR_INVALID;
   if (n == 0) return KH_OK;
   if (!out_mask) return KH_ERR_INVALID;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
-  const uint64_t* dk = static_cast<const uint64_t*>(keys);
-  uint8_t* dm = out_mask;
-  char* blk = nullptr;
-  hipError_t e = hipSuccess;
-  if (where == KH_MEM_HOST) {
-    HIPCHK(pool_alloc(device, n * 8 * kw + n, reinterpret_cast<void**>(&blk)));
-    e = hipMemcpyAsync(blk, keys, n * 8 * kw, hipMemcpyHostToDevice, stream);
-    dk = reinterpret_cast<const uint64_t*>(blk); dm = reinterpret_cast<uint8_t*>(blk + n * 8 * kw);
-  }
-  if (e == hipSuccess) {
-    const uint32_t grid = grid_for(n, 256);
+  HIPCHK0(hipSetDevice(device));
+  Scratch scr(device, stream);
+  const uint64_t* dk = nullptr; uint8_t* dm = nullptr;
+  if (!scr.layout([&](Scratch& c) { dk = c.in(static_cast<const uint64_t*>(keys), n * kw, where); dm = c.out(out_mask, n, where); })) return scr.finish();
+  const uint32_t grid = grid_for(n, 256);
 #define KH_SY_MASK(CANON, KW) KH_SWITCH_HASH(hash, hipLaunchKernelGGL((k_syncmer_mask<HASH, CANON, KW>), dim3(grid), dim3(256), 0, stream, dk, n, k, s, seed, dm))
-    if (kw == 2) { if (canonical) { KH_SY_MASK(true, 2); } else { KH_SY_MASK(false, 2); } }
-    else if (canonical) { KH_SY_MASK(true, 1); }
-    else { KH_SY_MASK(false, 1); }
+  if (kw == 2) { if (canonical) { KH_SY_MASK(true, 2); } else { KH_SY_MASK(false, 2); } }
+  else if (canonical) { KH_SY_MASK(true, 1); }
+  else { KH_SY_MASK(false, 1); }
 #undef KH_SY_MASK
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && where == KH_MEM_HOST) e = hipMemcpyAsync(out_mask, dm, n, hipMemcpyDeviceToHost, stream);
-  const hipError_t es = hipStreamSynchronize(stream);
-  pool_free(device, blk);
-  return e == hipSuccess && es == hipSuccess ? KH_OK : KH_ERR_HIP;
+  scr.launched();
+  scr.copy_back(dm, n);
+  scr.sync();      // (device memory too: the mask is ready when the call returns)
+  return scr.finish();
 }
 }  // namespace
 extern "C" {
@@ -2657,13 +2672,12 @@ struct kh_hll {
 };
 extern "C" {
 kh_status kh_hll_create(kh_hll** out, uint32_t precision, uint32_t ignore_msb, kh_hash hash, uint64_t seed, int device) {
-  kh_table* t = nullptr;
   if (!out) return KH_ERR_INVALID;
   *out = nullptr;
   if (precision < 4 || precision > 18 || precision + ignore_msb >= 64 || (int)hash < 0 || (int)hash > 3) return KH_ERR_INVALID;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return KH_ERR_HIP;
-  HIPCHK(hipSetDevice(device));
+  HIPCHK0(hipSetDevice(device));
   kh_hll* h = new kh_hll();
   h->device = device; h->hash = (int)hash; h->seed = seed; h->precision = precision; h->ignored = ignore_msb; h->stream = nullptr; h->regs = nullptr;
   if (pool_alloc(device, sizeof(uint32_t) << precision, reinterpret_cast<void**>(&h->regs)) != hipSuccess) { delete h; return KH_ERR_NOMEM; }
@@ -2690,20 +2704,14 @@ kh_status kh_hll_set_stream(kh_hll* h, void* s) {
 }
 // kw: 64-bit words per key (2: 16-byte keys, from_keys only)
 static kh_status hll_update(kh_hll* h, const void* in, uint64_t n, kh_mem where, bool from_keys, uint32_t kw = 1) {
-  kh_table* t = nullptr;
   if (!h) return KH_ERR_INVALID;
   if (n == 0) return KH_OK;
   if (!in) return KH_ERR_INVALID;
   if (kw == 2 && where == KH_MEM_DEVICE && (reinterpret_cast<uintptr_t>(in) & 15u) != 0) return KH_ERR_INVALID;      // one 16-byte load per key
-  HIPCHK(hipSetDevice(h->device));
-  const uint64_t* d = static_cast<const uint64_t*>(in);
-  uint64_t* tmp = nullptr;
-  if (where == KH_MEM_HOST) {
-    HIPCHK(pool_alloc(h->device, n * 8 * kw, reinterpret_cast<void**>(&tmp)));
-    hipError_t e = hipMemcpyAsync(tmp, in, n * 8 * kw, hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) { pool_free(h->device, tmp); return KH_ERR_HIP; }
-    d = tmp;
-  }
+  HIPCHK0(hipSetDevice(h->device));
+  Scratch s(h->device, h->stream);
+  const uint64_t* d = nullptr;
+  if (!s.layout([&](Scratch& c) { d = c.in(static_cast<const uint64_t*>(in), n * kw, where); })) return s.finish();
   const int use_lds = h->precision <= 13 ? 1 : 0;
   const size_t smem = use_lds ? (sizeof(uint32_t) << h->precision) : 0;
   const uint32_t grid = grid_for(n, 256, 1024);
@@ -2711,9 +2719,8 @@ static kh_status hll_update(kh_hll* h, const void* in, uint64_t n, kh_mem where,
   if (kw == 2) { KH_SWITCH_HASH(h->hash, hipLaunchKernelGGL((k_hll_update<HASH, KH_HLL_WIDE_KEYS>), dim3(grid), dim3(256), smem, h->stream, d, n, h->seed, R)); }
   else if (from_keys) { KH_SWITCH_HASH(h->hash, hipLaunchKernelGGL((k_hll_update<HASH, KH_HLL_KEYS>), dim3(grid), dim3(256), smem, h->stream, d, n, KhSeed{h->seed, 0u}, R)); }
   else hipLaunchKernelGGL((k_hll_update<KHH_IDENTITY, KH_HLL_HASHVALS>), dim3(grid), dim3(256), smem, h->stream, d, n, KhSeed{h->seed, 0u}, R);
-  hipError_t e = hipGetLastError();
-  if (tmp) { if (e == hipSuccess) e = hipStreamSynchronize(h->stream); pool_free(h->device, tmp); }
-  return e == hipSuccess ? KH_OK : KH_ERR_HIP;
+  s.launched();
+  return s.finish();
 }
 kh_status kh_hll_update(kh_hll* h, const void* keys, uint64_t n, kh_mem where) { return hll_update(h, keys, n, where, true); }
 kh_status kh_hll_update_via_hashval(kh_hll* h, const void* hashes, uint64_t n, kh_mem where) { return hll_update(h, hashes, n, where, false); }
@@ -2721,64 +2728,45 @@ kh_status kh_hll_update_wide(kh_hll* h, const void* keys, uint64_t n, kh_mem whe
 
 // the fused text pass: text [-> k_fastq_mask] -> k_hll_from_text.  Grid: min(tiles of KH_KM_TILE positions, KH_HLL_TEXT_WGS_PER_CU x CUs).
 static kh_status hll_from_text(kh_hll* h, const void* text, uint64_t n, uint32_t k, int canonical, kh_mem where, bool fastq, uint64_t* n_kmers) {
-  kh_table* t = nullptr;
   if (n_kmers) *n_kmers = 0;
   if (!h || k < 1 || k > 64) return KH_ERR_INVALID;
   if (n < k) return KH_OK;      // (n == 0 included) no window: the registers stay as they are
   if (!text) return KH_ERR_INVALID;
-  HIPCHK(hipSetDevice(h->device));
-  if (!h->ncu) {
-    int ncu = 0;
-    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
-    h->ncu = ncu > 0 ? ncu : 1;
-  }
-  // workspace: [window counter, 256 B] [text copy (host input)] [masked text (FASTQ)] [line sums] [line offsets]
-  const uint64_t ntl = (n + KH_CMP_TILE - 1) / KH_CMP_TILE, nkt = (n + KH_KM_TILE - 1) / KH_KM_TILE;
-  const size_t sz_txt = (n + 255) & ~size_t(255);
-  const size_t sz_seq = where == KH_MEM_HOST ? sz_txt : 0, sz_msk = fastq ? sz_txt : 0;
-  const size_t sz_sum = fastq ? ((ntl * 4 + 255) & ~size_t(255)) : 0, sz_off = fastq ? (((ntl + 1) * 8 + 255) & ~size_t(255)) : 0;
-  const size_t need = 256 + sz_seq + sz_msk + sz_sum + sz_off;
-  if (h->ws && h->ws_stream != h->stream) HIPCHK(hipStreamSynchronize(h->ws_stream));      // its last user ran on another stream
+  HIPCHK0(hipSetDevice(h->device));
+  if (!h->ncu) h->ncu = cu_count(h->device);
+  // the estimator's own workspace, carved like a call's block: the window counter, then the text front end (line sums / offsets: FASTQ only)
+  Scratch s(h->device, h->stream);
+  unsigned long long* counter = nullptr;
+  TextFront F;
+  auto lay = [&](Scratch& c) { counter = c.take<unsigned long long>(1); F.carve(c, text, n, where, fastq, fastq ? cmp_tiles(n) : 0); };
+  const size_t need = s.measure(lay);
+  if (h->ws && h->ws_stream != h->stream) HIPCHK0(hipStreamSynchronize(h->ws_stream));      // its last user ran on another stream
   if (h->ws_cap < need) {
-    if (h->ws) { HIPCHK(hipStreamSynchronize(h->ws_stream)); pool_free(h->device, h->ws); h->ws = nullptr; h->ws_cap = 0; }
-    HIPCHK(pool_alloc(h->device, need, reinterpret_cast<void**>(&h->ws)));
+    if (h->ws) { HIPCHK0(hipStreamSynchronize(h->ws_stream)); pool_free(h->device, h->ws); h->ws = nullptr; h->ws_cap = 0; }
+    HIPCHK0(pool_alloc(h->device, need, reinterpret_cast<void**>(&h->ws)));
     h->ws_cap = need;
   }
   h->ws_stream = h->stream;
-  char* p = h->ws;
-  unsigned long long* counter = reinterpret_cast<unsigned long long*>(p); p += 256;
-  const uint8_t* dseq = static_cast<const uint8_t*>(text);
-  if (where == KH_MEM_HOST) {
-    HIPCHK(hipMemcpyAsync(p, text, n, hipMemcpyHostToDevice, h->stream));
-    dseq = reinterpret_cast<const uint8_t*>(p); p += sz_seq;
-  }
-  if (fastq) {
-    uint8_t* msk = reinterpret_cast<uint8_t*>(p); p += sz_msk;
-    uint32_t* sums = reinterpret_cast<uint32_t*>(p); p += sz_sum;
-    uint64_t* offs = reinterpret_cast<uint64_t*>(p);
-    fastq_mask_text(dseq, n, sums, offs, msk, h->stream);
-    dseq = msk;
-  }
-  if (n_kmers) HIPCHK(hipMemsetAsync(counter, 0, 8, h->stream)); else counter = nullptr;
+  s.carve(h->ws, lay);
+  if (!s.ok()) return s.finish();
+  F.mask(n, h->stream);
+  const uint8_t* dseq = F.text;
+  if (n_kmers) s.zero(counter, 8); else counter = nullptr;
   const int use_lds = h->precision <= 13 ? 1 : 0;
   const size_t smem = use_lds ? (sizeof(uint32_t) << h->precision) : 0;
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(nkt, (uint64_t)KH_HLL_TEXT_WGS_PER_CU * (uint64_t)h->ncu);
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(km_tiles(n), (uint64_t)KH_HLL_TEXT_WGS_PER_CU * (uint64_t)h->ncu);
   const KhHllRegs R{h->regs, h->precision, h->ignored, use_lds};
 #define KH_HLL_TEXT_LAUNCH(KW, CANON) \
   KH_SWITCH_HASH(h->hash, hipLaunchKernelGGL((k_hll_from_text<HASH, KW, CANON>), dim3(grid), dim3(KH_KM_THREADS), smem, h->stream, dseq, n, k, h->seed, R, counter))
   if (k > 32) { if (canonical) { KH_HLL_TEXT_LAUNCH(2, true); } else { KH_HLL_TEXT_LAUNCH(2, false); } }
   else { if (canonical) { KH_HLL_TEXT_LAUNCH(1, true); } else { KH_HLL_TEXT_LAUNCH(1, false); } }
 #undef KH_HLL_TEXT_LAUNCH
-  HIPCHK(hipGetLastError());
-  if (n_kmers) {
-    unsigned long long total = 0;
-    HIPCHK(hipMemcpyAsync(&total, counter, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    *n_kmers = total;
-  } else if (where == KH_MEM_HOST) {
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  return KH_OK;
+  s.launched();
+  unsigned long long total = 0;
+  if (n_kmers) s.read(&total, counter);
+  const kh_status st = s.finish();      // (waits for the count or for a host text; a call on device memory without a count only queues)
+  if (st == KH_OK && n_kmers) *n_kmers = total;
+  return st;
 }
 kh_status kh_hll_update_from_sequence(kh_hll* h, const void* seq, uint64_t n, uint32_t k, int canonical, kh_mem where, uint64_t* n_kmers) {
   return hll_from_text(h, seq, n, k, canonical, where, false, n_kmers);
@@ -2787,30 +2775,27 @@ kh_status kh_hll_update_from_fastq(kh_hll* h, const void* text, uint64_t n, uint
   return hll_from_text(h, text, n, k, canonical, where, true, n_kmers);
 }
 kh_status kh_hll_merge(kh_hll* h, const kh_hll* other) {
-  kh_table* t = nullptr;
   if (!h || !other || h->precision != other->precision || h->device != other->device) return KH_ERR_INVALID;
-  HIPCHK(hipSetDevice(h->device));
+  HIPCHK0(hipSetDevice(h->device));
   const uint32_t m = 1u << h->precision;
-  if (other->stream != h->stream) HIPCHK(hipStreamSynchronize(other->stream));      // other's pending updates land before its registers are read
+  if (other->stream != h->stream) HIPCHK0(hipStreamSynchronize(other->stream));      // other's pending updates land before its registers are read
   hipLaunchKernelGGL(k_hll_merge, dim3((m + 255) / 256), dim3(256), 0, h->stream, h->regs, other->regs, m);
-  HIPCHK(hipGetLastError());
+  HIPCHK0(hipGetLastError());
   return KH_OK;
 }
 kh_status kh_hll_clear(kh_hll* h) {
-  kh_table* t = nullptr;
   if (!h) return KH_ERR_INVALID;
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipMemsetAsync(h->regs, 0, sizeof(uint32_t) << h->precision, h->stream));
+  HIPCHK0(hipSetDevice(h->device));
+  HIPCHK0(hipMemsetAsync(h->regs, 0, sizeof(uint32_t) << h->precision, h->stream));
   return KH_OK;
 }
 kh_status kh_hll_registers(kh_hll* h, uint8_t* out_host) {
-  kh_table* t = nullptr;
   if (!h || !out_host) return KH_ERR_INVALID;
-  HIPCHK(hipSetDevice(h->device));
+  HIPCHK0(hipSetDevice(h->device));
   const uint32_t m = 1u << h->precision;
   std::vector<uint32_t> r(m);
-  HIPCHK(hipMemcpyAsync(r.data(), h->regs, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK0(hipMemcpyAsync(r.data(), h->regs, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK0(hipStreamSynchronize(h->stream));
   for (uint32_t i = 0; i < m; ++i) out_host[i] = (uint8_t)r[i];
   return KH_OK;
 }
@@ -3051,8 +3036,7 @@ kh_status kw_do_find(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, u
   uint32_t* dv = out_vals; uint8_t* df = out_found;
   if (compacted || (host && dv) || !dv) TAKE(dv, uint32_t, n);
   if (compacted || host || !df) TAKE(df, uint8_t, n);
-  int ncu = 256;
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, t->device);
+  const int ncu = cu_count(t);
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + KW_Q_THREADS * KW_Q_ITEMS - 1) / (KW_Q_THREADS * KW_Q_ITEMS), (uint64_t)ncu * 8));
   { Launch L(t, count_only ? "kw_count" : "kw_find");
     if (count_only) { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((kw_find<HASH, KW_FIND_COUNT>), dim3(grid), dim3(KW_Q_THREADS), 0, t->stream, wide(t->cur), q, n, t->seed.s, dv, df, (unsigned long long*)nullptr)); }
@@ -3382,13 +3366,18 @@ void index_launch_lookup(kh_index* x, const uint64_t* q, uint64_t n, uint32_t* b
   }
 }
 // exclusive scan of n (> 0) device counts into n + 1 offsets of type OUT; ssums: ull[tiles + 1] of workspace
+// (ssums[tiles] is left holding the total)
+template <typename OUT>
+void scan_counts(hipStream_t stream, const uint32_t* counts, uint64_t n, unsigned long long* ssums, OUT* out) {
+  const uint64_t nst = (n + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
+  hipLaunchKernelGGL(k_index_tile_sums, dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, counts, n, ssums);
+  hipLaunchKernelGGL(k_index_scan_sums, dim3(1), dim3(KI_SUMS_THREADS), 0, stream, ssums, nst);
+  hipLaunchKernelGGL((k_index_scan_apply<OUT>), dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, counts, n, (const unsigned long long*)ssums, out);
+}
 template <typename OUT>
 kh_status index_scan(kh_table* t, const uint32_t* counts, uint64_t n, unsigned long long* ssums, OUT* out) {
-  const uint64_t nst = (n + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
   Launch L(t, "k_index_scan");
-  hipLaunchKernelGGL(k_index_tile_sums, dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, t->stream, counts, n, ssums);
-  hipLaunchKernelGGL(k_index_scan_sums, dim3(1), dim3(KI_SUMS_THREADS), 0, t->stream, ssums, nst);
-  hipLaunchKernelGGL((k_index_scan_apply<OUT>), dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, t->stream, counts, n, (const unsigned long long*)ssums, out);
+  scan_counts(t->stream, counts, n, ssums, out);
   HIPCHK(hipGetLastError());
   return KH_OK;
 }
@@ -3563,22 +3552,13 @@ kh_status index_pairs(kh_index* x, const void* keys, const void* pos, uint64_t n
   if (!keys || !pos) return xfail(x, KH_ERR_INVALID, "null argument");
   kh_table* t = x->t;
   HIPCHK(hipSetDevice(x->device));
-  const uint64_t* dk = static_cast<const uint64_t*>(keys);
-  const uint32_t* dp = static_cast<const uint32_t*>(pos);
-  char* blk = nullptr;
-  hipError_t e = hipSuccess;
-  if (where == KH_MEM_HOST) {          // (not in the table's workspace: the counting insert resets it)
-    const uint64_t kb = n * 8 * x->kw;
-    HIPCHK(pool_alloc(x->device, kb + n * 4, reinterpret_cast<void**>(&blk)));
-    e = hipMemcpyAsync(blk, keys, kb, hipMemcpyHostToDevice, t->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(blk + kb, pos, n * 4, hipMemcpyHostToDevice, t->stream);
-    dk = reinterpret_cast<const uint64_t*>(blk); dp = reinterpret_cast<const uint32_t*>(blk + kb);
-  }
-  kh_status st = KH_ERR_HIP;
-  if (e == hipSuccess) st = append ? index_append_device(x, dk, dp, n) : index_build_device(x, dk, dp, n);
-  else fail(t, KH_ERR_HIP, "kh_index_build: staging the pairs failed");
-  hipStreamSynchronize(t->stream);
-  pool_free(x->device, blk);
+  Scratch s(x->device, t->stream);      // (host pairs: not in the table's workspace, the counting insert resets it)
+  const uint64_t* dk = nullptr; const uint32_t* dp = nullptr;
+  s.layout([&](Scratch& c) { dk = c.in(static_cast<const uint64_t*>(keys), n * x->kw, where); dp = c.in(static_cast<const uint32_t*>(pos), n, where); });
+  if (!s.ok()) { const hipError_t e = s.error(); s.finish(); return hip_fail(t, "kh_index_build: staging the pairs", e); }      // (the index is untouched)
+  const kh_status st = append ? index_append_device(x, dk, dp, n) : index_build_device(x, dk, dp, n);
+  s.sync();
+  s.finish();
   return st == KH_OK ? KH_OK : index_abandon(x, st);
 }
 // what a stranded index refuses before it is touched: the strand is that of the canonical choice, and a stamped position has 31 bits
@@ -3612,16 +3592,14 @@ kh_status index_text(kh_index* x, const void* text, uint64_t n, uint32_t k, int 
   kh_table* t = x->t;
   HIPCHK(hipSetDevice(x->device));
   // host text is staged once; k-mers and positions never leave the device
-  const size_t sz_text = where == KH_MEM_HOST ? ((n + 255) & ~size_t(255)) : 0;
-  char* blk = nullptr;
-  HIPCHK(pool_alloc(x->device, sz_text + n * (8 * x->kw + 4), reinterpret_cast<void**>(&blk)));
-  const void* dtext = text;
-  hipError_t e = hipSuccess;
-  if (where == KH_MEM_HOST) { e = hipMemcpyAsync(blk, text, n, hipMemcpyHostToDevice, t->stream); dtext = blk; }
-  uint64_t* dk = reinterpret_cast<uint64_t*>(blk + sz_text);
-  uint32_t* dp = reinterpret_cast<uint32_t*>(blk + sz_text + n * 8 * x->kw);
+  Scratch s(x->device, t->stream);
+  TextFront F;      // (staging only: the k-mer front end masks and scans in a block of its own)
+  uint64_t* dk = nullptr; uint32_t* dp = nullptr;
+  s.layout([&](Scratch& c) { F.carve(c, text, n, where, false, 0); dk = c.take<uint64_t>(n * x->kw); dp = c.take<uint32_t>(n); });
+  if (!s.ok()) { const hipError_t e = s.error(); s.finish(); return hip_fail(t, "kh_index: scratch for the k-mers", e); }
+  const void* dtext = F.text;
   uint64_t m = 0;
-  kh_status st = e == hipSuccess ? kmers_impl(x->kw, dtext, n, k, canonical, KH_MEM_DEVICE, fastq, dk, &m, x->device, t->stream, dp) : KH_ERR_HIP;
+  kh_status st = kmers_impl(x->kw, dtext, n, k, canonical, KH_MEM_DEVICE, fastq, dk, &m, x->device, t->stream, dp);
   bool touched = !append;      // (a build starts from an empty index: abandoning it changes nothing)
   if (st != KH_OK) fail(t, st, "kh_index: k-mer generation failed");
   else if (append && (x->total + m) >> 32) st = fail(t, KH_ERR_INVALID, "kh_index_append: offsets are 32-bit, the index must stay below 2^32 positions");
@@ -3634,8 +3612,8 @@ kh_status index_text(kh_index* x, const void* text, uint64_t n, uint32_t k, int 
     }
     if (st == KH_OK) st = append ? index_append_device(x, dk, dp, m) : index_build_device(x, dk, dp, m);
   }
-  hipStreamSynchronize(t->stream);
-  pool_free(x->device, blk);
+  s.sync();
+  s.finish();
   if (st == KH_OK) return KH_OK;
   return touched ? index_abandon(x, st) : xfail(x, st, t->err);
 }
@@ -3658,28 +3636,24 @@ kh_status index_minimizers(kh_index* x, const void* text, uint64_t n, uint32_t k
   if (!text) return xfail(x, KH_ERR_INVALID, "null text");
   kh_table* t = x->t;
   HIPCHK(hipSetDevice(x->device));
-  MzWork M;
+  MzWork M(x->device, t->stream);
   if (syncmers) { M.s = w; M.kw = x->kw; }
   uint64_t m = 0;
-  kh_status st = mz_count(t, M, text, n, k, w, canonical, hash, seed, where, fastq, x->device, t->stream, &m);
+  kh_status st = mz_count(t, M, text, n, k, w, canonical, hash, seed, where, fastq, t->stream, &m);
   if (st != KH_OK) return xfail(x, st, t->err);
-  if (append && (x->total + m) >> 32) { mz_free(M); return xfail(x, KH_ERR_INVALID, "kh_index_append: offsets are 32-bit, the index must stay below 2^32 positions"); }
-  if (m == 0) { mz_free(M); return KH_OK; }
-  char* pairs = nullptr;
-  const hipError_t e = pool_alloc(x->device, m * (8 * x->kw + 4), reinterpret_cast<void**>(&pairs));
-  if (e != hipSuccess) { mz_free(M); return xfail(x, e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP, "kh_index: no memory for the sampled pairs"); }
-  uint64_t* dk = reinterpret_cast<uint64_t*>(pairs);
-  uint32_t* dp = reinterpret_cast<uint32_t*>(pairs + m * 8 * x->kw);
+  if (append && (x->total + m) >> 32) return xfail(x, KH_ERR_INVALID, "kh_index_append: offsets are 32-bit, the index must stay below 2^32 positions");
+  if (m == 0) return KH_OK;
+  uint64_t* dk = nullptr; uint32_t* dp = nullptr;
+  if (!M.scr.layout([&](Scratch& c) { dk = c.take<uint64_t>(m * x->kw); dp = c.take<uint32_t>(m); })) return xfail(x, M.scr.finish(), "kh_index: no memory for the sampled pairs");
   st = mz_emit(t, M, t->stream, dk, dp, append && !x->stranded ? pos_base : 0u);
-  if (st == KH_OK && x->stranded) st = index_stamp(x, M.dseq, n, k, dp, m, append ? pos_base : 0u);      // (FASTQ: the masked text; sequence lines are kept in it)
+  if (st == KH_OK && x->stranded) st = index_stamp(x, M.F.text, n, k, dp, m, append ? pos_base : 0u);      // (FASTQ: the masked text; sequence lines are kept in it)
   bool touched = !append;      // (a build starts from an empty index: abandoning it changes nothing)
   if (st == KH_OK) {
     touched = true;
     st = append ? index_append_device(x, dk, dp, m) : index_build_device(x, dk, dp, m);
   }
-  hipStreamSynchronize(t->stream);
-  pool_free(x->device, pairs);
-  mz_free(M);
+  M.scr.sync();
+  M.scr.finish();
   if (st == KH_OK) return KH_OK;
   return touched ? index_abandon(x, st) : xfail(x, st, t->err);
 }
@@ -3953,157 +3927,103 @@ kh_status kh_wide_index_find(kh_windex* x, const void* keys, uint64_t n, kh_mem 
   return kh_index_find(x, keys, n, where, out_offsets, out_pos, cap_out, n_out);
 }
 
-// ---- a permuted CSR back into query order (kernels: kh_kernels_csr.h).  No handle: device buffers, the caller's stream.  One
-//      allocation holds every temporary; it is freed on every path after the stream has drained.
+// ---- a permuted CSR back into query order (kernels: kh_kernels_csr.h).  No handle: device buffers, the caller's stream.
 kh_status kh_csr_unpermute(const uint32_t* counts_perm, const uint32_t* pos_perm, const uint32_t* origin, uint64_t n, uint32_t* out_counts,
                            uint64_t* out_offsets, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, void* stream_) {
-  kh_table* t = nullptr;
   if (n >> 32) return KH_ERR_INVALID;
   if (n_out) *n_out = 0;
   if (n && (!counts_perm || !origin)) return KH_ERR_INVALID;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (n == 0) {
     if (!out_offsets) return KH_OK;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMemsetAsync(out_offsets, 0, 8, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK0(hipSetDevice(device));
+    HIPCHK0(hipMemsetAsync(out_offsets, 0, 8, stream));
+    HIPCHK0(hipStreamSynchronize(stream));
     return KH_OK;
   }
-  HIPCHK(hipSetDevice(device));
+  HIPCHK0(hipSetDevice(device));
   const uint64_t nst = (n + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
-  // ssums ull[nst + 1] | offsets u64[n + 1] (unless the caller's) | begin_perm u32[n + 1] | begin_q u32[n] | counts u32[n] (unless the caller's)
-  const size_t b_ssums = (nst + 1) * 8, b_off = out_offsets ? 0 : (n + 1) * 8, b_bp = (n + 2) / 2 * 8, b_bq = (n + 1) / 2 * 8, b_cq = out_counts ? 0 : n * 4;
-  char* blk = nullptr;
-  HIPCHK(pool_alloc(device, b_ssums + b_off + b_bp + b_bq + b_cq, reinterpret_cast<void**>(&blk)));
-  unsigned long long* ssums = reinterpret_cast<unsigned long long*>(blk);
-  uint64_t* doff = out_offsets ? out_offsets : reinterpret_cast<uint64_t*>(blk + b_ssums);
-  uint32_t* begin_perm = reinterpret_cast<uint32_t*>(blk + b_ssums + b_off);
-  uint32_t* begin_q = reinterpret_cast<uint32_t*>(blk + b_ssums + b_off + b_bp);
-  uint32_t* cq = out_counts ? out_counts : reinterpret_cast<uint32_t*>(blk + b_ssums + b_off + b_bp + b_bq);
-  int ncu = 256;
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
-  if (ncu <= 0) ncu = 256;
+  Scratch s(device, stream);
+  unsigned long long* ssums = nullptr; uint64_t* doff = nullptr; uint32_t *begin_perm = nullptr, *begin_q = nullptr, *cq = nullptr;
+  if (!s.layout([&](Scratch& c) {
+        ssums = c.take<unsigned long long>(nst + 1);
+        doff = out_offsets ? out_offsets : c.take<uint64_t>(n + 1);      // (the caller's, where it gave one)
+        begin_perm = c.take<uint32_t>(n + 1);
+        begin_q = c.take<uint32_t>(n);
+        cq = out_counts ? out_counts : c.take<uint32_t>(n);
+      })) return s.finish();
+  const uint32_t ncu = (uint32_t)cu_count(device);
   uint64_t total = 0;
   kh_status st = KH_OK;
   // 1. where every permuted slot's segment begins; the total is known (and checked) before any output is written
-  hipLaunchKernelGGL(k_index_tile_sums, dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, counts_perm, n, ssums);
-  hipLaunchKernelGGL(k_index_scan_sums, dim3(1), dim3(KI_SUMS_THREADS), 0, stream, ssums, nst);
-  hipLaunchKernelGGL((k_index_scan_apply<uint32_t>), dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, counts_perm, n, (const unsigned long long*)ssums, begin_perm);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(&total, ssums + nst, 8, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e == hipSuccess && (total >> 32)) st = KH_ERR_INVALID;
-  if (e == hipSuccess && st == KH_OK) {
+  scan_counts(stream, counts_perm, n, ssums, begin_perm);
+  s.launched();
+  s.read(&total, (const uint64_t*)(ssums + nst));
+  if (s.sync() && (total >> 32)) st = KH_ERR_INVALID;
+  if (s.ok() && st == KH_OK) {
     if (n_out) *n_out = total;
     // 2. counts and begins to their query; 3. the query-order offsets
-    hipLaunchKernelGGL(k_csr_scatter, dim3(grid_for(n, KC_THREADS, (uint32_t)ncu * 8)), dim3(KC_THREADS), 0, stream, counts_perm, (const uint32_t*)begin_perm, origin, n, cq, begin_q);
+    hipLaunchKernelGGL(k_csr_scatter, dim3(grid_for(n, KC_THREADS, ncu * 8)), dim3(KC_THREADS), 0, stream, counts_perm, (const uint32_t*)begin_perm, origin, n, cq, begin_q);
     const bool move = out_pos && total && total <= cap_out;
-    if (out_offsets || move) {
-      hipLaunchKernelGGL(k_index_tile_sums, dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, (const uint32_t*)cq, n, ssums);
-      hipLaunchKernelGGL(k_index_scan_sums, dim3(1), dim3(KI_SUMS_THREADS), 0, stream, ssums, nst);
-      hipLaunchKernelGGL((k_index_scan_apply<uint64_t>), dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, (const uint32_t*)cq, n, (const unsigned long long*)ssums, doff);
-    }
+    if (out_offsets || move) scan_counts(stream, (const uint32_t*)cq, n, ssums, doff);
     if (out_pos && total > cap_out) st = KH_ERR_INVALID;
     else if (move && !pos_perm) st = KH_ERR_INVALID;
     // 4. the segments, one output element per lane
     else if (move)
-      hipLaunchKernelGGL(k_index_gather, dim3(grid_for(total, 256, (uint32_t)ncu * 8)), dim3(256), 0, stream, pos_perm, (const uint32_t*)begin_q, (const uint64_t*)doff, n, total, out_pos);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+      hipLaunchKernelGGL(k_index_gather, dim3(grid_for(total, 256, ncu * 8)), dim3(256), 0, stream, pos_perm, (const uint32_t*)begin_q, (const uint64_t*)doff, n, total, out_pos);
+    s.launched();
   }
-  pool_free(device, blk);
-  if (e != hipSuccess) return e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP;
-  return st;
+  const kh_status fs = s.finish();
+  return fs != KH_OK ? fs : st;
 }
 
 // ---- strand of window positions (kernel: k_pos_strand in kh_kernels_index.h).  No handle.  Device memory: nothing is allocated and the
 //      call only queues its kernel unless n_invalid is asked for; host memory: text and positions are staged in one pooled block.
 kh_status kh_stamp_strand(const void* text, uint64_t n, uint32_t k, const uint32_t* pos, uint64_t m, uint32_t pos_base, kh_mem where, uint32_t* out,
                           uint64_t* n_invalid, int device, void* stream_) {
-  kh_table* t = nullptr;
   if (n_invalid) *n_invalid = 0;
   if (k < 1 || k > 64 || (n >> 31) || (uint64_t)pos_base + n > (uint64_t(1) << 31)) return KH_ERR_INVALID;
   if (m == 0) return KH_OK;
   if (!pos || !out || (!text && n)) return KH_ERR_INVALID;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
-  const bool host = where == KH_MEM_HOST;
-  // [text copy] [positions, stamped in place] (host input) [counter]
-  const size_t sz_text = host ? ((n + 255) & ~size_t(255)) : 0, sz_pos = host ? ((m * 4 + 255) & ~size_t(255)) : 0, sz_cnt = n_invalid ? 256 : 0;
-  char* blk = nullptr;
-  if (sz_text + sz_pos + sz_cnt) HIPCHK(pool_alloc(device, sz_text + sz_pos + sz_cnt, reinterpret_cast<void**>(&blk)));
-  const uint8_t* dtext = static_cast<const uint8_t*>(text);
-  const uint32_t* dpos = pos;
-  uint32_t* dout = out;
-  unsigned long long* dcnt = n_invalid ? reinterpret_cast<unsigned long long*>(blk + sz_text + sz_pos) : nullptr;
-  hipError_t e = hipSuccess;
-  if (host) {
-    if (n) e = hipMemcpyAsync(blk, text, n, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(blk + sz_text, pos, m * 4, hipMemcpyHostToDevice, stream);
-    dtext = reinterpret_cast<const uint8_t*>(blk); dout = reinterpret_cast<uint32_t*>(blk + sz_text); dpos = dout;
-  }
-  if (e == hipSuccess && dcnt) e = hipMemsetAsync(dcnt, 0, 8, stream);
-  if (e == hipSuccess) {
-    int ncu = 256;
-    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
-    if (ncu <= 0) ncu = 256;
-    hipLaunchKernelGGL((k_pos_strand<true>), dim3(grid_for(m, 256, (uint32_t)ncu * 8)), dim3(256), 0, stream, dtext, n, k, dpos, m, pos_base, dout, dcnt);
-    e = hipGetLastError();
-  }
+  HIPCHK0(hipSetDevice(device));
+  Scratch s(device, stream);
+  const uint8_t* dtext = nullptr; const uint32_t* dpos = nullptr; uint32_t* dout = nullptr; unsigned long long* dcnt = nullptr;
+  if (!s.layout([&](Scratch& c) {
+        dtext = c.in(static_cast<const uint8_t*>(text), n, where);
+        dpos = c.in(pos, m, where);
+        dout = c.out(out, m, where);
+        dcnt = c.take<unsigned long long>(n_invalid ? 1 : 0);
+      })) return s.finish();
+  if (dcnt) s.zero(dcnt, 8);
+  hipLaunchKernelGGL((k_pos_strand<true>), dim3(grid_for(m, 256, (uint32_t)cu_count(device) * 8)), dim3(256), 0, stream, dtext, n, k, dpos, m, pos_base, dout, dcnt);
+  s.launched();
   unsigned long long bad = 0;
-  if (e == hipSuccess && dcnt) e = hipMemcpyAsync(&bad, dcnt, 8, hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess && host) e = hipMemcpyAsync(out, dout, m * 4, hipMemcpyDeviceToHost, stream);
-  if (blk) {                                   // (staged input or a counter: the block is in use until the stream has drained)
-    const hipError_t e2 = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = e2;
-    pool_free(device, blk);
-  }
-  if (e != hipSuccess) return e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP;
-  if (n_invalid) *n_invalid = bad;
-  return KH_OK;
+  if (dcnt) s.read(&bad, dcnt);
+  s.copy_back(dout, m);
+  const kh_status st = s.finish();      // (staged arrays or a counter: waits; else the kernel is only queued)
+  if (st == KH_OK && n_invalid) *n_invalid = bad;
+  return st;
 }
 // ---- a CSR of hits over stamped positions into flat anchors (kernel: k_anchors_expand).  No handle; device memory: queued only.
 kh_status kh_anchors_from_csr(const uint32_t* qpos, const uint64_t* offsets, uint64_t n, const uint32_t* pos, uint64_t total, kh_mem where,
                               uint32_t* out_qpos, uint32_t* out_rpos, uint8_t* out_rev, int device, void* stream_) {
-  kh_table* t = nullptr;
   if (total >> 32) return KH_ERR_INVALID;
   if (n == 0 || total == 0) return KH_OK;
   if (!qpos || !offsets || !pos || !out_qpos || !out_rpos || !out_rev) return KH_ERR_INVALID;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
-  const bool host = where == KH_MEM_HOST;
-  char* blk = nullptr;
-  const uint64_t* doff = offsets;
-  const uint32_t *dq = qpos, *dp = pos;
-  uint32_t *oq = out_qpos, *orp = out_rpos; uint8_t* orv = out_rev;
-  hipError_t e = hipSuccess;
-  const size_t b_off = (n + 1) * 8, b_q = (n * 4 + 7) & ~size_t(7), b_p = (total * 4 + 7) & ~size_t(7);
-  if (host) {      // offsets u64[n + 1] | qpos u32[n] | pos u32[total] | out_qpos u32[total] | out_rpos u32[total] | out_rev u8[total]
-    HIPCHK(pool_alloc(device, b_off + b_q + 3 * b_p + total, reinterpret_cast<void**>(&blk)));
-    e = hipMemcpyAsync(blk, offsets, b_off, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(blk + b_off, qpos, n * 4, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(blk + b_off + b_q, pos, total * 4, hipMemcpyHostToDevice, stream);
-    doff = reinterpret_cast<const uint64_t*>(blk); dq = reinterpret_cast<const uint32_t*>(blk + b_off); dp = reinterpret_cast<const uint32_t*>(blk + b_off + b_q);
-    oq = reinterpret_cast<uint32_t*>(blk + b_off + b_q + b_p); orp = reinterpret_cast<uint32_t*>(blk + b_off + b_q + 2 * b_p);
-    orv = reinterpret_cast<uint8_t*>(blk + b_off + b_q + 3 * b_p);
-  }
-  if (e == hipSuccess) {
-    int ncu = 256;
-    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
-    if (ncu <= 0) ncu = 256;
-    hipLaunchKernelGGL(k_anchors_expand, dim3(grid_for(total, 256, (uint32_t)ncu * 8)), dim3(256), 0, stream, dq, doff, n, dp, total, oq, orp, orv);
-    e = hipGetLastError();
-  }
-  if (host) {
-    if (e == hipSuccess) e = hipMemcpyAsync(out_qpos, oq, total * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rpos, orp, total * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rev, orv, total, hipMemcpyDeviceToHost, stream);
-    const hipError_t e2 = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = e2;
-    pool_free(device, blk);
-  }
-  if (e != hipSuccess) return e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP;
-  return KH_OK;
+  HIPCHK0(hipSetDevice(device));
+  Scratch s(device, stream);
+  const uint64_t* doff = nullptr; const uint32_t *dq = nullptr, *dp = nullptr;
+  uint32_t *oq = nullptr, *orp = nullptr; uint8_t* orv = nullptr;
+  if (!s.layout([&](Scratch& c) {
+        doff = c.in(offsets, n + 1, where); dq = c.in(qpos, n, where); dp = c.in(pos, total, where);
+        oq = c.out(out_qpos, total, where); orp = c.out(out_rpos, total, where); orv = c.out(out_rev, total, where);
+      })) return s.finish();
+  hipLaunchKernelGGL(k_anchors_expand, dim3(grid_for(total, 256, (uint32_t)cu_count(device) * 8)), dim3(256), 0, stream, dq, doff, n, dp, total, oq, orp, orv);
+  s.launched();
+  s.copy_back(oq, total); s.copy_back(orp, total); s.copy_back(orv, total);
+  return s.finish();
 }
 // ---- collinear chains per segment from flat anchors (kernels: kh_kernels_chain.h).  No handle; one pooled block holds the scratch (and
 //      the staged arrays of a host call); every kernel is queued on the caller's stream and the one host wait is the one for *n_chains.
@@ -4111,7 +4031,6 @@ kh_status kh_chain_anchors(const uint32_t* qpos, const uint32_t* rpos, const uin
                            uint32_t lookback, uint32_t max_gap, uint32_t band, int32_t min_score, uint32_t min_count, kh_mem where, int32_t* out_score,
                            int32_t* out_pred, int32_t* out_chain, uint32_t* c_first, uint32_t* c_last, uint32_t* c_count, int32_t* c_score, uint64_t cap_chains,
                            uint64_t* n_chains, int device, void* stream_) {
-  kh_table* t = nullptr;
   const int n_tab = (c_first != nullptr) + (c_last != nullptr) + (c_count != nullptr) + (c_score != nullptr);
   if (k < 1 || k > 64 || lookback < 1 || lookback > 64 || max_gap < 1 || (max_gap >> 31) || (band >> 31)) return KH_ERR_INVALID;
   if (m > (uint64_t(1) << 24) || (where != KH_MEM_HOST && where != KH_MEM_DEVICE) || (n_tab != 0 && n_tab != 4)) return KH_ERR_INVALID;
@@ -4119,85 +4038,53 @@ kh_status kh_chain_anchors(const uint32_t* qpos, const uint32_t* rpos, const uin
   if (m && (!qpos || !rpos || !rev || !out_score || !out_pred || !out_chain)) return KH_ERR_INVALID;
   if (m == 0) { if (n_chains) *n_chains = 0; return KH_OK; }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK(hipSetDevice(device));
-  const bool host = where == KH_MEM_HOST, table = n_tab == 4;
+  HIPCHK0(hipSetDevice(device));
+  const bool table = n_tab == 4;
   const uint64_t nst = (m + KI_SCAN_TILE - 1) / KI_SCAN_TILE, tab = table ? std::min<uint64_t>(cap_chains, m) : 0;
-  auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-  // scratch: best child / flags i32[m] | count u32[m] | last u32[m] | bad u32 (these three zeroed) | chain numbers u32[m + 1] | tile sums u64[nst + 1]
-  const size_t b_a = up(m * 4), b_num = up((m + 1) * 4), b_sums = up((nst + 1) * 8), b_zero = 2 * b_a + 256;
-  // host call: qpos | rpos | rev | seg | score | pred | chain | 4 table columns
-  const size_t b_rev = host ? up(m) : 0, b_seg = host && seg_offsets ? up((n_seg + 1) * 8) : 0, b_col = host ? up(tab * 4) : 0;
-  const size_t b_scratch = b_a + b_zero + b_num + b_sums, b_stage = host ? 5 * b_a + b_rev + b_seg + 4 * b_col : 0;
-  char* blk = nullptr;
-  HIPCHK(pool_alloc(device, b_scratch + b_stage, reinterpret_cast<void**>(&blk)));
-  int32_t* bc = reinterpret_cast<int32_t*>(blk);
-  uint32_t* cnt = reinterpret_cast<uint32_t*>(blk + b_a);
-  uint32_t* last = reinterpret_cast<uint32_t*>(blk + 2 * b_a);
-  uint32_t* bad = reinterpret_cast<uint32_t*>(blk + 3 * b_a);
-  uint32_t* num = reinterpret_cast<uint32_t*>(blk + b_a + b_zero);
-  unsigned long long* ssums = reinterpret_cast<unsigned long long*>(blk + b_a + b_zero + b_num);
-  const uint32_t *dq = qpos, *dr = rpos; const uint8_t* dv = rev; const uint64_t* dseg = seg_offsets;
-  int32_t *df = out_score, *dp = out_pred, *dc = out_chain, *t_score = c_score;
-  uint32_t *t_first = c_first, *t_last = c_last, *t_count = c_count;
-  hipError_t e = hipSuccess;
-  if (host) {
-    char* s = blk + b_scratch;
-    e = hipMemcpyAsync(s, qpos, m * 4, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s + b_a, rpos, m * 4, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s + 2 * b_a, rev, m, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess && seg_offsets) e = hipMemcpyAsync(s + 2 * b_a + b_rev, seg_offsets, (n_seg + 1) * 8, hipMemcpyHostToDevice, stream);
-    dq = reinterpret_cast<const uint32_t*>(s); dr = reinterpret_cast<const uint32_t*>(s + b_a); dv = reinterpret_cast<const uint8_t*>(s + 2 * b_a);
-    if (seg_offsets) dseg = reinterpret_cast<const uint64_t*>(s + 2 * b_a + b_rev);
-    char* o = s + 2 * b_a + b_rev + b_seg;
-    df = reinterpret_cast<int32_t*>(o); dp = reinterpret_cast<int32_t*>(o + b_a); dc = reinterpret_cast<int32_t*>(o + 2 * b_a);
-    if (table) {
-      t_first = reinterpret_cast<uint32_t*>(o + 3 * b_a); t_last = reinterpret_cast<uint32_t*>(o + 3 * b_a + b_col);
-      t_count = reinterpret_cast<uint32_t*>(o + 3 * b_a + 2 * b_col); t_score = reinterpret_cast<int32_t*>(o + 3 * b_a + 3 * b_col);
-    }
-  }
-  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, b_zero, stream);
+  Scratch s(device, stream);
+  int32_t* bc = nullptr; uint32_t *cnt = nullptr, *last = nullptr, *bad = nullptr, *num = nullptr; unsigned long long* ssums = nullptr;
+  const uint32_t *dq = nullptr, *dr = nullptr; const uint8_t* dv = nullptr; const uint64_t* dseg = nullptr;
+  int32_t *df = nullptr, *dp = nullptr, *dc = nullptr, *t_score = nullptr;
+  uint32_t *t_first = nullptr, *t_last = nullptr, *t_count = nullptr;
+  if (!s.layout([&](Scratch& c) {
+        bc = c.take<int32_t>(m);                                                                   // best child, then the kept-chain flags
+        // taken in a row: one memset clears the three (bad: one word, taken as a whole 256 bytes so that the memset ends on the boundary)
+        cnt = c.take<uint32_t>(m); last = c.take<uint32_t>(m); bad = c.take<uint32_t>(64);
+        num = c.take<uint32_t>(m + 1);                                                             // chain numbers
+        ssums = c.take<unsigned long long>(nst + 1);
+        dq = c.in(qpos, m, where); dr = c.in(rpos, m, where); dv = c.in(rev, m, where);
+        dseg = c.in(seg_offsets, seg_offsets ? n_seg + 1 : 0, where);
+        df = c.out(out_score, m, where); dp = c.out(out_pred, m, where); dc = c.out(out_chain, m, where);
+        t_first = c.out(c_first, tab, where); t_last = c.out(c_last, tab, where); t_count = c.out(c_count, tab, where); t_score = c.out(c_score, tab, where);
+      })) return s.finish();
+  s.zero(cnt, reinterpret_cast<char*>(bad + 64) - reinterpret_cast<char*>(cnt));
+  const uint32_t ncu = (uint32_t)cu_count(device);
+  const uint32_t m32 = (uint32_t)m, ns32 = (uint32_t)n_seg;
+  const uint32_t gseg = grid_for(dseg ? n_seg : 1, KCH_WAVES, ncu * 8), gflat = grid_for(m, 256, ncu * 8);
+  const KchParams P{k, lookback, max_gap, band};
+  hipLaunchKernelGGL(k_chain_dp, dim3(gseg), dim3(KCH_THREADS), 0, stream, dq, dr, dv, m32, dseg, ns32, P, df, dp, bad);
+  hipLaunchKernelGGL(k_chain_link, dim3(gseg), dim3(KCH_THREADS), 0, stream, (const int32_t*)df, (const int32_t*)dp, m32, dseg, ns32, bc, dc, cnt, last);
+  uint32_t* flag = reinterpret_cast<uint32_t*>(bc);          // (the best children are done with)
+  hipLaunchKernelGGL((k_chain_emit<0>), dim3(gflat), dim3(256), 0, stream, (const int32_t*)df, (const int32_t*)dp, dc, m32, (const uint32_t*)cnt, (const uint32_t*)last,
+                     min_score, min_count, flag, (const uint32_t*)num, (const unsigned long long*)(ssums + nst), (const uint32_t*)bad, t_first, t_last, t_count, t_score, tab);
+  scan_counts(stream, (const uint32_t*)flag, m, ssums, num);
+  hipLaunchKernelGGL((k_chain_emit<1>), dim3(gflat), dim3(256), 0, stream, (const int32_t*)df, (const int32_t*)dp, dc, m32, (const uint32_t*)cnt, (const uint32_t*)last,
+                     min_score, min_count, flag, (const uint32_t*)num, (const unsigned long long*)(ssums + nst), (const uint32_t*)bad, t_first, t_last, t_count, t_score, tab);
+  s.launched();
   unsigned long long total = 0;
   uint32_t hbad = 0;
-  if (e == hipSuccess) {
-    int ncu = 256;
-    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
-    if (ncu <= 0) ncu = 256;
-    const uint32_t m32 = (uint32_t)m, ns32 = (uint32_t)n_seg;
-    const uint32_t gseg = grid_for(dseg ? n_seg : 1, KCH_WAVES, (uint32_t)ncu * 8), gflat = grid_for(m, 256, (uint32_t)ncu * 8);
-    const KchParams P{k, lookback, max_gap, band};
-    hipLaunchKernelGGL(k_chain_dp, dim3(gseg), dim3(KCH_THREADS), 0, stream, dq, dr, dv, m32, dseg, ns32, P, df, dp, bad);
-    hipLaunchKernelGGL(k_chain_link, dim3(gseg), dim3(KCH_THREADS), 0, stream, (const int32_t*)df, (const int32_t*)dp, m32, dseg, ns32, bc, dc, cnt, last);
-    uint32_t* flag = reinterpret_cast<uint32_t*>(bc);          // (the best children are done with)
-    hipLaunchKernelGGL((k_chain_emit<0>), dim3(gflat), dim3(256), 0, stream, (const int32_t*)df, (const int32_t*)dp, dc, m32, (const uint32_t*)cnt, (const uint32_t*)last,
-                       min_score, min_count, flag, (const uint32_t*)num, (const unsigned long long*)(ssums + nst), (const uint32_t*)bad, t_first, t_last, t_count, t_score, tab);
-    hipLaunchKernelGGL(k_index_tile_sums, dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, (const uint32_t*)flag, m, ssums);
-    hipLaunchKernelGGL(k_index_scan_sums, dim3(1), dim3(KI_SUMS_THREADS), 0, stream, ssums, nst);
-    hipLaunchKernelGGL((k_index_scan_apply<uint32_t>), dim3((uint32_t)nst), dim3(KI_SCAN_THREADS), 0, stream, (const uint32_t*)flag, m, (const unsigned long long*)ssums, num);
-    hipLaunchKernelGGL((k_chain_emit<1>), dim3(gflat), dim3(256), 0, stream, (const int32_t*)df, (const int32_t*)dp, dc, m32, (const uint32_t*)cnt, (const uint32_t*)last,
-                       min_score, min_count, flag, (const uint32_t*)num, (const unsigned long long*)(ssums + nst), (const uint32_t*)bad, t_first, t_last, t_count, t_score, tab);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, ssums + nst, 8, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, stream);
-  }
-  { const hipError_t e2 = hipStreamSynchronize(stream); if (e == hipSuccess) e = e2; }
+  s.read(&total, (const unsigned long long*)(ssums + nst));
+  s.read(&hbad, (const uint32_t*)bad);
+  s.sync();      // the one host wait of a device call: *n_chains
   kh_status st = KH_OK;
-  if (e == hipSuccess && hbad) { st = KH_ERR_INVALID; total = 0; }
-  if (e == hipSuccess && !hbad && table && total > cap_chains) st = KH_ERR_INVALID;
-  if (e == hipSuccess && host && !hbad) {
-    e = hipMemcpyAsync(out_score, df, m * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_pred, dp, m * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_chain, dc, m * 4, hipMemcpyDeviceToHost, stream);
-    if (table && st == KH_OK && total) {
-      if (e == hipSuccess) e = hipMemcpyAsync(c_first, t_first, total * 4, hipMemcpyDeviceToHost, stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(c_last, t_last, total * 4, hipMemcpyDeviceToHost, stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(c_count, t_count, total * 4, hipMemcpyDeviceToHost, stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(c_score, t_score, total * 4, hipMemcpyDeviceToHost, stream);
-    }
-    const hipError_t e2 = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = e2;
+  if (hbad) { st = KH_ERR_INVALID; total = 0; }
+  else if (table && total > cap_chains) st = KH_ERR_INVALID;
+  if (!hbad) {
+    s.copy_back(df, m); s.copy_back(dp, m); s.copy_back(dc, m);
+    if (st == KH_OK) { s.copy_back(t_first, total); s.copy_back(t_last, total); s.copy_back(t_count, total); s.copy_back(t_score, total); }
   }
-  pool_free(device, blk);
-  if (e != hipSuccess) return e == hipErrorOutOfMemory ? KH_ERR_NOMEM : KH_ERR_HIP;
+  const kh_status fs = s.finish();
+  if (fs != KH_OK) return fs;
   if (n_chains) *n_chains = total;
   return st;
 }
