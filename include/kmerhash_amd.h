@@ -739,6 +739,42 @@ kh_status kh_chain_anchors(const uint32_t* qpos /*[h|d] u32[m]*/, const uint32_t
                            uint32_t* c_first, uint32_t* c_last, uint32_t* c_count, int32_t* c_score /* each [cap_chains], or all NULL */,
                            uint64_t cap_chains, uint64_t* n_chains, int device, void* hip_stream);
 
+/* ---- edit distance per chain.  kh_chain_edits verifies the chains of kh_chain_anchors against the two texts: the unit-cost (Levenshtein)
+ *      distance of every link of every kept chain, and per chain their sum.  Inputs: the query text qtext[nq]; the reference text
+ *      rtext[nr], which covers the reference coordinates [ref_base, ref_base + nr) (an index keeps no text: the caller supplies it); the
+ *      anchors qpos, rpos, rev [m]; pred and chain [m] as kh_chain_anchors wrote them; n_chains, k, max_edits.
+ *      Bases.  A/a = 0, C/c = 1, G/g = 2, T/t = 3, any other byte = 4.  Two bases MATCH iff both codes are < 4 and equal; on the reverse
+ *      strand iff both are < 4 and sum to 3.  An N matches nothing, another N included.
+ *      Links.  Anchor i HAS A LINK iff 0 <= chain[i] < n_chains, 0 <= pred[i] < i and chain[pred[i]] == chain[i]: it continues its
+ *      predecessor's kept chain.  With j = pred[i], dq = q_i - q_j and the strand taken from bit 0 of rev[i]:
+ *        forward: dr = r_i - r_j, A = qtext[q_j, q_i), B = rtext[r_j - ref_base, r_i - ref_base);
+ *        reverse: dr = r_j - r_i, A as above, B = the reverse complement of rtext[r_i + k - ref_base, r_j + k - ref_base)
+ *      -- the stretch of reference A faces, given that the k bases at r_j are the reverse complement of the k at q_j.  Both strings start
+ *      at the seed of anchor j; the last anchor of a chain adds its k matching bases and nothing else.
+ *      out_link[i] = KH_EDITS_NOLINK: i has no link.  KH_EDITS_OVER: a position is >= 2^31; or dq < 1, dr < 1, q_i + k > nq, or a bound
+ *      of B's stretch of rtext (with its + k on the reverse strand) lies outside [0, nr]; or |dq - dr| > max_edits; or lev(A, B) >
+ *      max_edits.  Otherwise lev(A, B), the Levenshtein distance under the match rule above (substitution, insertion, deletion: 1 each).
+ *      c_edits[c] = the sum of out_link over the links of chain c that are >= 0, c_over[c] = the number of its KH_EDITS_OVER links; the
+ *      call zeroes both arrays [n_chains] first.  No byte outside the two texts is ever read, whatever the arrays hold, and no element
+ *      outside the arrays is written.
+ *      Route: one lane per anchor settles NOLINK, the range checks and the links with dq == dr whose strings match exactly; the others
+ *      go through a furthest-reaching-point (Landau-Vishkin) pass, one wavefront per link with one diagonal per lane, which is why
+ *      max_edits <= 31 (kh_kernels_edits.h fixes the orientation).
+ *      All arrays live in the memory `where` names.  Device memory: the call only queues work on hip_stream and never waits -- there is
+ *      no count to return, and bad input becomes NOLINK / OVER, not an error word; its scratch block returns to the pool from a host function
+ *      queued behind the kernels.  The call is not capturable into a graph: on a capturing stream it waits like a host call (and so
+ *      ends the capture with an error).  Host memory: staged, and the call synchronises.
+ *      KH_ERR_INVALID before anything is allocated, read or written: k outside 1..64, max_edits > 31, m > 2^24, nq >= 2^31,
+ *      ref_base + nr > 2^31, `where` outside the enum, n_chains > 0 with a null c_edits or c_over, and while m > 0 a null array or a null
+ *      text of positive length.  m == 0: KH_OK, c_edits and c_over zeroed if n_chains > 0. */
+#define KH_EDITS_NOLINK (-1)
+#define KH_EDITS_OVER (-2)
+kh_status kh_chain_edits(const void* qtext /*[h|d] u8[nq]*/, uint64_t nq, const void* rtext /*[h|d] u8[nr]*/, uint64_t nr, uint32_t ref_base,
+                         const uint32_t* qpos /*[h|d] u32[m]*/, const uint32_t* rpos /*[h|d] u32[m]*/, const uint8_t* rev /*[h|d] u8[m]*/,
+                         const int32_t* pred /*[h|d] i32[m]*/, const int32_t* chain /*[h|d] i32[m]*/, uint64_t m, uint64_t n_chains,
+                         uint32_t k /*1..64*/, uint32_t max_edits /*0..31*/, kh_mem where, int32_t* out_link /*[m]*/,
+                         uint32_t* c_edits /*[n_chains]*/, uint32_t* c_over /*[n_chains]*/, int device, void* hip_stream);
+
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);
 

@@ -84,6 +84,8 @@ SYMBOLS = [
     "kh_stamp_strand", "kh_index_set_stranded", "kh_wide_index_set_stranded", "kh_anchors_from_csr",
     # collinear chains per segment (read) from flat anchors
     "kh_chain_anchors",
+    # edit distance of every chain link against the two texts
+    "kh_chain_edits",
 ]
 
 _lib = None
@@ -262,6 +264,7 @@ def lib():
     L.kh_wide_index_set_stranded.argtypes = [vp, i32]
     L.kh_anchors_from_csr.argtypes = [vp, vp, u64, vp, u64, i32, vp, vp, vp, i32, vp]
     L.kh_chain_anchors.argtypes = [vp, vp, vp, u64, vp, u64, u32, u32, u32, u32, i32, u32, i32, vp, vp, vp, vp, vp, vp, vp, u64, pu64, i32, vp]
+    L.kh_chain_edits.argtypes = [vp, u64, vp, u64, u32, vp, vp, vp, vp, vp, u64, u64, u32, u32, i32, vp, vp, vp, i32, vp]
     for s in SYMBOLS:
         if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error", "kh_wide_index_last_error"):
             getattr(L, s).restype = i32

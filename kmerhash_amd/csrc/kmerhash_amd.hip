@@ -15,6 +15,7 @@
 //             kh_windex: the same host code on a wide table (kh_index::kw == 2) and the kernels that touch a 32-byte slot (kh_kernels_index_wide.h).
 //   csr     : kh_csr_unpermute, a CSR that arrives in a permuted order back into query order: the index's scans and gather around one scatter (kh_kernels_csr.h).
 //   chain   : kh_chain_anchors, collinear chains per segment from flat anchors: a wavefront per segment, the last 64 anchors in registers (kh_kernels_chain.h).
+//   edits   : kh_chain_edits, edit distance of every link of every kept chain: a lane per anchor, then a wavefront per unsettled link (kh_kernels_edits.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
 #include "kh_kernels_values.h"
@@ -22,6 +23,7 @@
 #include "kh_kernels_index_wide.h"
 #include "kh_kernels_csr.h"
 #include "kh_kernels_chain.h"
+#include "kh_kernels_edits.h"
 #include "kh_part_sizing.h"
 #include "kh_scratch.h"
 #include "../../include/kmerhash_amd.h"
@@ -55,12 +57,20 @@ struct DevPool {
 DevPool g_pool[16];
 const size_t kPoolGranule = size_t(2) << 20;
 
+// INVARIANT: no HIP call is made while P.m is held.  Scratch::release takes P.m on a runtime thread, in stream order, so a holder
+// that sat in a synchronising call (hipFree waits for the streams of the device) would wait for the stream, the stream for the host
+// function, the host function for the lock.  The blocks leave the maps under the lock and go to the driver after it is dropped.
 void pool_trim(int dev) {
   DevPool& P = g_pool[dev & 15];
-  std::lock_guard<std::mutex> g(P.m);
-  for (auto& kv : P.free_) { hipFree(kv.second); P.size_of.erase(kv.second); }
-  P.free_.clear();
-  P.cached = 0;
+  std::vector<void*> drop;
+  {
+    std::lock_guard<std::mutex> g(P.m);
+    drop.reserve(P.free_.size());
+    for (auto& kv : P.free_) { drop.push_back(kv.second); P.size_of.erase(kv.second); }
+    P.free_.clear();
+    P.cached = 0;
+  }
+  for (void* p : drop) hipFree(p);
 }
 hipError_t pool_alloc(int dev, size_t bytes, void** out) {
   DevPool& P = g_pool[dev & 15];
@@ -91,11 +101,16 @@ hipError_t pool_alloc(int dev, size_t bytes, void** out) {
 void pool_free(int dev, void* p) {
   if (!p) return;
   DevPool& P = g_pool[dev & 15];
-  std::lock_guard<std::mutex> g(P.m);
-  auto it = P.size_of.find(p);
-  if (it == P.size_of.end()) { hipFree(p); return; }
-  P.free_.insert(std::make_pair(it->second, p));
-  P.cached += it->second;
+  {
+    std::lock_guard<std::mutex> g(P.m);
+    auto it = P.size_of.find(p);
+    if (it != P.size_of.end()) {
+      P.free_.insert(std::make_pair(it->second, p));
+      P.cached += it->second;
+      return;
+    }
+  }
+  hipFree(p);      // (not a pooled block; outside the lock: see the invariant at pool_trim)
 }
 // pinned host scratch blocks (512 B, one per table) and profiling events are recycled too: hipHostFree synchronises the
 // device (0.2 ms per table destroyed, 4% of a benchmark step)
@@ -294,8 +309,29 @@ class Scratch {
     nblk_ = 0; nout_ = 0; busy_ = pending_ = false;
     return hip_status(err_);
   }
+  // finish() for a call that must not wait for its stream: when only kernels of this call use the blocks (no host copy is pending), a
+  // host function queued behind them returns the blocks to the pool; anything else, or a stream that refuses the function, is finish()
+  kh_status finish_queued() {
+    if (!ok() || pending_ || !nblk_ || !busy_) return finish();
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;      // a captured host node would hand the block back on every replay
+    if (hipStreamIsCapturing(stream_, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return finish(); }
+    Release* r = new Release;
+    r->device = device_; r->n = nblk_;
+    for (int i = 0; i < nblk_; ++i) r->blk[i] = blk_[i];
+    if (hipLaunchHostFunc(stream_, &Scratch::release, r) != hipSuccess) { (void)hipGetLastError(); delete r; return finish(); }
+    nblk_ = 0; nout_ = 0; busy_ = false;
+    return KH_OK;
+  }
 
  private:
+  struct Release { int device, n; void* blk[4]; };
+  // On a runtime thread, in stream order: it must neither call HIP nor wait for anyone who does.  pool_free of a pooled block only
+  // takes the pool's mutex, and no holder of that mutex calls HIP (the invariant at pool_trim); every block here came from pool_alloc.
+  static void release(void* arg) {
+    Release* r = static_cast<Release*>(arg);
+    for (int i = 0; i < r->n; ++i) pool_free(r->device, r->blk[i]);
+    delete r;
+  }
   void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
     if (ok()) { err_ = hipMemcpyAsync(dst, src, bytes, kind, stream_); pending_ = true; }
   }
@@ -4087,5 +4123,45 @@ kh_status kh_chain_anchors(const uint32_t* qpos, const uint32_t* rpos, const uin
   if (fs != KH_OK) return fs;
   if (n_chains) *n_chains = total;
   return st;
+}
+// ---- edit distance per chain link (kernels: kh_kernels_edits.h).  No handle; one pooled block holds the worklist (and the staged arrays
+//      of a host call).  A device call only queues: two memsets, two kernels and the return of the block, all on the caller's stream.
+kh_status kh_chain_edits(const void* qtext, uint64_t nq, const void* rtext, uint64_t nr, uint32_t ref_base, const uint32_t* qpos, const uint32_t* rpos,
+                         const uint8_t* rev, const int32_t* pred, const int32_t* chain, uint64_t m, uint64_t n_chains, uint32_t k, uint32_t max_edits,
+                         kh_mem where, int32_t* out_link, uint32_t* c_edits, uint32_t* c_over, int device, void* stream_) {
+  const uint64_t lim = uint64_t(1) << 31;
+  if (k < 1 || k > 64 || max_edits > 31 || m > (uint64_t(1) << 24) || nq >= lim || nr > lim || ref_base + nr > lim) return KH_ERR_INVALID;
+  if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || (n_chains && (!c_edits || !c_over))) return KH_ERR_INVALID;
+  if (m && (!qpos || !rpos || !rev || !pred || !chain || !out_link || (nq && !qtext) || (nr && !rtext))) return KH_ERR_INVALID;
+  const uint64_t nc = std::min<uint64_t>(n_chains, lim);      // (a chain number is an int32: rows beyond 2^31 are never addressed)
+  if (m == 0 && where == KH_MEM_HOST) {
+    if (nc) { memset(c_edits, 0, nc * sizeof(uint32_t)); memset(c_over, 0, nc * sizeof(uint32_t)); }
+    return KH_OK;
+  }
+  if (m == 0 && nc == 0) return KH_OK;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK0(hipSetDevice(device));
+  Scratch s(device, stream);
+  uint32_t *wl = nullptr, *wl_count = nullptr, *de = nullptr, *dov = nullptr;
+  int32_t* dl = nullptr;
+  KedArgs P{};
+  if (!s.layout([&](Scratch& c) {
+        wl = c.take<uint32_t>(m); wl_count = c.take<uint32_t>(m ? 1 : 0);
+        P.qtext = c.in(static_cast<const uint8_t*>(qtext), m ? nq : 0, where); P.rtext = c.in(static_cast<const uint8_t*>(rtext), m ? nr : 0, where);
+        P.qpos = c.in(qpos, m, where); P.rpos = c.in(rpos, m, where); P.rev = c.in(rev, m, where);
+        P.pred = c.in(pred, m, where); P.chain = c.in(chain, m, where);
+        dl = c.out(out_link, m, where); de = c.out(c_edits, nc, where); dov = c.out(c_over, nc, where);
+      })) return s.finish();
+  if (nc) { s.zero(de, nc * sizeof(uint32_t)); s.zero(dov, nc * sizeof(uint32_t)); }
+  if (m) {
+    s.zero(wl_count, sizeof(uint32_t));
+    P.nq = (uint32_t)nq; P.nr = (uint32_t)nr; P.ref_base = ref_base; P.m = (uint32_t)m; P.n_chains = (uint32_t)nc; P.k = k; P.max_edits = max_edits;
+    const uint32_t ncu = (uint32_t)cu_count(device);
+    hipLaunchKernelGGL(k_edits_classify, dim3(grid_for(m, KED_THREADS, ncu * 8)), dim3(KED_THREADS), 0, stream, P, dl, dov, wl, wl_count);
+    hipLaunchKernelGGL(k_edits_wfa, dim3(grid_for(m, KED_WAVES, ncu * 8)), dim3(KED_THREADS), 0, stream, P, (const uint32_t*)wl, (const uint32_t*)wl_count, dl, de, dov);
+    s.launched();
+  }
+  s.copy_back(dl, m); s.copy_back(de, nc); s.copy_back(dov, nc);
+  return s.finish_queued();
 }
 }  // extern "C"

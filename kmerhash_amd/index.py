@@ -300,9 +300,13 @@ class KmerPositionIndex:
         strand, the query interval [q_start, q_end) and the reference interval [r_start, r_end) its first and last anchor span, its
         number of anchors and its score -- then anchors = (qpos, rpos, rev) as anchors() returns them and chain[j] = the row of anchor
         j or -1.  numpy in, numpy out; a CUDA tensor in, tensors out on the current stream."""
-        from .kmers import chain_anchors
         if not self.stranded:
             raise ValueError("chains() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        return self._chains(seq, read_starts, params)[0]
+
+    def _chains(self, seq, read_starts, params):
+        """the body of chains(): -> (ChainTable, pred per anchor as chain_anchors wrote it)"""
+        from .kmers import chain_anchors
         q, r, v = self.anchors(seq)
         dev = torch is not None and isinstance(q, torch.Tensor)
         if read_starts is None:
@@ -327,7 +331,24 @@ class KmerPositionIndex:
             qf, ql, rf, rl = q[first], q[last], r[first], r[last]
             sg = np.zeros(len(first), dtype=np.uint32) if seg is None else (np.searchsorted(seg, first.astype(np.uint64), side="right") - 1).astype(np.uint32)
             rows = (sg, v[first], qf, ql + np.uint32(self.k), np.minimum(rf, rl), np.maximum(rf, rl) + np.uint32(self.k), c.count, c.cscore)
-        return ChainTable(*rows, (q, r, v), c.chain)
+        return ChainTable(*rows, (q, r, v), c.chain), c.pred
+
+    def chain_edits(self, seq, ref_text, read_starts=None, ref_base=0, max_edits=31, **params):
+        """chains(seq, read_starts, **params), then every kept chain verified against the texts on the device: kmers.chain_edits over the
+        chains' own anchors, with `seq` as the query text and ref_text as the text the index was built from -- the index keeps none;
+        ref_text covers the indexed positions [ref_base, ref_base + len(ref_text)) and lives where seq lives.
+        -> (ChainTable, ChainEdits(link, edits, over)): the table of chains(), the edit distance per anchor link (-1: no link, -2: outside
+        the texts or more than max_edits, 0..31) and, per row of the table, the sum of its links' distances and the number of its -2
+        links.  The chain's last seed adds k matching bases and no edits."""
+        from .kmers import chain_edits
+        if not self.stranded:
+            raise ValueError("chain_edits() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        if isinstance(seq, (bytes, bytearray)):
+            seq = np.frombuffer(seq, dtype=np.uint8)
+        table, pred = self._chains(seq, read_starts, params)
+        q, r, v = table.anchors
+        n_chains = int(table.count.numel() if torch is not None and isinstance(table.count, torch.Tensor) else len(table.count))
+        return table, chain_edits(seq, ref_text, q, r, v, pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
 
     def _syncmers(self, seq, fastq=False):
         """the closed syncmers of a text under the index's own parameters"""

@@ -315,6 +315,59 @@ def chain_anchors(qpos, rpos, rev, k, seg_offsets=None, lookback=64, max_gap=500
     return Chains(*per, *(t[:n.value] for t in tab))
 
 
+ChainEdits = collections.namedtuple("ChainEdits", "link edits over")
+EDITS_NOLINK, EDITS_OVER = -1, -2      # KH_EDITS_NOLINK, KH_EDITS_OVER
+
+
+def chain_edits(qtext, rtext, qpos, rpos, rev, pred, chain, n_chains, k, ref_base=0, max_edits=31, device=0):
+    """edit distance of every chain link against the two texts (kh_chain_edits in include/kmerhash_amd.h, which holds the definition):
+    anchor i with pred[i] in the same kept chain is a link, A = qtext[q_pred, q_i) and B = the stretch of rtext it faces (rtext covers the
+    reference coordinates [ref_base, ref_base + len(rtext)); reverse-strand links read it as its reverse complement).  pred and chain are
+    those of chain_anchors, n_chains the number of its kept chains.  -> ChainEdits(link, edits, over): link[i] = the Levenshtein distance
+    of the link, -1 (EDITS_NOLINK) where i has none, -2 (EDITS_OVER) where it leaves the texts or needs more than max_edits (0..31)
+    edits; edits[c] = the sum of chain c's distances, over[c] = the number of its -2 links.  numpy in (uint8 / bytes, uint32, uint32,
+    uint8, int32, int32), numpy out (int32, uint32, uint32); CUDA tensors in, int32 tensors out on the current stream, without a wait.
+    At most 2^24 anchors per call."""
+    from . import _capi as K
+    from .table import _Buf, KhError
+    if not 1 <= int(k) <= 64:
+        raise ValueError("k must be 1..64, got %r" % (k,))
+    if not 0 <= int(max_edits) <= 31:
+        raise ValueError("max_edits must be 0..31 (one diagonal per lane of a wavefront), got %r" % (max_edits,))
+    if not 0 <= int(n_chains) <= 2 ** 31:
+        raise ValueError("n_chains must be 0..2^31, got %r" % (n_chains,))
+    qtext, rtext = (np.frombuffer(t, dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else t for t in (qtext, rtext))
+    tq, tr = _Buf(qtext, np.uint8, 1), _Buf(rtext, np.uint8, 1)
+    qb, rb, vb = _Buf(qpos, np.uint32, 4), _Buf(rpos, np.uint32, 4), _Buf(rev, np.uint8, 1)
+    pb, cb = _Buf(pred, np.int32, 4), _Buf(chain, np.int32, 4)
+    if not tq.where == tr.where == qb.where == rb.where == vb.where == pb.where == cb.where:
+        raise ValueError("the texts, qpos, rpos, rev, pred and chain must live in the same memory")
+    m, nc = qb.n, int(n_chains)
+    if not rb.n == vb.n == pb.n == cb.n == m:
+        raise ValueError("qpos, rpos, rev, pred and chain must have one entry per anchor, got %d, %d, %d, %d and %d" % (m, rb.n, vb.n, pb.n, cb.n))
+    if m > 2 ** 24:
+        raise ValueError("at most 2^24 anchors per call (batch over reads), got %d" % m)
+    if tq.n >= 2 ** 31:
+        raise ValueError("the query text must be shorter than 2^31 bytes, got %d" % tq.n)
+    if not 0 <= int(ref_base) or int(ref_base) + tr.n > 2 ** 31:
+        raise ValueError("ref_base + len(rtext) must stay within 2^31 (a position has 31 bits), got %r + %d" % (ref_base, tr.n))
+    if qb.where == K.KH_MEM_DEVICE:
+        link = torch.empty(m, dtype=torch.int32, device=qb.device)
+        edits, over = (torch.empty(nc, dtype=torch.int32, device=qb.device) for _ in range(2))
+        ptrs, stream = [t.data_ptr() if t.numel() else None for t in (link, edits, over)], torch.cuda.current_stream(device).cuda_stream
+    else:
+        link, edits, over = np.zeros(m, dtype=np.int32), np.zeros(nc, dtype=np.uint32), np.zeros(nc, dtype=np.uint32)
+        ptrs, stream = [a.ctypes.data if a.size else None for a in (link, edits, over)], None
+    if m == 0 and nc == 0:
+        return ChainEdits(link, edits, over)
+    ins = [b.ptr if b.n else None for b in (qb, rb, vb, pb, cb)]
+    st = K.lib().kh_chain_edits(tq.ptr if tq.n else None, tq.n, tr.ptr if tr.n else None, tr.n, int(ref_base), *ins, m, nc, int(k), int(max_edits), qb.where,
+                                *ptrs, device, stream)
+    if st != K.KH_OK:
+        raise KhError(st, "kh_chain_edits")
+    return ChainEdits(link, edits, over)
+
+
 class KmerCounter:
     """counting index: k-mer -> number of occurrences (Reducer = std::plus, value 1 per occurrence)"""
 
