@@ -4,18 +4,17 @@ import ctypes as C
 import numpy as np
 
 from . import _capi as K
-from .table import _Buf, _hash_id, torch
+from ._call import HOST, _Buf, _Handle, alloc, check, torch
+from .table import _hash_id
 
 
 def estimate_from_registers(registers, precision=12):
     """internal_estimate (hyperloglog64.hpp:201-236) on host registers (uint8[2^precision]); needs no GPU"""
-    regs = np.ascontiguousarray(registers, dtype=np.uint8)
-    if regs.size != (1 << precision):
+    regs = _Buf(np.asarray(registers), np.uint8)
+    if regs.n != (1 << precision):
         raise ValueError("expected %d registers" % (1 << precision))
     d = C.c_double()
-    st = K.lib().kh_hll_estimate_registers(regs.ctypes.data, precision, C.byref(d))
-    if st != K.KH_OK:
-        raise K.KhError(st, "kh_hll_estimate_registers")
+    check(K.lib().kh_hll_estimate_registers(regs.ptr, precision, C.byref(d)), "kh_hll_estimate_registers")
     return d.value
 
 
@@ -42,56 +41,44 @@ def estimate_average_per_rank(hll, group=None):
     return estimate_global(hll, group) / float(p)
 
 
-class hyperloglog64:
+class hyperloglog64(_Handle):
+    PREFIX = "kh_hll_"
+
     def __init__(self, precision=12, ignore_msb=0, hash="murmur3avx64", seed=43, device=0):
-        self._L = K.lib()
-        self._h = C.c_void_p()
         self.precision = precision
         self.device = device
-        st = self._L.kh_hll_create(C.byref(self._h), precision, ignore_msb, _hash_id(hash), seed, device)
-        if st != K.KH_OK:
-            self._h = C.c_void_p()
-            raise K.KhError(st, "kh_hll_create failed")
+        self._create(precision, ignore_msb, _hash_id(hash), seed, device, hint="")
 
     # est_error_rate (hyperloglog64.hpp:262): 1.04 / 2^(precision/2)
     @property
     def est_error_rate(self):
         return 1.04 / float(1 << (self.precision >> 1))
 
-    def _chk(self, st, what):
-        if st != K.KH_OK:
-            raise K.KhError(st, what)
-
-    def _stream(self, b):
-        """a call with a device argument runs on torch's current stream (the argument is ready in that stream's order).  merge, clear,
-        registers and estimate have none and do not adopt it: they run on the stream of the last such call, in call order behind it --
-        kh_hll_set_stream waits for the old stream when it switches, kh_hll_merge for the other estimator's."""
-        if b.where == K.KH_MEM_DEVICE and torch is not None:
-            self._L.kh_hll_set_stream(self._h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+    # A call with a device argument runs on torch's current stream (_adopt_stream: the argument is ready in that stream's order).  merge,
+    # clear, registers and estimate have none and do not adopt it: they run on the stream of the last such call, in call order behind it --
+    # kh_hll_set_stream waits for the old stream when it switches, kh_hll_merge for the other estimator's.  The estimator keeps no last
+    # error: every status check names its entry point.
 
     def update(self, keys):
-        b = _Buf(keys, np.uint64, 8)
-        self._stream(b)
+        b = _Buf.keys(keys)
+        self._adopt_stream(b)
         self._chk(self._L.kh_hll_update(self._h, b.ptr, b.n, b.where), "kh_hll_update")
 
     def update_via_hashval(self, hashes):
-        b = _Buf(hashes, np.uint64, 8)
-        self._stream(b)
+        b = _Buf.keys(hashes)
+        self._adopt_stream(b)
         self._chk(self._L.kh_hll_update_via_hashval(self._h, b.ptr, b.n, b.where), "kh_hll_update_via_hashval")
 
     def update_wide(self, keys):
         """16-byte keys: (n, 2) numpy uint64 array or CUDA int64 tensor ({w0, w1} per key; a device tensor must be 16-byte aligned).
         The registers afterwards equal update_via_hashval(hash_batch_wide(keys)) with the estimator's hash and seed."""
-        from .wide import _keys
-        b = _keys(keys)
-        self._stream(b)
-        self._chk(self._L.kh_hll_update_wide(self._h, b.ptr, b.n // 2, b.where), "kh_hll_update_wide")
+        b = _Buf.keys(keys, 2)
+        self._adopt_stream(b)
+        self._chk(self._L.kh_hll_update_wide(self._h, b.ptr, b.n, b.where), "kh_hll_update_wide")
 
     def _from_text(self, fn, text, k, canonical):
-        if isinstance(text, (bytes, bytearray)):
-            text = np.frombuffer(text, dtype=np.uint8)
-        b = _Buf(text, np.uint8, 1)
-        self._stream(b)
+        b = _Buf.text(text)
+        self._adopt_stream(b)
         n = C.c_uint64()
         self._chk(getattr(self._L, fn)(self._h, b.ptr, b.n, k, 1 if canonical else 0, b.where, C.byref(n)), fn)
         return n.value
@@ -122,22 +109,11 @@ class hyperloglog64:
         self._chk(self._L.kh_hll_clear(self._h), "kh_hll_clear")
 
     def registers(self):
-        out = np.zeros(1 << self.precision, dtype=np.uint8)
-        self._chk(self._L.kh_hll_registers(self._h, out.ctypes.data), "kh_hll_registers")
-        return out
+        regs, ptr = alloc(HOST, 1 << self.precision, np.uint8)
+        self._chk(self._L.kh_hll_registers(self._h, ptr), "kh_hll_registers")
+        return regs
 
     def estimate(self):
         d = C.c_double()
         self._chk(self._L.kh_hll_estimate(self._h, C.byref(d)), "kh_hll_estimate")
         return d.value
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.kh_hll_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -10,9 +10,10 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi as K
-from ._capi import KhError
-from .table import _Buf, _hash_id, torch
+from ._call import HOST, _Buf, _Handle, alloc, check_same, torch
+from .kmers import anchors_from_csr, chain_anchors, chain_edits, stamp_strand
+from .seqs import is_syncmer, is_syncmer128, kmers_from_sequence, minimizers_from_sequence, syncmers128_from_sequence, syncmers_from_sequence
+from .table import _hash_id
 
 # entries of positions a workgroup of the build sorts in LDS at a time (KI_SORT_TILE in csrc/kh_kernels_index.h): a segment that crosses
 # a multiple of it takes the radix path
@@ -21,7 +22,7 @@ SORT_TILE = 4096
 ChainTable = collections.namedtuple("ChainTable", "seg rev q_start q_end r_start r_end count score anchors chain")
 
 
-class KmerPositionIndex:
+class KmerPositionIndex(_Handle):
     """k-mer -> ascending positions of all its occurrences.  64-bit k-mers (k <= 32), one GPU."""
     PREFIX = "kh_index_"          # the C entry points of this key width
     KMAX = 32
@@ -59,64 +60,35 @@ class KmerPositionIndex:
         self.w = None if w is None else int(w)
         self.order_hash, self.order_seed = _hash_id(order_hash), int(order_seed)
         self.k, self.canonical, self.device = int(k), bool(canonical), int(device)
-        self._L = K.lib()
-        self._h = C.c_void_p()
-        st = self._fn("create")(C.byref(self._h), _hash_id(hash), seed, min_load_factor, max_load_factor, self.device)
-        if st != K.KH_OK:
-            self._h = C.c_void_p()
-            raise KhError(st, self.PREFIX + "create failed (is a GPU visible and the HIP library built?)")
+        self._create(_hash_id(hash), seed, min_load_factor, max_load_factor, self.device)
         if self.stranded:
             self._chk(self._fn("set_stranded")(self._h, 1))
 
     # -- plumbing --------------------------------------------------------------------------------
-    def _fn(self, name):
-        return getattr(self._L, self.PREFIX + name)
+    def _pairs(self, keys, pos):
+        """a batch of (k-mer, position) pairs, the current stream adopted"""
+        kb, pb = _Buf.keys(keys, self.WORDS), _Buf(pos, np.uint32)
+        check_same("keys and positions must have the same length and live in the same memory", kb, pb)
+        self._adopt_stream(kb, pb)
+        return kb, pb
 
-    def _kbuf(self, keys):
-        """a key batch -> (_Buf over its words, number of keys)"""
-        b = _Buf(keys, np.uint64, 8)
-        return b, b.n
-
-    def _chk(self, st):
-        if st != K.KH_OK:
-            raise KhError(st, self._fn("last_error")(self._h).decode())
-
-    def _stream(self, *bufs):
-        if torch is not None and any(b.where == K.KH_MEM_DEVICE for b in bufs):
-            self._fn("set_stream")(self._h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-
-    def _scalar(self, name):
-        v = C.c_uint64()
-        self._chk(self._fn(name)(self._h, C.byref(v)))
-        return v.value
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._fn("destroy")(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _query(self, keys):
+        """a key batch, the current stream adopted"""
+        q = _Buf.keys(keys, self.WORDS)
+        self._adopt_stream(q)
+        return q
 
     # -- build -----------------------------------------------------------------------------------
     def build(self, keys, pos):
         """(k-mer, position) pairs in any order: uint64 keys and uint32 positions, both numpy or both CUDA tensors.  The index must
         be empty (clear() first); duplicate pairs are kept."""
-        (kb, n), pb = self._kbuf(keys), _Buf(pos, np.uint32, 4)
-        if n != pb.n or kb.where != pb.where:
-            raise ValueError("keys and positions must have the same length and live in the same memory")
-        self._stream(kb, pb)
-        self._chk(self._fn("build")(self._h, kb.ptr, pb.ptr, n, kb.where))
-        return n
+        kb, pb = self._pairs(keys, pos)
+        self._chk(self._fn("build")(self._h, kb.ptr, pb.ptr, kb.n, kb.where))
+        return kb.n
 
     def _build_text(self, fn, text, *more):
-        if isinstance(text, (bytes, bytearray)):
-            text = np.frombuffer(text, dtype=np.uint8)
-        b = _Buf(text, np.uint8, 1)
-        self._stream(b)
+        b = _Buf.text(text)
+        self._adopt_stream(b)
         if self.w is not None or self.s is not None:      # the same four calls over the minimizers / closed syncmers of the text
             verb, _, form = fn.partition("_from_")
             sampler, arg = ("_from_minimizers", self.w) if self.s is None else ("_from_syncmers", self.s)
@@ -141,12 +113,9 @@ class KmerPositionIndex:
     def append(self, keys, pos):
         """more (k-mer, position) pairs onto an index in any state (on an empty one: build).  Afterwards the index is that of all pairs
         given so far; the table is laid out like a counting table fed the same batches one by one."""
-        (kb, n), pb = self._kbuf(keys), _Buf(pos, np.uint32, 4)
-        if n != pb.n or kb.where != pb.where:
-            raise ValueError("keys and positions must have the same length and live in the same memory")
-        self._stream(kb, pb)
-        self._chk(self._fn("append")(self._h, kb.ptr, pb.ptr, n, kb.where))
-        return n
+        kb, pb = self._pairs(keys, pos)
+        self._chk(self._fn("append")(self._h, kb.ptr, pb.ptr, kb.n, kb.where))
+        return kb.n
 
     def _base(self, pos_base):
         top = 31 if self.stranded else 32                     # (a stamped position has 31 bits)
@@ -164,10 +133,9 @@ class KmerPositionIndex:
 
     def erase(self, keys):
         """every occurrence of the given k-mers out of the index (misses and repeats are harmless) -> (distinct keys erased, positions erased)"""
-        q, n = self._kbuf(keys)
-        self._stream(q)
+        q = self._query(keys)
         nk, npos = C.c_uint64(), C.c_uint64()
-        self._chk(self._fn("erase")(self._h, q.ptr, n, q.where, C.byref(nk), C.byref(npos)))
+        self._chk(self._fn("erase")(self._h, q.ptr, q.n, q.where, C.byref(nk), C.byref(npos)))
         return nk.value, npos.value
 
     def erase_counts(self, lo, hi):
@@ -205,24 +173,18 @@ class KmerPositionIndex:
         """(keys uint64[size] in slot order, offsets uint32[size + 1], positions uint32[total]) as numpy arrays: the positions of
         keys[r] are positions[offsets[r]:offsets[r + 1]], ascending"""
         size, total = self.size(), self.total()
-        keys = np.zeros(size if self.WORDS == 1 else (size, self.WORDS), dtype=np.uint64)
-        offsets = np.zeros(size + 1, dtype=np.uint32)
-        positions = np.zeros(total, dtype=np.uint32)
-        self._chk(self._fn("export")(self._h, keys.ctypes.data, offsets.ctypes.data, positions.ctypes.data))
+        keys, kptr = alloc(HOST, size if self.WORDS == 1 else (size, self.WORDS), np.uint64)
+        offsets, optr = alloc(HOST, size + 1, np.uint32)
+        positions, pptr = alloc(HOST, total, np.uint32)
+        self._chk(self._fn("export")(self._h, kptr, optr, pptr))
         return keys, offsets, positions
 
     # -- lookup ----------------------------------------------------------------------------------
     def count(self, keys):
         """occurrences of every query key (uint32; 0 on a miss)"""
-        q, n = self._kbuf(keys)
-        self._stream(q)
-        if q.where == K.KH_MEM_DEVICE:
-            out = torch.zeros(n, dtype=torch.int32, device=q.device)
-            optr = out.data_ptr()
-        else:
-            out = np.zeros(n, dtype=np.uint32)
-            optr = out.ctypes.data
-        self._chk(self._fn("count")(self._h, q.ptr, n, q.where, optr))
+        q = self._query(keys)
+        out, optr = alloc(q, q.n, np.uint32, zero=True)
+        self._chk(self._fn("count")(self._h, q.ptr, q.n, q.where, optr))
         return out
 
     def find(self, keys, positions=True, cap_out=None):
@@ -230,29 +192,17 @@ class KmerPositionIndex:
         are positions[offsets[i]:offsets[i + 1]], ascending; a repeated key repeats its positions.  positions=False: offsets only
         (positions is None).  cap_out: room to offer for the positions (default: exactly what is needed, found by an offsets-only pass);
         too little raises KhError(KH_ERR_INVALID)."""
-        q, n = self._kbuf(keys)
-        self._stream(q)
-        dev = q.where == K.KH_MEM_DEVICE
+        q = self._query(keys)
         n_out = C.c_uint64()
-        if dev:
-            offs = torch.zeros(n + 1, dtype=torch.int64, device=q.device)
-            optr = offs.data_ptr()
-        else:
-            offs = np.zeros(n + 1, dtype=np.uint64)
-            optr = offs.ctypes.data
+        offs, optr = alloc(q, q.n + 1, np.uint64, zero=True)
         if not positions or cap_out is None:
-            self._chk(self._fn("find")(self._h, q.ptr, n, q.where, optr, None, 0, C.byref(n_out)))
+            self._chk(self._fn("find")(self._h, q.ptr, q.n, q.where, optr, None, 0, C.byref(n_out)))
             if not positions:
                 return offs, None
             cap_out = n_out.value
         cap_out = int(cap_out)
-        if dev:
-            out = torch.empty(max(cap_out, 1), dtype=torch.int32, device=q.device)
-            pptr = out.data_ptr()
-        else:
-            out = np.zeros(max(cap_out, 1), dtype=np.uint32)
-            pptr = out.ctypes.data
-        self._chk(self._fn("find")(self._h, q.ptr, n, q.where, optr, pptr, cap_out, C.byref(n_out)))
+        out, pptr = alloc(q, max(cap_out, 1), np.uint32)
+        self._chk(self._fn("find")(self._h, q.ptr, q.n, q.where, optr, pptr, cap_out, C.byref(n_out)))
         return offs, out[: n_out.value]
 
     def find_sequences(self, seq):
@@ -267,7 +217,6 @@ class KmerPositionIndex:
 
     def _sample(self, seq):
         """(k-mers, window offsets) of a query text, sampled as the index samples"""
-        from .kmers import kmers_from_sequence, minimizers_from_sequence
         if self.WORDS != 1 and self.s is None:
             raise ValueError("find_sequences is not supported for 16-byte k-mers without s")
         if self.s is not None:
@@ -282,11 +231,9 @@ class KmerPositionIndex:
         is expanded on the device (kh_anchors_from_csr).  rev[j] == 0: the k bases at rpos[j] in the indexed text equal those at qpos[j]
         in `seq`; rev[j] == 1: they are their reverse complement.  numpy in, numpy out (uint32, uint32, uint8); a CUDA tensor in, tensors
         out (int32, int32, uint8) on the current stream.  chains(seq) chains them per read."""
-        from .kmers import anchors_from_csr, stamp_strand
         if not self.stranded:
             raise ValueError("anchors() needs an index made with stranded=True: without the strand bit a hit has no orientation")
-        if isinstance(seq, (bytes, bytearray)):
-            seq = np.frombuffer(seq, dtype=np.uint8)
+        seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to two calls)
         km, qpos = self._sample(seq)
         sq = stamp_strand(seq, qpos, self.k, 0, self.device)
         offsets, positions = self.find(km)
@@ -306,7 +253,6 @@ class KmerPositionIndex:
 
     def _chains(self, seq, read_starts, params):
         """the body of chains(): -> (ChainTable, pred per anchor as chain_anchors wrote it)"""
-        from .kmers import chain_anchors
         q, r, v = self.anchors(seq)
         dev = torch is not None and isinstance(q, torch.Tensor)
         if read_starts is None:
@@ -340,11 +286,9 @@ class KmerPositionIndex:
         -> (ChainTable, ChainEdits(link, edits, over)): the table of chains(), the edit distance per anchor link (-1: no link, -2: outside
         the texts or more than max_edits, 0..31) and, per row of the table, the sum of its links' distances and the number of its -2
         links.  The chain's last seed adds k matching bases and no edits."""
-        from .kmers import chain_edits
         if not self.stranded:
             raise ValueError("chain_edits() needs an index made with stranded=True: without the strand bit a hit has no orientation")
-        if isinstance(seq, (bytes, bytearray)):
-            seq = np.frombuffer(seq, dtype=np.uint8)
+        seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to two calls)
         table, pred = self._chains(seq, read_starts, params)
         q, r, v = table.anchors
         n_chains = int(table.count.numel() if torch is not None and isinstance(table.count, torch.Tensor) else len(table.count))
@@ -352,8 +296,7 @@ class KmerPositionIndex:
 
     def _syncmers(self, seq, fastq=False):
         """the closed syncmers of a text under the index's own parameters"""
-        from .kmers import syncmers_from_sequence
-        return syncmers_from_sequence(seq, self.k, self.s, self.canonical, self.order_hash, self.order_seed, self.device, _fastq=fastq)
+        return (syncmers_from_sequence if self.WORDS == 1 else syncmers128_from_sequence)(seq, self.k, self.s, self.canonical, self.order_hash, self.order_seed, self.device, _fastq=fastq)
 
     def sampled(self, keys):
         """bool per key: could the index hold it?  True for every key of an index of all windows; is_syncmer(keys) under the index's
@@ -361,14 +304,10 @@ class KmerPositionIndex:
         where it is False.  An index made with w raises: a minimizer is chosen by its neighbours, not by the k-mer."""
         if self.w is not None:
             raise ValueError("sampled() has no answer for a minimizer index (w=): selection there depends on the neighbouring windows")
-        q, n = self._kbuf(keys)
+        q = _Buf.keys(keys, self.WORDS)
         if self.s is None:
-            return torch.ones(n, dtype=torch.bool, device=q.device) if q.where == K.KH_MEM_DEVICE else np.ones(n, dtype=bool)
-        return self._is_syncmer(keys)
-
-    def _is_syncmer(self, keys):
-        from .kmers import is_syncmer
-        return is_syncmer(keys, self.k, self.s, self.canonical, self.order_hash, self.order_seed, self.device)
+            return torch.ones(q.n, dtype=torch.bool, device=q.device) if q.dev else np.ones(q.n, dtype=bool)
+        return (is_syncmer if self.WORDS == 1 else is_syncmer128)(keys, self.k, self.s, self.canonical, self.order_hash, self.order_seed, self.device)
 
     # -- measurement -----------------------------------------------------------------------------
     def profile_enable(self, on=True):
@@ -376,13 +315,7 @@ class KmerPositionIndex:
 
     def profile(self):
         """{kernel name: (launches, total ms)} since profile_enable(True)"""
-        buf = C.create_string_buffer(1 << 16)
-        self._chk(self._fn("profile_dump")(self._h, buf, len(buf)))
-        out = {}
-        for line in buf.value.decode().splitlines():
-            name, launches, ms = line.split()
-            out[name] = (int(launches), float(ms))
-        return out
+        return self._profile()
 
 
 class WideKmerPositionIndex(KmerPositionIndex):
@@ -398,21 +331,8 @@ class WideKmerPositionIndex(KmerPositionIndex):
         super().__init__(k, canonical, hash, min_load_factor, max_load_factor, device, seed, w=w, order_hash=order_hash, order_seed=order_seed, s=s,
                          stranded=stranded)
 
-    def _syncmers(self, seq, fastq=False):
-        from .wide import syncmers128_from_sequence
-        return syncmers128_from_sequence(seq, self.k, self.s, self.canonical, self.order_hash, self.order_seed, self.device, _fastq=fastq)
-
-    def _is_syncmer(self, keys):
-        from .wide import is_syncmer128
-        return is_syncmer128(keys, self.k, self.s, self.canonical, self.order_hash, self.order_seed, self.device)
-
     def export_info(self):
         """the Robin Hood info byte of every bucket of the index's table (uint8[capacity]): the counting twin's"""
-        out = np.zeros(self.capacity(), dtype=np.uint8)
-        self._chk(self._L.kh_wide_index_export_info(self._h, out.ctypes.data))
-        return out
-
-    def _kbuf(self, keys):
-        from .wide import _keys
-        b = _keys(keys)
-        return b, b.n // 2
+        info, ptr = alloc(HOST, self.capacity(), np.uint8)
+        self._chk(self._L.kh_wide_index_export_info(self._h, ptr))
+        return info

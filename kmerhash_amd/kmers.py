@@ -5,11 +5,18 @@ The reference takes its parser and k-mer type from kmerind (absent), so the k-me
 (see kh_kmers_from_sequence in include/kmerhash_amd.h): 2-bit packed, first base most significant, A=0 C=1 G=2 T=3,
 windows containing any other byte are skipped, canonical = min(k-mer, reverse complement)."""
 import collections
+import ctypes as C
+import time
 
 import numpy as np
 
-from .table import hashmap_robinhood_doubling, torch
-from .wide import _kmers, hashmap_robinhood_doubling_wide, kmers128_from_fastq, kmers128_from_sequence
+from . import _capi as K
+from ._call import _Buf, _is_tensor, alloc, check, check_same, stream_of, torch
+from .hll import estimate_average_per_rank, hyperloglog64
+from .seqs import (is_syncmer, kmers128_from_fastq, kmers128_from_sequence, kmers_from_fastq, kmers_from_sequence,  # noqa: F401  (re-exported)
+                   minimizers_from_fastq, minimizers_from_sequence, syncmers_from_fastq, syncmers_from_sequence)
+from .table import hashmap_robinhood_doubling
+from .wide import hashmap_robinhood_doubling_wide
 
 
 def sequences_from_fastq(buf):
@@ -36,158 +43,6 @@ def sequences_from_fasta(buf):
     return np.frombuffer(b"".join(parts), dtype=np.uint8).copy()
 
 
-def kmers_from_fastq(text, k=31, canonical=True, device=0, with_positions=False):
-    """raw FASTQ text (whole 4-line records; bytes / uint8 array on the host, or a uint8 CUDA tensor) -> packed k-mers of the
-    sequence lines: the record structure is resolved on the GPU (kh_kmers_from_fastq), no host-side parsing.
-    with_positions: -> (k-mers, byte offsets of their windows in the raw text)"""
-    return kmers_from_sequence(text, k, canonical, device, _fastq=True, with_positions=with_positions)
-
-
-def kmers_from_sequence(seq, k=31, canonical=True, device=0, _fastq=False, with_positions=False):
-    """-> packed k-mers (numpy uint64 for host input, torch int64 CUDA tensor for device input), sequence order.
-    with_positions: -> (k-mers, positions): positions[i] (numpy uint32 / torch int32) is the byte offset in `seq` of the first base
-    of the window that gave k-mers[i] (kh_kmers_from_sequence_pos; a text of 2^32 bytes or more is refused)"""
-    if with_positions:
-        return _kmers_pos("kh_kmers_from_fastq_pos" if _fastq else "kh_kmers_from_sequence_pos", seq, k, canonical, device)
-    return _kmers("kh_kmers_from_fastq" if _fastq else "kh_kmers_from_sequence", 1, seq, k, canonical, device)
-
-
-def _kmers_pos(fn_name, seq, k, canonical, device):
-    import ctypes as C
-    from . import _capi as K
-    from .table import _Buf, KhError
-    if isinstance(seq, (bytes, bytearray)):
-        seq = np.frombuffer(seq, dtype=np.uint8)
-    b = _Buf(seq, np.uint8, 1)
-    n_out = C.c_uint64()
-    if b.where == K.KH_MEM_DEVICE:
-        out = torch.empty(max(b.n, 1), dtype=torch.int64, device=b.device)
-        pos = torch.empty(max(b.n, 1), dtype=torch.int32, device=b.device)
-        optr, pptr, stream = out.data_ptr(), pos.data_ptr(), torch.cuda.current_stream(device).cuda_stream
-    else:
-        out = np.zeros(max(b.n, 1), dtype=np.uint64)
-        pos = np.zeros(max(b.n, 1), dtype=np.uint32)
-        optr, pptr, stream = out.ctypes.data, pos.ctypes.data, None
-    st = getattr(K.lib(), fn_name)(b.ptr, b.n, k, 1 if canonical else 0, b.where, optr, pptr, C.byref(n_out), device, stream)
-    if st != K.KH_OK:
-        raise KhError(st, fn_name)
-    return out[: n_out.value], pos[: n_out.value]
-
-
-def minimizers_from_sequence(seq, k=15, w=10, canonical=True, order_hash="murmur", order_seed=42, device=0, _fastq=False):
-    """(w,k)-minimizers of `seq` -> (k-mers, positions), ascending positions: of every w consecutive valid windows the one whose
-    k-mer has the smallest order_hash(k-mer, order_seed) is kept (ties: the leftmost), each once -- about 2 / (w + 1) of the windows
-    of kmers_from_sequence(with_positions=True), and all of them for w = 1 (kh_minimizers_from_sequence in include/kmerhash_amd.h).
-    numpy uint64 / uint32 for host input, torch int64 / int32 CUDA tensors for device input.  A count pass first, then an exact
-    allocation.  In a stretch of equal k-mers (poly-A) every full-window start is kept."""
-    import ctypes as C
-    from . import _capi as K
-    from .table import _Buf, KhError, _hash_id
-    fn_name = "kh_minimizers_from_fastq" if _fastq else "kh_minimizers_from_sequence"
-    if isinstance(seq, (bytes, bytearray)):
-        seq = np.frombuffer(seq, dtype=np.uint8)
-    b = _Buf(seq, np.uint8, 1)
-    dev = b.where == K.KH_MEM_DEVICE
-    stream = torch.cuda.current_stream(device).cuda_stream if dev else None
-    fn, n_out = getattr(K.lib(), fn_name), C.c_uint64()
-    args = (b.ptr, b.n, int(k), int(w), 1 if canonical else 0, _hash_id(order_hash), int(order_seed), b.where)
-    st = fn(*args, None, None, 0, C.byref(n_out), device, stream)
-    if st != K.KH_OK:
-        raise KhError(st, fn_name)
-    m = n_out.value
-    if dev:
-        out = torch.empty(m, dtype=torch.int64, device=b.device)
-        pos = torch.empty(m, dtype=torch.int32, device=b.device)
-        optr, pptr = out.data_ptr(), pos.data_ptr()
-    else:
-        out = np.zeros(m, dtype=np.uint64)
-        pos = np.zeros(m, dtype=np.uint32)
-        optr, pptr = out.ctypes.data, pos.ctypes.data
-    if m:
-        st = fn(*args, optr, pptr, m, C.byref(n_out), device, stream)
-        if st != K.KH_OK:
-            raise KhError(st, fn_name)
-    return out, pos
-
-
-def minimizers_from_fastq(text, k=15, w=10, canonical=True, order_hash="murmur", order_seed=42, device=0):
-    """minimizers_from_sequence over the sequence lines of raw FASTQ text (whole 4-line records); positions are byte offsets into
-    the text, no pick falls on an id or quality line and no window spans two reads"""
-    return minimizers_from_sequence(text, k, w, canonical, order_hash, order_seed, device, _fastq=True)
-
-
-def _syncmers(fn_name, words, seq, k, s, canonical, order_hash, order_seed, device):
-    """shared body of syncmers_from_sequence / syncmers128_from_sequence (and their FASTQ forms): a count pass, an exact allocation,
-    the emit pass; `words` 64-bit words per k-mer"""
-    import ctypes as C
-    from . import _capi as K
-    from .table import _Buf, KhError, _hash_id
-    if isinstance(seq, (bytes, bytearray)):
-        seq = np.frombuffer(seq, dtype=np.uint8)
-    b = _Buf(seq, np.uint8, 1)
-    dev = b.where == K.KH_MEM_DEVICE
-    stream = torch.cuda.current_stream(device).cuda_stream if dev else None
-    fn, n_out = getattr(K.lib(), fn_name), C.c_uint64()
-    args = (b.ptr, b.n, int(k), int(s), 1 if canonical else 0, _hash_id(order_hash), int(order_seed), b.where)
-    st = fn(*args, None, None, 0, C.byref(n_out), device, stream)
-    if st != K.KH_OK:
-        raise KhError(st, fn_name)
-    m = n_out.value
-    shape = m if words == 1 else (m, words)
-    if dev:
-        out = torch.empty(shape, dtype=torch.int64, device=b.device)
-        pos = torch.empty(m, dtype=torch.int32, device=b.device)
-        optr, pptr = out.data_ptr(), pos.data_ptr()
-    else:
-        out = np.zeros(shape, dtype=np.uint64)
-        pos = np.zeros(m, dtype=np.uint32)
-        optr, pptr = out.ctypes.data, pos.ctypes.data
-    if m:
-        st = fn(*args, optr, pptr, m, C.byref(n_out), device, stream)
-        if st != K.KH_OK:
-            raise KhError(st, fn_name)
-    return out, pos
-
-
-def _syncmer_mask(fn_name, kb, n, k, s, canonical, order_hash, order_seed, device):
-    """shared body of is_syncmer / is_syncmer128 over a _Buf of key words: -> bool array / tensor of n entries"""
-    from . import _capi as K
-    from .table import KhError, _hash_id
-    if kb.where == K.KH_MEM_DEVICE:
-        out = torch.zeros(n, dtype=torch.uint8, device=kb.device)
-        optr, stream = out.data_ptr(), torch.cuda.current_stream(device).cuda_stream
-    else:
-        out = np.zeros(n, dtype=np.uint8)
-        optr, stream = out.ctypes.data, None
-    st = getattr(K.lib(), fn_name)(kb.ptr, n, int(k), int(s), 1 if canonical else 0, _hash_id(order_hash), int(order_seed), kb.where, optr, device,
-                                   stream)
-    if st != K.KH_OK:
-        raise KhError(st, fn_name)
-    return out.bool() if kb.where == K.KH_MEM_DEVICE else out.astype(bool)
-
-
-def syncmers_from_sequence(seq, k=15, s=11, canonical=True, order_hash="murmur", order_seed=42, device=0, _fastq=False):
-    """closed syncmers of `seq` -> (k-mers, positions), ascending positions: the windows of kmers_from_sequence(with_positions=True)
-    whose smallest s-mer by order_hash(s-mer, order_seed) -- of the canonical s-mer when `canonical` -- is the first or the last of the
-    k - s + 1 (kh_syncmers_from_sequence in include/kmerhash_amd.h).  About 2 / (k - s + 1) of the windows; all of them for s = k.
-    Whether a k-mer is kept depends on the k-mer alone (is_syncmer asks without a text).  numpy uint64 / uint32 for host input, torch
-    int64 / int32 CUDA tensors for device input.  In a homopolymer every window is kept."""
-    return _syncmers("kh_syncmers_from_fastq" if _fastq else "kh_syncmers_from_sequence", 1, seq, k, s, canonical, order_hash, order_seed, device)
-
-
-def syncmers_from_fastq(text, k=15, s=11, canonical=True, order_hash="murmur", order_seed=42, device=0):
-    """syncmers_from_sequence over the sequence lines of raw FASTQ text (whole 4-line records); positions are byte offsets into the text"""
-    return syncmers_from_sequence(text, k, s, canonical, order_hash, order_seed, device, _fastq=True)
-
-
-def is_syncmer(keys, k=15, s=11, canonical=True, order_hash="murmur", order_seed=42, device=0):
-    """for packed k-mers (uint64 numpy array or int64 CUDA tensor): a bool array / tensor, True where the k-mer is a closed syncmer
-    under these parameters -- the k-mers syncmers_from_sequence keeps, whatever text they stand in (kh_syncmer_mask)"""
-    from .table import _Buf
-    kb = _Buf(keys, np.uint64, 8)
-    return _syncmer_mask("kh_syncmer_mask", kb, kb.n, k, s, canonical, order_hash, order_seed, device)
-
-
 POS_INVALID = 0xFFFFFFFF          # KH_POS_INVALID: the stamp of a window that is not k bases inside the text
 
 
@@ -198,35 +53,23 @@ def stamp_strand(text, pos, k, pos_base=0, device=0, count_invalid=False):
     that is no base gives POS_INVALID.  Positions in any order, repeats allowed; k = 1..64; pos_base + len(text) <= 2^31.
     numpy uint8 / uint32 in, numpy uint32 out; CUDA tensors in (uint8 text, int32 positions), an int32 tensor out, queued on the current
     stream.  count_invalid: -> (stamped, number of POS_INVALID written), which waits for the stream."""
-    import ctypes as C
-    from . import _capi as K
-    from .table import _Buf, KhError
-    if isinstance(text, (bytes, bytearray)):
-        text = np.frombuffer(text, dtype=np.uint8)
-    tb, pb = _Buf(text, np.uint8, 1), _Buf(pos, np.uint32, 4)
-    if tb.where != pb.where:
-        raise ValueError("text and positions must live in the same memory")
+    tb, pb = _Buf.text(text), _Buf(pos, np.uint32)
+    check_same("text and positions must live in the same memory", tb, pb, length=False)
     if not 1 <= int(k) <= 64:
         raise ValueError("k must be 1..64, got %r" % (k,))
     if not 0 <= int(pos_base) or int(pos_base) + tb.n > 2 ** 31:
         raise ValueError("pos_base + len(text) must stay within 2^31 (a stamped position has 31 bits), got %r + %d" % (pos_base, tb.n))
-    if pb.where == K.KH_MEM_DEVICE:
-        out = torch.empty(pb.n, dtype=torch.int32, device=pb.device)
-        optr, stream = out.data_ptr(), torch.cuda.current_stream(device).cuda_stream
-    else:
-        out = np.zeros(pb.n, dtype=np.uint32)
-        optr, stream = out.ctypes.data, None
+    out, optr = alloc(pb, pb.n, np.uint32)
     bad = C.c_uint64()
-    st = K.lib().kh_stamp_strand(tb.ptr, tb.n, int(k), pb.ptr, pb.n, int(pos_base), pb.where, optr, C.byref(bad) if count_invalid else None, device, stream)
-    if st != K.KH_OK:
-        raise KhError(st, "kh_stamp_strand")
+    check(K.lib().kh_stamp_strand(tb.ptr, tb.n, int(k), pb.ptr, pb.n, int(pos_base), pb.where, optr, C.byref(bad) if count_invalid else None, device,
+                                  stream_of(pb, device)), "kh_stamp_strand")
     return (out, bad.value) if count_invalid else out
 
 
 def unstamp(v):
     """stamped positions -> (positions, strand bits): v >> 1 and v & 1 (numpy uint32 or int32 CUDA tensors holding uint32; POS_INVALID is
     the caller's to filter)"""
-    if torch is not None and isinstance(v, torch.Tensor):
+    if _is_tensor(v):
         return (v >> 1) & 0x7FFFFFFF, v & 1
     v = np.asarray(v, dtype=np.uint32)
     return v >> np.uint32(1), v & np.uint32(1)
@@ -235,22 +78,13 @@ def unstamp(v):
 def anchors_from_csr(qpos, offsets, pos, device=0):
     """the CSR of a find over a stranded index (stamped query positions, offsets, stamped hits) -> (qpos, rpos, rev) with one entry per hit
     (kh_anchors_from_csr): rev = 0 where the reference window equals the query window, 1 where it is its reverse complement"""
-    from . import _capi as K
-    from .table import _Buf, KhError
-    qb, ob, pb = _Buf(qpos, np.uint32, 4), _Buf(offsets, np.uint64, 8), _Buf(pos, np.uint32, 4)
-    if not qb.where == ob.where == pb.where or ob.n != qb.n + 1:
-        raise ValueError("qpos, offsets (len(qpos) + 1 entries) and pos must live in the same memory")
-    total = pb.n
-    if qb.where == K.KH_MEM_DEVICE:
-        oq, orp = (torch.empty(total, dtype=torch.int32, device=pb.device) for _ in range(2))
-        orv = torch.empty(total, dtype=torch.uint8, device=pb.device)
-        ptrs, stream = (oq.data_ptr(), orp.data_ptr(), orv.data_ptr()), torch.cuda.current_stream(device).cuda_stream
-    else:
-        oq, orp, orv = np.zeros(total, dtype=np.uint32), np.zeros(total, dtype=np.uint32), np.zeros(total, dtype=np.uint8)
-        ptrs, stream = (oq.ctypes.data, orp.ctypes.data, orv.ctypes.data), None
-    st = K.lib().kh_anchors_from_csr(qb.ptr, ob.ptr, qb.n, pb.ptr, total, qb.where, *ptrs, device, stream)
-    if st != K.KH_OK:
-        raise KhError(st, "kh_anchors_from_csr")
+    qb, ob, pb = _Buf(qpos, np.uint32), _Buf(offsets, np.uint64), _Buf(pos, np.uint32)
+    msg = "qpos, offsets (len(qpos) + 1 entries) and pos must live in the same memory"
+    check_same(msg, qb, ob, pb, length=False)
+    if ob.n != qb.n + 1:
+        raise ValueError(msg)
+    (oq, qptr), (orp, rptr), (orv, vptr) = alloc(pb, pb.n, np.uint32), alloc(pb, pb.n, np.uint32), alloc(pb, pb.n, np.uint8)
+    check(K.lib().kh_anchors_from_csr(qb.ptr, ob.ptr, qb.n, pb.ptr, pb.n, qb.where, qptr, rptr, vptr, device, stream_of(qb, device)), "kh_anchors_from_csr")
     return oq, orp, orv
 
 
@@ -280,14 +114,10 @@ def chain_anchors(qpos, rpos, rev, k, seg_offsets=None, lookback=64, max_gap=500
     first anchor.  -> Chains(score, pred, chain, first, last, count, cscore): f(i), pred(i) (-1: none) and the chain number (-1: not
     kept) per anchor, then first / last anchor, anchor count and score per kept chain.  numpy in (uint32, uint32, uint8, uint64), numpy
     out; CUDA tensors in (int32, int32, uint8, int64), tensors out on the current stream.  At most 2^24 anchors per call."""
-    import ctypes as C
-    from . import _capi as K
-    from .table import _Buf, KhError
     _check_chain_params(k, lookback, max_gap, band, min_score, min_count)
-    qb, rb, vb = _Buf(qpos, np.uint32, 4), _Buf(rpos, np.uint32, 4), _Buf(rev, np.uint8, 1)
-    sb = None if seg_offsets is None else _Buf(seg_offsets, np.uint64, 8)
-    if not qb.where == rb.where == vb.where or (sb is not None and sb.where != qb.where):
-        raise ValueError("qpos, rpos, rev and seg_offsets must live in the same memory")
+    qb, rb, vb = _Buf(qpos, np.uint32), _Buf(rpos, np.uint32), _Buf(rev, np.uint8)
+    sb = None if seg_offsets is None else _Buf(seg_offsets, np.uint64)
+    check_same("qpos, rpos, rev and seg_offsets must live in the same memory", qb, rb, vb, sb, length=False)
     m = qb.n
     if rb.n != m or vb.n != m:
         raise ValueError("qpos, rpos and rev must have one entry per anchor, got %d, %d and %d" % (m, rb.n, vb.n))
@@ -296,23 +126,14 @@ def chain_anchors(qpos, rpos, rev, k, seg_offsets=None, lookback=64, max_gap=500
     if sb is not None and (sb.n < 1 or sb.n - 1 > m + 2 ** 24 or (sb.n == 1 and m)):
         raise ValueError("seg_offsets must hold n_seg + 1 entries ascending from 0 to the number of anchors, got %d entries for %d anchors" % (sb.n, m))
     cap = m // max(1, int(min_count))          # kept chains are disjoint and hold min_count anchors each
-    if qb.where == K.KH_MEM_DEVICE:
-        per = [torch.empty(m, dtype=torch.int32, device=qb.device) for _ in range(3)]
-        tab = [torch.empty(cap, dtype=torch.int32, device=qb.device) for _ in range(4)]
-        ptrs, stream = [t.data_ptr() if t.numel() else None for t in per + tab], torch.cuda.current_stream(device).cuda_stream
-    else:
-        per = [np.zeros(m, dtype=np.int32) for _ in range(3)]
-        tab = [np.zeros(cap, dtype=np.uint32) for _ in range(3)] + [np.zeros(cap, dtype=np.int32)]
-        ptrs, stream = [a.ctypes.data if a.size else None for a in per + tab], None
-    if cap == 0:
-        ptrs[3:] = [None] * 4
+    # score, pred and chain per anchor (int32), then first, last, count (uint32) and score (int32) per kept chain
+    outs = [alloc(qb, size, dt, empty=True) for size, dt in [(m, np.int32)] * 3 + [(cap, np.uint32)] * 3 + [(cap, np.int32)]]
     n = C.c_uint64()
-    st = K.lib().kh_chain_anchors(qb.ptr if m else None, rb.ptr if m else None, vb.ptr if m else None, m, None if sb is None else sb.ptr,
+    st = K.lib().kh_chain_anchors(qb.ptr_or_null, rb.ptr_or_null, vb.ptr_or_null, m, None if sb is None else sb.ptr,
                                   0 if sb is None else sb.n - 1, int(k), int(lookback), int(max_gap), int(band), int(min_score), int(min_count), qb.where,
-                                  *ptrs, cap, C.byref(n), device, stream)
-    if st != K.KH_OK:
-        raise KhError(st, "kh_chain_anchors" + (": seg_offsets do not ascend from 0 to the number of anchors" if st == K.KH_ERR_INVALID else ""))
-    return Chains(*per, *(t[:n.value] for t in tab))
+                                  *(ptr for _, ptr in outs), cap, C.byref(n), device, stream_of(qb, device))
+    check(st, "kh_chain_anchors" + (": seg_offsets do not ascend from 0 to the number of anchors" if st == K.KH_ERR_INVALID else ""))
+    return Chains(*(a for a, _ in outs[:3]), *(a[:n.value] for a, _ in outs[3:]))
 
 
 ChainEdits = collections.namedtuple("ChainEdits", "link edits over")
@@ -328,43 +149,28 @@ def chain_edits(qtext, rtext, qpos, rpos, rev, pred, chain, n_chains, k, ref_bas
     edits; edits[c] = the sum of chain c's distances, over[c] = the number of its -2 links.  numpy in (uint8 / bytes, uint32, uint32,
     uint8, int32, int32), numpy out (int32, uint32, uint32); CUDA tensors in, int32 tensors out on the current stream, without a wait.
     At most 2^24 anchors per call."""
-    from . import _capi as K
-    from .table import _Buf, KhError
     if not 1 <= int(k) <= 64:
         raise ValueError("k must be 1..64, got %r" % (k,))
     if not 0 <= int(max_edits) <= 31:
         raise ValueError("max_edits must be 0..31 (one diagonal per lane of a wavefront), got %r" % (max_edits,))
     if not 0 <= int(n_chains) <= 2 ** 31:
         raise ValueError("n_chains must be 0..2^31, got %r" % (n_chains,))
-    qtext, rtext = (np.frombuffer(t, dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else t for t in (qtext, rtext))
-    tq, tr = _Buf(qtext, np.uint8, 1), _Buf(rtext, np.uint8, 1)
-    qb, rb, vb = _Buf(qpos, np.uint32, 4), _Buf(rpos, np.uint32, 4), _Buf(rev, np.uint8, 1)
-    pb, cb = _Buf(pred, np.int32, 4), _Buf(chain, np.int32, 4)
-    if not tq.where == tr.where == qb.where == rb.where == vb.where == pb.where == cb.where:
-        raise ValueError("the texts, qpos, rpos, rev, pred and chain must live in the same memory")
+    tq, tr = _Buf.text(qtext), _Buf.text(rtext)
+    qb, rb, vb = _Buf(qpos, np.uint32), _Buf(rpos, np.uint32), _Buf(rev, np.uint8)
+    pb, cb = _Buf(pred, np.int32), _Buf(chain, np.int32)
+    check_same("the texts, qpos, rpos, rev, pred and chain must live in the same memory", tq, tr, qb, rb, vb, pb, cb, length=False)
     m, nc = qb.n, int(n_chains)
-    if not rb.n == vb.n == pb.n == cb.n == m:
-        raise ValueError("qpos, rpos, rev, pred and chain must have one entry per anchor, got %d, %d, %d, %d and %d" % (m, rb.n, vb.n, pb.n, cb.n))
+    check_same("qpos, rpos, rev, pred and chain must have one entry per anchor, got %d, %d, %d, %d and %d" % (m, rb.n, vb.n, pb.n, cb.n), qb, rb, vb, pb, cb)
     if m > 2 ** 24:
         raise ValueError("at most 2^24 anchors per call (batch over reads), got %d" % m)
     if tq.n >= 2 ** 31:
         raise ValueError("the query text must be shorter than 2^31 bytes, got %d" % tq.n)
     if not 0 <= int(ref_base) or int(ref_base) + tr.n > 2 ** 31:
         raise ValueError("ref_base + len(rtext) must stay within 2^31 (a position has 31 bits), got %r + %d" % (ref_base, tr.n))
-    if qb.where == K.KH_MEM_DEVICE:
-        link = torch.empty(m, dtype=torch.int32, device=qb.device)
-        edits, over = (torch.empty(nc, dtype=torch.int32, device=qb.device) for _ in range(2))
-        ptrs, stream = [t.data_ptr() if t.numel() else None for t in (link, edits, over)], torch.cuda.current_stream(device).cuda_stream
-    else:
-        link, edits, over = np.zeros(m, dtype=np.int32), np.zeros(nc, dtype=np.uint32), np.zeros(nc, dtype=np.uint32)
-        ptrs, stream = [a.ctypes.data if a.size else None for a in (link, edits, over)], None
-    if m == 0 and nc == 0:
-        return ChainEdits(link, edits, over)
-    ins = [b.ptr if b.n else None for b in (qb, rb, vb, pb, cb)]
-    st = K.lib().kh_chain_edits(tq.ptr if tq.n else None, tq.n, tr.ptr if tr.n else None, tr.n, int(ref_base), *ins, m, nc, int(k), int(max_edits), qb.where,
-                                *ptrs, device, stream)
-    if st != K.KH_OK:
-        raise KhError(st, "kh_chain_edits")
+    (link, lptr), (edits, eptr), (over, optr) = (alloc(qb, size, dt, empty=True) for size, dt in ((m, np.int32), (nc, np.uint32), (nc, np.uint32)))
+    if m or nc:
+        check(K.lib().kh_chain_edits(tq.ptr_or_null, tq.n, tr.ptr_or_null, tr.n, int(ref_base), *(b.ptr_or_null for b in (qb, rb, vb, pb, cb)), m, nc, int(k),
+                                     int(max_edits), qb.where, lptr, eptr, optr, device, stream_of(qb, device)), "kh_chain_edits")
     return ChainEdits(link, edits, over)
 
 
@@ -385,7 +191,6 @@ class KmerCounter:
 
     def _presize(self, text, fastq):
         if self.hll is None:      # the table's hash, seed 43, precision 12 (the reference's hyperloglog64<Key, Hash, 12>)
-            from .hll import hyperloglog64
             self.hll = hyperloglog64(12, 0, self._hash, 43, self.device)
         (self.hll.update_from_fastq if fastq else self.hll.update_from_sequence)(text, self.k, self.canonical)
         est = self.hll.estimate()
@@ -504,22 +309,7 @@ def synthetic_read_sequences(n_reads, read_len=150, genome_len=1_000_000, seed=7
 def synthetic_fastq_fixed(n_reads, read_len=150, genome_len=1_000_000, seed=7, n_rate=0.001):
     """raw FASTQ text of synthetic_read_sequences' reads (vectorised, fixed-width records: '@' + 11-digit id, sequence, '+',
     quality 'I' * read_len), as a uint8 array -- the input shape of BenchmarkKmerCounter, for the GPU FASTQ path"""
-    seq = synthetic_read_sequences(n_reads, read_len, genome_len, seed, n_rate).reshape(n_reads, read_len + 1)
-    w = 1 + 11 + 1 + (read_len + 1) + 2 + (read_len + 1)
-    out = np.empty((n_reads, w), dtype=np.uint8)
-    out[:, 0] = ord("@")
-    ids = np.arange(n_reads, dtype=np.int64)
-    for d in range(11):
-        out[:, 11 - d] = ord("0") + (ids % 10)
-        ids //= 10
-    out[:, 12] = 10
-    out[:, 13: 13 + read_len + 1] = seq
-    o = 13 + read_len + 1
-    out[:, o] = ord("+"); out[:, o + 1] = 10
-    out[:, o + 2: o + 2 + read_len] = ord("I")
-    out[:, o + 2 + read_len] = 10
-    return out.reshape(-1)
-
+    return fastq_from_sequence_lines(synthetic_read_sequences(n_reads, read_len, genome_len, seed, n_rate), n_reads, read_len)
 
 
 class ShardedKmerCounter:
@@ -573,7 +363,6 @@ class ShardedKmerCounter:
             # estimator's standard error 1.04 / sqrt(m)) before it inserts: every rank updates its registers with ITS k-mers, the
             # registers are merged over all ranks (all-reduce(max): hyperloglog64.hpp:477-484 merge_distributed / estimate_global) and
             # every rank reserves its share of the global estimate (estimate_average_per_rank :487-489).  Collective: all ranks, every batch.
-            from .hll import estimate_average_per_rank
             if self.estimate_from_text:
                 if len(text):
                     self.hll.update_from_fastq(text, self.k, self.canonical)
@@ -588,7 +377,6 @@ class ShardedKmerCounter:
     def cycle(self, queries):
         """count -> find -> erase -> count over `queries` (this rank's sample; collective).  Returns per-rank numbers:
         hits of the first count, sum of the counts find returned, keys erased on this rank's local table, hits afterwards."""
-        import time
         cuda = getattr(queries, "is_cuda", False)
 
         def lap(t0):
@@ -650,7 +438,7 @@ def synthetic_reads(n_reads, read_len=150, genome_len=1_000_000, genome_seed=7, 
 
 
 def fastq_from_sequence_lines(seq_lines, n_reads, read_len):
-    """fixed-width FASTQ text around the given sequence lines (the layout of synthetic_fastq_fixed)"""
+    """fixed-width FASTQ text around the given sequence lines: '@' + 11-digit id, the line, '+', quality 'I' * read_len per record"""
     seq = seq_lines.reshape(n_reads, read_len + 1)
     w = 1 + 11 + 1 + (read_len + 1) + 2 + (read_len + 1)
     out = np.empty((n_reads, w), dtype=np.uint8)

@@ -14,13 +14,9 @@ import ctypes as C
 import numpy as np
 
 from . import _capi as K
+from ._call import HOST, _Buf, _Handle, alloc, check, check_same, stream_of, torch  # noqa: F401  (torch: imported from here by other modules)
 from ._capi import (KH_HASH_FARM64, KH_HASH_IDENTITY, KH_HASH_MURMUR3_X64_128_H0, KH_HASH_MURMUR3_X86_128_LO64,
-                    KH_KIND_LINEARPROBE, KH_KIND_ROBINHOOD, KhError, KhLogicError, KhRetry)
-
-try:  # torch is optional for host-array use
-    import torch
-except Exception:  # pragma: no cover
-    torch = None
+                    KH_KIND_LINEARPROBE, KH_KIND_ROBINHOOD, KhError, KhLogicError, KhRetry)  # noqa: F401
 
 HASHES = {
     "identity": KH_HASH_IDENTITY,
@@ -31,109 +27,51 @@ HASHES = {
 }
 
 
-def _is_tensor(x):
-    return torch is not None and isinstance(x, torch.Tensor)
-
-
 def _hash_id(h):
     return HASHES[h] if isinstance(h, str) else int(h)
 
 
-class _Buf:
-    """pointer + memory kind of one batch argument"""
-
-    def __init__(self, x, np_dtype, itemsize):
-        if _is_tensor(x):
-            if not x.is_cuda:
-                x = x.cpu().numpy()
-            else:
-                if x.element_size() != itemsize:
-                    raise TypeError("tensor element size %d, expected %d" % (x.element_size(), itemsize))
-                self.obj = x.contiguous()
-                self.ptr = self.obj.data_ptr()
-                self.n = self.obj.numel()
-                self.where = K.KH_MEM_DEVICE
-                self.device = self.obj.device
-                return
-        a = np.ascontiguousarray(x, dtype=np_dtype)
-        self.obj = a
-        self.ptr = a.ctypes.data
-        self.n = a.size
-        self.where = K.KH_MEM_HOST
-        self.device = None
-
-
-class _TableCore:
+class _TableCore(_Handle):
     """handle + scalar state of a table of either key width over the C-ABI entry points PREFIX + name; no batch members"""
     PREFIX = "kh_"
+    STATUS_ERRORS = {K.KH_ERR_FULL: KhLogicError, K.KH_ERR_RETRY: KhRetry}
     KIND = None
     DEFAULT_MIN_LF = None
     DEFAULT_MAX_LF = None
 
     def __init__(self, capacity=128, min_load_factor=None, max_load_factor=None, hash="murmur3avx64", seed=43, device=0):
-        self._L = K.lib()
-        self._h = C.c_void_p()
         self.device = int(device)
         mn = self.DEFAULT_MIN_LF if min_load_factor is None else min_load_factor
         mx = self.DEFAULT_MAX_LF if max_load_factor is None else max_load_factor
-        widths = (8, 4) if self.PREFIX == "kh_" else ()      # kh_create takes the key / value widths, kh_wide_create has them fixed
-        st = self._fn("create")(C.byref(self._h), self.KIND, *widths, _hash_id(hash), seed, capacity, mn, mx, self.device)
-        if st != K.KH_OK:
-            self._h = C.c_void_p()
-            raise KhError(st, "%screate failed (is a GPU visible and the HIP library built?)" % self.PREFIX)
+        widths = (8, 4) if self.WORDS == 1 else ()      # kh_create takes the key / value widths, kh_wide_create has them fixed
+        self._create(self.KIND, *widths, _hash_id(hash), seed, capacity, mn, mx, self.device)
 
-    # -- plumbing --------------------------------------------------------------------------------
-    def _fn(self, name):
-        return getattr(self._L, self.PREFIX + name)
+    def _kv(self, keys, vals, msg="keys/vals must have equal length and live in the same memory space", memory_msg=None):
+        """the key batch and the optional value batch of one call, checked, the current stream adopted -> (kb, vb, pointer to the values)"""
+        kb = _Buf.keys(keys, self.WORDS)
+        vb = None if vals is None else _Buf(vals, np.uint32)
+        if memory_msg is not None:          # (a caller that says which of the two it was)
+            check_same(msg, kb, vb, memory=False)
+            msg = memory_msg
+        check_same(msg, kb, vb)
+        self._adopt_stream(kb, vb)
+        return kb, vb, None if vb is None else vb.ptr
 
-    def _chk(self, st):
-        if st == K.KH_OK:
-            return
-        msg = self._fn("last_error")(self._h).decode()
-        if st == K.KH_ERR_FULL:
-            raise KhLogicError(st, msg)
-        if st == K.KH_ERR_RETRY:
-            raise KhRetry(st, msg)
-        raise KhError(st, msg)
-
-    def _sync_stream(self, *bufs):
-        """issue the table's work on torch's current stream when device tensors are involved"""
-        if torch is not None and any(b is not None and b.where == K.KH_MEM_DEVICE for b in bufs):
-            s = torch.cuda.current_stream(self.device).cuda_stream
-            self._fn("set_stream")(self._h, C.c_void_p(s))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._fn("destroy")(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _out(self, like, shape, np_dtype, torch_dtype, zero=False):
-        """an output where the queries live; host arrays are always zeroed, device tensors when `zero`"""
-        if like.where == K.KH_MEM_DEVICE:
-            t = (torch.zeros if zero else torch.empty)(shape, dtype=torch_dtype, device=like.device)
-            return t, t.data_ptr()
-        a = np.zeros(shape, dtype=np_dtype)
-        return a, a.ctypes.data
+    def _query(self, keys):
+        """the key batch of a lookup or an erase, the current stream adopted"""
+        kb = _Buf.keys(keys, self.WORDS)
+        self._adopt_stream(kb)
+        return kb
 
     # -- scalar state ------------------------------------------------------------------------------
     def size(self):
-        v = C.c_uint64()
-        self._chk(self._fn("size")(self._h, C.byref(v)))
-        return v.value
+        return self._scalar("size")
 
     def __len__(self):
         return self.size()
 
     def capacity(self):
-        v = C.c_uint64()
-        self._chk(self._fn("capacity")(self._h, C.byref(v)))
-        return v.value
+        return self._scalar("capacity")
 
     def set_min_load_factor(self, f):
         self._chk(self._fn("set_min_load_factor")(self._h, f))
@@ -165,14 +103,14 @@ class _TableCore:
         self._chk(self._fn("rehash")(self._h, int(b)))
 
     def displacement_histogram(self):
-        out = np.zeros(128, dtype=np.uint64)
-        self._chk(self._fn("displacement_histogram")(self._h, out.ctypes.data))
-        return out
+        hist, ptr = alloc(HOST, 128, np.uint64)
+        self._chk(self._fn("displacement_histogram")(self._h, ptr))
+        return hist
 
     def export_info(self):
-        out = np.zeros(self.capacity(), dtype=np.uint8)
-        self._chk(self._fn("export_info")(self._h, out.ctypes.data))
-        return out
+        info, ptr = alloc(HOST, self.capacity(), np.uint8)
+        self._chk(self._fn("export_info")(self._h, ptr))
+        return info
 
     # -- value-range operations: the elements with lo <= value <= hi (unsigned 32-bit), one pass over the slots on the GPU ---------
     @staticmethod
@@ -186,9 +124,9 @@ class _TableCore:
         """uint64[nbins]: out[b] = number of elements with value b, the last bin those with value >= nbins - 1 (nbins 1..16384).
         On a k-mer counter this is the k-mer spectrum."""
         nbins = int(nbins)
-        out = np.zeros(min(max(nbins, 1), 16384), dtype=np.uint64)
-        self._chk(self._fn("value_histogram")(self._h, nbins if 0 <= nbins <= 0xFFFFFFFF else 0, out.ctypes.data))      # (0: refused by the library)
-        return out
+        hist, ptr = alloc(HOST, min(max(nbins, 1), 16384), np.uint64)
+        self._chk(self._fn("value_histogram")(self._h, nbins if 0 <= nbins <= 0xFFFFFFFF else 0, ptr))      # (0: refused by the library)
+        return hist
 
     def count_values(self, lo, hi):
         """number of elements with lo <= value <= hi (lo > hi: the empty range)"""
@@ -202,23 +140,15 @@ class _TableCore:
         tensors (int64 keys, int32 values: the bit patterns) written on the GPU when device=True.  A table of 16-byte keys returns
         (m, 2) keys.  select_values(0, 0xFFFFFFFF, device=True) is to_vector() into device memory."""
         lo, hi = self._value_range(lo, hi)
-        words = 1 if self.PREFIX == "kh_" else 2
         m = self.size() if (lo, hi) == (0, 0xFFFFFFFF) else self.count_values(lo, hi)
-        shape = m if words == 1 else (m, 2)
+        if device and torch is None:
+            raise RuntimeError("select_values(device=True) needs torch")
+        mem = _Buf.memory(self.device) if device else HOST
+        keys, kptr = alloc(mem, m if self.WORDS == 1 else (m, self.WORDS), np.uint64, empty=True)
+        vals, vptr = alloc(mem, m, np.uint32, empty=True)
+        self._adopt_stream(mem)
         n = C.c_uint64()
-        if device:
-            if torch is None:
-                raise RuntimeError("select_values(device=True) needs torch")
-            dev = torch.device("cuda", self.device)
-            keys = torch.empty(shape, dtype=torch.int64, device=dev)
-            vals = torch.empty(m, dtype=torch.int32, device=dev)
-            self._fn("set_stream")(self._h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-            kptr, vptr, where = keys.data_ptr() if m else None, vals.data_ptr() if m else None, K.KH_MEM_DEVICE
-        else:
-            keys = np.zeros(shape, dtype=np.uint64)
-            vals = np.zeros(m, dtype=np.uint32)
-            kptr, vptr, where = keys.ctypes.data if m else None, vals.ctypes.data if m else None, K.KH_MEM_HOST
-        self._chk(self._fn("select_values")(self._h, lo, hi, where, kptr, vptr, m, C.byref(n)))
+        self._chk(self._fn("select_values")(self._h, lo, hi, mem.where, kptr, vptr, m, C.byref(n)))
         assert n.value == m, (n.value, m)
         return keys, vals
 
@@ -263,20 +193,13 @@ class _HashMapBase(_TableCore):
     def insert(self, keys, vals=None):
         """insert(Iter,Iter) / insert(vector const&): first value wins.  Returns #inserted.
         `keys` may also be an (n,2)-shaped uint64 pair array laid out like std::pair<uint64_t,uint32_t>."""
+        kb, _, vptr = self._kv(keys, vals)
+        new = C.c_uint64()
         if vals is None:
-            kb = _Buf(keys, np.uint64, 8)
-            self._sync_stream(kb)
-            n = kb.n // 2
-            out = C.c_uint64()
-            self._chk(self._L.kh_insert_pairs(self._h, kb.ptr, n, kb.where, C.byref(out)))
-            return out.value
-        kb, vb = _Buf(keys, np.uint64, 8), _Buf(vals, np.uint32, 4)
-        if kb.n != vb.n or kb.where != vb.where:
-            raise ValueError("keys/vals must have equal length and live in the same memory space")
-        self._sync_stream(kb, vb)
-        out = C.c_uint64()
-        self._chk(self._L.kh_insert(self._h, kb.ptr, vb.ptr, kb.n, kb.where, C.byref(out)))
-        return out.value
+            self._chk(self._L.kh_insert_pairs(self._h, kb.ptr, kb.n // 2, kb.where, C.byref(new)))
+        else:
+            self._chk(self._L.kh_insert(self._h, kb.ptr, vptr, kb.n, kb.where, C.byref(new)))
+        return new.value
 
     def insert_one(self, key, val):
         """insert(value_type const&): the single-key form -- no trailing reserve(size()) (hashmap_robinhood.hpp:522-626)."""
@@ -286,13 +209,10 @@ class _HashMapBase(_TableCore):
 
     def update(self, keys, vals):
         """update(k,v) applied in batch order: insert, or overwrite with the last value given."""
-        kb, vb = _Buf(keys, np.uint64, 8), _Buf(vals, np.uint32, 4)
-        if kb.n != vb.n or kb.where != vb.where:
-            raise ValueError("keys/vals must have equal length and live in the same memory space")
-        self._sync_stream(kb, vb)
-        out = C.c_uint64()
-        self._chk(self._L.kh_update(self._h, kb.ptr, vb.ptr, kb.n, kb.where, C.byref(out)))
-        return out.value
+        kb, vb, vptr = self._kv(keys, vals)
+        new = C.c_uint64()
+        self._chk(self._L.kh_update(self._h, kb.ptr, vptr, kb.n, kb.where, C.byref(new)))
+        return new.value
 
     # -- streamed insert: one insert whose pairs arrive in pieces (multi-GPU exchange) ----------------------------
     def insert_begin(self, n_total, reduce_plus=False, repeatable=False, reduce=None):
@@ -304,12 +224,8 @@ class _HashMapBase(_TableCore):
 
     def insert_feed(self, keys, vals=None):
         """partition this piece now (asynchronous for device tensors); the pieces count as one batch in feed order"""
-        kb = _Buf(keys, np.uint64, 8)
-        vb = _Buf(vals, np.uint32, 4) if vals is not None else None
-        if vb is not None and (kb.n != vb.n or kb.where != vb.where):
-            raise ValueError("keys/vals must have equal length and live in the same memory space")
-        self._sync_stream(kb, vb)
-        self._chk(self._L.kh_insert_feed(self._h, kb.ptr, vb.ptr if vb is not None else None, kb.n, kb.where))
+        kb, _, vptr = self._kv(keys, vals)
+        self._chk(self._L.kh_insert_feed(self._h, kb.ptr, vptr, kb.n, kb.where))
 
     def insert_end(self):
         out = C.c_uint64()
@@ -323,14 +239,10 @@ class _HashMapBase(_TableCore):
     def insert_reduce_plus(self, keys, vals=None):
         """Reducer = std::plus (k-mer counting when vals is None: every occurrence adds 1).  Returns #new keys.
         reference: hashmap_robinhood_offsets_reduction::insert(keys, T(1)), counting_batched_robinhood_map."""
-        kb = _Buf(keys, np.uint64, 8)
-        vb = _Buf(vals, np.uint32, 4) if vals is not None else None
-        if vb is not None and (kb.n != vb.n or kb.where != vb.where):
-            raise ValueError("keys/vals must have equal length and live in the same memory space")
-        self._sync_stream(kb, vb)
-        out = C.c_uint64()
-        self._chk(self._L.kh_insert_reduce_plus(self._h, kb.ptr, vb.ptr if vb is not None else None, kb.n, kb.where, C.byref(out)))
-        return out.value
+        kb, _, vptr = self._kv(keys, vals)
+        new = C.c_uint64()
+        self._chk(self._L.kh_insert_reduce_plus(self._h, kb.ptr, vptr, kb.n, kb.where, C.byref(new)))
+        return new.value
 
     def insert_reduce(self, keys, vals=None, op="plus"):
         """reducer insert with Reducer `op`: "plus" (== insert_reduce_plus), "min", "max" (unsigned) or "or" on the 32-bit values.  A new
@@ -339,25 +251,20 @@ class _HashMapBase(_TableCore):
         rop = K.reduce_op(op)
         if vals is None and rop != K.KH_REDUCE_PLUS:
             raise ValueError("insert_reduce(op=%r) needs values: only 'plus' has a default (1 per occurrence)" % (op,))
-        kb = _Buf(keys, np.uint64, 8)
-        vb = _Buf(vals, np.uint32, 4) if vals is not None else None
-        if vb is not None and (kb.n != vb.n or kb.where != vb.where):
-            raise ValueError("keys/vals must have equal length and live in the same memory space")
-        self._sync_stream(kb, vb)
-        out = C.c_uint64()
-        self._chk(self._L.kh_insert_reduce(self._h, kb.ptr, vb.ptr if vb is not None else None, kb.n, kb.where, rop, C.byref(out)))
-        return out.value
+        kb, _, vptr = self._kv(keys, vals)
+        new = C.c_uint64()
+        self._chk(self._L.kh_insert_reduce(self._h, kb.ptr, vptr, kb.n, kb.where, rop, C.byref(new)))
+        return new.value
 
     def count(self, keys, out=None):
         """count(Iter,Iter): 0/1 per query, query order (uint8).  out: a contiguous uint8 CUDA tensor of the queries' length to write
         into (device queries only; nothing is allocated or copied then)."""
-        kb = _Buf(keys, np.uint64, 8)
-        self._sync_stream(kb)
-        if out is not None and kb.where == K.KH_MEM_DEVICE:
+        kb = self._query(keys)
+        if out is not None and kb.dev:
             assert out.is_contiguous() and out.numel() == kb.n and out.element_size() == 1
             optr = out.data_ptr()
         else:
-            out, optr = self._out(kb, kb.n, np.uint8, torch.uint8 if torch else None)
+            out, optr = alloc(kb, kb.n, np.uint8)
         self._chk(self._L.kh_count(self._h, kb.ptr, kb.n, kb.where, optr))
         return out
 
@@ -365,44 +272,30 @@ class _HashMapBase(_TableCore):
         """per-query form: (values, found) aligned with the queries (values of misses are 0).  out_vals / out_found: contiguous
         int32 / uint8 CUDA tensors of the queries' length to write into (device queries only; out_vals must hold 0 where a miss is to
         read 0: the library leaves the values of misses untouched).  want_total=False: the call does not wait for the device."""
-        kb = _Buf(keys, np.uint64, 8)
-        self._sync_stream(kb)
-        if kb.where == K.KH_MEM_DEVICE:
-            vals = out_vals if out_vals is not None else torch.zeros(kb.n, dtype=torch.int32, device=kb.device)
-            found = out_found if out_found is not None else torch.empty(kb.n, dtype=torch.uint8, device=kb.device)
+        kb = self._query(keys)
+        vals, vptr = alloc(kb, kb.n, np.uint32, zero=True) if out_vals is None or not kb.dev else (out_vals, out_vals.data_ptr())
+        found, fptr = alloc(kb, kb.n, np.uint8) if out_found is None or not kb.dev else (out_found, out_found.data_ptr())
+        if kb.dev:
             assert vals.is_contiguous() and found.is_contiguous() and vals.numel() == kb.n and found.numel() == kb.n
-            vptr, fptr = vals.data_ptr(), found.data_ptr()
-        else:
-            vals = np.zeros(kb.n, dtype=np.uint32)
-            found = np.zeros(kb.n, dtype=np.uint8)
-            vptr, fptr = vals.ctypes.data, found.ctypes.data
         nf = C.c_uint64()
         self._chk(self._L.kh_find(self._h, kb.ptr, kb.n, kb.where, vptr, fptr, C.byref(nf) if want_total else None))
         return vals, found
 
     def find(self, keys):
         """find(Iter,Iter): the (key, value) pairs of the hits only, in query order -> (keys, vals)."""
-        kb = _Buf(keys, np.uint64, 8)
-        self._sync_stream(kb)
-        if kb.where == K.KH_MEM_DEVICE:
-            ok = torch.empty(kb.n, dtype=torch.int64, device=kb.device)
-            ov = torch.empty(kb.n, dtype=torch.int32, device=kb.device)
-            kptr, vptr = ok.data_ptr(), ov.data_ptr()
-        else:
-            ok = np.zeros(kb.n, dtype=np.uint64)
-            ov = np.zeros(kb.n, dtype=np.uint32)
-            kptr, vptr = ok.ctypes.data, ov.ctypes.data
+        kb = self._query(keys)
+        ok, kptr = alloc(kb, kb.n, np.uint64)
+        ov, vptr = alloc(kb, kb.n, np.uint32)
         nf = C.c_uint64()
         self._chk(self._L.kh_find_compact(self._h, kb.ptr, kb.n, kb.where, kptr, vptr, C.byref(nf)))
         return ok[: nf.value], ov[: nf.value]
 
     def erase(self, keys):
         """erase(Iter,Iter): returns #erased (RH never shrinks here; LP may, as in the reference)."""
-        kb = _Buf(keys, np.uint64, 8)
-        self._sync_stream(kb)
-        out = C.c_uint64()
-        self._chk(self._L.kh_erase(self._h, kb.ptr, kb.n, kb.where, C.byref(out)))
-        return out.value
+        kb = self._query(keys)
+        erased = C.c_uint64()
+        self._chk(self._L.kh_erase(self._h, kb.ptr, kb.n, kb.where, C.byref(erased)))
+        return erased.value
 
     def erase_one(self, key):
         """erase(key): single-key form, halves the table when size < min_load."""
@@ -413,10 +306,10 @@ class _HashMapBase(_TableCore):
     # -- iteration / exports -----------------------------------------------------------------------------
     def to_vector(self):
         n = self.size()
-        k = np.zeros(max(n, 1), dtype=np.uint64)
-        v = np.zeros(max(n, 1), dtype=np.uint32)
+        k, kptr = alloc(HOST, max(n, 1), np.uint64)
+        v, vptr = alloc(HOST, max(n, 1), np.uint32)
         m = C.c_uint64()
-        self._chk(self._L.kh_to_vector(self._h, k.ctypes.data, v.ctypes.data, C.byref(m)))
+        self._chk(self._L.kh_to_vector(self._h, kptr, vptr, C.byref(m)))
         assert m.value == n, (m.value, n)
         return k[:n], v[:n]
 
@@ -429,9 +322,9 @@ class _HashMapBase(_TableCore):
         return k[o], v[o]
 
     def export_slots(self):
-        k = np.zeros(self.capacity(), dtype=np.uint64)
-        v = np.zeros(self.capacity(), dtype=np.uint32)
-        self._chk(self._L.kh_export_slots(self._h, k.ctypes.data, v.ctypes.data))
+        k, kptr = alloc(HOST, self.capacity(), np.uint64)
+        v, vptr = alloc(HOST, self.capacity(), np.uint32)
+        self._chk(self._L.kh_export_slots(self._h, kptr, vptr))
         return k, v
 
     # -- measurement ---------------------------------------------------------------------------------------
@@ -443,13 +336,7 @@ class _HashMapBase(_TableCore):
 
     def profile(self):
         """{kernel name: (launches, total_ms)} measured with HIP events on the table's stream"""
-        buf = C.create_string_buffer(1 << 16)
-        self._chk(self._L.kh_profile_dump(self._h, buf, len(buf)))
-        out = {}
-        for line in buf.value.decode().splitlines():
-            name, n, ms = line.split()
-            out[name] = (int(n), float(ms))
-        return out
+        return self._profile()
 
 
 class hashmap_robinhood_doubling(_HashMapBase):
@@ -474,18 +361,8 @@ class hashmap_linearprobe_doubling(_HashMapBase):
 def hash_batch(keys, hash="murmur3avx64", seed=43, device=0, lex_less_k=0):
     """Hash::operator()(Key const*, count, out): batched 64-bit hashing on the GPU; lex_less_k = k: TransformedHash with the
     lex_less pre-transform on 2-bit packed DNA k-mers (hash of min(k-mer, reverse complement))."""
-    L = K.lib()
-    kb = _Buf(keys, np.uint64, 8)
-    if kb.where == K.KH_MEM_DEVICE:
-        out = torch.empty(kb.n, dtype=torch.int64, device=kb.device)
-        optr = out.data_ptr()
-        stream = torch.cuda.current_stream(device).cuda_stream
-    else:
-        out = np.zeros(kb.n, dtype=np.uint64)
-        optr = out.ctypes.data
-        stream = None
-    st = L.kh_hash_batch_transformed(_hash_id(hash), seed, K.KH_XF_DNA_LEX_LESS if lex_less_k else K.KH_XF_IDENTITY, int(lex_less_k),
-                                     kb.ptr, kb.n, kb.where, optr, device, stream)
-    if st != K.KH_OK:
-        raise KhError(st, "kh_hash_batch_transformed")
-    return out
+    kb = _Buf.keys(keys)
+    hashes, hptr = alloc(kb, kb.n, np.uint64)
+    check(K.lib().kh_hash_batch_transformed(_hash_id(hash), seed, K.KH_XF_DNA_LEX_LESS if lex_less_k else K.KH_XF_IDENTITY, int(lex_less_k),
+                                            kb.ptr, kb.n, kb.where, hptr, device, stream_of(kb, device)), "kh_hash_batch_transformed")
+    return hashes
