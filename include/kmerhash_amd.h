@@ -775,6 +775,50 @@ kh_status kh_chain_edits(const void* qtext /*[h|d] u8[nq]*/, uint64_t nq, const 
                          uint32_t k /*1..64*/, uint32_t max_edits /*0..31*/, kh_mem where, int32_t* out_link /*[m]*/,
                          uint32_t* c_edits /*[n_chains]*/, uint32_t* c_over /*[n_chains]*/, int device, void* hip_stream);
 
+/* ---- alignment operations per chain.  kh_chain_cigars says WHICH edits kh_chain_edits counted: for every link a run-length alignment
+ *      of A against B, found by the traceback of the same furthest-reaching-point pass.  Inputs: those of kh_chain_edits (texts, anchors,
+ *      pred, chain, n_chains, k; links, strings A and B, orientation and the match rule are defined there) and link[m], the out_link
+ *      array that call wrote over the same inputs.
+ *      Output: a CSR in anchor order.  Row i = out_ops[out_offsets[i] .. out_offsets[i + 1]) describes how A = qtext[q_j, q_i) becomes
+ *      B, the reference stretch A faces (reverse-complemented on the reverse strand), read from the seed of anchor j = pred[i] forwards.
+ *      Each run is one uint32 in BAM encoding, (len << 4) | op, with op I = 1 (a base of A that B lacks), D = 2 (a base of B that A
+ *      lacks), '=' = 7 (matching bases) and X = 8 (a substitution).  Adjacent runs of a row never share an op; a row has at most
+ *      2 link[i] + 1 runs.
+ *      Which rows are non-empty.  Row i is empty unless anchor i has a link that passes the range checks of kh_chain_edits with
+ *      max_edits = 31 -- 0 <= chain[i] < n_chains, 0 <= pred[i] < i, chain[pred[i]] == chain[i]; all four positions < 2^31; dq >= 1,
+ *      dr >= 1, q_i + k <= nq, B's stretch of rtext (with its + k on the reverse strand) inside [0, nr]; |dq - dr| <= 31 -- and unless
+ *      0 <= link[i] <= 31, dq < 2^28 and dr < 2^28.  Then:
+ *        link[i] == 0 and dq == dr: the single run "dq =".  The texts are not read.
+ *        link[i] == 0 and dq != dr: an empty row.
+ *        link[i] > 0: the canonical alignment below, looked for among the distances 0..link[i].  If the target is reached at a smaller
+ *        e than link[i], that alignment is the row; if it is not reached by link[i], the row is empty.
+ *      Garbage in link, pred or chain therefore yields empty or wrong rows; it never causes a read outside the texts or a write outside
+ *      the arrays.
+ *      Canonical alignment.  Fixed on the furthest-reaching points, so that it depends on no scheduling and tests/cigar_model.py equals
+ *      it bit for bit.  n = |A|, mB = |B|; diagonal d = (offset in B) - (offset in A), -31..31; hi(d) = min(n, mB - d); ext(v, d) = the
+ *      offset in A after the run of matching bases from v on d, at most hi(d) (an N matches nothing).  F_0[0] = ext(0, 0), every other
+ *      diagonal is unreached.  For e >= 1 the candidates of d are  X: F_{e-1}[d] + 1,  I: F_{e-1}[d+1] + 1,  D: F_{e-1}[d-1];  a
+ *      candidate is valid iff its source is reached and its value v satisfies v <= hi(d) and v + d >= 0 -- an invalid one is dropped,
+ *      not clamped: a clamped value is no real edit and cannot be traced back.  pre_e[d] = the greatest valid candidate, the MOVE of
+ *      (e, d) the first of X, I, D that attains it, F_e[d] = ext(pre_e[d], d).  The alignment is complete at the first e with
+ *      F_e[mB - n] == n; the traceback follows the moves from (e, mB - n) to (0, 0).  Read forwards the row is F_0[0] '=', then per
+ *      level t one base of its move and F_t[d_t] - pre_t[d_t] of '='; zero lengths are dropped and equal neighbours merged.
+ *      c_ins[c] and c_del[c] = the I and D bases summed over the non-empty rows of chain c; the call zeroes both arrays [n_chains]
+ *      first.  With c_edits they give a chain's mismatches (edits - I - D), its matched bases (q_end - q_start - X - I) and its
+ *      alignment block length without a look at the ops.
+ *      All arrays live in the memory `where` names.  out_ops == NULL: count only -- out_offsets, *n_ops and the chain arrays are
+ *      written.  More runs than cap_ops: KH_ERR_INVALID with *n_ops set, out_offsets written and out_ops untouched.  Device memory:
+ *      everything is queued on hip_stream and the one host wait is the one that learns *n_ops.  Host memory: staged, the call synchronises.
+ *      KH_ERR_INVALID before anything is allocated, read or written: k outside 1..64, m > 2^24, nq >= 2^31, ref_base + nr > 2^31, `where`
+ *      outside the enum, n_chains > 0 with a null c_ins or c_del, a null out_offsets or n_ops, and while m > 0 a null array (link
+ *      included) or a null text of positive length.  m == 0: KH_OK, *n_ops = 0, out_offsets[0] = 0, c_ins and c_del zeroed. */
+kh_status kh_chain_cigars(const void* qtext /*[h|d] u8[nq]*/, uint64_t nq, const void* rtext /*[h|d] u8[nr]*/, uint64_t nr, uint32_t ref_base,
+                          const uint32_t* qpos /*[h|d] u32[m]*/, const uint32_t* rpos /*[h|d] u32[m]*/, const uint8_t* rev /*[h|d] u8[m]*/,
+                          const int32_t* pred /*[h|d] i32[m]*/, const int32_t* chain /*[h|d] i32[m]*/, uint64_t m, uint64_t n_chains,
+                          uint32_t k /*1..64*/, const int32_t* link /*[h|d] i32[m], out_link of kh_chain_edits*/, kh_mem where,
+                          uint64_t* out_offsets /*[m+1]*/, uint32_t* out_ops /*[cap_ops] or NULL*/, uint64_t cap_ops, uint64_t* n_ops,
+                          uint32_t* c_ins /*[n_chains]*/, uint32_t* c_del /*[n_chains]*/, int device, void* hip_stream);
+
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);
 

@@ -16,6 +16,7 @@
 //   csr     : kh_csr_unpermute, a CSR that arrives in a permuted order back into query order: the index's scans and gather around one scatter (kh_kernels_csr.h).
 //   chain   : kh_chain_anchors, collinear chains per segment from flat anchors: a wavefront per segment, the last 64 anchors in registers (kh_kernels_chain.h).
 //   edits   : kh_chain_edits, edit distance of every link of every kept chain: a lane per anchor, then a wavefront per unsettled link (kh_kernels_edits.h).
+//   cigars  : kh_chain_cigars, the alignment operations of every link as run-length rows of a CSR: the same wavefront pass with a traceback (kh_kernels_cigar.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
 #include "kh_kernels_values.h"
@@ -24,6 +25,7 @@
 #include "kh_kernels_csr.h"
 #include "kh_kernels_chain.h"
 #include "kh_kernels_edits.h"
+#include "kh_kernels_cigar.h"
 #include "kh_part_sizing.h"
 #include "kh_scratch.h"
 #include "../../include/kmerhash_amd.h"
@@ -4162,6 +4164,68 @@ kh_status kh_chain_edits(const void* qtext, uint64_t nq, const void* rtext, uint
     s.launched();
   }
   s.copy_back(dl, m); s.copy_back(de, nc); s.copy_back(dov, nc);
+  return s.finish_queued();
+}
+// ---- alignment operations per chain link (kernels: kh_kernels_cigar.h).  No handle; one pooled block holds the worklist, the run counts
+//      and the path words (and the staged arrays of a host call), a second one the staged rows of a host call.  Everything is queued on
+//      the caller's stream; the one host wait is the one that learns *n_ops.
+kh_status kh_chain_cigars(const void* qtext, uint64_t nq, const void* rtext, uint64_t nr, uint32_t ref_base, const uint32_t* qpos, const uint32_t* rpos,
+                          const uint8_t* rev, const int32_t* pred, const int32_t* chain, uint64_t m, uint64_t n_chains, uint32_t k, const int32_t* link,
+                          kh_mem where, uint64_t* out_offsets, uint32_t* out_ops, uint64_t cap_ops, uint64_t* n_ops, uint32_t* c_ins, uint32_t* c_del,
+                          int device, void* stream_) {
+  const uint64_t lim = uint64_t(1) << 31;
+  if (k < 1 || k > 64 || m > (uint64_t(1) << 24) || nq >= lim || nr > lim || ref_base + nr > lim) return KH_ERR_INVALID;
+  if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || (n_chains && (!c_ins || !c_del)) || !out_offsets || !n_ops) return KH_ERR_INVALID;
+  if (m && (!qpos || !rpos || !rev || !pred || !chain || !link || (nq && !qtext) || (nr && !rtext))) return KH_ERR_INVALID;
+  const uint64_t nc = std::min<uint64_t>(n_chains, lim);      // (a chain number is an int32: rows beyond 2^31 are never addressed)
+  *n_ops = 0;
+  if (m == 0 && where == KH_MEM_HOST) {
+    if (nc) { memset(c_ins, 0, nc * sizeof(uint32_t)); memset(c_del, 0, nc * sizeof(uint32_t)); }
+    out_offsets[0] = 0;
+    return KH_OK;
+  }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK0(hipSetDevice(device));
+  if (m == 0) {      // device memory: three memsets, queued
+    HIPCHK0(hipMemsetAsync(out_offsets, 0, sizeof(uint64_t), stream));
+    if (nc) { HIPCHK0(hipMemsetAsync(c_ins, 0, nc * sizeof(uint32_t), stream)); HIPCHK0(hipMemsetAsync(c_del, 0, nc * sizeof(uint32_t), stream)); }
+    return KH_OK;
+  }
+  const uint64_t nst = (m + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
+  Scratch s(device, stream);
+  uint32_t *wl = nullptr, *wl_count = nullptr, *runs = nullptr, *di = nullptr, *dd = nullptr, *dops = nullptr;
+  uint64_t *paths = nullptr, *doff = nullptr; unsigned long long* ssums = nullptr;
+  const int32_t* dlink = nullptr;
+  KedArgs P{};
+  if (!s.layout([&](Scratch& c) {
+        wl = c.take<uint32_t>(m); wl_count = c.take<uint32_t>(1); runs = c.take<uint32_t>(m); paths = c.take<uint64_t>(m);
+        ssums = c.take<unsigned long long>(nst + 1);
+        P.qtext = c.in(static_cast<const uint8_t*>(qtext), nq, where); P.rtext = c.in(static_cast<const uint8_t*>(rtext), nr, where);
+        P.qpos = c.in(qpos, m, where); P.rpos = c.in(rpos, m, where); P.rev = c.in(rev, m, where);
+        P.pred = c.in(pred, m, where); P.chain = c.in(chain, m, where); dlink = c.in(link, m, where);
+        doff = c.out(out_offsets, m + 1, where); di = c.out(c_ins, nc, where); dd = c.out(c_del, nc, where);
+      })) return s.finish();
+  if (nc) { s.zero(di, nc * sizeof(uint32_t)); s.zero(dd, nc * sizeof(uint32_t)); }
+  s.zero(wl_count, sizeof(uint32_t));
+  P.nq = (uint32_t)nq; P.nr = (uint32_t)nr; P.ref_base = ref_base; P.m = (uint32_t)m; P.n_chains = (uint32_t)nc; P.k = k; P.max_edits = 31;
+  const uint32_t ncu = (uint32_t)cu_count(device);
+  hipLaunchKernelGGL(k_cigar_classify, dim3(grid_for(m, KED_THREADS, ncu * 8)), dim3(KED_THREADS), 0, stream, P, dlink, runs, wl, wl_count);
+  hipLaunchKernelGGL(k_cigar_wfa, dim3(grid_for(m, KED_WAVES, ncu * 8)), dim3(KED_THREADS), 0, stream, P, dlink, (const uint32_t*)wl, (const uint32_t*)wl_count, runs,
+                     paths, di, dd);
+  scan_counts(stream, (const uint32_t*)runs, m, ssums, doff);
+  s.launched();
+  unsigned long long total = 0;
+  s.read(&total, (const unsigned long long*)(ssums + nst));
+  s.copy_back(doff, m + 1); s.copy_back(di, nc); s.copy_back(dd, nc);
+  if (!s.sync()) return s.finish();      // the one host wait of a device call: *n_ops
+  *n_ops = total;
+  if (!out_ops || total == 0) return s.finish();
+  if (total > cap_ops) { s.finish(); return KH_ERR_INVALID; }
+  if (!s.layout([&](Scratch& c) { dops = c.out(out_ops, total, where); })) return s.finish();
+  hipLaunchKernelGGL(k_cigar_emit, dim3(grid_for(m, KED_THREADS, ncu * 8)), dim3(KED_THREADS), 0, stream, P, dlink, (const uint64_t*)doff, (const uint64_t*)paths,
+                     (uint64_t)total, dops);
+  s.launched();
+  s.copy_back(dops, total);
   return s.finish_queued();
 }
 }  // extern "C"

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from ._call import HOST, _Buf, _Handle, alloc, check_same, torch
-from .kmers import anchors_from_csr, chain_anchors, chain_edits, stamp_strand
+from .kmers import anchors_from_csr, chain_anchors, chain_cigars, chain_edits, stamp_strand
 from .seqs import is_syncmer, is_syncmer128, kmers_from_sequence, minimizers_from_sequence, syncmers128_from_sequence, syncmers_from_sequence
 from .table import _hash_id
 
@@ -293,6 +293,20 @@ class KmerPositionIndex(_Handle):
         q, r, v = table.anchors
         n_chains = int(table.count.numel() if torch is not None and isinstance(table.count, torch.Tensor) else len(table.count))
         return table, chain_edits(seq, ref_text, q, r, v, pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
+
+    def chain_cigars(self, seq, ref_text, read_starts=None, ref_base=0, max_edits=31, **params):
+        """chain_edits(seq, ref_text, ...), then the alignment behind every distance: kmers.chain_cigars over the same anchors and texts
+        with the link array chain_edits wrote -> (ChainTable, ChainEdits, ChainCigars(offsets, ops, ins, dels)): a CSR of run-length rows in
+        anchor order and the inserted and deleted bases per row of the table.  kmers.cigar_string(cigars, table, row, k) is the CIGAR
+        of one chain as text."""
+        if not self.stranded:
+            raise ValueError("chain_cigars() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to three calls)
+        table, pred = self._chains(seq, read_starts, params)
+        q, r, v = table.anchors
+        n_chains = int(table.count.numel() if torch is not None and isinstance(table.count, torch.Tensor) else len(table.count))
+        edits = chain_edits(seq, ref_text, q, r, v, pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
+        return table, edits, chain_cigars(seq, ref_text, q, r, v, pred, table.chain, n_chains, self.k, edits.link, ref_base, self.device)
 
     def _syncmers(self, seq, fastq=False):
         """the closed syncmers of a text under the index's own parameters"""

@@ -174,6 +174,78 @@ def chain_edits(qtext, rtext, qpos, rpos, rev, pred, chain, n_chains, k, ref_bas
     return ChainEdits(link, edits, over)
 
 
+ChainCigars = collections.namedtuple("ChainCigars", "offsets ops ins dels")
+CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}      # the BAM operation codes kh_chain_cigars writes: a run is (len << 4) | op
+
+
+def chain_cigars(qtext, rtext, qpos, rpos, rev, pred, chain, n_chains, k, link, ref_base=0, device=0):
+    """which edits chain_edits counted (kh_chain_cigars in include/kmerhash_amd.h, which holds the definition): per anchor link a
+    run-length alignment of A = qtext[q_pred, q_i) against B = the stretch of rtext it faces, found by the traceback of the same
+    furthest-reaching-point pass.  The inputs are those of chain_edits plus `link`, the array that call returned over them.
+    -> ChainCigars(offsets, ops, ins, dels): a CSR in anchor order -- row i is ops[offsets[i]:offsets[i + 1]], each run (len << 4) | op
+    with I = 1 (a base of A that B lacks), D = 2, '=' = 7 and X = 8; empty where i has no link, where the link is outside the texts or
+    link[i] is not its distance -- then ins[c] and dels[c], the I and D bases of chain c.  Count, then emit: two calls, one allocation of
+    the exact size.  numpy in, numpy out (uint64, uint32, uint32, uint32); CUDA tensors in, tensors out on the current stream (int64, then
+    int32 holding the uint32 bits); the call waits for the stream once per pass, to learn the number of runs.  At most 2^24 anchors per
+    call.  cigar_string() turns the rows of one chain into text."""
+    if not 1 <= int(k) <= 64:
+        raise ValueError("k must be 1..64, got %r" % (k,))
+    if not 0 <= int(n_chains) <= 2 ** 31:
+        raise ValueError("n_chains must be 0..2^31, got %r" % (n_chains,))
+    tq, tr = _Buf.text(qtext), _Buf.text(rtext)
+    qb, rb, vb = _Buf(qpos, np.uint32), _Buf(rpos, np.uint32), _Buf(rev, np.uint8)
+    pb, cb, lb = _Buf(pred, np.int32), _Buf(chain, np.int32), _Buf(link, np.int32)
+    check_same("the texts, qpos, rpos, rev, pred, chain and link must live in the same memory", tq, tr, qb, rb, vb, pb, cb, lb, length=False)
+    m, nc = qb.n, int(n_chains)
+    check_same("qpos, rpos, rev, pred, chain and link must have one entry per anchor, got %d, %d, %d, %d, %d and %d" % (m, rb.n, vb.n, pb.n, cb.n, lb.n),
+               qb, rb, vb, pb, cb, lb)
+    if m > 2 ** 24:
+        raise ValueError("at most 2^24 anchors per call (batch over reads), got %d" % m)
+    if tq.n >= 2 ** 31:
+        raise ValueError("the query text must be shorter than 2^31 bytes, got %d" % tq.n)
+    if not 0 <= int(ref_base) or int(ref_base) + tr.n > 2 ** 31:
+        raise ValueError("ref_base + len(rtext) must stay within 2^31 (a position has 31 bits), got %r + %d" % (ref_base, tr.n))
+    (offs, optr), (ins, iptr), (dels, dptr) = alloc(qb, m + 1, np.uint64, zero=True), alloc(qb, nc, np.uint32, empty=True), alloc(qb, nc, np.uint32, empty=True)
+    if m == 0 and (nc == 0 or not qb.dev):      # nothing to queue: the zeroed host arrays are the answer
+        return ChainCigars(offs, alloc(qb, 0, np.uint32)[0], ins, dels)
+    fn, n, stream = K.lib().kh_chain_cigars, C.c_uint64(), stream_of(qb, device)
+    args = (tq.ptr_or_null, tq.n, tr.ptr_or_null, tr.n, int(ref_base), *(b.ptr_or_null for b in (qb, rb, vb, pb, cb)), m, nc, int(k), lb.ptr_or_null, qb.where, optr)
+    check(fn(*args, None, 0, C.byref(n), iptr, dptr, device, stream), "kh_chain_cigars")
+    ops, pptr = alloc(qb, n.value, np.uint32)
+    if n.value:
+        check(fn(*args, pptr, n.value, C.byref(n), iptr, dptr, device, stream), "kh_chain_cigars")
+    return ChainCigars(offs, ops, ins, dels)
+
+
+def _host(x, dtype):
+    return (x.cpu().numpy() if _is_tensor(x) else np.asarray(x)).view(dtype) if len(x) else np.zeros(0, dtype=dtype)
+
+
+def cigar_string(cigars, table, row, k):
+    """the CIGAR of chain `row` of a ChainTable as text (a host helper: the arrays are copied to the host if they are tensors): the rows
+    of the chain's anchors in ascending anchor order, then k '=' for its last seed, equal neighbours merged -- the query interval
+    [q_start, q_end) against the reference interval [r_start, r_end), reverse-complemented for a reverse-strand chain.  None where a
+    link of the chain has an empty row (outside the texts or more than max_edits: over[row] > 0 is the usual case): such a chain has no
+    whole-chain alignment."""
+    offs, ops, chain = _host(cigars.offsets, np.int64), _host(cigars.ops, np.uint32), _host(table.chain, np.int32)
+    members = np.flatnonzero(chain == int(row))
+    if members.size == 0:
+        raise ValueError("chain %r has no anchors in this table" % (row,))
+    runs = []
+    for i in members[1:]:
+        if offs[i + 1] == offs[i]:
+            return None
+        runs.extend((int(v) & 15, int(v) >> 4) for v in ops[offs[i]:offs[i + 1]])
+    runs.append((7, int(k)))
+    out = []
+    for op, n in runs:
+        if out and out[-1][0] == op:
+            out[-1][1] += n
+        else:
+            out.append([op, n])
+    return "".join("%d%s" % (n, CIGAR_OPS[op]) for op, n in out)
+
+
 class KmerCounter:
     """counting index: k-mer -> number of occurrences (Reducer = std::plus, value 1 per occurrence)"""
 
