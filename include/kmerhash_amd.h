@@ -819,6 +819,57 @@ kh_status kh_chain_cigars(const void* qtext /*[h|d] u8[nq]*/, uint64_t nq, const
                           uint64_t* out_offsets /*[m+1]*/, uint32_t* out_ops /*[cap_ops] or NULL*/, uint64_t cap_ops, uint64_t* n_ops,
                           uint32_t* c_ins /*[n_chains]*/, uint32_t* c_del /*[n_chains]*/, int device, void* hip_stream);
 
+/* ---- the ends of every chain.  kh_chain_edits and kh_chain_cigars stop at the seeds: a chain's alignment covers the read from its first
+ *      seed's first base to its last seed's last base.  kh_chain_ends looks at the rest of the read: from either outermost seed it
+ *      extends the alignment outwards until the read ends or until stopping scores better (a soft clip), and says how far it came, at
+ *      what cost, and by which operations.  Inputs: the two texts with ref_base and the anchors qpos, rpos, rev [m] as for
+ *      kh_chain_edits (bases and the match rule are defined there: an N matches nothing); c_first, c_last [n_chains], the anchor
+ *      indices of each kept chain's first and last anchor as kh_chain_anchors wrote them; q_lo, q_hi [n_chains], the byte interval
+ *      [q_lo, q_hi) of the chain's read in qtext; k, max_edits (0..31) and clip_cost (1..255; 4 is a usual value).
+ *      Rows.  Chain c has two ends: row 2c is its HEAD, the part of the read before its first seed, row 2c + 1 its TAIL, the part behind
+ *      its last seed.  With f = c_first[c], l = c_last[c], the strand taken from bit 0 of rev[f] for the head and of rev[l] for the
+ *      tail, both strings run AWAY from the seed:
+ *        tail, A = qtext[q_l + k, q_hi) read upwards;  B forward: rtext read upwards from r_l + k - ref_base;  B reverse: the complement
+ *              of rtext read downwards from r_l - ref_base - 1;
+ *        head, A = qtext[q_lo, q_f) read DOWNWARDS from q_f - 1;  B forward: rtext read downwards from r_f - ref_base - 1 (no
+ *              complement);  B reverse: the complement of rtext read upwards from r_f + k - ref_base.
+ *      n = |A|; |B| = min(n + max_edits, the bases rtext has left in that direction).
+ *      Which rows are looked at.  With x = f for the head and x = l for the tail, a row is EMPTY -- no runs, all four numbers 0 --
+ *      unless x < m; q_x < 2^31 and r_x < 2^31; the seed lies inside the read and the read inside the text, q_lo <= q_x and
+ *      q_x + k <= q_hi <= nq; the seed lies inside rtext, ref_base <= r_x and r_x + k - ref_base <= nr; and 1 <= n < 2^28.  (n == 0: the
+ *      seed touches the read's end; nothing is left to align and e_clip is 0.)  Garbage in the arrays therefore yields empty or wrong
+ *      rows; no byte outside the two texts is ever read and no element outside the arrays is written.
+ *      Extension.  The furthest-reaching points F_e[d] are those of the canonical alignment of kh_chain_cigars, word for word: diagonal
+ *      d = (offset in B) - (offset in A), -31..31; hi(d) = min(n, |B| - d); F_0[0] = ext(0, 0); candidates X, I, D, an invalid one
+ *      dropped, not clamped; the move of (e, d) the first of X, I, D that attains the greatest valid candidate.  What differs is the
+ *      target: A must be used up, B may end anywhere, and the alignment may stop early.  Levels e = 0..E are computed, E = the first
+ *      level at which some diagonal holds n, or max_edits if none does.  Every reached point scores S(e, d) = F_e[d] - clip_cost * e:
+ *      one for each base of the read it aligns, clip_cost off for each edit.  The end's alignment stops at the point of greatest S; ties
+ *      go to the smaller e, then to the smaller |d|, then to d < 0.  (0, 0) is always reached, so an end never scores below its
+ *      exact-match extension.  Stopping at E loses nothing: F never exceeds n, so a later level scores below n - clip_cost * E.
+ *      Outputs per row: e_q = F at that point, the bases of the read that are aligned; e_r = F + d, the bases of the reference they
+ *      face; e_edits = e; e_clip = n - F, the bases of the read left over (a soft clip); and a CSR row of runs in the BAM encoding of
+ *      kh_chain_cigars (I, D, =, X -- no S: e_clip says it), found by the traceback from that point to (0, 0).  A tail's row is stored
+ *      as it is found, from the seed outwards.  A HEAD's row is stored in READ order, the reverse of the order in which it is found --
+ *      so head row, the chain's link rows, k '=' for the last seed and tail row concatenate to the CIGAR of the whole read.  Adjacent
+ *      runs never share an op; a row has at most 2 e_edits + 1 <= 63 runs.
+ *      All arrays live in the memory `where` names.  out_ops == NULL: count only -- the four numbers, out_offsets [2 n_chains + 1] and
+ *      *n_ops are written.  More runs than cap_ops: KH_ERR_INVALID with *n_ops set, the numbers and out_offsets written and out_ops
+ *      untouched.  Device memory: everything is queued on hip_stream and the one host wait is the one that learns *n_ops.  Host memory:
+ *      staged, the call synchronises.
+ *      KH_ERR_INVALID before anything is allocated, read or written: k outside 1..64, max_edits > 31, clip_cost outside 1..255,
+ *      m > 2^24, n_chains > 2^23, nq >= 2^31, ref_base + nr > 2^31, `where` outside the enum, a null out_offsets or n_ops, while
+ *      n_chains > 0 a null chain array or output, and while both n_chains > 0 and m > 0 a null anchor array or a null text of positive
+ *      length.  n_chains == 0: KH_OK, *n_ops = 0, out_offsets[0] = 0. */
+kh_status kh_chain_ends(const void* qtext /*[h|d] u8[nq]*/, uint64_t nq, const void* rtext /*[h|d] u8[nr]*/, uint64_t nr, uint32_t ref_base,
+                        const uint32_t* qpos /*[h|d] u32[m]*/, const uint32_t* rpos /*[h|d] u32[m]*/, const uint8_t* rev /*[h|d] u8[m]*/, uint64_t m,
+                        const uint32_t* c_first /*[h|d] u32[n_chains]*/, const uint32_t* c_last /*[h|d] u32[n_chains]*/,
+                        const uint32_t* q_lo /*[h|d] u32[n_chains]*/, const uint32_t* q_hi /*[h|d] u32[n_chains]*/, uint64_t n_chains,
+                        uint32_t k /*1..64*/, uint32_t max_edits /*0..31*/, uint32_t clip_cost /*1..255*/, kh_mem where,
+                        uint32_t* e_q, uint32_t* e_r, uint32_t* e_edits, uint32_t* e_clip /* each [2 n_chains] */,
+                        uint64_t* out_offsets /*[2 n_chains + 1]*/, uint32_t* out_ops /*[cap_ops] or NULL*/, uint64_t cap_ops, uint64_t* n_ops,
+                        int device, void* hip_stream);
+
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);
 

@@ -37,11 +37,12 @@ __device__ __forceinline__ int kcg_link(const KedArgs& P, const int32_t* __restr
 }
 
 // the runs of a row, built in forward order: equal neighbours merge, zero lengths vanish; with EMIT run r goes to out[r] while r < cap
+// -- with `back` to out[cap - 1 - r]: a row that was found from its far end (the head of a chain, kh_kernels_ends.h)
 template <bool EMIT>
 struct KcgRuns {
-  uint32_t* out; uint32_t cap, n, op, len, ins, del;
+  uint32_t* out; uint32_t cap, n, op, len, ins, del, back;
   __device__ __forceinline__ void flush() {
-    if (len) { if (EMIT && n < cap) out[n] = (len << 4) | op; ++n; }
+    if (len) { if (EMIT && n < cap) out[back ? cap - 1u - n : n] = (len << 4) | op; ++n; }
   }
   __device__ __forceinline__ void add(uint32_t o, uint32_t l) {
     if (!l) return;
@@ -50,9 +51,11 @@ struct KcgRuns {
     op = o; len = l;
   }
 };
-// forward replay of a path word along one diagonal per level -> false if the path does not end in (|A|, |B|): nothing it says is used then
-template <bool EMIT>
-__device__ __forceinline__ bool kcg_replay(const KedArgs& P, const KedLink& L, uint64_t path, KcgRuns<EMIT>& R) {
+// forward replay of a path word along one diagonal per level, over the strings L (a KedLink, or the KenEnd of kh_kernels_ends.h: a STR of
+// ked_extend with dq = |A| and dr = |B|) -> the point (v_end, d_end) it ends in, or false where a move leaves the strings or the word has
+// a 32nd level
+template <bool EMIT, typename STR>
+__device__ __forceinline__ bool kcg_walk(const KedArgs& P, const STR& L, uint64_t path, KcgRuns<EMIT>& R, int& v_end, int& d_end) {
   int d = 0, v = ked_extend(P, L, 0, 0, min(L.dq, L.dr));
   R.add(KCG_EQ, (uint32_t)v);
   for (uint32_t t = 0; t < 31u; ++t, path >>= 2) {
@@ -68,7 +71,14 @@ __device__ __forceinline__ bool kcg_replay(const KedArgs& P, const KedLink& L, u
     v = w;
   }
   R.flush();
-  return (path & 3u) == 0 && v == L.dq && d == L.dr - L.dq;
+  v_end = v; d_end = d;
+  return (path & 3u) == 0;
+}
+// the replay of a link's path -> false if it does not end in (|A|, |B|): nothing it says is used then
+template <bool EMIT>
+__device__ __forceinline__ bool kcg_replay(const KedArgs& P, const KedLink& L, uint64_t path, KcgRuns<EMIT>& R) {
+  int v, d;
+  return kcg_walk<EMIT>(P, L, path, R, v, d) && v == L.dq && d == L.dr - L.dq;
 }
 
 __global__ __launch_bounds__(KED_THREADS) void k_cigar_classify(KedArgs P, const int32_t* __restrict__ link, uint32_t* __restrict__ runs, uint32_t* __restrict__ wl,

@@ -30,7 +30,12 @@ struct KedArgs {
 };
 // a link that passed the range checks: A = qtext[a0, a0 + dq); B forward = rtext[b0, b0 + dr), B reverse = the complement of
 // rtext[b0 - dr, b0) read downwards from b0 - 1
-struct KedLink { uint32_t a0, b0, rev; int dq, dr, chain; };
+struct KedLink {
+  uint32_t a0, b0, rev; int dq, dr, chain;
+  __device__ __forceinline__ uint32_t a_down() const { return 0u; }      // (how ked_extend reads the two strings)
+  __device__ __forceinline__ uint32_t b_down() const { return rev; }
+  __device__ __forceinline__ uint32_t comp() const { return rev; }
+};
 
 #define KED_B(x) (0x0101010101010101ull * (uint64_t)(x))
 // bit 7 of every byte of v that is not zero (exact: no carry leaves a byte)
@@ -57,12 +62,17 @@ __device__ __forceinline__ uint64_t ked_load_down(const uint8_t* __restrict__ te
   for (uint32_t t = 0; t < end; ++t) w |= (uint64_t)text[end - 1u - t] << (8u * t);
   return w;
 }
-// from offset i in A on diagonal d: the offset after the run of matching bases, at most hi (= min(dq, dr - d): inside both strings)
-__device__ __forceinline__ int ked_extend(const KedArgs& P, const KedLink& L, int i, int d, int hi) {
+// from offset i in A on diagonal d: the offset after the run of matching bases, at most hi (= min(|A|, |B| - d): inside both strings).
+// STR says how the two strings lie in the texts: a string read upwards from x has its base t at text[x + t], one read downwards from x at
+// text[x - 1 - t]; comp(): B's bases are complemented.  A link (KedLink) reads A upwards and B upwards, or downwards and complemented on
+// the reverse strand; the ends of a chain (KenEnd, kh_kernels_ends.h) run away from the seed in all four ways.
+template <typename STR>
+__device__ __forceinline__ int ked_extend(const KedArgs& P, const STR& L, int i, int d, int hi) {
   while (i < hi) {
-    const uint64_t a = ked_codes(ked_load_up(P.qtext, P.nq, L.a0 + (uint32_t)i));
+    const uint64_t a = ked_codes(L.a_down() ? ked_load_down(P.qtext, L.a0 - (uint32_t)i) : ked_load_up(P.qtext, P.nq, L.a0 + (uint32_t)i));
     const uint32_t j = (uint32_t)(i + d);
-    const uint64_t b = L.rev ? ked_codes(ked_load_down(P.rtext, L.b0 - j)) ^ KED_B(0x02) : ked_codes(ked_load_up(P.rtext, P.nr, L.b0 + j));
+    const uint64_t b = L.b_down() ? ked_codes(ked_load_down(P.rtext, L.b0 - j)) ^ (L.comp() ? KED_B(0x02) : 0ull)
+                                  : ked_codes(ked_load_up(P.rtext, P.nr, L.b0 + j)) ^ (L.comp() ? KED_B(0x02) : 0ull);
     const uint64_t bad = ked_nonzero((a ^ b) | (a & KED_B(0x80)));     // a valid and equal to b: b is valid too
     int run = bad ? (int)((uint32_t)__builtin_ctzll(bad) >> 3) : 8;
     run = min(run, hi - i);

@@ -17,6 +17,7 @@
 //   chain   : kh_chain_anchors, collinear chains per segment from flat anchors: a wavefront per segment, the last 64 anchors in registers (kh_kernels_chain.h).
 //   edits   : kh_chain_edits, edit distance of every link of every kept chain: a lane per anchor, then a wavefront per unsettled link (kh_kernels_edits.h).
 //   cigars  : kh_chain_cigars, the alignment operations of every link as run-length rows of a CSR: the same wavefront pass with a traceback (kh_kernels_cigar.h).
+//   ends    : kh_chain_ends, both ends of every kept chain extended to the ends of its read or to a soft clip: a wavefront per end, target free, stop by score (kh_kernels_ends.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
 #include "kh_kernels_values.h"
@@ -26,6 +27,7 @@
 #include "kh_kernels_chain.h"
 #include "kh_kernels_edits.h"
 #include "kh_kernels_cigar.h"
+#include "kh_kernels_ends.h"
 #include "kh_part_sizing.h"
 #include "kh_scratch.h"
 #include "../../include/kmerhash_amd.h"
@@ -4224,6 +4226,58 @@ kh_status kh_chain_cigars(const void* qtext, uint64_t nq, const void* rtext, uin
   if (!s.layout([&](Scratch& c) { dops = c.out(out_ops, total, where); })) return s.finish();
   hipLaunchKernelGGL(k_cigar_emit, dim3(grid_for(m, KED_THREADS, ncu * 8)), dim3(KED_THREADS), 0, stream, P, dlink, (const uint64_t*)doff, (const uint64_t*)paths,
                      (uint64_t)total, dops);
+  s.launched();
+  s.copy_back(dops, total);
+  return s.finish_queued();
+}
+// ---- the ends of every kept chain (kernels: kh_kernels_ends.h).  No handle; one pooled block holds the run counts and the path words
+//      (and the staged arrays of a host call), a second one the staged rows of a host call.  Everything is queued on the caller's
+//      stream; the one host wait is the one that learns *n_ops.
+kh_status kh_chain_ends(const void* qtext, uint64_t nq, const void* rtext, uint64_t nr, uint32_t ref_base, const uint32_t* qpos, const uint32_t* rpos,
+                        const uint8_t* rev, uint64_t m, const uint32_t* c_first, const uint32_t* c_last, const uint32_t* q_lo, const uint32_t* q_hi,
+                        uint64_t n_chains, uint32_t k, uint32_t max_edits, uint32_t clip_cost, kh_mem where, uint32_t* e_q, uint32_t* e_r, uint32_t* e_edits,
+                        uint32_t* e_clip, uint64_t* out_offsets, uint32_t* out_ops, uint64_t cap_ops, uint64_t* n_ops, int device, void* stream_) {
+  const uint64_t lim = uint64_t(1) << 31;
+  if (k < 1 || k > 64 || max_edits > 31 || clip_cost < 1 || clip_cost > 255) return KH_ERR_INVALID;
+  if (m > (uint64_t(1) << 24) || n_chains > (uint64_t(1) << 23) || nq >= lim || nr > lim || ref_base + nr > lim) return KH_ERR_INVALID;
+  if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !out_offsets || !n_ops) return KH_ERR_INVALID;
+  if (n_chains && (!c_first || !c_last || !q_lo || !q_hi || !e_q || !e_r || !e_edits || !e_clip)) return KH_ERR_INVALID;
+  if (n_chains && m && (!qpos || !rpos || !rev || (nq && !qtext) || (nr && !rtext))) return KH_ERR_INVALID;
+  *n_ops = 0;
+  if (n_chains == 0 && where == KH_MEM_HOST) { out_offsets[0] = 0; return KH_OK; }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK0(hipSetDevice(device));
+  if (n_chains == 0) { HIPCHK0(hipMemsetAsync(out_offsets, 0, sizeof(uint64_t), stream)); return KH_OK; }
+  const uint64_t rows = 2 * n_chains, nst = (rows + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
+  Scratch s(device, stream);
+  uint32_t *runs = nullptr, *dq = nullptr, *dr = nullptr, *de = nullptr, *dc = nullptr, *dops = nullptr;
+  uint64_t *paths = nullptr, *doff = nullptr; unsigned long long* ssums = nullptr;
+  KenArgs P{};
+  if (!s.layout([&](Scratch& c) {
+        runs = c.take<uint32_t>(rows); paths = c.take<uint64_t>(rows); ssums = c.take<unsigned long long>(nst + 1);
+        P.T.qtext = c.in(static_cast<const uint8_t*>(qtext), m ? nq : 0, where); P.T.rtext = c.in(static_cast<const uint8_t*>(rtext), m ? nr : 0, where);
+        P.T.qpos = c.in(qpos, m, where); P.T.rpos = c.in(rpos, m, where); P.T.rev = c.in(rev, m, where);
+        P.c_first = c.in(c_first, n_chains, where); P.c_last = c.in(c_last, n_chains, where);
+        P.q_lo = c.in(q_lo, n_chains, where); P.q_hi = c.in(q_hi, n_chains, where);
+        dq = c.out(e_q, rows, where); dr = c.out(e_r, rows, where); de = c.out(e_edits, rows, where); dc = c.out(e_clip, rows, where);
+        doff = c.out(out_offsets, rows + 1, where);
+      })) return s.finish();
+  P.T.nq = (uint32_t)nq; P.T.nr = (uint32_t)nr; P.T.ref_base = ref_base; P.T.m = (uint32_t)m; P.T.n_chains = (uint32_t)n_chains; P.T.k = k; P.T.max_edits = max_edits;
+  P.clip_cost = clip_cost;
+  const uint32_t ncu = (uint32_t)cu_count(device);
+  hipLaunchKernelGGL(k_ends_wfa, dim3(grid_for(rows, KED_WAVES, ncu * 8)), dim3(KED_THREADS), 0, stream, P, dq, dr, de, dc, runs, paths);
+  scan_counts(stream, (const uint32_t*)runs, rows, ssums, doff);
+  s.launched();
+  unsigned long long total = 0;
+  s.read(&total, (const unsigned long long*)(ssums + nst));
+  s.copy_back(doff, rows + 1); s.copy_back(dq, rows); s.copy_back(dr, rows); s.copy_back(de, rows); s.copy_back(dc, rows);
+  if (!s.sync()) return s.finish();      // the one host wait of a device call: *n_ops
+  *n_ops = total;
+  if (!out_ops || total == 0) return s.finish();
+  if (total > cap_ops) { s.finish(); return KH_ERR_INVALID; }
+  if (!s.layout([&](Scratch& c) { dops = c.out(out_ops, total, where); })) return s.finish();
+  hipLaunchKernelGGL(k_ends_emit, dim3(grid_for(rows, KED_THREADS, ncu * 8)), dim3(KED_THREADS), 0, stream, P, (const uint64_t*)doff, (const uint64_t*)paths, (uint64_t)total,
+                     dops);
   s.launched();
   s.copy_back(dops, total);
   return s.finish_queued();

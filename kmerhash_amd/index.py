@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from ._call import HOST, _Buf, _Handle, alloc, check_same, torch
-from .kmers import anchors_from_csr, chain_anchors, chain_cigars, chain_edits, stamp_strand
+from .kmers import anchors_from_csr, chain_anchors, chain_cigars, chain_edits, chain_ends, stamp_strand
 from .seqs import is_syncmer, is_syncmer128, kmers_from_sequence, minimizers_from_sequence, syncmers128_from_sequence, syncmers_from_sequence
 from .table import _hash_id
 
@@ -252,7 +252,7 @@ class KmerPositionIndex(_Handle):
         return self._chains(seq, read_starts, params)[0]
 
     def _chains(self, seq, read_starts, params):
-        """the body of chains(): -> (ChainTable, pred per anchor as chain_anchors wrote it)"""
+        """the body of chains(): -> (ChainTable, the Chains chain_anchors returned: pred per anchor, first and last anchor per chain)"""
         q, r, v = self.anchors(seq)
         dev = torch is not None and isinstance(q, torch.Tensor)
         if read_starts is None:
@@ -277,7 +277,7 @@ class KmerPositionIndex(_Handle):
             qf, ql, rf, rl = q[first], q[last], r[first], r[last]
             sg = np.zeros(len(first), dtype=np.uint32) if seg is None else (np.searchsorted(seg, first.astype(np.uint64), side="right") - 1).astype(np.uint32)
             rows = (sg, v[first], qf, ql + np.uint32(self.k), np.minimum(rf, rl), np.maximum(rf, rl) + np.uint32(self.k), c.count, c.cscore)
-        return ChainTable(*rows, (q, r, v), c.chain), c.pred
+        return ChainTable(*rows, (q, r, v), c.chain), c
 
     def chain_edits(self, seq, ref_text, read_starts=None, ref_base=0, max_edits=31, **params):
         """chains(seq, read_starts, **params), then every kept chain verified against the texts on the device: kmers.chain_edits over the
@@ -289,10 +289,10 @@ class KmerPositionIndex(_Handle):
         if not self.stranded:
             raise ValueError("chain_edits() needs an index made with stranded=True: without the strand bit a hit has no orientation")
         seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to two calls)
-        table, pred = self._chains(seq, read_starts, params)
+        table, c = self._chains(seq, read_starts, params)
         q, r, v = table.anchors
         n_chains = int(table.count.numel() if torch is not None and isinstance(table.count, torch.Tensor) else len(table.count))
-        return table, chain_edits(seq, ref_text, q, r, v, pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
+        return table, chain_edits(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
 
     def chain_cigars(self, seq, ref_text, read_starts=None, ref_base=0, max_edits=31, **params):
         """chain_edits(seq, ref_text, ...), then the alignment behind every distance: kmers.chain_cigars over the same anchors and texts
@@ -302,11 +302,46 @@ class KmerPositionIndex(_Handle):
         if not self.stranded:
             raise ValueError("chain_cigars() needs an index made with stranded=True: without the strand bit a hit has no orientation")
         seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to three calls)
-        table, pred = self._chains(seq, read_starts, params)
+        table, c = self._chains(seq, read_starts, params)
         q, r, v = table.anchors
         n_chains = int(table.count.numel() if torch is not None and isinstance(table.count, torch.Tensor) else len(table.count))
-        edits = chain_edits(seq, ref_text, q, r, v, pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
-        return table, edits, chain_cigars(seq, ref_text, q, r, v, pred, table.chain, n_chains, self.k, edits.link, ref_base, self.device)
+        edits = chain_edits(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
+        return table, edits, chain_cigars(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, edits.link, ref_base, self.device)
+
+    def chain_ends(self, seq, ref_text, read_starts=None, read_ends=None, ref_base=0, max_edits=31, clip_cost=4, **params):
+        """chain_cigars(seq, ref_text, ...), then both ends of every chain extended to the ends of its read or to a soft clip:
+        kmers.chain_ends over the same anchors and texts, with the chains' first and last anchors and the byte interval of each chain's
+        read -- [read_starts[seg], read_ends[seg]); read_ends defaults to the next read's start and len(seq) for the last read, so give
+        it where the reads are separated by bytes that belong to none of them.
+        -> (ChainTable, ChainEdits, ChainCigars, ChainEnds(q, r, edits, clip, offsets, ops)): rows 2c and 2c + 1 of the ends are the head
+        and tail of row c of the table.  kmers.read_cigar(cigars, ends, table, row, k) is the CIGAR of a whole read,
+        kmers.extended_intervals(table, ends) the intervals it maps."""
+        if not self.stranded:
+            raise ValueError("chain_ends() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to four calls)
+        table, c = self._chains(seq, read_starts, params)
+        q, r, v = table.anchors
+        dev = torch is not None and isinstance(q, torch.Tensor)
+        n_chains = int(table.count.numel() if dev else len(table.count))
+        n_text = int(seq.numel() if dev else seq.size)
+        rs = np.zeros(1, dtype=np.int64) if read_starts is None else np.asarray(
+            read_starts.cpu() if torch is not None and isinstance(read_starts, torch.Tensor) else read_starts, dtype=np.int64).ravel()
+        if read_ends is None:
+            re_ = np.concatenate([rs[1:], [n_text]])
+        else:
+            re_ = np.asarray(read_ends.cpu() if torch is not None and isinstance(read_ends, torch.Tensor) else read_ends, dtype=np.int64).ravel()
+            if re_.size != rs.size or (re_ < rs).any() or (re_ > n_text).any():
+                raise ValueError("read_ends must hold one byte offset per read, read_starts[s] <= read_ends[s] <= len(seq)")
+        if dev:
+            sg = table.seg.long()
+            lo, hi = torch.from_numpy(rs).to(q.device)[sg].int(), torch.from_numpy(re_).to(q.device)[sg].int()
+        else:
+            sg = table.seg.astype(np.int64)
+            lo, hi = rs[sg].astype(np.uint32), re_[sg].astype(np.uint32)
+        edits = chain_edits(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
+        cigars = chain_cigars(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, edits.link, ref_base, self.device)
+        ends = chain_ends(seq, ref_text, q, r, v, c.first, c.last, lo, hi, self.k, ref_base, max_edits, clip_cost, self.device)
+        return table, edits, cigars, ends
 
     def _syncmers(self, seq, fastq=False):
         """the closed syncmers of a text under the index's own parameters"""

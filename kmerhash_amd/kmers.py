@@ -246,6 +246,91 @@ def cigar_string(cigars, table, row, k):
     return "".join("%d%s" % (n, CIGAR_OPS[op]) for op, n in out)
 
 
+ChainEnds = collections.namedtuple("ChainEnds", "q r edits clip offsets ops")
+
+
+def chain_ends(qtext, rtext, qpos, rpos, rev, first, last, q_lo, q_hi, k, ref_base=0, max_edits=31, clip_cost=4, device=0):
+    """both ends of every chain, extended from its outermost seeds to the ends of its read or to a soft clip (kh_chain_ends in
+    include/kmerhash_amd.h, which holds the definition).  first / last: the anchor indices of each chain's first and last anchor
+    (Chains.first / .last of chain_anchors); q_lo / q_hi: the byte interval [q_lo, q_hi) of the chain's read in qtext.  Row 2c is the head
+    of chain c (the read's bases before its first seed), row 2c + 1 its tail (those behind its last seed); an end stops at the point of
+    greatest (aligned read bases - clip_cost * edits) among at most max_edits (0..31) edits, clip_cost 1..255.
+    -> ChainEnds(q, r, edits, clip, offsets, ops): per row the read bases aligned, the reference bases they face, the edits, and the read
+    bases left over (the soft clip); then a CSR of runs (len << 4) | op as chain_cigars writes them, a head's row in read order.  Count,
+    then emit: two calls, one allocation of the exact size.  numpy in, numpy out (uint32 x 4, uint64, uint32); CUDA tensors in, tensors out
+    on the current stream (int32 holding the uint32 bits, int64 offsets); the call waits for the stream once per pass, to learn the number
+    of runs.  At most 2^24 anchors and 2^23 chains per call.  read_cigar() and extended_intervals() put the ends onto a ChainTable."""
+    if not 1 <= int(k) <= 64:
+        raise ValueError("k must be 1..64, got %r" % (k,))
+    if not 0 <= int(max_edits) <= 31:
+        raise ValueError("max_edits must be 0..31 (one diagonal per lane of a wavefront), got %r" % (max_edits,))
+    if not 1 <= int(clip_cost) <= 255:
+        raise ValueError("clip_cost must be 1..255, got %r" % (clip_cost,))
+    tq, tr = _Buf.text(qtext), _Buf.text(rtext)
+    qb, rb, vb = _Buf(qpos, np.uint32), _Buf(rpos, np.uint32), _Buf(rev, np.uint8)
+    fb, lb, ob, hb = _Buf(first, np.uint32), _Buf(last, np.uint32), _Buf(q_lo, np.uint32), _Buf(q_hi, np.uint32)
+    check_same("the texts, qpos, rpos, rev, first, last, q_lo and q_hi must live in the same memory", tq, tr, qb, rb, vb, fb, lb, ob, hb, length=False)
+    m, nc = qb.n, fb.n
+    check_same("qpos, rpos and rev must have one entry per anchor, got %d, %d and %d" % (m, rb.n, vb.n), qb, rb, vb)
+    check_same("first, last, q_lo and q_hi must have one entry per chain, got %d, %d, %d and %d" % (nc, lb.n, ob.n, hb.n), fb, lb, ob, hb)
+    if m > 2 ** 24:
+        raise ValueError("at most 2^24 anchors per call (batch over reads), got %d" % m)
+    if nc > 2 ** 23:
+        raise ValueError("at most 2^23 chains per call (batch over reads), got %d" % nc)
+    if tq.n >= 2 ** 31:
+        raise ValueError("the query text must be shorter than 2^31 bytes, got %d" % tq.n)
+    if not 0 <= int(ref_base) or int(ref_base) + tr.n > 2 ** 31:
+        raise ValueError("ref_base + len(rtext) must stay within 2^31 (a position has 31 bits), got %r + %d" % (ref_base, tr.n))
+    nums = [alloc(fb, 2 * nc, np.uint32, empty=True) for _ in range(4)]
+    offs, optr = alloc(fb, 2 * nc + 1, np.uint64, zero=True)
+    if nc == 0:      # nothing to queue: the zeroed offset is the answer
+        return ChainEnds(*(a for a, _ in nums), offs, alloc(fb, 0, np.uint32)[0])
+    fn, n, stream = K.lib().kh_chain_ends, C.c_uint64(), stream_of(fb, device)
+    args = (tq.ptr_or_null, tq.n, tr.ptr_or_null, tr.n, int(ref_base), qb.ptr_or_null, rb.ptr_or_null, vb.ptr_or_null, m, fb.ptr, lb.ptr, ob.ptr, hb.ptr, nc,
+            int(k), int(max_edits), int(clip_cost), fb.where, *(p for _, p in nums), optr)
+    check(fn(*args, None, 0, C.byref(n), device, stream), "kh_chain_ends")
+    ops, pptr = alloc(fb, n.value, np.uint32)
+    if n.value:
+        check(fn(*args, pptr, n.value, C.byref(n), device, stream), "kh_chain_ends")
+    return ChainEnds(*(a for a, _ in nums), offs, ops)
+
+
+def read_cigar(cigars, ends, table, row, k):
+    """the CIGAR of the whole read of chain `row` as text (a host helper like cigar_string): 'S' for the bases the head clips, the head's
+    row, what cigar_string(cigars, table, row, k) gives, the tail's row, 'S' for the bases the tail clips, equal neighbours merged -- in
+    read order, for a reverse-strand chain too; with extended_intervals() it is the alignment record of the read.  None where
+    cigar_string is None."""
+    mid = cigar_string(cigars, table, row, k)
+    if mid is None:
+        return None
+    import re
+    offs, ops, clip = _host(ends.offsets, np.int64), _host(ends.ops, np.uint32), _host(ends.clip, np.uint32)
+    h, t = 2 * int(row), 2 * int(row) + 1
+    runs = [("S", int(clip[h]))] + [(CIGAR_OPS[int(v) & 15], int(v) >> 4) for v in ops[offs[h]:offs[h + 1]]]
+    runs += [(o, int(n)) for n, o in re.findall(r"(\d+)([ID=X])", mid)]
+    runs += [(CIGAR_OPS[int(v) & 15], int(v) >> 4) for v in ops[offs[t]:offs[t + 1]]] + [("S", int(clip[t]))]
+    out = []
+    for op, n in runs:
+        if n == 0:
+            continue
+        if out and out[-1][0] == op:
+            out[-1][1] += n
+        else:
+            out.append([op, n])
+    return "".join("%d%s" % (n, op) for op, n in out)
+
+
+def extended_intervals(table, ends):
+    """the intervals of a ChainTable with the ends added (a host helper) -> (q_start, q_end, r_start, r_end), int64 arrays with one entry
+    per row: the head moves q_start down and the tail q_end up by the read bases they align; on the forward strand the head moves r_start
+    down and the tail r_end up by the reference bases they face, on the reverse strand the head extends r_end and the tail r_start."""
+    q0, q1, r0, r1 = (_host(x, np.uint32).astype(np.int64) for x in (table.q_start, table.q_end, table.r_start, table.r_end))
+    rev = _host(table.rev, np.uint8).astype(bool)
+    eq, er = _host(ends.q, np.uint32).astype(np.int64), _host(ends.r, np.uint32).astype(np.int64)
+    hq, tq, hr, tr = eq[0::2], eq[1::2], er[0::2], er[1::2]
+    return q0 - hq, q1 + tq, r0 - np.where(rev, tr, hr), r1 + np.where(rev, hr, tr)
+
+
 class KmerCounter:
     """counting index: k-mer -> number of occurrences (Reducer = std::plus, value 1 per occurrence)"""
 
