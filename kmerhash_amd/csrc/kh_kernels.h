@@ -632,6 +632,10 @@ struct KhPartParams {
   //  to a bucket.  Hashed keys in any order fill the eight alike.  hash = identity with sorted or sequential keys does not -- the tiles of
   //  workgroups w & 7 == x then hold keys of half of the digits only -- and such a batch is repeated with exact offsets, as after any overflow.)
   uint64_t sub_slot; uint32_t seg_shift; int xcd_buckets;
+  // optimistic attempt of a bulk insert (queued behind the duplicate sample without a host read): the sample's duplicate count, final
+  // before this kernel starts.  Non-zero: every workgroup returns at once -- no reservation, no record, no flag -- and the host,
+  // which reads the word with the build's control words, repeats the batch the way that count asks for.  Null: no predicate.
+  const uint32_t* skip;
   // (k_part_scatter<HASH, true>: rec_in / orec hold KhRec12 records instead -- histogram-free mode only)
 };
 
@@ -735,6 +739,7 @@ __global__ KH_PART_LB(RK) void k_part_scatter(KhPartParams P) {
   const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const uint32_t ntiles = P.tiles ? *P.ntiles_dev : P.ntiles;
   if (blockIdx.x >= ntiles) return;
+  if (P.skip && *P.skip) return;                    // (written by a kernel that has completed on this stream: a plain load)
   uint32_t tile = blockIdx.x;
   const uint32_t xcd = blockIdx.x & 7u;             // (of the workgroup, not of the swizzled tile)
   if (P.xcd_buckets) {                              // (the grid is nb1 * 8 * tps, nb1 a multiple of 8) XCD x: buckets x, x + 8, ..., each 8 * tps tiles
@@ -975,9 +980,27 @@ __global__ __launch_bounds__(512) void k_part_direct(const char* __restrict__ kb
 // k-mers none; a few keys with 10^4 copies among 10^8 slip through -- the slot overflow flag catches those.
 #define KH_SAMPLE_N 65536u
 #define KH_SAMPLE_SET (1u << 18)
+// both levels of a histogram-free partition: level-1 cursors, level-2 cursors + slot starts, the overflow flag (cursor[j] = j * slot)
+// (sub1 = 8: eight level-1 cursors per bucket, cursor b * 8 + x at the start of bucket b's x-th sub-slot of slot1 / 8 records; else sub1 = 1)
+struct KhCursorInit {
+  unsigned long long* cur1; uint64_t n1, slot1; uint32_t sub1;
+  unsigned long long* cur2; uint64_t* starts; uint64_t n2, slot2;      // cur2 == null: nothing to initialise
+  uint32_t* ovf;
+};
+__device__ __forceinline__ void kh_init_cursors2(const KhCursorInit& I, uint64_t i) {
+  if (i < I.n1 * I.sub1) I.cur1[i] = (i / I.sub1) * I.slot1 + (i % I.sub1) * (I.slot1 / I.sub1);
+  if (i < I.n2) I.cur2[i] = i * I.slot2;
+  if (i <= I.n2) I.starts[i] = i * I.slot2;
+  if (i == 0) *I.ovf = 0u;
+}
+// (I: the cursors of the partition queued behind the sample -- written here, by a grid-stride loop, instead of by a launch of their own)
 __global__ void k_sample_dups(const char* __restrict__ kbase, uint32_t kstride, uint64_t n, unsigned long long* __restrict__ set /* zeroed */,
-                              uint32_t* __restrict__ dups) {
+                              uint32_t* __restrict__ dups, KhCursorInit I) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (I.cur2) {
+    const uint64_t words = I.n1 * I.sub1 > I.n2 + 1 ? I.n1 * I.sub1 : I.n2 + 1;
+    for (uint64_t w = i; w < words; w += (uint64_t)gridDim.x * blockDim.x) kh_init_cursors2(I, w);
+  }
   if (i >= KH_SAMPLE_N) return;
   const uint64_t pos = (uint64_t)i * (n / KH_SAMPLE_N);
   const unsigned long long key = *reinterpret_cast<const uint64_t*>(kbase + pos * kstride) ^ 0x8000000000000001ull;     // (0 marks an empty entry)
@@ -992,16 +1015,8 @@ __global__ void k_sample_dups(const char* __restrict__ kbase, uint32_t kstride, 
 }
 
 // histogram-free partition: cursor[j] = j * slot (and, if asked, the same values as partition start offsets)
-// both levels of a histogram-free partition in one launch: level-1 cursors, level-2 cursors + slot starts, the overflow flag
-// (sub1 = 8: eight level-1 cursors per bucket, cursor b * 8 + x at the start of bucket b's x-th sub-slot of slot1 / 8 records; else sub1 = 1)
-__global__ void k_init_cursors2(unsigned long long* __restrict__ cur1, uint64_t n1, uint64_t slot1, uint32_t sub1, unsigned long long* __restrict__ cur2,
-                                uint64_t* __restrict__ starts, uint64_t n2, uint64_t slot2, uint32_t* __restrict__ ovf) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n1 * sub1) cur1[i] = (i / sub1) * slot1 + (i % sub1) * (slot1 / sub1);
-  if (i < n2) cur2[i] = i * slot2;
-  if (i <= n2) starts[i] = i * slot2;
-  if (i == 0) *ovf = 0u;
-}
+// (the cursors of a partition that no sample precedes: a launch of their own, one thread per word)
+__global__ void k_init_cursors2(KhCursorInit I) { kh_init_cursors2(I, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ void k_init_cursors(unsigned long long* __restrict__ cursor, uint64_t* __restrict__ starts, uint64_t n, uint64_t slot) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) cursor[i] = i * slot;
@@ -1806,8 +1821,10 @@ __global__ void k_chunk_carry(const long long* __restrict__ sumA, const long lon
 // its own run-over -- so the slices of all workgroups tile the (circular) table exactly once and every info byte,
 // occupied or empty, is written by exactly one workgroup with coalesced stores.
 #define KH_SPILL 256     // run-over slots staged in LDS; anything further out (only LP clusters) is stored directly
-template <int KIND, int HASH>
-__global__ __launch_bounds__(KH_CHUNK_THREADS) void k_chunk_place(KhRebuildParams P) {
+// (chunk c with the carry-in xcarry, an absolute position.  TAIL: chunk 0 of a one-launch build, placed by k_fused_tail -- its new
+//  elements are the n0 parked ones, P.ck / P.cv [0, n0), instead of partition lists)
+template <int KIND, int HASH, bool TAIL>
+__device__ __forceinline__ void kh_chunk_place(const KhRebuildParams& P, const uint32_t c, const long long xcarry, const uint32_t n0) {
   __shared__ uint64_t skeys[KH_L + KH_SPILL];
   __shared__ uint32_t svals[KH_L + KH_SPILL];
   __shared__ uint32_t sinfo_w[(KH_L + KH_SPILL) / 4];
@@ -1817,7 +1834,7 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS) void k_chunk_place(KhRebuildParam
   __shared__ long long s_pend;
   __shared__ KhMP s_wtot[KH_CHUNK_THREADS / 64];
   uint8_t* sinfo = reinterpret_cast<uint8_t*>(sinfo_w);
-  const uint32_t tid = threadIdx.x, c = blockIdx.x;
+  const uint32_t tid = threadIdx.x;
   const uint32_t Ln = P.New.cap > KH_L ? KH_L : (uint32_t)P.New.cap;
   const uint64_t Sc = (uint64_t)c * Ln, mask_n = P.New.cap - 1;
   const uint32_t empty4 = KIND == KHK_RH ? 0u : 0x40404040u;
@@ -1833,7 +1850,7 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS) void k_chunk_place(KhRebuildParam
     fill[tid * KH_HOMES_PER_THREAD + j] = 0;
   }
   KhMP excl = kh_block_scan_mp(v, s_wtot, nullptr);
-  const long long xr = P.xcarry[c] - (long long)Sc;          // carry-in relative to the chunk start (<= 0: none)
+  const long long xr = xcarry - (long long)Sc;               // carry-in relative to the chunk start (<= 0: none)
   long long p = excl.A > xr + excl.n ? excl.A : xr + excl.n;
 #pragma unroll
   for (uint32_t j = 0; j < KH_HOMES_PER_THREAD; ++j) {
@@ -1860,7 +1877,9 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS) void k_chunk_place(KhRebuildParam
     else kh_slot_st(P.New.s + ((Sc + prel) & mask_n), key, val, ib);
   };
   kh_for_each_old<KIND, HASH>(P, c, &s_emin, place);
-  kh_for_each_new<HASH>(P, c, place);
+  if (TAIL) {
+    for (uint32_t i = tid; i < n0; i += KH_CHUNK_THREADS) { const uint64_t key = P.ck[i]; place(key, P.cv[i], kh_hash64<HASH>(key, P.seed) & mask_n); }
+  } else kh_for_each_new<HASH>(P, c, place);
   __syncthreads();
   // stream the slice out
   long long pend = s_pend;
@@ -1872,6 +1891,8 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS) void k_chunk_place(KhRebuildParam
     kh_slot_st(P.New.s + ((Sc + s0) & mask_n), skeys[s0], svals[s0], sinfo[s0]);
   }
 }
+template <int KIND, int HASH>
+__global__ __launch_bounds__(KH_CHUNK_THREADS) void k_chunk_place(KhRebuildParams P) { kh_chunk_place<KIND, HASH, false>(P, blockIdx.x, P.xcarry[blockIdx.x], 0u); }
 
 // ---------------------------------------------------------------------------------------------
 // Fused bulk build (empty table, one partition == one chunk of the predicted capacity): de-dup, home count, carry
@@ -1909,7 +1930,14 @@ struct KhFusedParams {
   int nodup;                                             // SRC == 0: a sample of the batch found no duplicate -- skip the LDS hash-set fold and
                                                          //   CHECK instead that no home bucket received two equal keys (any duplicate: general path)
   KhRebuildParams R;                                     // SRC == 1 only: source table, erase mask, new distinct elements
+  // SRC == 0: the duplicate count of the sample this attempt was queued behind (see KhPartParams::skip): non-zero -> every workgroup returns at once
+  const uint32_t* skip;
+  // k_build_lean: KH_FUSED_NCNT zeroed words, one per 128 bytes; chunk c ADDS its count to word c % KH_FUSED_NCNT (an atomic nobody waits
+  // for, 1024 per word and build) and k_fused_tail sums them: no reduction launch over the granules
+  unsigned long long* cnt;
 };
+#define KH_FUSED_NCNT 64u
+#define KH_FUSED_CNT_STRIDE 16u  // in words
 
 // SRC == 1 (Robin Hood): the chunk's elements come from the CURRENT table (same capacity or half of the new one) plus the
 // batch's new distinct keys, instead of from partition records -- the one-launch form of k_chunk_count + k_chunk_carry +
@@ -2043,6 +2071,7 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS) void k_build_fused(KhFusedParams 
   const uint64_t cap = P.New.cap, mask_n = cap - 1;
   const uint32_t nch = (uint32_t)(cap >> KH_LB);          // host guarantees cap >= 2 * KH_L
   KH_STAMP(0);
+  if (SRC == 0 && P.skip && *P.skip) return;              // (the sample kernel has completed on this stream: a plain load)
   if (tid == 0) {
     s_chunk = blockIdx.x;
     s_max = 0;
@@ -2486,6 +2515,7 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS, 8) void k_build_lean(KhFusedParam
   const uint64_t Sc = (uint64_t)c * KH_L;
   const unsigned long long VALID = 1ull << 63;
   KH_STAMP_L(0);
+  if (P.skip && *P.skip) return;                  // (the sample kernel has completed on this stream: a plain load)
   if (tid == 0) s_abort = (uint32_t)__hip_atomic_load(&P.est[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   // (one histogram-free or exact source of 12-byte records: addressed directly, no source table)
   const uint32_t q = P.PB ? (__brev(c) >> (32 - P.PB)) : 0u;
@@ -2567,7 +2597,7 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS, 8) void k_build_lean(KhFusedParam
     if (tid == 0) {
       if (!early) atomicOr(&P.flags[KH_FLAG_FUSE_INVALID], 1u);
       __hip_atomic_store(&P.pub[0], VALID | ((unsigned long long)spill0 << 32) | n_c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      P.maxidx[0] = 0;
+      (void)__hip_atomic_fetch_add(&P.cnt[0], (unsigned long long)n_c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 #pragma unroll
     for (uint32_t j = 0; j < KH_HOMES_PER_THREAD; ++j) P.homecnt0[tid * KH_HOMES_PER_THREAD + j] = (uint16_t)cb[j];
@@ -2577,6 +2607,8 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS, 8) void k_build_lean(KhFusedParam
   // ---- publish (as k_build_fused); the look-back's load is issued here and collected after the duplicate check
   unsigned long long w0 = 0;
   if (tid == 0) {
+    // (the chunk's count towards the build's total: whatever happens to this chunk later raises a flag and does not change it)
+    (void)__hip_atomic_fetch_add(&P.cnt[(c & (KH_FUSED_NCNT - 1u)) * KH_FUSED_CNT_STRIDE], (unsigned long long)n_c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (c < 64) {     // the first 64 chunks vote on the duplicate ratio (all records distinct here: the vote can only confirm)
       const unsigned long long mine = ((unsigned long long)n_c << 32) | m;
       const unsigned long long tot = atomicAdd(&P.est[0], mine) + mine;
@@ -2591,7 +2623,7 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS, 8) void k_build_lean(KhFusedParam
     }
     if (early) __hip_atomic_store(&P.pub[c], VALID | ((unsigned long long)spill0 << 32) | n_c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     w0 = __hip_atomic_load(&P.pub[c - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    P.maxidx[c] = 0;
+    // (no maxidx: 12-byte records carry no stream position, the word the host would read stays zero)
   }
   // ---- group starts without the carry-in, record counts in front of every bucket
   {
@@ -3319,13 +3351,30 @@ __global__ __launch_bounds__(KH_CHUNK_THREADS, 6) void k_insert_stream(KhFusedPa
 // carry-in of chunk 0 = run-over of the last chunk (circular table)
 // (also what the tail placement of chunk 0 needs besides: its list offsets {0, 0} and its list length = the count field of pub[0] --
 //  one launch instead of a kernel, a fill and a copy)
-__global__ void k_fused_tail_carry(const unsigned long long* __restrict__ pub, uint32_t nch, long long* __restrict__ xcarry0,
-                                   uint64_t* __restrict__ noff0 = nullptr, uint32_t* __restrict__ ncnt0 = nullptr) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    xcarry0[0] = (long long)((pub[nch - 1] >> 32) & 0x7FFFFFFFull);
-    if (noff0) { noff0[0] = 0; noff0[1] = 0; }
-    if (ncnt0) ncnt0[0] = (uint32_t)pub[0];
+// The tail launch of a one-launch build, ONE workgroup behind the build kernel on its stream (every granule is final: plain loads):
+//  - status[0..1] = the sample's duplicate count (KhFusedParams::skip) and the partition's overflow word, so that they reach the host with
+//    the control words they lie next to, in one copy; a non-zero duplicate count ends the launch there, like the kernels before it;
+//  - cnt != null (k_build_lean): totals[0] = sum of the KH_FUSED_NCNT count words;
+//  - chunk 0 placed with the run-over field of the last chunk's granule as its carry-in and the count field of its own as the length of
+//    its parked list -- both taken from the granules by every lane itself, not passed through memory.
+struct KhTailParams {
+  const unsigned long long* pub; uint32_t nch;
+  const unsigned long long* cnt; unsigned long long* totals;
+  const uint32_t* skip; const uint32_t* ovf; uint32_t* status;
+};
+template <int KIND, int HASH>
+__global__ __launch_bounds__(KH_CHUNK_THREADS) void k_fused_tail(KhRebuildParams P, KhTailParams E) {
+  const uint32_t dups = E.skip ? *E.skip : 0u;
+  if (threadIdx.x == 0) { E.status[0] = dups; E.status[1] = E.ovf ? *E.ovf : 0u; }
+  if (dups) return;
+  if (E.cnt && threadIdx.x < 64) {
+    static_assert(KH_FUSED_NCNT == 64, "one count word per lane of the first wave");
+    unsigned long long sum = E.cnt[threadIdx.x * KH_FUSED_CNT_STRIDE];
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    if (threadIdx.x == 0) E.totals[0] = sum;
   }
+  const long long xcarry = (long long)((E.pub[E.nch - 1] >> 32) & 0x7FFFFFFFull);
+  kh_chunk_place<KIND, HASH, true>(P, 0u, xcarry, (uint32_t)E.pub[0]);
 }
 
 // totals of a fused build: sum of the per-chunk counts (low word of the published granules) and max of maxidx.

@@ -189,6 +189,11 @@ struct kh_table {
   uint32_t* part_overflow = nullptr;      // device flag of the histogram-free partition feeding the operation in flight (or null)
   double batch_vf = 1.0;                  // variance factor E[m^2]/E[m] the duplicate sample gave for the batch in flight (1: no duplicate seen)
   bool batch_nodup = false;               // a sample of the batch in flight found no duplicate key (k_sample_dups)
+  // optimistic attempt in flight (insert_core): queued behind the sample without reading it.  sample_dups: the sample's device word, which
+  // the kernels of the attempt test and launch_fused brings to the host; fused_blk: launch_fused's control block, zeroed by the same fill
+  // as the sample set (fused_blk_bytes long)
+  uint32_t* sample_dups = nullptr;
+  char* fused_blk = nullptr; size_t fused_blk_bytes = 0;
   bool prof = false;
   std::vector<ProfRec> recs;
   std::vector<std::pair<std::string, std::pair<double, uint64_t> > > prof_acc;
@@ -532,52 +537,64 @@ const bool g_disable_fused_rebuild = getenv("KH_DISABLE_FUSED_BUILD") != nullptr
 const long long g_poll_limit = getenv("KH_DEBUG_POLL_LIMIT") ? atoll(getenv("KH_DEBUG_POLL_LIMIT")) : (1ll << 23);     // test hook: look-back time-out
 struct FusedRun { unsigned long long* totals; uint32_t* flags; };
 const bool g_disable_lean = getenv("KH_DISABLE_LEAN_BUILD") != nullptr;      // test hook / A-B: the general one-launch build for 12-byte records too
+// granules, control words (256 bytes), maxidx, the lean build's count words: zeroed by ONE fill
+inline size_t fused_blk_bytes(uint32_t nch) { return (size_t)nch * 12 + 256 + (size_t)KH_FUSED_NCNT * KH_FUSED_CNT_STRIDE * 8; }
 kh_status launch_fused(kh_table* t, int src, KhFusedParams& F, const KhSlots& nw, uint32_t PB_tail, const char* name, FusedRun* out) {
   const uint32_t nch = (uint32_t)(nw.cap >> KH_LB);
-  char* blk; uint32_t* maxidx; uint64_t* ck0; uint32_t* cv0; uint16_t* hc0; long long* xc0; uint64_t* noff0; uint32_t* ncnt0;
-  const size_t sz_pub = (size_t)nch * 8, sz_ctl = sz_pub + 256, sz_all = sz_ctl + (size_t)nch * 4;      // granules, control words, maxidx: ONE fill
-  TAKE(blk, char, sz_all);
+  char* blk; uint32_t* maxidx; uint64_t* ck0; uint32_t* cv0; uint16_t* hc0;
+  const size_t sz_pub = (size_t)nch * 8, sz_ctl = sz_pub + 256, sz_all = fused_blk_bytes(nch);
+  // (an optimistic bulk insert has zeroed the block with its sample set, before the partition: no fill between the second pass and the build)
+  if (t->fused_blk && t->fused_blk_bytes == sz_all) blk = t->fused_blk;
+  else { TAKE(blk, char, sz_all); HIPCHK(hipMemsetAsync(blk, 0, sz_all, t->stream)); }
+  t->fused_blk = nullptr;
   maxidx = reinterpret_cast<uint32_t*>(blk + sz_ctl);
-  TAKE(ck0, uint64_t, KH_DD_M); TAKE(cv0, uint32_t, KH_DD_M); TAKE(hc0, uint16_t, KH_L); TAKE(xc0, long long, 1);
-  TAKE(noff0, uint64_t, 2); TAKE(ncnt0, uint32_t, 1);
-  HIPCHK(hipMemsetAsync(blk, 0, sz_all, t->stream));
+  TAKE(ck0, uint64_t, KH_DD_M); TAKE(cv0, uint32_t, KH_DD_M); TAKE(hc0, uint16_t, KH_L);
   F.New = nw; F.seed = t->seed;
   F.pub = reinterpret_cast<unsigned long long*>(blk);
-  unsigned long long* totals = reinterpret_cast<unsigned long long*>(blk + sz_pub);   // 2 x u64 (k_fused_totals)
+  unsigned long long* totals = reinterpret_cast<unsigned long long*>(blk + sz_pub);   // 2 x u64 (k_fused_totals / k_fused_tail)
   F.maxidx = maxidx; F.ck0 = ck0; F.cv0 = cv0; F.homecnt0 = hc0;
+  F.cnt = reinterpret_cast<unsigned long long*>(blk + sz_ctl + (size_t)nch * 4);
+  F.skip = src == 0 ? t->sample_dups : nullptr;
   F.est = reinterpret_cast<unsigned long long*>(blk + sz_pub + 32);          // 2 x u64
   F.flags = reinterpret_cast<uint32_t*>(blk + sz_pub + 64);                  // KH_NFLAGS x u32
   F.poll_limit = g_poll_limit;
   F.R.New = nw; F.R.seed = t->seed; F.R.flags = F.flags;
+  bool lean = false;
   { Launch L(t, name);
     // (the benchmark case -- a duplicate-free sample, one source of 12-byte records -- has its own kernel with 17 KB less LDS: 4 workgroups per CU)
     // (... as long as a chunk of mean + 5 sigma records fits its smaller staging arrays: a table filled to 0.9 would fail it in a chunk or two
     //  of 65536 and pay for the discarded launch)
     const double mean_c = (double)F.n_total / (double)nch;
     const bool lean_fits = mean_c + 5.0 * std::sqrt(mean_c) < (double)KH_LEAN_M;
-    if (src == 0 && F.nodup && F.src.rec12 == 1 && F.src.n == 1 && lean_fits && !g_disable_lean) { KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_build_lean<KIND, HASH>), dim3(nch), dim3(KH_CHUNK_THREADS), 0, t->stream, F)); }
+    lean = src == 0 && F.nodup && F.src.rec12 == 1 && F.src.n == 1 && lean_fits && !g_disable_lean;
+    if (lean) { KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_build_lean<KIND, HASH>), dim3(nch), dim3(KH_CHUNK_THREADS), 0, t->stream, F)); }
     else if (src == 0) { KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_build_fused<KIND, HASH, 0>), dim3(nch), dim3(KH_CHUNK_THREADS), 0, t->stream, F)); }
     else if (src == 1) { KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_build_fused<KIND, HASH, 1>), dim3(nch), dim3(KH_CHUNK_THREADS), 0, t->stream, F)); }
     else if (src == 3) { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_build_fused<KHK_RH, HASH, 3>), dim3(nch), dim3(KH_CHUNK_THREADS), 0, t->stream, F)); }      // (batch erase: Robin Hood only)
     else if (src == 4) { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_erase_stream<HASH>), dim3(nch), dim3(KH_CHUNK_THREADS), 0, t->stream, F)); }              // (batch erase as an ordered stream)
     else if (src == 5) { KH_SWITCH_HASH(t->hash, hipLaunchKernelGGL((k_insert_stream<HASH>), dim3(nch), dim3(KH_CHUNK_THREADS), 0, t->stream, F)); }             // (insert into a loaded table as an ordered stream)
     else { KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_build_fused<KIND, HASH, 2>), dim3(nch), dim3(KH_CHUNK_THREADS), 0, t->stream, F)); } }
-  { Launch L(t, "k_fused_totals");
+  // (the lean build has added its chunks' counts to F.cnt and carries no stream positions: the tail launch sums the count words itself)
+  if (!lean) { Launch L(t, "k_fused_totals");
     hipLaunchKernelGGL(k_fused_totals, dim3(std::max<uint32_t>(1u, std::min<uint32_t>(64u, nch / 1024u))), dim3(1024), 0, t->stream, F.pub, maxidx, nch, totals); }
-  { // chunk 0: placed now that the last chunk's run-over is known (one workgroup of the general placement kernel)
+  { // chunk 0: placed now that the last chunk's run-over is known (one workgroup, the placement of the general path); the same launch
+    // gathers what the host reads: the totals of the lean build, the sample's and the partition's words next to the control words
     Launch L(t, "k_fused_tail");
-    hipLaunchKernelGGL(k_fused_tail_carry, dim3(1), dim3(64), 0, t->stream, F.pub, nch, xc0, noff0, ncnt0);      // (+ list offsets {0, 0}, list length = count field of pub[0])
     KhRebuildParams T0;
     memset(&T0, 0, sizeof(T0));
-    T0.Old = kNoSlots; T0.New = nw; T0.ck = ck0; T0.cv = cv0; T0.noff = noff0; T0.ncnt = ncnt0; T0.PB = PB_tail;
-    T0.seed = t->seed; T0.homecnt = hc0; T0.xcarry = xc0; T0.flags = F.flags;
-    KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_chunk_place<KIND, HASH>), dim3(1), dim3(KH_CHUNK_THREADS), 0, t->stream, T0));
+    T0.Old = kNoSlots; T0.New = nw; T0.ck = ck0; T0.cv = cv0; T0.PB = PB_tail;
+    T0.seed = t->seed; T0.homecnt = hc0; T0.flags = F.flags;
+    KhTailParams E;
+    E.pub = F.pub; E.nch = nch; E.cnt = lean ? F.cnt : nullptr; E.totals = totals;
+    E.skip = F.skip; E.ovf = t->part_overflow; E.status = reinterpret_cast<uint32_t*>(blk + sz_pub + 16);
+    KH_SWITCH_KIND_HASH(t->kind, t->hash, hipLaunchKernelGGL((k_fused_tail<KIND, HASH>), dim3(1), dim3(KH_CHUNK_THREADS), 0, t->stream, T0, E));
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(t->hpin, blk + sz_pub, 128, hipMemcpyDeviceToHost, t->stream));
-  t->hpin[30] = 0;
-  if (t->part_overflow) HIPCHK(hipMemcpyAsync(t->hpin + 30, t->part_overflow, 4, hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(hipMemcpyAsync(t->hpin, blk + sz_pub, 128, hipMemcpyDeviceToHost, t->stream));      // the one copy: totals, status words, vote, flags
   HIPCHK(hipStreamSynchronize(t->stream));
+  { const uint32_t* status = reinterpret_cast<const uint32_t*>(t->hpin + 2);
+    t->hpin[31] = status[0];      // duplicates the sample found (optimistic attempt; non-zero: every kernel of the attempt returned at once)
+    t->hpin[30] = status[1]; }    // a partition outgrew its slot
   out->totals = totals; out->flags = F.flags;
   return KH_OK;
 }
@@ -758,11 +775,15 @@ inline uint64_t part_buffer_records(uint64_t n, uint32_t PB, bool allow_slack, d
   return (slack_slot((double)n / (double)(uint64_t(1) << PB), vf) << PB) + KH_PART_TILE;        // slots + the dump area of the scatter
 }
 
+// the duplicate sample of an optimistic bulk insert (insert_core): taken by the launch that initialises the partition's cursors, and both
+// passes return at once if it finds a duplicate (KhPartParams::skip).  set / dups: zeroed by the caller
+struct SampleRun { unsigned long long* set; uint32_t* dups; };
 // Partitions n input pairs into `fin` (n records); `tmp` (n records) is scratch for the first of two passes.  idx_base =
 // stream position of the first pair (pairs fed before it in a streamed insert).  Asynchronous on the table's stream.
 kh_status partition_batch(kh_table* t, const char* kbase, uint32_t kstride, const char* vbase, uint32_t vstride,
                           uint32_t vconst, uint64_t n, uint64_t idx_base, uint32_t PB, ulonglong2* tmp, ulonglong2* fin, Partitioned& out,
-                          bool allow_slack = false, int rec12 = 0, const SlackShared* shared = nullptr, bool force_slack = false, double vf = 1.0) {
+                          bool allow_slack = false, int rec12 = 0, const SlackShared* shared = nullptr, bool force_slack = false, double vf = 1.0,
+                          const SampleRun* sample = nullptr) {
   const uint32_t nparts = 1u << PB;
   out.slot = 0; out.cursor = nullptr; out.overflow = nullptr; out.rec12 = 0;
   // (force_slack: the caller has sized tmp / fin for the fixed slots itself -- (slack_slot(n / 2^PB) << PB) + KH_PART_TILE records each --
@@ -790,9 +811,16 @@ kh_status partition_batch(kh_table* t, const char* kbase, uint32_t kstride, cons
     const uint32_t tps = sub_slot ? tps_sub : (uint32_t)((fill_cap + KH_PART_TILE - 1) / KH_PART_TILE);
     const uint32_t max_tiles = (sub_slot ? nb1 * 8u : nb1) * tps;
     if (shared) hipLaunchKernelGGL(k_init_cursors, dim3((nb1 + 255) / 256), dim3(256), 0, t->stream, cur1, (uint64_t*)nullptr, (uint64_t)nb1, slot1);
-    else hipLaunchKernelGGL(k_init_cursors2, dim3((nparts + 256) / 256), dim3(256), 0, t->stream, cur1, (uint64_t)nb1, slot1, sub_slot ? 8u : 1u, cur2, starts, (uint64_t)nparts, slot, ovf);
+    else {
+      KhCursorInit I;
+      I.cur1 = cur1; I.n1 = nb1; I.slot1 = slot1; I.sub1 = sub_slot ? 8u : 1u; I.cur2 = cur2; I.starts = starts; I.n2 = nparts; I.slot2 = slot; I.ovf = ovf;
+      if (sample) { Launch L(t, "k_sample_dups");
+        hipLaunchKernelGGL(k_sample_dups, dim3(KH_SAMPLE_N / 256), dim3(256), 0, t->stream, kbase, kstride, n, sample->set, sample->dups, I); }
+      else hipLaunchKernelGGL(k_init_cursors2, dim3((nparts + 256) / 256), dim3(256), 0, t->stream, I);
+    }
     KhPartParams P;
     memset(&P, 0, sizeof(P));
+    P.skip = sample ? sample->dups : nullptr;
     P.idx_base = idx_base;
     P.xcd_swizzle = g_xcd_swizzle;
     P.kbase = kbase; P.kstride = kstride; P.vbase = vbase; P.vstride = vstride; P.vconst = vconst; P.n = n;
@@ -944,6 +972,8 @@ bool g_disable_fused = getenv("KH_DISABLE_FUSED_BUILD") != nullptr;   // test ho
 
 // second half of an insert: the n pairs have been partitioned (one source per feed); de-dup, capacity decision, build
 const kh_status KH_RETRY_EXACT = static_cast<kh_status>(100);      // internal: a histogram-free partition overflowed a slot
+const kh_status KH_RETRY_DUPS = static_cast<kh_status>(101);       // internal: the sample an optimistic attempt was queued behind found duplicates
+const bool g_sync_sample = getenv("KH_DISABLE_OPTIMISTIC_SAMPLE") != nullptr;      // test hook / A-B: the host reads every sample before it partitions
 kh_status insert_finish(kh_table* t, KhSrcSet S, uint64_t n, uint32_t PB, uint64_t cap_u, int mode, uint64_t forced_cap,
                         ulonglong2* spare, uint64_t* n_new_out, uint64_t list_cap = 0);
 
@@ -967,25 +997,15 @@ kh_status insert_core(kh_table* t, const char* kbase, uint32_t kstride, const ch
   int first_attempt = 0;
   bool dup_heavy = false;
   double vf = 1.0;            // variance factor of the histogram-free slots (duplicates: see below)
-  if (part_buffer_records(n, PB, true) != n) {
-    // histogram-free partition only for batches a sample finds (nearly) free of duplicates
-    unsigned long long* sset; uint32_t* dups;
-    TAKE(sset, unsigned long long, KH_SAMPLE_SET); TAKE(dups, uint32_t, 1);
-    HIPCHK(hipMemsetAsync(sset, 0, sizeof(unsigned long long) * KH_SAMPLE_SET, t->stream));
-    HIPCHK(hipMemsetAsync(dups, 0, 4, t->stream));
-    { Launch L(t, "k_sample_dups");
-      hipLaunchKernelGGL(k_sample_dups, dim3(KH_SAMPLE_N / 256), dim3(256), 0, t->stream, kbase, kstride, n, sset, dups); }
-    HIPCHK(hipMemcpyAsync(t->hpin + 31, dups, 4, hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));
-    // ANY duplicate among the 65536 sampled keys sends the batch down the exact path: the fixed slots are sized for partition counts
-    // that are Poisson in the number of RECORDS, and already a mean multiplicity of 1.5 (a k-mer counter's file batch at low coverage:
-    // ~7 duplicate pairs in the sample, birthday-bound) widens them enough to overflow a slot somewhere among 2^19 partitions --
-    // measured: every such batch paid a discarded 7.5 ms partition attempt; the histogram sweep of the exact path costs 2.5 ms
-    // ... UNLESS the slots are sized for the duplicates: a partition then fills key by key, E[m^2] / E[m] records at a time, and that factor
-    // follows from the sample -- d duplicates among S sampled keys of n say sum m (m - 1) / n = 2 n d / S^2 (the reference benchmark's x5.5 input:
-    // 129 duplicates -> 7.0; a k-mer counter's batch at coverage 1.5: 7 -> 2.5).  Taken at its upper end (d + 3 sqrt(d) + 3) and only while the
-    // slot stays below twice the mean; an overflow after all repeats the batch with exact offsets as before.
-    const uint32_t dsample = (uint32_t)t->hpin[31];
+  // ANY duplicate among the 65536 sampled keys sends the batch down the exact path: the fixed slots are sized for partition counts
+  // that are Poisson in the number of RECORDS, and already a mean multiplicity of 1.5 (a k-mer counter's file batch at low coverage:
+  // ~7 duplicate pairs in the sample, birthday-bound) widens them enough to overflow a slot somewhere among 2^19 partitions --
+  // measured: every such batch paid a discarded 7.5 ms partition attempt; the histogram sweep of the exact path costs 2.5 ms
+  // ... UNLESS the slots are sized for the duplicates: a partition then fills key by key, E[m^2] / E[m] records at a time, and that factor
+  // follows from the sample -- d duplicates among S sampled keys of n say sum m (m - 1) / n = 2 n d / S^2 (the reference benchmark's x5.5 input:
+  // 129 duplicates -> 7.0; a k-mer counter's batch at coverage 1.5: 7 -> 2.5).  Taken at its upper end (d + 3 sqrt(d) + 3) and only while the
+  // slot stays below twice the mean; an overflow after all repeats the batch with exact offsets as before.
+  auto decide = [&](uint32_t dsample) {
     if (dsample >= 1u) {
       dup_heavy = true;
       const double d_ub = (double)dsample + 3.0 * std::sqrt((double)dsample) + 3.0;
@@ -995,12 +1015,41 @@ kh_status insert_core(kh_table* t, const char* kbase, uint32_t kstride, const ch
       else first_attempt = 1;
     }
     t->batch_nodup = dsample == 0u;
-    t->blk = keep_blk; t->off = keep_off;
-  } else first_attempt = 1;
+  };
+  // histogram-free partition only for batches a sample finds (nearly) free of duplicates.  Ahead of the one-launch bulk build the host does
+  // not wait for the sample: it queues what a clean sample would make it choose (vf = 1, 12-byte records where nodup_build_applies) directly
+  // behind it, every kernel of that attempt tests the sample's word and returns at once if it is not zero, and the word reaches the host with
+  // the build's control words (launch_fused) -- a batch with duplicates then pays one discarded round trip and goes on exactly as below.
+  // Every other path (a loaded table, one chunk, a reducer other than plus: the general path decides on the host first) reads the sample now.
+  const bool slackable = part_buffer_records(n, PB, true) != n;
+  bool optimistic = slackable && fused_build_applies(t, cap_u, PB) && one_launch_mode(mode) && !g_sync_sample;
+  if (slackable && !optimistic) {
+    unsigned long long* sset; uint32_t* dups;      // (adjacent: one fill)
+    { char* b; TAKE(b, char, sizeof(unsigned long long) * KH_SAMPLE_SET + 256);
+      sset = reinterpret_cast<unsigned long long*>(b); dups = reinterpret_cast<uint32_t*>(b + sizeof(unsigned long long) * KH_SAMPLE_SET);
+      HIPCHK(hipMemsetAsync(b, 0, sizeof(unsigned long long) * KH_SAMPLE_SET + 256, t->stream)); }
+    { Launch L(t, "k_sample_dups");
+      hipLaunchKernelGGL(k_sample_dups, dim3(KH_SAMPLE_N / 256), dim3(256), 0, t->stream, kbase, kstride, n, sset, dups, KhCursorInit{}); }
+    HIPCHK(hipMemcpyAsync(t->hpin + 31, dups, 4, hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    decide((uint32_t)t->hpin[31]);
+  } else if (!slackable) first_attempt = 1;
   for (int attempt = first_attempt; attempt < 2; ++attempt) {
     const bool slack = attempt == 0;          // histogram-free first; exact offsets if a partition outgrew its slot (skewed keys)
     const uint64_t m = part_buffer_records(n, PB, slack, vf);
-    if (!slack && attempt == 1) { t->blk = keep_blk; t->off = keep_off; }
+    t->blk = keep_blk; t->off = keep_off;     // (the sample set, an attempt before this one: dead)
+    SampleRun sample;
+    const size_t rec0 = t->recs.size();
+    if (optimistic) {
+      // ONE fill for the call: the build's control block, the sample's count word and its set, adjacent
+      const size_t fb = (fused_blk_bytes((uint32_t)(cap_u >> KH_LB)) + 255) & ~size_t(255), hb = fb + 256 + sizeof(unsigned long long) * KH_SAMPLE_SET;
+      char* head; TAKE(head, char, hb);
+      HIPCHK(hipMemsetAsync(head, 0, hb, t->stream));
+      t->fused_blk = head; t->fused_blk_bytes = fused_blk_bytes((uint32_t)(cap_u >> KH_LB));
+      sample.dups = reinterpret_cast<uint32_t*>(head + fb); sample.set = reinterpret_cast<unsigned long long*>(head + fb + 256);
+      t->sample_dups = sample.dups;
+      t->batch_nodup = true;
+    }
     // no duplicate in the sample and an empty table ahead of the one-launch build: the records need no stream position
     // (12 bytes instead of 16); whatever that build cannot take (a duplicate after all, a dense chunk) repeats the batch
     const bool rec12 = slack && t->batch_nodup && nodup_build_applies(t, cap_u, PB, mode);
@@ -1015,15 +1064,26 @@ kh_status insert_core(kh_table* t, const char* kbase, uint32_t kstride, const ch
       tmp = reinterpret_cast<ulonglong2*>(a); fin = reinterpret_cast<ulonglong2*>(b); spare = tmp;
       if (kind == 2) { char* c; TAKE(c, char, m * 12); spare = reinterpret_cast<ulonglong2*>(c); } }     // (lists of distinct keys + counts: 12 bytes per entry)
     Partitioned R;
-    kh_status st = partition_batch(t, kbase, kstride, vbase, vstride, mode == INS_PLUS ? 1u : 0u, n, 0, PB, tmp, fin, R, slack, kind, nullptr, false, vf);
-    if (st != KH_OK) return st;
-    KhSrcSet S;
-    memset(&S, 0, sizeof(S));
-    S.rec[0] = R.rec; S.off[0] = R.part_off; S.n = 1; S.merged_off = R.part_off; S.slot[0] = R.slot; S.cur[0] = R.cursor;
-    S.rec12 = (uint32_t)R.rec12;
-    t->part_overflow = R.overflow; t->batch_vf = vf;
-    st = insert_finish(t, S, n, PB, cap_u, mode, forced_cap, spare, n_new_out, m);
-    t->part_overflow = nullptr; t->batch_nodup = false; t->batch_vf = 1.0;
+    kh_status st = partition_batch(t, kbase, kstride, vbase, vstride, mode == INS_PLUS ? 1u : 0u, n, 0, PB, tmp, fin, R, slack, kind, nullptr, false, vf,
+                                   optimistic ? &sample : nullptr);
+    if (st == KH_OK) {
+      KhSrcSet S;
+      memset(&S, 0, sizeof(S));
+      S.rec[0] = R.rec; S.off[0] = R.part_off; S.n = 1; S.merged_off = R.part_off; S.slot[0] = R.slot; S.cur[0] = R.cursor;
+      S.rec12 = (uint32_t)R.rec12;
+      t->part_overflow = R.overflow; t->batch_vf = vf;
+      st = insert_finish(t, S, n, PB, cap_u, mode, forced_cap, spare, n_new_out, m);
+    }
+    t->part_overflow = nullptr; t->batch_nodup = false; t->batch_vf = 1.0; t->sample_dups = nullptr; t->fused_blk = nullptr;
+    const bool was_optimistic = optimistic;
+    optimistic = false;
+    if (st == KH_RETRY_DUPS && was_optimistic) {      // the sample found duplicates: nothing was written; decide as above and start over
+      decide((uint32_t)t->hpin[31]);
+      // (profile: the launches that returned at once do not count as passes or builds; they keep their times under a label of their own)
+      for (size_t i = rec0; i < t->recs.size(); ++i) if (strcmp(t->recs[i].name, "k_sample_dups")) t->recs[i].name = "k_attempt_skipped";
+      attempt = first_attempt - 1;
+      continue;
+    }
     if (st != KH_RETRY_EXACT) return st;
   }
   return fail(t, KH_ERR_HIP, "internal: exact partition reported a slot overflow");
@@ -1057,6 +1117,7 @@ kh_status insert_finish(kh_table* t, KhSrcSet S, uint64_t n, uint32_t PB, uint64
     F.half_max_load = (cap_u >> 1) >= t->cur.cap ? threshold(cap_u >> 1, t->max_lf) : 0;
     FusedRun run;
     { kh_status fs = launch_fused(t, 0, F, nw, PB, "k_build_fused", &run); if (fs != KH_OK) return fs; }
+    if (F.skip && (uint32_t)t->hpin[31]) { retire_slots(t, nw); return KH_RETRY_DUPS; }      // (every kernel of the attempt returned at once)
     if (t->part_overflow && (uint32_t)t->hpin[30]) { retire_slots(t, nw); return KH_RETRY_EXACT; }
     unsigned long long* totals = run.totals;
     const uint64_t fd = t->hpin[0];
@@ -1898,7 +1959,7 @@ kh_status kh_insert_feed(kh_table* t, const void* keys, const void* vals, uint64
       HIPCHK(hipMemsetAsync(sset, 0, sizeof(unsigned long long) * KH_SAMPLE_SET, t->stream));
       HIPCHK(hipMemsetAsync(dups, 0, 4, t->stream));
       { Launch L(t, "k_sample_dups");
-        hipLaunchKernelGGL(k_sample_dups, dim3(KH_SAMPLE_N / 256), dim3(256), 0, t->stream, reinterpret_cast<const char*>(dk), 8u, n, sset, dups); }
+        hipLaunchKernelGGL(k_sample_dups, dim3(KH_SAMPLE_N / 256), dim3(256), 0, t->stream, reinterpret_cast<const char*>(dk), 8u, n, sset, dups, KhCursorInit{}); }
       HIPCHK(hipMemcpyAsync(t->hpin + 31, dups, 4, hipMemcpyDeviceToHost, t->stream));
       HIPCHK(hipStreamSynchronize(t->stream));
       t->ins.nodup = (uint32_t)t->hpin[31] == 0u;
