@@ -870,6 +870,49 @@ kh_status kh_chain_ends(const void* qtext /*[h|d] u8[nq]*/, uint64_t nq, const v
                         uint64_t* out_offsets /*[2 n_chains + 1]*/, uint32_t* out_ops /*[cap_ops] or NULL*/, uint64_t cap_ops, uint64_t* n_ops,
                         int device, void* hip_stream);
 
+/* ---- primary chains and a mapping quality.  The calls above leave a read that touches a repeat as several chains; kh_chain_select says
+ *      which of them is the answer, which are alternatives worth keeping, and how sure the answer is.  Integers only, no floating point
+ *      anywhere: the kernels equal the model of tests/select_model.py bit for bit.
+ *      Inputs.  n_chains chains; chain c has a query interval [q_start[c], q_end[c]) (u32), a score s_c (i32, any value) and an anchor
+ *      count cnt_c (u32).  A CSR of GROUPS -- group g is the chains [offsets[g], offsets[g + 1]), one read; offsets == NULL: one group
+ *      [0, n_chains).  (kh_chain_anchors numbers chains by their start anchor, so the chains of a read already form a contiguous run.)
+ *      Parameters mask_pct 0..100 (usual value 50), pri_pct 0..100 (80), best_n (5).
+ *      Rank.  Inside a group, chains are ordered by score descending, ties to the smaller chain number; rank_c is the 0-based position
+ *      of c in that order.
+ *      Overlap, all arithmetic in signed 64-bit.  len_c = max(0, qe_c - qs_c); ov(c, p) = max(0, min(qe_c, qe_p) - max(qs_c, qs_p));
+ *      p COVERS c iff 100 * ov(c, p) >= mask_pct * min(len_c, len_p).  So a chain of length 0 is covered by anything, and mask_pct = 0
+ *      means one primary per read.
+ *      Primaries.  Take the chains of a group in rank order.  Chain c is SECONDARY if an earlier chain that is itself primary covers it;
+ *      its parent is then the covering primary of smallest rank.  Otherwise c is PRIMARY and parent_c = c.  A secondary never covers
+ *      anything.
+ *      Per primary p: nsub_p = the number of its secondaries; sub_p = max(0, the greatest score among them), 0 when it has none;
+ *      mapq_p = 0 if s_p <= 0, otherwise
+ *        mapq_p = min(60, floor(60 * (s_p - sub_p) * min(cnt_p, 10) * min(s_p, 100) / (1000 * s_p)))
+ *      (the product stays below 2^47; sub_p <= s_p follows from the rank order).  Per secondary: mapq = 0, sub = 0, nsub = 0.
+ *      Flags (u8).  Bit 0 is set for a primary, bit 1 for a KEPT chain.  A primary is always kept.  A secondary c with parent p is kept
+ *      iff 100 * s_c >= pri_pct * s_p and fewer than best_n secondaries of p precede c in rank order -- what minimap2's -p and -N do.
+ *      Per group: out_best[g] = the chain of rank 0, -1 for an empty group (an unmapped read).
+ *      The formula is this project's own integer form of minimap2's mm_set_parent / mm_set_mapq.  It has the same ingredients -- the
+ *      score gap to the best secondary, the anchor count, a score floor -- but it is not minimap2's float formula, and the results are
+ *      not comparable number for number.
+ *      Outputs per chain: out_parent (a chain number), out_rank, out_mapq, out_flag, out_sub, out_nsub; per group out_best (may be NULL;
+ *      one entry with offsets == NULL).  All arrays live in the memory `where` names.  Host memory: staged, the call synchronises.
+ *      Device memory: every kernel is queued on hip_stream and the call returns WITHOUT waiting for the stream -- it returns no count,
+ *      so it needs no wait; its scratch comes from the pooled block and goes back from a host function queued behind the kernels (not
+ *      capturable into a graph, as kh_chain_edits).
+ *      KH_ERR_INVALID before anything is allocated, read or written: mask_pct > 100, pri_pct > 100, n_chains > 2^23 (the cap of
+ *      kh_chain_ends), n_grp > n_chains + 2^24, n_grp == 0 with offsets given, `where` outside the enum, and while n_chains > 0 a null
+ *      input or per-chain output.  n_chains == 0: KH_OK and every out_best entry = -1 (host memory: without a device).
+ *      Offsets that do not ascend from 0 to n_chains: in host memory they are refused on the host, KH_ERR_INVALID with nothing written.
+ *      In device memory nobody can see them before the kernels run: every group is clamped to [0, n_chains), nothing outside the
+ *      arrays is touched, the outputs of the affected chains are unspecified and the status is KH_OK.  This is the price of not
+ *      waiting. */
+kh_status kh_chain_select(const uint32_t* q_start, const uint32_t* q_end, const int32_t* score, const uint32_t* count, uint64_t n_chains,
+                          const uint64_t* offsets /* u64[n_grp+1] or NULL */, uint64_t n_grp,
+                          uint32_t mask_pct, uint32_t pri_pct, uint32_t best_n, kh_mem where,
+                          int32_t* out_parent, uint32_t* out_rank, uint8_t* out_mapq, uint8_t* out_flag, int32_t* out_sub, uint32_t* out_nsub /* each [n_chains] */,
+                          int32_t* out_best /* [n_grp], [1] with offsets == NULL; may be NULL */, int device, void* hip_stream);
+
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);
 

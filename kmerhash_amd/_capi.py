@@ -90,6 +90,8 @@ SYMBOLS = [
     "kh_chain_cigars",
     # both ends of every chain extended to the ends of its read or to a soft clip
     "kh_chain_ends",
+    # primary / secondary chains per read and a mapping quality per primary
+    "kh_chain_select",
 ]
 
 _lib = None
@@ -271,6 +273,7 @@ def lib():
     L.kh_chain_edits.argtypes = [vp, u64, vp, u64, u32, vp, vp, vp, vp, vp, u64, u64, u32, u32, i32, vp, vp, vp, i32, vp]
     L.kh_chain_cigars.argtypes = [vp, u64, vp, u64, u32, vp, vp, vp, vp, vp, u64, u64, u32, vp, i32, vp, vp, u64, pu64, vp, vp, i32, vp]
     L.kh_chain_ends.argtypes = [vp, u64, vp, u64, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, u32, u32, u32, i32, vp, vp, vp, vp, vp, vp, u64, pu64, i32, vp]
+    L.kh_chain_select.argtypes = [vp, vp, vp, vp, u64, vp, u64, u32, u32, u32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     for s in SYMBOLS:
         if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error", "kh_wide_index_last_error"):
             getattr(L, s).restype = i32

@@ -17,6 +17,7 @@
 //   chain   : kh_chain_anchors, collinear chains per segment from flat anchors: a wavefront per segment, the last 64 anchors in registers (kh_kernels_chain.h).
 //   edits   : kh_chain_edits, edit distance of every link of every kept chain: a lane per anchor, then a wavefront per unsettled link (kh_kernels_edits.h).
 //   cigars  : kh_chain_cigars, the alignment operations of every link as run-length rows of a CSR: the same wavefront pass with a traceback (kh_kernels_cigar.h).
+//   select  : kh_chain_select, primary / secondary chains per read and a mapping quality: a wavefront per read, a workgroup for a read of more than 64 chains (kh_kernels_select.h).
 //   ends    : kh_chain_ends, both ends of every kept chain extended to the ends of its read or to a soft clip: a wavefront per end, target free, stop by score (kh_kernels_ends.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
@@ -28,6 +29,7 @@
 #include "kh_kernels_edits.h"
 #include "kh_kernels_cigar.h"
 #include "kh_kernels_ends.h"
+#include "kh_kernels_select.h"
 #include "kh_part_sizing.h"
 #include "kh_scratch.h"
 #include "../../include/kmerhash_amd.h"
@@ -4342,5 +4344,49 @@ kh_status kh_chain_ends(const void* qtext, uint64_t nq, const void* rtext, uint6
   s.launched();
   s.copy_back(dops, total);
   return s.finish_queued();
+}
+// ---- primaries, secondaries and a mapping quality per group of chains (kernels: kh_kernels_select.h).  No handle; there is no count to
+//      learn, so a device call only queues: at most one memset, two kernels and the return of the pooled block, and never waits.
+kh_status kh_chain_select(const uint32_t* q_start, const uint32_t* q_end, const int32_t* score, const uint32_t* count, uint64_t n_chains, const uint64_t* offsets,
+                          uint64_t n_grp, uint32_t mask_pct, uint32_t pri_pct, uint32_t best_n, kh_mem where, int32_t* out_parent, uint32_t* out_rank,
+                          uint8_t* out_mapq, uint8_t* out_flag, int32_t* out_sub, uint32_t* out_nsub, int32_t* out_best, int device, void* stream_) {
+  if (mask_pct > 100 || pri_pct > 100 || n_chains > (uint64_t(1) << 23) || n_grp > n_chains + (uint64_t(1) << 24)) return KH_ERR_INVALID;
+  if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || (offsets && n_grp == 0)) return KH_ERR_INVALID;
+  if (n_chains && (!q_start || !q_end || !score || !count || !out_parent || !out_rank || !out_mapq || !out_flag || !out_sub || !out_nsub)) return KH_ERR_INVALID;
+  const uint64_t ng = offsets ? n_grp : 1;
+  if (offsets && where == KH_MEM_HOST) {      // (device memory: nobody can look before the kernels run; they clamp)
+    if (offsets[0] != 0 || offsets[ng] != n_chains) return KH_ERR_INVALID;
+    for (uint64_t g = 0; g < ng; ++g)
+      if (offsets[g] > offsets[g + 1]) return KH_ERR_INVALID;
+  }
+  if (n_chains == 0 && (where == KH_MEM_HOST || !out_best)) {
+    for (uint64_t g = 0; out_best && g < ng; ++g) out_best[g] = -1;
+    return KH_OK;
+  }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK0(hipSetDevice(device));
+  if (n_chains == 0) { HIPCHK0(hipMemsetAsync(out_best, 0xFF, ng * sizeof(int32_t), stream)); return KH_OK; }
+  const uint64_t big = n_chains > 64 ? n_chains : 0;      // no group of more than 64 chains without that many chains
+  const uint64_t stride = (big + 63) & ~uint64_t(63);     // words per scratch array (whole 256 bytes)
+  Scratch s(device, stream);
+  KselArgs P{};
+  KselScratch W{};
+  if (!s.layout([&](Scratch& c) {
+        W.base = c.take<uint32_t>(KSEL_SCRATCH_ARRAYS * stride);
+        P.qs = c.in(q_start, n_chains, where); P.qe = c.in(q_end, n_chains, where); P.score = c.in(score, n_chains, where); P.count = c.in(count, n_chains, where);
+        P.off = c.in(offsets, offsets ? ng + 1 : 0, where);
+        P.parent = c.out(out_parent, n_chains, where); P.rank = c.out(out_rank, n_chains, where); P.mapq = c.out(out_mapq, n_chains, where);
+        P.flag = c.out(out_flag, n_chains, where); P.sub = c.out(out_sub, n_chains, where); P.nsub = c.out(out_nsub, n_chains, where);
+        P.best = c.out(out_best, out_best ? ng : 0, where);
+      })) return s.finish();
+  W.stride = (uint32_t)stride;
+  P.n = (uint32_t)n_chains; P.n_grp = (uint32_t)ng; P.mask_pct = mask_pct; P.pri_pct = pri_pct; P.best_n = best_n;
+  const uint32_t ncu = (uint32_t)cu_count(device);
+  hipLaunchKernelGGL(k_select_wave, dim3(grid_for(ng, KSEL_WAVES, ncu * 8)), dim3(KSEL_THREADS), 0, stream, P);
+  if (big) hipLaunchKernelGGL(k_select_block, dim3(grid_for(ng, 1, ncu * 2)), dim3(KSEL_THREADS), 0, stream, P, W);
+  s.launched();
+  s.copy_back(P.parent, n_chains); s.copy_back(P.rank, n_chains); s.copy_back(P.mapq, n_chains); s.copy_back(P.flag, n_chains);
+  s.copy_back(P.sub, n_chains); s.copy_back(P.nsub, n_chains); s.copy_back(P.best, ng);
+  return s.finish_queued();      // (host memory: copies are pending, so this waits)
 }
 }  // extern "C"

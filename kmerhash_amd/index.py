@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from ._call import HOST, _Buf, _Handle, alloc, check_same, torch
-from .kmers import anchors_from_csr, chain_anchors, chain_cigars, chain_edits, chain_ends, stamp_strand
+from .kmers import anchors_from_csr, chain_anchors, chain_cigars, chain_edits, chain_ends, select_table, stamp_strand
 from .seqs import is_syncmer, is_syncmer128, kmers_from_sequence, minimizers_from_sequence, syncmers128_from_sequence, syncmers_from_sequence
 from .table import _hash_id
 
@@ -342,6 +342,16 @@ class KmerPositionIndex(_Handle):
         cigars = chain_cigars(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, edits.link, ref_base, self.device)
         ends = chain_ends(seq, ref_text, q, r, v, c.first, c.last, lo, hi, self.k, ref_base, max_edits, clip_cost, self.device)
         return table, edits, cigars, ends
+
+    def chain_select(self, seq, read_starts=None, mask_pct=50, pri_pct=80, best_n=5, **params):
+        """chains(seq, read_starts, **params), then which chain of every read is the answer: kmers.select_table over the table with one
+        group per read -> (ChainTable, ChainSelect(parent, rank, mapq, flag, sub, nsub, best)): per row of the table its primary, its
+        rank in its read, the mapping quality of a primary and the primary / kept flags; best[s] = the best row of read s, -1 for a read
+        without chains.  The score is the chaining score; kmers.select_chains takes any other."""
+        if not self.stranded:
+            raise ValueError("chain_select() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        table = self._chains(seq, read_starts, params)[0]
+        return table, select_table(table, 1 if read_starts is None else len(read_starts), mask_pct=mask_pct, pri_pct=pri_pct, best_n=best_n, device=self.device)
 
     def _syncmers(self, seq, fastq=False):
         """the closed syncmers of a text under the index's own parameters"""

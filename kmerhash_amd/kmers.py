@@ -295,6 +295,77 @@ def chain_ends(qtext, rtext, qpos, rpos, rev, first, last, q_lo, q_hi, k, ref_ba
     return ChainEnds(*(a for a, _ in nums), offs, ops)
 
 
+ChainSelect = collections.namedtuple("ChainSelect", "parent rank mapq flag sub nsub best")
+FLAG_PRIMARY, FLAG_KEPT = 1, 2      # the bits of ChainSelect.flag
+
+
+def _check_select_params(mask_pct, pri_pct, best_n):
+    """the refusals of kh_chain_select that depend on the parameters alone, as ValueError"""
+    if not 0 <= int(mask_pct) <= 100:
+        raise ValueError("mask_pct must be 0..100, got %r" % (mask_pct,))
+    if not 0 <= int(pri_pct) <= 100:
+        raise ValueError("pri_pct must be 0..100, got %r" % (pri_pct,))
+    if not 0 <= int(best_n) < 2 ** 32:
+        raise ValueError("best_n must be 0..2^32-1, got %r" % (best_n,))
+
+
+def select_chains(q_start, q_end, score, count, read_offsets=None, mask_pct=50, pri_pct=80, best_n=5, device=0):
+    """which chain of every read is the answer, and how sure (kh_chain_select in include/kmerhash_amd.h, which holds the definition): per
+    group -- the chains [read_offsets[g], read_offsets[g + 1]), one read; None: all of them -- the chains in order of score (ties: the
+    smaller number); a chain is secondary when an earlier primary covers mask_pct % of the shorter of the two query intervals, else
+    primary; a primary gets a mapping quality 0..60 from the score gap to its best secondary, its anchor count and its score.
+    -> ChainSelect(parent, rank, mapq, flag, sub, nsub, best): per chain the chain number of its primary (its own for a primary), its
+    rank in the group, the mapping quality (0 for a secondary), flag bit 0 = primary and bit 1 = kept (a primary; a secondary with
+    100 * score >= pri_pct * its parent's that is among the first best_n of its parent), and for a primary the best secondary score and
+    the number of secondaries; per group the chain of rank 0, -1 for a read without chains.  numpy in (uint32, uint32, int32, uint32,
+    uint64), numpy out (int32, uint32, uint8, uint8, int32, uint32, int32); CUDA tensors in (int32 x 4, int64), tensors out on the current
+    stream (int32 holding the uint32 bits) -- queued only: the call does not wait for the stream.  At most 2^23 chains per call."""
+    _check_select_params(mask_pct, pri_pct, best_n)
+    sb, eb, cb, nb = _Buf(q_start, np.uint32), _Buf(q_end, np.uint32), _Buf(score, np.int32), _Buf(count, np.uint32)
+    ob = None if read_offsets is None else _Buf(read_offsets, np.uint64)
+    check_same("q_start, q_end, score, count and read_offsets must live in the same memory", sb, eb, cb, nb, ob, length=False)
+    n = sb.n
+    check_same("q_start, q_end, score and count must have one entry per chain, got %d, %d, %d and %d" % (n, eb.n, cb.n, nb.n), sb, eb, cb, nb)
+    if n > 2 ** 23:
+        raise ValueError("at most 2^23 chains per call (batch over reads), got %d" % n)
+    if ob is not None and (ob.n < 2 or ob.n - 1 > n + 2 ** 24):
+        raise ValueError("read_offsets must hold n_reads + 1 >= 2 entries ascending from 0 to the number of chains, got %d entries for %d chains" % (ob.n, n))
+    ng = 1 if ob is None else ob.n - 1
+    outs = [alloc(sb, n, dt, empty=True) for dt in (np.int32, np.uint32, np.uint8, np.uint8, np.int32, np.uint32)]
+    best, bptr = alloc(sb, ng, np.int32)
+    # (no chains in host memory: the call answers without a device)
+    st = K.lib().kh_chain_select(sb.ptr_or_null, eb.ptr_or_null, cb.ptr_or_null, nb.ptr_or_null, n, None if ob is None else ob.ptr, 0 if ob is None else ng,
+                                 int(mask_pct), int(pri_pct), int(best_n), sb.where, *(p for _, p in outs), bptr, device, stream_of(sb, device))
+    check(st, "kh_chain_select" + (": read_offsets do not ascend from 0 to the number of chains" if st == K.KH_ERR_INVALID else ""))
+    return ChainSelect(*(a for a, _ in outs), best)
+
+
+def select_table(table, n_reads=None, **params):
+    """select_chains over the rows of a ChainTable (index.chains): the groups are the runs of equal table.seg, which does not descend.
+    n_reads: the number of reads (default: the last seg + 1, 0 for an empty table); a read without chains gets best == -1.
+    params: mask_pct, pri_pct, best_n, device."""
+    seg = table.seg
+    dev = _is_tensor(seg) and seg.is_cuda
+    rows = int(seg.numel() if _is_tensor(seg) else len(seg))
+    if n_reads is None:
+        n_reads = int(seg.max()) + 1 if rows else 0
+    n_reads = int(n_reads)
+    if n_reads < 0 or (rows and n_reads == 0):
+        raise ValueError("n_reads must cover the reads of the table, got %r" % (n_reads,))
+    if n_reads == 0:               # an empty table of no reads: nothing to select, no group to report
+        _check_select_params(params.get("mask_pct", 50), params.get("pri_pct", 80), params.get("best_n", 5))
+        like = _Buf(table.score, np.int32)
+        return ChainSelect(*(alloc(like, 0, dt)[0] for dt in (np.int32, np.uint32, np.uint8, np.uint8, np.int32, np.uint32, np.int32)))
+    # read g owns the rows with seg == g: offsets[g] = the first row with seg >= g
+    if dev:
+        offs = torch.searchsorted(seg.long(), torch.arange(n_reads + 1, dtype=torch.int64, device=seg.device))
+    else:
+        offs = np.searchsorted(np.asarray(seg).astype(np.int64), np.arange(n_reads + 1, dtype=np.int64), side="left").astype(np.uint64)
+    if int(offs[-1]) != rows:
+        raise ValueError("n_reads = %d does not cover the reads of the table (seg reaches %d)" % (n_reads, int(seg.max())))
+    return select_chains(table.q_start, table.q_end, table.score, table.count, offs, **params)
+
+
 def read_cigar(cigars, ends, table, row, k):
     """the CIGAR of the whole read of chain `row` as text (a host helper like cigar_string): 'S' for the bases the head clips, the head's
     row, what cigar_string(cigars, table, row, k) gives, the tail's row, 'S' for the bases the tail clips, equal neighbours merged -- in
