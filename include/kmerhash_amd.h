@@ -913,6 +913,71 @@ kh_status kh_chain_select(const uint32_t* q_start, const uint32_t* q_end, const 
                           int32_t* out_parent, uint32_t* out_rank, uint8_t* out_mapq, uint8_t* out_flag, int32_t* out_sub, uint32_t* out_nsub /* each [n_chains] */,
                           int32_t* out_best /* [n_grp], [1] with offsets == NULL; may be NULL */, int device, void* hip_stream);
 
+/* ---- one alignment record per chain.  The chain calls leave a read's alignment in pieces: one CSR row per anchor link
+ *      (kh_chain_cigars), two rows and two clips per chain (kh_chain_ends), the intervals in the chains' first and last anchors.
+ *      kh_chain_records joins them: per chain one row of runs -- the CIGAR of the whole read -- and the numbers of a PAF line.  It
+ *      reads no text; it consumes only what the earlier calls wrote.
+ *      Inputs: per anchor [m] qpos, rpos, rev and chain (the chain number of kh_chain_anchors, -1: none); the link CSR of
+ *      kh_chain_cigars, lk_offsets [m + 1] and lk_ops [n_lk]; per chain [n_chains] c_first, c_last (anchor indices) and the read's byte
+ *      interval [q_lo, q_hi); the ends of kh_chain_ends, e_q, e_r, e_clip [2 n_chains], en_offsets [2 n_chains + 1], en_ops [n_en];
+ *      k (1..64) and ref_order (0 or 1).
+ *      Rows of the two input CSRs.  Row i of a CSR with n runs is [a, b) with a = min(offsets[i], n), b = min(offsets[i + 1], n); it is
+ *      EMPTY where b <= a or b - a > 63 (no row of the two calls is longer: 2 * 31 + 1).
+ *      Members.  The members of chain c are the anchors i in [c_first[c], c_last[c]] with chain[i] == c; ascending anchor order is
+ *      chain order (kh_chain_anchors: pred[i] < i).
+ *      Validity.  out_valid[c] = 1 iff  c_first[c] <= c_last[c] < m;  chain[c_first[c]] == chain[c_last[c]] == c;
+ *      q_lo <= qpos[first];  qpos[last] + k <= q_hi;  q_hi - q_lo < 2^28;  and every member but the first has a link row that is not
+ *      empty (the condition under which the chain has a whole alignment at all).
+ *      The row of a valid chain is the sequence of pieces, in read order:  S x (e_clip[2c] mod 2^28);  end row 2c (the head);  the link
+ *      row of every member except the first, ascending;  k x '=' (the last seed);  end row 2c + 1 (the tail);
+ *      S x (e_clip[2c + 1] mod 2^28)  -- fed run by run through this rule: a run of length 0 vanishes; a run whose op equals the op of
+ *      the run before it adds its length to that run (mod 2^28, the width of the length field); any other run starts a new one.  Runs
+ *      are (len << 4) | op in the BAM encoding (S = 4, I = 1, D = 2, '=' = 7, X = 8).  With ref_order == 1 the row of a chain whose
+ *      bit 0 of rev[c_first[c]] is set is stored in the reverse run order, the orientation PAF and SAM expect; ref_order == 0 keeps
+ *      read order.  An invalid chain has an empty row.
+ *      Numbers per chain, all u32 with wrapping arithmetic.  Where the first two validity conditions hold, with f = c_first[c],
+ *      l = c_last[c]:  qs = qpos[f] - e_q[2c] - q_lo  and  qe = qpos[l] + k + e_q[2c + 1] - q_lo, read-relative;
+ *      rs = min(rpos[f], rpos[l]) - x  and  re = max(rpos[f], rpos[l]) + k + y  in reference coordinates, with (x, y) =
+ *      (e_r[2c], e_r[2c + 1]) on the forward strand and (e_r[2c + 1], e_r[2c]) on the reverse strand (bit 0 of rev[f]): head and
+ *      tail swap sides.  Elsewhere the four are 0.  qlen = q_hi - q_lo always.  For a valid chain n_match = the sum of its '=' runs,
+ *      n_block = the sum of its '=', X, I and D runs, nm = the sum of its X, I and D runs; 0 for an invalid one.
+ *      All arrays live in the memory `where` names.  out_ops == NULL: count only -- out_valid, the eight numbers, out_offsets
+ *      [n_chains + 1] and *n_ops are written.  More runs than cap_ops: KH_ERR_INVALID with *n_ops set, the numbers and out_offsets
+ *      written and out_ops untouched.  Device memory: everything is queued on hip_stream and the one host wait of a pass is the one
+ *      that learns *n_ops.  Host memory: staged, the call synchronises.  Garbage in the arrays yields empty or wrong rows; no element
+ *      outside the arrays is read or written.
+ *      KH_ERR_INVALID before anything is allocated, read or written: k outside 1..64, ref_order > 1, m > 2^24, n_chains > 2^23, n_lk or
+ *      n_en > 2^31, `where` outside the enum, a null out_offsets or n_ops, while n_chains > 0 a null chain array, end array or output
+ *      (en_ops may be null while n_en == 0), and while both n_chains > 0 and m > 0 a null anchor array or link array (lk_ops may be
+ *      null while n_lk == 0).  n_chains == 0: KH_OK, *n_ops = 0, out_offsets[0] = 0. */
+kh_status kh_chain_records(const uint32_t* qpos /*[h|d] u32[m]*/, const uint32_t* rpos, const uint8_t* rev, const int32_t* chain, uint64_t m,
+                           const uint64_t* lk_offsets /*[m+1]*/, const uint32_t* lk_ops /*[n_lk]*/, uint64_t n_lk,
+                           const uint32_t* c_first, const uint32_t* c_last, const uint32_t* q_lo, const uint32_t* q_hi /* each [n_chains] */, uint64_t n_chains,
+                           const uint32_t* e_q, const uint32_t* e_r, const uint32_t* e_clip /* each [2 n_chains] */,
+                           const uint64_t* en_offsets /*[2 n_chains + 1]*/, const uint32_t* en_ops /*[n_en]*/, uint64_t n_en,
+                           uint32_t k /*1..64*/, uint32_t ref_order /*0|1*/, kh_mem where,
+                           uint8_t* out_valid, uint32_t* out_qs, uint32_t* out_qe, uint32_t* out_rs, uint32_t* out_re, uint32_t* out_qlen,
+                           uint32_t* out_match, uint32_t* out_block, uint32_t* out_nm /* each [n_chains] */,
+                           uint64_t* out_offsets /*[n_chains + 1]*/, uint32_t* out_ops /*[cap_ops] or NULL*/, uint64_t cap_ops, uint64_t* n_ops,
+                           int device, void* hip_stream);
+
+/* ---- a run CSR as CIGAR text.  Any (offsets [n_rows + 1], ops [n_ops]) pair of runs (len << 4) | op -- link rows, end rows, record
+ *      rows -- becomes a byte CSR: row i is the ASCII of its runs, each the decimal length (1..9 digits: a length has 28 bits; 0 prints
+ *      as "0") followed by the op letter from "MIDNSHP=X", '?' for the op codes 9..15.  No separator, no terminator.
+ *      Bounds.  With o(i) = min(offsets[i], n_ops), base = o(0) and b(i) = max(o(i), base):  out_offsets[i] = the bytes of the runs
+ *      [base, b(i)), and out_text holds the text of the runs [base, b(n_rows)) -- for offsets that ascend within [0, n_ops] exactly the
+ *      rows' texts one after the other.  Offsets that descend give descending out_offsets; nothing outside the arrays is read or
+ *      written.
+ *      out_text == NULL: count only -- out_offsets and *n_text are written.  More bytes than cap_text: KH_ERR_INVALID with *n_text set,
+ *      out_offsets written and out_text untouched.  Device memory: everything is queued on hip_stream, one host wait per pass to learn
+ *      *n_text.  Host memory: staged, the call synchronises.
+ *      KH_ERR_INVALID before anything is touched: n_rows or n_ops > 2^31, `where` outside the enum, a null out_offsets or n_text, a null
+ *      offsets while n_rows > 0, a null ops while both n_rows > 0 and n_ops > 0.  n_rows == 0 or n_ops == 0: KH_OK, *n_text = 0, every
+ *      out_offsets entry 0 (host memory: no device is needed). */
+kh_status kh_cigar_text(const uint64_t* offsets /*[h|d] u64[n_rows+1]*/, uint64_t n_rows, const uint32_t* ops /*[h|d] u32[n_ops]*/, uint64_t n_ops, kh_mem where,
+                        uint64_t* out_offsets /*[n_rows + 1]*/, uint8_t* out_text /*[cap_text] or NULL*/, uint64_t cap_text, uint64_t* n_text,
+                        int device, void* hip_stream);
+
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);
 

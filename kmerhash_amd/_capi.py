@@ -92,6 +92,9 @@ SYMBOLS = [
     "kh_chain_ends",
     # primary / secondary chains per read and a mapping quality per primary
     "kh_chain_select",
+    # one alignment record per chain from the link rows, end rows and clips; a run CSR as CIGAR text
+    "kh_chain_records",
+    "kh_cigar_text",
 ]
 
 _lib = None
@@ -274,6 +277,8 @@ def lib():
     L.kh_chain_cigars.argtypes = [vp, u64, vp, u64, u32, vp, vp, vp, vp, vp, u64, u64, u32, vp, i32, vp, vp, u64, pu64, vp, vp, i32, vp]
     L.kh_chain_ends.argtypes = [vp, u64, vp, u64, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, u32, u32, u32, i32, vp, vp, vp, vp, vp, vp, u64, pu64, i32, vp]
     L.kh_chain_select.argtypes = [vp, vp, vp, vp, u64, vp, u64, u32, u32, u32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    L.kh_chain_records.argtypes = [vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, u32, u32, i32] + [vp] * 11 + [u64, pu64, i32, vp]
+    L.kh_cigar_text.argtypes = [vp, u64, vp, u64, i32, vp, vp, u64, pu64, i32, vp]
     for s in SYMBOLS:
         if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error", "kh_wide_index_last_error"):
             getattr(L, s).restype = i32

@@ -18,6 +18,7 @@
 //   edits   : kh_chain_edits, edit distance of every link of every kept chain: a lane per anchor, then a wavefront per unsettled link (kh_kernels_edits.h).
 //   cigars  : kh_chain_cigars, the alignment operations of every link as run-length rows of a CSR: the same wavefront pass with a traceback (kh_kernels_cigar.h).
 //   select  : kh_chain_select, primary / secondary chains per read and a mapping quality: a wavefront per read, a workgroup for a read of more than 64 chains (kh_kernels_select.h).
+//   records : kh_chain_records, one run-length row and one line of numbers per chain from the link rows, end rows and clips: a wavefront per chain; kh_cigar_text, a run CSR as text (kh_kernels_records.h).
 //   ends    : kh_chain_ends, both ends of every kept chain extended to the ends of its read or to a soft clip: a wavefront per end, target free, stop by score (kh_kernels_ends.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
@@ -30,6 +31,7 @@
 #include "kh_kernels_cigar.h"
 #include "kh_kernels_ends.h"
 #include "kh_kernels_select.h"
+#include "kh_kernels_records.h"
 #include "kh_part_sizing.h"
 #include "kh_scratch.h"
 #include "../../include/kmerhash_amd.h"
@@ -346,7 +348,7 @@ class Scratch {
   void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
     if (ok()) { err_ = hipMemcpyAsync(dst, src, bytes, kind, stream_); pending_ = true; }
   }
-  static const int kMaxBlocks = 4, kMaxOut = 8;
+  static const int kMaxBlocks = 4, kMaxOut = 16;
   struct Out { void* host; const void* dev; };
   int device_; hipStream_t stream_;
   hipError_t err_ = hipSuccess;
@@ -4388,5 +4390,101 @@ kh_status kh_chain_select(const uint32_t* q_start, const uint32_t* q_end, const 
   s.copy_back(P.parent, n_chains); s.copy_back(P.rank, n_chains); s.copy_back(P.mapq, n_chains); s.copy_back(P.flag, n_chains);
   s.copy_back(P.sub, n_chains); s.copy_back(P.nsub, n_chains); s.copy_back(P.best, ng);
   return s.finish_queued();      // (host memory: copies are pending, so this waits)
+}
+// ---- one record per chain (kernels: kh_kernels_records.h).  No handle; one pooled block holds the run counts and the scan's tile sums
+//      (and the staged arrays of a host call), a second one the staged rows of a host call.  Everything is queued on the caller's
+//      stream; the one host wait of a pass is the one that learns *n_ops.
+kh_status kh_chain_records(const uint32_t* qpos, const uint32_t* rpos, const uint8_t* rev, const int32_t* chain, uint64_t m, const uint64_t* lk_offsets,
+                           const uint32_t* lk_ops, uint64_t n_lk, const uint32_t* c_first, const uint32_t* c_last, const uint32_t* q_lo, const uint32_t* q_hi,
+                           uint64_t n_chains, const uint32_t* e_q, const uint32_t* e_r, const uint32_t* e_clip, const uint64_t* en_offsets, const uint32_t* en_ops,
+                           uint64_t n_en, uint32_t k, uint32_t ref_order, kh_mem where, uint8_t* out_valid, uint32_t* out_qs, uint32_t* out_qe, uint32_t* out_rs,
+                           uint32_t* out_re, uint32_t* out_qlen, uint32_t* out_match, uint32_t* out_block, uint32_t* out_nm, uint64_t* out_offsets,
+                           uint32_t* out_ops, uint64_t cap_ops, uint64_t* n_ops, int device, void* stream_) {
+  const uint64_t lim = uint64_t(1) << 31;
+  if (k < 1 || k > 64 || ref_order > 1 || m > (uint64_t(1) << 24) || n_chains > (uint64_t(1) << 23) || n_lk > lim || n_en > lim) return KH_ERR_INVALID;
+  if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !out_offsets || !n_ops) return KH_ERR_INVALID;
+  if (n_chains && (!c_first || !c_last || !q_lo || !q_hi || !e_q || !e_r || !e_clip || !en_offsets || (n_en && !en_ops))) return KH_ERR_INVALID;
+  if (n_chains && (!out_valid || !out_qs || !out_qe || !out_rs || !out_re || !out_qlen || !out_match || !out_block || !out_nm)) return KH_ERR_INVALID;
+  if (n_chains && m && (!qpos || !rpos || !rev || !chain || !lk_offsets || (n_lk && !lk_ops))) return KH_ERR_INVALID;
+  *n_ops = 0;
+  if (n_chains == 0 && where == KH_MEM_HOST) { out_offsets[0] = 0; return KH_OK; }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK0(hipSetDevice(device));
+  if (n_chains == 0) { HIPCHK0(hipMemsetAsync(out_offsets, 0, sizeof(uint64_t), stream)); return KH_OK; }
+  const uint64_t nst = (n_chains + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
+  Scratch s(device, stream);
+  uint32_t *runs = nullptr, *dops = nullptr; uint64_t* doff = nullptr; unsigned long long* ssums = nullptr;
+  KrcArgs P{};
+  KrcOut O{};
+  if (!s.layout([&](Scratch& c) {
+        runs = c.take<uint32_t>(n_chains); ssums = c.take<unsigned long long>(nst + 1);
+        P.qpos = c.in(qpos, m, where); P.rpos = c.in(rpos, m, where); P.rev = c.in(rev, m, where); P.chain = c.in(chain, m, where);
+        P.lk_off = c.in(lk_offsets, m ? m + 1 : 0, where); P.lk_ops = c.in(lk_ops, m ? n_lk : 0, where);
+        P.c_first = c.in(c_first, n_chains, where); P.c_last = c.in(c_last, n_chains, where); P.q_lo = c.in(q_lo, n_chains, where); P.q_hi = c.in(q_hi, n_chains, where);
+        P.e_q = c.in(e_q, 2 * n_chains, where); P.e_r = c.in(e_r, 2 * n_chains, where); P.e_clip = c.in(e_clip, 2 * n_chains, where);
+        P.en_off = c.in(en_offsets, 2 * n_chains + 1, where); P.en_ops = c.in(en_ops, n_en, where);
+        O.valid = c.out(out_valid, n_chains, where); O.qs = c.out(out_qs, n_chains, where); O.qe = c.out(out_qe, n_chains, where);
+        O.rs = c.out(out_rs, n_chains, where); O.re = c.out(out_re, n_chains, where); O.qlen = c.out(out_qlen, n_chains, where);
+        O.n_match = c.out(out_match, n_chains, where); O.n_block = c.out(out_block, n_chains, where); O.nm = c.out(out_nm, n_chains, where);
+        doff = c.out(out_offsets, n_chains + 1, where);
+      })) return s.finish();
+  P.n_lk = m ? n_lk : 0; P.n_en = n_en; P.m = (uint32_t)m; P.n_chains = (uint32_t)n_chains; P.k = k; P.ref_order = ref_order;
+  const uint32_t ncu = (uint32_t)cu_count(device);
+  hipLaunchKernelGGL(k_records_count, dim3(grid_for(n_chains, KRC_WAVES, ncu * 8)), dim3(KRC_THREADS), 0, stream, P, O, runs);
+  scan_counts(stream, (const uint32_t*)runs, n_chains, ssums, doff);
+  s.launched();
+  unsigned long long total = 0;
+  s.read(&total, (const unsigned long long*)(ssums + nst));
+  s.copy_back(doff, n_chains + 1); s.copy_back(O.valid, n_chains); s.copy_back(O.qs, n_chains); s.copy_back(O.qe, n_chains); s.copy_back(O.rs, n_chains);
+  s.copy_back(O.re, n_chains); s.copy_back(O.qlen, n_chains); s.copy_back(O.n_match, n_chains); s.copy_back(O.n_block, n_chains); s.copy_back(O.nm, n_chains);
+  if (!s.sync()) return s.finish();      // the one host wait of a device call: *n_ops
+  *n_ops = total;
+  if (!out_ops || total == 0) return s.finish();
+  if (total > cap_ops) { s.finish(); return KH_ERR_INVALID; }
+  if (!s.layout([&](Scratch& c) { dops = c.out(out_ops, total, where); })) return s.finish();
+  s.zero(dops, total * sizeof(uint32_t));      // (the runs are added onto zeroes)
+  hipLaunchKernelGGL(k_records_emit, dim3(grid_for(n_chains, KRC_WAVES, ncu * 8)), dim3(KRC_THREADS), 0, stream, P, (const uint64_t*)doff, (uint64_t)total, dops);
+  s.launched();
+  s.copy_back(dops, total);
+  return s.finish_queued();
+}
+// ---- a run CSR as text (kernels: kh_kernels_records.h).  The same protocol: count, scan, one host wait for *n_text, emit.
+kh_status kh_cigar_text(const uint64_t* offsets, uint64_t n_rows, const uint32_t* ops, uint64_t n_ops, kh_mem where, uint64_t* out_offsets, uint8_t* out_text,
+                        uint64_t cap_text, uint64_t* n_text, int device, void* stream_) {
+  const uint64_t lim = uint64_t(1) << 31;
+  if (n_rows > lim || n_ops > lim || (where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !out_offsets || !n_text) return KH_ERR_INVALID;
+  if ((n_rows && !offsets) || (n_rows && n_ops && !ops)) return KH_ERR_INVALID;
+  *n_text = 0;
+  if ((n_rows == 0 || n_ops == 0) && where == KH_MEM_HOST) { memset(out_offsets, 0, (n_rows + 1) * sizeof(uint64_t)); return KH_OK; }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK0(hipSetDevice(device));
+  if (n_rows == 0 || n_ops == 0) { HIPCHK0(hipMemsetAsync(out_offsets, 0, (n_rows + 1) * sizeof(uint64_t), stream)); return KH_OK; }
+  const uint64_t nst = (n_ops + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
+  Scratch s(device, stream);
+  uint32_t* bytes = nullptr; uint64_t *boff = nullptr, *doff = nullptr; unsigned long long *ssums = nullptr, *dtotal = nullptr;
+  const uint64_t* din = nullptr; const uint32_t* dops = nullptr; uint8_t* dtext = nullptr;
+  if (!s.layout([&](Scratch& c) {
+        bytes = c.take<uint32_t>(n_ops); boff = c.take<uint64_t>(n_ops + 1); ssums = c.take<unsigned long long>(nst + 1); dtotal = c.take<unsigned long long>(1);
+        din = c.in(offsets, n_rows + 1, where); dops = c.in(ops, n_ops, where);
+        doff = c.out(out_offsets, n_rows + 1, where);
+      })) return s.finish();
+  const uint32_t ncu = (uint32_t)cu_count(device);
+  hipLaunchKernelGGL(k_text_count, dim3(grid_for(n_ops, KTX_THREADS, ncu * 8)), dim3(KTX_THREADS), 0, stream, dops, n_ops, bytes);
+  scan_counts(stream, (const uint32_t*)bytes, n_ops, ssums, boff);
+  hipLaunchKernelGGL(k_text_rows, dim3(grid_for(n_rows + 1, KTX_THREADS, ncu * 8)), dim3(KTX_THREADS), 0, stream, din, n_rows, n_ops, (const uint64_t*)boff, doff, dtotal);
+  s.launched();
+  unsigned long long total = 0;
+  s.read(&total, (const unsigned long long*)dtotal);
+  s.copy_back(doff, n_rows + 1);
+  if (!s.sync()) return s.finish();      // the one host wait of a device call: *n_text
+  *n_text = total;
+  if (!out_text || total == 0) return s.finish();
+  if (total > cap_text) { s.finish(); return KH_ERR_INVALID; }
+  if (!s.layout([&](Scratch& c) { dtext = c.out(out_text, total, where); })) return s.finish();
+  hipLaunchKernelGGL(k_text_emit, dim3(grid_for(n_ops, KTX_THREADS, ncu * 8)), dim3(KTX_THREADS), 0, stream, dops, din, n_rows, n_ops, (const uint64_t*)boff, (uint64_t)total,
+                     dtext);
+  s.launched();
+  s.copy_back(dtext, total);
+  return s.finish_queued();
 }
 }  // extern "C"

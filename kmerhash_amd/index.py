@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from ._call import HOST, _Buf, _Handle, alloc, check_same, torch
-from .kmers import anchors_from_csr, chain_anchors, chain_cigars, chain_edits, chain_ends, select_table, stamp_strand
+from .kmers import Mapping, anchors_from_csr, chain_anchors, chain_cigars, chain_edits, chain_ends, chain_records, select_table, stamp_strand
 from .seqs import is_syncmer, is_syncmer128, kmers_from_sequence, minimizers_from_sequence, syncmers128_from_sequence, syncmers_from_sequence
 from .table import _hash_id
 
@@ -318,6 +318,10 @@ class KmerPositionIndex(_Handle):
         kmers.extended_intervals(table, ends) the intervals it maps."""
         if not self.stranded:
             raise ValueError("chain_ends() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        return self._ends(seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, params)[:4]
+
+    def _ends(self, seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, params):
+        """the body of chain_ends(): -> (ChainTable, ChainEdits, ChainCigars, ChainEnds, the Chains of chain_anchors, q_lo, q_hi per chain)"""
         seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to four calls)
         table, c = self._chains(seq, read_starts, params)
         q, r, v = table.anchors
@@ -341,7 +345,22 @@ class KmerPositionIndex(_Handle):
         edits = chain_edits(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
         cigars = chain_cigars(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, edits.link, ref_base, self.device)
         ends = chain_ends(seq, ref_text, q, r, v, c.first, c.last, lo, hi, self.k, ref_base, max_edits, clip_cost, self.device)
-        return table, edits, cigars, ends
+        return table, edits, cigars, ends, c, lo, hi
+
+    def map(self, seq, ref_text, read_starts=None, read_ends=None, ref_base=0, max_edits=31, clip_cost=4, mask_pct=50, pri_pct=80, best_n=5, ref_order=True,
+            **params):
+        """the whole mapper in one call: chain_ends(seq, ref_text, ...), kmers.select_table over its table with one group per read, and
+        kmers.chain_records over all of it -> Mapping(table, edits, cigars, ends, select, records): row c of table, select and records is
+        one candidate alignment -- its read, strand and intervals, whether it is the read's primary and how sure, and its CIGAR as a
+        row of runs with the PAF numbers beside it.  ref_order (default True): the CIGAR rows of reverse-strand chains run in reference
+        order, as PAF and SAM want them; False gives read order, what kmers.read_cigar() prints.  kmers.write_paf() writes the lines."""
+        if not self.stranded:
+            raise ValueError("map() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        table, edits, cigars, ends, c, lo, hi = self._ends(seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, params)
+        select = select_table(table, 1 if read_starts is None else len(read_starts), mask_pct=mask_pct, pri_pct=pri_pct, best_n=best_n, device=self.device)
+        q, r, v = table.anchors
+        records = chain_records(q, r, v, table.chain, cigars, c.first, c.last, lo, hi, ends, self.k, ref_order, self.device)
+        return Mapping(table, edits, cigars, ends, select, records)
 
     def chain_select(self, seq, read_starts=None, mask_pct=50, pri_pct=80, best_n=5, **params):
         """chains(seq, read_starts, **params), then which chain of every read is the answer: kmers.select_table over the table with one

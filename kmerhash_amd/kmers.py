@@ -402,6 +402,121 @@ def extended_intervals(table, ends):
     return q0 - hq, q1 + tq, r0 - np.where(rev, tr, hr), r1 + np.where(rev, hr, tr)
 
 
+ChainRecords = collections.namedtuple("ChainRecords", "valid qs qe rs re qlen n_match n_block nm offsets ops")
+Mapping = collections.namedtuple("Mapping", "table edits cigars ends select records")
+TEXT_OPS = "MIDNSHP=X"      # the op letters kh_cigar_text prints; '?' for the codes 9..15
+
+
+def chain_records(qpos, rpos, rev, chain, cigars, first, last, q_lo, q_hi, ends, k, ref_order=False, device=0):
+    """one alignment record per chain (kh_chain_records in include/kmerhash_amd.h, which holds the definition), from what the chain calls
+    wrote and nothing else: the anchors with their chain numbers, the ChainCigars of chain_cigars, first / last / q_lo / q_hi as
+    chain_ends took them and the ChainEnds it returned.
+    -> ChainRecords(valid, qs, qe, rs, re, qlen, n_match, n_block, nm, offsets, ops): per chain whether it has a whole alignment, the
+    read-relative query interval, the reference interval, the read's length, the matching bases, the alignment block length and the
+    edits (PAF columns 3, 4, 8, 9, 2, 10, 11 and NM); then a CSR whose row c is the CIGAR of the whole read of chain c as runs
+    (len << 4) | op -- S, the head, the links, k '=', the tail, S, equal neighbours merged: what read_cigar() prints.  ref_order: the
+    rows of reverse-strand chains are stored back to front, as PAF and SAM want them.  An invalid chain has an empty row.  Count, then
+    emit: two calls, one allocation of the exact size.  numpy in, numpy out (uint8, uint32 x 8, uint64, uint32); CUDA tensors in, tensors
+    out on the current stream (int32 holding the uint32 bits, int64 offsets); the call waits for the stream once per pass.  At most 2^24
+    anchors and 2^23 chains per call.  cigar_text() renders the rows, write_paf() the lines."""
+    if not 1 <= int(k) <= 64:
+        raise ValueError("k must be 1..64, got %r" % (k,))
+    qb, rb, vb, cb = _Buf(qpos, np.uint32), _Buf(rpos, np.uint32), _Buf(rev, np.uint8), _Buf(chain, np.int32)
+    lo_, lp = _Buf(cigars.offsets, np.uint64), _Buf(cigars.ops, np.uint32)
+    fb, lb, ob, hb = _Buf(first, np.uint32), _Buf(last, np.uint32), _Buf(q_lo, np.uint32), _Buf(q_hi, np.uint32)
+    eq, er, ec, eo, ep = _Buf(ends.q, np.uint32), _Buf(ends.r, np.uint32), _Buf(ends.clip, np.uint32), _Buf(ends.offsets, np.uint64), _Buf(ends.ops, np.uint32)
+    check_same("the anchors, the cigars, first, last, q_lo, q_hi and the ends must live in the same memory", qb, rb, vb, cb, lo_, lp, fb, lb, ob, hb, eq, er, ec, eo, ep,
+               length=False)
+    m, nc = qb.n, fb.n
+    check_same("qpos, rpos, rev and chain must have one entry per anchor, got %d, %d, %d and %d" % (m, rb.n, vb.n, cb.n), qb, rb, vb, cb)
+    check_same("first, last, q_lo and q_hi must have one entry per chain, got %d, %d, %d and %d" % (nc, lb.n, ob.n, hb.n), fb, lb, ob, hb)
+    if lo_.n != m + 1:
+        raise ValueError("cigars.offsets must hold one entry per anchor and one more, got %d for %d anchors" % (lo_.n, m))
+    if eq.n != 2 * nc or er.n != 2 * nc or ec.n != 2 * nc or eo.n != 2 * nc + 1:
+        raise ValueError("the ends must hold two rows per chain (q, r, clip: %d, %d, %d; offsets: %d) for %d chains" % (eq.n, er.n, ec.n, eo.n, nc))
+    if m > 2 ** 24:
+        raise ValueError("at most 2^24 anchors per call (batch over reads), got %d" % m)
+    if nc > 2 ** 23:
+        raise ValueError("at most 2^23 chains per call (batch over reads), got %d" % nc)
+    valid, vptr = alloc(fb, nc, np.uint8, empty=True)
+    nums = [alloc(fb, nc, np.uint32, empty=True) for _ in range(8)]
+    offs, optr = alloc(fb, nc + 1, np.uint64, zero=True)
+    if nc == 0:      # nothing to queue: the zeroed offset is the answer
+        return ChainRecords(valid, *(a for a, _ in nums), offs, alloc(fb, 0, np.uint32)[0])
+    fn, n, stream = K.lib().kh_chain_records, C.c_uint64(), stream_of(fb, device)
+    args = (qb.ptr_or_null, rb.ptr_or_null, vb.ptr_or_null, cb.ptr_or_null, m, lo_.ptr if m else None, lp.ptr_or_null, lp.n, fb.ptr, lb.ptr, ob.ptr, hb.ptr, nc,
+            eq.ptr, er.ptr, ec.ptr, eo.ptr, ep.ptr_or_null, ep.n, int(k), 1 if ref_order else 0, fb.where, vptr, *(p for _, p in nums), optr)
+    check(fn(*args, None, 0, C.byref(n), device, stream), "kh_chain_records")
+    ops, pptr = alloc(fb, n.value, np.uint32)
+    if n.value:
+        check(fn(*args, pptr, n.value, C.byref(n), device, stream), "kh_chain_records")
+    return ChainRecords(valid, *(a for a, _ in nums), offs, ops)
+
+
+def cigar_text(offsets, ops, device=0):
+    """a CSR of runs (len << 4) | op as CIGAR text (kh_cigar_text): row i becomes the decimal length and the op letter ("MIDNSHP=X", '?'
+    beyond) of each of its runs.  Any run CSR will do: ChainCigars, ChainEnds or ChainRecords offsets / ops.
+    -> (text_offsets, text): row i is text[text_offsets[i]:text_offsets[i + 1]].  numpy in (uint64, uint32), numpy out (uint64, uint8);
+    CUDA tensors in (int64, int32), tensors out (int64, uint8) on the current stream; count, then emit, one wait per pass."""
+    ob, pb = _Buf(offsets, np.uint64), _Buf(ops, np.uint32)
+    check_same("offsets and ops must live in the same memory", ob, pb, length=False)
+    if ob.n < 1:
+        raise ValueError("offsets must hold n_rows + 1 >= 1 entries")
+    rows = ob.n - 1
+    if rows > 2 ** 31 or pb.n > 2 ** 31:
+        raise ValueError("at most 2^31 rows and 2^31 runs per call, got %d and %d" % (rows, pb.n))
+    toff, tptr = alloc(ob, rows + 1, np.uint64, zero=True)
+    if rows == 0 or pb.n == 0:      # nothing to queue: the zeroed offsets are the answer
+        return toff, alloc(ob, 0, np.uint8)[0]
+    fn, n, stream = K.lib().kh_cigar_text, C.c_uint64(), stream_of(ob, device)
+    args = (ob.ptr, rows, pb.ptr, pb.n, ob.where, tptr)
+    check(fn(*args, None, 0, C.byref(n), device, stream), "kh_cigar_text")
+    text, xptr = alloc(ob, n.value, np.uint8)
+    if n.value:
+        check(fn(*args, xptr, n.value, C.byref(n), device, stream), "kh_cigar_text")
+    return toff, text
+
+
+def paf_lines(mapping, text_offsets, text, read_names, ref_name, ref_len, k, ref_start=0, kept_only=True):
+    """the formatting half of write_paf() (host only): the columns of a Mapping and the text CSR of its record rows -> (lines, skipped)"""
+    t, sel, rec = mapping.table, mapping.select, mapping.records
+    seg, rev, count, score = _host(t.seg, np.uint32), _host(t.rev, np.uint8), _host(t.count, np.uint32), _host(t.score, np.int32)
+    flag, mapq, sub = _host(sel.flag, np.uint8), _host(sel.mapq, np.uint8), _host(sel.sub, np.int32)
+    valid = _host(rec.valid, np.uint8)
+    cols = [_host(x, np.uint32) for x in (rec.qlen, rec.qs, rec.qe, rec.rs, rec.re, rec.n_match, rec.n_block, rec.nm)]
+    toff, raw = _host(text_offsets, np.int64), _host(text, np.uint8).tobytes().decode("ascii")
+    lines, skipped = [], 0
+    for c in range(len(valid)):
+        if kept_only and not flag[c] & FLAG_KEPT:
+            continue
+        if not valid[c]:
+            skipped += 1
+            continue
+        qlen, qs, qe, rs, re_, n_match, n_block, nm = (int(x[c]) for x in cols)
+        pri = bool(flag[c] & FLAG_PRIMARY)
+        f = [str(read_names[int(seg[c])]), qlen, qs, qe, "-" if rev[c] & 1 else "+", str(ref_name), int(ref_len), rs - int(ref_start), re_ - int(ref_start), n_match, n_block,
+             int(mapq[c]), "tp:A:%s" % ("P" if pri else "S"), "cm:i:%d" % int(count[c]), "s1:i:%d" % int(score[c])]
+        if pri:
+            f.append("s2:i:%d" % int(sub[c]))
+        f += ["NM:i:%d" % nm, "cg:Z:%s" % raw[toff[c]:toff[c + 1]]]
+        lines.append("\t".join(str(x) for x in f))
+    return lines, skipped
+
+
+def write_paf(fh, mapping, read_names, ref_name, ref_len, k, ref_start=0, kept_only=True, device=0):
+    """the rows of a Mapping (index.map) as PAF lines into the text file `fh`: one cigar_text() call over the records, one copy of every
+    column to the host, then one line per row -- qname qlen qs qe strand tname tlen rs-ref_start re-ref_start n_match n_block mapq,
+    then tp:A:P|S, cm:i:<anchors>, s1:i:<chain score>, s2:i:<best secondary score> (primaries only), NM:i:<edits>, cg:Z:<CIGAR>.
+    read_names[s]: the name of read s; one target (ref_name, ref_len) whose base 0 is reference coordinate ref_start.  kept_only: only
+    the rows select kept (flag bit 1).  Rows without a whole alignment (valid == 0) are skipped.  Make the Mapping with ref_order=True:
+    PAF wants the CIGAR of a reverse-strand row in reference order.  -> (lines written, rows skipped as invalid)"""
+    toff, text = cigar_text(mapping.records.offsets, mapping.records.ops, device)
+    lines, skipped = paf_lines(mapping, toff, text, read_names, ref_name, ref_len, k, ref_start, kept_only)
+    for ln in lines:
+        fh.write(ln + "\n")
+    return len(lines), skipped
+
+
 class KmerCounter:
     """counting index: k-mer -> number of occurrences (Reducer = std::plus, value 1 per occurrence)"""
 
