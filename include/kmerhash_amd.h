@@ -978,6 +978,48 @@ kh_status kh_cigar_text(const uint64_t* offsets /*[h|d] u64[n_rows+1]*/, uint64_
                         uint64_t* out_offsets /*[n_rows + 1]*/, uint8_t* out_text /*[cap_text] or NULL*/, uint64_t cap_text, uint64_t* n_text,
                         int device, void* hip_stream);
 
+/* ---- anchors by target.  A reference of several sequences (contigs, chromosomes, transcripts) is indexed as ONE text in which the
+ *      targets are separated by spacers of at least 32 bytes that are no base: a non-base byte matches nothing (kh_chain_edits), so a
+ *      spacer costs at least 32 edits, more than max_edits can be (31) -- neither a chain link nor an end extension crosses one.  What
+ *      is left is the chaining DP, which reads no text: kh_anchor_targets regroups the anchors of every segment (read) by the target
+ *      they fall in, and the (segment, target) groups it returns are the segments to hand to kh_chain_anchors.  "Chains never cross a
+ *      segment boundary" then reads "chains never cross a target".  Integers only.
+ *      Inputs: the anchors qpos, rpos, rev [m] and the segment CSR seg_offsets [n_seg + 1] (NULL: one segment [0, m)) as
+ *      kh_chain_anchors takes them; the target table t_start, t_end [n_t] -- target t covers the reference coordinates
+ *      [t_start[t], t_end[t]), ascending and disjoint in a well-formed table; the seed length k.
+ *      Target of an anchor.  With r = rpos[i]:
+ *        lo = 0; hi = n_t; while (lo < hi) { mid = (lo + hi) >> 1; if (t_start[mid] <= r) lo = mid + 1; else hi = mid; }
+ *      ub = lo (the plain upper bound of r in t_start) and t = ub - 1.  tid(i) = t iff t >= 0 and r < 2^31 and r + k <= t_end[t];
+ *      otherwise tid(i) = KH_TARGET_NONE: the seed starts before every target, in a spacer, or runs over its target's end.  The table
+ *      is not validated: an unsorted table gives the ids this loop gives, and never an access outside [0, n_t).
+ *      Order.  Segment s is clamped as kh_chain_anchors clamps it: a = min(seg_offsets[s], m), b = max(a, min(seg_offsets[s + 1], m)).
+ *      The output is the input sorted by (segment, tid, input index); KH_TARGET_NONE is the largest id, so those anchors stand last in
+ *      their segment.  out_src[j] = the input index of output anchor j; out_q[j], out_r[j], out_v[j], out_tid[j] = qpos, rpos, rev
+ *      and tid of that anchor, except that out_r[j] = KH_POS_INVALID where the id is KH_TARGET_NONE -- the DP never links such an
+ *      anchor.  A segment whose anchors all have one id keeps its order: for a reference of one target the regrouping is the identity.
+ *      Groups.  The groups are the maximal runs of equal (segment, tid) of the output, in order: group g is the output anchors
+ *      [g_offsets[g], g_offsets[g + 1]) with g_offsets[0] = 0 and g_offsets[*n_grp] = m, g_seg[g] its segment and g_tid[g] its id
+ *      (KH_TARGET_NONE for the group of the anchors without a target).  A segment without anchors has no group.  *n_grp <= m.
+ *      All arrays live in the memory `where` names.  Device memory: every kernel is queued on hip_stream and the call waits once, to
+ *      learn *n_grp.  Host memory: staged, the call synchronises.
+ *      seg_offsets that do not ascend from 0 to m are seen on the device only: KH_ERR_INVALID after the kernels have run, with
+ *      *n_grp = 0 and unspecified output contents; nothing outside the arrays is touched.
+ *      KH_ERR_INVALID before anything is allocated, read or written: k outside 1..64, m > 2^24, n_t outside 1..2^24,
+ *      n_seg > m + 2^24 or n_seg == 0 with seg_offsets given and m > 0, `where` outside the enum, a null g_offsets or n_grp, and while
+ *      m > 0 a null input, table or output array.  m == 0: KH_OK, *n_grp = 0, g_offsets[0] = 0 (host memory: without a device).
+ *      Route (kh_kernels_targets.h): one lane per anchor searches the table -- staged in LDS once per workgroup while
+ *      n_t <= KH_TARGETS_STAGED_MAX (8192 targets: 64 KiB), through L2 beyond; then one wavefront per segment takes the smallest
+ *      unplaced id, ballots the lanes that hold it and places them behind the running offset, one step per distinct id -- run twice,
+ *      to count the groups and to write. */
+#define KH_TARGET_NONE 0xFFFFFFFFu
+#define KH_TARGETS_STAGED_MAX 8192u
+kh_status kh_anchor_targets(const uint32_t* qpos /*[h|d] u32[m]*/, const uint32_t* rpos, const uint8_t* rev, uint64_t m,
+                            const uint64_t* seg_offsets /*[n_seg+1] or NULL: one segment*/, uint64_t n_seg,
+                            const uint32_t* t_start, const uint32_t* t_end /* each [n_t] */, uint64_t n_t, uint32_t k /*1..64*/, kh_mem where,
+                            uint32_t* out_q, uint32_t* out_r, uint8_t* out_v, uint32_t* out_tid, uint32_t* out_src /* each [m] */,
+                            uint64_t* g_offsets /*[m+1]*/, uint32_t* g_seg /*[m]*/, uint32_t* g_tid /*[m]*/, uint64_t* n_grp,
+                            int device, void* hip_stream);
+
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);
 

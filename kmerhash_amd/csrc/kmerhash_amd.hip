@@ -19,6 +19,7 @@
 //   cigars  : kh_chain_cigars, the alignment operations of every link as run-length rows of a CSR: the same wavefront pass with a traceback (kh_kernels_cigar.h).
 //   select  : kh_chain_select, primary / secondary chains per read and a mapping quality: a wavefront per read, a workgroup for a read of more than 64 chains (kh_kernels_select.h).
 //   records : kh_chain_records, one run-length row and one line of numbers per chain from the link rows, end rows and clips: a wavefront per chain; kh_cigar_text, a run CSR as text (kh_kernels_records.h).
+//   targets : kh_anchor_targets, the anchors of every read regrouped by the target (contig) they fall in: a lane per anchor, then a wavefront per read (kh_kernels_targets.h).
 //   ends    : kh_chain_ends, both ends of every kept chain extended to the ends of its read or to a soft clip: a wavefront per end, target free, stop by score (kh_kernels_ends.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
@@ -32,6 +33,7 @@
 #include "kh_kernels_ends.h"
 #include "kh_kernels_select.h"
 #include "kh_kernels_records.h"
+#include "kh_kernels_targets.h"
 #include "kh_part_sizing.h"
 #include "kh_scratch.h"
 #include "../../include/kmerhash_amd.h"
@@ -4486,5 +4488,66 @@ kh_status kh_cigar_text(const uint64_t* offsets, uint64_t n_rows, const uint32_t
   s.launched();
   s.copy_back(dtext, total);
   return s.finish_queued();
+}
+// ---- the anchors of every segment regrouped by target (kernels: kh_kernels_targets.h).  No handle; one pooled block holds the ids, the
+//      group counts and the scan's workspace (and the staged arrays of a host call).  Everything is queued on the caller's stream; the
+//      one host wait is the one that learns *n_grp.
+static_assert(KTG_NONE == KH_TARGET_NONE && KTG_NONE == KH_POS_INVALID, "one word for no target and no position");
+kh_status kh_anchor_targets(const uint32_t* qpos, const uint32_t* rpos, const uint8_t* rev, uint64_t m, const uint64_t* seg_offsets, uint64_t n_seg,
+                            const uint32_t* t_start, const uint32_t* t_end, uint64_t n_t, uint32_t k, kh_mem where, uint32_t* out_q, uint32_t* out_r, uint8_t* out_v,
+                            uint32_t* out_tid, uint32_t* out_src, uint64_t* g_offsets, uint32_t* g_seg, uint32_t* g_tid, uint64_t* n_grp, int device, void* stream_) {
+  if (k < 1 || k > 64 || m > (uint64_t(1) << 24) || n_t < 1 || n_t > (uint64_t(1) << 24)) return KH_ERR_INVALID;
+  if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !g_offsets || !n_grp) return KH_ERR_INVALID;
+  if (seg_offsets && (n_seg > m + (uint64_t(1) << 24) || (n_seg == 0 && m))) return KH_ERR_INVALID;
+  if (m && (!qpos || !rpos || !rev || !t_start || !t_end || !out_q || !out_r || !out_v || !out_tid || !out_src || !g_seg || !g_tid)) return KH_ERR_INVALID;
+  *n_grp = 0;
+  if (m == 0 && where == KH_MEM_HOST) { g_offsets[0] = 0; return KH_OK; }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK0(hipSetDevice(device));
+  if (m == 0) { HIPCHK0(hipMemsetAsync(g_offsets, 0, sizeof(uint64_t), stream)); return KH_OK; }
+  const uint64_t ns = seg_offsets ? n_seg : 1, nst = (ns + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
+  Scratch s(device, stream);
+  uint32_t *tid = nullptr, *counts = nullptr, *bad = nullptr; uint64_t* first_grp = nullptr; unsigned long long* ssums = nullptr;
+  const uint32_t *ts = nullptr, *te = nullptr;
+  KtgIn P{};
+  KtgOut O{};
+  if (!s.layout([&](Scratch& c) {
+        tid = c.take<uint32_t>(m); counts = c.take<uint32_t>(ns); first_grp = c.take<uint64_t>(ns + 1); ssums = c.take<unsigned long long>(nst + 1);
+        bad = c.take<uint32_t>(1);
+        P.qpos = c.in(qpos, m, where); P.rpos = c.in(rpos, m, where); P.rev = c.in(rev, m, where);
+        P.seg = c.in(seg_offsets, seg_offsets ? n_seg + 1 : 0, where);
+        ts = c.in(t_start, n_t, where); te = c.in(t_end, n_t, where);
+        O.q = c.out(out_q, m, where); O.r = c.out(out_r, m, where); O.v = c.out(out_v, m, where); O.tid = c.out(out_tid, m, where); O.src = c.out(out_src, m, where);
+        O.g_off = c.out(g_offsets, m + 1, where); O.g_seg = c.out(g_seg, m, where); O.g_tid = c.out(g_tid, m, where);
+      })) return s.finish();
+  s.zero(bad, sizeof(uint32_t));
+  P.m = (uint32_t)m; P.n_seg = (uint32_t)n_seg;
+  const uint32_t ncu = (uint32_t)cu_count(device), gseg = grid_for(ns, KTG_WAVES, ncu * 8);
+  if (n_t <= KH_TARGETS_STAGED_MAX) {
+    // both tables in LDS, 8 n_t bytes per workgroup: as many workgroups per CU as 160 KiB hold, at most 8
+    const size_t lds = (size_t)n_t * 2 * sizeof(uint32_t);
+    const uint32_t per_cu = (uint32_t)std::min<size_t>(8, (size_t(160) << 10) / lds);
+    hipLaunchKernelGGL((k_target_find<true>), dim3(grid_for(m, KTG_THREADS, ncu * per_cu)), dim3(KTG_THREADS), lds, stream, P.rpos, P.m, ts, te, (uint32_t)n_t, k, tid);
+  } else {
+    hipLaunchKernelGGL((k_target_find<false>), dim3(grid_for(m, KTG_THREADS, ncu * 8)), dim3(KTG_THREADS), 0, stream, P.rpos, P.m, ts, te, (uint32_t)n_t, k, tid);
+  }
+  hipLaunchKernelGGL((k_target_group<false>), dim3(gseg), dim3(KTG_THREADS), 0, stream, P, (const uint32_t*)tid, counts, (const uint64_t*)first_grp, bad, O);
+  scan_counts(stream, (const uint32_t*)counts, ns, ssums, first_grp);
+  hipLaunchKernelGGL((k_target_group<true>), dim3(gseg), dim3(KTG_THREADS), 0, stream, P, (const uint32_t*)tid, counts, (const uint64_t*)first_grp, bad, O);
+  s.launched();
+  unsigned long long total = 0;
+  uint32_t hbad = 0;
+  s.read(&total, (const unsigned long long*)(ssums + nst));
+  s.read(&hbad, (const uint32_t*)bad);
+  s.sync();      // the one host wait of a device call: *n_grp
+  if (s.ok() && !hbad && total <= m) {
+    s.copy_back(O.q, m); s.copy_back(O.r, m); s.copy_back(O.v, m); s.copy_back(O.tid, m); s.copy_back(O.src, m);
+    s.copy_back(O.g_off, total + 1); s.copy_back(O.g_seg, total); s.copy_back(O.g_tid, total);
+  }
+  const kh_status fs = s.finish();
+  if (fs != KH_OK) return fs;
+  if (hbad || total > m) return KH_ERR_INVALID;
+  *n_grp = total;
+  return KH_OK;
 }
 }  // extern "C"

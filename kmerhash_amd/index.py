@@ -11,7 +11,8 @@ import ctypes as C
 import numpy as np
 
 from ._call import HOST, _Buf, _Handle, alloc, check_same, torch
-from .kmers import Mapping, anchors_from_csr, chain_anchors, chain_cigars, chain_edits, chain_ends, chain_records, select_table, stamp_strand
+from .kmers import Mapping, anchors_from_csr, chain_anchors, chain_cigars, chain_edits, chain_ends, chain_records, group_anchors, select_table, stamp_strand
+from .targets import Targets
 from .seqs import is_syncmer, is_syncmer128, kmers_from_sequence, minimizers_from_sequence, syncmers128_from_sequence, syncmers_from_sequence
 from .table import _hash_id
 
@@ -20,6 +21,20 @@ from .table import _hash_id
 SORT_TILE = 4096
 
 ChainTable = collections.namedtuple("ChainTable", "seg rev q_start q_end r_start r_end count score anchors chain")
+
+
+def _check_targets_text(targets, ref_text, ref_base, max_edits):
+    """the refusals of the calls that read the reference text of a multi-target index: the text must be the one the Targets lay out, from
+    coordinate 0, and no alignment may afford a spacer"""
+    if not isinstance(targets, Targets):
+        raise ValueError("targets must be a kmerhash_amd.Targets where the reference text is read, got %r" % (type(targets).__name__,))
+    if targets.spacer <= int(max_edits):
+        raise ValueError("the spacer between targets (%d) must exceed max_edits (%r): an alignment could cross it" % (targets.spacer, max_edits))
+    if int(ref_base) != 0:
+        raise ValueError("ref_base must be 0 with targets (their coordinates are those of the whole text), got %r" % (ref_base,))
+    n = _Buf.text(ref_text).n
+    if n != int(targets.ends[-1]):
+        raise ValueError("ref_text must be the text the targets lay out (%d bytes), got %d" % (int(targets.ends[-1]), n))
 
 
 class KmerPositionIndex(_Handle):
@@ -239,24 +254,37 @@ class KmerPositionIndex(_Handle):
         offsets, positions = self.find(km)
         return anchors_from_csr(sq, offsets, positions, self.device)
 
-    def chains(self, seq, read_starts=None, **params):
+    def anchor_groups(self, seq, read_starts=None, targets=None):
+        """anchors(seq), then kmers.group_anchors: the anchors of every read (read_starts as chains() takes them; None: one read)
+        regrouped by the target they fall in -> AnchorGroups.  targets: a kmerhash_amd.Targets (or a (starts, ends) pair)."""
+        if not self.stranded:
+            raise ValueError("anchor_groups() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        if targets is None:
+            raise ValueError("anchor_groups() needs targets=")
+        q, r, v = self.anchors(seq)
+        return group_anchors(q, r, v, targets, self.k, self._read_segments(q, read_starts), self.device)
+
+    def chains(self, seq, read_starts=None, targets=None, **params):
         """candidate loci of the reads in a query text on a stranded index: anchors(seq), then collinear chains per read on the device
         (kmers.chain_anchors with the index's k; params: lookback, max_gap, band, min_score, min_count).  read_starts: ascending byte
         offsets of the reads in `seq`, the first one 0 (None: one read); a chain never holds anchors of two reads.
         -> ChainTable(seg, rev, q_start, q_end, r_start, r_end, count, score, anchors, chain): one row per kept chain -- its read, its
         strand, the query interval [q_start, q_end) and the reference interval [r_start, r_end) its first and last anchor span, its
         number of anchors and its score -- then anchors = (qpos, rpos, rev) as anchors() returns them and chain[j] = the row of anchor
-        j or -1.  numpy in, numpy out; a CUDA tensor in, tensors out on the current stream."""
+        j or -1.  numpy in, numpy out; a CUDA tensor in, tensors out on the current stream.
+        targets: a kmerhash_amd.Targets when the index holds several sequences laid out by it (build_sequences(targets.text)): the
+        anchors of every read are first regrouped by target (kmers.group_anchors) and chained per (read, target), so no chain crosses a
+        contig; `anchors` are then the regrouped ones, seg stays the read, and targets.locate(r_start) names a row's target.  None:
+        exactly the calls of an index of one sequence."""
         if not self.stranded:
             raise ValueError("chains() needs an index made with stranded=True: without the strand bit a hit has no orientation")
-        return self._chains(seq, read_starts, params)[0]
+        return self._chains(seq, read_starts, params, targets)[0]
 
-    def _chains(self, seq, read_starts, params):
-        """the body of chains(): -> (ChainTable, the Chains chain_anchors returned: pred per anchor, first and last anchor per chain)"""
-        q, r, v = self.anchors(seq)
+    def _read_segments(self, q, read_starts):
+        """the segment CSR of the reads over the anchors' query positions q (None: one read, no CSR)"""
         dev = torch is not None and isinstance(q, torch.Tensor)
         if read_starts is None:
-            seg, rs = None, None
+            seg = None
         else:
             rs = np.asarray(read_starts.cpu() if torch is not None and isinstance(read_starts, torch.Tensor) else read_starts, dtype=np.int64).ravel()
             if rs.size == 0 or rs[0] != 0 or (np.diff(rs) < 0).any():
@@ -266,64 +294,87 @@ class KmerPositionIndex(_Handle):
                 seg = torch.cat([torch.searchsorted(q.long(), torch.from_numpy(rs).to(q.device)), torch.tensor([q.numel()], dtype=torch.int64, device=q.device)])
             else:
                 seg = np.concatenate([np.searchsorted(q, rs, side="left"), [len(q)]]).astype(np.uint64)
+        return seg
+
+    def _chains(self, seq, read_starts, params, targets=None):
+        """the body of chains(): -> (ChainTable, the Chains chain_anchors returned: pred per anchor, first and last anchor per chain)"""
+        q, r, v = self.anchors(seq)
+        dev = torch is not None and isinstance(q, torch.Tensor)
+        seg = self._read_segments(q, read_starts)
+        groups = None
+        if targets is not None:      # chain per (read, target): the group CSR takes the place of the read CSR
+            groups = group_anchors(q, r, v, targets, self.k, seg, self.device)
+            q, r, v, seg = groups.qpos, groups.rpos, groups.rev, groups.offsets
         c = chain_anchors(q, r, v, self.k, seg, device=self.device, **params)
         if dev:
             first, last = c.first.long(), c.last.long()
             qf, ql, rf, rl = q[first], q[last], r[first], r[last]
             sg = torch.zeros_like(c.first) if seg is None else (torch.searchsorted(seg, first, right=True) - 1).int()
+            if groups is not None:
+                sg = groups.seg[sg.long()]
             rows = (sg, v[first], qf, ql + self.k, torch.minimum(rf, rl), torch.maximum(rf, rl) + self.k, c.count, c.cscore)
         else:
             first, last = c.first.astype(np.int64), c.last.astype(np.int64)
             qf, ql, rf, rl = q[first], q[last], r[first], r[last]
             sg = np.zeros(len(first), dtype=np.uint32) if seg is None else (np.searchsorted(seg, first.astype(np.uint64), side="right") - 1).astype(np.uint32)
+            if groups is not None:
+                sg = groups.seg[sg.astype(np.int64)]
             rows = (sg, v[first], qf, ql + np.uint32(self.k), np.minimum(rf, rl), np.maximum(rf, rl) + np.uint32(self.k), c.count, c.cscore)
         return ChainTable(*rows, (q, r, v), c.chain), c
 
-    def chain_edits(self, seq, ref_text, read_starts=None, ref_base=0, max_edits=31, **params):
+    def chain_edits(self, seq, ref_text, read_starts=None, ref_base=0, max_edits=31, targets=None, **params):
         """chains(seq, read_starts, **params), then every kept chain verified against the texts on the device: kmers.chain_edits over the
         chains' own anchors, with `seq` as the query text and ref_text as the text the index was built from -- the index keeps none;
         ref_text covers the indexed positions [ref_base, ref_base + len(ref_text)) and lives where seq lives.
         -> (ChainTable, ChainEdits(link, edits, over)): the table of chains(), the edit distance per anchor link (-1: no link, -2: outside
         the texts or more than max_edits, 0..31) and, per row of the table, the sum of its links' distances and the number of its -2
-        links.  The chain's last seed adds k matching bases and no edits."""
+        links.  The chain's last seed adds k matching bases and no edits.
+        targets: as for chains(); ref_text must then be targets.text (or a copy where seq lives) with ref_base 0."""
         if not self.stranded:
             raise ValueError("chain_edits() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        if targets is not None:
+            _check_targets_text(targets, ref_text, ref_base, max_edits)
         seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to two calls)
-        table, c = self._chains(seq, read_starts, params)
+        table, c = self._chains(seq, read_starts, params, targets)
         q, r, v = table.anchors
         n_chains = int(table.count.numel() if torch is not None and isinstance(table.count, torch.Tensor) else len(table.count))
         return table, chain_edits(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
 
-    def chain_cigars(self, seq, ref_text, read_starts=None, ref_base=0, max_edits=31, **params):
+    def chain_cigars(self, seq, ref_text, read_starts=None, ref_base=0, max_edits=31, targets=None, **params):
         """chain_edits(seq, ref_text, ...), then the alignment behind every distance: kmers.chain_cigars over the same anchors and texts
         with the link array chain_edits wrote -> (ChainTable, ChainEdits, ChainCigars(offsets, ops, ins, dels)): a CSR of run-length rows in
         anchor order and the inserted and deleted bases per row of the table.  kmers.cigar_string(cigars, table, row, k) is the CIGAR
-        of one chain as text."""
+        of one chain as text.  targets: as for chain_edits()."""
         if not self.stranded:
             raise ValueError("chain_cigars() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        if targets is not None:
+            _check_targets_text(targets, ref_text, ref_base, max_edits)
         seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to three calls)
-        table, c = self._chains(seq, read_starts, params)
+        table, c = self._chains(seq, read_starts, params, targets)
         q, r, v = table.anchors
         n_chains = int(table.count.numel() if torch is not None and isinstance(table.count, torch.Tensor) else len(table.count))
         edits = chain_edits(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
         return table, edits, chain_cigars(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, edits.link, ref_base, self.device)
 
-    def chain_ends(self, seq, ref_text, read_starts=None, read_ends=None, ref_base=0, max_edits=31, clip_cost=4, **params):
+    def chain_ends(self, seq, ref_text, read_starts=None, read_ends=None, ref_base=0, max_edits=31, clip_cost=4, targets=None, **params):
         """chain_cigars(seq, ref_text, ...), then both ends of every chain extended to the ends of its read or to a soft clip:
         kmers.chain_ends over the same anchors and texts, with the chains' first and last anchors and the byte interval of each chain's
         read -- [read_starts[seg], read_ends[seg]); read_ends defaults to the next read's start and len(seq) for the last read, so give
         it where the reads are separated by bytes that belong to none of them.
         -> (ChainTable, ChainEdits, ChainCigars, ChainEnds(q, r, edits, clip, offsets, ops)): rows 2c and 2c + 1 of the ends are the head
         and tail of row c of the table.  kmers.read_cigar(cigars, ends, table, row, k) is the CIGAR of a whole read,
-        kmers.extended_intervals(table, ends) the intervals it maps."""
+        kmers.extended_intervals(table, ends) the intervals it maps.  targets: as for chain_edits(); an end never runs into a spacer:
+        every spacer byte costs clip_cost and gains nothing."""
         if not self.stranded:
             raise ValueError("chain_ends() needs an index made with stranded=True: without the strand bit a hit has no orientation")
-        return self._ends(seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, params)[:4]
+        return self._ends(seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, params, targets)[:4]
 
-    def _ends(self, seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, params):
+    def _ends(self, seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, params, targets=None):
         """the body of chain_ends(): -> (ChainTable, ChainEdits, ChainCigars, ChainEnds, the Chains of chain_anchors, q_lo, q_hi per chain)"""
+        if targets is not None:
+            _check_targets_text(targets, ref_text, ref_base, max_edits)
         seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to four calls)
-        table, c = self._chains(seq, read_starts, params)
+        table, c = self._chains(seq, read_starts, params, targets)
         q, r, v = table.anchors
         dev = torch is not None and isinstance(q, torch.Tensor)
         n_chains = int(table.count.numel() if dev else len(table.count))
@@ -348,15 +399,17 @@ class KmerPositionIndex(_Handle):
         return table, edits, cigars, ends, c, lo, hi
 
     def map(self, seq, ref_text, read_starts=None, read_ends=None, ref_base=0, max_edits=31, clip_cost=4, mask_pct=50, pri_pct=80, best_n=5, ref_order=True,
-            **params):
+            targets=None, **params):
         """the whole mapper in one call: chain_ends(seq, ref_text, ...), kmers.select_table over its table with one group per read, and
         kmers.chain_records over all of it -> Mapping(table, edits, cigars, ends, select, records): row c of table, select and records is
         one candidate alignment -- its read, strand and intervals, whether it is the read's primary and how sure, and its CIGAR as a
         row of runs with the PAF numbers beside it.  ref_order (default True): the CIGAR rows of reverse-strand chains run in reference
-        order, as PAF and SAM want them; False gives read order, what kmers.read_cigar() prints.  kmers.write_paf() writes the lines."""
+        order, as PAF and SAM want them; False gives read order, what kmers.read_cigar() prints.  kmers.write_paf() writes the lines.
+        targets: a kmerhash_amd.Targets for an index of several sequences (see chains()); ref_text is then targets.text, the rows of one
+        read on different targets compete in select, and write_paf(..., targets=targets) names each row's target."""
         if not self.stranded:
             raise ValueError("map() needs an index made with stranded=True: without the strand bit a hit has no orientation")
-        table, edits, cigars, ends, c, lo, hi = self._ends(seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, params)
+        table, edits, cigars, ends, c, lo, hi = self._ends(seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, params, targets)
         select = select_table(table, 1 if read_starts is None else len(read_starts), mask_pct=mask_pct, pri_pct=pri_pct, best_n=best_n, device=self.device)
         q, r, v = table.anchors
         records = chain_records(q, r, v, table.chain, cigars, c.first, c.last, lo, hi, ends, self.k, ref_order, self.device)
@@ -366,10 +419,12 @@ class KmerPositionIndex(_Handle):
         """chains(seq, read_starts, **params), then which chain of every read is the answer: kmers.select_table over the table with one
         group per read -> (ChainTable, ChainSelect(parent, rank, mapq, flag, sub, nsub, best)): per row of the table its primary, its
         rank in its read, the mapping quality of a primary and the primary / kept flags; best[s] = the best row of read s, -1 for a read
-        without chains.  The score is the chaining score; kmers.select_chains takes any other."""
+        without chains.  The score is the chaining score; kmers.select_chains takes any other.  The keyword targets= (a
+        kmerhash_amd.Targets, see chains()) travels with params: the rows of a read on different targets then compete with each other."""
         if not self.stranded:
             raise ValueError("chain_select() needs an index made with stranded=True: without the strand bit a hit has no orientation")
-        table = self._chains(seq, read_starts, params)[0]
+        targets = params.pop("targets", None)
+        table = self._chains(seq, read_starts, params, targets)[0]
         return table, select_table(table, 1 if read_starts is None else len(read_starts), mask_pct=mask_pct, pri_pct=pri_pct, best_n=best_n, device=self.device)
 
     def _syncmers(self, seq, fastq=False):

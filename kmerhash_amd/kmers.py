@@ -16,6 +16,7 @@ from .hll import estimate_average_per_rank, hyperloglog64
 from .seqs import (is_syncmer, kmers128_from_fastq, kmers128_from_sequence, kmers_from_fastq, kmers_from_sequence,  # noqa: F401  (re-exported)
                    minimizers_from_fastq, minimizers_from_sequence, syncmers_from_fastq, syncmers_from_sequence)
 from .table import hashmap_robinhood_doubling
+from .targets import TARGET_NONE, Targets  # noqa: F401  (TARGET_NONE re-exported)
 from .wide import hashmap_robinhood_doubling_wide
 
 
@@ -134,6 +135,50 @@ def chain_anchors(qpos, rpos, rev, k, seg_offsets=None, lookback=64, max_gap=500
                                   *(ptr for _, ptr in outs), cap, C.byref(n), device, stream_of(qb, device))
     check(st, "kh_chain_anchors" + (": seg_offsets do not ascend from 0 to the number of anchors" if st == K.KH_ERR_INVALID else ""))
     return Chains(*(a for a, _ in outs[:3]), *(a[:n.value] for a, _ in outs[3:]))
+
+
+AnchorGroups = collections.namedtuple("AnchorGroups", "qpos rpos rev tid src offsets seg target")
+
+
+def group_anchors(qpos, rpos, rev, targets, k, seg_offsets=None, device=0):
+    """the anchors of every segment (read) regrouped by the target (contig) they fall in (kh_anchor_targets in include/kmerhash_amd.h,
+    which holds the definition).  targets: a kmerhash_amd.Targets, or a (starts, ends) pair of arrays that live where the anchors live;
+    an anchor belongs to target t iff its k bases lie inside [starts[t], ends[t]), to none (TARGET_NONE, 0xFFFFFFFF) otherwise.
+    -> AnchorGroups(qpos, rpos, rev, tid, src, offsets, seg, target): the anchors sorted by (segment, target, input index) with their
+    target ids and input indices (rpos = POS_INVALID where the id is TARGET_NONE: the chaining DP skips such an anchor), then the group
+    CSR -- group g is the anchors [offsets[g], offsets[g + 1]), all of segment seg[g] and target target[g].  Hand `offsets` to
+    chain_anchors as its seg_offsets and no chain crosses a target.  numpy in, numpy out (uint32, uint32, uint8, uint32, uint32, uint64,
+    uint32, uint32); CUDA tensors in, tensors out on the current stream (int32 holding the uint32 bits, int64 offsets); the call waits for
+    the stream once, to learn the number of groups.  At most 2^24 anchors and 2^24 targets per call."""
+    if not 1 <= int(k) <= 64:
+        raise ValueError("k must be 1..64, got %r" % (k,))
+    qb, rb, vb = _Buf(qpos, np.uint32), _Buf(rpos, np.uint32), _Buf(rev, np.uint8)
+    sb = None if seg_offsets is None else _Buf(seg_offsets, np.uint64)
+    if isinstance(targets, Targets):
+        starts, ends = targets.to(qb.device) if qb.dev else (targets.starts, targets.ends)
+    else:
+        starts, ends = targets
+    tsb, teb = _Buf(starts, np.uint32), _Buf(ends, np.uint32)
+    check_same("qpos, rpos, rev, seg_offsets and the target table must live in the same memory", qb, rb, vb, sb, tsb, teb, length=False)
+    m = qb.n
+    if rb.n != m or vb.n != m:
+        raise ValueError("qpos, rpos and rev must have one entry per anchor, got %d, %d and %d" % (m, rb.n, vb.n))
+    if m > 2 ** 24:
+        raise ValueError("at most 2^24 anchors per call (batch over reads), got %d" % m)
+    if not 1 <= tsb.n <= 2 ** 24 or teb.n != tsb.n:
+        raise ValueError("the target table must hold 1..2^24 targets, one start and one end each, got %d and %d" % (tsb.n, teb.n))
+    if sb is not None and (sb.n < 1 or sb.n - 1 > m + 2 ** 24 or (sb.n == 1 and m)):
+        raise ValueError("seg_offsets must hold n_seg + 1 entries ascending from 0 to the number of anchors, got %d entries for %d anchors" % (sb.n, m))
+    outs = [alloc(qb, m, dt, empty=True) for dt in (np.uint32, np.uint32, np.uint8, np.uint32, np.uint32)]
+    offs, optr = alloc(qb, m + 1, np.uint64, zero=not m)
+    (gseg, sptr), (gtid, tptr) = alloc(qb, m, np.uint32, empty=True), alloc(qb, m, np.uint32, empty=True)
+    n = C.c_uint64()
+    if m:
+        st = K.lib().kh_anchor_targets(qb.ptr, rb.ptr, vb.ptr, m, None if sb is None else sb.ptr, 0 if sb is None else sb.n - 1, tsb.ptr, teb.ptr, tsb.n, int(k),
+                                       qb.where, *(p for _, p in outs), optr, sptr, tptr, C.byref(n), device, stream_of(qb, device))
+        check(st, "kh_anchor_targets" + (": seg_offsets do not ascend from 0 to the number of anchors" if st == K.KH_ERR_INVALID else ""))
+    g = n.value
+    return AnchorGroups(*(a for a, _ in outs), offs[:g + 1], gseg[:g], gtid[:g])
 
 
 ChainEdits = collections.namedtuple("ChainEdits", "link edits over")
@@ -477,24 +522,36 @@ def cigar_text(offsets, ops, device=0):
     return toff, text
 
 
-def paf_lines(mapping, text_offsets, text, read_names, ref_name, ref_len, k, ref_start=0, kept_only=True):
+def paf_lines(mapping, text_offsets, text, read_names, ref_name=None, ref_len=None, k=None, ref_start=0, kept_only=True, targets=None):
     """the formatting half of write_paf() (host only): the columns of a Mapping and the text CSR of its record rows -> (lines, skipped)"""
+    if targets is not None:
+        if ref_name is not None or ref_len is not None or int(ref_start) != 0:
+            raise ValueError("with targets the names, lengths and starts are theirs: ref_name and ref_len must be None and ref_start 0")
+    elif ref_name is None or ref_len is None:
+        raise ValueError("ref_name and ref_len are needed without targets")
     t, sel, rec = mapping.table, mapping.select, mapping.records
     seg, rev, count, score = _host(t.seg, np.uint32), _host(t.rev, np.uint8), _host(t.count, np.uint32), _host(t.score, np.int32)
     flag, mapq, sub = _host(sel.flag, np.uint8), _host(sel.mapq, np.uint8), _host(sel.sub, np.int32)
     valid = _host(rec.valid, np.uint8)
     cols = [_host(x, np.uint32) for x in (rec.qlen, rec.qs, rec.qe, rec.rs, rec.re, rec.n_match, rec.n_block, rec.nm)]
     toff, raw = _host(text_offsets, np.int64), _host(text, np.uint8).tobytes().decode("ascii")
+    if targets is not None:      # a row's target is the one its first reference base lies in; its end must lie there too
+        tgt, local = targets.locate(cols[3])
+        inside = (tgt >= 0) & (cols[4].astype(np.int64) <= targets.ends.astype(np.int64)[np.maximum(tgt, 0)])
     lines, skipped = [], 0
     for c in range(len(valid)):
         if kept_only and not flag[c] & FLAG_KEPT:
             continue
-        if not valid[c]:
+        if not valid[c] or (targets is not None and not inside[c]):
             skipped += 1
             continue
         qlen, qs, qe, rs, re_, n_match, n_block, nm = (int(x[c]) for x in cols)
         pri = bool(flag[c] & FLAG_PRIMARY)
-        f = [str(read_names[int(seg[c])]), qlen, qs, qe, "-" if rev[c] & 1 else "+", str(ref_name), int(ref_len), rs - int(ref_start), re_ - int(ref_start), n_match, n_block,
+        if targets is None:
+            tname, tlen, t0 = str(ref_name), int(ref_len), int(ref_start)
+        else:
+            tname, tlen, t0 = targets.names[int(tgt[c])], int(targets.lengths[int(tgt[c])]), int(targets.starts[int(tgt[c])])
+        f = [str(read_names[int(seg[c])]), qlen, qs, qe, "-" if rev[c] & 1 else "+", tname, tlen, rs - t0, re_ - t0, n_match, n_block,
              int(mapq[c]), "tp:A:%s" % ("P" if pri else "S"), "cm:i:%d" % int(count[c]), "s1:i:%d" % int(score[c])]
         if pri:
             f.append("s2:i:%d" % int(sub[c]))
@@ -503,15 +560,18 @@ def paf_lines(mapping, text_offsets, text, read_names, ref_name, ref_len, k, ref
     return lines, skipped
 
 
-def write_paf(fh, mapping, read_names, ref_name, ref_len, k, ref_start=0, kept_only=True, device=0):
+def write_paf(fh, mapping, read_names, ref_name=None, ref_len=None, k=None, ref_start=0, kept_only=True, device=0, targets=None):
     """the rows of a Mapping (index.map) as PAF lines into the text file `fh`: one cigar_text() call over the records, one copy of every
     column to the host, then one line per row -- qname qlen qs qe strand tname tlen rs-ref_start re-ref_start n_match n_block mapq,
     then tp:A:P|S, cm:i:<anchors>, s1:i:<chain score>, s2:i:<best secondary score> (primaries only), NM:i:<edits>, cg:Z:<CIGAR>.
     read_names[s]: the name of read s; one target (ref_name, ref_len) whose base 0 is reference coordinate ref_start.  kept_only: only
     the rows select kept (flag bit 1).  Rows without a whole alignment (valid == 0) are skipped.  Make the Mapping with ref_order=True:
-    PAF wants the CIGAR of a reverse-strand row in reference order.  -> (lines written, rows skipped as invalid)"""
+    PAF wants the CIGAR of a reverse-strand row in reference order.  targets: the kmerhash_amd.Targets the Mapping was made with
+    (index.map(..., targets=T)) -- columns 6 to 9 are then the row's own target name, its length and the target-local interval, and
+    ref_name / ref_len / ref_start stay None / None / 0; a row whose interval does not lie inside one target counts as skipped.
+    -> (lines written, rows skipped as invalid)"""
     toff, text = cigar_text(mapping.records.offsets, mapping.records.ops, device)
-    lines, skipped = paf_lines(mapping, toff, text, read_names, ref_name, ref_len, k, ref_start, kept_only)
+    lines, skipped = paf_lines(mapping, toff, text, read_names, ref_name, ref_len, k, ref_start, kept_only, targets)
     for ln in lines:
         fh.write(ln + "\n")
     return len(lines), skipped
