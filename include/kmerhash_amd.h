@@ -1020,6 +1020,66 @@ kh_status kh_anchor_targets(const uint32_t* qpos /*[h|d] u32[m]*/, const uint32_
                             uint64_t* g_offsets /*[m+1]*/, uint32_t* g_seg /*[m]*/, uint32_t* g_tid /*[m]*/, uint64_t* n_grp,
                             int device, void* hip_stream);
 
+/* ---- the difference strings of alignment records.  The CIGAR of a record (kh_chain_records) says where its X, I and D runs are;
+ *      kh_record_diffs reads the two texts and says which bases they were: per row the short cs string (minimap2's cs:Z:) or the MD
+ *      string of SAM (MD:Z:).
+ *      Inputs: the two texts as kh_chain_edits takes them -- rtext covers the reference coordinates [ref_base, ref_base + nr); a run
+ *      CSR offsets [n_rows + 1], ops [n_ops] in the encoding of kh_chain_records, IN REFERENCE ORDER (the rows ref_order = 1 gives);
+ *      per row [n_rows]: valid (ChainRecords), rev (bit 0: the strand), the read's byte interval [q_lo, q_hi) as kh_chain_records
+ *      took it, and rs, the record's reference start.
+ *      Bases.  The code of a byte is that of kh_chain_edits: A/a = 0, C/c = 1, G/g = 2, T/t = 3, any other byte 4.  With
+ *      L = q_hi - q_lo the ORIENTED READ O of a row is  O[j] = code(qtext[q_lo + j])  on the forward strand and, with
+ *      c = code(qtext[q_hi - 1 - j]),  O[j] = 3 - c if c < 4, else 4  on the reverse strand.  R[r] = code(rtext[r - ref_base]).
+ *      The walk.  Row c is the runs [a, b), a = min(offsets[c], n_ops), b = min(offsets[c + 1], n_ops).  Cursors j = 0, r = rs[c]; the
+ *      runs in order; a run of length 0 is skipped (whatever its op); otherwise with l its length:  S (4): j += l;  '=' (7) consumes l
+ *      of both;  X (8) consumes l of both, base by base;  I (1) consumes l of O;  D (2) consumes l of R;  any other op code spoils the
+ *      row.
+ *      out_ok[c] = 1 iff  valid[c] != 0;  b > a;  q_lo <= q_hi <= nq;  no run spoils the row;  the walk ends with j = L;  every
+ *      reference base the walk consumes lies in [ref_base, ref_base + nr)  -- all sums in 64 bits -- and the row's text is shorter
+ *      than 2^32 bytes (no such text fits texts of at most 2^32 bases but one of X runs alone in cs).  Any other row has out_ok = 0
+ *      and an empty text.
+ *      KH_DIFF_CS, run by run:  '=' -> ':' and the decimal l;  X -> per base '*', "acgtn"[R], "acgtn"[O];  I -> '+' and l letters of
+ *      O;  D -> '-' and l letters of R;  S -> nothing.  A row of S runs alone is ok and empty.
+ *      KH_DIFF_MD keeps a counter n = 0 (u32, wrapping):  '=' adds l to n;  X -> per base the decimal n, "ACGTN"[R], n = 0;
+ *      D -> the decimal n, '^', l letters of R, n = 0;  I and S print nothing and leave n alone;  after the last run the decimal n.
+ *      So a row that starts or ends with an edit starts or ends with "0", two neighbouring edits have "0" between them, the matches on
+ *      both sides of an insertion make one number, and the text matches [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)*.
+ *      Output: a byte CSR, out_offsets [n_rows + 1] and out_text, under the conventions of kh_cigar_text: out_text == NULL counts only
+ *      -- out_ok, out_offsets and *n_text are written; more bytes than cap_text: KH_ERR_INVALID with *n_text set, out_ok and
+ *      out_offsets written and out_text untouched.  Device memory: everything is queued on hip_stream, one host wait per pass to learn
+ *      *n_text.  Host memory: staged, the call synchronises.  Garbage in any array yields empty or wrong rows; no element outside the
+ *      arrays is read or written.
+ *      KH_ERR_INVALID before anything is touched: kind > 1, n_rows or n_ops > 2^31, nq or nr > 2^32, `where` outside the enum, a null
+ *      out_offsets or n_text, and while n_rows > 0 a null offsets, per-row array or out_ok, a null ops while n_ops > 0 and a null text
+ *      of a length > 0.  n_rows == 0: KH_OK, *n_text = 0, out_offsets[0] = 0 (host memory: without a device).
+ *      Route (kh_kernels_sam.h): one wavefront per row, 64 runs per step; wave prefix sums give every lane its cursors and its byte
+ *      offset, a segmented wave sum the number in front of an MD edit; count, scan, emit. */
+#define KH_DIFF_CS 0u
+#define KH_DIFF_MD 1u
+kh_status kh_record_diffs(const void* qtext /*[h|d]*/, uint64_t nq, const void* rtext, uint64_t nr, uint32_t ref_base,
+                          const uint64_t* offsets /*[n_rows+1]*/, const uint32_t* ops /*[n_ops]*/, uint64_t n_ops,
+                          const uint8_t* valid, const uint8_t* rev, const uint32_t* q_lo, const uint32_t* q_hi, const uint32_t* rs /* each [n_rows] */,
+                          uint64_t n_rows, uint32_t kind /* KH_DIFF_CS | KH_DIFF_MD */, kh_mem where,
+                          uint8_t* out_ok /*[n_rows]*/, uint64_t* out_offsets /*[n_rows+1]*/, uint8_t* out_text /*[cap_text] or NULL*/, uint64_t cap_text,
+                          uint64_t* n_text, int device, void* hip_stream);
+
+/* ---- byte ranges of a text as rows in reference orientation: SEQ and QUAL of SAM.  Row c is text[a, b) with a = min(lo[c], n) and
+ *      b = min(hi[c], n), empty where b <= a.  Where bit 0 of rev[c] is clear the row is copied as it stands; where it is set it is
+ *      copied back to front, and with complement == 1 every byte of such a row goes through A<->T, C<->G, a<->t, c<->g -- every other
+ *      byte stays itself: N stays N, the case is kept.  complement == 0 reverses only (a quality string).
+ *      Output: a byte CSR whose offsets are the prefix sums of the row lengths, under the conventions of kh_record_diffs (count only
+ *      with out_text == NULL; KH_ERR_INVALID with *n_text set and out_offsets written when cap_text is too small; device memory:
+ *      queued on hip_stream, one host wait per pass; host memory: staged).
+ *      KH_ERR_INVALID before anything is touched: complement > 1, n_rows > 2^31, n > 2^32, `where` outside the enum, a null
+ *      out_offsets or n_text, and while n_rows > 0 a null lo, hi or rev and a null text while n > 0.  n_rows == 0: KH_OK,
+ *      *n_text = 0, out_offsets[0] = 0 (host memory: without a device).
+ *      Route: one lane per row for the lengths, the index's scan, then one wavefront per row that moves 8-byte words: a reversed
+ *      word is a byte swap and a SWAR complement. */
+kh_status kh_oriented_rows(const void* text /*[h|d]*/, uint64_t n, const uint32_t* lo, const uint32_t* hi, const uint8_t* rev /* each [n_rows] */, uint64_t n_rows,
+                           uint32_t complement /*0|1*/, kh_mem where,
+                           uint64_t* out_offsets /*[n_rows+1]*/, uint8_t* out_text /*[cap_text] or NULL*/, uint64_t cap_text, uint64_t* n_text,
+                           int device, void* hip_stream);
+
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);
 

@@ -14,6 +14,7 @@ from .kmers import select_chains, select_table, ChainSelect  # noqa: F401
 from .kmers import chain_records, cigar_text, write_paf, paf_lines, ChainRecords, Mapping  # noqa: F401
 from .kmers import group_anchors, AnchorGroups  # noqa: F401
 from .targets import Targets, TARGET_NONE  # noqa: F401
+from .sam import record_diffs, oriented_rows, sam_header, sam_lines, write_sam, RecordDiffs  # noqa: F401
 from .wide import syncmers128_from_sequence, syncmers128_from_fastq, is_syncmer128  # noqa: F401
 from .dist_index import ShardedKmerPositionIndex, IndexGpuBackend, WideIndexGpuBackend  # noqa: F401
 from . import workloads  # noqa: F401
@@ -26,4 +27,5 @@ __all__ = ["hashmap_robinhood_doubling", "hashmap_linearprobe_doubling", "hash_b
            "chain_edits", "chain_cigars", "cigar_string", "chain_ends", "read_cigar", "extended_intervals",
            "select_chains", "select_table", "ChainSelect",
            "chain_records", "cigar_text", "write_paf", "paf_lines", "ChainRecords", "Mapping",
-           "group_anchors", "AnchorGroups", "Targets", "TARGET_NONE"]
+           "group_anchors", "AnchorGroups", "Targets", "TARGET_NONE",
+           "record_diffs", "oriented_rows", "sam_header", "sam_lines", "write_sam", "RecordDiffs"]

@@ -20,6 +20,7 @@
 //   select  : kh_chain_select, primary / secondary chains per read and a mapping quality: a wavefront per read, a workgroup for a read of more than 64 chains (kh_kernels_select.h).
 //   records : kh_chain_records, one run-length row and one line of numbers per chain from the link rows, end rows and clips: a wavefront per chain; kh_cigar_text, a run CSR as text (kh_kernels_records.h).
 //   targets : kh_anchor_targets, the anchors of every read regrouped by the target (contig) they fall in: a lane per anchor, then a wavefront per read (kh_kernels_targets.h).
+//   sam     : kh_record_diffs, the cs or MD string of every record row: a wavefront per row along the two texts; kh_oriented_rows, byte ranges copied as they stand or back to front and complemented (kh_kernels_sam.h).
 //   ends    : kh_chain_ends, both ends of every kept chain extended to the ends of its read or to a soft clip: a wavefront per end, target free, stop by score (kh_kernels_ends.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
@@ -34,6 +35,7 @@
 #include "kh_kernels_select.h"
 #include "kh_kernels_records.h"
 #include "kh_kernels_targets.h"
+#include "kh_kernels_sam.h"
 #include "kh_part_sizing.h"
 #include "kh_scratch.h"
 #include "../../include/kmerhash_amd.h"
@@ -4549,5 +4551,91 @@ kh_status kh_anchor_targets(const uint32_t* qpos, const uint32_t* rpos, const ui
   if (hbad || total > m) return KH_ERR_INVALID;
   *n_grp = total;
   return KH_OK;
+}
+// ---- the cs or MD string of every record row (kernels: kh_kernels_sam.h).  The protocol of kh_cigar_text: count, scan, one host wait for
+//      *n_text, emit.  One pooled block holds the byte counts and the scan's tile sums (and the staged arrays of a host call), a second
+//      one the staged text of a host call.
+kh_status kh_record_diffs(const void* qtext, uint64_t nq, const void* rtext, uint64_t nr, uint32_t ref_base, const uint64_t* offsets, const uint32_t* ops, uint64_t n_ops,
+                          const uint8_t* valid, const uint8_t* rev, const uint32_t* q_lo, const uint32_t* q_hi, const uint32_t* rs, uint64_t n_rows, uint32_t kind,
+                          kh_mem where, uint8_t* out_ok, uint64_t* out_offsets, uint8_t* out_text, uint64_t cap_text, uint64_t* n_text, int device, void* stream_) {
+  const uint64_t lim = uint64_t(1) << 31, tlim = uint64_t(1) << 32;
+  if (kind > KH_DIFF_MD || n_rows > lim || n_ops > lim || nq > tlim || nr > tlim) return KH_ERR_INVALID;
+  if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !out_offsets || !n_text) return KH_ERR_INVALID;
+  if (n_rows && (!offsets || !valid || !rev || !q_lo || !q_hi || !rs || !out_ok || (n_ops && !ops) || (nq && !qtext) || (nr && !rtext))) return KH_ERR_INVALID;
+  *n_text = 0;
+  if (n_rows == 0 && where == KH_MEM_HOST) { out_offsets[0] = 0; return KH_OK; }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK0(hipSetDevice(device));
+  if (n_rows == 0) { HIPCHK0(hipMemsetAsync(out_offsets, 0, sizeof(uint64_t), stream)); return KH_OK; }
+  const uint64_t nst = (n_rows + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
+  Scratch s(device, stream);
+  uint32_t* bytes = nullptr; uint64_t* doff = nullptr; unsigned long long* ssums = nullptr; uint8_t *dok = nullptr, *dtext = nullptr;
+  KdfArgs P{};
+  if (!s.layout([&](Scratch& c) {
+        bytes = c.take<uint32_t>(n_rows); ssums = c.take<unsigned long long>(nst + 1);
+        P.qtext = c.in(static_cast<const uint8_t*>(qtext), nq, where); P.rtext = c.in(static_cast<const uint8_t*>(rtext), nr, where);
+        P.off = c.in(offsets, n_rows + 1, where); P.ops = c.in(ops, n_ops, where);
+        P.valid = c.in(valid, n_rows, where); P.rev = c.in(rev, n_rows, where); P.q_lo = c.in(q_lo, n_rows, where); P.q_hi = c.in(q_hi, n_rows, where);
+        P.rs = c.in(rs, n_rows, where);
+        dok = c.out(out_ok, n_rows, where); doff = c.out(out_offsets, n_rows + 1, where);
+      })) return s.finish();
+  P.nq = nq; P.nr = nr; P.n_ops = n_ops; P.ref_base = ref_base; P.n_rows = (uint32_t)n_rows;
+  const uint32_t ncu = (uint32_t)cu_count(device);
+  const dim3 grid(grid_for(n_rows, KDF_WAVES, ncu * 8));
+  if (kind == KH_DIFF_CS) hipLaunchKernelGGL((k_diffs_count<KDF_CS>), grid, dim3(KDF_THREADS), 0, stream, P, dok, bytes);
+  else hipLaunchKernelGGL((k_diffs_count<KDF_MD>), grid, dim3(KDF_THREADS), 0, stream, P, dok, bytes);
+  scan_counts(stream, (const uint32_t*)bytes, n_rows, ssums, doff);
+  s.launched();
+  unsigned long long total = 0;
+  s.read(&total, (const unsigned long long*)(ssums + nst));
+  s.copy_back(doff, n_rows + 1); s.copy_back(dok, n_rows);
+  if (!s.sync()) return s.finish();      // the one host wait of a device call: *n_text
+  *n_text = total;
+  if (!out_text || total == 0) return s.finish();
+  if (total > cap_text) { s.finish(); return KH_ERR_INVALID; }
+  if (!s.layout([&](Scratch& c) { dtext = c.out(out_text, total, where); })) return s.finish();
+  if (kind == KH_DIFF_CS) hipLaunchKernelGGL((k_diffs_emit<KDF_CS>), grid, dim3(KDF_THREADS), 0, stream, P, (const uint8_t*)dok, (const uint64_t*)doff, (uint64_t)total, dtext);
+  else hipLaunchKernelGGL((k_diffs_emit<KDF_MD>), grid, dim3(KDF_THREADS), 0, stream, P, (const uint8_t*)dok, (const uint64_t*)doff, (uint64_t)total, dtext);
+  s.launched();
+  s.copy_back(dtext, total);
+  return s.finish_queued();
+}
+// ---- byte ranges of a text as rows, reverse-strand rows back to front (kernels: kh_kernels_sam.h).  The same protocol.
+kh_status kh_oriented_rows(const void* text, uint64_t n, const uint32_t* lo, const uint32_t* hi, const uint8_t* rev, uint64_t n_rows, uint32_t complement, kh_mem where,
+                           uint64_t* out_offsets, uint8_t* out_text, uint64_t cap_text, uint64_t* n_text, int device, void* stream_) {
+  if (complement > 1 || n_rows > (uint64_t(1) << 31) || n > (uint64_t(1) << 32)) return KH_ERR_INVALID;
+  if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !out_offsets || !n_text) return KH_ERR_INVALID;
+  if (n_rows && (!lo || !hi || !rev || (n && !text))) return KH_ERR_INVALID;
+  *n_text = 0;
+  if (n_rows == 0 && where == KH_MEM_HOST) { out_offsets[0] = 0; return KH_OK; }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK0(hipSetDevice(device));
+  if (n_rows == 0) { HIPCHK0(hipMemsetAsync(out_offsets, 0, sizeof(uint64_t), stream)); return KH_OK; }
+  const uint64_t nst = (n_rows + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
+  Scratch s(device, stream);
+  uint32_t* len = nullptr; uint64_t* doff = nullptr; unsigned long long* ssums = nullptr; uint8_t* dtext = nullptr;
+  const uint8_t *din = nullptr, *drev = nullptr; const uint32_t *dlo = nullptr, *dhi = nullptr;
+  if (!s.layout([&](Scratch& c) {
+        len = c.take<uint32_t>(n_rows); ssums = c.take<unsigned long long>(nst + 1);
+        din = c.in(static_cast<const uint8_t*>(text), n, where); dlo = c.in(lo, n_rows, where); dhi = c.in(hi, n_rows, where); drev = c.in(rev, n_rows, where);
+        doff = c.out(out_offsets, n_rows + 1, where);
+      })) return s.finish();
+  const uint32_t ncu = (uint32_t)cu_count(device);
+  hipLaunchKernelGGL(k_orient_len, dim3(grid_for(n_rows, KOR_THREADS, ncu * 8)), dim3(KOR_THREADS), 0, stream, dlo, dhi, n_rows, n, len);
+  scan_counts(stream, (const uint32_t*)len, n_rows, ssums, doff);
+  s.launched();
+  unsigned long long total = 0;
+  s.read(&total, (const unsigned long long*)(ssums + nst));
+  s.copy_back(doff, n_rows + 1);
+  if (!s.sync()) return s.finish();      // the one host wait of a device call: *n_text
+  *n_text = total;
+  if (!out_text || total == 0) return s.finish();
+  if (total > cap_text) { s.finish(); return KH_ERR_INVALID; }
+  if (!s.layout([&](Scratch& c) { dtext = c.out(out_text, total, where); })) return s.finish();
+  hipLaunchKernelGGL(k_orient_copy, dim3(grid_for(n_rows, KOR_WAVES, ncu * 8)), dim3(KOR_THREADS), 0, stream, din, n, dlo, dhi, drev, (uint32_t)n_rows, complement,
+                     (const uint64_t*)doff, (uint64_t)total, dtext);
+  s.launched();
+  s.copy_back(dtext, total);
+  return s.finish_queued();
 }
 }  // extern "C"

@@ -522,8 +522,9 @@ def cigar_text(offsets, ops, device=0):
     return toff, text
 
 
-def paf_lines(mapping, text_offsets, text, read_names, ref_name=None, ref_len=None, k=None, ref_start=0, kept_only=True, targets=None):
-    """the formatting half of write_paf() (host only): the columns of a Mapping and the text CSR of its record rows -> (lines, skipped)"""
+def paf_lines(mapping, text_offsets, text, read_names, ref_name=None, ref_len=None, k=None, ref_start=0, kept_only=True, targets=None, cs=None):
+    """the formatting half of write_paf() (host only): the columns of a Mapping and the text CSR of its record rows -> (lines, skipped).
+    cs: a RecordDiffs of kind "cs" over the mapping's records (sam.record_diffs), printed as a trailing cs:Z: tag"""
     if targets is not None:
         if ref_name is not None or ref_len is not None or int(ref_start) != 0:
             raise ValueError("with targets the names, lengths and starts are theirs: ref_name and ref_len must be None and ref_start 0")
@@ -535,6 +536,8 @@ def paf_lines(mapping, text_offsets, text, read_names, ref_name=None, ref_len=No
     valid = _host(rec.valid, np.uint8)
     cols = [_host(x, np.uint32) for x in (rec.qlen, rec.qs, rec.qe, rec.rs, rec.re, rec.n_match, rec.n_block, rec.nm)]
     toff, raw = _host(text_offsets, np.int64), _host(text, np.uint8).tobytes().decode("ascii")
+    if cs is not None:
+        cs_off, cs_raw = _host(cs.offsets, np.int64), _host(cs.text, np.uint8).tobytes().decode("ascii")
     if targets is not None:      # a row's target is the one its first reference base lies in; its end must lie there too
         tgt, local = targets.locate(cols[3])
         inside = (tgt >= 0) & (cols[4].astype(np.int64) <= targets.ends.astype(np.int64)[np.maximum(tgt, 0)])
@@ -556,11 +559,13 @@ def paf_lines(mapping, text_offsets, text, read_names, ref_name=None, ref_len=No
         if pri:
             f.append("s2:i:%d" % int(sub[c]))
         f += ["NM:i:%d" % nm, "cg:Z:%s" % raw[toff[c]:toff[c + 1]]]
+        if cs is not None:
+            f.append("cs:Z:%s" % cs_raw[cs_off[c]:cs_off[c + 1]])
         lines.append("\t".join(str(x) for x in f))
     return lines, skipped
 
 
-def write_paf(fh, mapping, read_names, ref_name=None, ref_len=None, k=None, ref_start=0, kept_only=True, device=0, targets=None):
+def write_paf(fh, mapping, read_names, ref_name=None, ref_len=None, k=None, ref_start=0, kept_only=True, device=0, targets=None, cs=None):
     """the rows of a Mapping (index.map) as PAF lines into the text file `fh`: one cigar_text() call over the records, one copy of every
     column to the host, then one line per row -- qname qlen qs qe strand tname tlen rs-ref_start re-ref_start n_match n_block mapq,
     then tp:A:P|S, cm:i:<anchors>, s1:i:<chain score>, s2:i:<best secondary score> (primaries only), NM:i:<edits>, cg:Z:<CIGAR>.
@@ -569,9 +574,11 @@ def write_paf(fh, mapping, read_names, ref_name=None, ref_len=None, k=None, ref_
     PAF wants the CIGAR of a reverse-strand row in reference order.  targets: the kmerhash_amd.Targets the Mapping was made with
     (index.map(..., targets=T)) -- columns 6 to 9 are then the row's own target name, its length and the target-local interval, and
     ref_name / ref_len / ref_start stay None / None / 0; a row whose interval does not lie inside one target counts as skipped.
+    cs: a RecordDiffs of kind "cs" for the mapping's records (sam.record_diffs) -- every line then ends with cs:Z:<text>, what
+    paftools call reads; None: no such tag.
     -> (lines written, rows skipped as invalid)"""
     toff, text = cigar_text(mapping.records.offsets, mapping.records.ops, device)
-    lines, skipped = paf_lines(mapping, toff, text, read_names, ref_name, ref_len, k, ref_start, kept_only, targets)
+    lines, skipped = paf_lines(mapping, toff, text, read_names, ref_name, ref_len, k, ref_start, kept_only, targets, cs)
     for ln in lines:
         fh.write(ln + "\n")
     return len(lines), skipped

@@ -1,0 +1,248 @@
+"""SAM output of a Mapping (index.map): the difference strings MD:Z: and cs:Z: and the reads in reference orientation come from the
+device (kh_record_diffs, kh_oriented_rows in include/kmerhash_amd.h, which holds the definitions); the header, the flags and the
+lines are host formatting beside kmers.paf_lines."""
+import collections
+import ctypes as C
+
+import numpy as np
+
+from . import _capi as K
+from ._call import _Buf, _is_tensor, alloc, check, check_same, stream_of, torch
+from .kmers import FLAG_KEPT, FLAG_PRIMARY, Mapping, _host, cigar_text
+
+RecordDiffs = collections.namedtuple("RecordDiffs", "ok offsets text")
+DIFF_KINDS = {"cs": 0, "md": 1}      # KH_DIFF_CS, KH_DIFF_MD
+
+
+def record_diffs(qtext, rtext, records, rev, q_lo, q_hi, kind="cs", ref_base=0, device=0):
+    """which bases the X, I and D runs of every record were (kh_record_diffs): per row of `records` (a ChainRecords made with
+    ref_order=True) the short cs string (kind="cs": ':' matches, '*' reference base and read base, '+' inserted, '-' deleted bases, lower
+    case) or the MD string of SAM (kind="md").  qtext and rtext are the texts the records were made from, rtext covering the reference
+    coordinates [ref_base, ref_base + len(rtext)); rev (bit 0: the strand, table.rev), q_lo and q_hi (the byte interval of each row's
+    read in qtext) hold one entry per row.
+    -> RecordDiffs(ok, offsets, text): ok[c] = 1 where the row walks the two texts from end to end (an invalid row, or one that does not
+    fit its read or the reference text, has ok 0 and no text); row c is text[offsets[c]:offsets[c + 1]].  numpy in, numpy out (uint8,
+    uint64, uint8); CUDA tensors in, tensors out on the current stream (int64 offsets, uint8 text); count, then emit, one wait per pass."""
+    if kind not in DIFF_KINDS:
+        raise ValueError("kind must be 'cs' or 'md', got %r" % (kind,))
+    qb, rb = _Buf.text(qtext), _Buf.text(rtext)
+    ob, pb, vb, sb = _Buf(records.offsets, np.uint64), _Buf(records.ops, np.uint32), _Buf(records.valid, np.uint8), _Buf(records.rs, np.uint32)
+    eb, lb, hb = _Buf(rev, np.uint8), _Buf(q_lo, np.uint32), _Buf(q_hi, np.uint32)
+    check_same("the texts, the records, rev, q_lo and q_hi must live in the same memory", qb, rb, ob, pb, vb, sb, eb, lb, hb, length=False)
+    rows = vb.n
+    check_same("records.valid, records.rs, rev, q_lo and q_hi must have one entry per row, got %d, %d, %d, %d and %d" % (rows, sb.n, eb.n, lb.n, hb.n), vb, sb, eb, lb, hb)
+    if ob.n != rows + 1:
+        raise ValueError("records.offsets must hold one entry per row and one more, got %d for %d rows" % (ob.n, rows))
+    if rows > 2 ** 31 or pb.n > 2 ** 31 or qb.n > 2 ** 32 or rb.n > 2 ** 32 or not 0 <= int(ref_base) < 2 ** 32:
+        raise ValueError("at most 2^31 rows and runs and texts of 2^32 bytes per call, ref_base a u32")
+    ok, kptr = alloc(vb, rows, np.uint8, empty=True)
+    offs, optr = alloc(vb, rows + 1, np.uint64, zero=True)
+    if rows == 0:      # nothing to queue: the zeroed offset is the answer
+        return RecordDiffs(ok, offs, alloc(vb, 0, np.uint8)[0])
+    fn, n, stream = K.lib().kh_record_diffs, C.c_uint64(), stream_of(vb, device)
+    args = (qb.ptr_or_null, qb.n, rb.ptr_or_null, rb.n, int(ref_base), ob.ptr, pb.ptr_or_null, pb.n, vb.ptr, eb.ptr, lb.ptr, hb.ptr, sb.ptr, rows, DIFF_KINDS[kind], vb.where,
+            kptr, optr)
+    check(fn(*args, None, 0, C.byref(n), device, stream), "kh_record_diffs")
+    text, xptr = alloc(vb, n.value, np.uint8)
+    if n.value:
+        check(fn(*args, xptr, n.value, C.byref(n), device, stream), "kh_record_diffs")
+    return RecordDiffs(ok, offs, text)
+
+
+def oriented_rows(text, lo, hi, rev, complement=True, device=0):
+    """byte ranges of a text as rows in reference orientation (kh_oriented_rows): row c is text[lo[c]:hi[c]] (clamped to the text, empty
+    where hi <= lo) as it stands where bit 0 of rev[c] is clear and back to front where it is set -- with complement every base of a
+    reversed row complemented (A<->T, C<->G, case kept, any other byte itself): SEQ; without, reversed only: QUAL.
+    -> (offsets, text): row c is text[offsets[c]:offsets[c + 1]].  numpy in, numpy out (uint64, uint8); CUDA tensors in, tensors out on
+    the current stream (int64, uint8); count, then emit, one wait per pass."""
+    tb, lb, hb, eb = _Buf.text(text), _Buf(lo, np.uint32), _Buf(hi, np.uint32), _Buf(rev, np.uint8)
+    check_same("text, lo, hi and rev must live in the same memory", tb, lb, hb, eb, length=False)
+    check_same("lo, hi and rev must have one entry per row, got %d, %d and %d" % (lb.n, hb.n, eb.n), lb, hb, eb)
+    rows = lb.n
+    if rows > 2 ** 31 or tb.n > 2 ** 32:
+        raise ValueError("at most 2^31 rows and a text of 2^32 bytes per call, got %d and %d" % (rows, tb.n))
+    offs, optr = alloc(lb, rows + 1, np.uint64, zero=True)
+    if rows == 0:
+        return offs, alloc(lb, 0, np.uint8)[0]
+    fn, n, stream = K.lib().kh_oriented_rows, C.c_uint64(), stream_of(lb, device)
+    args = (tb.ptr_or_null, tb.n, lb.ptr, hb.ptr, eb.ptr, rows, 1 if complement else 0, lb.where, optr)
+    check(fn(*args, None, 0, C.byref(n), device, stream), "kh_oriented_rows")
+    out, xptr = alloc(lb, n.value, np.uint8)
+    if n.value:
+        check(fn(*args, xptr, n.value, C.byref(n), device, stream), "kh_oriented_rows")
+    return offs, out
+
+
+def sam_header(targets=None, ref_name=None, ref_len=None):
+    """the header of a SAM file as one string: @HD VN:1.6 SO:unsorted, one @SQ per target (targets: a kmerhash_amd.Targets; or the one
+    reference ref_name / ref_len), @PG with the library's version"""
+    if targets is not None:
+        if ref_name is not None or ref_len is not None:
+            raise ValueError("with targets the names and lengths are theirs: ref_name and ref_len must be None")
+        sq = [(n, int(l)) for n, l in zip(targets.names, targets.lengths)]
+    elif ref_name is None or ref_len is None:
+        raise ValueError("ref_name and ref_len are needed without targets")
+    else:
+        sq = [(str(ref_name), int(ref_len))]
+    lines = ["@HD\tVN:1.6\tSO:unsorted"] + ["@SQ\tSN:%s\tLN:%d" % s for s in sq]
+    lines.append("@PG\tID:kmerhash_amd\tPN:kmerhash_amd\tVN:%s" % K.lib().kh_version().decode())
+    return "".join(l + "\n" for l in lines)
+
+
+def _printable(mapping, targets, kept_only):
+    """the rows write_paf would print, and the other rows it would look at -> (printable, considered, target per row or None)"""
+    flag, valid = _host(mapping.select.flag, np.uint8), _host(mapping.records.valid, np.uint8)
+    considered = (flag & FLAG_KEPT) != 0 if kept_only else np.ones(len(valid), dtype=bool)
+    good, tgt = valid != 0, None
+    if targets is not None:      # a row's target is the one its first reference base lies in; its end must lie there too
+        rs, re_ = _host(mapping.records.rs, np.uint32), _host(mapping.records.re, np.uint32)
+        tgt, _ = targets.locate(rs)
+        good = good & (tgt >= 0) & (re_.astype(np.int64) <= targets.ends.astype(np.int64)[np.maximum(tgt, 0)])
+    return considered & good, considered, tgt
+
+
+def _mapped_reads(mapping, printable):
+    """per read: is select.best[s] a printable row?"""
+    best = _host(mapping.select.best, np.int32).astype(np.int64)
+    inside = (best >= 0) & (best < len(printable))
+    return inside & printable[np.where(inside, best, 0)] if len(printable) else np.zeros(len(best), dtype=bool)
+
+
+def _rows_of(pair):
+    offs, text = pair
+    return _host(offs, np.int64), _host(text, np.uint8).tobytes().decode("latin-1")
+
+
+def sam_lines(mapping, text_offsets, text, seq_rows, read_names, qual_rows=None, md=None, cs=None, ref_name=None, ref_len=None, ref_start=0, targets=None,
+              kept_only=True, unmapped=True, header=True):
+    """the formatting half of write_sam() (host only).  text_offsets, text: the CIGAR text CSR of the record rows (cigar_text); md, cs:
+    RecordDiffs of the two kinds or None; seq_rows (and qual_rows, or None): an (offsets, text) CSR of n_rows + n_reads rows -- row c
+    the oriented read of table row c (needed for the primary rows that are printed), row n_rows + s read s as given (needed for the
+    unmapped reads).  -> (lines, skipped, unmapped_reads): the header lines first when `header`."""
+    if targets is not None and int(ref_start) != 0:
+        raise ValueError("with targets the starts are theirs: ref_start must be 0")
+    head = sam_header(targets, ref_name, ref_len).splitlines()      # (checks ref_name / ref_len against targets)
+    t, sel, rec = mapping.table, mapping.select, mapping.records
+    seg, rev, count, score = _host(t.seg, np.uint32), _host(t.rev, np.uint8), _host(t.count, np.uint32), _host(t.score, np.int32)
+    flag, mapq, sub, best = _host(sel.flag, np.uint8), _host(sel.mapq, np.uint8), _host(sel.sub, np.int32), _host(sel.best, np.int32)
+    rs, nm = _host(rec.rs, np.uint32), _host(rec.nm, np.uint32)
+    n_rows, n_reads = len(flag), len(best)
+    printable, considered, tgt = _printable(mapping, targets, kept_only)
+    mapped = _mapped_reads(mapping, printable)
+    toff, raw = _rows_of((text_offsets, text))
+    soff, sraw = _rows_of(seq_rows)
+    qoff, qraw = _rows_of(qual_rows) if qual_rows is not None else (None, None)
+    diffs = [(tag, _host(d.ok, np.uint8), *_rows_of((d.offsets, d.text))) for tag, d in (("MD", md), ("cs", cs)) if d is not None]
+    if len(soff) != n_rows + n_reads + 1 or (qoff is not None and len(qoff) != len(soff)):
+        raise ValueError("seq_rows and qual_rows must hold one row per table row and one per read")
+    rows_of = [[] for _ in range(n_reads)]
+    for c in np.flatnonzero(considered):
+        if int(seg[c]) < n_reads:
+            rows_of[int(seg[c])].append(int(c))
+    lines, skipped, n_unmapped = (list(head) if header else []), 0, 0
+    for s in range(n_reads):
+        name = str(read_names[s])
+        if not mapped[s]:
+            n_unmapped += 1
+            skipped += len(rows_of[s])
+            if unmapped:
+                r = n_rows + s
+                lines.append("\t".join([name, "4", "*", "0", "0", "*", "*", "0", "0", sraw[soff[r]:soff[r + 1]] or "*",
+                                        (qraw[qoff[r]:qoff[r + 1]] if qraw is not None else "") or "*"]))
+            continue
+        for c in rows_of[s]:
+            if not printable[c]:
+                skipped += 1
+                continue
+            pri = bool(flag[c] & FLAG_PRIMARY)
+            fl = (0x10 if rev[c] & 1 else 0) | (0 if pri else 0x100) | (0x800 if pri and c != int(best[s]) else 0)
+            if targets is None:
+                tname, t0 = str(ref_name), int(ref_start)
+            else:
+                tname, t0 = targets.names[int(tgt[c])], int(targets.starts[int(tgt[c])])
+            f = [name, fl, tname, int(rs[c]) - t0 + 1, int(mapq[c]), raw[toff[c]:toff[c + 1]], "*", 0, 0,
+                 (sraw[soff[c]:soff[c + 1]] if pri else "") or "*", (qraw[qoff[c]:qoff[c + 1]] if pri and qraw is not None else "") or "*",
+                 "NM:i:%d" % int(nm[c]), "tp:A:%s" % ("P" if pri else "S"), "cm:i:%d" % int(count[c]), "s1:i:%d" % int(score[c])]
+            if pri:
+                f.append("s2:i:%d" % int(sub[c]))
+            for tag, ok, doff, draw in diffs:
+                if not ok[c]:
+                    raise ValueError("row %d does not walk the two texts: make the Mapping with ref_order=True and pass the texts it was made from" % c)
+                f.append("%s:Z:%s" % (tag, draw[doff[c]:doff[c + 1]]))
+            lines.append("\t".join(str(x) for x in f))
+    return lines, skipped, n_unmapped
+
+
+def _host_columns(mapping):
+    """the per-row columns of a Mapping on the host, copied once (the CSRs stay where they are)"""
+    t, sel, rec = mapping.table, mapping.select, mapping.records
+    h = lambda x, dt: _host(x, dt)      # noqa: E731
+    table = t._replace(seg=h(t.seg, np.uint32), rev=h(t.rev, np.uint8), count=h(t.count, np.uint32), score=h(t.score, np.int32))
+    select = sel._replace(flag=h(sel.flag, np.uint8), mapq=h(sel.mapq, np.uint8), sub=h(sel.sub, np.int32), best=h(sel.best, np.int32))
+    records = rec._replace(valid=h(rec.valid, np.uint8), rs=h(rec.rs, np.uint32), re=h(rec.re, np.uint32), nm=h(rec.nm, np.uint32))
+    return Mapping(table, mapping.edits, mapping.cigars, mapping.ends, select, records)
+
+
+def write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends=None, qual=None, ref_name=None, ref_len=None, ref_start=0, ref_base=0, targets=None,
+              kept_only=True, unmapped=True, header=True, md=True, cs=False, device=0):
+    """the rows of a Mapping (index.map) as a SAM file into the text file `fh`.  On the device: one cigar_text() call over the records,
+    one record_diffs() call per difference string asked for (md: MD:Z:, cs: the short cs:Z:), one oriented_rows() call for SEQ and one
+    for QUAL when `qual` is given; then one copy of the columns to the host and one line per row (sam_lines).
+    seq, ref_text: the texts the Mapping was made from (ref_text covers [ref_base, ref_base + len)), living where the Mapping lives;
+    read_starts / read_ends: the byte interval of every read in seq, as index.map took them; qual: a text like seq in which qual[i] is
+    the quality of seq[i]; read_names[s]: the name of read s.  One target (ref_name, ref_len) whose base 0 is reference coordinate
+    ref_start, or targets: the kmerhash_amd.Targets the Mapping was made with (then ref_name / ref_len / ref_start stay None / None / 0).
+    A row is printable under the rules of write_paf: kept (with kept_only), valid, inside one target.  Read s is represented by row
+    select.best[s]: where that row is missing or not printable the read is written as unmapped (flag 4, the read as given) -- or
+    dropped with unmapped=False -- and its other printable rows count as skipped; otherwise every printable row of the read gives a
+    line: QNAME, FLAG (0x10 reverse strand, 0x100 secondary, 0x800 a primary other than best[s]), RNAME, POS = rs - start + 1, MAPQ,
+    CIGAR (S I D = X), * 0 0, SEQ and QUAL in reference orientation ('*' for secondaries, QUAL '*' without qual), then NM:i, tp:A:P|S,
+    cm:i, s1:i, s2:i (primaries), MD:Z, cs:Z.  Lines are grouped by read, reads ascending, a read's rows in table order.
+    Make the Mapping with ref_order=True: SAM wants the CIGAR of a reverse-strand row in reference order, and so do the difference
+    strings -- a row that does not walk the texts raises ValueError.
+    -> (alignment lines written, rows skipped, unmapped reads)"""
+    sb = _Buf.text(seq)
+    seq = sb.obj
+    n_text = sb.n
+    rs_ = np.asarray(read_starts.cpu() if _is_tensor(read_starts) else read_starts, dtype=np.int64).ravel()
+    if read_ends is None:
+        re_ = np.concatenate([rs_[1:], [n_text]])
+    else:
+        re_ = np.asarray(read_ends.cpu() if _is_tensor(read_ends) else read_ends, dtype=np.int64).ravel()
+    if re_.size != rs_.size or (re_ < rs_).any() or (re_ > n_text).any() or (rs_ < 0).any():
+        raise ValueError("read_starts and read_ends must hold one byte offset per read, 0 <= read_starts[s] <= read_ends[s] <= len(seq)")
+    hm = _host_columns(mapping)
+    n_reads = len(hm.select.best)
+    if rs_.size != n_reads:
+        raise ValueError("read_starts holds %d reads, the Mapping %d" % (rs_.size, n_reads))
+    seg = hm.table.seg.astype(np.int64)
+    if len(seg) and int(seg.max()) >= n_reads:
+        raise ValueError("the table names read %d, the Mapping holds %d reads" % (int(seg.max()), n_reads))
+    lo, hi = rs_[seg].astype(np.uint32), re_[seg].astype(np.uint32)
+    dev = sb.dev
+
+    def place(a):      # a host column to where the texts live
+        a = np.ascontiguousarray(a)
+        return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(sb.device) if dev else a
+
+    rec = mapping.records
+    toff, ctext = cigar_text(rec.offsets, rec.ops, device)
+    dlo, dhi = place(lo), place(hi)
+    diffs = {kind: record_diffs(seq, ref_text, rec, mapping.table.rev, dlo, dhi, kind, ref_base, device) if want else None for kind, want in (("md", md), ("cs", cs))}
+    # SEQ and QUAL: the oriented read for the primary rows that are printed, the read as given for the unmapped reads
+    printable, _, _ = _printable(hm, targets, kept_only)
+    mapped = _mapped_reads(hm, printable)
+    need = printable & ((hm.select.flag & FLAG_PRIMARY) != 0) & mapped[seg] if len(seg) else np.zeros(0, dtype=bool)
+    show = ~mapped if unmapped else np.zeros(n_reads, dtype=bool)
+    all_lo = np.concatenate([lo, rs_.astype(np.uint32)])
+    all_hi = np.concatenate([np.where(need, hi, lo), np.where(show, re_, rs_).astype(np.uint32)]).astype(np.uint32)
+    all_rev = np.concatenate([hm.table.rev & 1, np.zeros(n_reads, dtype=np.uint8)]).astype(np.uint8)
+    plo, phi, prev = place(all_lo), place(all_hi), place(all_rev)
+    seq_rows = oriented_rows(seq, plo, phi, prev, True, device)
+    qual_rows = oriented_rows(qual, plo, phi, prev, False, device) if qual is not None else None
+    lines, skipped, n_unmapped = sam_lines(hm, toff, ctext, seq_rows, read_names, qual_rows, diffs["md"], diffs["cs"], ref_name, ref_len, ref_start, targets,
+                                           kept_only, unmapped, header)
+    for ln in lines:
+        fh.write(ln + "\n")
+    n_head = len(sam_header(targets, ref_name, ref_len).splitlines()) if header else 0
+    return len(lines) - n_head - (n_unmapped if unmapped else 0), skipped, n_unmapped
