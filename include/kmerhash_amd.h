@@ -1080,6 +1080,66 @@ kh_status kh_oriented_rows(const void* text /*[h|d]*/, uint64_t n, const uint32_
                            uint64_t* out_offsets /*[n_rows+1]*/, uint8_t* out_text /*[cap_text] or NULL*/, uint64_t cap_text, uint64_t* n_text,
                            int device, void* hip_stream);
 
+/* ---- paired reads.  The calls above map every read on its own; kh_pair_chains looks at the chain rows of the two mates of a fragment
+ *      together: it picks the concordant combination, says whether the pair is proper, raises the quality of a mate that its partner
+ *      pins to one copy of a repeat, and gives the template length.  Integers only: the kernel equals the model of tests/pair_model.py
+ *      bit for bit.
+ *      Inputs.  Per chain c of n_chains: the reference interval [rs[c], re[c]) (u32, global coordinates: ChainRecords rs / re), rev[c]
+ *      (u8, bit 0: the strand), score[c] (i32, any value), tid[c] (u32 target number, KH_TARGET_NONE allowed; tid == NULL: all chains
+ *      lie in one target), use[c] (u8, non-zero: the chain is a candidate; NULL: all are), mapq_in[c] (u8, the single-read quality;
+ *      NULL: 0).  A CSR offsets [n_reads + 1] (required) gives the chains [offsets[s], offsets[s + 1]) of read s.  Reads 2p and 2p + 1
+ *      are mate 1 and mate 2 of pair p; n_reads is even.  Parameters min_ins <= max_ins (u32, fragment length bounds) and unpaired_pen
+ *      (u32).
+ *      Candidates.  A chain TAKES PART if use says so and re > rs.  Of each mate only its KH_PAIR_CANDIDATES (64) best taking-part
+ *      chains are candidates, in the CANDIDATE ORDER: score descending, ties to the smaller chain number.  A read with more kept loci
+ *      is a repeat, whatever its partner says; the cap belongs to the definition (it bounds the work per pair), not to the kernel.
+ *      A combination (a, b) -- a a candidate of mate 1, b one of mate 2 -- is CONCORDANT, for a forward-reverse library, iff
+ *      tid[a] == tid[b] != KH_TARGET_NONE; bit 0 of rev[a] and rev[b] differ; with f the forward chain of the two and r the reverse
+ *      one, rs_f <= rs_r and re_f <= re_r; and frag = re_r - rs_f lies in [min_ins, max_ins].  Its pair score is ps = s_a + s_b in
+ *      signed 64-bit.  Combinations are ordered by ps descending, then a ascending, then b ascending (chain numbers); (a*, b*) is the
+ *      first, ps* its score.
+ *      Singles.  a0 and b0 are the first candidate of each mate in the candidate order, -1 for a mate without candidates.
+ *      Proper.  Pair p is PROPER iff a concordant combination exists and ps* + unpaired_pen >= s_a0 + s_b0 (64-bit).  Its rows are then
+ *      (a*, b*), otherwise (a0, b0).
+ *      Quality.  For a proper pair and mate 1: alt1 = max(0, the greatest ps over the concordant combinations with a != a*), 0 if
+ *      there is none; pq1 = 0 if ps* <= 0, else min(60, floor(60 * (ps* - alt1) / ps*)); out_mapq[2p] = max(mapq_in[a*], pq1).  Mate 2
+ *      likewise over b != b*.  A pair that is not proper: out_mapq[s] = mapq_in[out_row[s]], 0 where the read has no row.
+ *      Template length.  Where both mates have a row and the two rows share a target that is not KH_TARGET_NONE (tid == NULL: they
+ *      always do): t = max(re) - min(rs) over the two rows, in 64-bit, clamped to 2^31 - 1; the mate whose rs is smaller gets +t, the
+ *      other -t; equal rs: mate 1 gets +t.  Otherwise 0.
+ *      Outputs.  Per read [n_reads]: out_row (i32, a chain number or -1), out_mapq (u8), out_tlen (i32).  Per pair [n_reads / 2]:
+ *      out_flag (u8: bit 0 = proper, bit 1 = both mates have a row, bit 2 = the two rows share a target as above), out_score (i32: ps*
+ *      clamped to the i32 range) and out_nconc (u32: the number of concordant combinations, at most 4096).
+ *      Corners this text decides.  out_score and out_nconc describe the concordant combinations whether or not the pair is proper;
+ *      both are 0 when there is none.  A chain with re <= rs never takes part, not even as a single.  The test of a combination
+ *      compares the strand bits only: two chains of one target with the same strand, or reverse before forward, are never concordant,
+ *      whatever their distance.  A mate whose candidates all have tid == KH_TARGET_NONE can have a row (its single) but no proper
+ *      pair, bit 2 stays clear and its template length is 0.  The rows of a pair that is not proper may lie on one target: then bit 2 is
+ *      set and the template length is given, the way SAM prints TLEN for a discordant pair on one reference.
+ *      Conventions are those of kh_chain_select.  All arrays live in the memory `where` names.  Device memory: the kernel is queued on
+ *      hip_stream and the call returns WITHOUT waiting for the stream (it returns no count); the staging block of a host call comes
+ *      from the pooled block.  Host memory: staged, the call synchronises.
+ *      KH_ERR_INVALID before anything is allocated, read or written: odd n_reads, min_ins > max_ins, n_chains > 2^23,
+ *      n_reads > n_chains + 2^24, `where` outside the enum, a null offsets, while n_reads > 0 a null per-read or per-pair output, and
+ *      while n_chains > 0 a null rs, re, rev or score.  n_reads == 0: KH_OK, nothing written.  n_chains == 0: every out_row entry -1 and
+ *      every other output 0 (host memory: without a device).
+ *      Offsets that do not ascend from 0 to n_chains: in host memory they are refused on the host, KH_ERR_INVALID with nothing written
+ *      (n_reads == 0 included: offsets[0] must be 0 = n_chains).  In device memory nobody can see them before the kernel runs: every
+ *      group is clamped to [0, n_chains], nothing outside the arrays is touched, the outputs of the affected pairs are unspecified and
+ *      the status is KH_OK.
+ *      Route (kh_kernels_pair.h): one wavefront per pair, no LDS, no scratch, no atomics.  A mate's candidates are streamed 64 chains
+ *      at a time -- rank by counting, push into order, the lane-wise larger of the kept 64 and the reversed chunk (half a bitonic
+ *      merge), rank and push again; a group of at most 64 chains is one load -- then lane i holds candidate i of mate 1, a uniform loop
+ *      broadcasts those of mate 2, and (a*, b*) is one wave max over a packed 64-bit key.
+ *      Not here: an insert-size distribution, mate rescue, other library orientations. */
+#define KH_PAIR_CANDIDATES 64u
+kh_status kh_pair_chains(const uint32_t* rs /*[h|d] u32[n_chains]*/, const uint32_t* re, const uint8_t* rev, const int32_t* score,
+                         const uint32_t* tid /* or NULL */, const uint8_t* use /* or NULL */, const uint8_t* mapq_in /* or NULL */, uint64_t n_chains,
+                         const uint64_t* offsets /* u64[n_reads+1] */, uint64_t n_reads /* even */,
+                         uint32_t min_ins, uint32_t max_ins, uint32_t unpaired_pen, kh_mem where,
+                         int32_t* out_row, uint8_t* out_mapq, int32_t* out_tlen /* each [n_reads] */,
+                         uint8_t* out_flag, int32_t* out_score, uint32_t* out_nconc /* each [n_reads / 2] */, int device, void* hip_stream);
+
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);
 

@@ -13,8 +13,9 @@ from .kmers import stamp_strand, unstamp, anchors_from_csr, chain_anchors, chain
 from .kmers import select_chains, select_table, ChainSelect  # noqa: F401
 from .kmers import chain_records, cigar_text, write_paf, paf_lines, ChainRecords, Mapping  # noqa: F401
 from .kmers import group_anchors, AnchorGroups  # noqa: F401
+from .kmers import pair_chains, pair_mapping, PairSelect  # noqa: F401
 from .targets import Targets, TARGET_NONE  # noqa: F401
-from .sam import record_diffs, oriented_rows, sam_header, sam_lines, write_sam, RecordDiffs  # noqa: F401
+from .sam import record_diffs, oriented_rows, sam_header, sam_lines, write_sam, write_sam_pairs, RecordDiffs  # noqa: F401
 from .wide import syncmers128_from_sequence, syncmers128_from_fastq, is_syncmer128  # noqa: F401
 from .dist_index import ShardedKmerPositionIndex, IndexGpuBackend, WideIndexGpuBackend  # noqa: F401
 from . import workloads  # noqa: F401
@@ -28,4 +29,5 @@ __all__ = ["hashmap_robinhood_doubling", "hashmap_linearprobe_doubling", "hash_b
            "select_chains", "select_table", "ChainSelect",
            "chain_records", "cigar_text", "write_paf", "paf_lines", "ChainRecords", "Mapping",
            "group_anchors", "AnchorGroups", "Targets", "TARGET_NONE",
-           "record_diffs", "oriented_rows", "sam_header", "sam_lines", "write_sam", "RecordDiffs"]
+           "record_diffs", "oriented_rows", "sam_header", "sam_lines", "write_sam", "RecordDiffs",
+           "pair_chains", "pair_mapping", "PairSelect", "write_sam_pairs"]

@@ -17,6 +17,7 @@
 //   chain   : kh_chain_anchors, collinear chains per segment from flat anchors: a wavefront per segment, the last 64 anchors in registers (kh_kernels_chain.h).
 //   edits   : kh_chain_edits, edit distance of every link of every kept chain: a lane per anchor, then a wavefront per unsettled link (kh_kernels_edits.h).
 //   cigars  : kh_chain_cigars, the alignment operations of every link as run-length rows of a CSR: the same wavefront pass with a traceback (kh_kernels_cigar.h).
+//   pair    : kh_pair_chains, the concordant chain pair of two mates, proper flag, pair quality and template length: a wavefront per pair (kh_kernels_pair.h).
 //   select  : kh_chain_select, primary / secondary chains per read and a mapping quality: a wavefront per read, a workgroup for a read of more than 64 chains (kh_kernels_select.h).
 //   records : kh_chain_records, one run-length row and one line of numbers per chain from the link rows, end rows and clips: a wavefront per chain; kh_cigar_text, a run CSR as text (kh_kernels_records.h).
 //   targets : kh_anchor_targets, the anchors of every read regrouped by the target (contig) they fall in: a lane per anchor, then a wavefront per read (kh_kernels_targets.h).
@@ -36,6 +37,7 @@
 #include "kh_kernels_records.h"
 #include "kh_kernels_targets.h"
 #include "kh_kernels_sam.h"
+#include "kh_kernels_pair.h"
 #include "kh_part_sizing.h"
 #include "kh_scratch.h"
 #include "../../include/kmerhash_amd.h"
@@ -4637,5 +4639,55 @@ kh_status kh_oriented_rows(const void* text, uint64_t n, const uint32_t* lo, con
   s.launched();
   s.copy_back(dtext, total);
   return s.finish_queued();
+}
+// ---- the concordant chain pair of every read pair (kernel: kh_kernels_pair.h).  No handle and no count to learn: a device call queues
+//      one kernel and never waits; a host call stages through one pooled block.
+static_assert(KPR_NONE == KH_TARGET_NONE && KPR_CAP == KH_PAIR_CANDIDATES, "one word for no target, one cap");
+kh_status kh_pair_chains(const uint32_t* rs, const uint32_t* re, const uint8_t* rev, const int32_t* score, const uint32_t* tid, const uint8_t* use, const uint8_t* mapq_in,
+                         uint64_t n_chains, const uint64_t* offsets, uint64_t n_reads, uint32_t min_ins, uint32_t max_ins, uint32_t unpaired_pen, kh_mem where,
+                         int32_t* out_row, uint8_t* out_mapq, int32_t* out_tlen, uint8_t* out_flag, int32_t* out_score, uint32_t* out_nconc, int device, void* stream_) {
+  if ((n_reads & 1) || min_ins > max_ins || n_chains > (uint64_t(1) << 23) || n_reads > n_chains + (uint64_t(1) << 24)) return KH_ERR_INVALID;
+  if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !offsets) return KH_ERR_INVALID;
+  if (n_reads && (!out_row || !out_mapq || !out_tlen || !out_flag || !out_score || !out_nconc)) return KH_ERR_INVALID;
+  if (n_chains && (!rs || !re || !rev || !score)) return KH_ERR_INVALID;
+  if (where == KH_MEM_HOST) {      // (device memory: nobody can look before the kernel runs; it clamps)
+    if (offsets[0] != 0 || offsets[n_reads] != n_chains) return KH_ERR_INVALID;
+    for (uint64_t g = 0; g < n_reads; ++g)
+      if (offsets[g] > offsets[g + 1]) return KH_ERR_INVALID;
+  }
+  if (n_reads == 0) return KH_OK;
+  const uint64_t n_pairs = n_reads / 2;
+  if (n_chains == 0 && where == KH_MEM_HOST) {
+    for (uint64_t s = 0; s < n_reads; ++s) { out_row[s] = -1; out_mapq[s] = 0; out_tlen[s] = 0; }
+    for (uint64_t p = 0; p < n_pairs; ++p) { out_flag[p] = 0; out_score[p] = 0; out_nconc[p] = 0; }
+    return KH_OK;
+  }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK0(hipSetDevice(device));
+  if (n_chains == 0) {
+    HIPCHK0(hipMemsetAsync(out_row, 0xFF, n_reads * sizeof(int32_t), stream));
+    HIPCHK0(hipMemsetAsync(out_mapq, 0, n_reads, stream));
+    HIPCHK0(hipMemsetAsync(out_tlen, 0, n_reads * sizeof(int32_t), stream));
+    HIPCHK0(hipMemsetAsync(out_flag, 0, n_pairs, stream));
+    HIPCHK0(hipMemsetAsync(out_score, 0, n_pairs * sizeof(int32_t), stream));
+    HIPCHK0(hipMemsetAsync(out_nconc, 0, n_pairs * sizeof(uint32_t), stream));
+    return KH_OK;
+  }
+  Scratch s(device, stream);
+  KprArgs P{};
+  if (!s.layout([&](Scratch& c) {
+        P.rs = c.in(rs, n_chains, where); P.re = c.in(re, n_chains, where); P.rev = c.in(rev, n_chains, where); P.score = c.in(score, n_chains, where);
+        P.tid = c.in(tid, tid ? n_chains : 0, where); P.use = c.in(use, use ? n_chains : 0, where); P.mapq_in = c.in(mapq_in, mapq_in ? n_chains : 0, where);
+        P.off = c.in(offsets, n_reads + 1, where);
+        P.row = c.out(out_row, n_reads, where); P.mapq = c.out(out_mapq, n_reads, where); P.tlen = c.out(out_tlen, n_reads, where);
+        P.flag = c.out(out_flag, n_pairs, where); P.score_out = c.out(out_score, n_pairs, where); P.nconc = c.out(out_nconc, n_pairs, where);
+      })) return s.finish();
+  P.n = (uint32_t)n_chains; P.n_pairs = (uint32_t)n_pairs; P.min_ins = min_ins; P.max_ins = max_ins; P.pen = unpaired_pen;
+  const uint32_t ncu = (uint32_t)cu_count(device);
+  hipLaunchKernelGGL(k_pair_wave, dim3(grid_for(n_pairs, KPR_WAVES, ncu * 8)), dim3(KPR_THREADS), 0, stream, P);
+  s.launched();
+  s.copy_back(P.row, n_reads); s.copy_back(P.mapq, n_reads); s.copy_back(P.tlen, n_reads);
+  s.copy_back(P.flag, n_pairs); s.copy_back(P.score_out, n_pairs); s.copy_back(P.nconc, n_pairs);
+  return s.finish_queued();      // (host memory: copies are pending, so this waits)
 }
 }  // extern "C"

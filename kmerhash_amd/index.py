@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from ._call import HOST, _Buf, _Handle, alloc, check_same, torch
-from .kmers import Mapping, anchors_from_csr, chain_anchors, chain_cigars, chain_edits, chain_ends, chain_records, group_anchors, select_table, stamp_strand
+from .kmers import Mapping, anchors_from_csr, chain_anchors, chain_cigars, chain_edits, chain_ends, chain_records, group_anchors, pair_mapping, select_table, stamp_strand
 from .targets import Targets
 from .seqs import is_syncmer, is_syncmer128, kmers_from_sequence, minimizers_from_sequence, syncmers128_from_sequence, syncmers_from_sequence
 from .table import _hash_id
@@ -414,6 +414,22 @@ class KmerPositionIndex(_Handle):
         q, r, v = table.anchors
         records = chain_records(q, r, v, table.chain, cigars, c.first, c.last, lo, hi, ends, self.k, ref_order, self.device)
         return Mapping(table, edits, cigars, ends, select, records)
+
+    def map_pairs(self, seq, ref_text, read_starts, read_ends=None, ref_base=0, max_edits=31, clip_cost=4, mask_pct=50, pri_pct=80, best_n=5,
+                  min_ins=0, max_ins=1000, unpaired_pen=17, targets=None, **params):
+        """paired reads: map(seq, ref_text, read_starts, ...) with ref_order=True over reads that are interleaved -- read 2p is mate 1 and
+        read 2p + 1 mate 2 of fragment p, both as the sequencer gives them (a forward-reverse library) -- then kmers.pair_mapping over the
+        Mapping -> (Mapping, PairSelect(row, mapq, tlen, flag, score, nconc)): per read the row that represents it in its pair, its
+        quality and its template length; per pair whether it is proper.  min_ins / max_ins bound the fragment length of a concordant
+        pair, unpaired_pen is what two unpaired best rows must win by.  An odd number of reads raises ValueError.
+        write_sam_pairs() prints the mate columns."""
+        if not self.stranded:
+            raise ValueError("map_pairs() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        n_reads = 1 if read_starts is None else len(read_starts)
+        if n_reads % 2:
+            raise ValueError("reads come in pairs (mate 1, mate 2, ...): an even number of reads is needed, got %d" % n_reads)
+        mp = self.map(seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, mask_pct, pri_pct, best_n, True, targets, **params)
+        return mp, pair_mapping(mp, n_reads, targets, min_ins=min_ins, max_ins=max_ins, unpaired_pen=unpaired_pen, device=self.device)
 
     def chain_select(self, seq, read_starts=None, mask_pct=50, pri_pct=80, best_n=5, **params):
         """chains(seq, read_starts, **params), then which chain of every read is the answer: kmers.select_table over the table with one

@@ -411,6 +411,95 @@ def select_table(table, n_reads=None, **params):
     return select_chains(table.q_start, table.q_end, table.score, table.count, offs, **params)
 
 
+PairSelect = collections.namedtuple("PairSelect", "row mapq tlen flag score nconc")
+PAIR_PROPER, PAIR_BOTH, PAIR_SAME_TARGET = 1, 2, 4      # the bits of PairSelect.flag
+
+
+def _check_pair_params(min_ins, max_ins, unpaired_pen):
+    """the refusals of kh_pair_chains that depend on the parameters alone, as ValueError"""
+    if not 0 <= int(min_ins) <= int(max_ins) < 2 ** 32:
+        raise ValueError("0 <= min_ins <= max_ins < 2^32 is needed, got %r and %r" % (min_ins, max_ins))
+    if not 0 <= int(unpaired_pen) < 2 ** 32:
+        raise ValueError("unpaired_pen must be 0..2^32-1, got %r" % (unpaired_pen,))
+
+
+def pair_chains(rs, re, rev, score, read_offsets, tid=None, use=None, mapq=None, min_ins=0, max_ins=1000, unpaired_pen=17, device=0):
+    """the chain rows of the two mates of every read pair, looked at together (kh_pair_chains in include/kmerhash_amd.h, which holds the
+    definition).  Reads 2p and 2p + 1 are mate 1 and mate 2 of pair p; read s owns the chains [read_offsets[s], read_offsets[s + 1]).
+    Per chain: the reference interval [rs, re), the strand rev, the score, and optionally its target number tid (None: one target), use
+    (non-zero: a candidate; None: all) and the single-read quality mapq (None: 0).  A combination of one candidate per mate is
+    concordant when both lie on one target, on opposite strands, forward before reverse, with a fragment length re_reverse - rs_forward
+    in [min_ins, max_ins]; the pair is proper when the best concordant pair score + unpaired_pen reaches the sum of the two best single
+    scores.  Only the 64 best candidates of a mate take part.
+    -> PairSelect(row, mapq, tlen, flag, score, nconc): per read the chain that represents it (-1: none), its quality -- for a proper
+    pair raised to 60 * (1 - best other pair score / pair score) where that is more -- and the signed template length; per pair flag
+    bit 0 = proper, bit 1 = both mates have a row, bit 2 = the rows share a target, the best concordant pair score and the number of
+    concordant combinations.  numpy in (uint32, uint32, uint8, int32, uint64; uint32, uint8, uint8), numpy out (int32, uint8, int32,
+    uint8, int32, uint32); CUDA tensors in, tensors out on the current stream -- queued only: the call does not wait for the stream.
+    At most 2^23 chains per call."""
+    _check_pair_params(min_ins, max_ins, unpaired_pen)
+    sb, eb, vb, cb, ob = _Buf(rs, np.uint32), _Buf(re, np.uint32), _Buf(rev, np.uint8), _Buf(score, np.int32), _Buf(read_offsets, np.uint64)
+    tb = None if tid is None else _Buf(tid, np.uint32)
+    ub = None if use is None else _Buf(use, np.uint8)
+    mb = None if mapq is None else _Buf(mapq, np.uint8)
+    check_same("rs, re, rev, score, read_offsets, tid, use and mapq must live in the same memory", sb, eb, vb, cb, ob, tb, ub, mb, length=False)
+    n = sb.n
+    check_same("rs, re, rev, score, tid, use and mapq must have one entry per chain", sb, eb, vb, cb, tb, ub, mb)
+    if n > 2 ** 23:
+        raise ValueError("at most 2^23 chains per call (batch over reads), got %d" % n)
+    if ob.n < 1 or ob.n - 1 > n + 2 ** 24:
+        raise ValueError("read_offsets must hold n_reads + 1 entries ascending from 0 to the number of chains, got %d entries for %d chains" % (ob.n, n))
+    n_reads = ob.n - 1
+    if n_reads % 2:
+        raise ValueError("reads come in pairs (mate 1, mate 2, ...): an even number of reads is needed, got %d" % n_reads)
+    per_read = [alloc(ob, n_reads, dt, empty=True) for dt in (np.int32, np.uint8, np.int32)]
+    per_pair = [alloc(ob, n_reads // 2, dt, empty=True) for dt in (np.uint8, np.int32, np.uint32)]
+    opt = lambda b: None if b is None else b.ptr_or_null      # noqa: E731
+    st = K.lib().kh_pair_chains(sb.ptr_or_null, eb.ptr_or_null, vb.ptr_or_null, cb.ptr_or_null, opt(tb), opt(ub), opt(mb), n, ob.ptr, n_reads,
+                                int(min_ins), int(max_ins), int(unpaired_pen), ob.where, *(p for _, p in per_read + per_pair), device, stream_of(ob, device))
+    check(st, "kh_pair_chains" + (": read_offsets do not ascend from 0 to the number of chains" if st == K.KH_ERR_INVALID else ""))
+    return PairSelect(*(a for a, _ in per_read + per_pair))
+
+
+def pair_mapping(mapping, n_reads, targets=None, **params):
+    """pair_chains over the rows of a Mapping (index.map) whose reads are interleaved mate 1, mate 2, ...: a row is a candidate when
+    select kept it and records.valid says it has a whole alignment -- and, with targets (the kmerhash_amd.Targets the Mapping was made
+    with), when its interval lies inside one target: the printable rule of write_paf.  The intervals are records.rs / records.re, the
+    strand table.rev, the score table.score, the quality select.mapq, the target targets.locate(records.rs), the CSR the runs of equal
+    table.seg as select_table() makes it.  params: min_ins, max_ins, unpaired_pen, device.  -> PairSelect
+    n_reads must cover the reads of the table.  A numpy Mapping is checked (ValueError); a tensor Mapping is not, because the check would
+    be a host wait: rows of reads at or beyond n_reads then fall outside the CSR and take no part, silently."""
+    n_reads = int(n_reads)
+    if n_reads < 0 or n_reads % 2:
+        raise ValueError("reads come in pairs (mate 1, mate 2, ...): an even number of reads is needed, got %r" % (n_reads,))
+    t, sel, rec = mapping.table, mapping.select, mapping.records
+    seg = t.seg
+    dev = _is_tensor(seg) and seg.is_cuda
+    rows = int(seg.numel() if _is_tensor(seg) else len(seg))
+    tid = None
+    if dev:
+        offs = torch.searchsorted(seg.long(), torch.arange(n_reads + 1, dtype=torch.int64, device=seg.device))
+        use = ((sel.flag & FLAG_KEPT) != 0) & (rec.valid != 0)
+        if targets is not None:
+            tgt, _ = targets.locate(rec.rs)
+            ends = targets.to(seg.device)[1].long() & 0xFFFFFFFF
+            use = use & (tgt >= 0) & ((rec.re.long() & 0xFFFFFFFF) <= ends[tgt.clamp(min=0)])
+            tid = tgt.int()      # (-1 holds the bits of KH_TARGET_NONE)
+        use = use.to(torch.uint8)
+    else:
+        sg = np.asarray(seg).astype(np.int64)
+        offs = np.searchsorted(sg, np.arange(n_reads + 1, dtype=np.int64), side="left").astype(np.uint64)
+        if int(offs[-1]) != rows:
+            raise ValueError("n_reads = %d does not cover the reads of the table (seg reaches %d)" % (n_reads, int(sg.max())))
+        use = ((_host(sel.flag, np.uint8) & FLAG_KEPT) != 0) & (_host(rec.valid, np.uint8) != 0)
+        if targets is not None:
+            tgt, _ = targets.locate(_host(rec.rs, np.uint32))
+            use = use & (tgt >= 0) & (_host(rec.re, np.uint32).astype(np.int64) <= targets.ends.astype(np.int64)[np.maximum(tgt, 0)])
+            tid = tgt.astype(np.int64).astype(np.uint32) if len(tgt) else np.zeros(0, dtype=np.uint32)
+        use = use.astype(np.uint8)
+    return pair_chains(rec.rs, rec.re, t.rev, t.score, offs, tid, use, sel.mapq, **params)
+
+
 def read_cigar(cigars, ends, table, row, k):
     """the CIGAR of the whole read of chain `row` as text (a host helper like cigar_string): 'S' for the bases the head clips, the head's
     row, what cigar_string(cigars, table, row, k) gives, the tail's row, 'S' for the bases the tail clips, equal neighbours merged -- in

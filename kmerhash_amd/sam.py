@@ -108,17 +108,42 @@ def _mapped_reads(mapping, printable):
     return inside & printable[np.where(inside, best, 0)] if len(printable) else np.zeros(len(best), dtype=bool)
 
 
+ROLE_REP, ROLE_SUPP, ROLE_SEC = 1, 2, 3      # what a printable row of a paired read is printed as: the representative, 0x800, 0x100
+
+
+def _pair_roles(mapping, pairs, printable):
+    """paired output: -> (rep, role): rep[s] = the row that represents read s -- pairs.row[s] where that is a printable row of the read,
+    else -1 (unmapped) --; role[c] of every printable row of a mapped read: ROLE_REP for the representative, ROLE_SEC for a row that is
+    a secondary in select or the select.parent of the representative, ROLE_SUPP for any other; 0 for the rows that are not printed"""
+    seg, flag = _host(mapping.table.seg, np.uint32).astype(np.int64), _host(mapping.select.flag, np.uint8)
+    parent = _host(mapping.select.parent, np.int32).astype(np.int64)
+    row = _host(pairs.row, np.int32).astype(np.int64)
+    n_rows, n_reads = len(flag), len(row)
+    if n_rows == 0:
+        return np.full(n_reads, -1, dtype=np.int64), np.zeros(0, dtype=np.uint8)
+    inside = (row >= 0) & (row < n_rows)
+    at = np.where(inside, row, 0)
+    rep = np.where(inside & printable[at] & (seg[at] == np.arange(n_reads)), row, -1)
+    own = np.where(seg < n_reads, rep[np.minimum(seg, max(n_reads - 1, 0))], -1) if n_reads else np.full(n_rows, -1, dtype=np.int64)
+    shown = printable & (own >= 0)
+    c = np.arange(n_rows)
+    sec = ((flag & FLAG_PRIMARY) == 0) | (c == parent[np.maximum(own, 0)])
+    role = np.where(c == own, ROLE_REP, np.where(sec, ROLE_SEC, ROLE_SUPP)).astype(np.uint8)
+    return rep, np.where(shown, role, 0).astype(np.uint8)
+
+
 def _rows_of(pair):
     offs, text = pair
     return _host(offs, np.int64), _host(text, np.uint8).tobytes().decode("latin-1")
 
 
 def sam_lines(mapping, text_offsets, text, seq_rows, read_names, qual_rows=None, md=None, cs=None, ref_name=None, ref_len=None, ref_start=0, targets=None,
-              kept_only=True, unmapped=True, header=True):
+              kept_only=True, unmapped=True, header=True, pairs=None):
     """the formatting half of write_sam() (host only).  text_offsets, text: the CIGAR text CSR of the record rows (cigar_text); md, cs:
     RecordDiffs of the two kinds or None; seq_rows (and qual_rows, or None): an (offsets, text) CSR of n_rows + n_reads rows -- row c
     the oriented read of table row c (needed for the primary rows that are printed), row n_rows + s read s as given (needed for the
-    unmapped reads).  -> (lines, skipped, unmapped_reads): the header lines first when `header`."""
+    unmapped reads).  pairs: the PairSelect of the reads (see write_sam_pairs), whose representatives and 0x800 rows then need their seq_rows.
+    -> (lines, skipped, unmapped_reads): the header lines first when `header`."""
     if targets is not None and int(ref_start) != 0:
         raise ValueError("with targets the starts are theirs: ref_start must be 0")
     head = sam_header(targets, ref_name, ref_len).splitlines()      # (checks ref_name / ref_len against targets)
@@ -128,7 +153,7 @@ def sam_lines(mapping, text_offsets, text, seq_rows, read_names, qual_rows=None,
     rs, nm = _host(rec.rs, np.uint32), _host(rec.nm, np.uint32)
     n_rows, n_reads = len(flag), len(best)
     printable, considered, tgt = _printable(mapping, targets, kept_only)
-    mapped = _mapped_reads(mapping, printable)
+    mapped = _mapped_reads(mapping, printable) if pairs is None else None      # (paired: the representatives say who is mapped)
     toff, raw = _rows_of((text_offsets, text))
     soff, sraw = _rows_of(seq_rows)
     qoff, qraw = _rows_of(qual_rows) if qual_rows is not None else (None, None)
@@ -140,6 +165,49 @@ def sam_lines(mapping, text_offsets, text, seq_rows, read_names, qual_rows=None,
         if int(seg[c]) < n_reads:
             rows_of[int(seg[c])].append(int(c))
     lines, skipped, n_unmapped = (list(head) if header else []), 0, 0
+    if pairs is not None:
+        pmapq, ptlen, pflag = _host(pairs.mapq, np.uint8), _host(pairs.tlen, np.int32), _host(pairs.flag, np.uint8)
+        if n_reads % 2 or any(len(x) != n_reads for x in (_host(pairs.row, np.int32), pmapq, ptlen)) or len(pflag) != n_reads // 2:
+            raise ValueError("pairs must hold one entry per read of the Mapping (row, mapq, tlen) and one per pair (flag), and the reads must come in pairs")
+        rep, role = _pair_roles(mapping, pairs, printable)
+
+        def place(c):      # -> (target number, RNAME, POS) of row c
+            if targets is None:
+                return 0, str(ref_name), int(rs[c]) - int(ref_start) + 1
+            return int(tgt[c]), targets.names[int(tgt[c])], int(rs[c]) - int(targets.starts[int(tgt[c])]) + 1
+
+        for s in range(n_reads):
+            name, r, mr = str(read_names[s]), int(rep[s]), int(rep[s ^ 1])
+            fl0 = 0x1 | (0x80 if s & 1 else 0x40) | (0x8 if mr < 0 else (0x20 if rev[mr] & 1 else 0))
+            at = mr if mr >= 0 else r      # (an unmapped mate is placed at this read's representative: the mate columns point there)
+            mt, mname, mpos = place(at) if at >= 0 else (-1, "*", 0)
+            both = r >= 0 and mr >= 0      # (0x2 and TLEN need both representatives: a PairSelect made under other targets or kept_only may name a row that is not printed)
+            if r < 0:
+                n_unmapped += 1
+                skipped += len(rows_of[s])
+                if unmapped:      # at the mate's place, as the SAM specification recommends
+                    x = n_rows + s
+                    lines.append("\t".join([name, str(fl0 | 0x4), mname, str(mpos), "0", "*", "=" if mr >= 0 else "*", str(mpos), "0", sraw[soff[x]:soff[x + 1]] or "*",
+                                            (qraw[qoff[x]:qoff[x + 1]] if qraw is not None else "") or "*"]))
+                continue
+            for c in rows_of[s]:
+                if not printable[c]:
+                    skipped += 1
+                    continue
+                is_rep, pri = c == r, role[c] != ROLE_SEC
+                fl = fl0 | (0x10 if rev[c] & 1 else 0) | {ROLE_REP: 0, ROLE_SUPP: 0x800, ROLE_SEC: 0x100}[int(role[c])] | (0x2 if is_rep and both and pflag[s >> 1] & 1 else 0)
+                tn, tname, pos = place(c)
+                f = [name, fl, tname, pos, int(pmapq[s]) if is_rep else int(mapq[c]), raw[toff[c]:toff[c + 1]], "=" if mt == tn else mname, mpos,
+                     int(ptlen[s]) if is_rep and both else 0, (sraw[soff[c]:soff[c + 1]] if pri else "") or "*", (qraw[qoff[c]:qoff[c + 1]] if pri and qraw is not None else "") or "*",
+                     "NM:i:%d" % int(nm[c]), "tp:A:%s" % ("P" if pri else "S"), "cm:i:%d" % int(count[c]), "s1:i:%d" % int(score[c])]
+                if pri:
+                    f.append("s2:i:%d" % int(sub[c]))
+                for tag, ok, doff, draw in diffs:
+                    if not ok[c]:
+                        raise ValueError("row %d does not walk the two texts: make the Mapping with ref_order=True and pass the texts it was made from" % c)
+                    f.append("%s:Z:%s" % (tag, draw[doff[c]:doff[c + 1]]))
+                lines.append("\t".join(str(x) for x in f))
+        return lines, skipped, n_unmapped
     for s in range(n_reads):
         name = str(read_names[s])
         if not mapped[s]:
@@ -173,12 +241,14 @@ def sam_lines(mapping, text_offsets, text, seq_rows, read_names, qual_rows=None,
     return lines, skipped, n_unmapped
 
 
-def _host_columns(mapping):
-    """the per-row columns of a Mapping on the host, copied once (the CSRs stay where they are)"""
+def _host_columns(mapping, parent=False):
+    """the per-row columns of a Mapping on the host, copied once (the CSRs stay where they are); parent: select.parent too"""
     t, sel, rec = mapping.table, mapping.select, mapping.records
     h = lambda x, dt: _host(x, dt)      # noqa: E731
     table = t._replace(seg=h(t.seg, np.uint32), rev=h(t.rev, np.uint8), count=h(t.count, np.uint32), score=h(t.score, np.int32))
     select = sel._replace(flag=h(sel.flag, np.uint8), mapq=h(sel.mapq, np.uint8), sub=h(sel.sub, np.int32), best=h(sel.best, np.int32))
+    if parent:
+        select = select._replace(parent=h(sel.parent, np.int32))
     records = rec._replace(valid=h(rec.valid, np.uint8), rs=h(rec.rs, np.uint32), re=h(rec.re, np.uint32), nm=h(rec.nm, np.uint32))
     return Mapping(table, mapping.edits, mapping.cigars, mapping.ends, select, records)
 
@@ -200,7 +270,34 @@ def write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends=Non
     cm:i, s1:i, s2:i (primaries), MD:Z, cs:Z.  Lines are grouped by read, reads ascending, a read's rows in table order.
     Make the Mapping with ref_order=True: SAM wants the CIGAR of a reverse-strand row in reference order, and so do the difference
     strings -- a row that does not walk the texts raises ValueError.
+    write_sam_pairs() writes the same file with the mate columns of paired reads.
     -> (alignment lines written, rows skipped, unmapped reads)"""
+    return _write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends, qual, ref_name, ref_len, ref_start, ref_base, targets, kept_only, unmapped, header, md, cs,
+                      device, None)
+
+
+def write_sam_pairs(fh, mapping, pairs, seq, ref_text, read_names, read_starts, read_ends=None, qual=None, ref_name=None, ref_len=None, ref_start=0, ref_base=0,
+                    targets=None, kept_only=True, unmapped=True, header=True, md=True, cs=False, device=0):
+    """write_sam() for paired reads: the same device calls, texts and arguments, and the mate columns filled from
+    pairs: the PairSelect of index.map_pairs / kmers.pair_mapping over this Mapping (reads interleaved mate 1, mate 2, ...).
+    Read s is represented by row pairs.row[s] (unmapped where that is -1 or not
+    printable) and that line carries pairs.mapq[s] and TLEN = pairs.tlen[s]; another printable row of the read is printed 0x100 if
+    select made it a secondary or if it is the select.parent of the representative, else 0x800; SEQ, QUAL and tp:A:P go to the
+    representative and the 0x800 rows.  Every line has 0x1 and 0x40 / 0x80 by mate number, 0x20 where the mate's representative is on
+    the reverse strand, 0x8 where the mate is unmapped, and RNEXT / PNEXT = the mate's representative's target ('=' for the line's own)
+    and POS; 0x2 is set on the representatives of a proper pair.  An unmapped read whose mate is mapped stands at the mate's RNAME /
+    POS, with RNEXT '=' and the same PNEXT, and the mate's own RNEXT / PNEXT point there too; two unmapped mates keep * 0 ... * 0 0.
+    Names are printed as given.  write_sam() itself is unchanged: it knows nothing of pairs and writes what it wrote.
+    -> (alignment lines written, rows skipped, unmapped reads)"""
+    if pairs is None:
+        raise ValueError("write_sam_pairs() needs a PairSelect; write_sam() writes unpaired reads")
+    return _write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends, qual, ref_name, ref_len, ref_start, ref_base, targets, kept_only, unmapped, header, md, cs,
+                      device, pairs)
+
+
+def _write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends, qual, ref_name, ref_len, ref_start, ref_base, targets, kept_only, unmapped, header, md, cs,
+               device, pairs):
+    """the body of write_sam() (pairs None) and write_sam_pairs()"""
     sb = _Buf.text(seq)
     seq = sb.obj
     n_text = sb.n
@@ -211,7 +308,7 @@ def write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends=Non
         re_ = np.asarray(read_ends.cpu() if _is_tensor(read_ends) else read_ends, dtype=np.int64).ravel()
     if re_.size != rs_.size or (re_ < rs_).any() or (re_ > n_text).any() or (rs_ < 0).any():
         raise ValueError("read_starts and read_ends must hold one byte offset per read, 0 <= read_starts[s] <= read_ends[s] <= len(seq)")
-    hm = _host_columns(mapping)
+    hm = _host_columns(mapping, parent=pairs is not None)
     n_reads = len(hm.select.best)
     if rs_.size != n_reads:
         raise ValueError("read_starts holds %d reads, the Mapping %d" % (rs_.size, n_reads))
@@ -233,6 +330,12 @@ def write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends=Non
     printable, _, _ = _printable(hm, targets, kept_only)
     mapped = _mapped_reads(hm, printable)
     need = printable & ((hm.select.flag & FLAG_PRIMARY) != 0) & mapped[seg] if len(seg) else np.zeros(0, dtype=bool)
+    if pairs is not None:      # SEQ goes to the representatives and the 0x800 rows; the unmapped reads are those without a representative
+        if n_reads % 2 or len(pairs.row) != n_reads:
+            raise ValueError("pairs must hold one entry per read of the Mapping and the reads must come in pairs")
+        pairs = pairs._replace(row=_host(pairs.row, np.int32), mapq=_host(pairs.mapq, np.uint8), tlen=_host(pairs.tlen, np.int32), flag=_host(pairs.flag, np.uint8))
+        rep, role = _pair_roles(hm, pairs, printable)
+        need, mapped = (role == ROLE_REP) | (role == ROLE_SUPP), rep >= 0
     show = ~mapped if unmapped else np.zeros(n_reads, dtype=bool)
     all_lo = np.concatenate([lo, rs_.astype(np.uint32)])
     all_hi = np.concatenate([np.where(need, hi, lo), np.where(show, re_, rs_).astype(np.uint32)]).astype(np.uint32)
@@ -241,7 +344,7 @@ def write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends=Non
     seq_rows = oriented_rows(seq, plo, phi, prev, True, device)
     qual_rows = oriented_rows(qual, plo, phi, prev, False, device) if qual is not None else None
     lines, skipped, n_unmapped = sam_lines(hm, toff, ctext, seq_rows, read_names, qual_rows, diffs["md"], diffs["cs"], ref_name, ref_len, ref_start, targets,
-                                           kept_only, unmapped, header)
+                                           kept_only, unmapped, header, *(() if pairs is None else (pairs,)))
     for ln in lines:
         fh.write(ln + "\n")
     n_head = len(sam_header(targets, ref_name, ref_len).splitlines()) if header else 0
