@@ -1,5 +1,5 @@
-"""The one scaffold of a Python call across the C-ABI: argument buffers, outputs, the stream rule, the status check, the count-then-emit
-call of the samplers and the base class of the handles.  table, wide, index, hll, kmers and seqs cross the C-ABI through it alone.
+"""The one scaffold of a Python call across the C-ABI: argument buffers, outputs, the stream rule, the status check, the two-pass call of
+the count-scan-emit entry points, the count-then-emit call of the samplers and the base class of the handles.  table, wide, index, hll, kmers and seqs cross the C-ABI through it alone.
 
 numpy arrays (and bytes) are host memory, torch CUDA tensors device memory; a CPU tensor goes through numpy.  torch is optional and
 plumbing only: device buffers and the handle of the current stream."""
@@ -113,6 +113,18 @@ def check(st, name):
     """status of a handle-free call -> KhError naming the entry point"""
     if st != K.KH_OK:
         raise KhError(st, name)
+
+
+def two_pass(fn_name, lead, like, np_dtype, device, trail=()):
+    """a count-scan-emit entry point called twice: the count pass with a null output and capacity 0, an allocation of the exact size
+    where `like` lives, the emit pass -- skipped when the count is zero -> the output.  lead: the arguments before the (out, cap, n)
+    triple; trail: those between the triple and (device, stream), as kh_chain_cigars has them"""
+    fn, n, stream = getattr(K.lib(), fn_name), C.c_uint64(), stream_of(like, device)
+    check(fn(*lead, None, 0, C.byref(n), *trail, device, stream), fn_name)
+    out, ptr = alloc(like, n.value, np_dtype)
+    if n.value:
+        check(fn(*lead, ptr, n.value, C.byref(n), *trail, device, stream), fn_name)
+    return out
 
 
 def count_then_emit(fn_name, words, text, params, device):

@@ -4,12 +4,13 @@
 // tests/cigar_model.py).  Links, strings, orientation, base codes and the 8-bases-per-step compare are those of kh_kernels_edits.h
 // (KedArgs with max_edits = 31, ked_link, ked_extend); link[i] is the distance kh_chain_edits found and bounds the search here.
 //   k_cigar_classify  one lane per anchor: 0 runs for a row that is empty by the range checks, 1 run for link == 0 with dq == dr (no
-//                     text is read); the rest goes onto a worklist of anchor indices, one reservation per wave
+//                     text is read); the rest goes onto a worklist of anchor indices, one reservation per wave (ked_wave_reserve)
 //   k_cigar_wfa       one wavefront per worklist entry, fixed grid, grid-stride over the device-side count: the furthest-reaching points
 //                     with one diagonal per lane (lane l owns d = l - 32), and per lane the MOVE of its diagonal at every level as 2 bits
-//                     of one 64-bit register (31 levels: 62 bits) -- no LDS, no history of F.  At the level that reaches the target the
-//                     traceback walks the moves backwards with lane reads and packs them, level t at bits 2(t - 1), into the link's path
-//                     word; a forward replay of that path (ked_extend on one diagonal per level) counts the row's runs and its I and D bases
+//                     of one 64-bit register (31 levels: 62 bits) -- no LDS, no history of F (kcg_level).  At the level that reaches the
+//                     target the traceback (kcg_traceback) walks the moves backwards with lane reads and packs them, level t at bits
+//                     2(t - 1), into the link's path word; a forward replay of that path (ked_extend on one diagonal per level) counts the
+//                     row's runs and its I and D bases
 //   k_cigar_emit      one lane per anchor with a non-empty row: the single run of a link == 0 row, or the replay of the stored path, runs
 //                     written in forward order; the recurrence does not run again
 // Moves: 1 = X (from F[d] + 1), 2 = I (from F[d + 1] + 1: a base of A), 3 = D (from F[d - 1]: a base of B), 0 = no level -- so the number
@@ -80,6 +81,38 @@ __device__ __forceinline__ bool kcg_replay(const KedArgs& P, const KedLink& L, u
   int v, d;
   return kcg_walk<EMIT>(P, L, path, R, v, d) && v == L.dq && d == L.dr - L.dq;
 }
+// one level of the furthest-reaching points with moves, by whole waves: lane `lane` holds F of diagonal d = lane - 32 at level `level`
+// -> its F at level + 1 before the extension, from the neighbours by lane shuffles; a candidate outside [-d, hi] is dropped, ties go to
+// X, then I, then D, and the move goes into bits 2 level of `moves`
+__device__ __forceinline__ int kcg_level(int F, int d, int hi, uint32_t lane, uint32_t level, uint64_t& moves) {
+  int up = __shfl_up(F, 1), dn = __shfl_down(F, 1);
+  if (lane == 0u) up = KED_NEG;
+  if (lane == 63u) dn = KED_NEG;
+  const int lo = -d;                                         // v + d >= 0
+  const int x = F >= 0 && F + 1 <= hi && F + 1 >= lo ? F + 1 : KED_NEG;
+  const int a = dn >= 0 && dn + 1 <= hi && dn + 1 >= lo ? dn + 1 : KED_NEG;
+  const int b = up >= 0 && up <= hi && up >= lo ? up : KED_NEG;
+  int best = x; uint32_t mv = 1u;
+  if (a > best) { best = a; mv = 2u; }
+  if (b > best) { best = b; mv = 3u; }
+  if (lane == 0u || best < 0) { best = KED_NEG; mv = 0u; }   // (lane 0 is d = -32: stays empty)
+  moves |= (uint64_t)mv << (2u * level);                     // level + 1 at bits 2 level
+  return best;
+}
+// the walk back through the moves from diagonal dd at level `level` to level 0, one lane read per level, by whole waves -> the path
+// word; dd: the diagonal the walk ends on (0: it began at the origin); ok (false on entry: no walk) stays true while every level has a
+// move and dd + 32 stays a lane of this wave
+__device__ __forceinline__ uint64_t kcg_traceback(uint64_t moves, int level, int& dd, bool& ok) {
+  uint64_t path = 0;
+  for (int t = level; ok && t >= 1; --t) {
+    const uint32_t lo32 = (uint32_t)__shfl((int)(uint32_t)moves, dd + 32), hi32 = (uint32_t)__shfl((int)(uint32_t)(moves >> 32), dd + 32);
+    const uint64_t mv = ((((uint64_t)hi32 << 32) | lo32) >> (2 * (t - 1))) & 3ull;
+    path |= mv << (2 * (t - 1));
+    dd += mv == 2ull ? 1 : mv == 3ull ? -1 : 0;
+    ok = mv != 0ull && dd >= -31 && dd <= 31;
+  }
+  return path;
+}
 
 __global__ __launch_bounds__(KED_THREADS) void k_cigar_classify(KedArgs P, const int32_t* __restrict__ link, uint32_t* __restrict__ runs, uint32_t* __restrict__ wl,
                                                                 uint32_t* __restrict__ wl_count) {
@@ -93,15 +126,7 @@ __global__ __launch_bounds__(KED_THREADS) void k_cigar_classify(KedArgs P, const
       queue = e > 0;
       runs[i] = e == 0 && L.dq == L.dr ? 1u : 0u;      // (a queued row: until k_cigar_wfa has settled it)
     }
-    // one reservation per wave, as in k_edits_classify
-    const unsigned long long mask = __ballot(queue);
-    if (mask) {
-      const uint32_t leader = (uint32_t)__builtin_ctzll(mask);
-      uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(wl_count, (uint32_t)__popcll(mask));
-      base = (uint32_t)__shfl((int)base, (int)leader);
-      if (queue) wl[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = i;      // (at most one entry per anchor: base + rank < m)
-    }
+    ked_wave_reserve(queue, lane, i, wl, wl_count);
   }
 }
 
@@ -125,31 +150,12 @@ __global__ __launch_bounds__(KED_THREADS) void k_cigar_wfa(KedArgs P, const int3
       if (F >= 0) F = ked_extend(P, L, F, d, hi);
       if (__ballot(d == td && F == L.dq)) { found = e; break; }
       if (e == bound) break;
-      int up = __shfl_up(F, 1), dn = __shfl_down(F, 1);
-      if (lane == 0u) up = KED_NEG;
-      if (lane == 63u) dn = KED_NEG;
-      const int lo = -d;                                         // v + d >= 0
-      const int x = F >= 0 && F + 1 <= hi && F + 1 >= lo ? F + 1 : KED_NEG;
-      const int a = dn >= 0 && dn + 1 <= hi && dn + 1 >= lo ? dn + 1 : KED_NEG;
-      const int b = up >= 0 && up <= hi && up >= lo ? up : KED_NEG;
-      int best = x; uint32_t mv = 1u;
-      if (a > best) { best = a; mv = 2u; }
-      if (b > best) { best = b; mv = 3u; }
-      if (lane == 0u || best < 0) { best = KED_NEG; mv = 0u; }   // (lane 0 is d = -32: stays empty)
-      F = best;
-      moves |= (uint64_t)mv << (2 * e);                          // level e + 1 at bits 2e
+      F = kcg_level(F, d, hi, lane, (uint32_t)e, moves);
     }
-    // traceback from (found, td) to (0, 0): one lane read per level
-    uint64_t path = 0;
+    // traceback from (found, td) to (0, 0)
     bool ok = found >= 0;
     int dd = td;
-    for (int t = found; ok && t >= 1; --t) {
-      const uint32_t lo32 = (uint32_t)__shfl((int)(uint32_t)moves, dd + 32), hi32 = (uint32_t)__shfl((int)(uint32_t)(moves >> 32), dd + 32);
-      const uint64_t mv = ((((uint64_t)hi32 << 32) | lo32) >> (2 * (t - 1))) & 3ull;
-      path |= mv << (2 * (t - 1));
-      dd += mv == 2ull ? 1 : mv == 3ull ? -1 : 0;
-      ok = mv != 0ull && dd >= -31 && dd <= 31;                  // (dd + 32 stays a lane of this wave)
-    }
+    const uint64_t path = kcg_traceback(moves, found, dd, ok);
     if (lane == 0u) {
       KcgRuns<false> R{nullptr, 0u, 0u, 0u, 0u, 0u, 0u};
       if (ok && dd == 0 && kcg_replay<false>(P, L, path, R)) {

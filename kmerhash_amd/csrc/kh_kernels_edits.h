@@ -3,7 +3,7 @@
 // Unit-cost edit distance of every link of every kept chain (definition: include/kmerhash_amd.h, model: tests/edits_model.py).  A link
 // is anchor i with its predecessor j = pred(i) in the same kept chain; A = the query bases [q_j, q_i), B = the reference bases A faces.
 //   k_edits_classify  one lane per anchor: link or not, the range checks, and where |A| == |B| a direct compare, 8 bases per step; what
-//                     is not settled goes onto a worklist of anchor indices, one reservation per wave
+//                     is not settled goes onto a worklist of anchor indices, one reservation per wave (ked_wave_reserve)
 //   k_edits_wfa       one wavefront per worklist entry, fixed grid, grid-stride over the device-side count: furthest-reaching points
 //                     (Landau-Vishkin) with one diagonal per lane, neighbours by lane shuffles, the points in one register per lane
 // Orientation of k_edits_wfa: lane l owns diagonal d = l - 32 = (offset in B) - (offset in A); F[d] is the furthest offset in A reached
@@ -98,6 +98,19 @@ __device__ __forceinline__ int ked_link(const KedArgs& P, uint32_t i, KedLink& L
   L.a0 = qj; L.b0 = (uint32_t)(rv ? hi : lo); L.rev = rv; L.dq = dq; L.dr = dr;
   return 0;
 }
+// one reservation per wave on a worklist, called by whole waves: the first queued lane adds the wave's count to *wl_count, every queued
+// lane takes its rank behind that base and puts anchor i into that slot of wl; a lane that does not queue writes nothing.  (The slot is
+// used here and not returned: handing it to the caller cost k_edits_classify one more VGPR and k_cigar_classify two.)
+__device__ __forceinline__ void ked_wave_reserve(bool queue, uint32_t lane, uint32_t i, uint32_t* __restrict__ wl, uint32_t* __restrict__ wl_count) {
+  const unsigned long long mask = __ballot(queue);
+  if (mask) {
+    const uint32_t leader = (uint32_t)__builtin_ctzll(mask);
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(wl_count, (uint32_t)__popcll(mask));
+    base = (uint32_t)__shfl((int)base, (int)leader);
+    if (queue) wl[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = i;      // (at most one entry per anchor: base + rank < m)
+  }
+}
 
 __global__ __launch_bounds__(KED_THREADS) void k_edits_classify(KedArgs P, int32_t* __restrict__ out_link, uint32_t* __restrict__ c_over, uint32_t* __restrict__ wl,
                                                                 uint32_t* __restrict__ wl_count) {
@@ -116,15 +129,7 @@ __global__ __launch_bounds__(KED_THREADS) void k_edits_classify(KedArgs P, int32
         if (res == KED_OVER) atomicAdd(&c_over[L.chain], 1u);
       }
     }
-    // one reservation per wave: the first queued lane adds the wave's count, every queued lane takes its rank behind that base
-    const unsigned long long mask = __ballot(queue);
-    if (mask) {
-      const uint32_t leader = (uint32_t)__builtin_ctzll(mask);
-      uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(wl_count, (uint32_t)__popcll(mask));
-      base = (uint32_t)__shfl((int)base, (int)leader);
-      if (queue) wl[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = i;      // (at most one entry per anchor: base + rank < m)
-    }
+    ked_wave_reserve(queue, lane, i, wl, wl_count);
   }
 }
 

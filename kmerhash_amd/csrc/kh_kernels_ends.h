@@ -3,13 +3,14 @@
 // The two ends of every kept chain -- row 2c the HEAD (the read's bases before the chain's first seed), row 2c + 1 the TAIL (those behind
 // its last seed) -- extended from the seed outwards until the read ends or stopping scores better, with the alignment as a run-length row
 // of a CSR (definition: include/kmerhash_amd.h, model: tests/ends_model.py).  Base codes, the match rule, the 8-bases-per-step compare
-// (ked_extend), the moves, the path word, KcgRuns and the replay (kcg_walk) are those of kh_kernels_edits.h / _cigar.h.
+// (ked_extend), the level step with its moves (kcg_level), the traceback into a path word (kcg_traceback), KcgRuns and the replay
+// (kcg_walk) are those of kh_kernels_edits.h / _cigar.h.
 //   k_ends_wfa    one wavefront per end, fixed grid, grid-stride over the 2 n_chains rows (no worklist: an end of no bases costs a wave a
 //                 few loads): the furthest-reaching points with one diagonal per lane (lane l owns d = l - 32), F and the 2-bit moves in
-//                 one register each as in k_cigar_wfa, and per lane the best S = F - clip_cost * e of its own diagonal with the level it
+//                 one register each (kcg_level), and per lane the best S = F - clip_cost * e of its own diagonal with the level it
 //                 was first seen at.  The levels stop where a diagonal holds |A| (or at max_edits); one butterfly over a packed key then
-//                 picks the winner (S, then smaller e, then smaller |d|, then d < 0), the traceback walks the moves back from it with lane
-//                 reads into the end's path word, and a forward replay of that path counts the row's runs
+//                 picks the winner (S, then smaller e, then smaller |d|, then d < 0), kcg_traceback walks the moves back from it with
+//                 lane reads into the end's path word, and a forward replay of that path counts the row's runs
 //   k_ends_emit   one lane per end with a non-empty row: the replay of the stored path, runs written in forward order for a tail and back
 //                 to front for a head -- so that head row, link rows, the last seed and tail row read as one CIGAR
 // A differs from a link in that B's end is free (|B| = min(|A| + max_edits, what rtext has left in that direction), every diagonal may be
@@ -94,36 +95,17 @@ __global__ __launch_bounds__(KED_THREADS) void k_ends_wfa(KenArgs P, uint32_t* _
         if (S > bestS) { bestS = S; bestE = e; }
       }
       if (__ballot(F == E.dq) || e == P.T.max_edits) break;
-      int up = __shfl_up(F, 1), dn = __shfl_down(F, 1);
-      if (lane == 0u) up = KED_NEG;
-      if (lane == 63u) dn = KED_NEG;
-      const int lo = -d;                                         // v + d >= 0
-      const int x = F >= 0 && F + 1 <= hi && F + 1 >= lo ? F + 1 : KED_NEG;
-      const int a = dn >= 0 && dn + 1 <= hi && dn + 1 >= lo ? dn + 1 : KED_NEG;
-      const int b = up >= 0 && up <= hi && up >= lo ? up : KED_NEG;
-      int best = x; uint32_t mv = 1u;
-      if (a > best) { best = a; mv = 2u; }
-      if (b > best) { best = b; mv = 3u; }
-      if (lane == 0u || best < 0) { best = KED_NEG; mv = 0u; }   // (lane 0 is d = -32: stays empty)
-      F = best;
-      moves |= (uint64_t)mv << (2u * e);                         // level e + 1 at bits 2e
+      F = kcg_level(F, d, hi, lane, e, moves);
     }
     // the winner: lane 32 was reached at level 0, so the maximum is a real key
     const uint64_t key = ken_wave_max(bestS > KED_NEG ? ken_key(bestS, bestE, d) : 0ull);
     const int we = 31 - (int)((key >> 6) & 31u), tie = 63 - (int)(key & 63u);
     const int wd = (tie & 1) ? (tie >> 1) : -(tie >> 1);
     const int wF = (int)(uint32_t)(key >> 11) - (1 << 13) + (int)P.clip_cost * we;
-    // traceback from (we, wd) to (0, 0): one lane read per level
-    uint64_t path = 0;
+    // traceback from (we, wd) to (0, 0)
     bool ok = true;
     int dd = wd;
-    for (int t = we; ok && t >= 1; --t) {
-      const uint32_t lo32 = (uint32_t)__shfl((int)(uint32_t)moves, dd + 32), hi32 = (uint32_t)__shfl((int)(uint32_t)(moves >> 32), dd + 32);
-      const uint64_t mv = ((((uint64_t)hi32 << 32) | lo32) >> (2 * (t - 1))) & 3ull;
-      path |= mv << (2 * (t - 1));
-      dd += mv == 2ull ? 1 : mv == 3ull ? -1 : 0;
-      ok = mv != 0ull && dd >= -31 && dd <= 31;                  // (dd + 32 stays a lane of this wave)
-    }
+    const uint64_t path = kcg_traceback(moves, we, dd, ok);
     uint32_t n_runs = 0xffffffffu;                               // lane 0 replays the path; all ones: not confirmed
     if (lane == 0u) {
       KcgRuns<false> R{nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u};

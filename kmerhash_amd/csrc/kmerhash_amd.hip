@@ -365,6 +365,49 @@ class Scratch {
   bool pending_ = false;      // a copy from or to host memory has been queued since the last wait
 };
 
+// ---- the shared halves of a count-scan-emit call ------------------------------------------------------
+// Such a call writes fixed outputs and the offsets of a CSR, learns the CSR's total with one host wait and, given room, emits the rows.
+// empty_rows: the front of a call with nothing to do -- `n_entries` zero offsets, at once in host memory, as one queued memset in device
+// memory (the only case that touches the device).
+inline kh_status empty_rows(uint64_t* out_offsets, uint64_t n_entries, kh_mem where, int device, hipStream_t stream) {
+  if (where == KH_MEM_HOST) { memset(out_offsets, 0, n_entries * sizeof(uint64_t)); return KH_OK; }
+  HIPCHK0(hipSetDevice(device));
+  HIPCHK0(hipMemsetAsync(out_offsets, 0, n_entries * sizeof(uint64_t), stream));
+  return KH_OK;
+}
+// emit_total: the tail, entered with the read of `total` and the copy-backs of the first pass queued (`total` is the host variable that
+// read fills: it holds the count only after the wait, hence the reference).  The one host wait of a device call; *n_total is set before
+// anything can be refused; without an output or rows the call is over; a total beyond `cap` is refused with nothing of `out` touched;
+// else `out` gets a block of its own where it is host memory, emit(device rows) launches the call's emit kernels, and the rows are
+// copied back and the blocks returned in stream order.
+template <typename T, typename Emit>
+kh_status emit_total(Scratch& s, const unsigned long long& total, T* out, uint64_t cap, uint64_t* n_total, kh_mem where, Emit&& emit) {
+  if (!s.sync()) return s.finish();
+  *n_total = total;
+  if (!out || total == 0) return s.finish();
+  if (total > cap) { s.finish(); return KH_ERR_INVALID; }
+  T* drows = nullptr;
+  if (!s.layout([&](Scratch& c) { drows = c.out(out, total, where); })) return s.finish();
+  emit(drows);
+  s.launched();
+  s.copy_back(drows, total);
+  return s.finish_queued();
+}
+// what kh_chain_edits, kh_chain_cigars and kh_chain_ends ask of k, the anchors and the two texts (a position has 31 bits)
+inline bool chain_text_limits_ok(uint32_t k, uint64_t m, uint64_t nq, uint64_t nr, uint32_t ref_base) {
+  const uint64_t lim = uint64_t(1) << 31;
+  return k >= 1 && k <= 64 && m <= (uint64_t(1) << 24) && nq < lim && nr <= lim && ref_base + nr <= lim;
+}
+// ... and their texts and anchors as a KedArgs, inside a layout function: the texts are staged only where there are anchors to face
+// them; pred and chain are absent (null) for the ends.  n_chains and max_edits are the caller's.
+inline void chain_text_args(Scratch& c, KedArgs& P, const void* qtext, uint64_t nq, const void* rtext, uint64_t nr, uint32_t ref_base, const uint32_t* qpos,
+                            const uint32_t* rpos, const uint8_t* rev, const int32_t* pred, const int32_t* chain, uint64_t m, uint32_t k, kh_mem where) {
+  P.qtext = c.in(static_cast<const uint8_t*>(qtext), m ? nq : 0, where); P.rtext = c.in(static_cast<const uint8_t*>(rtext), m ? nr : 0, where);
+  P.qpos = c.in(qpos, m, where); P.rpos = c.in(rpos, m, where); P.rev = c.in(rev, m, where);
+  if (pred) { P.pred = c.in(pred, m, where); P.chain = c.in(chain, m, where); }
+  P.nq = (uint32_t)nq; P.nr = (uint32_t)nr; P.ref_base = ref_base; P.m = (uint32_t)m; P.k = k;
+}
+
 // ---- workspace arena ---------------------------------------------------------------------------
 void arena_reset(kh_table* t) { t->blk = 0; t->off = 0; }
 kh_status arena_take(kh_table* t, size_t bytes, void** out) {
@@ -4204,11 +4247,10 @@ kh_status kh_chain_anchors(const uint32_t* qpos, const uint32_t* rpos, const uin
 kh_status kh_chain_edits(const void* qtext, uint64_t nq, const void* rtext, uint64_t nr, uint32_t ref_base, const uint32_t* qpos, const uint32_t* rpos,
                          const uint8_t* rev, const int32_t* pred, const int32_t* chain, uint64_t m, uint64_t n_chains, uint32_t k, uint32_t max_edits,
                          kh_mem where, int32_t* out_link, uint32_t* c_edits, uint32_t* c_over, int device, void* stream_) {
-  const uint64_t lim = uint64_t(1) << 31;
-  if (k < 1 || k > 64 || max_edits > 31 || m > (uint64_t(1) << 24) || nq >= lim || nr > lim || ref_base + nr > lim) return KH_ERR_INVALID;
+  if (!chain_text_limits_ok(k, m, nq, nr, ref_base) || max_edits > 31) return KH_ERR_INVALID;
   if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || (n_chains && (!c_edits || !c_over))) return KH_ERR_INVALID;
   if (m && (!qpos || !rpos || !rev || !pred || !chain || !out_link || (nq && !qtext) || (nr && !rtext))) return KH_ERR_INVALID;
-  const uint64_t nc = std::min<uint64_t>(n_chains, lim);      // (a chain number is an int32: rows beyond 2^31 are never addressed)
+  const uint64_t nc = std::min<uint64_t>(n_chains, uint64_t(1) << 31);      // (a chain number is an int32: rows beyond 2^31 are never addressed)
   if (m == 0 && where == KH_MEM_HOST) {
     if (nc) { memset(c_edits, 0, nc * sizeof(uint32_t)); memset(c_over, 0, nc * sizeof(uint32_t)); }
     return KH_OK;
@@ -4222,15 +4264,13 @@ kh_status kh_chain_edits(const void* qtext, uint64_t nq, const void* rtext, uint
   KedArgs P{};
   if (!s.layout([&](Scratch& c) {
         wl = c.take<uint32_t>(m); wl_count = c.take<uint32_t>(m ? 1 : 0);
-        P.qtext = c.in(static_cast<const uint8_t*>(qtext), m ? nq : 0, where); P.rtext = c.in(static_cast<const uint8_t*>(rtext), m ? nr : 0, where);
-        P.qpos = c.in(qpos, m, where); P.rpos = c.in(rpos, m, where); P.rev = c.in(rev, m, where);
-        P.pred = c.in(pred, m, where); P.chain = c.in(chain, m, where);
+        chain_text_args(c, P, qtext, nq, rtext, nr, ref_base, qpos, rpos, rev, pred, chain, m, k, where);
         dl = c.out(out_link, m, where); de = c.out(c_edits, nc, where); dov = c.out(c_over, nc, where);
       })) return s.finish();
   if (nc) { s.zero(de, nc * sizeof(uint32_t)); s.zero(dov, nc * sizeof(uint32_t)); }
   if (m) {
     s.zero(wl_count, sizeof(uint32_t));
-    P.nq = (uint32_t)nq; P.nr = (uint32_t)nr; P.ref_base = ref_base; P.m = (uint32_t)m; P.n_chains = (uint32_t)nc; P.k = k; P.max_edits = max_edits;
+    P.n_chains = (uint32_t)nc; P.max_edits = max_edits;
     const uint32_t ncu = (uint32_t)cu_count(device);
     hipLaunchKernelGGL(k_edits_classify, dim3(grid_for(m, KED_THREADS, ncu * 8)), dim3(KED_THREADS), 0, stream, P, dl, dov, wl, wl_count);
     hipLaunchKernelGGL(k_edits_wfa, dim3(grid_for(m, KED_WAVES, ncu * 8)), dim3(KED_THREADS), 0, stream, P, (const uint32_t*)wl, (const uint32_t*)wl_count, dl, de, dov);
@@ -4246,41 +4286,37 @@ kh_status kh_chain_cigars(const void* qtext, uint64_t nq, const void* rtext, uin
                           const uint8_t* rev, const int32_t* pred, const int32_t* chain, uint64_t m, uint64_t n_chains, uint32_t k, const int32_t* link,
                           kh_mem where, uint64_t* out_offsets, uint32_t* out_ops, uint64_t cap_ops, uint64_t* n_ops, uint32_t* c_ins, uint32_t* c_del,
                           int device, void* stream_) {
-  const uint64_t lim = uint64_t(1) << 31;
-  if (k < 1 || k > 64 || m > (uint64_t(1) << 24) || nq >= lim || nr > lim || ref_base + nr > lim) return KH_ERR_INVALID;
+  if (!chain_text_limits_ok(k, m, nq, nr, ref_base)) return KH_ERR_INVALID;
   if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || (n_chains && (!c_ins || !c_del)) || !out_offsets || !n_ops) return KH_ERR_INVALID;
   if (m && (!qpos || !rpos || !rev || !pred || !chain || !link || (nq && !qtext) || (nr && !rtext))) return KH_ERR_INVALID;
-  const uint64_t nc = std::min<uint64_t>(n_chains, lim);      // (a chain number is an int32: rows beyond 2^31 are never addressed)
-  *n_ops = 0;
-  if (m == 0 && where == KH_MEM_HOST) {
-    if (nc) { memset(c_ins, 0, nc * sizeof(uint32_t)); memset(c_del, 0, nc * sizeof(uint32_t)); }
-    out_offsets[0] = 0;
-    return KH_OK;
-  }
+  const uint64_t nc = std::min<uint64_t>(n_chains, uint64_t(1) << 31);      // (a chain number is an int32: rows beyond 2^31 are never addressed)
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  HIPCHK0(hipSetDevice(device));
-  if (m == 0) {      // device memory: three memsets, queued
-    HIPCHK0(hipMemsetAsync(out_offsets, 0, sizeof(uint64_t), stream));
-    if (nc) { HIPCHK0(hipMemsetAsync(c_ins, 0, nc * sizeof(uint32_t), stream)); HIPCHK0(hipMemsetAsync(c_del, 0, nc * sizeof(uint32_t), stream)); }
+  *n_ops = 0;
+  if (m == 0) {      // the offset and the two counters: cleared at once in host memory, by three queued memsets in device memory
+    const kh_status st = empty_rows(out_offsets, 1, where, device, stream);
+    if (st != KH_OK || nc == 0) return st;
+    if (where == KH_MEM_HOST) { memset(c_ins, 0, nc * sizeof(uint32_t)); memset(c_del, 0, nc * sizeof(uint32_t)); return KH_OK; }
+    HIPCHK0(hipMemsetAsync(c_ins, 0, nc * sizeof(uint32_t), stream));
+    HIPCHK0(hipMemsetAsync(c_del, 0, nc * sizeof(uint32_t), stream));
     return KH_OK;
   }
+  HIPCHK0(hipSetDevice(device));
   const uint64_t nst = (m + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
   Scratch s(device, stream);
-  uint32_t *wl = nullptr, *wl_count = nullptr, *runs = nullptr, *di = nullptr, *dd = nullptr, *dops = nullptr;
+  uint32_t *wl = nullptr, *wl_count = nullptr, *runs = nullptr, *di = nullptr, *dd = nullptr;
   uint64_t *paths = nullptr, *doff = nullptr; unsigned long long* ssums = nullptr;
   const int32_t* dlink = nullptr;
   KedArgs P{};
   if (!s.layout([&](Scratch& c) {
         wl = c.take<uint32_t>(m); wl_count = c.take<uint32_t>(1); runs = c.take<uint32_t>(m); paths = c.take<uint64_t>(m);
         ssums = c.take<unsigned long long>(nst + 1);
-        P.qtext = c.in(static_cast<const uint8_t*>(qtext), nq, where); P.rtext = c.in(static_cast<const uint8_t*>(rtext), nr, where);
-        P.qpos = c.in(qpos, m, where); P.rpos = c.in(rpos, m, where); P.rev = c.in(rev, m, where);
-        P.pred = c.in(pred, m, where); P.chain = c.in(chain, m, where); dlink = c.in(link, m, where);
+        chain_text_args(c, P, qtext, nq, rtext, nr, ref_base, qpos, rpos, rev, pred, chain, m, k, where);
+        dlink = c.in(link, m, where);
         doff = c.out(out_offsets, m + 1, where); di = c.out(c_ins, nc, where); dd = c.out(c_del, nc, where);
       })) return s.finish();
   if (nc) { s.zero(di, nc * sizeof(uint32_t)); s.zero(dd, nc * sizeof(uint32_t)); }
   s.zero(wl_count, sizeof(uint32_t));
-  P.nq = (uint32_t)nq; P.nr = (uint32_t)nr; P.ref_base = ref_base; P.m = (uint32_t)m; P.n_chains = (uint32_t)nc; P.k = k; P.max_edits = 31;
+  P.n_chains = (uint32_t)nc; P.max_edits = 31;
   const uint32_t ncu = (uint32_t)cu_count(device);
   hipLaunchKernelGGL(k_cigar_classify, dim3(grid_for(m, KED_THREADS, ncu * 8)), dim3(KED_THREADS), 0, stream, P, dlink, runs, wl, wl_count);
   hipLaunchKernelGGL(k_cigar_wfa, dim3(grid_for(m, KED_WAVES, ncu * 8)), dim3(KED_THREADS), 0, stream, P, dlink, (const uint32_t*)wl, (const uint32_t*)wl_count, runs,
@@ -4290,16 +4326,10 @@ kh_status kh_chain_cigars(const void* qtext, uint64_t nq, const void* rtext, uin
   unsigned long long total = 0;
   s.read(&total, (const unsigned long long*)(ssums + nst));
   s.copy_back(doff, m + 1); s.copy_back(di, nc); s.copy_back(dd, nc);
-  if (!s.sync()) return s.finish();      // the one host wait of a device call: *n_ops
-  *n_ops = total;
-  if (!out_ops || total == 0) return s.finish();
-  if (total > cap_ops) { s.finish(); return KH_ERR_INVALID; }
-  if (!s.layout([&](Scratch& c) { dops = c.out(out_ops, total, where); })) return s.finish();
-  hipLaunchKernelGGL(k_cigar_emit, dim3(grid_for(m, KED_THREADS, ncu * 8)), dim3(KED_THREADS), 0, stream, P, dlink, (const uint64_t*)doff, (const uint64_t*)paths,
-                     (uint64_t)total, dops);
-  s.launched();
-  s.copy_back(dops, total);
-  return s.finish_queued();
+  return emit_total(s, total, out_ops, cap_ops, n_ops, where, [&](uint32_t* dops) {
+    hipLaunchKernelGGL(k_cigar_emit, dim3(grid_for(m, KED_THREADS, ncu * 8)), dim3(KED_THREADS), 0, stream, P, dlink, (const uint64_t*)doff, (const uint64_t*)paths,
+                       (uint64_t)total, dops);
+  });
 }
 // ---- the ends of every kept chain (kernels: kh_kernels_ends.h).  No handle; one pooled block holds the run counts and the path words
 //      (and the staged arrays of a host call), a second one the staged rows of a host call.  Everything is queued on the caller's
@@ -4308,33 +4338,28 @@ kh_status kh_chain_ends(const void* qtext, uint64_t nq, const void* rtext, uint6
                         const uint8_t* rev, uint64_t m, const uint32_t* c_first, const uint32_t* c_last, const uint32_t* q_lo, const uint32_t* q_hi,
                         uint64_t n_chains, uint32_t k, uint32_t max_edits, uint32_t clip_cost, kh_mem where, uint32_t* e_q, uint32_t* e_r, uint32_t* e_edits,
                         uint32_t* e_clip, uint64_t* out_offsets, uint32_t* out_ops, uint64_t cap_ops, uint64_t* n_ops, int device, void* stream_) {
-  const uint64_t lim = uint64_t(1) << 31;
-  if (k < 1 || k > 64 || max_edits > 31 || clip_cost < 1 || clip_cost > 255) return KH_ERR_INVALID;
-  if (m > (uint64_t(1) << 24) || n_chains > (uint64_t(1) << 23) || nq >= lim || nr > lim || ref_base + nr > lim) return KH_ERR_INVALID;
+  if (!chain_text_limits_ok(k, m, nq, nr, ref_base) || max_edits > 31 || clip_cost < 1 || clip_cost > 255 || n_chains > (uint64_t(1) << 23)) return KH_ERR_INVALID;
   if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !out_offsets || !n_ops) return KH_ERR_INVALID;
   if (n_chains && (!c_first || !c_last || !q_lo || !q_hi || !e_q || !e_r || !e_edits || !e_clip)) return KH_ERR_INVALID;
   if (n_chains && m && (!qpos || !rpos || !rev || (nq && !qtext) || (nr && !rtext))) return KH_ERR_INVALID;
-  *n_ops = 0;
-  if (n_chains == 0 && where == KH_MEM_HOST) { out_offsets[0] = 0; return KH_OK; }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
+  *n_ops = 0;
+  if (n_chains == 0) return empty_rows(out_offsets, 1, where, device, stream);
   HIPCHK0(hipSetDevice(device));
-  if (n_chains == 0) { HIPCHK0(hipMemsetAsync(out_offsets, 0, sizeof(uint64_t), stream)); return KH_OK; }
   const uint64_t rows = 2 * n_chains, nst = (rows + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
   Scratch s(device, stream);
-  uint32_t *runs = nullptr, *dq = nullptr, *dr = nullptr, *de = nullptr, *dc = nullptr, *dops = nullptr;
+  uint32_t *runs = nullptr, *dq = nullptr, *dr = nullptr, *de = nullptr, *dc = nullptr;
   uint64_t *paths = nullptr, *doff = nullptr; unsigned long long* ssums = nullptr;
   KenArgs P{};
   if (!s.layout([&](Scratch& c) {
         runs = c.take<uint32_t>(rows); paths = c.take<uint64_t>(rows); ssums = c.take<unsigned long long>(nst + 1);
-        P.T.qtext = c.in(static_cast<const uint8_t*>(qtext), m ? nq : 0, where); P.T.rtext = c.in(static_cast<const uint8_t*>(rtext), m ? nr : 0, where);
-        P.T.qpos = c.in(qpos, m, where); P.T.rpos = c.in(rpos, m, where); P.T.rev = c.in(rev, m, where);
+        chain_text_args(c, P.T, qtext, nq, rtext, nr, ref_base, qpos, rpos, rev, nullptr, nullptr, m, k, where);
         P.c_first = c.in(c_first, n_chains, where); P.c_last = c.in(c_last, n_chains, where);
         P.q_lo = c.in(q_lo, n_chains, where); P.q_hi = c.in(q_hi, n_chains, where);
         dq = c.out(e_q, rows, where); dr = c.out(e_r, rows, where); de = c.out(e_edits, rows, where); dc = c.out(e_clip, rows, where);
         doff = c.out(out_offsets, rows + 1, where);
       })) return s.finish();
-  P.T.nq = (uint32_t)nq; P.T.nr = (uint32_t)nr; P.T.ref_base = ref_base; P.T.m = (uint32_t)m; P.T.n_chains = (uint32_t)n_chains; P.T.k = k; P.T.max_edits = max_edits;
-  P.clip_cost = clip_cost;
+  P.T.n_chains = (uint32_t)n_chains; P.T.max_edits = max_edits; P.clip_cost = clip_cost;
   const uint32_t ncu = (uint32_t)cu_count(device);
   hipLaunchKernelGGL(k_ends_wfa, dim3(grid_for(rows, KED_WAVES, ncu * 8)), dim3(KED_THREADS), 0, stream, P, dq, dr, de, dc, runs, paths);
   scan_counts(stream, (const uint32_t*)runs, rows, ssums, doff);
@@ -4342,16 +4367,10 @@ kh_status kh_chain_ends(const void* qtext, uint64_t nq, const void* rtext, uint6
   unsigned long long total = 0;
   s.read(&total, (const unsigned long long*)(ssums + nst));
   s.copy_back(doff, rows + 1); s.copy_back(dq, rows); s.copy_back(dr, rows); s.copy_back(de, rows); s.copy_back(dc, rows);
-  if (!s.sync()) return s.finish();      // the one host wait of a device call: *n_ops
-  *n_ops = total;
-  if (!out_ops || total == 0) return s.finish();
-  if (total > cap_ops) { s.finish(); return KH_ERR_INVALID; }
-  if (!s.layout([&](Scratch& c) { dops = c.out(out_ops, total, where); })) return s.finish();
-  hipLaunchKernelGGL(k_ends_emit, dim3(grid_for(rows, KED_THREADS, ncu * 8)), dim3(KED_THREADS), 0, stream, P, (const uint64_t*)doff, (const uint64_t*)paths, (uint64_t)total,
-                     dops);
-  s.launched();
-  s.copy_back(dops, total);
-  return s.finish_queued();
+  return emit_total(s, total, out_ops, cap_ops, n_ops, where, [&](uint32_t* dops) {
+    hipLaunchKernelGGL(k_ends_emit, dim3(grid_for(rows, KED_THREADS, ncu * 8)), dim3(KED_THREADS), 0, stream, P, (const uint64_t*)doff, (const uint64_t*)paths, (uint64_t)total,
+                       dops);
+  });
 }
 // ---- primaries, secondaries and a mapping quality per group of chains (kernels: kh_kernels_select.h).  No handle; there is no count to
 //      learn, so a device call only queues: at most one memset, two kernels and the return of the pooled block, and never waits.
@@ -4412,14 +4431,13 @@ kh_status kh_chain_records(const uint32_t* qpos, const uint32_t* rpos, const uin
   if (n_chains && (!c_first || !c_last || !q_lo || !q_hi || !e_q || !e_r || !e_clip || !en_offsets || (n_en && !en_ops))) return KH_ERR_INVALID;
   if (n_chains && (!out_valid || !out_qs || !out_qe || !out_rs || !out_re || !out_qlen || !out_match || !out_block || !out_nm)) return KH_ERR_INVALID;
   if (n_chains && m && (!qpos || !rpos || !rev || !chain || !lk_offsets || (n_lk && !lk_ops))) return KH_ERR_INVALID;
-  *n_ops = 0;
-  if (n_chains == 0 && where == KH_MEM_HOST) { out_offsets[0] = 0; return KH_OK; }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
+  *n_ops = 0;
+  if (n_chains == 0) return empty_rows(out_offsets, 1, where, device, stream);
   HIPCHK0(hipSetDevice(device));
-  if (n_chains == 0) { HIPCHK0(hipMemsetAsync(out_offsets, 0, sizeof(uint64_t), stream)); return KH_OK; }
   const uint64_t nst = (n_chains + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
   Scratch s(device, stream);
-  uint32_t *runs = nullptr, *dops = nullptr; uint64_t* doff = nullptr; unsigned long long* ssums = nullptr;
+  uint32_t* runs = nullptr; uint64_t* doff = nullptr; unsigned long long* ssums = nullptr;
   KrcArgs P{};
   KrcOut O{};
   if (!s.layout([&](Scratch& c) {
@@ -4443,16 +4461,10 @@ kh_status kh_chain_records(const uint32_t* qpos, const uint32_t* rpos, const uin
   s.read(&total, (const unsigned long long*)(ssums + nst));
   s.copy_back(doff, n_chains + 1); s.copy_back(O.valid, n_chains); s.copy_back(O.qs, n_chains); s.copy_back(O.qe, n_chains); s.copy_back(O.rs, n_chains);
   s.copy_back(O.re, n_chains); s.copy_back(O.qlen, n_chains); s.copy_back(O.n_match, n_chains); s.copy_back(O.n_block, n_chains); s.copy_back(O.nm, n_chains);
-  if (!s.sync()) return s.finish();      // the one host wait of a device call: *n_ops
-  *n_ops = total;
-  if (!out_ops || total == 0) return s.finish();
-  if (total > cap_ops) { s.finish(); return KH_ERR_INVALID; }
-  if (!s.layout([&](Scratch& c) { dops = c.out(out_ops, total, where); })) return s.finish();
-  s.zero(dops, total * sizeof(uint32_t));      // (the runs are added onto zeroes)
-  hipLaunchKernelGGL(k_records_emit, dim3(grid_for(n_chains, KRC_WAVES, ncu * 8)), dim3(KRC_THREADS), 0, stream, P, (const uint64_t*)doff, (uint64_t)total, dops);
-  s.launched();
-  s.copy_back(dops, total);
-  return s.finish_queued();
+  return emit_total(s, total, out_ops, cap_ops, n_ops, where, [&](uint32_t* dops) {
+    s.zero(dops, total * sizeof(uint32_t));      // (the runs are added onto zeroes)
+    hipLaunchKernelGGL(k_records_emit, dim3(grid_for(n_chains, KRC_WAVES, ncu * 8)), dim3(KRC_THREADS), 0, stream, P, (const uint64_t*)doff, (uint64_t)total, dops);
+  });
 }
 // ---- a run CSR as text (kernels: kh_kernels_records.h).  The same protocol: count, scan, one host wait for *n_text, emit.
 kh_status kh_cigar_text(const uint64_t* offsets, uint64_t n_rows, const uint32_t* ops, uint64_t n_ops, kh_mem where, uint64_t* out_offsets, uint8_t* out_text,
@@ -4460,15 +4472,14 @@ kh_status kh_cigar_text(const uint64_t* offsets, uint64_t n_rows, const uint32_t
   const uint64_t lim = uint64_t(1) << 31;
   if (n_rows > lim || n_ops > lim || (where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !out_offsets || !n_text) return KH_ERR_INVALID;
   if ((n_rows && !offsets) || (n_rows && n_ops && !ops)) return KH_ERR_INVALID;
-  *n_text = 0;
-  if ((n_rows == 0 || n_ops == 0) && where == KH_MEM_HOST) { memset(out_offsets, 0, (n_rows + 1) * sizeof(uint64_t)); return KH_OK; }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
+  *n_text = 0;
+  if (n_rows == 0 || n_ops == 0) return empty_rows(out_offsets, n_rows + 1, where, device, stream);
   HIPCHK0(hipSetDevice(device));
-  if (n_rows == 0 || n_ops == 0) { HIPCHK0(hipMemsetAsync(out_offsets, 0, (n_rows + 1) * sizeof(uint64_t), stream)); return KH_OK; }
   const uint64_t nst = (n_ops + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
   Scratch s(device, stream);
   uint32_t* bytes = nullptr; uint64_t *boff = nullptr, *doff = nullptr; unsigned long long *ssums = nullptr, *dtotal = nullptr;
-  const uint64_t* din = nullptr; const uint32_t* dops = nullptr; uint8_t* dtext = nullptr;
+  const uint64_t* din = nullptr; const uint32_t* dops = nullptr;
   if (!s.layout([&](Scratch& c) {
         bytes = c.take<uint32_t>(n_ops); boff = c.take<uint64_t>(n_ops + 1); ssums = c.take<unsigned long long>(nst + 1); dtotal = c.take<unsigned long long>(1);
         din = c.in(offsets, n_rows + 1, where); dops = c.in(ops, n_ops, where);
@@ -4482,16 +4493,10 @@ kh_status kh_cigar_text(const uint64_t* offsets, uint64_t n_rows, const uint32_t
   unsigned long long total = 0;
   s.read(&total, (const unsigned long long*)dtotal);
   s.copy_back(doff, n_rows + 1);
-  if (!s.sync()) return s.finish();      // the one host wait of a device call: *n_text
-  *n_text = total;
-  if (!out_text || total == 0) return s.finish();
-  if (total > cap_text) { s.finish(); return KH_ERR_INVALID; }
-  if (!s.layout([&](Scratch& c) { dtext = c.out(out_text, total, where); })) return s.finish();
-  hipLaunchKernelGGL(k_text_emit, dim3(grid_for(n_ops, KTX_THREADS, ncu * 8)), dim3(KTX_THREADS), 0, stream, dops, din, n_rows, n_ops, (const uint64_t*)boff, (uint64_t)total,
-                     dtext);
-  s.launched();
-  s.copy_back(dtext, total);
-  return s.finish_queued();
+  return emit_total(s, total, out_text, cap_text, n_text, where, [&](uint8_t* dtext) {
+    hipLaunchKernelGGL(k_text_emit, dim3(grid_for(n_ops, KTX_THREADS, ncu * 8)), dim3(KTX_THREADS), 0, stream, dops, din, n_rows, n_ops, (const uint64_t*)boff, (uint64_t)total,
+                       dtext);
+  });
 }
 // ---- the anchors of every segment regrouped by target (kernels: kh_kernels_targets.h).  No handle; one pooled block holds the ids, the
 //      group counts and the scan's workspace (and the staged arrays of a host call).  Everything is queued on the caller's stream; the
@@ -4564,14 +4569,13 @@ kh_status kh_record_diffs(const void* qtext, uint64_t nq, const void* rtext, uin
   if (kind > KH_DIFF_MD || n_rows > lim || n_ops > lim || nq > tlim || nr > tlim) return KH_ERR_INVALID;
   if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !out_offsets || !n_text) return KH_ERR_INVALID;
   if (n_rows && (!offsets || !valid || !rev || !q_lo || !q_hi || !rs || !out_ok || (n_ops && !ops) || (nq && !qtext) || (nr && !rtext))) return KH_ERR_INVALID;
-  *n_text = 0;
-  if (n_rows == 0 && where == KH_MEM_HOST) { out_offsets[0] = 0; return KH_OK; }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
+  *n_text = 0;
+  if (n_rows == 0) return empty_rows(out_offsets, 1, where, device, stream);
   HIPCHK0(hipSetDevice(device));
-  if (n_rows == 0) { HIPCHK0(hipMemsetAsync(out_offsets, 0, sizeof(uint64_t), stream)); return KH_OK; }
   const uint64_t nst = (n_rows + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
   Scratch s(device, stream);
-  uint32_t* bytes = nullptr; uint64_t* doff = nullptr; unsigned long long* ssums = nullptr; uint8_t *dok = nullptr, *dtext = nullptr;
+  uint32_t* bytes = nullptr; uint64_t* doff = nullptr; unsigned long long* ssums = nullptr; uint8_t* dok = nullptr;
   KdfArgs P{};
   if (!s.layout([&](Scratch& c) {
         bytes = c.take<uint32_t>(n_rows); ssums = c.take<unsigned long long>(nst + 1);
@@ -4591,16 +4595,10 @@ kh_status kh_record_diffs(const void* qtext, uint64_t nq, const void* rtext, uin
   unsigned long long total = 0;
   s.read(&total, (const unsigned long long*)(ssums + nst));
   s.copy_back(doff, n_rows + 1); s.copy_back(dok, n_rows);
-  if (!s.sync()) return s.finish();      // the one host wait of a device call: *n_text
-  *n_text = total;
-  if (!out_text || total == 0) return s.finish();
-  if (total > cap_text) { s.finish(); return KH_ERR_INVALID; }
-  if (!s.layout([&](Scratch& c) { dtext = c.out(out_text, total, where); })) return s.finish();
-  if (kind == KH_DIFF_CS) hipLaunchKernelGGL((k_diffs_emit<KDF_CS>), grid, dim3(KDF_THREADS), 0, stream, P, (const uint8_t*)dok, (const uint64_t*)doff, (uint64_t)total, dtext);
-  else hipLaunchKernelGGL((k_diffs_emit<KDF_MD>), grid, dim3(KDF_THREADS), 0, stream, P, (const uint8_t*)dok, (const uint64_t*)doff, (uint64_t)total, dtext);
-  s.launched();
-  s.copy_back(dtext, total);
-  return s.finish_queued();
+  return emit_total(s, total, out_text, cap_text, n_text, where, [&](uint8_t* dtext) {
+    if (kind == KH_DIFF_CS) hipLaunchKernelGGL((k_diffs_emit<KDF_CS>), grid, dim3(KDF_THREADS), 0, stream, P, (const uint8_t*)dok, (const uint64_t*)doff, (uint64_t)total, dtext);
+    else hipLaunchKernelGGL((k_diffs_emit<KDF_MD>), grid, dim3(KDF_THREADS), 0, stream, P, (const uint8_t*)dok, (const uint64_t*)doff, (uint64_t)total, dtext);
+  });
 }
 // ---- byte ranges of a text as rows, reverse-strand rows back to front (kernels: kh_kernels_sam.h).  The same protocol.
 kh_status kh_oriented_rows(const void* text, uint64_t n, const uint32_t* lo, const uint32_t* hi, const uint8_t* rev, uint64_t n_rows, uint32_t complement, kh_mem where,
@@ -4608,14 +4606,13 @@ kh_status kh_oriented_rows(const void* text, uint64_t n, const uint32_t* lo, con
   if (complement > 1 || n_rows > (uint64_t(1) << 31) || n > (uint64_t(1) << 32)) return KH_ERR_INVALID;
   if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !out_offsets || !n_text) return KH_ERR_INVALID;
   if (n_rows && (!lo || !hi || !rev || (n && !text))) return KH_ERR_INVALID;
-  *n_text = 0;
-  if (n_rows == 0 && where == KH_MEM_HOST) { out_offsets[0] = 0; return KH_OK; }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
+  *n_text = 0;
+  if (n_rows == 0) return empty_rows(out_offsets, 1, where, device, stream);
   HIPCHK0(hipSetDevice(device));
-  if (n_rows == 0) { HIPCHK0(hipMemsetAsync(out_offsets, 0, sizeof(uint64_t), stream)); return KH_OK; }
   const uint64_t nst = (n_rows + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
   Scratch s(device, stream);
-  uint32_t* len = nullptr; uint64_t* doff = nullptr; unsigned long long* ssums = nullptr; uint8_t* dtext = nullptr;
+  uint32_t* len = nullptr; uint64_t* doff = nullptr; unsigned long long* ssums = nullptr;
   const uint8_t *din = nullptr, *drev = nullptr; const uint32_t *dlo = nullptr, *dhi = nullptr;
   if (!s.layout([&](Scratch& c) {
         len = c.take<uint32_t>(n_rows); ssums = c.take<unsigned long long>(nst + 1);
@@ -4629,16 +4626,10 @@ kh_status kh_oriented_rows(const void* text, uint64_t n, const uint32_t* lo, con
   unsigned long long total = 0;
   s.read(&total, (const unsigned long long*)(ssums + nst));
   s.copy_back(doff, n_rows + 1);
-  if (!s.sync()) return s.finish();      // the one host wait of a device call: *n_text
-  *n_text = total;
-  if (!out_text || total == 0) return s.finish();
-  if (total > cap_text) { s.finish(); return KH_ERR_INVALID; }
-  if (!s.layout([&](Scratch& c) { dtext = c.out(out_text, total, where); })) return s.finish();
-  hipLaunchKernelGGL(k_orient_copy, dim3(grid_for(n_rows, KOR_WAVES, ncu * 8)), dim3(KOR_THREADS), 0, stream, din, n, dlo, dhi, drev, (uint32_t)n_rows, complement,
-                     (const uint64_t*)doff, (uint64_t)total, dtext);
-  s.launched();
-  s.copy_back(dtext, total);
-  return s.finish_queued();
+  return emit_total(s, total, out_text, cap_text, n_text, where, [&](uint8_t* dtext) {
+    hipLaunchKernelGGL(k_orient_copy, dim3(grid_for(n_rows, KOR_WAVES, ncu * 8)), dim3(KOR_THREADS), 0, stream, din, n, dlo, dhi, drev, (uint32_t)n_rows, complement,
+                       (const uint64_t*)doff, (uint64_t)total, dtext);
+  });
 }
 // ---- the concordant chain pair of every read pair (kernel: kh_kernels_pair.h).  No handle and no count to learn: a device call queues
 //      one kernel and never waits; a host call stages through one pooled block.

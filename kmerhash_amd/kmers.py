@@ -11,7 +11,7 @@ import time
 import numpy as np
 
 from . import _capi as K
-from ._call import _Buf, _is_tensor, alloc, check, check_same, stream_of, torch
+from ._call import _Buf, _is_tensor, alloc, check, check_same, stream_of, torch, two_pass
 from .hll import estimate_average_per_rank, hyperloglog64
 from .seqs import (is_syncmer, kmers128_from_fastq, kmers128_from_sequence, kmers_from_fastq, kmers_from_sequence,  # noqa: F401  (re-exported)
                    minimizers_from_fastq, minimizers_from_sequence, syncmers_from_fastq, syncmers_from_sequence)
@@ -185,6 +185,18 @@ ChainEdits = collections.namedtuple("ChainEdits", "link edits over")
 EDITS_NOLINK, EDITS_OVER = -1, -2      # KH_EDITS_NOLINK, KH_EDITS_OVER
 
 
+def _check_text_limits(k, m, tq, tr, ref_base):
+    """what chain_edits, chain_cigars and chain_ends ask of k, the number of anchors and the two texts"""
+    if not 1 <= int(k) <= 64:
+        raise ValueError("k must be 1..64, got %r" % (k,))
+    if m > 2 ** 24:
+        raise ValueError("at most 2^24 anchors per call (batch over reads), got %d" % m)
+    if tq.n >= 2 ** 31:
+        raise ValueError("the query text must be shorter than 2^31 bytes, got %d" % tq.n)
+    if not 0 <= int(ref_base) or int(ref_base) + tr.n > 2 ** 31:
+        raise ValueError("ref_base + len(rtext) must stay within 2^31 (a position has 31 bits), got %r + %d" % (ref_base, tr.n))
+
+
 def chain_edits(qtext, rtext, qpos, rpos, rev, pred, chain, n_chains, k, ref_base=0, max_edits=31, device=0):
     """edit distance of every chain link against the two texts (kh_chain_edits in include/kmerhash_amd.h, which holds the definition):
     anchor i with pred[i] in the same kept chain is a link, A = qtext[q_pred, q_i) and B = the stretch of rtext it faces (rtext covers the
@@ -194,8 +206,6 @@ def chain_edits(qtext, rtext, qpos, rpos, rev, pred, chain, n_chains, k, ref_bas
     edits; edits[c] = the sum of chain c's distances, over[c] = the number of its -2 links.  numpy in (uint8 / bytes, uint32, uint32,
     uint8, int32, int32), numpy out (int32, uint32, uint32); CUDA tensors in, int32 tensors out on the current stream, without a wait.
     At most 2^24 anchors per call."""
-    if not 1 <= int(k) <= 64:
-        raise ValueError("k must be 1..64, got %r" % (k,))
     if not 0 <= int(max_edits) <= 31:
         raise ValueError("max_edits must be 0..31 (one diagonal per lane of a wavefront), got %r" % (max_edits,))
     if not 0 <= int(n_chains) <= 2 ** 31:
@@ -206,12 +216,7 @@ def chain_edits(qtext, rtext, qpos, rpos, rev, pred, chain, n_chains, k, ref_bas
     check_same("the texts, qpos, rpos, rev, pred and chain must live in the same memory", tq, tr, qb, rb, vb, pb, cb, length=False)
     m, nc = qb.n, int(n_chains)
     check_same("qpos, rpos, rev, pred and chain must have one entry per anchor, got %d, %d, %d, %d and %d" % (m, rb.n, vb.n, pb.n, cb.n), qb, rb, vb, pb, cb)
-    if m > 2 ** 24:
-        raise ValueError("at most 2^24 anchors per call (batch over reads), got %d" % m)
-    if tq.n >= 2 ** 31:
-        raise ValueError("the query text must be shorter than 2^31 bytes, got %d" % tq.n)
-    if not 0 <= int(ref_base) or int(ref_base) + tr.n > 2 ** 31:
-        raise ValueError("ref_base + len(rtext) must stay within 2^31 (a position has 31 bits), got %r + %d" % (ref_base, tr.n))
+    _check_text_limits(k, m, tq, tr, ref_base)
     (link, lptr), (edits, eptr), (over, optr) = (alloc(qb, size, dt, empty=True) for size, dt in ((m, np.int32), (nc, np.uint32), (nc, np.uint32)))
     if m or nc:
         check(K.lib().kh_chain_edits(tq.ptr_or_null, tq.n, tr.ptr_or_null, tr.n, int(ref_base), *(b.ptr_or_null for b in (qb, rb, vb, pb, cb)), m, nc, int(k),
@@ -233,8 +238,6 @@ def chain_cigars(qtext, rtext, qpos, rpos, rev, pred, chain, n_chains, k, link, 
     the exact size.  numpy in, numpy out (uint64, uint32, uint32, uint32); CUDA tensors in, tensors out on the current stream (int64, then
     int32 holding the uint32 bits); the call waits for the stream once per pass, to learn the number of runs.  At most 2^24 anchors per
     call.  cigar_string() turns the rows of one chain into text."""
-    if not 1 <= int(k) <= 64:
-        raise ValueError("k must be 1..64, got %r" % (k,))
     if not 0 <= int(n_chains) <= 2 ** 31:
         raise ValueError("n_chains must be 0..2^31, got %r" % (n_chains,))
     tq, tr = _Buf.text(qtext), _Buf.text(rtext)
@@ -244,22 +247,12 @@ def chain_cigars(qtext, rtext, qpos, rpos, rev, pred, chain, n_chains, k, link, 
     m, nc = qb.n, int(n_chains)
     check_same("qpos, rpos, rev, pred, chain and link must have one entry per anchor, got %d, %d, %d, %d, %d and %d" % (m, rb.n, vb.n, pb.n, cb.n, lb.n),
                qb, rb, vb, pb, cb, lb)
-    if m > 2 ** 24:
-        raise ValueError("at most 2^24 anchors per call (batch over reads), got %d" % m)
-    if tq.n >= 2 ** 31:
-        raise ValueError("the query text must be shorter than 2^31 bytes, got %d" % tq.n)
-    if not 0 <= int(ref_base) or int(ref_base) + tr.n > 2 ** 31:
-        raise ValueError("ref_base + len(rtext) must stay within 2^31 (a position has 31 bits), got %r + %d" % (ref_base, tr.n))
+    _check_text_limits(k, m, tq, tr, ref_base)
     (offs, optr), (ins, iptr), (dels, dptr) = alloc(qb, m + 1, np.uint64, zero=True), alloc(qb, nc, np.uint32, empty=True), alloc(qb, nc, np.uint32, empty=True)
     if m == 0 and (nc == 0 or not qb.dev):      # nothing to queue: the zeroed host arrays are the answer
         return ChainCigars(offs, alloc(qb, 0, np.uint32)[0], ins, dels)
-    fn, n, stream = K.lib().kh_chain_cigars, C.c_uint64(), stream_of(qb, device)
     args = (tq.ptr_or_null, tq.n, tr.ptr_or_null, tr.n, int(ref_base), *(b.ptr_or_null for b in (qb, rb, vb, pb, cb)), m, nc, int(k), lb.ptr_or_null, qb.where, optr)
-    check(fn(*args, None, 0, C.byref(n), iptr, dptr, device, stream), "kh_chain_cigars")
-    ops, pptr = alloc(qb, n.value, np.uint32)
-    if n.value:
-        check(fn(*args, pptr, n.value, C.byref(n), iptr, dptr, device, stream), "kh_chain_cigars")
-    return ChainCigars(offs, ops, ins, dels)
+    return ChainCigars(offs, two_pass("kh_chain_cigars", args, qb, np.uint32, device, trail=(iptr, dptr)), ins, dels)
 
 
 def _host(x, dtype):
@@ -305,8 +298,6 @@ def chain_ends(qtext, rtext, qpos, rpos, rev, first, last, q_lo, q_hi, k, ref_ba
     then emit: two calls, one allocation of the exact size.  numpy in, numpy out (uint32 x 4, uint64, uint32); CUDA tensors in, tensors out
     on the current stream (int32 holding the uint32 bits, int64 offsets); the call waits for the stream once per pass, to learn the number
     of runs.  At most 2^24 anchors and 2^23 chains per call.  read_cigar() and extended_intervals() put the ends onto a ChainTable."""
-    if not 1 <= int(k) <= 64:
-        raise ValueError("k must be 1..64, got %r" % (k,))
     if not 0 <= int(max_edits) <= 31:
         raise ValueError("max_edits must be 0..31 (one diagonal per lane of a wavefront), got %r" % (max_edits,))
     if not 1 <= int(clip_cost) <= 255:
@@ -318,26 +309,16 @@ def chain_ends(qtext, rtext, qpos, rpos, rev, first, last, q_lo, q_hi, k, ref_ba
     m, nc = qb.n, fb.n
     check_same("qpos, rpos and rev must have one entry per anchor, got %d, %d and %d" % (m, rb.n, vb.n), qb, rb, vb)
     check_same("first, last, q_lo and q_hi must have one entry per chain, got %d, %d, %d and %d" % (nc, lb.n, ob.n, hb.n), fb, lb, ob, hb)
-    if m > 2 ** 24:
-        raise ValueError("at most 2^24 anchors per call (batch over reads), got %d" % m)
+    _check_text_limits(k, m, tq, tr, ref_base)
     if nc > 2 ** 23:
         raise ValueError("at most 2^23 chains per call (batch over reads), got %d" % nc)
-    if tq.n >= 2 ** 31:
-        raise ValueError("the query text must be shorter than 2^31 bytes, got %d" % tq.n)
-    if not 0 <= int(ref_base) or int(ref_base) + tr.n > 2 ** 31:
-        raise ValueError("ref_base + len(rtext) must stay within 2^31 (a position has 31 bits), got %r + %d" % (ref_base, tr.n))
     nums = [alloc(fb, 2 * nc, np.uint32, empty=True) for _ in range(4)]
     offs, optr = alloc(fb, 2 * nc + 1, np.uint64, zero=True)
     if nc == 0:      # nothing to queue: the zeroed offset is the answer
         return ChainEnds(*(a for a, _ in nums), offs, alloc(fb, 0, np.uint32)[0])
-    fn, n, stream = K.lib().kh_chain_ends, C.c_uint64(), stream_of(fb, device)
     args = (tq.ptr_or_null, tq.n, tr.ptr_or_null, tr.n, int(ref_base), qb.ptr_or_null, rb.ptr_or_null, vb.ptr_or_null, m, fb.ptr, lb.ptr, ob.ptr, hb.ptr, nc,
             int(k), int(max_edits), int(clip_cost), fb.where, *(p for _, p in nums), optr)
-    check(fn(*args, None, 0, C.byref(n), device, stream), "kh_chain_ends")
-    ops, pptr = alloc(fb, n.value, np.uint32)
-    if n.value:
-        check(fn(*args, pptr, n.value, C.byref(n), device, stream), "kh_chain_ends")
-    return ChainEnds(*(a for a, _ in nums), offs, ops)
+    return ChainEnds(*(a for a, _ in nums), offs, two_pass("kh_chain_ends", args, fb, np.uint32, device))
 
 
 ChainSelect = collections.namedtuple("ChainSelect", "parent rank mapq flag sub nsub best")
@@ -577,14 +558,9 @@ def chain_records(qpos, rpos, rev, chain, cigars, first, last, q_lo, q_hi, ends,
     offs, optr = alloc(fb, nc + 1, np.uint64, zero=True)
     if nc == 0:      # nothing to queue: the zeroed offset is the answer
         return ChainRecords(valid, *(a for a, _ in nums), offs, alloc(fb, 0, np.uint32)[0])
-    fn, n, stream = K.lib().kh_chain_records, C.c_uint64(), stream_of(fb, device)
     args = (qb.ptr_or_null, rb.ptr_or_null, vb.ptr_or_null, cb.ptr_or_null, m, lo_.ptr if m else None, lp.ptr_or_null, lp.n, fb.ptr, lb.ptr, ob.ptr, hb.ptr, nc,
             eq.ptr, er.ptr, ec.ptr, eo.ptr, ep.ptr_or_null, ep.n, int(k), 1 if ref_order else 0, fb.where, vptr, *(p for _, p in nums), optr)
-    check(fn(*args, None, 0, C.byref(n), device, stream), "kh_chain_records")
-    ops, pptr = alloc(fb, n.value, np.uint32)
-    if n.value:
-        check(fn(*args, pptr, n.value, C.byref(n), device, stream), "kh_chain_records")
-    return ChainRecords(valid, *(a for a, _ in nums), offs, ops)
+    return ChainRecords(valid, *(a for a, _ in nums), offs, two_pass("kh_chain_records", args, fb, np.uint32, device))
 
 
 def cigar_text(offsets, ops, device=0):
@@ -602,13 +578,7 @@ def cigar_text(offsets, ops, device=0):
     toff, tptr = alloc(ob, rows + 1, np.uint64, zero=True)
     if rows == 0 or pb.n == 0:      # nothing to queue: the zeroed offsets are the answer
         return toff, alloc(ob, 0, np.uint8)[0]
-    fn, n, stream = K.lib().kh_cigar_text, C.c_uint64(), stream_of(ob, device)
-    args = (ob.ptr, rows, pb.ptr, pb.n, ob.where, tptr)
-    check(fn(*args, None, 0, C.byref(n), device, stream), "kh_cigar_text")
-    text, xptr = alloc(ob, n.value, np.uint8)
-    if n.value:
-        check(fn(*args, xptr, n.value, C.byref(n), device, stream), "kh_cigar_text")
-    return toff, text
+    return toff, two_pass("kh_cigar_text", (ob.ptr, rows, pb.ptr, pb.n, ob.where, tptr), ob, np.uint8, device)
 
 
 def paf_lines(mapping, text_offsets, text, read_names, ref_name=None, ref_len=None, k=None, ref_start=0, kept_only=True, targets=None, cs=None):

@@ -2,12 +2,11 @@
 device (kh_record_diffs, kh_oriented_rows in include/kmerhash_amd.h, which holds the definitions); the header, the flags and the
 lines are host formatting beside kmers.paf_lines."""
 import collections
-import ctypes as C
 
 import numpy as np
 
 from . import _capi as K
-from ._call import _Buf, _is_tensor, alloc, check, check_same, stream_of, torch
+from ._call import _Buf, _is_tensor, alloc, check_same, torch, two_pass
 from .kmers import FLAG_KEPT, FLAG_PRIMARY, Mapping, _host, cigar_text
 
 RecordDiffs = collections.namedtuple("RecordDiffs", "ok offsets text")
@@ -39,14 +38,9 @@ def record_diffs(qtext, rtext, records, rev, q_lo, q_hi, kind="cs", ref_base=0, 
     offs, optr = alloc(vb, rows + 1, np.uint64, zero=True)
     if rows == 0:      # nothing to queue: the zeroed offset is the answer
         return RecordDiffs(ok, offs, alloc(vb, 0, np.uint8)[0])
-    fn, n, stream = K.lib().kh_record_diffs, C.c_uint64(), stream_of(vb, device)
     args = (qb.ptr_or_null, qb.n, rb.ptr_or_null, rb.n, int(ref_base), ob.ptr, pb.ptr_or_null, pb.n, vb.ptr, eb.ptr, lb.ptr, hb.ptr, sb.ptr, rows, DIFF_KINDS[kind], vb.where,
             kptr, optr)
-    check(fn(*args, None, 0, C.byref(n), device, stream), "kh_record_diffs")
-    text, xptr = alloc(vb, n.value, np.uint8)
-    if n.value:
-        check(fn(*args, xptr, n.value, C.byref(n), device, stream), "kh_record_diffs")
-    return RecordDiffs(ok, offs, text)
+    return RecordDiffs(ok, offs, two_pass("kh_record_diffs", args, vb, np.uint8, device))
 
 
 def oriented_rows(text, lo, hi, rev, complement=True, device=0):
@@ -64,13 +58,8 @@ def oriented_rows(text, lo, hi, rev, complement=True, device=0):
     offs, optr = alloc(lb, rows + 1, np.uint64, zero=True)
     if rows == 0:
         return offs, alloc(lb, 0, np.uint8)[0]
-    fn, n, stream = K.lib().kh_oriented_rows, C.c_uint64(), stream_of(lb, device)
     args = (tb.ptr_or_null, tb.n, lb.ptr, hb.ptr, eb.ptr, rows, 1 if complement else 0, lb.where, optr)
-    check(fn(*args, None, 0, C.byref(n), device, stream), "kh_oriented_rows")
-    out, xptr = alloc(lb, n.value, np.uint8)
-    if n.value:
-        check(fn(*args, xptr, n.value, C.byref(n), device, stream), "kh_oriented_rows")
-    return offs, out
+    return offs, two_pass("kh_oriented_rows", args, lb, np.uint8, device)
 
 
 def sam_header(targets=None, ref_name=None, ref_len=None):

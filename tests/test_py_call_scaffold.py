@@ -124,6 +124,71 @@ def test_stream_rule_and_status_check_on_the_host():
     assert e.value.status == K.KH_ERR_INVALID and type(e.value) is K.KhError
 
 
+class FakeRows:
+    """stands in for the loaded library: a count-scan-emit entry point that records its calls, reports `count` rows and, given room,
+    fills them with 1, 2, 3, ...; statuses: one per call"""
+
+    def __init__(self, count, statuses=(K.KH_OK, K.KH_OK), itemsize=4):
+        self.count, self.statuses, self.itemsize, self.calls = count, list(statuses), itemsize, []
+
+    def kh_fake_rows(self, *args):
+        self.calls.append(args)
+        lead, (out, cap, n), rest = args[:3], args[3:6], args[6:]
+        n._obj.value = self.count
+        if out is not None and cap >= self.count:
+            C.memmove(out, np.arange(1, self.count + 1, dtype={4: np.uint32, 1: np.uint8}[self.itemsize]).ctypes.data, self.count * self.itemsize)
+        return self.statuses[len(self.calls) - 1]
+
+
+def two_pass_with(monkeypatch, fake, np_dtype, trail=()):
+    monkeypatch.setattr(K, "lib", lambda: fake)
+    return S.two_pass("kh_fake_rows", ("lead", 7, None), S.HOST, np_dtype, 3, trail=trail)
+
+
+@pytest.mark.parametrize("np_dtype,trail", [(np.uint32, ()), (np.uint8, ()), (np.uint32, (0x1111, 0x2222))])
+def test_two_pass_counts_allocates_and_emits(monkeypatch, np_dtype, trail):
+    fake = FakeRows(5, itemsize=np.dtype(np_dtype).itemsize)
+    out = two_pass_with(monkeypatch, fake, np_dtype, trail)
+    assert type(out) is np.ndarray and out.dtype == np_dtype and out.tolist() == [1, 2, 3, 4, 5]
+    first, second = fake.calls
+    assert first[:3] == second[:3] == ("lead", 7, None), "the leading arguments of both passes"
+    assert first[3] is None and first[4] == 0, "the count pass: a null output, capacity 0"
+    assert second[3] == out.ctypes.data and second[4] == 5, "the emit pass: the exact allocation and the count as capacity"
+    assert first[5]._obj is second[5]._obj and second[5]._obj.value == 5
+    # what follows the triple: the trailing arguments (kh_chain_cigars: its two counter arrays), then device and stream
+    assert first[6:] == second[6:] == trail + (3, None)
+
+
+@pytest.mark.parametrize("np_dtype", [np.uint32, np.uint8])
+def test_two_pass_makes_one_call_when_nothing_is_counted(monkeypatch, np_dtype):
+    fake = FakeRows(0)
+    out = two_pass_with(monkeypatch, fake, np_dtype)
+    assert len(fake.calls) == 1 and fake.calls[0][3] is None and fake.calls[0][4] == 0
+    assert type(out) is np.ndarray and out.dtype == np_dtype and out.shape == (0,), "empty, of the right dtype, in host memory"
+
+
+@pytest.mark.parametrize("statuses,n_calls", [((K.KH_ERR_INVALID, K.KH_OK), 1), ((K.KH_OK, K.KH_ERR_INVALID), 2)])
+def test_two_pass_raises_the_status_of_either_pass(monkeypatch, statuses, n_calls):
+    fake = FakeRows(5, statuses)
+    with pytest.raises(K.KhError, match="KH_ERR_INVALID: kh_fake_rows") as e:
+        two_pass_with(monkeypatch, fake, np.uint32)
+    assert e.value.status == K.KH_ERR_INVALID and len(fake.calls) == n_calls
+
+
+@needs_torch
+def test_two_pass_takes_memory_and_stream_from_the_buffer(monkeypatch):
+    """a device buffer: the output is allocated where it lives and the stream rule is asked for that buffer and the call's device
+    (no GPU: the allocator and the stream rule are stood in for)"""
+    fake, asked = FakeRows(0), []
+    far = S._Buf.memory()
+    far.where, far.device = K.KH_MEM_DEVICE, "cuda:3"
+    monkeypatch.setattr(K, "lib", lambda: fake)
+    monkeypatch.setattr(S, "stream_of", lambda like, device: asked.append((like, device)) or 0xABC)
+    monkeypatch.setattr(S, "alloc", lambda like, shape, np_dtype: asked.append((like, shape, np_dtype)) or ("the tensor", 0x5000))
+    assert S.two_pass("kh_fake_rows", ("lead", 7, None), far, np.uint8, 3) == "the tensor"
+    assert asked == [(far, 3), (far, 0, np.uint8)] and fake.calls[0][6:] == (3, 0xABC)
+
+
 class FakeLib:
     """stands in for the loaded library: counts destroy calls, answers one status"""
 
