@@ -406,7 +406,16 @@ kh_status kh_hll_estimate_registers(const uint8_t* registers_host, uint32_t prec
  *      table rule for rule (float load thresholds, one doubling per insert() call while size >= max_load, the trailing reserve(size()),
  *      batch erase never shrinks, first value wins, std::plus wraps at 32 bits, KH_ERR_PROBE_OVERFLOW leaves the table unchanged);
  *      its info array (kh_wide_export_info) is the canonical Robin Hood layout of the key set at the capacity.  A distinct handle type:
- *      a kh_wtable passed to a kh_table entry point does not compile. */
+ *      a kh_wtable passed to a kh_table entry point does not compile.
+ *      ALIGNMENT: A DEVICE ARRAY OF 16-BYTE KEYS MUST BE 16-BYTE ALIGNED wherever a key is moved as one 16-byte access.  Every entry point
+ *      that READS such an array with KH_MEM_DEVICE and n > 0 -- kh_wide_insert / _insert_reduce_plus / _insert_reduce / _insert_feed,
+ *      kh_wide_count / _find / _find_compact / _erase, kh_wide_hash_batch, kh_wide_shard_permute, kh_hll_update_wide,
+ *      kh_wide_syncmer_mask and kh_wide_index_build / _append / _erase / _count / _find -- and every one that WRITES one with a 16-byte
+ *      store per key -- out_keys_dev of kh_wide_shard_permute, out_kmers of kh_kmers128_from_sequence / _from_fastq and their _pos
+ *      forms and of kh_syncmers128_from_sequence / _from_fastq -- returns KH_ERR_INVALID otherwise, before anything is launched: the
+ *      handle, its table or registers, *n_out (0) and every output array are untouched (a streamed insert stays open with nothing
+ *      fed).  Host arrays may have any alignment, they are staged.  Only out_keys of kh_wide_find_compact and of kh_wide_select_values
+ *      are written as two 64-bit words per key: 8-byte alignment is enough there. */
 typedef struct kh_wtable kh_wtable;
 kh_status kh_wide_create(kh_wtable** out, kh_kind kind /* KH_KIND_LINEARPROBE: KH_ERR_UNSUPPORTED */, kh_hash hash, uint64_t seed,
                          uint64_t capacity, float min_load_factor, float max_load_factor, int device);
@@ -459,8 +468,8 @@ kh_status kh_wide_insert_end(kh_wtable* t, uint64_t* n_inserted);
 kh_status kh_wide_insert_abort(kh_wtable* t);
 /* kh_shard_permute for 16-byte keys: rank = hash of the 16 bytes (what kh_wide_hash_batch computes) & (nranks-1), or % nranks when
  *      nranks is not a power of two; pairs grouped by destination rank, rank 0 first, INPUT ORDER KEPT inside a rank.  Device buffers
- *      only; nranks 1..64; out_keys_dev == NULL: count only; n == 0: counts of 0.  keys_dev and out_keys_dev MUST BE 16-BYTE ALIGNED
- *      (every key is read and written as one 16-byte access): KH_ERR_INVALID otherwise. */
+ *      only; nranks 1..64; out_keys_dev == NULL: count only; n == 0: counts of 0.  keys_dev and out_keys_dev: the alignment rule of the wide keys
+ *      (above kh_wide_create). */
 kh_status kh_wide_shard_permute(kh_hash hash, uint64_t seed, uint32_t nranks,
                                 const uint64_t* keys_dev /* u64[2n] */, const uint32_t* vals_dev /* may be NULL */, uint64_t n,
                                 uint64_t* out_keys_dev /* u64[2n]; NULL = count only */, uint32_t* out_vals_dev,
@@ -480,7 +489,7 @@ kh_status kh_kmers128_from_fastq(const void* text, uint64_t n, uint32_t k /*1..6
  *      calls, kh_hll_update and kh_hll_update_via_hashval.  Whether 8-byte and 16-byte keys belong in ONE estimate is the caller's
  *      business: the same k-mer hashes differently at the two widths.
  *      kh_hll_update_wide: the registers afterwards equal those after kh_hll_update_via_hashval of kh_wide_hash_batch(keys) with the
- *      estimator's hash and seed.  Device keys must be 16-byte aligned (one 16-byte load per key): KH_ERR_INVALID otherwise.
+ *      estimator's hash and seed.  Device keys: the alignment rule of the wide keys (above kh_wide_create).
  *      kh_hll_update_from_sequence / _from_fastq: ONE pass text -> windows -> canonical form -> hash -> registers, 1 byte read per base
  *      and no k-mer written.  The registers afterwards equal those after kh_hll_update of kh_kmers_from_sequence / _from_fastq (k <= 32:
  *      the 8-byte k-mer is hashed) or kh_hll_update_wide of kh_kmers128_from_sequence / _from_fastq (k > 32: the 16-byte k-mer {w0, w1}),

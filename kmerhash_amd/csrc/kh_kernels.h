@@ -104,7 +104,8 @@ __device__ __forceinline__ uint64_t kh_find_pos(const KhSlot* __restrict__ slots
 // ---------------------------------------------------------------------------------------------
 // A key of KW 64-bit words as the key-width-generic front end (batched hashing, sharding, HyperLogLog) sees it: the register type,
 // the seed its hash takes (only 8-byte keys have a key transform), one load / one store per key (16-byte keys: one dwordx4 access,
-// so their arrays must be 16-byte aligned -- the host entry points check), and the keys a lane of the shard kernels owns.
+// so their arrays must be 16-byte aligned -- every host entry point that takes a device array of 16-byte keys checks, for these kernels
+// and for the kw_* ones: wide_keys_aligned in kmerhash_amd.hip), and the keys a lane of the shard kernels owns.
 // ---------------------------------------------------------------------------------------------
 template <int KW> struct KhKey;
 template <> struct KhKey<1> {
@@ -483,6 +484,9 @@ __global__ void k_flag_tile_sums(const uint8_t* __restrict__ flags, uint64_t n, 
 // flight at once), the 16 chunk scans run in registers with ONE barrier between them and the write-out.  (The earlier
 // version swept 16384 counts at a time with three barriers and a dependent load per sweep: 77 us for the 65537 counts of
 // a 10^8-key partition.)
+// `in` is never a caller's pointer: every launch passes counts taken from the table's workspace arena or from a call's Scratch, both
+// carved at 256-byte boundaries, so the `aligned` branch is the one that runs and the word-by-word branch of a misaligned `in` is
+// unreachable from the C-ABI (kept as the tail of a chunk needs it anyway); no test passes a misaligned pointer here.
 #define KH_SCAN_THREADS 512
 #define KH_SCAN_CHUNKS 16
 #define KH_SCAN_CHUNK (KH_SCAN_THREADS * 4)

@@ -49,6 +49,8 @@ __device__ __forceinline__ uint64_t ked_codes(uint64_t w) {
   return c | ked_nonzero(u ^ expect);
 }
 // text[pos, pos + 8) with byte t in bits 8t..; bytes at or beyond n come as 0 (no base).  pos <= n.
+// (The padding bounds the READ, not the result: ked_extend cuts every run at hi, which lies inside both strings, so no caller ever
+//  looks at a byte at or beyond n, and no result test can tell the zero from whatever lies behind the text.)
 __device__ __forceinline__ uint64_t ked_load_up(const uint8_t* __restrict__ text, uint32_t n, uint32_t pos) {
   uint64_t w = 0;
   if (n - pos >= 8u) { __builtin_memcpy(&w, text + pos, 8); return w; }

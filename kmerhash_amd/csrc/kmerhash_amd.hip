@@ -231,6 +231,13 @@ kh_status hip_fail(kh_table* t, const char* call, hipError_t e) {
   if (t) t->err = std::string(call) + ": " + hipGetErrorString(e);
   return hip_status(e);
 }
+// The wide-key alignment rule (kmerhash_amd.h, "wide keys"): the kernels read a 16-byte key with one dwordx4 load, so an entry point
+// refuses a device array of 16-byte keys that is not 16-byte aligned before it launches or changes anything.  kw: 64-bit words per key
+// (8-byte keys pass); host arrays pass at any alignment, they are staged into aligned device memory.
+inline bool wide_keys_aligned(uint32_t kw, const void* keys, kh_mem where) {
+  return kw != 2 || where != KH_MEM_DEVICE || (reinterpret_cast<uintptr_t>(keys) & 15u) == 0;
+}
+const char* const kWideKeysMisaligned = "a device array of 16-byte keys must be 16-byte aligned";
 // HIPCHK: in a function with a table `t` in scope, whose error text it sets; HIPCHK0: where there is no table
 #define HIPCHK_T(table, call)                                                                          \
   do {                                                                                                 \
@@ -2394,7 +2401,7 @@ inline KhSeed make_seed(uint64_t seed, kh_key_transform xf, uint32_t k) { return
 // Hash::operator()(Key const*, count, out) for keys of kw 64-bit words: stage host keys in, hash, copy the hashes out
 kh_status hash_batch_impl(uint32_t kw, kh_hash hash, KhSeed seed, const void* keys, uint64_t n, kh_mem where, uint64_t* out, int device, void* stream_) {
   if (n == 0) return KH_OK;
-  if (!keys || !out || (int)hash < 0 || (int)hash > 3) return KH_ERR_INVALID;
+  if (!keys || !out || (int)hash < 0 || (int)hash > 3 || !wide_keys_aligned(kw, keys, where)) return KH_ERR_INVALID;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   HIPCHK0(hipSetDevice(device));
   Scratch s(device, stream);
@@ -2416,7 +2423,7 @@ kh_status shard_permute_impl(uint32_t kw, kh_hash hash, uint64_t seed_, kh_key_t
   if (!keys || (out_keys && vals && !out_vals)) return KH_ERR_INVALID;
   const uint64_t tile = kw == 2 ? KH_SHARD_TILE(2) : KH_SHARD_TILE(1);
   if (kw == 2) {
-    if (((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(out_keys)) & 15u) != 0) return KH_ERR_INVALID;     // one 16-byte access per key
+    if (!wide_keys_aligned(2, keys, KH_MEM_DEVICE) || !wide_keys_aligned(2, out_keys, KH_MEM_DEVICE)) return KH_ERR_INVALID;     // (out_keys too: one 16-byte store per key)
     if ((n + tile - 1) / tile > 0x7FFFFFFFull) return KH_ERR_UNSUPPORTED;
   }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -2600,7 +2607,7 @@ kh_status kmers_impl(uint32_t kw, const void* seq, uint64_t n, uint32_t k, int c
   if (n_out) *n_out = 0;
   if (k < 1 || k > 32 * kw || !n_out) return KH_ERR_INVALID;
   if (n < k) return KH_OK;
-  if (!seq || !out_kmers) return KH_ERR_INVALID;
+  if (!seq || !out_kmers || !wide_keys_aligned(kw, out_kmers, where)) return KH_ERR_INVALID;      // (kw_kmers_emit*: one 16-byte store per k-mer)
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   HIPCHK0(hipSetDevice(device));
   const uint64_t nkt = km_tiles(n);
@@ -2701,6 +2708,7 @@ kh_status sampled_impl(MzWork& M, bool args_ok, uint64_t min_n, const void* seq,
                        bool fastq, uint64_t* out_kmers, uint32_t* out_pos, uint64_t cap_out, uint64_t* n_out, int device, hipStream_t stream) {
   if (n_out) *n_out = 0;
   if (!n_out || !args_ok || (out_kmers && !out_pos)) return KH_ERR_INVALID;
+  if (!wide_keys_aligned(M.kw, out_kmers, where)) return KH_ERR_INVALID;      // (k_syncmers_emit<2>: one 16-byte store per k-mer; before the count pass)
   if (n < min_n) return KH_OK;
   HIPCHK0(hipSetDevice(device));
   uint64_t total = 0;
@@ -2740,7 +2748,7 @@ kh_status syncmer_mask_impl(uint32_t kw, const void* keys, uint64_t n, uint32_t 
                             int device, void* stream_) {
   if (!sy_args_ok(kw, keys, n, k, s, hash)) return KH_ERR_INVALID;
   if (n == 0) return KH_OK;
-  if (!out_mask) return KH_ERR_INVALID;
+  if (!out_mask || !wide_keys_aligned(kw, keys, where)) return KH_ERR_INVALID;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   HIPCHK0(hipSetDevice(device));
   Scratch scr(device, stream);
@@ -2861,7 +2869,7 @@ static kh_status hll_update(kh_hll* h, const void* in, uint64_t n, kh_mem where,
   if (!h) return KH_ERR_INVALID;
   if (n == 0) return KH_OK;
   if (!in) return KH_ERR_INVALID;
-  if (kw == 2 && where == KH_MEM_DEVICE && (reinterpret_cast<uintptr_t>(in) & 15u) != 0) return KH_ERR_INVALID;      // one 16-byte load per key
+  if (from_keys && !wide_keys_aligned(kw, in, where)) return KH_ERR_INVALID;
   HIPCHK0(hipSetDevice(h->device));
   Scratch s(h->device, h->stream);
   const uint64_t* d = nullptr;
@@ -3156,6 +3164,7 @@ kh_status kw_do_insert(kh_wtable* t, const void* keys, const void* vals, uint64_
   if (n_inserted) *n_inserted = 0;
   if (t->ins.active) return refuse_streaming(t);
   if (n && !keys) return fail(t, KH_ERR_INVALID, "null keys");
+  if (n && !wide_keys_aligned(2, keys, where)) return fail(t, KH_ERR_INVALID, kWideKeysMisaligned);
   if (is_reduce(mode) && mode != INS_PLUS && !vals) return fail(t, KH_ERR_INVALID, "null values: only the std::plus reducer has a default value (1)");
   HIPCHK(hipSetDevice(t->device));
   const uint64_t np_ = std::min<uint64_t>(n, g_max_pass);
@@ -3180,6 +3189,7 @@ kh_status kw_do_find(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, u
   if (t->ins.active) return refuse_streaming(t);
   if (n == 0) return KH_OK;
   if (!keys) return fail(t, KH_ERR_INVALID, "null keys");
+  if (!wide_keys_aligned(2, keys, where)) return fail(t, KH_ERR_INVALID, kWideKeysMisaligned);
   HIPCHK(hipSetDevice(t->device));
   { kh_status ps = arena_prepare(t, n * 48 + (n / KH_CMP_TILE + 8) * 16 + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
   const uint64_t* q = static_cast<const uint64_t*>(keys);
@@ -3223,6 +3233,7 @@ kh_status kw_do_erase(kh_wtable* t, const void* keys, uint64_t n, kh_mem where, 
   if (t->ins.active) return refuse_streaming(t);
   if (n == 0) return KH_OK;
   if (!keys) return fail(t, KH_ERR_INVALID, "null keys");
+  if (!wide_keys_aligned(2, keys, where)) return fail(t, KH_ERR_INVALID, kWideKeysMisaligned);
   HIPCHK(hipSetDevice(t->device));
   { kh_status ps = arena_prepare(t, n * 16 + ws_rebuild(t->cur.cap) + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
   const uint64_t* q = static_cast<const uint64_t*>(keys);
@@ -3361,6 +3372,7 @@ kh_status kh_wide_insert_feed(kh_wtable* t, const void* keys, const void* vals, 
   if (!t->ins.active) return fail(t, KH_ERR_INVALID, "kh_wide_insert_feed without kh_wide_insert_begin_ex");
   if (n == 0) return KH_OK;
   if (!keys) return fail(t, KH_ERR_INVALID, "null keys");
+  if (!wide_keys_aligned(2, keys, where)) return fail(t, KH_ERR_INVALID, kWideKeysMisaligned);      // (the streamed insert stays open, nothing was fed)
   if (!vals && t->ins.mode != INS_PLUS) return fail(t, KH_ERR_INVALID, "null values");
   if (t->ins.fed + n > t->ins.n_total) return fail(t, KH_ERR_INVALID, "more pairs fed than announced to kh_wide_insert_begin_ex");
   if (t->ins.wsrc == KH_MAX_SRC) return fail(t, KH_ERR_UNSUPPORTED, "more than 16 feeds in one streamed insert");     // (either form: the limit does not depend on table state)
@@ -3704,6 +3716,7 @@ kh_status index_pairs(kh_index* x, const void* keys, const void* pos, uint64_t n
   if (append && (x->total + n) >> 32) return xfail(x, KH_ERR_INVALID, "kh_index_append: offsets are 32-bit, the index must stay below 2^32 positions");
   if (n == 0) return KH_OK;
   if (!keys || !pos) return xfail(x, KH_ERR_INVALID, "null argument");
+  if (!wide_keys_aligned(x->kw, keys, where)) return xfail(x, KH_ERR_INVALID, kWideKeysMisaligned);
   kh_table* t = x->t;
   HIPCHK(hipSetDevice(x->device));
   Scratch s(x->device, t->stream);      // (host pairs: not in the table's workspace, the counting insert resets it)
@@ -3900,6 +3913,7 @@ kh_status kh_index_erase(kh_index* x, const void* keys, uint64_t n, kh_mem where
   if (n_pos_erased) *n_pos_erased = 0;
   if (!x) return KH_ERR_INVALID;
   if (n && !keys) return xfail(x, KH_ERR_INVALID, "null argument");
+  if (n && !wide_keys_aligned(x->kw, keys, where)) return xfail(x, KH_ERR_INVALID, kWideKeysMisaligned);      // (before the table's own erase: its refusal would abandon the index)
   kh_table* t = x->t;
   HIPCHK(hipSetDevice(x->device));
   if (n == 0 || !x->built) { HIPCHK(hipStreamSynchronize(t->stream)); return KH_OK; }
@@ -3959,6 +3973,7 @@ kh_status kh_index_count(kh_index* x, const void* keys, uint64_t n, kh_mem where
   if (!x) return KH_ERR_INVALID;
   if (n == 0) return KH_OK;
   if (!keys || !out_counts) return xfail(x, KH_ERR_INVALID, "null argument");
+  if (!wide_keys_aligned(x->kw, keys, where)) return xfail(x, KH_ERR_INVALID, kWideKeysMisaligned);
   kh_table* t = x->t;
   HIPCHK(hipSetDevice(x->device));
   { kh_status ps = arena_prepare(t, n * (8 * x->kw + 4) + (size_t(1) << 20)); if (ps != KH_OK) return ps; }
@@ -3977,6 +3992,7 @@ kh_status kh_index_find(kh_index* x, const void* keys, uint64_t n, kh_mem where,
   if (n_out) *n_out = 0;
   if (!x) return KH_ERR_INVALID;
   if (!out_offsets || (n && !keys)) return xfail(x, KH_ERR_INVALID, "null argument");
+  if (n && !wide_keys_aligned(x->kw, keys, where)) return xfail(x, KH_ERR_INVALID, kWideKeysMisaligned);
   kh_table* t = x->t;
   HIPCHK(hipSetDevice(x->device));
   const bool host = where == KH_MEM_HOST;
