@@ -1140,7 +1140,8 @@ kh_status kh_oriented_rows(const void* text /*[h|d]*/, uint64_t n, const uint32_
  *      at a time -- rank by counting, push into order, the lane-wise larger of the kept 64 and the reversed chunk (half a bitonic
  *      merge), rank and push again; a group of at most 64 chains is one load -- then lane i holds candidate i of mate 1, a uniform loop
  *      broadcasts those of mate 2, and (a*, b*) is one wave max over a packed 64-bit key.
- *      Not here: an insert-size distribution, mate rescue, other library orientations. */
+ *      Not here: an insert-size distribution, other library orientations.  A mate that has no row at all is kh_mate_rescue's
+ *      (below); re-pairing a mate whose own rows are all discordant is not done anywhere. */
 #define KH_PAIR_CANDIDATES 64u
 kh_status kh_pair_chains(const uint32_t* rs /*[h|d] u32[n_chains]*/, const uint32_t* re, const uint8_t* rev, const int32_t* score,
                          const uint32_t* tid /* or NULL */, const uint8_t* use /* or NULL */, const uint8_t* mapq_in /* or NULL */, uint64_t n_chains,
@@ -1148,6 +1149,62 @@ kh_status kh_pair_chains(const uint32_t* rs /*[h|d] u32[n_chains]*/, const uint3
                          uint32_t min_ins, uint32_t max_ins, uint32_t unpaired_pen, kh_mem where,
                          int32_t* out_row, uint8_t* out_mapq, int32_t* out_tlen /* each [n_reads] */,
                          uint8_t* out_flag, int32_t* out_score, uint32_t* out_nconc /* each [n_reads / 2] */, int device, void* hip_stream);
+
+/* ---- mate rescue.  kh_pair_chains only looks at rows that seeding found.  A mate whose seeds were all destroyed (errors every dozen
+ *      bases, a variant cluster) or masked (drop_above) has no row, although its partner says to within max_ins bases where it must
+ *      lie.  kh_mate_rescue aligns such a mate END TO END inside a window of the reference: where it ends, at what distance, where it
+ *      starts and by which operations.  There is no seed, so the first phase scans the whole window; the second is the extension of
+ *      kh_chain_ends run backwards from the end the scan found.  Integers only: the kernels equal tests/rescue_model.py bit for bit.
+ *      Inputs.  The two texts with ref_base as for kh_chain_ends; bases and the match rule are those of kh_chain_edits (an N matches
+ *      nothing, another N included); max_edits 0..31.  Per request j of n: q_lo[j], q_hi[j] (u32) -- the mate is qtext[q_lo, q_hi),
+ *      m = q_hi - q_lo; w_lo[j], w_hi[j] (u32) -- the window in global reference coordinates, rtext[w_lo - ref_base, w_hi - ref_base),
+ *      W = w_hi - w_lo; rev[j] (u8) -- bit 0 is the strand on which the mate is expected.
+ *      Pattern.  R = the mate as it stands if rev is 0, its reverse complement if 1.  Everything below is in reference order, like
+ *      ChainRecords with ref_order.
+ *      Which requests are looked at.  out_edits[j] = KH_RESCUE_NONE (-1), all other numbers 0 and an empty row unless
+ *      q_lo < q_hi <= nq; 1 <= m <= KH_RESCUE_MAX_READ (512); ref_base <= w_lo <= w_hi; w_hi - ref_base <= nr; and
+ *      W <= KH_RESCUE_MAX_WINDOW (65536).  Garbage therefore yields -1 or wrong rows; it never causes a read outside the texts or a
+ *      write outside the arrays.
+ *      Phase 1, the scan.  D is the unit-cost edit matrix of R (rows 0..m) against the window (columns 0..W) with a free reference
+ *      start: D[0][c] = 0 for every c, D[i][0] = i, D[i][c] = min(D[i-1][c-1] + (R[i-1] does not match window base c-1), D[i-1][c] + 1,
+ *      D[i][c-1] + 1).  d* = min over c of D[m][c]; e = the smallest c attaining d*, last = the greatest.  d* > max_edits:
+ *      out_edits[j] = KH_RESCUE_OVER (-2), all other numbers 0 and an empty row.
+ *      Phase 2, start and operations: the extension of kh_chain_ends, word for word, for a HEAD.  A = R read downwards from its last
+ *      base, n = m; B = the reference read downwards from window column e - 1, |B| = min(m + max_edits, e), so B never leaves the
+ *      window.  Diagonals, hi(d), the candidates X / I / D, "dropped, not clamped" and the move rule are as defined there.  One
+ *      difference: the alignment never stops early and there is no clip cost -- the target is the first level E <= max_edits at which
+ *      some diagonal holds n; among the diagonals that hold n at level E the smaller |d| wins, then d < 0.  (That is the extension
+ *      with clip_cost 0: S = F.)  E EQUALS d* BY CONSTRUCTION: an alignment of all of R that ends at column e costs D[m][e] = d* at
+ *      the least, and the one that attains it uses at most m + d* reference bases and stays within |d| <= d*.  The traceback from
+ *      that point to (0, 0), stored in the reverse of the order found, is the row: the row is in reference order.
+ *      Outputs per request: out_edits (i32: d*, -1 or -2); out_rs, out_re (u32, global: re = w_lo + e, rs = re - (n + d));
+ *      out_span (u32: last - e) -- an ambiguity measure: ends tied within d* columns are one placement with its gaps shifted, a larger
+ *      span means a second placement inside the window; and a CSR out_offsets [n + 1] / out_ops in the BAM run encoding of
+ *      kh_chain_cigars (=, X, I, D; no S).  Adjacent runs never share an op; a row has at most 2 d* + 1 <= 63 runs, consumes exactly
+ *      m bases of R and re - rs reference bases and has d* edit bases.
+ *      Mapping quality.  The call gives none.  The rule of the SAM writer (write_sam_rescued) is: a rescued mate takes the pair
+ *      quality of its partner if out_span <= out_edits, else 0.
+ *      Conventions are those of kh_chain_ends.  All arrays live in the memory `where` names.  out_ops == NULL: count only -- the four
+ *      numbers, out_offsets and *n_ops are written.  More runs than cap_ops: KH_ERR_INVALID with *n_ops set, the numbers and
+ *      out_offsets written and out_ops untouched.  Device memory: everything is queued on hip_stream and the one host wait is the one
+ *      that learns *n_ops.  Host memory: staged, the call synchronises.
+ *      KH_ERR_INVALID before anything is allocated, read or written: max_edits > 31, n > 2^24, nq >= 2^31, ref_base + nr > 2^31,
+ *      `where` outside the enum, a null out_offsets or n_ops, and while n > 0 a null array, a null output or a null text of positive
+ *      length.  n == 0: KH_OK, *n_ops = 0, out_offsets[0] = 0.
+ *      Route (kh_kernels_rescue.h): phase 1 is one LANE per request, Myers' bit-vector recurrence in Hyyro's block form over
+ *      ceil(m / 64) words with the pattern as three bit planes, all in registers, instantiated by word count; phase 2 one wavefront
+ *      per request that phase 1 settled, through the device functions of kh_chain_ends; then the one count-scan-emit tail.
+ *      Not here: soft clips in a rescued alignment, a mate with a discordant row of its own, other library orientations. */
+#define KH_RESCUE_NONE (-1)
+#define KH_RESCUE_OVER (-2)
+#define KH_RESCUE_MAX_READ 512u
+#define KH_RESCUE_MAX_WINDOW 65536u
+kh_status kh_mate_rescue(const void* qtext /*[h|d] u8[nq]*/, uint64_t nq, const void* rtext /*[h|d] u8[nr]*/, uint64_t nr, uint32_t ref_base,
+                         const uint32_t* q_lo /*[h|d] u32[n]*/, const uint32_t* q_hi, const uint32_t* w_lo, const uint32_t* w_hi,
+                         const uint8_t* rev /*[h|d] u8[n]*/, uint64_t n, uint32_t max_edits /*0..31*/, kh_mem where,
+                         int32_t* out_edits, uint32_t* out_rs, uint32_t* out_re, uint32_t* out_span /* each [n] */,
+                         uint64_t* out_offsets /*[n + 1]*/, uint32_t* out_ops /*[cap_ops] or NULL*/, uint64_t cap_ops, uint64_t* n_ops,
+                         int device, void* hip_stream);
 
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);

@@ -102,6 +102,8 @@ SYMBOLS = [
     "kh_oriented_rows",
     # paired reads: the concordant chain pair of two mates, proper flag, pair quality, template length
     "kh_pair_chains",
+    # mate rescue: a mate without a row aligned end to end inside the window its partner allows
+    "kh_mate_rescue",
 ]
 
 _lib = None
@@ -289,6 +291,7 @@ def lib():
     L.kh_record_diffs.argtypes = [vp, u64, vp, u64, u32, vp, vp, u64, vp, vp, vp, vp, vp, u64, u32, i32, vp, vp, vp, u64, pu64, i32, vp]
     L.kh_oriented_rows.argtypes = [vp, u64, vp, vp, vp, u64, u32, i32, vp, vp, u64, pu64, i32, vp]
     L.kh_pair_chains.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, u64, u32, u32, u32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
+    L.kh_mate_rescue.argtypes = [vp, u64, vp, u64, u32, vp, vp, vp, vp, vp, u64, u32, i32, vp, vp, vp, vp, vp, vp, u64, pu64, i32, vp]
     L.kh_anchor_targets.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, u64, u32, i32] + [vp] * 8 + [pu64, i32, vp]
     for s in SYMBOLS:
         if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error", "kh_wide_index_last_error"):

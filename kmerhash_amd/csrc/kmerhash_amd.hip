@@ -38,6 +38,7 @@
 #include "kh_kernels_targets.h"
 #include "kh_kernels_sam.h"
 #include "kh_kernels_pair.h"
+#include "kh_kernels_rescue.h"
 #include "kh_part_sizing.h"
 #include "kh_scratch.h"
 #include "../../include/kmerhash_amd.h"
@@ -4696,5 +4697,53 @@ kh_status kh_pair_chains(const uint32_t* rs, const uint32_t* re, const uint8_t* 
   s.copy_back(P.row, n_reads); s.copy_back(P.mapq, n_reads); s.copy_back(P.tlen, n_reads);
   s.copy_back(P.flag, n_pairs); s.copy_back(P.score_out, n_pairs); s.copy_back(P.nconc, n_pairs);
   return s.finish_queued();      // (host memory: copies are pending, so this waits)
+}
+// ---- a mate without a row aligned inside the window its partner allows (kernels: kh_kernels_rescue.h).  No handle; one pooled block
+//      holds the run counts and the path words (and the staged arrays of a host call), a second one the staged rows of a host call.
+//      Everything is queued on the caller's stream; the one host wait is the one that learns *n_ops.
+static_assert(KRS_NONE == KH_RESCUE_NONE && KRS_OVER == KH_RESCUE_OVER && KRS_MAX_READ == KH_RESCUE_MAX_READ && KRS_MAX_WINDOW == KH_RESCUE_MAX_WINDOW,
+              "one word for no answer, one for too far, one set of limits");
+kh_status kh_mate_rescue(const void* qtext, uint64_t nq, const void* rtext, uint64_t nr, uint32_t ref_base, const uint32_t* q_lo, const uint32_t* q_hi,
+                         const uint32_t* w_lo, const uint32_t* w_hi, const uint8_t* rev, uint64_t n, uint32_t max_edits, kh_mem where, int32_t* out_edits,
+                         uint32_t* out_rs, uint32_t* out_re, uint32_t* out_span, uint64_t* out_offsets, uint32_t* out_ops, uint64_t cap_ops, uint64_t* n_ops,
+                         int device, void* stream_) {
+  if (!chain_text_limits_ok(1, n, nq, nr, ref_base) || max_edits > 31) return KH_ERR_INVALID;
+  if ((where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !out_offsets || !n_ops) return KH_ERR_INVALID;
+  if (n && (!q_lo || !q_hi || !w_lo || !w_hi || !rev || !out_edits || !out_rs || !out_re || !out_span || (nq && !qtext) || (nr && !rtext))) return KH_ERR_INVALID;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  *n_ops = 0;
+  if (n == 0) return empty_rows(out_offsets, 1, where, device, stream);
+  HIPCHK0(hipSetDevice(device));
+  const uint64_t nst = (n + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
+  Scratch s(device, stream);
+  uint32_t *runs = nullptr, *ds = nullptr, *de = nullptr, *dsp = nullptr;
+  int32_t* dd = nullptr;
+  uint64_t *paths = nullptr, *doff = nullptr; unsigned long long* ssums = nullptr;
+  KrsArgs P{};
+  if (!s.layout([&](Scratch& c) {
+        runs = c.take<uint32_t>(n); paths = c.take<uint64_t>(n); ssums = c.take<unsigned long long>(nst + 1);
+        P.T.qtext = c.in(static_cast<const uint8_t*>(qtext), nq, where); P.T.rtext = c.in(static_cast<const uint8_t*>(rtext), nr, where);
+        P.q_lo = c.in(q_lo, n, where); P.q_hi = c.in(q_hi, n, where); P.w_lo = c.in(w_lo, n, where); P.w_hi = c.in(w_hi, n, where); P.rev = c.in(rev, n, where);
+        dd = c.out(out_edits, n, where); ds = c.out(out_rs, n, where); de = c.out(out_re, n, where); dsp = c.out(out_span, n, where);
+        doff = c.out(out_offsets, n + 1, where);
+      })) return s.finish();
+  P.T.nq = (uint32_t)nq; P.T.nr = (uint32_t)nr; P.T.ref_base = ref_base; P.T.max_edits = max_edits; P.n = (uint32_t)n;      // (no anchors: the rest of T stays null)
+  const uint32_t ncu = (uint32_t)cu_count(device);
+  const dim3 gscan(grid_for(n, KRS_THREADS, ncu * 16)), bscan(KRS_THREADS);
+  hipLaunchKernelGGL((k_rescue_scan<1>), gscan, bscan, 0, stream, P, dd, ds, de, dsp, runs);
+  hipLaunchKernelGGL((k_rescue_scan<2>), gscan, bscan, 0, stream, P, dd, ds, de, dsp, runs);
+  hipLaunchKernelGGL((k_rescue_scan<3>), gscan, bscan, 0, stream, P, dd, ds, de, dsp, runs);
+  hipLaunchKernelGGL((k_rescue_scan<4>), gscan, bscan, 0, stream, P, dd, ds, de, dsp, runs);
+  hipLaunchKernelGGL((k_rescue_scan<8>), gscan, bscan, 0, stream, P, dd, ds, de, dsp, runs);
+  hipLaunchKernelGGL(k_rescue_wfa, dim3(grid_for(n, KED_WAVES, ncu * 8)), dim3(KED_THREADS), 0, stream, P, dd, ds, de, dsp, runs, paths);
+  scan_counts(stream, (const uint32_t*)runs, n, ssums, doff);
+  s.launched();
+  unsigned long long total = 0;
+  s.read(&total, (const unsigned long long*)(ssums + nst));
+  s.copy_back(doff, n + 1); s.copy_back(dd, n); s.copy_back(ds, n); s.copy_back(de, n); s.copy_back(dsp, n);
+  return emit_total(s, total, out_ops, cap_ops, n_ops, where, [&](uint32_t* dops) {
+    hipLaunchKernelGGL(k_rescue_emit, dim3(grid_for(n, KED_THREADS, ncu * 8)), dim3(KED_THREADS), 0, stream, P, (const int32_t*)dd, (const uint32_t*)de,
+                       (const uint64_t*)doff, (const uint64_t*)paths, (uint64_t)total, dops);
+  });
 }
 }  // extern "C"

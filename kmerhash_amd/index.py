@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from ._call import HOST, _Buf, _Handle, alloc, check_same, torch
-from .kmers import Mapping, anchors_from_csr, chain_anchors, chain_cigars, chain_edits, chain_ends, chain_records, group_anchors, pair_mapping, select_table, stamp_strand
+from .kmers import Mapping, anchors_from_csr, chain_anchors, chain_cigars, chain_edits, chain_ends, chain_records, group_anchors, pair_mapping, rescue_mates, rescue_requests, select_table, stamp_strand
 from .targets import Targets
 from .seqs import is_syncmer, is_syncmer128, kmers_from_sequence, minimizers_from_sequence, syncmers128_from_sequence, syncmers_from_sequence
 from .table import _hash_id
@@ -430,6 +430,27 @@ class KmerPositionIndex(_Handle):
             raise ValueError("reads come in pairs (mate 1, mate 2, ...): an even number of reads is needed, got %d" % n_reads)
         mp = self.map(seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, mask_pct, pri_pct, best_n, True, targets, **params)
         return mp, pair_mapping(mp, n_reads, targets, min_ins=min_ins, max_ins=max_ins, unpaired_pen=unpaired_pen, device=self.device)
+
+    def map_pairs_rescued(self, seq, ref_text, read_starts, read_ends=None, ref_base=0, max_edits=31, clip_cost=4, mask_pct=50, pri_pct=80, best_n=5,
+                          min_ins=0, max_ins=1000, unpaired_pen=17, targets=None, **params):
+        """map_pairs(seq, ref_text, read_starts, ...) with the same parameters, then mate rescue: kmers.rescue_requests over its result
+        -- a mate that pairing left without a row, next to a partner that has one, is looked for where a concordant pair would put it --
+        and kmers.rescue_mates over those requests, which aligns each such mate end to end inside its window on the device.
+        -> (Mapping, PairSelect, MateRescue(read, edits, rs, re, rev, span, offsets, ops)): the first two are exactly what map_pairs
+        returns; the third holds one entry per request, read = the number of the rescued read, edits >= 0 where it was placed within
+        max_edits.  write_sam_rescued() prints such a read as mapped."""
+        mp, pairs = self.map_pairs(seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, mask_pct, pri_pct, best_n, min_ins, max_ins, unpaired_pen,
+                                   targets, **params)
+        sb, rb = _Buf.text(seq), _Buf.text(ref_text)
+        rs, re_ = read_starts, read_ends
+        if re_ is None:      # the next read's start, len(seq) for the last read: made where read_starts lives
+            if torch is not None and isinstance(rs, torch.Tensor):
+                re_ = torch.cat([rs.ravel()[1:], torch.tensor([sb.n], dtype=rs.dtype, device=rs.device)])
+            else:
+                re_ = np.concatenate([np.asarray(rs, dtype=np.int64).ravel()[1:], [sb.n]])
+        rq = rescue_requests(mp, pairs, rs, re_, min_ins, max_ins, max_edits, targets, rb.n, ref_base)
+        res = rescue_mates(sb.obj, rb.obj, rq.q_lo, rq.q_hi, rq.w_lo, rq.w_hi, rq.rev, ref_base, max_edits, self.device)
+        return mp, pairs, res._replace(read=rq.read)
 
     def chain_select(self, seq, read_starts=None, mask_pct=50, pri_pct=80, best_n=5, **params):
         """chains(seq, read_starts, **params), then which chain of every read is the answer: kmers.select_table over the table with one

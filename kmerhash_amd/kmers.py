@@ -481,6 +481,128 @@ def pair_mapping(mapping, n_reads, targets=None, **params):
     return pair_chains(rec.rs, rec.re, t.rev, t.score, offs, tid, use, sel.mapq, **params)
 
 
+MateRescue = collections.namedtuple("MateRescue", "read edits rs re rev span offsets ops")
+RescueRequests = collections.namedtuple("RescueRequests", "q_lo q_hi w_lo w_hi rev read")
+RESCUE_NONE, RESCUE_OVER = -1, -2                    # KH_RESCUE_NONE, KH_RESCUE_OVER in MateRescue.edits
+RESCUE_MAX_READ, RESCUE_MAX_WINDOW = 512, 65536      # KH_RESCUE_MAX_READ, KH_RESCUE_MAX_WINDOW
+
+
+def rescue_mates(qtext, rtext, q_lo, q_hi, w_lo, w_hi, rev, ref_base=0, max_edits=31, device=0):
+    """mates without a row aligned end to end inside a window of the reference (kh_mate_rescue in include/kmerhash_amd.h, which holds the
+    definition).  Request j: the mate qtext[q_lo[j]:q_hi[j]] (at most 512 bases), as it stands where bit 0 of rev[j] is clear and as its
+    reverse complement where it is set, against the window [w_lo[j], w_hi[j]) of global reference coordinates (at most 65536 bases;
+    rtext covers [ref_base, ref_base + len(rtext))).  The whole window is scanned for the end column of least edit distance d* (ties:
+    the first), then the alignment is traced back from there; max_edits 0..31.
+    -> MateRescue(read, edits, rs, re, rev, span, offsets, ops): read = the request's number (index.map_pairs_rescued puts the read
+    number there); edits = d*, RESCUE_NONE (-1: a request outside the texts or the limits) or RESCUE_OVER (-2: d* > max_edits);
+    [rs, re) the reference interval, rev as given, span = the distance from the first to the last end column attaining d* (more than
+    d*: a second placement inside the window); then a CSR of runs (len << 4) | op in reference order (=, X, I, D; end to end, no S).
+    Count, then emit: two calls, one allocation of the exact size.  numpy in, numpy out (uint32, int32, uint32 x 2, uint8, uint32,
+    uint64, uint32); CUDA tensors in, tensors out on the current stream (int32 holding the uint32 bits, int64 offsets); the call waits
+    for the stream once per pass.  At most 2^24 requests per call."""
+    if not 0 <= int(max_edits) <= 31:
+        raise ValueError("max_edits must be 0..31 (one diagonal per lane of a wavefront), got %r" % (max_edits,))
+    tq, tr = _Buf.text(qtext), _Buf.text(rtext)
+    lb, hb, wl, wh, vb = _Buf(q_lo, np.uint32), _Buf(q_hi, np.uint32), _Buf(w_lo, np.uint32), _Buf(w_hi, np.uint32), _Buf(rev, np.uint8)
+    check_same("the texts, q_lo, q_hi, w_lo, w_hi and rev must live in the same memory", tq, tr, lb, hb, wl, wh, vb, length=False)
+    n = lb.n
+    check_same("q_lo, q_hi, w_lo, w_hi and rev must have one entry per request, got %d, %d, %d, %d and %d" % (n, hb.n, wl.n, wh.n, vb.n), lb, hb, wl, wh, vb)
+    _check_text_limits(1, 0, tq, tr, ref_base)
+    if n > 2 ** 24:
+        raise ValueError("at most 2^24 requests per call (batch over reads), got %d" % n)
+    edits, eptr = alloc(lb, n, np.int32, empty=True)
+    nums = [alloc(lb, n, np.uint32, empty=True) for _ in range(3)]
+    offs, optr = alloc(lb, n + 1, np.uint64, zero=True)
+    read = torch.arange(n, dtype=torch.int32, device=lb.device) if lb.dev else np.arange(n, dtype=np.uint32)
+    if n == 0:      # nothing to queue: the zeroed offset is the answer
+        return MateRescue(read, edits, nums[0][0], nums[1][0], vb.obj, nums[2][0], offs, alloc(lb, 0, np.uint32)[0])
+    args = (tq.ptr_or_null, tq.n, tr.ptr_or_null, tr.n, int(ref_base), lb.ptr, hb.ptr, wl.ptr, wh.ptr, vb.ptr, n, int(max_edits), lb.where, eptr,
+            *(p for _, p in nums), optr)
+    ops = two_pass("kh_mate_rescue", args, lb, np.uint32, device)
+    return MateRescue(read, edits, nums[0][0], nums[1][0], vb.obj, nums[2][0], offs, ops)
+
+
+def rescue_requests(mapping, pairs, read_starts, read_ends, min_ins=0, max_ins=1000, max_edits=31, targets=None, ref_len=None, ref_base=0):
+    """the requests of rescue_mates for the mates pairing left without a row, derived with array operations where the Mapping lives (no
+    column goes to the host; the one wait is the one that learns how many requests there are).  mapping, pairs: what index.map_pairs
+    returned; read_starts / read_ends: the byte interval of every read in the query text -- CUDA tensors are used where they are, host
+    arrays next to a device Mapping are uploaded.
+    Mate Y of a pair gets a request iff pairs.row[Y] == -1, its partner X has a representative row pairs.row[X] >= 0, and that row lies
+    on a target (with targets: targets.locate(rs) names one).  Only concordant places of a forward-reverse library are searched.  With
+    m the length of Y and [rs, re) the interval of X's row:
+      X forward: Y is expected reverse (rev = 1) in [max(rs, rs + min_ins - m - max_edits), rs + max_ins);
+      X reverse: Y is expected forward (rev = 0) in [re - max_ins, min(re, re - min_ins + m + max_edits)).
+    Both windows are clamped to X's target -- targets (a kmerhash_amd.Targets), or [ref_base, ref_base + ref_len) -- and to
+    RESCUE_MAX_WINDOW bases, of which the ones nearest to X are kept.
+    -> RescueRequests(q_lo, q_hi, w_lo, w_hi, rev, read): the arguments of rescue_mates and the read number of every request,
+    ascending."""
+    _check_pair_params(min_ins, max_ins, 0)
+    if not 0 <= int(max_edits) <= 31:
+        raise ValueError("max_edits must be 0..31, got %r" % (max_edits,))
+    if targets is None and ref_len is None:
+        raise ValueError("ref_len is needed without targets: the windows are clamped to [ref_base, ref_base + ref_len)")
+    row, rec, trev = pairs.row, mapping.records, mapping.table.rev
+    dev = _is_tensor(row) and row.is_cuda
+    n_reads = int(row.numel() if dev else len(row))
+    if n_reads % 2:
+        raise ValueError("reads come in pairs (mate 1, mate 2, ...): an even number of reads is needed, got %d" % n_reads)
+
+    def offsets(x):      # a column of byte offsets where the Mapping lives: a CUDA tensor stays on its device, anything else is uploaded once
+        if dev and _is_tensor(x) and x.is_cuda:
+            return x.long().ravel()
+        a = np.asarray(x.cpu() if _is_tensor(x) else x, dtype=np.int64).ravel()
+        return torch.from_numpy(a).to(row.device) if dev else a
+
+    starts, ends = offsets(read_starts), offsets(read_ends)
+    if len(starts) != n_reads or len(ends) != n_reads:
+        raise ValueError("read_starts and read_ends must hold one entry per read of pairs (%d), got %d and %d" % (n_reads, len(starts), len(ends)))
+    min_ins, max_ins, max_edits = int(min_ins), int(max_ins), int(max_edits)
+    if dev:
+        where, lo_, hi_ = torch.where, torch.maximum, torch.minimum
+        i64 = lambda x, mask=False: (x.long() & 0xFFFFFFFF) if mask else x.long()      # noqa: E731
+        idx = torch.arange(n_reads, dtype=torch.int64, device=row.device)
+        const = lambda v: torch.full((n_reads,), int(v), dtype=torch.int64, device=row.device)      # noqa: E731
+    else:
+        where, lo_, hi_ = np.where, np.maximum, np.minimum
+        i64 = lambda x, mask=False: np.asarray(x).astype(np.int64)      # noqa: E731
+        idx = np.arange(n_reads, dtype=np.int64)
+        const = lambda v: np.full(n_reads, int(v), dtype=np.int64)      # noqa: E731
+        row, trev = _host(row, np.int32), _host(trev, np.uint8)
+    own, n_rows = i64(row), int(rec.rs.numel() if dev else len(rec.rs))
+    prow = own[idx ^ 1]
+    need = (own == -1) & (prow >= 0) & (prow < n_rows)
+    if n_rows == 0 or n_reads == 0:
+        empty = [alloc(_Buf(row, np.int32), 0, dt)[0] for dt in (np.uint32, np.uint32, np.uint32, np.uint32, np.uint8, np.uint32)]
+        return RescueRequests(*empty)
+    at = where(need, prow, const(0))
+    prs, pre = (i64(x if dev else _host(x, np.uint32), True)[at] for x in (rec.rs, rec.re))
+    fwd = (i64(trev)[at] & 1) == 0
+    if targets is not None:
+        tgt, _ = targets.locate(prs)
+        need = need & (tgt >= 0)
+        tc = where(tgt >= 0, tgt, const(0))
+        if dev:
+            ts, te = (x.long() & 0xFFFFFFFF for x in targets.to(row.device))
+        else:
+            ts, te = targets.starts.astype(np.int64), targets.ends.astype(np.int64)
+        tlo, thi = ts[tc], te[tc]
+    else:
+        tlo, thi = const(ref_base), const(int(ref_base) + int(ref_len))
+    m = ends - starts
+    w_lo = where(fwd, lo_(prs, prs + (min_ins - max_edits) - m), pre - max_ins)
+    w_hi = where(fwd, prs + max_ins, hi_(pre, pre - (min_ins - max_edits) + m))
+    w_lo = hi_(lo_(w_lo, tlo), thi)
+    w_hi = lo_(hi_(w_hi, thi), w_lo)
+    w_hi = where(fwd, hi_(w_hi, w_lo + RESCUE_MAX_WINDOW), w_hi)
+    w_lo = where(fwd, w_lo, lo_(w_lo, w_hi - RESCUE_MAX_WINDOW))
+    if dev:
+        sel = torch.nonzero(need).ravel()      # (the one wait: the number of requests)
+        return RescueRequests(starts[sel].int(), ends[sel].int(), w_lo[sel].int(), w_hi[sel].int(), fwd[sel].to(torch.uint8), sel.int())
+    sel = np.flatnonzero(need)
+    return RescueRequests(starts[sel].astype(np.uint32), ends[sel].astype(np.uint32), w_lo[sel].astype(np.uint32), w_hi[sel].astype(np.uint32),
+                          fwd[sel].astype(np.uint8), sel.astype(np.uint32))
+
+
 def read_cigar(cigars, ends, table, row, k):
     """the CIGAR of the whole read of chain `row` as text (a host helper like cigar_string): 'S' for the bases the head clips, the head's
     row, what cigar_string(cigars, table, row, k) gives, the tail's row, 'S' for the bases the tail clips, equal neighbours merged -- in

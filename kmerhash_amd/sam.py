@@ -7,7 +7,7 @@ import numpy as np
 
 from . import _capi as K
 from ._call import _Buf, _is_tensor, alloc, check_same, torch, two_pass
-from .kmers import FLAG_KEPT, FLAG_PRIMARY, Mapping, _host, cigar_text
+from .kmers import FLAG_KEPT, FLAG_PRIMARY, ChainRecords, Mapping, _host, cigar_text
 
 RecordDiffs = collections.namedtuple("RecordDiffs", "ok offsets text")
 DIFF_KINDS = {"cs": 0, "md": 1}      # KH_DIFF_CS, KH_DIFF_MD
@@ -133,14 +133,26 @@ def sam_lines(mapping, text_offsets, text, seq_rows, read_names, qual_rows=None,
     the oriented read of table row c (needed for the primary rows that are printed), row n_rows + s read s as given (needed for the
     unmapped reads).  pairs: the PairSelect of the reads (see write_sam_pairs), whose representatives and 0x800 rows then need their seq_rows.
     -> (lines, skipped, unmapped_reads): the header lines first when `header`."""
+    return _sam_lines(mapping, text_offsets, text, seq_rows, read_names, qual_rows, md, cs, ref_name, ref_len, ref_start, targets, kept_only, unmapped, header, pairs, None)
+
+
+def _tlen(s, own, mate):
+    """the template-length rule of kh_pair_chains over the intervals (rs, re) of read s and of its mate"""
+    t = min(max(own[1], mate[1]) - min(own[0], mate[0]), 2 ** 31 - 1)
+    return t if own[0] < mate[0] or (own[0] == mate[0] and s % 2 == 0) else -t
+
+
+def _sam_lines(mapping, text_offsets, text, seq_rows, read_names, qual_rows, md, cs, ref_name, ref_len, ref_start, targets, kept_only, unmapped, header, pairs, rescued):
+    """the body of sam_lines(); rescued (paired output only): {read: the alignment mate rescue gave it} as _write_sam builds it, or None"""
     if targets is not None and int(ref_start) != 0:
         raise ValueError("with targets the starts are theirs: ref_start must be 0")
     head = sam_header(targets, ref_name, ref_len).splitlines()      # (checks ref_name / ref_len against targets)
     t, sel, rec = mapping.table, mapping.select, mapping.records
     seg, rev, count, score = _host(t.seg, np.uint32), _host(t.rev, np.uint8), _host(t.count, np.uint32), _host(t.score, np.int32)
     flag, mapq, sub, best = _host(sel.flag, np.uint8), _host(sel.mapq, np.uint8), _host(sel.sub, np.int32), _host(sel.best, np.int32)
-    rs, nm = _host(rec.rs, np.uint32), _host(rec.nm, np.uint32)
+    rs, re_, nm = _host(rec.rs, np.uint32), _host(rec.re, np.uint32), _host(rec.nm, np.uint32)
     n_rows, n_reads = len(flag), len(best)
+    rescued = rescued or {}
     printable, considered, tgt = _printable(mapping, targets, kept_only)
     mapped = _mapped_reads(mapping, printable) if pairs is None else None      # (paired: the representatives say who is mapped)
     toff, raw = _rows_of((text_offsets, text))
@@ -167,9 +179,26 @@ def sam_lines(mapping, text_offsets, text, seq_rows, read_names, qual_rows=None,
 
         for s in range(n_reads):
             name, r, mr = str(read_names[s]), int(rep[s]), int(rep[s ^ 1])
-            fl0 = 0x1 | (0x80 if s & 1 else 0x40) | (0x8 if mr < 0 else (0x20 if rev[mr] & 1 else 0))
+            me, mate = rescued.get(s), rescued.get(s ^ 1)      # the alignment mate rescue gave this read / its mate (then r < 0 <= mr / mr < 0 <= r)
+            if me is not None:      # printed as mapped: a concordant pair by construction
+                x = n_rows + s
+                pt, pname, ppos = place(mr)
+                fl = 0x1 | (0x80 if s & 1 else 0x40) | 0x2 | (0x10 if me["rev"] else 0) | (0x20 if rev[mr] & 1 else 0)
+                f = [name, fl, me["tname"], me["pos"], me["mapq"], me["cigar"], "=" if pt == me["tn"] else pname, ppos,
+                     _tlen(s, (me["rs"], me["re"]), (int(rs[mr]), int(re_[mr]))) if pt == me["tn"] else 0, sraw[soff[x]:soff[x + 1]] or "*",
+                     (qraw[qoff[x]:qoff[x + 1]] if qraw is not None else "") or "*", "NM:i:%d" % me["nm"], "tp:A:R"] + me["tags"]
+                skipped += len(rows_of[s])
+                lines.append("\t".join(str(v) for v in f))
+                continue
+            fl0 = 0x1 | (0x80 if s & 1 else 0x40)
+            if mate is not None:
+                fl0 |= 0x20 if mate["rev"] else 0
+            else:
+                fl0 |= 0x8 if mr < 0 else (0x20 if rev[mr] & 1 else 0)
             at = mr if mr >= 0 else r      # (an unmapped mate is placed at this read's representative: the mate columns point there)
             mt, mname, mpos = place(at) if at >= 0 else (-1, "*", 0)
+            if mate is not None:
+                mt, mname, mpos = mate["tn"], mate["tname"], mate["pos"]
             both = r >= 0 and mr >= 0      # (0x2 and TLEN need both representatives: a PairSelect made under other targets or kept_only may name a row that is not printed)
             if r < 0:
                 n_unmapped += 1
@@ -184,10 +213,14 @@ def sam_lines(mapping, text_offsets, text, seq_rows, read_names, qual_rows=None,
                     skipped += 1
                     continue
                 is_rep, pri = c == r, role[c] != ROLE_SEC
-                fl = fl0 | (0x10 if rev[c] & 1 else 0) | {ROLE_REP: 0, ROLE_SUPP: 0x800, ROLE_SEC: 0x100}[int(role[c])] | (0x2 if is_rep and both and pflag[s >> 1] & 1 else 0)
+                proper = is_rep and (mate is not None or (both and pflag[s >> 1] & 1))
+                fl = fl0 | (0x10 if rev[c] & 1 else 0) | {ROLE_REP: 0, ROLE_SUPP: 0x800, ROLE_SEC: 0x100}[int(role[c])] | (0x2 if proper else 0)
                 tn, tname, pos = place(c)
+                tlen = int(ptlen[s]) if is_rep and both else 0
+                if is_rep and mate is not None and mt == tn:
+                    tlen = _tlen(s, (int(rs[c]), int(re_[c])), (mate["rs"], mate["re"]))
                 f = [name, fl, tname, pos, int(pmapq[s]) if is_rep else int(mapq[c]), raw[toff[c]:toff[c + 1]], "=" if mt == tn else mname, mpos,
-                     int(ptlen[s]) if is_rep and both else 0, (sraw[soff[c]:soff[c + 1]] if pri else "") or "*", (qraw[qoff[c]:qoff[c + 1]] if pri and qraw is not None else "") or "*",
+                     tlen, (sraw[soff[c]:soff[c + 1]] if pri else "") or "*", (qraw[qoff[c]:qoff[c + 1]] if pri and qraw is not None else "") or "*",
                      "NM:i:%d" % int(nm[c]), "tp:A:%s" % ("P" if pri else "S"), "cm:i:%d" % int(count[c]), "s1:i:%d" % int(score[c])]
                 if pri:
                     f.append("s2:i:%d" % int(sub[c]))
@@ -284,9 +317,30 @@ def write_sam_pairs(fh, mapping, pairs, seq, ref_text, read_names, read_starts, 
                       device, pairs)
 
 
+def write_sam_rescued(fh, mapping, pairs, rescue, seq, ref_text, read_names, read_starts, read_ends=None, qual=None, ref_name=None, ref_len=None, ref_start=0, ref_base=0,
+                      targets=None, kept_only=True, unmapped=True, header=True, md=True, cs=False, device=0):
+    """write_sam_pairs() with the mates that mate rescue placed printed as mapped: the same device calls, texts and arguments, and
+    rescue: the MateRescue of index.map_pairs_rescued over this Mapping and PairSelect.  A read with rescue.edits >= 0 that has no
+    representative of its own, next to a mate that has one, gives one line: FLAG 0x1, 0x40 / 0x80, 0x10 from rescue.rev, 0x20 from
+    the partner's strand and 0x2 -- on BOTH mates: a rescued pair is concordant by construction --; RNAME and POS = rescue.rs,
+    target-local and 1-based; the CIGAR of its row (=, X, I, D: end to end); SEQ and QUAL oriented by oriented_rows; NM:i = edits,
+    tp:A:R, MD:Z / cs:Z from record_diffs over the rescue's columns; RNEXT / PNEXT = the partner's place and TLEN by the
+    template-length rule of kh_pair_chains over the two intervals.  The partner's line is updated to match: no 0x8, 0x20 from
+    rescue.rev, 0x2, RNEXT / PNEXT = the rescued place, the same TLEN with the other sign.
+    MAPQ of a rescued mate: pairs.mapq[partner] if rescue.span <= rescue.edits -- the end columns tied for the least distance are
+    then one placement with its gaps shifted --, else 0: a second placement lies inside the window.
+    A request that came back RESCUE_NONE or RESCUE_OVER, or with an alignment that faces no reference base (re == rs: a mate of at most
+    max_edits bases against an empty window, all insertions), leaves the read as write_sam_pairs() prints it.
+    -> (alignment lines written, rows skipped, unmapped reads)"""
+    if pairs is None or rescue is None:
+        raise ValueError("write_sam_rescued() needs a PairSelect and a MateRescue; write_sam_pairs() writes pairs without rescue")
+    return _write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends, qual, ref_name, ref_len, ref_start, ref_base, targets, kept_only, unmapped, header, md, cs,
+                      device, pairs, rescue)
+
+
 def _write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends, qual, ref_name, ref_len, ref_start, ref_base, targets, kept_only, unmapped, header, md, cs,
-               device, pairs):
-    """the body of write_sam() (pairs None) and write_sam_pairs()"""
+               device, pairs, rescue=None):
+    """the body of write_sam() (pairs None), write_sam_pairs() and write_sam_rescued()"""
     sb = _Buf.text(seq)
     seq = sb.obj
     n_text = sb.n
@@ -326,14 +380,42 @@ def _write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends, q
         rep, role = _pair_roles(hm, pairs, printable)
         need, mapped = (role == ROLE_REP) | (role == ROLE_SUPP), rep >= 0
     show = ~mapped if unmapped else np.zeros(n_reads, dtype=bool)
+    read_rev, rescued = np.zeros(n_reads, dtype=np.uint8), None
+    if rescue is not None:      # the rescued reads: one CIGAR text and one difference string per request, SEQ oriented by rescue.rev
+        rd, ed = _host(rescue.read, np.uint32).astype(np.int64), _host(rescue.edits, np.int32)
+        r_rs, r_re, r_span = (_host(x, np.uint32).astype(np.int64) for x in (rescue.rs, rescue.re, rescue.span))
+        r_rev = _host(rescue.rev, np.uint8) & 1
+        inside = (rd >= 0) & (rd < n_reads)
+        at = np.where(inside, rd, 0)
+        take = inside & (ed >= 0) & (r_re > r_rs) & (rep[at] < 0) & (rep[at ^ 1] >= 0) if n_reads else np.zeros(len(rd), dtype=bool)      # (re == rs: a row of insertions only has no place)
+        r_tgt = None
+        if targets is not None:      # printable under the rule of the rows: inside one target
+            r_tgt, _ = targets.locate(r_rs)
+            take = take & (r_tgt >= 0) & (r_re <= targets.ends.astype(np.int64)[np.maximum(r_tgt, 0)])
+        coff, craw = _rows_of(cigar_text(rescue.offsets, rescue.ops, device))
+        as_rec = ChainRecords(place(take.astype(np.uint8)), None, None, rescue.rs, rescue.re, None, None, None, None, rescue.offsets, rescue.ops)
+        r_lo, r_hi = place(rs_[at].astype(np.uint32)), place(re_[at].astype(np.uint32))
+        r_diffs = [(tag, _host(d.ok, np.uint8), *_rows_of((d.offsets, d.text))) for tag, d in
+                   ((tag, record_diffs(seq, ref_text, as_rec, rescue.rev, r_lo, r_hi, kind, ref_base, device)) for tag, kind, want in (("MD", "md", md), ("cs", "cs", cs)) if want)]
+        rescued = {}
+        for j in np.flatnonzero(take):
+            sr, tn = int(rd[j]), 0 if r_tgt is None else int(r_tgt[j])
+            tname, t0 = (str(ref_name), int(ref_start)) if targets is None else (targets.names[tn], int(targets.starts[tn]))
+            for tag, ok, _, _ in r_diffs:
+                if not ok[j]:
+                    raise ValueError("rescue request %d does not walk the two texts: pass the texts the MateRescue was made from" % j)
+            rescued[sr] = dict(tn=tn, tname=tname, pos=int(r_rs[j]) - t0 + 1, rs=int(r_rs[j]), re=int(r_re[j]), rev=int(r_rev[j]), nm=int(ed[j]),
+                               mapq=int(pairs.mapq[sr ^ 1]) if r_span[j] <= ed[j] else 0, cigar=craw[coff[j]:coff[j + 1]],
+                               tags=["%s:Z:%s" % (tag, draw[doff[j]:doff[j + 1]]) for tag, _, doff, draw in r_diffs])
+            show[sr], read_rev[sr] = True, r_rev[j]
     all_lo = np.concatenate([lo, rs_.astype(np.uint32)])
     all_hi = np.concatenate([np.where(need, hi, lo), np.where(show, re_, rs_).astype(np.uint32)]).astype(np.uint32)
-    all_rev = np.concatenate([hm.table.rev & 1, np.zeros(n_reads, dtype=np.uint8)]).astype(np.uint8)
+    all_rev = np.concatenate([hm.table.rev & 1, read_rev]).astype(np.uint8)
     plo, phi, prev = place(all_lo), place(all_hi), place(all_rev)
     seq_rows = oriented_rows(seq, plo, phi, prev, True, device)
     qual_rows = oriented_rows(qual, plo, phi, prev, False, device) if qual is not None else None
-    lines, skipped, n_unmapped = sam_lines(hm, toff, ctext, seq_rows, read_names, qual_rows, diffs["md"], diffs["cs"], ref_name, ref_len, ref_start, targets,
-                                           kept_only, unmapped, header, *(() if pairs is None else (pairs,)))
+    lines, skipped, n_unmapped = _sam_lines(hm, toff, ctext, seq_rows, read_names, qual_rows, diffs["md"], diffs["cs"], ref_name, ref_len, ref_start, targets,
+                                            kept_only, unmapped, header, pairs, rescued)
     for ln in lines:
         fh.write(ln + "\n")
     n_head = len(sam_header(targets, ref_name, ref_len).splitlines()) if header else 0
