@@ -5,36 +5,20 @@ reference tree): built from (k-mer, position) pairs or straight from sequence / 
 (append*, erase, erase_counts, drop_above).
 numpy arrays are host buffers, torch CUDA tensors device buffers, as in kmerhash_amd.table; results come back in the same kind of
 container.  There is no CPU fallback."""
-import collections
 import ctypes as C
 
 import numpy as np
 
+from . import mapper
 from ._call import HOST, _Buf, _Handle, alloc, check_same, torch
-from .kmers import Mapping, anchors_from_csr, chain_anchors, chain_cigars, chain_edits, chain_ends, chain_records, group_anchors, pair_mapping, rescue_mates, rescue_requests, select_table, stamp_strand
-from .targets import Targets
+from ._xp import namespace_of
+from .mapper import ChainTable, ReadLayout, anchors_from_csr, group_anchors, read_segments, stamp_strand  # noqa: F401  (ChainTable re-exported)
 from .seqs import is_syncmer, is_syncmer128, kmers_from_sequence, minimizers_from_sequence, syncmers128_from_sequence, syncmers_from_sequence
 from .table import _hash_id
 
 # entries of positions a workgroup of the build sorts in LDS at a time (KI_SORT_TILE in csrc/kh_kernels_index.h): a segment that crosses
 # a multiple of it takes the radix path
 SORT_TILE = 4096
-
-ChainTable = collections.namedtuple("ChainTable", "seg rev q_start q_end r_start r_end count score anchors chain")
-
-
-def _check_targets_text(targets, ref_text, ref_base, max_edits):
-    """the refusals of the calls that read the reference text of a multi-target index: the text must be the one the Targets lay out, from
-    coordinate 0, and no alignment may afford a spacer"""
-    if not isinstance(targets, Targets):
-        raise ValueError("targets must be a kmerhash_amd.Targets where the reference text is read, got %r" % (type(targets).__name__,))
-    if targets.spacer <= int(max_edits):
-        raise ValueError("the spacer between targets (%d) must exceed max_edits (%r): an alignment could cross it" % (targets.spacer, max_edits))
-    if int(ref_base) != 0:
-        raise ValueError("ref_base must be 0 with targets (their coordinates are those of the whole text), got %r" % (ref_base,))
-    n = _Buf.text(ref_text).n
-    if n != int(targets.ends[-1]):
-        raise ValueError("ref_text must be the text the targets lay out (%d bytes), got %d" % (int(targets.ends[-1]), n))
 
 
 class KmerPositionIndex(_Handle):
@@ -246,8 +230,7 @@ class KmerPositionIndex(_Handle):
         is expanded on the device (kh_anchors_from_csr).  rev[j] == 0: the k bases at rpos[j] in the indexed text equal those at qpos[j]
         in `seq`; rev[j] == 1: they are their reverse complement.  numpy in, numpy out (uint32, uint32, uint8); a CUDA tensor in, tensors
         out (int32, int32, uint8) on the current stream.  chains(seq) chains them per read."""
-        if not self.stranded:
-            raise ValueError("anchors() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        self._need_stranded("anchors")
         seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to two calls)
         km, qpos = self._sample(seq)
         sq = stamp_strand(seq, qpos, self.k, 0, self.device)
@@ -257,12 +240,16 @@ class KmerPositionIndex(_Handle):
     def anchor_groups(self, seq, read_starts=None, targets=None):
         """anchors(seq), then kmers.group_anchors: the anchors of every read (read_starts as chains() takes them; None: one read)
         regrouped by the target they fall in -> AnchorGroups.  targets: a kmerhash_amd.Targets (or a (starts, ends) pair)."""
-        if not self.stranded:
-            raise ValueError("anchor_groups() needs an index made with stranded=True: without the strand bit a hit has no orientation")
+        self._need_stranded("anchor_groups")
         if targets is None:
             raise ValueError("anchor_groups() needs targets=")
         q, r, v = self.anchors(seq)
-        return group_anchors(q, r, v, targets, self.k, self._read_segments(q, read_starts), self.device)
+        return group_anchors(q, r, v, targets, self.k, read_segments(namespace_of(q), q, ReadLayout(read_starts, None, None)), self.device)
+
+    def _need_stranded(self, name):
+        """the refusal every call that orients its hits opens with"""
+        if not self.stranded:
+            raise ValueError("%s() needs an index made with stranded=True: without the strand bit a hit has no orientation" % name)
 
     def chains(self, seq, read_starts=None, targets=None, **params):
         """candidate loci of the reads in a query text on a stranded index: anchors(seq), then collinear chains per read on the device
@@ -276,51 +263,8 @@ class KmerPositionIndex(_Handle):
         anchors of every read are first regrouped by target (kmers.group_anchors) and chained per (read, target), so no chain crosses a
         contig; `anchors` are then the regrouped ones, seg stays the read, and targets.locate(r_start) names a row's target.  None:
         exactly the calls of an index of one sequence."""
-        if not self.stranded:
-            raise ValueError("chains() needs an index made with stranded=True: without the strand bit a hit has no orientation")
-        return self._chains(seq, read_starts, params, targets)[0]
-
-    def _read_segments(self, q, read_starts):
-        """the segment CSR of the reads over the anchors' query positions q (None: one read, no CSR)"""
-        dev = torch is not None and isinstance(q, torch.Tensor)
-        if read_starts is None:
-            seg = None
-        else:
-            rs = np.asarray(read_starts.cpu() if torch is not None and isinstance(read_starts, torch.Tensor) else read_starts, dtype=np.int64).ravel()
-            if rs.size == 0 or rs[0] != 0 or (np.diff(rs) < 0).any():
-                raise ValueError("read_starts must be ascending byte offsets of the reads in seq, the first one 0")
-            # read s owns the anchors with read_starts[s] <= qpos < read_starts[s + 1]; qpos ascends
-            if dev:
-                seg = torch.cat([torch.searchsorted(q.long(), torch.from_numpy(rs).to(q.device)), torch.tensor([q.numel()], dtype=torch.int64, device=q.device)])
-            else:
-                seg = np.concatenate([np.searchsorted(q, rs, side="left"), [len(q)]]).astype(np.uint64)
-        return seg
-
-    def _chains(self, seq, read_starts, params, targets=None):
-        """the body of chains(): -> (ChainTable, the Chains chain_anchors returned: pred per anchor, first and last anchor per chain)"""
-        q, r, v = self.anchors(seq)
-        dev = torch is not None and isinstance(q, torch.Tensor)
-        seg = self._read_segments(q, read_starts)
-        groups = None
-        if targets is not None:      # chain per (read, target): the group CSR takes the place of the read CSR
-            groups = group_anchors(q, r, v, targets, self.k, seg, self.device)
-            q, r, v, seg = groups.qpos, groups.rpos, groups.rev, groups.offsets
-        c = chain_anchors(q, r, v, self.k, seg, device=self.device, **params)
-        if dev:
-            first, last = c.first.long(), c.last.long()
-            qf, ql, rf, rl = q[first], q[last], r[first], r[last]
-            sg = torch.zeros_like(c.first) if seg is None else (torch.searchsorted(seg, first, right=True) - 1).int()
-            if groups is not None:
-                sg = groups.seg[sg.long()]
-            rows = (sg, v[first], qf, ql + self.k, torch.minimum(rf, rl), torch.maximum(rf, rl) + self.k, c.count, c.cscore)
-        else:
-            first, last = c.first.astype(np.int64), c.last.astype(np.int64)
-            qf, ql, rf, rl = q[first], q[last], r[first], r[last]
-            sg = np.zeros(len(first), dtype=np.uint32) if seg is None else (np.searchsorted(seg, first.astype(np.uint64), side="right") - 1).astype(np.uint32)
-            if groups is not None:
-                sg = groups.seg[sg.astype(np.int64)]
-            rows = (sg, v[first], qf, ql + np.uint32(self.k), np.minimum(rf, rl), np.maximum(rf, rl) + np.uint32(self.k), c.count, c.cscore)
-        return ChainTable(*rows, (q, r, v), c.chain), c
+        self._need_stranded("chains")
+        return mapper.chains(self, seq, read_starts, targets, **params)
 
     def chain_edits(self, seq, ref_text, read_starts=None, ref_base=0, max_edits=31, targets=None, **params):
         """chains(seq, read_starts, **params), then every kept chain verified against the texts on the device: kmers.chain_edits over the
@@ -330,31 +274,16 @@ class KmerPositionIndex(_Handle):
         the texts or more than max_edits, 0..31) and, per row of the table, the sum of its links' distances and the number of its -2
         links.  The chain's last seed adds k matching bases and no edits.
         targets: as for chains(); ref_text must then be targets.text (or a copy where seq lives) with ref_base 0."""
-        if not self.stranded:
-            raise ValueError("chain_edits() needs an index made with stranded=True: without the strand bit a hit has no orientation")
-        if targets is not None:
-            _check_targets_text(targets, ref_text, ref_base, max_edits)
-        seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to two calls)
-        table, c = self._chains(seq, read_starts, params, targets)
-        q, r, v = table.anchors
-        n_chains = int(table.count.numel() if torch is not None and isinstance(table.count, torch.Tensor) else len(table.count))
-        return table, chain_edits(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
+        self._need_stranded("chain_edits")
+        return mapper.index_chain_edits(self, seq, ref_text, read_starts, ref_base, max_edits, targets, **params)
 
     def chain_cigars(self, seq, ref_text, read_starts=None, ref_base=0, max_edits=31, targets=None, **params):
         """chain_edits(seq, ref_text, ...), then the alignment behind every distance: kmers.chain_cigars over the same anchors and texts
         with the link array chain_edits wrote -> (ChainTable, ChainEdits, ChainCigars(offsets, ops, ins, dels)): a CSR of run-length rows in
         anchor order and the inserted and deleted bases per row of the table.  kmers.cigar_string(cigars, table, row, k) is the CIGAR
         of one chain as text.  targets: as for chain_edits()."""
-        if not self.stranded:
-            raise ValueError("chain_cigars() needs an index made with stranded=True: without the strand bit a hit has no orientation")
-        if targets is not None:
-            _check_targets_text(targets, ref_text, ref_base, max_edits)
-        seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to three calls)
-        table, c = self._chains(seq, read_starts, params, targets)
-        q, r, v = table.anchors
-        n_chains = int(table.count.numel() if torch is not None and isinstance(table.count, torch.Tensor) else len(table.count))
-        edits = chain_edits(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
-        return table, edits, chain_cigars(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, edits.link, ref_base, self.device)
+        self._need_stranded("chain_cigars")
+        return mapper.index_chain_cigars(self, seq, ref_text, read_starts, ref_base, max_edits, targets, **params)
 
     def chain_ends(self, seq, ref_text, read_starts=None, read_ends=None, ref_base=0, max_edits=31, clip_cost=4, targets=None, **params):
         """chain_cigars(seq, ref_text, ...), then both ends of every chain extended to the ends of its read or to a soft clip:
@@ -365,38 +294,8 @@ class KmerPositionIndex(_Handle):
         and tail of row c of the table.  kmers.read_cigar(cigars, ends, table, row, k) is the CIGAR of a whole read,
         kmers.extended_intervals(table, ends) the intervals it maps.  targets: as for chain_edits(); an end never runs into a spacer:
         every spacer byte costs clip_cost and gains nothing."""
-        if not self.stranded:
-            raise ValueError("chain_ends() needs an index made with stranded=True: without the strand bit a hit has no orientation")
-        return self._ends(seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, params, targets)[:4]
-
-    def _ends(self, seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, params, targets=None):
-        """the body of chain_ends(): -> (ChainTable, ChainEdits, ChainCigars, ChainEnds, the Chains of chain_anchors, q_lo, q_hi per chain)"""
-        if targets is not None:
-            _check_targets_text(targets, ref_text, ref_base, max_edits)
-        seq = _Buf.text(seq).obj          # (bytes as an array: the text goes to four calls)
-        table, c = self._chains(seq, read_starts, params, targets)
-        q, r, v = table.anchors
-        dev = torch is not None and isinstance(q, torch.Tensor)
-        n_chains = int(table.count.numel() if dev else len(table.count))
-        n_text = int(seq.numel() if dev else seq.size)
-        rs = np.zeros(1, dtype=np.int64) if read_starts is None else np.asarray(
-            read_starts.cpu() if torch is not None and isinstance(read_starts, torch.Tensor) else read_starts, dtype=np.int64).ravel()
-        if read_ends is None:
-            re_ = np.concatenate([rs[1:], [n_text]])
-        else:
-            re_ = np.asarray(read_ends.cpu() if torch is not None and isinstance(read_ends, torch.Tensor) else read_ends, dtype=np.int64).ravel()
-            if re_.size != rs.size or (re_ < rs).any() or (re_ > n_text).any():
-                raise ValueError("read_ends must hold one byte offset per read, read_starts[s] <= read_ends[s] <= len(seq)")
-        if dev:
-            sg = table.seg.long()
-            lo, hi = torch.from_numpy(rs).to(q.device)[sg].int(), torch.from_numpy(re_).to(q.device)[sg].int()
-        else:
-            sg = table.seg.astype(np.int64)
-            lo, hi = rs[sg].astype(np.uint32), re_[sg].astype(np.uint32)
-        edits = chain_edits(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, ref_base, max_edits, self.device)
-        cigars = chain_cigars(seq, ref_text, q, r, v, c.pred, table.chain, n_chains, self.k, edits.link, ref_base, self.device)
-        ends = chain_ends(seq, ref_text, q, r, v, c.first, c.last, lo, hi, self.k, ref_base, max_edits, clip_cost, self.device)
-        return table, edits, cigars, ends, c, lo, hi
+        self._need_stranded("chain_ends")
+        return mapper.index_chain_ends(self, seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, targets, **params)
 
     def map(self, seq, ref_text, read_starts=None, read_ends=None, ref_base=0, max_edits=31, clip_cost=4, mask_pct=50, pri_pct=80, best_n=5, ref_order=True,
             targets=None, **params):
@@ -407,13 +306,8 @@ class KmerPositionIndex(_Handle):
         order, as PAF and SAM want them; False gives read order, what kmers.read_cigar() prints.  kmers.write_paf() writes the lines.
         targets: a kmerhash_amd.Targets for an index of several sequences (see chains()); ref_text is then targets.text, the rows of one
         read on different targets compete in select, and write_paf(..., targets=targets) names each row's target."""
-        if not self.stranded:
-            raise ValueError("map() needs an index made with stranded=True: without the strand bit a hit has no orientation")
-        table, edits, cigars, ends, c, lo, hi = self._ends(seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, params, targets)
-        select = select_table(table, 1 if read_starts is None else len(read_starts), mask_pct=mask_pct, pri_pct=pri_pct, best_n=best_n, device=self.device)
-        q, r, v = table.anchors
-        records = chain_records(q, r, v, table.chain, cigars, c.first, c.last, lo, hi, ends, self.k, ref_order, self.device)
-        return Mapping(table, edits, cigars, ends, select, records)
+        self._need_stranded("map")
+        return mapper.map_reads(self, seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, mask_pct, pri_pct, best_n, ref_order, targets, **params)
 
     def map_pairs(self, seq, ref_text, read_starts, read_ends=None, ref_base=0, max_edits=31, clip_cost=4, mask_pct=50, pri_pct=80, best_n=5,
                   min_ins=0, max_ins=1000, unpaired_pen=17, targets=None, **params):
@@ -423,13 +317,9 @@ class KmerPositionIndex(_Handle):
         quality and its template length; per pair whether it is proper.  min_ins / max_ins bound the fragment length of a concordant
         pair, unpaired_pen is what two unpaired best rows must win by.  An odd number of reads raises ValueError.
         write_sam_pairs() prints the mate columns."""
-        if not self.stranded:
-            raise ValueError("map_pairs() needs an index made with stranded=True: without the strand bit a hit has no orientation")
-        n_reads = 1 if read_starts is None else len(read_starts)
-        if n_reads % 2:
-            raise ValueError("reads come in pairs (mate 1, mate 2, ...): an even number of reads is needed, got %d" % n_reads)
-        mp = self.map(seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, mask_pct, pri_pct, best_n, True, targets, **params)
-        return mp, pair_mapping(mp, n_reads, targets, min_ins=min_ins, max_ins=max_ins, unpaired_pen=unpaired_pen, device=self.device)
+        self._need_stranded("map_pairs")
+        return mapper.map_pairs(self, seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, mask_pct, pri_pct, best_n, min_ins, max_ins, unpaired_pen,
+                                targets, **params)
 
     def map_pairs_rescued(self, seq, ref_text, read_starts, read_ends=None, ref_base=0, max_edits=31, clip_cost=4, mask_pct=50, pri_pct=80, best_n=5,
                           min_ins=0, max_ins=1000, unpaired_pen=17, targets=None, **params):
@@ -439,18 +329,9 @@ class KmerPositionIndex(_Handle):
         -> (Mapping, PairSelect, MateRescue(read, edits, rs, re, rev, span, offsets, ops)): the first two are exactly what map_pairs
         returns; the third holds one entry per request, read = the number of the rescued read, edits >= 0 where it was placed within
         max_edits.  write_sam_rescued() prints such a read as mapped."""
-        mp, pairs = self.map_pairs(seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, mask_pct, pri_pct, best_n, min_ins, max_ins, unpaired_pen,
-                                   targets, **params)
-        sb, rb = _Buf.text(seq), _Buf.text(ref_text)
-        rs, re_ = read_starts, read_ends
-        if re_ is None:      # the next read's start, len(seq) for the last read: made where read_starts lives
-            if torch is not None and isinstance(rs, torch.Tensor):
-                re_ = torch.cat([rs.ravel()[1:], torch.tensor([sb.n], dtype=rs.dtype, device=rs.device)])
-            else:
-                re_ = np.concatenate([np.asarray(rs, dtype=np.int64).ravel()[1:], [sb.n]])
-        rq = rescue_requests(mp, pairs, rs, re_, min_ins, max_ins, max_edits, targets, rb.n, ref_base)
-        res = rescue_mates(sb.obj, rb.obj, rq.q_lo, rq.q_hi, rq.w_lo, rq.w_hi, rq.rev, ref_base, max_edits, self.device)
-        return mp, pairs, res._replace(read=rq.read)
+        self._need_stranded("map_pairs")
+        return mapper.map_pairs_rescued(self, seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, mask_pct, pri_pct, best_n, min_ins, max_ins,
+                                        unpaired_pen, targets, **params)
 
     def chain_select(self, seq, read_starts=None, mask_pct=50, pri_pct=80, best_n=5, **params):
         """chains(seq, read_starts, **params), then which chain of every read is the answer: kmers.select_table over the table with one
@@ -458,11 +339,8 @@ class KmerPositionIndex(_Handle):
         rank in its read, the mapping quality of a primary and the primary / kept flags; best[s] = the best row of read s, -1 for a read
         without chains.  The score is the chaining score; kmers.select_chains takes any other.  The keyword targets= (a
         kmerhash_amd.Targets, see chains()) travels with params: the rows of a read on different targets then compete with each other."""
-        if not self.stranded:
-            raise ValueError("chain_select() needs an index made with stranded=True: without the strand bit a hit has no orientation")
-        targets = params.pop("targets", None)
-        table = self._chains(seq, read_starts, params, targets)[0]
-        return table, select_table(table, 1 if read_starts is None else len(read_starts), mask_pct=mask_pct, pri_pct=pri_pct, best_n=best_n, device=self.device)
+        self._need_stranded("chain_select")
+        return mapper.chain_select(self, seq, read_starts, mask_pct, pri_pct, best_n, **params)
 
     def _syncmers(self, seq, fastq=False):
         """the closed syncmers of a text under the index's own parameters"""

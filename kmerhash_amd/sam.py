@@ -6,8 +6,10 @@ import collections
 import numpy as np
 
 from . import _capi as K
-from ._call import _Buf, _is_tensor, alloc, check_same, torch, two_pass
-from .kmers import FLAG_KEPT, FLAG_PRIMARY, ChainRecords, Mapping, _host, cigar_text
+from ._call import _Buf, alloc, check_same, two_pass
+from ._xp import NUMPY, namespace_of
+from .mapper import FLAG_PRIMARY, ChainRecords, Mapping, ReadLayout, _host, chain_read_intervals, cigar_text, printable as printable_rows
+from .targets import inside_target
 
 RecordDiffs = collections.namedtuple("RecordDiffs", "ok offsets text")
 DIFF_KINDS = {"cs": 0, "md": 1}      # KH_DIFF_CS, KH_DIFF_MD
@@ -78,18 +80,6 @@ def sam_header(targets=None, ref_name=None, ref_len=None):
     return "".join(l + "\n" for l in lines)
 
 
-def _printable(mapping, targets, kept_only):
-    """the rows write_paf would print, and the other rows it would look at -> (printable, considered, target per row or None)"""
-    flag, valid = _host(mapping.select.flag, np.uint8), _host(mapping.records.valid, np.uint8)
-    considered = (flag & FLAG_KEPT) != 0 if kept_only else np.ones(len(valid), dtype=bool)
-    good, tgt = valid != 0, None
-    if targets is not None:      # a row's target is the one its first reference base lies in; its end must lie there too
-        rs, re_ = _host(mapping.records.rs, np.uint32), _host(mapping.records.re, np.uint32)
-        tgt, _ = targets.locate(rs)
-        good = good & (tgt >= 0) & (re_.astype(np.int64) <= targets.ends.astype(np.int64)[np.maximum(tgt, 0)])
-    return considered & good, considered, tgt
-
-
 def _mapped_reads(mapping, printable):
     """per read: is select.best[s] a printable row?"""
     best = _host(mapping.select.best, np.int32).astype(np.int64)
@@ -153,7 +143,7 @@ def _sam_lines(mapping, text_offsets, text, seq_rows, read_names, qual_rows, md,
     rs, re_, nm = _host(rec.rs, np.uint32), _host(rec.re, np.uint32), _host(rec.nm, np.uint32)
     n_rows, n_reads = len(flag), len(best)
     rescued = rescued or {}
-    printable, considered, tgt = _printable(mapping, targets, kept_only)
+    printable, considered, tgt = printable_rows(NUMPY, mapping, targets, kept_only)
     mapped = _mapped_reads(mapping, printable) if pairs is None else None      # (paired: the representatives say who is mapped)
     toff, raw = _rows_of((text_offsets, text))
     soff, sraw = _rows_of(seq_rows)
@@ -343,14 +333,9 @@ def _write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends, q
     """the body of write_sam() (pairs None), write_sam_pairs() and write_sam_rescued()"""
     sb = _Buf.text(seq)
     seq = sb.obj
-    n_text = sb.n
-    rs_ = np.asarray(read_starts.cpu() if _is_tensor(read_starts) else read_starts, dtype=np.int64).ravel()
-    if read_ends is None:
-        re_ = np.concatenate([rs_[1:], [n_text]])
-    else:
-        re_ = np.asarray(read_ends.cpu() if _is_tensor(read_ends) else read_ends, dtype=np.int64).ravel()
-    if re_.size != rs_.size or (re_ < rs_).any() or (re_ > n_text).any() or (rs_ < 0).any():
-        raise ValueError("read_starts and read_ends must hold one byte offset per read, 0 <= read_starts[s] <= read_ends[s] <= len(seq)")
+    layout = ReadLayout(read_starts, read_ends, sb.n, 1)
+    layout.bounded(every=True)
+    rs_, re_ = layout.host
     hm = _host_columns(mapping, parent=pairs is not None)
     n_reads = len(hm.select.best)
     if rs_.size != n_reads:
@@ -358,19 +343,14 @@ def _write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends, q
     seg = hm.table.seg.astype(np.int64)
     if len(seg) and int(seg.max()) >= n_reads:
         raise ValueError("the table names read %d, the Mapping holds %d reads" % (int(seg.max()), n_reads))
-    lo, hi = rs_[seg].astype(np.uint32), re_[seg].astype(np.uint32)
-    dev = sb.dev
-
-    def place(a):      # a host column to where the texts live
-        a = np.ascontiguousarray(a)
-        return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(sb.device) if dev else a
-
+    lo, hi = chain_read_intervals(NUMPY, layout, seg)
+    place = namespace_of(seq).place      # a host column to where the texts live
     rec = mapping.records
     toff, ctext = cigar_text(rec.offsets, rec.ops, device)
     dlo, dhi = place(lo), place(hi)
     diffs = {kind: record_diffs(seq, ref_text, rec, mapping.table.rev, dlo, dhi, kind, ref_base, device) if want else None for kind, want in (("md", md), ("cs", cs))}
     # SEQ and QUAL: the oriented read for the primary rows that are printed, the read as given for the unmapped reads
-    printable, _, _ = _printable(hm, targets, kept_only)
+    printable, _, _ = printable_rows(NUMPY, hm, targets, kept_only)
     mapped = _mapped_reads(hm, printable)
     need = printable & ((hm.select.flag & FLAG_PRIMARY) != 0) & mapped[seg] if len(seg) else np.zeros(0, dtype=bool)
     if pairs is not None:      # SEQ goes to the representatives and the 0x800 rows; the unmapped reads are those without a representative
@@ -390,8 +370,8 @@ def _write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends, q
         take = inside & (ed >= 0) & (r_re > r_rs) & (rep[at] < 0) & (rep[at ^ 1] >= 0) if n_reads else np.zeros(len(rd), dtype=bool)      # (re == rs: a row of insertions only has no place)
         r_tgt = None
         if targets is not None:      # printable under the rule of the rows: inside one target
-            r_tgt, _ = targets.locate(r_rs)
-            take = take & (r_tgt >= 0) & (r_re <= targets.ends.astype(np.int64)[np.maximum(r_tgt, 0)])
+            inside, r_tgt = inside_target(NUMPY, targets, r_rs, r_re)
+            take = take & inside
         coff, craw = _rows_of(cigar_text(rescue.offsets, rescue.ops, device))
         as_rec = ChainRecords(place(take.astype(np.uint8)), None, None, rescue.rs, rescue.re, None, None, None, None, rescue.offsets, rescue.ops)
         r_lo, r_hi = place(rs_[at].astype(np.uint32)), place(re_[at].astype(np.uint32))

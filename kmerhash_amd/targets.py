@@ -6,7 +6,8 @@ neither a chain link nor an end extension crosses one, and kmers.group_anchors k
 a build-time step."""
 import numpy as np
 
-from ._call import _is_tensor, torch
+from ._call import torch
+from ._xp import namespace_of
 
 TARGET_NONE = 0xFFFFFFFF          # KH_TARGET_NONE: an anchor that lies in no target
 MIN_SPACER = 32                   # max_edits is at most 31
@@ -99,19 +100,24 @@ class Targets:
         """positions -> (target, local): the target every position lies in and its offset from that target's start; target -1 (and local
         0) for a position in a spacer or beyond the last target.  numpy in (any integer dtype; uint32 bits in an int32 array are read as
         uint32), numpy int64 out; a CUDA tensor in (int32 holding uint32 bits, or int64), int64 tensors out."""
-        if _is_tensor(pos) and pos.is_cuda:
-            p = pos.long()
-            if pos.dtype == torch.int32:
-                p = p & 0xFFFFFFFF
-            starts, ends = (x.long() & 0xFFFFFFFF for x in self.to(pos.device))
-            t = torch.searchsorted(starts, p, right=True) - 1
-            tc = t.clamp(min=0)
-            ok = (t >= 0) & (p < ends[tc])
-            return torch.where(ok, t, torch.full_like(t, -1)), torch.where(ok, p - starts[tc], torch.zeros_like(p))
-        p = np.asarray(pos.cpu().numpy() if _is_tensor(pos) else pos)
-        p = p.view(np.uint32).astype(np.int64) if p.dtype == np.int32 else p.astype(np.int64)
-        starts, ends = self.starts.astype(np.int64), self.ends.astype(np.int64)
-        t = np.searchsorted(starts, p, side="right") - 1
-        tc = np.maximum(t, 0)
+        return self.locate_on(namespace_of(pos), pos)
+
+    def bound(self, xp, end):
+        """starts (end = 0) or ends (end = 1) as an int64 column of the namespace xp"""
+        return (self.starts, self.ends)[end].astype(np.int64) if xp.host else xp.widen(self.to(xp.device)[end])
+
+    def locate_on(self, xp, pos):
+        """locate() over the array namespace xp (kmerhash_amd._xp), where pos lives"""
+        p = xp.widen(pos)
+        starts, ends = self.bound(xp, 0), self.bound(xp, 1)
+        t = xp.searchsorted(starts, p, right=True) - 1
+        tc = xp.maximum(t, 0)
         ok = (t >= 0) & (p < ends[tc])
-        return np.where(ok, t, -1), np.where(ok, p - starts[tc], 0)
+        return xp.where(ok, t, xp.full(len(t), -1)), xp.where(ok, p - starts[tc], xp.full(len(p), 0))
+
+
+def inside_target(xp, targets, rs, re_):
+    """the half of the printable-row rule that needs the contig table: the interval [rs, re) (uint32 bits or int64) lies inside one
+    target -- its first base in a target, its end not beyond that target's end -> (inside, target per row, -1: none)"""
+    tgt, _ = targets.locate_on(xp, rs)
+    return (tgt >= 0) & (xp.widen(re_) <= targets.bound(xp, 1)[xp.maximum(tgt, 0)]), tgt

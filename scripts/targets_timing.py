@@ -76,7 +76,7 @@ if __name__ == "__main__":
         x.build_sequences(text)
         reads, rs = reads_of(torch, text, a.reads, a.read_bases, 11)
         q, r, v = x.anchors(reads)
-        seg = x._read_segments(q, rs)
+        seg = kh.mapper.read_segments(kh.mapper.namespace_of(q), q, kh.mapper.ReadLayout(rs, None, None))
         group = lambda: KM.group_anchors(q, r, v, T, K, seg)                            # noqa: E731
         plain = lambda: x.map(reads, text, read_starts=rs)                              # noqa: E731
         multi = lambda: x.map(reads, text, read_starts=rs, targets=T)                   # noqa: E731
