@@ -1206,6 +1206,74 @@ kh_status kh_mate_rescue(const void* qtext /*[h|d] u8[nq]*/, uint64_t nq, const 
                          uint64_t* out_offsets /*[n + 1]*/, uint32_t* out_ops /*[cap_ops] or NULL*/, uint64_t cap_ops, uint64_t* n_ops,
                          int device, void* hip_stream);
 
+/* ---- SAM lines from line columns.  Everything a SAM alignment line is made of already exists as columns and byte CSRs (the read and
+ *      target names, kh_cigar_text, kh_oriented_rows, kh_record_diffs); kh_sam_lines turns n_lines rows of LINE COLUMNS into the text
+ *      of the lines.  It knows nothing of mappings or pairs: which line prints what is the caller's (sam.sam_line_columns), so one
+ *      call serves unpaired and paired output.  The kernels equal tests/samtext_model.py byte for byte.
+ *      Byte CSRs.  Seven of them, each four arguments: X_off (u64 [n_X + 1]), X_text (u8 [X_bytes]), the number of rows n_X and the
+ *      number of bytes X_bytes: names (read names), tnames (target names), cigar (CIGAR text), seq (SEQ rows), qual (QUAL rows), md
+ *      and cs (difference strings).  Any of them may be absent: n_X == 0 (then X_off and X_text may be null and are not read).
+ *      ROW r of a CSR: r is INSIDE iff 0 <= r < n_X; its bytes are X_text[a, b) with a = min(X_off[r], X_bytes) and
+ *      b = min(X_off[r + 1], X_bytes), EMPTY where b <= a.  A row index outside its CSR is never an access: what it prints is said
+ *      per field below.
+ *      Line columns, each [n_lines]: l_name, l_rname, l_cigar, l_rnext, l_seq, l_qual, l_md, l_cs (i32 row indexes into names,
+ *      tnames, cigar, tnames, seq, qual, md, cs); l_flag, l_pos, l_pnext, l_nm, l_cm (u32); l_tlen, l_s1, l_s2 (i32); l_mapq (u8);
+ *      l_tp (u8, one byte printed as it is); l_tags (u8, a mask of KH_SAMTAG_*).
+ *      Line i is, with TAB between the fields and no TAB at its end:
+ *        QNAME   row l_name[i] of names; '*' where the row is outside (an empty row prints nothing)
+ *        FLAG    l_flag[i]
+ *        RNAME   row l_rname[i] of tnames; '*' where outside (-1 is the way to say so)
+ *        POS     l_pos[i]
+ *        MAPQ    l_mapq[i]
+ *        CIGAR   row l_cigar[i] of cigar; '*' where outside
+ *        RNEXT   '=' where l_rnext[i] == KH_SAM_RNEXT_SAME (-2); else row l_rnext[i] of tnames; '*' where outside
+ *        PNEXT   l_pnext[i]
+ *        TLEN    l_tlen[i]
+ *        SEQ     row l_seq[i] of seq; '*' where the row is outside OR empty
+ *        QUAL    row l_qual[i] of qual; '*' where the row is outside OR empty
+ *      then, each with a TAB in front and only where its bit of l_tags[i] is set (the bits are independent; bits 4..7 are ignored):
+ *        KH_SAMTAG_BASE (1)   NM:i:<l_nm[i]>  tp:A:<the byte l_tp[i]>  cm:i:<l_cm[i]>  s1:i:<l_s1[i]>
+ *        KH_SAMTAG_S2 (2)     s2:i:<l_s2[i]>
+ *        KH_SAMTAG_MD (4)     MD:Z:<row l_md[i] of md; nothing where the row is outside>
+ *        KH_SAMTAG_CS (8)     cs:Z:<row l_cs[i] of cs; nothing where the row is outside>
+ *      and one line feed (10).  l_tags[i] == 0 gives exactly the 11 mandatory fields: the line of an unmapped read.  Numbers are
+ *      decimal without padding, a '-' in front of a negative one: what "%d" prints.
+ *      Output: a byte CSR -- out_offsets [n_lines + 1], the prefix sums of the line lengths, and out_text, the lines one after the
+ *      other -- under the conventions of kh_cigar_text: out_text == NULL counts only (out_offsets and *n_text are written); more
+ *      bytes than cap_text: KH_ERR_INVALID with *n_text set, out_offsets written and out_text untouched.  All arrays live in the
+ *      memory `where` names.  Device memory: everything is queued on hip_stream, one host wait per pass to learn *n_text.  Host
+ *      memory: staged, the call synchronises.
+ *      A line is shorter than 2^32 bytes because the call is: KH_ERR_INVALID unless
+ *      names_bytes + 2 tnames_bytes + cigar_bytes + seq_bytes + qual_bytes + md_bytes + cs_bytes + KH_SAM_LINE_FIXED < 2^32
+ *      (KH_SAM_LINE_FIXED = 256 bounds the separators, numbers and tag names of a line; a line can print a target name twice).
+ *      KH_ERR_INVALID before anything is allocated, read or written: that sum, n_lines or any n_X > 2^31, any X_bytes > 2^32, `where`
+ *      outside the enum, a null out_offsets or n_text, a null X_off while n_X > 0, a null X_text while X_bytes > 0, and a null line
+ *      column while n_lines > 0 (all nineteen are needed, whatever the masks say).  n_lines == 0: KH_OK, *n_text = 0,
+ *      out_offsets[0] = 0 (host memory: without a device).
+ *      Route (kh_kernels_samtext.h): both passes are one wavefront per line in which lane p sizes piece p (a field with the literal in
+ *      front of it) through one device function.  The count pass adds the sizes up by a wave sum -- row lengths and digit counts, no
+ *      text is read --; the index's scan makes the offsets; the emit pass places the pieces by a wave prefix sum, every lane writes
+ *      its own literal and digits and the wave copies the CSR rows in 8-byte words aligned to the destination. */
+#define KH_SAMTAG_BASE 1u
+#define KH_SAMTAG_S2 2u
+#define KH_SAMTAG_MD 4u
+#define KH_SAMTAG_CS 8u
+#define KH_SAM_RNEXT_SAME (-2)
+#define KH_SAM_LINE_FIXED 256u
+kh_status kh_sam_lines(const uint64_t* names_off /*[h|d] u64[n_names+1]*/, const uint8_t* names_text /*[h|d] u8[names_bytes]*/, uint64_t n_names, uint64_t names_bytes,
+                       const uint64_t* tnames_off, const uint8_t* tnames_text, uint64_t n_tnames, uint64_t tnames_bytes,
+                       const uint64_t* cigar_off, const uint8_t* cigar_text, uint64_t n_cigar, uint64_t cigar_bytes,
+                       const uint64_t* seq_off, const uint8_t* seq_text, uint64_t n_seq, uint64_t seq_bytes,
+                       const uint64_t* qual_off, const uint8_t* qual_text, uint64_t n_qual, uint64_t qual_bytes,
+                       const uint64_t* md_off, const uint8_t* md_text, uint64_t n_md, uint64_t md_bytes,
+                       const uint64_t* cs_off, const uint8_t* cs_text, uint64_t n_cs, uint64_t cs_bytes,
+                       const int32_t* l_name /*[h|d] each [n_lines]*/, const uint32_t* l_flag, const int32_t* l_rname, const uint32_t* l_pos, const uint8_t* l_mapq,
+                       const int32_t* l_cigar, const int32_t* l_rnext, const uint32_t* l_pnext, const int32_t* l_tlen, const int32_t* l_seq, const int32_t* l_qual,
+                       const uint8_t* l_tags, const uint32_t* l_nm, const uint8_t* l_tp, const uint32_t* l_cm, const int32_t* l_s1, const int32_t* l_s2,
+                       const int32_t* l_md, const int32_t* l_cs, uint64_t n_lines, kh_mem where,
+                       uint64_t* out_offsets /*[n_lines+1]*/, uint8_t* out_text /*[cap_text] or NULL*/, uint64_t cap_text, uint64_t* n_text,
+                       int device, void* hip_stream);
+
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);
 

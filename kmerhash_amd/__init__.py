@@ -17,6 +17,7 @@ from .kmers import pair_chains, pair_mapping, PairSelect  # noqa: F401
 from .kmers import rescue_mates, rescue_requests, MateRescue, RESCUE_NONE, RESCUE_OVER  # noqa: F401
 from .targets import Targets, TARGET_NONE  # noqa: F401
 from .sam import record_diffs, oriented_rows, sam_header, sam_lines, write_sam, write_sam_pairs, write_sam_rescued, RecordDiffs  # noqa: F401
+from .sam import names_csr, sam_line_columns, sam_lines_text, sam_text, write_sam_bytes, SamText, LineColumns  # noqa: F401
 from .wide import syncmers128_from_sequence, syncmers128_from_fastq, is_syncmer128  # noqa: F401
 from .dist_index import ShardedKmerPositionIndex, IndexGpuBackend, WideIndexGpuBackend  # noqa: F401
 from . import workloads  # noqa: F401
@@ -32,4 +33,5 @@ __all__ = ["hashmap_robinhood_doubling", "hashmap_linearprobe_doubling", "hash_b
            "group_anchors", "AnchorGroups", "Targets", "TARGET_NONE",
            "record_diffs", "oriented_rows", "sam_header", "sam_lines", "write_sam", "RecordDiffs",
            "pair_chains", "pair_mapping", "PairSelect", "write_sam_pairs",
-           "rescue_mates", "rescue_requests", "MateRescue", "RESCUE_NONE", "RESCUE_OVER", "write_sam_rescued"]
+           "rescue_mates", "rescue_requests", "MateRescue", "RESCUE_NONE", "RESCUE_OVER", "write_sam_rescued",
+           "names_csr", "sam_line_columns", "sam_lines_text", "sam_text", "write_sam_bytes", "SamText", "LineColumns"]

@@ -104,6 +104,8 @@ SYMBOLS = [
     "kh_pair_chains",
     # mate rescue: a mate without a row aligned end to end inside the window its partner allows
     "kh_mate_rescue",
+    # SAM lines on the device: the text of the alignment lines from line columns and byte CSRs
+    "kh_sam_lines",
 ]
 
 _lib = None
@@ -292,6 +294,7 @@ def lib():
     L.kh_oriented_rows.argtypes = [vp, u64, vp, vp, vp, u64, u32, i32, vp, vp, u64, pu64, i32, vp]
     L.kh_pair_chains.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, u64, u32, u32, u32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
     L.kh_mate_rescue.argtypes = [vp, u64, vp, u64, u32, vp, vp, vp, vp, vp, u64, u32, i32, vp, vp, vp, vp, vp, vp, u64, pu64, i32, vp]
+    L.kh_sam_lines.argtypes = [vp, vp, u64, u64] * 7 + [vp] * 19 + [u64, i32, vp, vp, u64, pu64, i32, vp]
     L.kh_anchor_targets.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, u64, u32, i32] + [vp] * 8 + [pu64, i32, vp]
     for s in SYMBOLS:
         if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error", "kh_wide_index_last_error"):

@@ -52,6 +52,14 @@ class _Numpy:
     def nonzero(self, mask):
         return np.flatnonzero(mask)
 
+    def prefix(self, x):
+        """counts or a mask -> their exclusive prefix sums and the total: int64, one entry more"""
+        return np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(np.asarray(x), dtype=np.int64)])
+
+    def ints(self, values):
+        """0-d results (a sum, a min, a max) -> Python ints"""
+        return [int(v) for v in values]
+
 
 class Torch:
     host = False                  # reading a value is a wait for the stream: the glue asks for none beyond the documented ones
@@ -98,6 +106,13 @@ class Torch:
 
     def nonzero(self, mask):
         return torch.nonzero(mask).ravel()
+
+    def prefix(self, x):
+        return torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), torch.cumsum(x.long(), 0)])
+
+    def ints(self, values):
+        """... gathered into one small tensor and read once: the one wait of a glue step that must look at its numbers"""
+        return torch.stack([v.long().reshape(()) for v in values]).tolist() if values else []
 
 
 NUMPY = _Numpy()

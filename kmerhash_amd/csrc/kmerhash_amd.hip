@@ -22,6 +22,7 @@
 //   records : kh_chain_records, one run-length row and one line of numbers per chain from the link rows, end rows and clips: a wavefront per chain; kh_cigar_text, a run CSR as text (kh_kernels_records.h).
 //   targets : kh_anchor_targets, the anchors of every read regrouped by the target (contig) they fall in: a lane per anchor, then a wavefront per read (kh_kernels_targets.h).
 //   sam     : kh_record_diffs, the cs or MD string of every record row: a wavefront per row along the two texts; kh_oriented_rows, byte ranges copied as they stand or back to front and complemented (kh_kernels_sam.h).
+//   samtext : kh_sam_lines, the text of SAM alignment lines from line columns and byte CSRs: a wavefront per line and a lane per field in both passes, the lengths by a wave sum, the places by a wave prefix sum (kh_kernels_samtext.h).
 //   ends    : kh_chain_ends, both ends of every kept chain extended to the ends of its read or to a soft clip: a wavefront per end, target free, stop by score (kh_kernels_ends.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
@@ -39,6 +40,7 @@
 #include "kh_kernels_sam.h"
 #include "kh_kernels_pair.h"
 #include "kh_kernels_rescue.h"
+#include "kh_kernels_samtext.h"
 #include "kh_part_sizing.h"
 #include "kh_scratch.h"
 #include "../../include/kmerhash_amd.h"
@@ -4744,6 +4746,70 @@ kh_status kh_mate_rescue(const void* qtext, uint64_t nq, const void* rtext, uint
   return emit_total(s, total, out_ops, cap_ops, n_ops, where, [&](uint32_t* dops) {
     hipLaunchKernelGGL(k_rescue_emit, dim3(grid_for(n, KED_THREADS, ncu * 8)), dim3(KED_THREADS), 0, stream, P, (const int32_t*)dd, (const uint32_t*)de,
                        (const uint64_t*)doff, (const uint64_t*)paths, (uint64_t)total, dops);
+  });
+}
+// ---- SAM lines from line columns and byte CSRs (kernels: kh_kernels_samtext.h).  The protocol of kh_cigar_text: count, scan, one host
+//      wait for *n_text, emit.  One pooled block holds the line lengths and the scan's tile sums (and the staged arrays of a host call), a
+//      second one the staged text of a host call.
+static_assert(KST_CSRS == 7 && KST_COLS == 19, "the seven CSRs and the nineteen line columns of the entry point");
+static_assert(KST_TAGS_BASE == KH_SAMTAG_BASE && KST_TAGS_S2 == KH_SAMTAG_S2 && KST_TAGS_MD == KH_SAMTAG_MD && KST_TAGS_CS == KH_SAMTAG_CS &&
+              KST_ROW_SAME == KH_SAM_RNEXT_SAME, "one set of tag bits, one word for the line's own target");
+kh_status kh_sam_lines(const uint64_t* names_off, const uint8_t* names_text, uint64_t n_names, uint64_t names_bytes, const uint64_t* tnames_off, const uint8_t* tnames_text,
+                       uint64_t n_tnames, uint64_t tnames_bytes, const uint64_t* cigar_off, const uint8_t* cigar_text, uint64_t n_cigar, uint64_t cigar_bytes,
+                       const uint64_t* seq_off, const uint8_t* seq_text, uint64_t n_seq, uint64_t seq_bytes, const uint64_t* qual_off, const uint8_t* qual_text,
+                       uint64_t n_qual, uint64_t qual_bytes, const uint64_t* md_off, const uint8_t* md_text, uint64_t n_md, uint64_t md_bytes, const uint64_t* cs_off,
+                       const uint8_t* cs_text, uint64_t n_cs, uint64_t cs_bytes, const int32_t* l_name, const uint32_t* l_flag, const int32_t* l_rname,
+                       const uint32_t* l_pos, const uint8_t* l_mapq, const int32_t* l_cigar, const int32_t* l_rnext, const uint32_t* l_pnext, const int32_t* l_tlen,
+                       const int32_t* l_seq, const int32_t* l_qual, const uint8_t* l_tags, const uint32_t* l_nm, const uint8_t* l_tp, const uint32_t* l_cm,
+                       const int32_t* l_s1, const int32_t* l_s2, const int32_t* l_md, const int32_t* l_cs, uint64_t n_lines, kh_mem where, uint64_t* out_offsets,
+                       uint8_t* out_text, uint64_t cap_text, uint64_t* n_text, int device, void* stream_) {
+  const uint64_t lim = uint64_t(1) << 31, tlim = uint64_t(1) << 32;
+  struct In { const uint64_t* off; const uint8_t* txt; uint64_t n_rows, n_bytes; };
+  const In in[7] = {{names_off, names_text, n_names, names_bytes}, {tnames_off, tnames_text, n_tnames, tnames_bytes}, {cigar_off, cigar_text, n_cigar, cigar_bytes},
+                    {seq_off, seq_text, n_seq, seq_bytes}, {qual_off, qual_text, n_qual, qual_bytes}, {md_off, md_text, n_md, md_bytes}, {cs_off, cs_text, n_cs, cs_bytes}};
+  if (n_lines > lim || (where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !out_offsets || !n_text) return KH_ERR_INVALID;
+  uint64_t longest = KH_SAM_LINE_FIXED + tnames_bytes;      // (a line can print a target name twice: RNAME and RNEXT)
+  for (const In& c : in) {
+    if (c.n_rows > lim || c.n_bytes > tlim || (c.n_rows && !c.off) || (c.n_bytes && !c.txt)) return KH_ERR_INVALID;
+    longest += c.n_bytes;
+  }
+  if (longest >= tlim) return KH_ERR_INVALID;
+  if (n_lines && (!l_name || !l_flag || !l_rname || !l_pos || !l_mapq || !l_cigar || !l_rnext || !l_pnext || !l_tlen || !l_seq || !l_qual || !l_tags || !l_nm || !l_tp ||
+                  !l_cm || !l_s1 || !l_s2 || !l_md || !l_cs)) return KH_ERR_INVALID;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  *n_text = 0;
+  if (n_lines == 0) return empty_rows(out_offsets, 1, where, device, stream);
+  HIPCHK0(hipSetDevice(device));
+  const uint64_t nst = (n_lines + KI_SCAN_TILE - 1) / KI_SCAN_TILE;
+  Scratch s(device, stream);
+  uint32_t* bytes = nullptr; uint64_t* doff = nullptr; unsigned long long* ssums = nullptr;
+  KstArgs P{};
+  if (!s.layout([&](Scratch& c) {
+        bytes = c.take<uint32_t>(n_lines); ssums = c.take<unsigned long long>(nst + 1);
+        for (int j = 0; j < 7; ++j) {      // (a CSR without rows stays null: every row index lies outside it)
+          P.csr[j].off = c.in(in[j].off, in[j].n_rows ? in[j].n_rows + 1 : 0, where); P.csr[j].txt = c.in(in[j].txt, in[j].n_rows ? in[j].n_bytes : 0, where);
+          P.csr[j].n_rows = in[j].n_rows; P.csr[j].n_bytes = in[j].n_rows ? in[j].n_bytes : 0;
+        }
+        int j = 0;
+        for (const uint32_t* p : {l_flag, l_pos, l_pnext, l_nm, l_cm}) { static const int at[5] = {1, 3, 7, 12, 14}; P.col[at[j++]] = c.in(p, n_lines, where); }
+        j = 0;
+        for (const int32_t* p : {l_name, l_rname, l_cigar, l_rnext, l_tlen, l_seq, l_qual, l_s1, l_s2, l_md, l_cs}) {
+          static const int at[11] = {0, 2, 5, 6, 8, 9, 10, 15, 16, 17, 18};
+          P.col[at[j++]] = c.in(p, n_lines, where);
+        }
+        P.col[KST_COL_MAPQ] = c.in(l_mapq, n_lines, where); P.col[KST_COL_TAGS] = c.in(l_tags, n_lines, where); P.col[KST_COL_TP] = c.in(l_tp, n_lines, where);
+        doff = c.out(out_offsets, n_lines + 1, where);
+      })) return s.finish();
+  P.n_lines = (uint32_t)n_lines;
+  const uint32_t ncu = (uint32_t)cu_count(device);
+  hipLaunchKernelGGL(k_samtext_count, dim3(grid_for(n_lines, KST_WAVES, ncu * 8)), dim3(KST_THREADS), 0, stream, P, bytes);
+  scan_counts(stream, (const uint32_t*)bytes, n_lines, ssums, doff);
+  s.launched();
+  unsigned long long total = 0;
+  s.read(&total, (const unsigned long long*)(ssums + nst));
+  s.copy_back(doff, n_lines + 1);
+  return emit_total(s, total, out_text, cap_text, n_text, where, [&](uint8_t* dtext) {
+    hipLaunchKernelGGL(k_samtext_emit, dim3(grid_for(n_lines, KST_WAVES, ncu * 8)), dim3(KST_THREADS), 0, stream, P, (const uint64_t*)doff, (uint64_t)total, dtext);
   });
 }
 }  // extern "C"

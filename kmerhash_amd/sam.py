@@ -6,7 +6,7 @@ import collections
 import numpy as np
 
 from . import _capi as K
-from ._call import _Buf, alloc, check_same, two_pass
+from ._call import _Buf, _is_tensor, alloc, check_same, two_pass
 from ._xp import NUMPY, namespace_of
 from .mapper import FLAG_PRIMARY, ChainRecords, Mapping, ReadLayout, _host, chain_read_intervals, cigar_text, printable as printable_rows
 from .targets import inside_target
@@ -400,3 +400,264 @@ def _write_sam(fh, mapping, seq, ref_text, read_names, read_starts, read_ends, q
         fh.write(ln + "\n")
     n_head = len(sam_header(targets, ref_name, ref_len).splitlines()) if header else 0
     return len(lines) - n_head - (n_unmapped if unmapped else 0), skipped, n_unmapped
+
+
+# ---- SAM lines on the device: the columns of every line from the Mapping (array glue), the text from kh_sam_lines
+TAG_BASE, TAG_S2, TAG_MD, TAG_CS = 1, 2, 4, 8      # KH_SAMTAG_*
+RNEXT_SAME = -2                                    # KH_SAM_RNEXT_SAME
+LINE_COLUMNS = ("name", "flag", "rname", "pos", "mapq", "cigar", "rnext", "pnext", "tlen", "seq", "qual", "tags", "nm", "tp", "cm", "s1", "s2", "md", "cs")
+LINE_DTYPES = (np.int32, np.uint32, np.int32, np.uint32, np.uint8, np.int32, np.int32, np.uint32, np.int32, np.int32, np.int32, np.uint8, np.uint32, np.uint8, np.uint32,
+               np.int32, np.int32, np.int32, np.int32)
+LineColumns = collections.namedtuple("LineColumns", LINE_COLUMNS + ("need", "show", "lines", "skipped", "unmapped_reads"))
+SamText = collections.namedtuple("SamText", "header offsets text lines skipped unmapped_reads")
+
+
+def names_csr(names):
+    """a list of names -> (offsets uint64 [n + 1], bytes uint8) on the host: one join, one encode.  Names must be ASCII
+    (UnicodeEncodeError otherwise): a character is then a byte and the lengths of the strings are the lengths of the rows."""
+    names = [n if isinstance(n, str) else str(n) for n in names]
+    offs = np.zeros(len(names) + 1, dtype=np.uint64)
+    np.cumsum(np.fromiter(map(len, names), dtype=np.uint64, count=len(names)), out=offs[1:])
+    return offs, np.frombuffer("".join(names).encode("ascii"), dtype=np.uint8)
+
+
+def _is_csr(x):
+    return isinstance(x, tuple) and len(x) == 2 and not isinstance(x[0], (str, bytes))
+
+
+def sam_line_columns(xp, mapping, targets=None, ref_start=0, kept_only=True, unmapped=True, md=True, cs=False, pairs=None, diff_ok=(), refuse=()):
+    """which rows and reads of a Mapping give a SAM line, in which order and with which columns: the rules of sam_lines() (and, with
+    pairs, of write_sam_pairs() without rescued mates) restated as array operations over the namespace xp (kmerhash_amd._xp) in which
+    the Mapping's columns -- and those of pairs, a PairSelect -- live: numpy, or torch on the Mapping's device.
+    The rows the columns name: `name` read s of the read names; `rname` / `rnext` the target number (0 without targets; -1 '*';
+    RNEXT_SAME '='); `cigar`, `md`, `cs` table row c; `seq` / `qual` row c of a CSR of n_rows + n_reads rows for a line of table row c
+    that prints its bases, row n_rows + s for the line of unmapped read s, -1 for '*' (the layout sam_lines() takes).
+    Order: reads ascending, a read's printable rows in table order, an unmapped read's line in the read's place -- table.seg does not
+    descend (mapper.seg_offsets), so a line's number is two prefix sums and one searchsorted away; nothing is sorted.
+    diff_ok: the ok columns of the RecordDiffs that will be printed; a printed row that is not ok raises the ValueError of write_sam.
+    refuse: checks of the caller that ride along in the one read, as pairs (a 0-d count, a message): a count that is not zero raises
+    ValueError(message), before the glue's own refusals.
+    A ref_start beyond the start of a printed row is refused (ValueError): POS is an unsigned column, where sam_lines() prints a
+    negative number.
+    -> LineColumns: the nineteen columns of kh_sam_lines in its containers; need [n_rows] / show [n_reads] (bool): the table rows and
+    the reads whose SEQ a line prints; lines, skipped, unmapped_reads: the triple of write_sam.  All numbers the host needs -- the
+    three counts, the number of lines, the diff_ok check and the range check of table.seg -- are read together, once: with torch one
+    wait for the stream."""
+    t, sel, rec = mapping.table, mapping.select, mapping.records
+    flag, rev = xp.signed(xp.col(sel.flag, np.uint8)), xp.signed(xp.col(t.rev, np.uint8)) & 1
+    seg = xp.widen(xp.col(t.seg, np.uint32))
+    n_rows, n_reads = len(flag), len(sel.best)
+    if n_reads == 0 and n_rows:
+        raise ValueError("the table names read %d, the Mapping holds %d reads" % (0, 0))
+    printable, considered, tgt = printable_rows(xp, mapping, targets, kept_only)
+    c, s = xp.arange(n_rows), xp.arange(n_reads)
+    in_range = seg < n_reads
+    segc = xp.minimum(seg, max(n_reads - 1, 0))      # (a row that names no read is reported below; until then it must address nothing)
+    row_of = lambda col, at: col[at] if n_rows else xp.full(len(at), 0)      # noqa: E731  (a gather from the rows, which may be none)
+    rs = xp.widen(xp.col(rec.rs, np.uint32))
+    if targets is None:
+        tn, pos = xp.full(n_rows, 0), rs - int(ref_start) + 1
+    else:
+        if int(ref_start) != 0:
+            raise ValueError("with targets the starts are theirs: ref_start must be 0")
+        tn = tgt
+        pos = rs - targets.bound(xp, 0)[xp.maximum(tgt, 0)] + 1
+    pri = (flag & FLAG_PRIMARY) != 0
+    if pairs is None:
+        best = xp.signed(xp.col(sel.best, np.int32))
+        inside = (best >= 0) & (best < n_rows)
+        mapped = inside & (row_of(xp.signed(printable), xp.where(inside, best, xp.full(n_reads, 0))) != 0)
+        shown = printable & in_range & mapped[segc] if n_reads else printable & in_range
+        r_flag = rev * 0x10 + xp.signed(~pri) * 0x100 + xp.signed(pri & (c != (best[segc] if n_reads else c))) * 0x800
+        r_mapq = xp.signed(xp.col(sel.mapq, np.uint8))
+        r_rnext, r_pnext, r_tlen = xp.full(n_rows, -1), xp.full(n_rows, 0), xp.full(n_rows, 0)
+        u_flag, u_rname, u_pos, u_rnext = xp.full(n_reads, 4), xp.full(n_reads, -1), xp.full(n_reads, 0), xp.full(n_reads, -1)
+    else:
+        prow, pmapq, ptlen = xp.signed(xp.col(pairs.row, np.int32)), xp.signed(xp.col(pairs.mapq, np.uint8)), xp.signed(xp.col(pairs.tlen, np.int32))
+        pflag = xp.signed(xp.col(pairs.flag, np.uint8))
+        if n_reads % 2 or len(prow) != n_reads or len(pmapq) != n_reads or len(ptlen) != n_reads or len(pflag) != n_reads // 2:
+            raise ValueError("pairs must hold one entry per read of the Mapping (row, mapq, tlen) and one per pair (flag), and the reads must come in pairs")
+        parent = xp.signed(xp.col(sel.parent, np.int32))
+        inside = (prow >= 0) & (prow < n_rows)
+        at = xp.where(inside, prow, xp.full(n_reads, 0))
+        rep = xp.where(inside & (row_of(xp.signed(printable), at) != 0) & (row_of(seg, at) == s), prow, xp.full(n_reads, -1))      # the row that represents a read
+        mapped = rep >= 0
+        own = xp.where(in_range, rep[segc], xp.full(n_rows, -1)) if n_reads else xp.full(n_rows, -1)
+        shown = printable & (own >= 0)
+        is_rep = c == own
+        pri = ~(((flag & FLAG_PRIMARY) == 0) | (c == row_of(parent, xp.maximum(own, 0)))) | is_rep      # (ROLE_REP and ROLE_SUPP print bases; ROLE_SEC does not)
+        mate = s ^ 1
+        mr = rep[mate] if n_reads else rep
+        mrc = xp.maximum(mr, 0)
+        fl0 = 0x1 + xp.where((s & 1) != 0, xp.full(n_reads, 0x80), xp.full(n_reads, 0x40)) + xp.where(mr < 0, xp.full(n_reads, 0x8), row_of(rev, mrc) * 0x20)
+        at = xp.where(mr >= 0, mr, rep)      # (an unmapped mate is placed at this read's representative: the mate columns point there)
+        atc = xp.maximum(at, 0)
+        mt = xp.where(at >= 0, row_of(tn, atc), xp.full(n_reads, -1))
+        mpos = xp.where(at >= 0, row_of(pos, atc), xp.full(n_reads, 0))
+        both = (rep >= 0) & (mr >= 0)
+        proper = both & ((pflag[s >> 1] & 1) != 0) if n_reads else both      # (0x2 and TLEN need both representatives)
+        g = lambda col: col[segc] if n_reads else xp.full(n_rows, 0)      # noqa: E731  (a per-read column at every row)
+        r_flag = g(fl0) + rev * 0x10 + xp.signed(~is_rep & pri) * 0x800 + xp.signed(~pri) * 0x100 + xp.signed(is_rep & (g(xp.signed(proper)) != 0)) * 0x2
+        r_mapq = xp.where(is_rep, g(pmapq), xp.signed(xp.col(sel.mapq, np.uint8)))
+        r_rnext = xp.where(g(mt) == tn, xp.full(n_rows, RNEXT_SAME), g(mt))
+        r_pnext = g(mpos)
+        r_tlen = xp.where(is_rep & (g(xp.signed(both)) != 0), g(ptlen), xp.full(n_rows, 0))
+        u_flag, u_rname, u_pos = fl0 + 0x4, mt, mpos
+        u_rnext = xp.where(mr >= 0, xp.full(n_reads, RNEXT_SAME), xp.full(n_reads, -1))
+    un_line = ~mapped if unmapped else (s < 0)
+    need = shown & pri
+    # the numbers the host must see, read once
+    bad = None
+    for ok in diff_ok:
+        b = shown & (xp.signed(xp.col(ok, np.uint8)) == 0)
+        bad = b if bad is None else bad | b
+    numbers = [shown.sum(), un_line.sum(), (considered & in_range & ~shown).sum(), (~mapped).sum(), (shown & (pos < 0)).sum()]
+    if n_rows:      # (a minimum or maximum needs an entry)
+        numbers += [seg.max(), xp.where(bad, c, xp.full(n_rows, n_rows)).min() if bad is not None else seg.max() * 0 + n_rows]
+    got = xp.ints([count for count, _ in refuse] + numbers)
+    for count, (_, message) in zip(got, refuse):
+        if count:
+            raise ValueError(message)
+    got = got[len(refuse):]
+    n_shown, n_un, skipped, n_unmapped, neg_pos, seg_max, first_bad = (got + [0, 0])[:7]
+    if n_rows and seg_max >= n_reads:
+        raise ValueError("the table names read %d, the Mapping holds %d reads" % (seg_max, n_reads))
+    if first_bad < n_rows:
+        raise ValueError("row %d does not walk the two texts: make the Mapping with ref_order=True and pass the texts it was made from" % first_bad)
+    if neg_pos:
+        raise ValueError("ref_start lies beyond the start of %d rows: a position is printed as an unsigned number" % neg_pos)
+    # the number of every line: shown rows before it plus unmapped-read lines before it
+    rows_before, reads_before = xp.prefix(shown), xp.prefix(un_line)
+    n_lines = n_shown + n_un
+    line_of_row = rows_before[:-1] + (reads_before[segc] if n_reads else 0)
+    line_of_read = reads_before[:-1] + rows_before[xp.searchsorted(seg, s)]
+    src = xp.full(n_lines + 1, 0)      # line -> table row c, or n_rows + s; the last entry takes what gives no line
+    src[xp.where(shown, line_of_row, xp.full(n_rows, n_lines))] = c
+    src[xp.where(un_line, line_of_read, xp.full(n_reads, n_lines))] = n_rows + s
+    src = src[:n_lines]
+    is_row = src < n_rows
+    cc = xp.where(is_row, src, xp.full(n_lines, 0))
+    ss = xp.where(is_row, row_of(segc, cc), src - n_rows)
+    R = lambda col: row_of(col, cc)      # noqa: E731
+    U = lambda col: col[ss] if n_reads else xp.full(n_lines, 0)      # noqa: E731
+    pick = lambda r, u: xp.where(is_row, r, u)      # noqa: E731
+    zero, minus = xp.full(n_lines, 0), xp.full(n_lines, -1)
+    lpri = R(xp.signed(pri)) != 0
+    tags = xp.where(is_row, TAG_BASE + xp.signed(lpri) * TAG_S2 + (TAG_MD if md else 0) + (TAG_CS if cs else 0), zero)
+    text_row = pick(xp.where(lpri, cc, minus), n_rows + ss)
+    cols = dict(name=ss, flag=pick(R(r_flag), U(u_flag)), rname=pick(R(tn), U(u_rname)), pos=pick(R(pos), U(u_pos)), mapq=pick(R(r_mapq), zero), cigar=pick(cc, minus),
+                rnext=pick(R(r_rnext), U(u_rnext)), pnext=pick(R(r_pnext), U(u_pos)), tlen=pick(R(r_tlen), zero), seq=text_row, qual=text_row, tags=tags,
+                nm=pick(R(xp.widen(xp.col(rec.nm, np.uint32))), zero), tp=xp.where(lpri, xp.full(n_lines, ord("P")), xp.full(n_lines, ord("S"))),
+                cm=pick(R(xp.widen(xp.col(t.count, np.uint32))), zero), s1=pick(R(xp.signed(xp.col(t.score, np.int32))), zero),
+                s2=pick(R(xp.signed(xp.col(sel.sub, np.int32))), zero), md=pick(cc, minus), cs=pick(cc, minus))
+    return LineColumns(*(xp.narrow(cols[k], dt) for k, dt in zip(LINE_COLUMNS, LINE_DTYPES)), need, un_line, n_shown, skipped, n_unmapped)
+
+
+def _csr_where(names, xp, what):
+    """read or target names -> (offsets _Buf, bytes _Buf): a list goes through names_csr() and to where the Mapping lives; a ready
+    (offsets, bytes) CSR must live there already"""
+    offs, text = names if _is_csr(names) else (xp.place(a) for a in names_csr(names))
+    ob, tb = _Buf(offs, np.uint64), _Buf.text(text)
+    if ob.n < 1:
+        raise ValueError("the offsets of %s must hold one entry per name and one more" % what)
+    return ob, tb
+
+
+def sam_lines_text(names, tnames, cigar, seq, qual, md, cs, columns, device=0):
+    """kh_sam_lines: SAM lines from line columns (the definition is in include/kmerhash_amd.h).  names, tnames, cigar, seq, qual, md,
+    cs: byte CSRs (offsets, text), each or None for an absent one; columns: the nineteen line columns in the order of LINE_COLUMNS.
+    -> (offsets, text): line i is text[offsets[i]:offsets[i + 1]], its line feed included.  numpy in, numpy out (uint64, uint8); CUDA
+    tensors in, tensors out on the current stream (int64, uint8); count, then emit, one wait per pass."""
+    cb = [_Buf(x, dt) for x, dt in zip(columns, LINE_DTYPES)]
+    check_same("the line columns must live in the same memory and have one entry per line", *cb)
+    like, n_lines, args = cb[0], cb[0].n, []
+    for pair in (names, tnames, cigar, seq, qual, md, cs):
+        if pair is None:
+            args += [None, None, 0, 0]
+            continue
+        ob, tb = (_Buf(pair[0], np.uint64), _Buf.text(pair[1])) if not isinstance(pair[0], _Buf) else pair
+        check_same("the CSRs and the line columns must live in the same memory", like, ob, tb, length=False)
+        if ob.n < 1:
+            raise ValueError("the offsets of a CSR hold one entry per row and one more")
+        args += [ob.ptr if ob.n > 1 else None, tb.ptr_or_null, ob.n - 1, tb.n]
+    if n_lines > 2 ** 31:
+        raise ValueError("at most 2^31 lines per call, got %d" % n_lines)
+    offs, optr = alloc(like, n_lines + 1, np.uint64, zero=True)
+    if n_lines == 0:
+        return offs, alloc(like, 0, np.uint8)[0]
+    lead = (*args, *(b.ptr for b in cb), n_lines, like.where, optr)
+    return offs, two_pass("kh_sam_lines", lead, like, np.uint8, device)
+
+
+def sam_text(mapping, seq, ref_text, read_names, read_starts, read_ends=None, qual=None, ref_name=None, ref_len=None, ref_start=0, ref_base=0, targets=None,
+             kept_only=True, unmapped=True, md=True, cs=False, pairs=None, device=0):
+    """the rows of a Mapping as the text of a SAM file, assembled where the Mapping lives: the file write_sam() writes -- with pairs (a
+    PairSelect) the file write_sam_pairs() writes -- byte for byte, without a line ever being formatted on the host.  Arguments as
+    write_sam(); read_names (and the names of targets) may be a ready (offsets, bytes) CSR that lives where the Mapping lives instead
+    of a list of ASCII names (names_csr() makes one).
+    Device calls: cigar_text(), record_diffs() per difference string asked for, oriented_rows() for SEQ and for QUAL over the rows and
+    the reads (the layout of sam_lines()), the array glue sam_line_columns() and kh_sam_lines.  No loop over rows or reads runs in
+    Python and SEQ, QUAL, the CIGAR text and the difference strings are never copied to the host; beyond the waits of those calls
+    (one per pass of a count-then-emit call) there is one: the glue reads its counts and checks together, once -- the bounds check of
+    read_starts / read_ends included where both are CUDA tensors (read_ends may be None); given on the host, or one of each, they
+    are checked there before anything is queued, and a CUDA tensor among them then costs a copy and a wait of its own.
+    One difference from write_sam(): a ref_start beyond the start of a printed row raises ValueError -- POS is an unsigned column of
+    kh_sam_lines, where write_sam() prints a negative POS.
+    A printed row whose difference string is not ok raises the ValueError of write_sam(): make the Mapping with ref_order=True.
+    A MateRescue is not taken: write_sam_rescued() keeps the host path.
+    -> SamText(header, offsets, text, lines, skipped, unmapped_reads): header the bytes of sam_header(); text the body, line i at
+    text[offsets[i]:offsets[i + 1]] -- uint8 / uint64 numpy arrays for numpy input, uint8 / int64 tensors on the current stream for
+    CUDA tensors; (lines, skipped, unmapped_reads) the triple write_sam() / write_sam_pairs() return."""
+    head = sam_header(targets, ref_name, ref_len).encode()      # (checks ref_name / ref_len against targets)
+    sb = _Buf.text(seq)
+    seq = sb.obj
+    xp = namespace_of(seq)
+    layout = ReadLayout(read_starts, read_ends, sb.n, 1)
+    on_device = lambda x: _is_tensor(x) and x.is_cuda      # noqa: E731
+    late = not xp.host and on_device(read_starts) and (read_ends is None or on_device(read_ends))      # the layout lives on the device: its check rides in the glue's one read
+    if not late:
+        layout.bounded(every=True)
+    rec, t = mapping.records, mapping.table
+    n_reads = len(mapping.select.best)
+    if layout.n_reads != n_reads:
+        raise ValueError("read_starts holds %d reads, the Mapping %d" % (layout.n_reads, n_reads))
+    names = _csr_where(read_names, xp, "read_names")
+    if names[0].n != n_reads + 1:
+        raise ValueError("read_names holds %d names, the Mapping %d reads" % (names[0].n - 1, n_reads))
+    tnames = _csr_where(getattr(targets, "names_csr", None) or targets.names, xp, "the target names") if targets is not None else _csr_where([str(ref_name)], xp, "ref_name")
+    starts, ends = layout.on(xp)
+    bad_layout = "read_starts and read_ends must hold one byte offset per read, 0 <= read_starts[s] <= read_ends[s] <= len(seq)"
+    if len(ends) != len(starts):
+        raise ValueError(bad_layout)
+    segc = xp.minimum(xp.widen(xp.col(t.seg, np.uint32)), max(n_reads - 1, 0))      # (a row that names no read: the glue refuses it below)
+    lo, hi = (xp.narrow(col[segc] if n_reads else segc, np.uint32) for col in (starts, ends))
+    ctext = cigar_text(rec.offsets, rec.ops, device)
+    diffs = {kind: record_diffs(seq, ref_text, rec, t.rev, lo, hi, kind, ref_base, device) if want else None for kind, want in (("md", md), ("cs", cs))}
+    L = sam_line_columns(xp, mapping, targets, ref_start, kept_only, unmapped, md, cs, pairs, [d.ok for d in diffs.values() if d is not None],
+                         [(((ends < starts) | (ends > sb.n) | (starts < 0)).sum(), bad_layout)] if late else [])      # (the device calls before this clamp what
+    #                          they are given: a wrong layout gave them wrong rows, never a stray access)
+    # SEQ and QUAL: the oriented read for the rows that print their bases, the read as given for the unmapped reads
+    all_lo = xp.narrow(xp.concat([xp.widen(lo), starts]), np.uint32)
+    all_hi = xp.narrow(xp.concat([xp.where(L.need, xp.widen(hi), xp.widen(lo)), xp.where(L.show, ends, starts)]), np.uint32)
+    all_rev = xp.narrow(xp.concat([xp.signed(xp.col(t.rev, np.uint8)) & 1, xp.full(n_reads, 0)]), np.uint8)
+    seq_rows = oriented_rows(seq, all_lo, all_hi, all_rev, True, device)
+    qual_rows = oriented_rows(qual, all_lo, all_hi, all_rev, False, device) if qual is not None else None
+    offs, text = sam_lines_text(names, tnames, ctext, seq_rows, qual_rows, *((d.offsets, d.text) if d is not None else None for d in (diffs["md"], diffs["cs"])),
+                                L[:len(LINE_COLUMNS)], device)
+    return SamText(head, offs, text, L.lines, L.skipped, L.unmapped_reads)
+
+
+def write_sam_bytes(fh, mapping, seq, ref_text, read_names, read_starts, read_ends=None, qual=None, ref_name=None, ref_len=None, ref_start=0, ref_base=0, targets=None,
+                    kept_only=True, unmapped=True, header=True, md=True, cs=False, pairs=None, device=0):
+    """write_sam() -- with pairs (a PairSelect) write_sam_pairs() -- into the BINARY file `fh`, the lines assembled on the device
+    (sam_text(), which lists the device calls): the header when `header`, then the body, which comes to the host as one copy of the
+    finished text.  The bytes are those the host writers give, encoded -- but a ref_start beyond the start of a printed
+    row, for which write_sam() prints a negative POS, raises ValueError here.  A MateRescue is not taken: write_sam_rescued() keeps the
+    host path.
+    -> (alignment lines written, rows skipped, unmapped reads)"""
+    st = sam_text(mapping, seq, ref_text, read_names, read_starts, read_ends, qual, ref_name, ref_len, ref_start, ref_base, targets, kept_only, unmapped, md, cs, pairs,
+                  device)
+    if header:
+        fh.write(st.header)
+    fh.write(_host(st.text, np.uint8).tobytes())
+    return st.lines, st.skipped, st.unmapped_reads
