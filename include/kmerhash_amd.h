@@ -1274,6 +1274,63 @@ kh_status kh_sam_lines(const uint64_t* names_off /*[h|d] u64[n_names+1]*/, const
                        uint64_t* out_offsets /*[n_lines+1]*/, uint8_t* out_text /*[cap_text] or NULL*/, uint64_t cap_text, uint64_t* n_text,
                        int device, void* hip_stream);
 
+/* ---- FASTQ records.  The mapper calls take (seq, read_starts, read_ends) and the SAM writers read names and a quality text laid out
+ *      like seq; kh_fastq_records finds where those are in the text of a FASTQ file and kh_pack_rows (below) gathers them, so the input
+ *      side needs no loop over reads on the host (fastq.read_fastq).  The kernels equal tests/fastq_model.py bit for bit.
+ *      Lines.  The line number of a byte is the number of '\n' (10) before it: the rule of kh_kmers_from_fastq.  Line j runs from after
+ *      newline j - 1 (line 0: from byte 0) up to, not including, newline j; a non-empty remainder after the last newline is a last line
+ *      that ends at n.  One '\r' (13) directly before the end of a line is not part of the line.  Multi-line records are not known.
+ *      Records.  Record r is lines 4r .. 4r + 3; *n_records = (number of lines) / 4; *tail_lines = the number of NON-EMPTY lines among
+ *      the up to three left over, 0..3 (one trailing blank line is harmless, lines of a record cut short are not).
+ *      Columns of record r, byte offsets into text:
+ *        [seq_lo, seq_hi)   line 4r + 1
+ *        qual_lo            the start of line 4r + 3 (the quality of base seq_lo + i is the byte qual_lo + i)
+ *        name_lo            the start of line 4r, plus 1 if that byte is '@'
+ *        name_hi            the first byte <= 0x20 (a blank, a tab: the comment begins) at or after name_lo, or the line's end
+ *      With KH_FASTQ_STRIP_MATE in flags: a name longer than 2 bytes that ends in "/1" or "/2" loses those two bytes (name_hi -= 2), so
+ *      the two mates of a pair carry one name; the name "/1" itself stays.
+ *      status[r] is a set of bits: KH_FASTQ_NO_AT (1) line 4r does not begin with '@'; KH_FASTQ_NO_PLUS (2) line 4r + 2 does not begin
+ *      with '+'; KH_FASTQ_LENGTHS (4) line 4r + 3 is not as long as line 4r + 1; KH_FASTQ_NO_NAME (8) the name is empty.  A record with
+ *      a status other than 0 is KEPT, so that every later record -- and a mate in a second file -- keeps its number, as an EMPTY read:
+ *      seq_hi = seq_lo and qual_lo = seq_lo (the name columns are as defined above).  *n_bad counts such records.
+ *      Count, then emit.  With the five columns NULL the call counts: only *n_records, *n_bad and *tail_lines are written (status and cap
+ *      are not looked at).  With the five columns given cap entries each (status: cap entries or NULL) cap must be >= the record count:
+ *      then entries [0, *n_records) of every column are written and no other; else KH_ERR_INVALID with *n_records set and nothing else
+ *      written.  n_bad and tail_lines may be NULL.  The text, the columns and status live in the memory `where` names; the three counts
+ *      are host variables.  Device memory: everything is queued on hip_stream, one host wait per call to learn the counts.  Host memory:
+ *      staged, the call synchronises.  The text may start at any byte: 8-byte loads where it is 8-byte aligned, bytes otherwise.
+ *      KH_ERR_INVALID before anything is allocated, read or written: n >= 2^32, a flag bit other than KH_FASTQ_STRIP_MATE, `where`
+ *      outside the enum, a NULL n_records, a NULL text while n > 0, some but not all of the five columns NULL.  n == 0: KH_OK and three
+ *      zeros, without a device.
+ *      Route (kh_kernels_fastq.h): k_newline_tile_sums and the scan of kh_kmers_from_fastq give every 2048-byte tile its first line;
+ *      k_fastq_line_ends writes the offset of every newline; k_fastq_records, a lane per record, reads five neighbouring line ends.  The
+ *      scratch holds one u32 per possible line: n of them in the count pass, 4 cap + 4 in the emit pass. */
+#define KH_FASTQ_STRIP_MATE 1u
+#define KH_FASTQ_NO_AT 1u
+#define KH_FASTQ_NO_PLUS 2u
+#define KH_FASTQ_LENGTHS 4u
+#define KH_FASTQ_NO_NAME 8u
+kh_status kh_fastq_records(const void* text /*[h|d] u8[n]*/, uint64_t n, uint32_t flags, kh_mem where,
+                           uint32_t* name_lo, uint32_t* name_hi, uint32_t* seq_lo, uint32_t* seq_hi, uint32_t* qual_lo /*[h|d] u32[cap], or all NULL*/,
+                           uint8_t* status /*[h|d] u8[cap] or NULL*/, uint64_t cap,
+                           uint64_t* n_records, uint64_t* n_bad, uint32_t* tail_lines, int device, void* hip_stream);
+
+/* ---- byte rows gathered to given places: out[dst[i] + j] = text[lo[i] + j] for j < len_i = hi[i] - lo[i], and with sep >= 0 also
+ *      out[dst[i] + len_i] = sep (behind EVERY row, an empty one too).  A row that is not inside the text -- hi[i] < lo[i] or
+ *      hi[i] > n -- is an empty row.  Every store is clamped to out_n: a byte that would land at or beyond it is dropped.  Bytes of
+ *      out that no row and no separator covers are not written, so several calls can fill one buffer (two files interleaved: the rows of
+ *      the first at the even places, of the second at the odd ones).  Keeping the destinations disjoint is the caller's: rows that
+ *      overlap leave unspecified bytes of theirs inside out, never a stray access.  This is the copy of kh_oriented_rows without its
+ *      CSR: the caller says where a row goes (fastq.read_fastq: cumulative sums of the lengths).
+ *      All arrays live in the memory `where` names.  Device memory: the one kernel (one wavefront per row, 8-byte words aligned to
+ *      the destination, 64 per step) is queued on hip_stream and the call does not wait.  Host memory: staged -- out is copied in and
+ *      back --, the call synchronises.
+ *      KH_ERR_INVALID before anything is read or written: n or out_n >= 2^32, n_rows > 2^31, sep outside -1..255, `where` outside
+ *      the enum, and with n_rows > 0 a NULL lo, hi or dst, a NULL text while n > 0, a NULL out while out_n > 0. */
+kh_status kh_pack_rows(const void* text /*[h|d] u8[n]*/, uint64_t n, const uint32_t* lo, const uint32_t* hi, const uint64_t* dst /*[h|d] [n_rows]*/, uint64_t n_rows,
+                       int sep /* -1: none, 0..255: written behind every row */, kh_mem where, uint8_t* out /*[h|d] u8[out_n]*/, uint64_t out_n,
+                       int device, void* hip_stream);
+
 /* freed table buffers and workspaces are cached per device for reuse; this returns them to the driver */
 kh_status kh_release_cached_memory(int device);
 

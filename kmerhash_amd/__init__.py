@@ -18,6 +18,7 @@ from .kmers import rescue_mates, rescue_requests, MateRescue, RESCUE_NONE, RESCU
 from .targets import Targets, TARGET_NONE  # noqa: F401
 from .sam import record_diffs, oriented_rows, sam_header, sam_lines, write_sam, write_sam_pairs, write_sam_rescued, RecordDiffs  # noqa: F401
 from .sam import names_csr, sam_line_columns, sam_lines_text, sam_text, write_sam_bytes, SamText, LineColumns  # noqa: F401
+from .fastq import fastq_records, pack_rows, read_fastq, FastqRecords, Reads  # noqa: F401
 from .wide import syncmers128_from_sequence, syncmers128_from_fastq, is_syncmer128  # noqa: F401
 from .dist_index import ShardedKmerPositionIndex, IndexGpuBackend, WideIndexGpuBackend  # noqa: F401
 from . import workloads  # noqa: F401
@@ -34,4 +35,5 @@ __all__ = ["hashmap_robinhood_doubling", "hashmap_linearprobe_doubling", "hash_b
            "record_diffs", "oriented_rows", "sam_header", "sam_lines", "write_sam", "RecordDiffs",
            "pair_chains", "pair_mapping", "PairSelect", "write_sam_pairs",
            "rescue_mates", "rescue_requests", "MateRescue", "RESCUE_NONE", "RESCUE_OVER", "write_sam_rescued",
-           "names_csr", "sam_line_columns", "sam_lines_text", "sam_text", "write_sam_bytes", "SamText", "LineColumns"]
+           "names_csr", "sam_line_columns", "sam_lines_text", "sam_text", "write_sam_bytes", "SamText", "LineColumns",
+           "fastq_records", "pack_rows", "read_fastq", "FastqRecords", "Reads"]

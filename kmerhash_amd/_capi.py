@@ -106,6 +106,8 @@ SYMBOLS = [
     "kh_mate_rescue",
     # SAM lines on the device: the text of the alignment lines from line columns and byte CSRs
     "kh_sam_lines",
+    # FASTQ in: the record structure of a FASTQ text, and byte rows gathered to given places
+    "kh_fastq_records", "kh_pack_rows",
 ]
 
 _lib = None
@@ -295,7 +297,9 @@ def lib():
     L.kh_pair_chains.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, u64, u32, u32, u32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
     L.kh_mate_rescue.argtypes = [vp, u64, vp, u64, u32, vp, vp, vp, vp, vp, u64, u32, i32, vp, vp, vp, vp, vp, vp, u64, pu64, i32, vp]
     L.kh_sam_lines.argtypes = [vp, vp, u64, u64] * 7 + [vp] * 19 + [u64, i32, vp, vp, u64, pu64, i32, vp]
-    L.kh_anchor_targets.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, u64, u32, i32] + [vp] * 8 + [pu64, i32, vp]
+    L.kh_fastq_records.argtypes = [vp, u64, u32, i32, vp, vp, vp, vp, vp, vp, u64, pu64, pu64, C.POINTER(C.c_uint32), i32, vp]
+    L.kh_pack_rows.argtypes = [vp, u64, vp, vp, vp, u64, i32, i32, vp, u64, i32, vp]
+    L.kh_anchor_targets.argtypes =[vp, vp, vp, u64, vp, u64, vp, vp, u64, u32, i32] + [vp] * 8 + [pu64, i32, vp]
     for s in SYMBOLS:
         if s not in ("kh_version", "kh_last_error", "kh_wide_last_error", "kh_index_last_error", "kh_wide_index_last_error"):
             getattr(L, s).restype = i32

@@ -6,7 +6,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "kmerhash_amd.hip")
 DEPS = [SRC, os.path.join(HERE, "csrc", "kh_kernels.h"), os.path.join(HERE, "csrc", "kh_kernels_wide.h"), os.path.join(HERE, "csrc", "kh_kernels_values.h"), os.path.join(HERE, "csrc", "kh_kernels_index.h"),
-        os.path.join(HERE, "csrc", "kh_kernels_index_wide.h"), os.path.join(HERE, "csrc", "kh_kernels_csr.h"), os.path.join(HERE, "csrc", "kh_kernels_chain.h"), os.path.join(HERE, "csrc", "kh_kernels_edits.h"), os.path.join(HERE, "csrc", "kh_kernels_cigar.h"), os.path.join(HERE, "csrc", "kh_kernels_ends.h"), os.path.join(HERE, "csrc", "kh_kernels_select.h"), os.path.join(HERE, "csrc", "kh_kernels_records.h"), os.path.join(HERE, "csrc", "kh_kernels_targets.h"), os.path.join(HERE, "csrc", "kh_kernels_sam.h"), os.path.join(HERE, "csrc", "kh_kernels_pair.h"), os.path.join(HERE, "csrc", "kh_kernels_rescue.h"), os.path.join(HERE, "csrc", "kh_kernels_samtext.h"), os.path.join(HERE, "csrc", "kh_scratch.h"), os.path.join(HERE, "csrc", "kh_part_sizing.h"),
+        os.path.join(HERE, "csrc", "kh_kernels_index_wide.h"), os.path.join(HERE, "csrc", "kh_kernels_csr.h"), os.path.join(HERE, "csrc", "kh_kernels_chain.h"), os.path.join(HERE, "csrc", "kh_kernels_edits.h"), os.path.join(HERE, "csrc", "kh_kernels_cigar.h"), os.path.join(HERE, "csrc", "kh_kernels_ends.h"), os.path.join(HERE, "csrc", "kh_kernels_select.h"), os.path.join(HERE, "csrc", "kh_kernels_records.h"), os.path.join(HERE, "csrc", "kh_kernels_targets.h"), os.path.join(HERE, "csrc", "kh_kernels_sam.h"), os.path.join(HERE, "csrc", "kh_kernels_pair.h"), os.path.join(HERE, "csrc", "kh_kernels_rescue.h"), os.path.join(HERE, "csrc", "kh_kernels_samtext.h"), os.path.join(HERE, "csrc", "kh_kernels_fastq.h"), os.path.join(HERE, "csrc", "kh_scratch.h"), os.path.join(HERE, "csrc", "kh_part_sizing.h"),
         os.path.join(HERE, "..", "include", "kmerhash_amd", "kh_hash.h"),
         os.path.join(HERE, "..", "include", "kmerhash_amd.h")]
 # KH_LIB_SUFFIX: experiment builds next to the product (libkmerhash_amd<suffix>.so, built with KH_EXTRA_FLAGS) for A/B runs on one box

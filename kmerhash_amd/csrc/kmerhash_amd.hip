@@ -23,6 +23,7 @@
 //   targets : kh_anchor_targets, the anchors of every read regrouped by the target (contig) they fall in: a lane per anchor, then a wavefront per read (kh_kernels_targets.h).
 //   sam     : kh_record_diffs, the cs or MD string of every record row: a wavefront per row along the two texts; kh_oriented_rows, byte ranges copied as they stand or back to front and complemented (kh_kernels_sam.h).
 //   samtext : kh_sam_lines, the text of SAM alignment lines from line columns and byte CSRs: a wavefront per line and a lane per field in both passes, the lengths by a wave sum, the places by a wave prefix sum (kh_kernels_samtext.h).
+//   fastq   : kh_fastq_records, the record structure of a FASTQ text: the line counting of kh_kmers_from_fastq, the offset of every newline, then a lane per record; kh_pack_rows, byte rows gathered to given places: a wavefront per row (kh_kernels_fastq.h).
 //   ends    : kh_chain_ends, both ends of every kept chain extended to the ends of its read or to a soft clip: a wavefront per end, target free, stop by score (kh_kernels_ends.h).
 #include "kh_kernels.h"
 #include "kh_kernels_wide.h"
@@ -41,6 +42,7 @@
 #include "kh_kernels_pair.h"
 #include "kh_kernels_rescue.h"
 #include "kh_kernels_samtext.h"
+#include "kh_kernels_fastq.h"
 #include "kh_part_sizing.h"
 #include "kh_scratch.h"
 #include "../../include/kmerhash_amd.h"
@@ -309,6 +311,12 @@ class Scratch {
     T* d = car_.take<T>(count);
     if (d && nout_ == kMaxOut) check(hipErrorInvalidValue);
     else if (d) outs_[nout_++] = Out{p, d};
+    return d;
+  }
+  // an array the call reads AND writes (kh_pack_rows fills some bytes of it): a host array is copied in as well
+  template <typename T> T* inout(T* p, uint64_t count, kh_mem where) {
+    T* d = out(p, count, where);
+    if (d && where == KH_MEM_HOST) copy(d, p, count * sizeof(T), hipMemcpyHostToDevice);
     return d;
   }
   // the first `count` elements of what out() returned as `d`, back to the host array it stands for (device memory: nothing to do)
@@ -4811,5 +4819,80 @@ kh_status kh_sam_lines(const uint64_t* names_off, const uint8_t* names_text, uin
   return emit_total(s, total, out_text, cap_text, n_text, where, [&](uint8_t* dtext) {
     hipLaunchKernelGGL(k_samtext_emit, dim3(grid_for(n_lines, KST_WAVES, ncu * 8)), dim3(KST_THREADS), 0, stream, P, (const uint64_t*)doff, (uint64_t)total, dtext);
   });
+}
+// ---- the record structure of a FASTQ text (kernels: kh_kernels_fastq.h).  One call is one pass: tile sums, scan, line ends, records,
+//      then the one host wait that learns the three counts.  The record kernel derives the record count itself, where the host does not
+//      know it yet: a call with too little room writes no column.  One pooled block holds the counts, the tile sums, the line ends (and
+//      the staged arrays of a host call).
+static_assert(KFQ_STRIP_MATE == KH_FASTQ_STRIP_MATE && KFQ_NO_AT == KH_FASTQ_NO_AT && KFQ_NO_PLUS == KH_FASTQ_NO_PLUS && KFQ_LENGTHS == KH_FASTQ_LENGTHS &&
+              KFQ_NO_NAME == KH_FASTQ_NO_NAME, "one flag, one set of status bits");
+kh_status kh_fastq_records(const void* text, uint64_t n, uint32_t flags, kh_mem where, uint32_t* name_lo, uint32_t* name_hi, uint32_t* seq_lo, uint32_t* seq_hi,
+                           uint32_t* qual_lo, uint8_t* status, uint64_t cap, uint64_t* n_records, uint64_t* n_bad, uint32_t* tail_lines, int device, void* stream_) {
+  const int given = (name_lo != nullptr) + (name_hi != nullptr) + (seq_lo != nullptr) + (seq_hi != nullptr) + (qual_lo != nullptr);
+  if (n >= (uint64_t(1) << 32) || (flags & ~KH_FASTQ_STRIP_MATE) || (where != KH_MEM_HOST && where != KH_MEM_DEVICE) || !n_records || (n && !text) ||
+      (given != 0 && given != 5)) return KH_ERR_INVALID;
+  const bool emit = given == 5;
+  if (n == 0) {
+    *n_records = 0;
+    if (n_bad) *n_bad = 0;
+    if (tail_lines) *tail_lines = 0;
+    return KH_OK;
+  }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK0(hipSetDevice(device));
+  const uint64_t ntl = cmp_tiles(n);
+  const uint64_t room = emit ? std::min<uint64_t>(cap, uint64_t(1) << 30) : 0;      // (n < 2^32 bytes: at most 2^30 records)
+  const uint64_t cap_lines = emit ? std::min<uint64_t>(n, 4 * room + 4) : n;        // a newline per line; the count pass knows no bound but n
+  Scratch s(device, stream);
+  KfqArgs P{};
+  uint32_t* sums = nullptr; uint64_t* offs = nullptr; uint32_t* line_end = nullptr;
+  if (!s.layout([&](Scratch& c) {
+        P.counts = c.take<uint32_t>(4); sums = c.take<uint32_t>(ntl); offs = c.take<uint64_t>(ntl + 1); line_end = c.take<uint32_t>(cap_lines);
+        P.text = c.in(static_cast<const uint8_t*>(text), n, where);
+        if (emit) {
+          P.name_lo = c.out(name_lo, room, where); P.name_hi = c.out(name_hi, room, where); P.seq_lo = c.out(seq_lo, room, where); P.seq_hi = c.out(seq_hi, room, where);
+          P.qual_lo = c.out(qual_lo, room, where); P.status = c.out(status, status ? room : 0, where);
+        }
+      })) return s.finish();
+  P.line_end = line_end; P.n_newlines = offs + ntl; P.n = n; P.cap_lines = cap_lines; P.cap = room; P.flags = flags;
+  s.zero(P.counts, 4 * sizeof(uint32_t));
+  hipLaunchKernelGGL(k_newline_tile_sums, dim3((uint32_t)ntl), dim3(256), 0, stream, P.text, n, sums);
+  hipLaunchKernelGGL(k_scan_u32_to_u64, dim3(1), dim3(KH_SCAN_THREADS), 0, stream, (const uint32_t*)sums, ntl, offs);
+  hipLaunchKernelGGL(k_fastq_line_ends, dim3((uint32_t)ntl), dim3(256), 0, stream, P.text, n, (const uint64_t*)offs, line_end, cap_lines);
+  hipLaunchKernelGGL(k_fastq_records, dim3(grid_for(cap_lines / 4 + 1, KFQ_THREADS, (uint32_t)cu_count(device) * 8)), dim3(KFQ_THREADS), 0, stream, P);
+  s.launched();
+  uint32_t counts[4] = {0, 0, 0, 0};
+  s.read(counts, (const uint32_t*)P.counts, 4);
+  if (!s.sync()) return s.finish();
+  *n_records = counts[0];
+  if (emit && counts[0] > cap) { s.finish(); return KH_ERR_INVALID; }
+  if (n_bad) *n_bad = counts[1];
+  if (tail_lines) *tail_lines = counts[2];
+  if (emit) {
+    s.copy_back(P.name_lo, counts[0]); s.copy_back(P.name_hi, counts[0]); s.copy_back(P.seq_lo, counts[0]); s.copy_back(P.seq_hi, counts[0]);
+    s.copy_back(P.qual_lo, counts[0]); s.copy_back(P.status, status ? counts[0] : 0);
+  }
+  return s.finish();
+}
+// ---- byte rows gathered to given places (kernel: kh_kernels_fastq.h).  No count to learn: a device call queues one kernel and never waits.
+kh_status kh_pack_rows(const void* text, uint64_t n, const uint32_t* lo, const uint32_t* hi, const uint64_t* dst, uint64_t n_rows, int sep, kh_mem where, uint8_t* out,
+                       uint64_t out_n, int device, void* stream_) {
+  const uint64_t tlim = uint64_t(1) << 32;
+  if (n >= tlim || out_n >= tlim || n_rows > (uint64_t(1) << 31) || sep < -1 || sep > 255 || (where != KH_MEM_HOST && where != KH_MEM_DEVICE)) return KH_ERR_INVALID;
+  if (n_rows && (!lo || !hi || !dst || (n && !text) || (out_n && !out))) return KH_ERR_INVALID;
+  if (n_rows == 0 || out_n == 0) return KH_OK;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPCHK0(hipSetDevice(device));
+  Scratch s(device, stream);
+  const uint8_t* din = nullptr; const uint32_t *dlo = nullptr, *dhi = nullptr; const uint64_t* ddst = nullptr; uint8_t* dout = nullptr;
+  if (!s.layout([&](Scratch& c) {
+        din = c.in(static_cast<const uint8_t*>(text), n, where); dlo = c.in(lo, n_rows, where); dhi = c.in(hi, n_rows, where); ddst = c.in(dst, n_rows, where);
+        dout = c.inout(out, out_n, where);
+      })) return s.finish();
+  hipLaunchKernelGGL(k_pack_rows, dim3(grid_for(n_rows, KFQ_WAVES, (uint32_t)cu_count(device) * 8)), dim3(KFQ_THREADS), 0, stream, din, n, dlo, dhi, ddst, (uint32_t)n_rows, sep,
+                     dout, out_n);
+  s.launched();
+  s.copy_back(dout, out_n);
+  return s.finish_queued();
 }
 }  // extern "C"

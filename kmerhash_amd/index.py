@@ -333,6 +333,20 @@ class KmerPositionIndex(_Handle):
         return mapper.map_pairs_rescued(self, seq, ref_text, read_starts, read_ends, ref_base, max_edits, clip_cost, mask_pct, pri_pct, best_n, min_ins, max_ins,
                                         unpaired_pen, targets, **params)
 
+    def map_fastq(self, text, ref_text, strict=True, strip_mate=None, **kw):
+        """FASTQ in: kmerhash_amd.read_fastq(text, strict=strict, strip_mate=strip_mate) where the text lives, then
+        map(reads.seq, ref_text, reads.read_starts, reads.read_ends, **kw) -> (Mapping, Reads).  write_sam_bytes(fh, mapping, reads.seq,
+        ref_text, reads.names, reads.read_starts, reads.read_ends, qual=reads.qual, ...) writes the file."""
+        self._need_stranded("map")
+        return mapper.map_fastq(self, text, ref_text, strict, strip_mate, **kw)
+
+    def map_fastq_pairs(self, text, ref_text, text2=None, rescue=False, strict=True, strip_mate=None, **kw):
+        """paired FASTQ in: read_fastq(text, text2, ...) -- text2=None: one interleaved file, mate 1, mate 2, ...; else the two files of a
+        run, interleaved here, a closing /1 or /2 dropped from the names -- then map_pairs (rescue: map_pairs_rescued) with **kw
+        -> (Mapping, PairSelect, Reads) or (Mapping, PairSelect, MateRescue, Reads).  An odd number of reads is the ValueError of map_pairs."""
+        self._need_stranded("map_pairs")
+        return mapper.map_fastq_pairs(self, text, ref_text, text2, rescue, strict, strip_mate, **kw)
+
     def chain_select(self, seq, read_starts=None, mask_pct=50, pri_pct=80, best_n=5, **params):
         """chains(seq, read_starts, **params), then which chain of every read is the answer: kmers.select_table over the table with one
         group per read -> (ChainTable, ChainSelect(parent, rank, mapq, flag, sub, nsub, best)): per row of the table its primary, its

@@ -6,7 +6,8 @@ rescue -> PAF (kmerhash_amd.sam writes SAM).  Three layers, top to bottom of thi
   the glue steps      what turns one stage's columns into the next stage's arguments -- the read layout, the segments of reads, the
                       ChainTable rows, the per-chain read intervals, the seg -> offsets CSR, the printable-row rule, the pair candidates,
                       the rescue windows -- each written once over an array namespace (kmerhash_amd._xp: numpy, or torch on a device);
-  the pipeline        chains ... map_pairs_rescued as plain functions of an index; the methods of KmerPositionIndex delegate here.
+  the pipeline        chains ... map_pairs_rescued as plain functions of an index, and map_fastq / map_fastq_pairs, which read a FASTQ
+                      text (kmerhash_amd.fastq.read_fastq) and call them; the methods of KmerPositionIndex delegate here.
 
 kmerhash_amd.kmers re-exports the public names under the module they were first published in."""
 import collections
@@ -17,6 +18,7 @@ import numpy as np
 from . import _capi as K
 from ._call import _Buf, _is_tensor, alloc, check, check_same, stream_of, torch, two_pass
 from ._xp import NUMPY, namespace_of
+from .fastq import read_fastq
 from .targets import Targets, inside_target
 
 
@@ -905,3 +907,13 @@ def map_pairs_rescued(ix, seq, ref_text, read_starts, read_ends=None, ref_base=0
     rq = rescue_windows(namespace_of(pairs.row), mp, pairs, layout, int(min_ins), int(max_ins), int(max_edits), targets, rb.n, ref_base)
     res = rescue_mates(sb.obj, rb.obj, rq.q_lo, rq.q_hi, rq.w_lo, rq.w_hi, rq.rev, ref_base, max_edits, ix.device)
     return mp, pairs, res._replace(read=rq.read)
+
+
+def map_fastq(ix, text, ref_text, strict=True, strip_mate=None, **kw):
+    reads = read_fastq(text, None, strict, strip_mate, ix.device)
+    return map_reads(ix, reads.seq, ref_text, reads.read_starts, reads.read_ends, **kw), reads
+
+
+def map_fastq_pairs(ix, text, ref_text, text2=None, rescue=False, strict=True, strip_mate=None, **kw):
+    reads = read_fastq(text, text2, strict, strip_mate, ix.device)
+    return (map_pairs_rescued if rescue else map_pairs)(ix, reads.seq, ref_text, reads.read_starts, reads.read_ends, **kw) + (reads,)
