@@ -276,6 +276,11 @@ kh_status kh_shard_plan_permute(kh_shard_plan* plan, uint32_t piece, const uint6
 kh_status kh_shard_plan_permute_global(kh_shard_plan* plan, uint32_t piece, const uint64_t* keys_dev, const uint32_t* vals_dev /* may be NULL */,
                                        uint64_t* out_keys_dev, uint32_t* out_vals_dev, void* hip_stream);
 kh_status kh_shard_plan_offsets(const kh_shard_plan* plan, uint64_t* offsets_host /* [nranks][pieces+1] */);
+/* Stream-ordered: destroy may be called as soon as the last kh_shard_plan_permute / _permute_global call has RETURNED, with the
+ * permutations still queued; the plan's device block returns to the library's pool only after every permutation queued from the plan has run
+ * (a host function queued behind them on their streams; a stream that refuses it is waited for).  A plan that was never permuted, or
+ * with n == 0, is freed at once.  The handle itself is invalid from the call on.  Permutations captured into a graph read the block
+ * at every replay: there the block is freed at once and nothing is queued, so destroy such a plan after the last replay.  NULL: no-op. */
 void kh_shard_plan_destroy(kh_shard_plan* plan);
 
 /* ---- k-mer generation front end (BenchmarkKmerCounter.cpp:1655-1706 reads sequences through kmerind's

@@ -18,8 +18,8 @@
  * tests to run p > 1 on a one-GPU box, where RCCL refuses two ranks on one device.
  *
  * All batch arguments are DEVICE pointers on the map's device.  Every entry point below except khd_unique_id, khd_local,
- * khd_last_error, khd_phase_ms, khd_set_stream, khd_set_option, khd_synchronize and khd_debug_fail_next is COLLECTIVE: all ranks
- * call it, in the same order.
+ * khd_last_error, khd_phase_ms, khd_set_stream, khd_set_option, khd_synchronize, khd_debug_fail_next and khd_debug_before_permute is
+ * COLLECTIVE: all ranks call it, in the same order.
  *
  * Failures.  The reference runs under MPI, where an exception on one rank ends the job (MPI_Abort).  Here a rank that fails LOCALLY
  * inside a collective call (allocation, a kh_* call on its table) never leaves its peers waiting: it keeps taking part in the
@@ -101,6 +101,11 @@ kh_status khd_size(khd_map* m, uint64_t* global_size);
  * before any payload, 3: in the local work between the payload exchanges, 4: in the build at the end of an insert / the local erase) as if an
  * allocation had failed there.  Used by tests/cpp/test_dist.cpp to check that no rank hangs and every rank reports. */
 kh_status khd_debug_fail_next(khd_map* m, int stage);
+/* test hook: the next khd_find / khd_count of this rank that runs the collectives calls fn(arg) once, on the calling thread, after its
+ * last host wait (the plan, the count exchange, the vote) and before it queues the first permutation.  From there on the call only queues
+ * work, so a test that holds the map's stream inside fn gets the call back with all of it pending (tests/cpp/test_dist.cpp: the scratch of
+ * a pending find must not be handed to anyone else).  fn == NULL clears the hook. */
+kh_status khd_debug_before_permute(khd_map* m, void (*fn)(void*), void* arg);
 
 /* per-phase device time of this rank since the last call (HIP events; ms): permute, exchange, feed, build, query.
  * Writes up to `cap` bytes of "name ms\n" lines. */

@@ -55,6 +55,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include <atomic>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -2503,7 +2504,17 @@ struct kh_shard_plan {
   int device, hash; KhSeed seed; uint32_t p, pmask, pieces, ntiles; uint64_t n;
   void* blk; const uint64_t* toff;      // the pooled block of the scan, and the scanned [rank][tile] offsets inside it
   std::vector<uint64_t> bnd;      // [p][pieces+1] scanned offsets at the piece boundaries
+  std::vector<hipStream_t> used;  // the streams a scatter that reads `toff` was queued on (kh_shard_plan_destroy frees behind them)
 };
+// On a runtime thread, in stream order: the rule at Scratch::release (no HIP call, no wait for anyone who makes one; the block is pooled)
+// One reference per stream that still has scatters queued, one for kh_shard_plan_destroy itself: who drops the last frees the block.
+struct PlanRelease { int device; void* blk; std::atomic<int> refs; };
+static void plan_release(void* arg) {
+  PlanRelease* r = static_cast<PlanRelease*>(arg);
+  if (r->refs.fetch_sub(1) != 1) return;
+  pool_free(r->device, r->blk);
+  delete r;
+}
 kh_status kh_shard_plan_create(kh_shard_plan** out, kh_hash hash, uint64_t seed_, kh_key_transform xf, uint32_t k, uint32_t p, const uint64_t* keys,
                                uint64_t n, uint32_t pieces, uint64_t* counts_host, uint64_t* bounds_host, int device, void* stream_) {
   if (!out) return KH_ERR_INVALID;
@@ -2557,6 +2568,7 @@ static kh_status shard_plan_permute(kh_shard_plan* P, uint32_t piece, const uint
   }
   KH_SWITCH_HASH(P->hash, hipLaunchKernelGGL((k_shard_scatter8<HASH, 1>), dim3(t1 - t0), dim3(KH_SHARD_THREADS), 0, stream, keys + b0, vals ? vals + b0 : nullptr, b1 - b0,
                                              P->seed, P->p, P->pmask, P->toff, P->ntiles, out_keys, out_vals, t0, adj));
+  if (std::find(P->used.begin(), P->used.end(), stream) == P->used.end()) P->used.push_back(stream);      // (before the check: a launch may be queued)
   HIPCHK0(hipGetLastError());
   return KH_OK;
 }
@@ -2574,8 +2586,24 @@ kh_status kh_shard_plan_offsets(const kh_shard_plan* P, uint64_t* out) {
   if (P->n == 0) for (size_t i = 0; i < P->bnd.size(); ++i) out[i] = 0;
   return KH_OK;
 }
+// May be called as soon as the last permute has RETURNED: the queued scatters still read the block, so it goes back to the pool behind
+// them -- a host function on every stream used (Scratch::finish_queued's way); the one that runs last frees.  A stream that refuses is
+// waited for on the host.  A capturing stream can neither be waited for nor given a host node (the node would hand the block back on
+// every replay): it holds nothing back, the captured scatters read the block only when replayed; the other streams still do.
 void kh_shard_plan_destroy(kh_shard_plan* P) {
   if (!P) return;
+  if (P->blk && !P->used.empty() && hipSetDevice(P->device) == hipSuccess) {
+    PlanRelease* r = new PlanRelease{P->device, P->blk, {1}};      // (the one reference is this call's)
+    P->blk = nullptr;
+    for (hipStream_t s : P->used) {
+      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
+      else if (cap != hipStreamCaptureStatusNone) continue;
+      r->refs.fetch_add(1);
+      if (hipLaunchHostFunc(s, &plan_release, r) != hipSuccess) { (void)hipGetLastError(); hipStreamSynchronize(s); plan_release(r); }
+    }
+    plan_release(r);
+  }
   pool_free(P->device, P->blk);
   delete P;
 }

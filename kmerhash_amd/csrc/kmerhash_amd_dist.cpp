@@ -257,6 +257,7 @@ struct khd_map {
   bool late_pending;            // a find / count is in flight whose peers' status words have not been looked at
   bool force, dead;
   int query_pieces, fail_stage;
+  void (*before_permute)(void*) = nullptr; void* before_permute_arg = nullptr;      // khd_debug_before_permute
   hipEvent_t ev_perm, ev_landed[2], ev_fed[2], ev_sent[2];
   hipEvent_t ev_p[kMaxQP], ev_k[kMaxQP], ev_q[kMaxQP], ev_done;
   std::vector<Phase> phases;
@@ -428,6 +429,11 @@ kh_status khd_set_option(khd_map* m, int option, long long value) {
   }
 }
 kh_status khd_debug_fail_next(khd_map* m, int stage) { if (!m) return KH_ERR_INVALID; m->fail_stage = stage; return KH_OK; }
+kh_status khd_debug_before_permute(khd_map* m, void (*fn)(void*), void* arg) {
+  if (!m) return KH_ERR_INVALID;
+  m->before_permute = fn; m->before_permute_arg = arg;
+  return KH_OK;
+}
 const char* khd_last_error(const khd_map* m) { return m ? m->err.c_str() : "null map"; }
 kh_table* khd_local(khd_map* m) { return m ? m->local : nullptr; }
 int khd_rank(const khd_map* m) { return m ? m->tp->rank() : -1; }
@@ -660,6 +666,7 @@ static kh_status query(khd_map* m, const uint64_t* keys, uint64_t n, uint64_t* o
   uint32_t* const lv = static_cast<uint32_t*>(m->res[0].p); uint8_t* const lf = static_cast<uint8_t*>(m->res[1].p);
   if (op == 1 && hipMemsetAsync(lv, 0, std::max<uint64_t>(rtot, 1) * 4, m->stream) != hipSuccess) note(KH_ERR_HIP, "hipMemsetAsync");
   if (inject(m, 3)) note(KH_ERR_NOMEM, "injected failure (stage 3)");
+  if (m->before_permute && op != 2) { void (*fn)(void*) = m->before_permute; m->before_permute = nullptr; fn(m->before_permute_arg); }
   for (int i = 0; i < rounds; ++i) {       // permutation of every piece first: the exchanges can start as early as possible
     if (!permuted && i < my_pieces && note.ok()) {
       Span sp(m, "permute", m->stream);

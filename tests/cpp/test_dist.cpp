@@ -6,11 +6,13 @@
 //           ncclAllReduce votes) runs as a self-exchange and must give the unsharded table's results
 //   part 3: a rank that fails locally (khd_debug_fail_next) at each stage of insert / find / erase: no rank hangs, every rank
 //           reports, the maps stay usable;  part 4: pipelined queries (KHD_OPT_QUERY_PIECES) equal the one-piece form
+//   part 5: a find / count that is still queued keeps the block of its shard plan while other plans are made (the stream is held)
 //   part 2: p = 4 and p = 3 ranks as threads of this process on one device (khd_create_local): the sharding / exchange /
 //           pipelined streamed insert code of the product over the in-process transport (RCCL refuses two ranks on one GPU)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -318,6 +320,89 @@ static void pipelined_queries(int P, size_t nq, bool timing) {
   for (int r = 0; r < P; ++r) OK(khd_destroy(maps[r]));
 }
 
+// ---- part 5: the plan of a pending find / count is nobody else's ----------------------------------------------------------------
+// khd_find and khd_count destroy their shard plan with its permutations still queued.  The map's stream is held by a host function from
+// the moment the call has made its last host wait (khd_debug_before_permute), so the call returns with every permutation pending; plans
+// made meanwhile on a second stream must not get the pending call's block.  The first of them is the one that would: it has p = 3, so
+// its counts and offsets are other numbers at the same places of the block (every array of a plan starts at a multiple of 256 bytes).
+// The second has the query's own n, p = 1 and pieces: its offsets equal the query's, it is there for the shape the query itself uses.  The hold ends on a flag, and after kHoldLimit regardless (then the check of the flag fails).
+struct Hold { hipStream_t stream; std::atomic<int> go, expired; };
+static const double kHoldLimit = 5.0;
+static void hold_wait(void* arg) {
+  Hold* h = static_cast<Hold*>(arg);
+  const auto t0 = std::chrono::steady_clock::now();
+  while (!h->go.load()) {
+    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > kHoldLimit) { h->expired.store(1); return; }
+    std::this_thread::sleep_for(std::chrono::microseconds(50));
+  }
+}
+static void hold_stream(void* arg) { Hold* h = static_cast<Hold*>(arg); CHECK(hipLaunchHostFunc(h->stream, hold_wait, h) == hipSuccess); }
+// a plan over `dk` on `s`, every piece permuted to its place in the whole batch; -> the permuted keys once `s` has run them
+static std::vector<uint64_t> plan_permuted(kh_shard_plan** plan, uint32_t p, uint32_t pieces, const uint64_t* dk, size_t n, uint64_t* out, hipStream_t s) {
+  std::vector<uint64_t> counts((size_t)p * pieces), bounds(pieces + 1);
+  OK(kh_shard_plan_create(plan, KH_HASH_MURMUR3_X86_128_LO64, KHD_DIST_SEED, KH_XF_IDENTITY, 0, p, dk, n, pieces, counts.data(), bounds.data(), 0, s));
+  for (uint32_t i = 0; i < pieces; ++i) OK(kh_shard_plan_permute_global(*plan, i, dk, nullptr, out, nullptr, s));
+  CHECK(hipStreamSynchronize(s) == hipSuccess);
+  return host(out, n);
+}
+static void pending_query_keeps_its_plan() {
+  char id[KHD_UNIQUE_ID_BYTES];
+  OK(khd_unique_id(id));
+  khd_map* m = nullptr;
+  OK(khd_create(&m, id, 1, 0, 0, KH_KIND_ROBINHOOD, KH_HASH_MURMUR3_X86_128_LO64, 43, 128, 0.35f, 0.8f, KH_HASH_MURMUR3_X86_128_LO64, KHD_DIST_SEED));
+  OK(khd_set_option(m, KHD_OPT_FORCE_COLLECTIVES, 1));
+  OK(khd_set_option(m, KHD_OPT_QUERY_PIECES, 2));
+  hipStream_t st, s2;
+  CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) == hipSuccess);
+  OK(khd_set_stream(m, st));
+  const size_t n = 2 * 4096 + 777;       // three tiles of the shard kernels, the last one ragged; two query pieces
+  std::vector<uint64_t> k(20000), q(n), other(n); std::vector<uint32_t> v(k.size());
+  uint64_t s = 77; std::map<uint64_t, uint32_t> gold;
+  for (size_t i = 0; i < k.size(); ++i) { k[i] = splitmix(s); v[i] = uint32_t(3 * i + 1); gold[k[i]] = v[i]; }
+  for (size_t i = 0; i < n; ++i) { q[i] = i % 3 ? k[splitmix(s) % k.size()] : (splitmix(s) | 1ull << 63); other[i] = splitmix(s); }
+  uint64_t* dk = dev(k); uint32_t* dv = dev(v); uint64_t* dq = dev(q); uint64_t* dother = dev(other); uint64_t ni = 0;
+  OK(khd_insert(m, dk, dv, k.size(), 2, 0, &ni)); CHECK(ni == gold.size());
+  uint64_t* ok = dev(std::vector<uint64_t>(n)); uint32_t* ov = dev(std::vector<uint32_t>(n, 7u)); uint8_t* of = dev(std::vector<uint8_t>(n, 9));
+  uint64_t* o1 = dev(std::vector<uint64_t>(n)); uint64_t* o3 = dev(std::vector<uint64_t>(n));
+  std::vector<uint64_t> hv(n);
+  OK(kh_hash_batch(KH_HASH_MURMUR3_X86_128_LO64, KHD_DIST_SEED, other.data(), n, KH_MEM_HOST, hv.data(), 0, nullptr));
+  std::vector<uint64_t> other3;          // `other` grouped by rank of 3, input order kept
+  for (uint64_t r = 0; r < 3; ++r) for (size_t i = 0; i < n; ++i) if (hv[i] % 3 == r) other3.push_back(other[i]);
+  for (int op = 0; op < 2; ++op) {       // find, then count
+    OK(khd_synchronize(m));
+    CHECK(hipDeviceSynchronize() == hipSuccess);
+    OK(kh_release_cached_memory(0));     // the pool is empty: a block freed too early is the next one handed out
+    Hold h; h.stream = st; h.go.store(0); h.expired.store(0);
+    OK(khd_debug_before_permute(m, hold_stream, &h));
+    if (op == 0) OK(khd_find(m, dq, n, ok, ov, of)); else OK(khd_count(m, dq, n, ok, of));
+    CHECK(hipStreamQuery(st) == hipErrorNotReady);      // back with its work queued behind the hold
+    (void)hipGetLastError();
+    kh_shard_plan *p1 = nullptr, *p3 = nullptr;
+    // p = 3 FIRST: the pool is empty, so a block the query freed too early is the one this create takes, and its scan puts the
+    // rank-0 tile offsets of three ranks (about 0, 1365, 2730) where the query's scatters are going to read 0, 4096, 8192
+    const std::vector<uint64_t> got3 = plan_permuted(&p3, 3, 2, dother, n, o3, s2), got1 = plan_permuted(&p1, 1, 2, dother, n, o1, s2);
+    CHECK(!h.go.load() && !h.expired.load() && hipStreamQuery(st) == hipErrorNotReady);      // the query was pending all the while
+    (void)hipGetLastError();
+    h.go.store(1);
+    kh_shard_plan_destroy(p1); kh_shard_plan_destroy(p3);
+    OK(khd_synchronize(m));
+    CHECK(!h.expired.load());
+    CHECK(got1 == other && got3 == other3);
+    CHECK(host(ok, n) == q);             // one rank: the permuted order is the input order
+    const auto f = host(of, n); const auto val = host(ov, n);
+    for (size_t i = 0; i < n; ++i) {
+      auto it = gold.find(q[i]);
+      CHECK(f[i] == (it != gold.end()));
+      if (op == 0) CHECK(val[i] == (it != gold.end() ? it->second : 0u));
+    }
+    CHECK(hipMemset(ok, 0, n * 8) == hipSuccess && hipMemset(of, 9, n) == hipSuccess);
+  }
+  OK(khd_destroy(m));
+  hipFree(dk); hipFree(dv); hipFree(dq); hipFree(dother); hipFree(ok); hipFree(ov); hipFree(of); hipFree(o1); hipFree(o3);
+  CHECK(hipStreamDestroy(st) == hipSuccess && hipStreamDestroy(s2) == hipSuccess);
+  std::printf("pending find / count: the plan's block stayed theirs while two other plans were made (stream held, flag unset)\n");
+}
+
 int main(int argc, char** argv) {
   setvbuf(stdout, nullptr, _IOLBF, 0);      // (progress survives a crash when stdout is a pipe)
   if (argc > 1 && !std::strcmp(argv[1], "--query-timing")) {
@@ -418,6 +503,7 @@ int main(int argc, char** argv) {
     hipFree(dk); hipFree(dv); hipFree(dq); hipFree(ok); hipFree(ov); hipFree(of); hipFree(oc); hipFree(pv); hipFree(pf);
     std::printf("rccl single rank, forced collectives ok (ncclAllToAll counts, grouped ncclAllToAllv x4 pieces + retry, ncclAllReduce votes, pipelined find/count, erase)\n");
   }
+  pending_query_keeps_its_plan();
   failure_votes(3);
   absent_peer();
   pipelined_queries(3, 300000, false);

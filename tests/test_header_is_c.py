@@ -34,3 +34,29 @@ def test_every_environment_switch_is_documented():
     doc = open(os.path.join(root, "INTEGRATION.md")).read()
     missing = sorted(n for n in names if n not in doc)
     assert len(names) >= 15 and not missing, missing
+
+
+def test_shard_plan_destroy_contract_and_signature(tmp_path):
+    """kh_shard_plan_destroy keeps its signature (void, one plan pointer: a C function pointer of that type takes it, -Werror) and the
+    header states when it may be called: once the last permute has returned, the block going back to the pool behind the queued work"""
+    import re
+    hdr = open(os.path.join(ROOT, "include", "kmerhash_amd.h")).read()
+    assert len(re.findall(r"^void\s+kh_shard_plan_destroy\s*\(\s*kh_shard_plan\s*\*\s*plan\s*\)\s*;", hdr, flags=re.M)) == 1
+    # the comment that ends right above the declaration is the contract
+    doc = re.search(r"/\*((?:(?!\*/).)*)\*/\s*void\s+kh_shard_plan_destroy", hdr, flags=re.S)
+    assert doc, "kh_shard_plan_destroy has no contract comment"
+    text = " ".join(doc.group(1).replace("*", " ").split())
+    for phrase in ("as soon as the last kh_shard_plan_permute / _permute_global call has RETURNED",
+                   "returns to the library's pool only after every permutation queued from the plan has run",
+                   "never permuted", "n == 0", "freed at once"):
+        assert phrase in text, phrase
+    src = tmp_path / "sig.c"
+    src.write_text('#include "kmerhash_amd.h"\n'
+                   'typedef void (*destroy_fn)(kh_shard_plan*);\n'
+                   'int main(void) { destroy_fn f = kh_shard_plan_destroy; return f == 0; }\n')
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-c", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "sig.o")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    # the C++ layer relies on it: find and count destroy their plan with the permutations queued, and add no wait of their own
+    dist = open(os.path.join(ROOT, "kmerhash_amd", "csrc", "kmerhash_amd_dist.cpp")).read()
+    assert re.search(r"~PlanGuard\(\)\s*\{\s*kh_shard_plan_destroy\(\s*h\s*\)\s*;\s*\}", dist)
